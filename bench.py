@@ -15,7 +15,13 @@ A "step" is one vector step over all envs of the rank.  Workloads:
   env   (config 2): random policy (Philox) -> env step kernel, auto-reset.
 --variant simv1 runs either on the simv1 constants / termination mask / stateless reward / pose pool (config 5;
 parity unpinned).  Inputs are synthetic (reference reset distribution, random-init 400x300 networks) and
-resident in HBM before the timed region.  One JSON line on rank 0; see DESIGN.md "Measurement" for the fields."""
+resident in HBM before the timed region.  One JSON line on rank 0; see DESIGN.md "Measurement" for the fields.
+
+--dump-outputs DIR: after the timed region, rank 0 writes what the last timed vector step computed as DIR/<name>.npy
+(float32): obs (the observations after the step), reward, done, and for the ddpg workload the stored action and every
+tensor of the four networks after the step's learn().  Inputs are seeded, and with this option the settle phase runs a
+step count fixed by the arguments instead of by the clock, so two builds run with the same arguments can be compared array
+by array.  When the per-env arrays would take the files past 64 MB, the same seeded sample of envs is kept in each of them."""
 import argparse
 import json
 import os
@@ -34,6 +40,8 @@ HBM_PEAK_GBS = 8000.0  # MI355X HBM3E spec (MI355X_MICROARCH.md)
 PMC_FILES = ("r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_pmc_traffic.json")      # newest first
 # the two gradient all-reduce sites of a data-parallel learn() (DDPG_agent.py:95-104): flat f32 buffers of these sizes
 GRAD_NUMEL = {"critic": 132201, "actor": 131601}
+DUMP_LIMIT_BYTES = 64 * 10 ** 6       # --dump-outputs: all files together
+DUMP_SETTLE_MS_PER_STEP = 0.1         # --dump-outputs: settle steps = settle-ms / this (a step of the default loop is ~0.09 ms)
 
 
 def parse():
@@ -73,7 +81,12 @@ def parse():
     ap.add_argument("--watchdog-seconds", type=float, default=float(os.environ.get("TT_BENCH_WATCHDOG_S", "300")),
                     help="N > 1: a phase of the run (set-up, warm-up, timed region, ...) that has not completed this many "
                     "seconds after it began ends the rank with exit code 3 and a line that names rank and phase")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the outputs of the last timed vector step to DIR/<name>.npy (module docstring)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 # ------------------------------------------------------------------------------------------------ N > 1 watchdog
@@ -332,6 +345,45 @@ def cpu_baseline(seconds):
     return out
 
 
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+def last_step_outputs(env, loop):
+    """Device copies of what the last vector step handed its caller: {name: (tensor, one row per env)}."""
+    if loop is None:        # env workload: the env's own output buffers
+        return {"obs": (env.obs.clone(), True), "reward": (env.reward.clone(), True), "done": (env.done.clone(), True)}
+    ring = loop.ring
+    t = ring.slot(ring.k - 1)       # the last step read obs[t] and wrote act[t], rew[t], done[t] and obs[t + 1]
+    out = {"obs": (ring.obs[ring.slot()].clone(), True), "action": (ring.act[t].clone(), True),
+           "reward": (ring.rew[t].clone(), True), "done": (ring.done[t].clone(), True)}
+    for net in ("actor", "critic", "target_actor", "target_critic"):
+        for name, v in getattr(loop.agent, net).state_dict().items():
+            out[f"{net}.{name}"] = (v.detach().clone(), False)
+    return out
+
+
+def write_outputs(out_dir, outputs, n):
+    """DIR/<name>.npy in float32 (float64 stays float64).  If the files would exceed DUMP_LIMIT_BYTES, every per-env array
+    keeps the same rows: a seeded sample of envs, in env order."""
+    import numpy as np
+    import torch
+    arrays = {}
+    for name, (t, _) in outputs.items():
+        t = t.cpu()
+        arrays[name] = t.numpy() if t.dtype == torch.float64 else t.float().numpy()
+    per_env = [name for name, (_, rows) in outputs.items() if rows]
+    fixed = sum(a.nbytes for name, a in arrays.items() if name not in per_env) + 256 * len(arrays)    # (+ .npy headers)
+    keep = (DUMP_LIMIT_BYTES - fixed) // sum(arrays[name].nbytes // n for name in per_env)
+    if keep < n:
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        for name in per_env:
+            arrays[name] = arrays[name][idx]
+    os.makedirs(out_dir, exist_ok=True)
+    paths = []
+    for name, a in arrays.items():
+        paths.append(os.path.join(out_dir, name + ".npy"))
+        np.save(paths[-1], a)
+    assert sum(os.path.getsize(p) for p in paths) <= DUMP_LIMIT_BYTES
+
+
 # ------------------------------------------------------------------------------------------------ the bench proper
 def main():
     args = parse()
@@ -561,6 +613,8 @@ def main():
         if world > 1:
             dist.all_reduce(per_unit, op=dist.ReduceOp.MIN)
         reps = min(2000, max(1, int(args.settle_ms * 1e-3 / max(float(per_unit.item()), 1e-6))))
+        if args.dump_outputs:       # the timed region starts from the same state in every run with these arguments
+            reps = min(2000, max(1, int(args.settle_ms / (DUMP_SETTLE_MS_PER_STEP * unit))))
         for _ in range(reps):       # a synchronize per unit: hundreds of queued replays leave the runtime resources to reclaim,
             run(unit)               # and it does that in the next synchronize -- the timed region's (0.3 ms; seen with the env workload)
             sync_all()
@@ -606,6 +660,8 @@ def main():
     sync_all()
     elapsed = time.perf_counter() - t0
     event_ms = e0.elapsed_time(e1)
+    # (copied on the device before the repeats below step the loop on)
+    dumped = last_step_outputs(env, ddpg_loop) if args.dump_outputs and rank == 0 else None
     wd.enter("after the timed region (repeats, per-dispatch kernel timing)")
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device=dev)
@@ -706,6 +762,8 @@ def main():
     if rank == 0:
         if cpu is not None:
             out["cpu_baseline"] = cpu
+        if dumped is not None:
+            write_outputs(args.dump_outputs, dumped, n)
         print(json.dumps(out), flush=True)
     wd.enter("shutdown")
     diverged = world > 1 and ddpg_loop is not None and not out["config"]["dp_mode"].get("ranks_hold_the_same_weights", True)

@@ -602,13 +602,15 @@ def test_probe_port_is_agreed_through_the_launcher_store():
     """dp_probe.probe_port(): under torch.distributed.run every rank reads the port rank 0 found free from the agent's store
     (no GPU, no process group needed); the ranks' votes are reduced with MIN by dp_probe.agree()."""
     import subprocess
+    # each rank writes its own file: the two ranks share the launcher's stdout, where their prints can interleave word by word
     code = ("import os, sys; sys.path.insert(0, %r)\n"
             "from ddpg_trucktrailer_amd import dp_probe\n"
             "import torch.distributed as dist\n"
             "p = dp_probe.probe_port()\n"
             "dist.init_process_group('gloo')\n"
             "r = dist.get_rank()\n"
-            "print('port', p, 'agree', dp_probe.agree(r == 0), dp_probe.agree(True), flush=True)\n"
+            "line = ' '.join(map(str, ('port', p, 'agree', dp_probe.agree(r == 0), dp_probe.agree(True))))\n"
+            "open(os.path.join(os.path.dirname(os.path.abspath(__file__)), 'rank%%d.txt' %% r), 'w').write(line + '\\n')\n"
             "dist.destroy_process_group()\n" % ROOT)
     import tempfile
     with tempfile.TemporaryDirectory() as d:
@@ -619,7 +621,7 @@ def test_probe_port_is_agreed_through_the_launcher_store():
         r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
                             "127.0.0.1", "--master-port", str(_free_port()), path], env=env, capture_output=True, text=True,
                            timeout=240)
-    lines = [l.split() for l in r.stdout.splitlines() if l.startswith("port")]
+        lines = [open(os.path.join(d, f)).read().split() for f in sorted(os.listdir(d)) if f.startswith("rank")]
     assert r.returncode == 0 and len(lines) == 2, r.stdout + r.stderr
     assert lines[0][1] == lines[1][1] and int(lines[0][1]) > 0          # one port for both ranks
     assert all(l[3] == "False" and l[4] == "True" for l in lines)       # one "no" vote is "no" everywhere
