@@ -16,6 +16,9 @@ INFO_ROWS = ("total_reward", "progress_reward", "heading_reward", "orientation_r
              "safety_penalty", "exploration_bonus", "final_success_bonus", "backward_penalty", "smoothness_penalty",
              "cumulative_backward", "movement_budget")
 NINFO = len(INFO_ROWS)
+# counters of the episode log (TT_LOG_NCOUNTS, include/ttenv.h: tt_env_set_episode_log), in their order
+LOG_COUNTS = ("episodes", "successes", "jackknife", "out_of_map", "max_steps", "goal_reached", "goal_passed",
+              "excessive_back", "success_flag")
 
 
 class TTParams(C.Structure):
@@ -117,6 +120,11 @@ _SIGNATURES = {
     "tt_env_state_bytes": (C.c_size_t, [_P]),
     "tt_env_export": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 4), _P]),
     "tt_env_import": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 4), _P]),
+    "tt_env_set_episode_log": (C.c_int, [_P, C.c_int64, _P]),
+    "tt_env_drain_episode_log": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tt_env_episode_log_bytes": (C.c_size_t, [_P]),
+    "tt_env_export_episode_log": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 2), _P]),
+    "tt_env_import_episode_log": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 2), _P]),
     "tt_env_rollout_random": (C.c_int, [_P, _I, _U64, _P, _P, _P, _P]),
     "tt_env_profile": (C.c_int, [_P, _I]),
     "tt_env_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -115,6 +115,19 @@ class BestModelTracker:
             self.best_success_rate, self.best_score = success_rate, avg_score
         return is_best, avg_score, success_rate
 
+    def update_many(self, records, first_episode):
+        """update() for every record of a drained episode log (TruckTrailerVecEnv.drain_episodes: ret, success, len), in
+        their order, as episodes first_episode, first_episode + 1, ...  Returns (indices into the records where is_best
+        fired, avg_score and success_rate after the last record; None, None when there are no records)."""
+        to_list = lambda x: x.tolist() if hasattr(x, "tolist") else list(x)
+        rets, succ, lens = to_list(records["ret"]), to_list(records["success"]), to_list(records["len"])
+        best, avg, rate = [], None, None
+        for j, (r, s_, n) in enumerate(zip(rets, succ, lens)):
+            is_best, avg, rate = self.update(first_episode + j, r, bool(s_), n)
+            if is_best:
+                best.append(j)
+        return best, avg, rate
+
     def training_state(self, episode_num):
         """The dict trainv2.py:210-229 pickles (same keys)."""
         return {"episode_num": episode_num, "score_history": list(self.score_history), "best_score": self.best_score,

@@ -651,6 +651,88 @@ __device__ __forceinline__ void write_info(const Info &info, size_t N, int i, co
 __device__ unsigned long long g_stepblk[1024][2];
 __device__ TTLog g_log_step;
 #endif
+// Episode log (tt_env_set_episode_log; DESIGN.md "Episode log"): one device block, laid out as
+//   header  [LOG_HDR] u64: the write index, the launch count, the exit ticket and the outcome counters [TT_LOG_NCOUNTS], each
+//           group on a 128-byte line of its own (atomics on one line are serialised where they are performed)
+//   records ret f64 [cap] | end_step i64 [cap] | len i32 [cap] | lane i32 [cap] | flags u8 [cap] | success u8 [cap] (to 8 B)
+//   accumulator f64 [npad]: the return of the running episode of every lane, summed in step order
+// so that a checkpoint of the log is one copy of the block.  The kernels get the header, the accumulator and the capacity
+// (6 SGPRs, not one pointer per column: the step kernels have none to spare) and find the columns from them.
+enum LogHdr : int { LG_WRITTEN = 0, LG_LAUNCHES = 16, LG_TICKET = 32, LG_COUNTS = 48, LOG_HDR = 64 };
+static_assert(LG_COUNTS + TT_LOG_NCOUNTS <= LOG_HDR, "episode-log header");
+
+struct EpLog {
+    unsigned long long *hdr;
+    double *acc;
+    unsigned long long capacity;
+};
+struct LogCols {
+    double *ret;
+    long long *end_step;
+    int32_t *len, *lane;
+    uint8_t *flags, *success;
+};
+__host__ __device__ inline LogCols log_cols(const EpLog &lg) {
+    const size_t cap = (size_t)lg.capacity;
+    char *p = reinterpret_cast<char *>(lg.hdr + LOG_HDR);
+    LogCols c;
+    c.ret = reinterpret_cast<double *>(p); p += sizeof(double) * cap;
+    c.end_step = reinterpret_cast<long long *>(p); p += sizeof(long long) * cap;
+    c.len = reinterpret_cast<int32_t *>(p); p += sizeof(int32_t) * cap;
+    c.lane = reinterpret_cast<int32_t *>(p); p += sizeof(int32_t) * cap;
+    c.flags = reinterpret_cast<uint8_t *>(p); p += cap;
+    c.success = reinterpret_cast<uint8_t *>(p);
+    return c;
+}
+// bytes of the block before the accumulator
+__host__ __device__ inline size_t log_records_bytes(unsigned long long cap) {
+    return (sizeof(unsigned long long) * LOG_HDR + (2 * sizeof(double) + 2 * sizeof(int32_t) + 2) * (size_t)cap + 7) & ~(size_t)7;
+}
+
+__device__ __forceinline__ unsigned long long atomic_add_agent(unsigned long long *p, unsigned long long v) {
+    return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The finishers of one wave append their records with ONE atomic on the write index (lane 0: the valid lanes of a wave are a
+// prefix, so lane 0 is active whenever any lane is); each finisher's slot is the base plus the number of finishers below it
+// (v_mbcnt).  Slots at or past the capacity are not stored, the index keeps counting.  Outcome counters: one integer atomic per
+// outcome that has a finisher in the wave.  Called by every active lane of the wave (the ballots need them all).
+// The record's end_step is the launch number, read here and at the workgroup's exit: both before the workgroup's exit ticket
+// (below, k_step_log), so before the last workgroup of the launch advances it.
+__device__ __forceinline__ void log_append(const EpLog &lg, int i, bool done, uint32_t flags, bool success, uint32_t len,
+                                           double ret) {
+    const unsigned long long fin = __ballot(done);
+    if (!fin) return;
+    const bool succ = done && success;
+    const bool lead = __lane_id() == 0;
+    unsigned long long base = 0;
+    if (lead) base = atomic_add_agent(lg.hdr + LG_WRITTEN, (unsigned long long)__popcll(fin));
+    // counters one ballot at a time (nine masks held at once cost 18 SGPRs, and the kernel then spilled)
+    if (lead) atomic_add_agent(lg.hdr + LG_COUNTS, (unsigned long long)__popcll(fin));
+    const unsigned long long ns = __ballot(succ);
+    if (lead && ns) atomic_add_agent(lg.hdr + LG_COUNTS + 1, (unsigned long long)__popcll(ns));
+#pragma unroll
+    for (int f = 0; f < TT_LOG_NCOUNTS - 2; ++f) {
+        const unsigned long long m = __ballot(done && ((flags >> f) & 1u));
+        if (lead && m) atomic_add_agent(lg.hdr + LG_COUNTS + 2 + f, (unsigned long long)__popcll(m));
+    }
+    base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+           (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)base);
+    if (done) {
+        const unsigned long long slot =
+            base + __builtin_amdgcn_mbcnt_hi((uint32_t)(fin >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fin, 0u));
+        if (slot < lg.capacity) {
+            const LogCols c = log_cols(lg);
+            c.ret[slot] = ret;
+            c.end_step[slot] = (long long)__hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            c.len[slot] = (int32_t)len;
+            c.lane[slot] = i;
+            c.flags[slot] = (uint8_t)flags;
+            c.success[slot] = succ ? 1 : 0;
+        }
+    }
+}
+
 template <bool PER_ENV, bool INFO, bool AUTO_RESET, bool RANDOM_POLICY>
 __global__ __launch_bounds__(BLOCK) void k_step(const KParams P, const int n, const Bufs b,
                                                 const float *__restrict__ action, float *__restrict__ action_out,
@@ -723,6 +805,82 @@ __global__ __launch_bounds__(BLOCK) void k_step(const KParams P, const int n, co
         tt_log_add(g_log_step, g_stepblk[blockIdx.x][0], g_stepblk[blockIdx.x][1]);
     }
 #endif
+}
+
+
+// k_step with the episode log on: the same step (the same inlined load_env / step_env / place_env / store_env /
+// store_obs_tile), plus the lane's running return -- loaded in the step's load burst, summed in step order --, the append of the
+// finishers' records and the launch count.  A kernel of its own, not a fifth template argument of k_step (that would rename
+// every k_step variant), and not a body shared with k_step either: moving k_step's body into a common inlined function
+// changed the register allocation of 8 of its 16 variants (DESIGN.md "Episode log").
+template <bool PER_ENV, bool INFO, bool AUTO_RESET, bool RANDOM_POLICY>
+__global__ __launch_bounds__(BLOCK) void k_step_log(const KParams P, const int n, const Bufs b,
+                                                    const float *__restrict__ action, float *__restrict__ action_out,
+                                                    float *__restrict__ obs, float *__restrict__ reward,
+                                                    uint8_t *__restrict__ done, const Info info, const uint64_t seed,
+                                                    const uint64_t policy_seed, const int *__restrict__ cursor,
+                                                    const EpLog lg) {
+    __shared__ __attribute__((aligned(16))) float tile[BLOCK * OBS];
+    if (cursor) {
+        obs += (size_t)cursor[1] * n * OBS;
+        reward += (size_t)cursor[0] * n;
+        done += (size_t)cursor[0] * n;
+    }
+    const int block_first = blockIdx.x * BLOCK;
+    const int i = block_first + threadIdx.x;
+    const bool valid = i < n;
+    const int nv = min(BLOCK, n - block_first);
+    float of[OBS];
+
+    if (b.counter && i == 0) *b.counter += 1;
+    if (valid) {
+        Env e;
+        load_env<PER_ENV>(P, b, i, e);
+        float a = 0.f;
+        if (!RANDOM_POLICY) a = action[i];
+        double ret = lg.acc[i];
+        __builtin_amdgcn_sched_barrier(0);     // every load of the step in one burst (k_step)
+        if (RANDOM_POLICY) {
+            a = random_action(policy_seed, (uint32_t)i, pk_steps(e.pk), b.episodes[i]);
+            if (action_out) action_out[i] = a;
+        }
+        StepOut o;
+        step_env(P, e, a, of, o);
+        if (P.nt) {
+            __builtin_nontemporal_store((float)o.total, reward + i);
+            __builtin_nontemporal_store((uint8_t)(o.done ? 1 : 0), done + i);
+        } else {
+            reward[i] = (float)o.total;
+            done[i] = o.done ? 1 : 0;
+        }
+        if (INFO) write_info(info, (size_t)n, i, e, o);
+        ret += o.total;
+        lg.acc[i] = o.done ? 0.0 : ret;        // a finished lane's next episode (auto-reset or not) starts from 0
+        const uint32_t len = pk_steps(e.pk);   // (the record is written after the reset: fewer registers live across it)
+        if (AUTO_RESET && o.done) {
+            const uint32_t ep = b.episodes[i] + 1u;
+            b.episodes[i] = ep;
+            double sx, sy, syaw;
+            random_pose(P, seed, (uint32_t)i, ep, sx, sy, syaw);
+            const Goal g0{P.gx, P.gy, P.sg, P.cg};
+            place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);
+        }
+        store_env(b, i, e);
+        log_append(lg, i, o.done, o.flags, o.final_bonus > 0.0, len, ret);
+    }
+    store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
+    // Launch count: after store_obs_tile's barrier every wave of this workgroup has read the count (its records hold it), so
+    // the workgroup's exit ticket follows its reads, and the workgroup that draws the last ticket follows every workgroup's.
+    // Nothing waits and nothing is published to other workgroups of this launch, so the atomics are relaxed (an acq_rel
+    // ticket wrote back and invalidated the L2 in every workgroup: 10 -> 78 us per launch at N = 65536).
+    if (threadIdx.x == 0) {
+        const unsigned long long launch = __hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long t = atomic_add_agent(lg.hdr + LG_TICKET, 1ull);
+        if (t == gridDim.x - 1u) {    // the last workgroup of the launch; the next launch reads the count
+            __hip_atomic_store(lg.hdr + LG_TICKET, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(lg.hdr + LG_LAUNCHES, launch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
 }
 
 // K vector steps in ONE launch with the random policy: the env stays in registers, only the last
@@ -932,6 +1090,38 @@ __global__ __launch_bounds__(BLOCK) void k_random_actions(const int n, const uin
     out[i] = (float)((2.0 * u01(r[0]) - 1.0) * (kPi / 4));
 }
 
+// the episode log's accumulator of lanes that start a new episode outside the step kernel (tt_env_reset with a mask,
+// tt_env_set_pose): entry j < k names lane idx[j] (idx NULL: lane j) and counts when mask is NULL or mask[lane] != 0
+__global__ __launch_bounds__(BLOCK) void k_log_zero(const int n, const int k, const uint8_t *mask, const int32_t *idx,
+                                                    double *acc) {
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= k) return;
+    const int i = idx ? idx[j] : j;
+    if (i < 0 || i >= n || (mask && !mask[i])) return;
+    acc[i] = 0.0;
+}
+
+__global__ __launch_bounds__(BLOCK) void k_log_drain(const EpLog lg, double *ret, int32_t *len, uint8_t *flags,
+                                                     uint8_t *success, int32_t *lane, long long *end_step,
+                                                     long long *n_out, unsigned long long *counts_out) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    const unsigned long long written = lg.hdr[LG_WRITTEN];
+    if (j < min(written, lg.capacity)) {
+        const LogCols c = log_cols(lg);
+        if (ret) ret[j] = c.ret[j];
+        if (len) len[j] = c.len[j];
+        if (flags) flags[j] = c.flags[j];
+        if (success) success[j] = c.success[j];
+        if (lane) lane[j] = c.lane[j];
+        if (end_step) end_step[j] = c.end_step[j];
+    }
+    if (j == 0) {
+        if (n_out) *n_out = (long long)written;
+        if (counts_out)
+            for (int c = 0; c < TT_LOG_NCOUNTS; ++c) counts_out[c] = lg.hdr[LG_COUNTS + c];
+    }
+}
+
 char g_err[256] = "";
 
 }  // namespace
@@ -951,6 +1141,10 @@ struct tt_env {
     size_t ev_used = 0;
     double prof_ms = 0.0;
     long prof_launches = 0;
+    // episode log (tt_env_set_episode_log): one device block, EpLog's pointers into it; log_bytes == 0 <=> off
+    void *log_block = nullptr;
+    size_t log_bytes = 0;
+    EpLog log{};
     char err[256] = "";
 };
 
@@ -1026,7 +1220,14 @@ void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_
         e->ev_used += 1;
     }
     // hipExtLaunchKernelGGL with null events is a plain launch; with events they time this dispatch alone
-    if (auto_reset)
+    if (e->log_bytes) {
+        if (auto_reset)
+            hipExtLaunchKernelGGL((k_step_log<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
+                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
+        else
+            hipExtLaunchKernelGGL((k_step_log<PER_ENV, INFO, false, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
+                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
+    } else if (auto_reset)
         hipExtLaunchKernelGGL((k_step<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
                               action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor);
     else
@@ -1055,6 +1256,9 @@ int step_common(tt_env *env, const float *action, float *action_out, float *obs,
     if (err != hipSuccess) return fail(env, TT_EHIP, "tt_env_step launch: %s", hipGetErrorString(err));
     return TT_OK;
 }
+
+constexpr long long kLogMaxCapacity = 1ll << 28;
+size_t log_block_bytes(long long cap, int npad) { return log_records_bytes((unsigned long long)cap) + sizeof(double) * (size_t)npad; }
 
 }  // namespace
 
@@ -1163,6 +1367,7 @@ int tt_env_destroy(tt_env *env) {
     if (env->b.hot) (void)hipFree(env->b.hot);
     if (env->b.cold) (void)hipFree(env->b.cold);
     if (env->b.episodes) (void)hipFree(env->b.episodes);
+    if (env->log_block) (void)hipFree(env->log_block);
     for (hipEvent_t ev : env->ev_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : env->ev_stop) (void)hipEventDestroy(ev);
     delete env;
@@ -1178,6 +1383,14 @@ int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out
     hipLaunchKernelGGL(k_reset, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
                        env->seed);
     TT_HIP(env, hipGetLastError());
+    if (env->log_bytes) {       // the reset lanes' episodes start from a zero return
+        if (mask)
+            hipLaunchKernelGGL(k_log_zero, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->n, env->n, mask, nullptr,
+                               env->log.acc);
+        else
+            TT_HIP(env, hipMemsetAsync(env->log.acc, 0, sizeof(double) * (size_t)env->npad, stream));
+        TT_HIP(env, hipGetLastError());
+    }
     return TT_OK;
 }
 
@@ -1200,6 +1413,10 @@ int tt_env_set_pose(tt_env *env, const int32_t *idx, int k, const double *start,
     hipLaunchKernelGGL(k_set_pose, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, idx, k, start, goal,
                        L2, obs_out);
     TT_HIP(env, hipGetLastError());
+    if (env->log_bytes) {
+        hipLaunchKernelGGL(k_log_zero, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, nullptr, idx, env->log.acc);
+        TT_HIP(env, hipGetLastError());
+    }
     return TT_OK;
 }
 
@@ -1363,10 +1580,76 @@ int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stre
     return TT_OK;
 }
 
+int tt_env_set_episode_log(tt_env *env, int64_t capacity, tt_stream_t stream) {
+    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_episode_log: NULL handle");
+    if (capacity < 0 || capacity > kLogMaxCapacity)
+        return fail(env, TT_EINVAL, "tt_env_set_episode_log: capacity %lld outside [0, %lld]", (long long)capacity, kLogMaxCapacity);
+    TT_HIP(env, hipSetDevice(env->device));
+    if (env->log_block) {       // launches in flight may still write the old block
+        TT_HIP(env, hipStreamSynchronize(stream));
+        TT_HIP(env, hipDeviceSynchronize());
+        TT_HIP(env, hipFree(env->log_block));
+        env->log_block = nullptr;
+        env->log_bytes = 0;
+        env->log = EpLog{};
+    }
+    if (capacity == 0) return TT_OK;
+    const size_t cap = (size_t)capacity, bytes = log_block_bytes(capacity, env->npad);
+    void *blk = nullptr;
+    hipError_t err = hipMalloc(&blk, bytes);
+    if (err != hipSuccess)
+        return fail(env, err == hipErrorOutOfMemory ? TT_ENOMEM : TT_EHIP, "tt_env_set_episode_log: %s", hipGetErrorString(err));
+    EpLog lg{};
+    lg.hdr = static_cast<unsigned long long *>(blk);
+    lg.acc = reinterpret_cast<double *>(static_cast<char *>(blk) + log_records_bytes(cap));
+    lg.capacity = (unsigned long long)cap;
+    env->log_block = blk;
+    env->log_bytes = bytes;
+    env->log = lg;
+    TT_HIP(env, hipMemsetAsync(blk, 0, bytes, stream));
+    return TT_OK;
+}
+
+int tt_env_drain_episode_log(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, int32_t *lane,
+                             int64_t *end_step, int64_t *n_out, uint64_t *counts_out, tt_stream_t stream) {
+    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_drain_episode_log: NULL handle");
+    if (!env->log_bytes) return fail(env, TT_EINVAL, "tt_env_drain_episode_log: the episode log is off");
+    TT_HIP(env, hipSetDevice(env->device));
+    hipLaunchKernelGGL(k_log_drain, dim3(grid_for((int)env->log.capacity)), dim3(BLOCK), 0, stream, env->log, ret, len, flags,
+                       success, lane, reinterpret_cast<long long *>(end_step), reinterpret_cast<long long *>(n_out),
+                       reinterpret_cast<unsigned long long *>(counts_out));
+    TT_HIP(env, hipGetLastError());
+    TT_HIP(env, hipMemsetAsync(env->log.hdr + LG_WRITTEN, 0, sizeof(unsigned long long), stream));
+    return TT_OK;
+}
+
+size_t tt_env_episode_log_bytes(const tt_env *env) { return env ? env->log_bytes : 0; }
+
+int tt_env_export_episode_log(tt_env *env, void *blob, uint64_t meta[2], tt_stream_t stream) {
+    if (!env || !blob || !meta) return fail(env, TT_EINVAL, "tt_env_export_episode_log: NULL argument");
+    if (!env->log_bytes) return fail(env, TT_EINVAL, "tt_env_export_episode_log: the episode log is off");
+    TT_HIP(env, hipSetDevice(env->device));
+    TT_HIP(env, hipMemcpyAsync(blob, env->log_block, env->log_bytes, hipMemcpyDeviceToDevice, stream));
+    meta[0] = env->log.capacity; meta[1] = (uint64_t)env->n;
+    return TT_OK;
+}
+
+int tt_env_import_episode_log(tt_env *env, const void *blob, const uint64_t meta[2], tt_stream_t stream) {
+    if (!env || !blob || !meta) return fail(env, TT_EINVAL, "tt_env_import_episode_log: NULL argument");
+    if (!env->log_bytes || meta[0] != env->log.capacity || meta[1] != (uint64_t)env->n)
+        return fail(env, TT_EINVAL, "tt_env_import_episode_log: blob is for capacity %llu and %llu envs, the handle's log has "
+                                    "capacity %llu (0 = off) and %d envs", (unsigned long long)meta[0],
+                    (unsigned long long)meta[1], env->log.capacity, env->n);
+    TT_HIP(env, hipSetDevice(env->device));
+    TT_HIP(env, hipMemcpyAsync(env->log_block, blob, env->log_bytes, hipMemcpyDeviceToDevice, stream));
+    return TT_OK;
+}
+
 int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float *obs_out, float *reward_sum,
                           int32_t *episodes_done, tt_stream_t stream) {
     if (!env) return fail(nullptr, TT_EINVAL, "tt_env_rollout_random: NULL handle");
     if (k_steps < 0) return fail(env, TT_EINVAL, "tt_env_rollout_random: k_steps=%d", k_steps);
+    if (env->log_bytes) return fail(env, TT_EINVAL, "tt_env_rollout_random: the episode log does not follow k_rollout; disable it first");
     if (k_steps == 0) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
     const dim3 g(grid_for(env->n)), b(BLOCK);

@@ -243,14 +243,87 @@ class TruckTrailerVecEnv:
                                                    _ptr(reward_sum), _ptr(episodes_done), self._stream()))
         return obs
 
+    # ------------------------------------------------------------------ episode log
+    @property
+    def episode_log_capacity(self):
+        """Records the episode log holds between drains (0: the log is off)."""
+        return getattr(self, "_log_capacity", 0)
+
+    def enable_episode_log(self, capacity=65536):
+        """Turn on the episode log (include/ttenv.h: tt_env_set_episode_log): from the next step on, every env that
+        finishes an episode appends its f64 return, length, termination flags, success (final_success_bonus > 0, the
+        trainv2.py test), lane and end step, and exact counters by outcome are kept; drain_episodes() collects them.  A
+        fresh log each call.  Captured step graphs are re-captured (graph_epoch)."""
+        capacity = int(capacity)
+        if capacity <= 0:
+            raise ValueError("capacity must be positive (disable_episode_log() turns the log off)")
+        self._check(self.lib.tt_env_set_episode_log(self._h, capacity, self._stream()))
+        self._log_capacity = capacity
+        self.graph_epoch += 1
+        with torch.cuda.device(self.device):
+            z = lambda dt: torch.zeros(capacity, dtype=dt, device=self.device)
+            self._log_out = dict(ret=z(torch.float64), len=z(torch.int32), flags=z(torch.uint8), success=z(torch.uint8),
+                                 lane=z(torch.int32), end_step=z(torch.int64))
+            self._log_n = torch.zeros(1, dtype=torch.int64, device=self.device)
+            self._log_counts = torch.zeros(len(L.LOG_COUNTS), dtype=torch.int64, device=self.device)
+
+    def disable_episode_log(self):
+        """Free the log; the step launches the kernel without it again (graphs are re-captured)."""
+        if self.episode_log_capacity:
+            self._check(self.lib.tt_env_set_episode_log(self._h, 0, self._stream()))
+        self._log_capacity = 0
+        self._log_out = None
+        self.graph_epoch += 1
+
+    def drain_episodes(self):
+        """Records appended since the last drain, sorted by (end_step, lane) -- the order inside a launch depends on its
+        atomics --, as device tensors: ret f64, len i32, flags u8, success bool, lane i32, end_step i64; plus `counts`
+        ({name: int}, cumulative since enable, include/ttenv.h TT_LOG_NCOUNTS order), `written` (records appended since the
+        last drain) and `dropped` (those of them past the capacity, not stored).  end_step counts the logging step launches
+        since enable_episode_log (in a DDPGRollout that enables it at construction: the vector step)."""
+        if not self.episode_log_capacity:
+            raise RuntimeError("the episode log is off (enable_episode_log)")
+        o = self._log_out
+        self._check(self.lib.tt_env_drain_episode_log(self._h, _ptr(o["ret"]), _ptr(o["len"]), _ptr(o["flags"]),
+                                                      _ptr(o["success"]), _ptr(o["lane"]), _ptr(o["end_step"]),
+                                                      _ptr(self._log_n), _ptr(self._log_counts), self._stream()))
+        written = int(self._log_n.item())                 # (synchronises this stream)
+        m = min(written, self.episode_log_capacity)
+        key = o["end_step"][:m] * self.n_envs + o["lane"][:m].long()      # unique: one record per lane per launch
+        order = torch.argsort(key)
+        out = {k: v[:m][order] for k, v in o.items()}
+        out["success"] = out["success"].bool()
+        out["counts"] = dict(zip(L.LOG_COUNTS, (int(x) for x in self._log_counts.tolist())))
+        out["written"], out["dropped"] = written, written - m
+        return out
+
+    def _episode_log_state(self):
+        nbytes = int(self.lib.tt_env_episode_log_bytes(self._h))
+        blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        meta = (C.c_uint64 * 2)()
+        self._check(self.lib.tt_env_export_episode_log(self._h, _ptr(blob), C.byref(meta), self._stream()))
+        return {"blob": blob.cpu(), "meta": [int(x) for x in meta]}
+
+    def _load_episode_log_state(self, sd):
+        cap = int(sd["meta"][0])
+        self.enable_episode_log(cap)
+        blob = sd["blob"].to(self.device)
+        meta = (C.c_uint64 * 2)(*sd["meta"])
+        self._check(self.lib.tt_env_import_episode_log(self._h, _ptr(blob), C.byref(meta), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()      # blob is a temporary
+
     def state_dict(self):
-        """Everything needed to resume this env batch (device blob copied to the host + host-side mode)."""
+        """Everything needed to resume this env batch (device blob copied to the host + host-side mode); with the episode
+        log on, its state as well (running returns, counters, launch count, records not drained yet)."""
         nbytes = int(self.lib.tt_env_state_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 4)()
         self._check(self.lib.tt_env_export(self._h, _ptr(blob), C.byref(meta), self._stream()))
-        return {"blob": blob.cpu(), "meta": [int(x) for x in meta], "variant": self.variant,
-                "pool": None if getattr(self, "_pool", None) is None else self._pool.cpu()}
+        sd = {"blob": blob.cpu(), "meta": [int(x) for x in meta], "variant": self.variant,
+              "pool": None if getattr(self, "_pool", None) is None else self._pool.cpu()}
+        if self.episode_log_capacity:
+            sd["episode_log"] = self._episode_log_state()
+        return sd
 
     def load_state_dict(self, sd):
         blob = sd["blob"].to(self.device)
@@ -260,6 +333,8 @@ class TruckTrailerVecEnv:
         torch.cuda.current_stream(self.device).synchronize()      # blob is a temporary
         if sd.get("pool") is not None:
             self.set_reset_pool(sd["pool"])
+        if sd.get("episode_log") is not None:
+            self._load_episode_log_state(sd["episode_log"])
 
     def profile(self, max_launches):
         """Time the next `max_launches` step-kernel dispatches with per-dispatch HIP events (0 = off)."""

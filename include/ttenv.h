@@ -216,6 +216,36 @@ size_t tt_env_state_bytes(const tt_env *env);
 int tt_env_export(tt_env *env, void *blob, uint64_t meta[4], tt_stream_t stream);
 int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stream_t stream);
 
+/* Episode log (the per-episode record trainv2.py:488-572 keeps: score, length, success; DESIGN.md "Episode log").
+ * Off by default.  tt_env_set_episode_log(env, capacity > 0) allocates and zeroes a device block (the one allocation
+ * after create: call it outside a graph capture) and from then on tt_env_step, tt_env_step_ring and tt_env_step_random
+ * launch the logging form of the step kernel: every lane keeps its running return (the f64 TT_I_TOTAL rewards summed in
+ * step order), and every env that finishes appends one record
+ *     ret f64 (the episode's return)        len i32 (env.episode_steps at the done step)
+ *     flags u8 (TT_F_* bits, unmasked)      success u8 (final_success_bonus > 0: trainv2.py:541)
+ *     lane i32                              end_step i64 (the logging launch it ended in, counted from 0 since enable)
+ * in an order that depends on the atomics of the launch (sort by (end_step, lane) for a deterministic one).  Records past
+ * `capacity` are not stored; the write index keeps counting.  Beside them, exact counters since enable
+ * [TT_LOG_NCOUNTS] u64: episodes, successes, then one per TT_F_* bit (bit 0 first).  A lane starts a new episode with a
+ * zero return when the step auto-resets it, on tt_env_reset (masked or full) and on tt_env_set_pose; tt_env_set_state and
+ * tt_env_set_steps continue the episode.  A lane that is mid-episode when the log is enabled counts its return from
+ * there.  tt_env_rollout_random refuses to run while the log is on.  capacity = 0 frees the log (the step kernel is then
+ * exactly the one without it).  Enabling again starts a fresh log. */
+#define TT_LOG_NCOUNTS 9
+int tt_env_set_episode_log(tt_env *env, int64_t capacity, tt_stream_t stream);
+/* Stream-ordered drain (follows graph replays with no host synchronisation): copies the first min(written, capacity)
+ * records into the caller's [capacity] arrays (any may be NULL), writes `written` (records appended since the last
+ * drain, stored or not) to *n_out (device int64) and the cumulative counters to counts_out [TT_LOG_NCOUNTS] (device u64,
+ * may be NULL), then sets the write index back to 0.  TT_EINVAL when the log is off. */
+int tt_env_drain_episode_log(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, int32_t *lane,
+                             int64_t *end_step, int64_t *n_out, uint64_t *counts_out, tt_stream_t stream);
+/* Checkpoint of the log: one opaque device blob of tt_env_episode_log_bytes(env) bytes (0 when off) holding the running
+ * returns, the counters, the launch count and the records not yet drained; meta[2] = {capacity, n_envs}.  Import needs a
+ * handle whose log is on with the same capacity and n_envs. */
+size_t tt_env_episode_log_bytes(const tt_env *env);
+int tt_env_export_episode_log(tt_env *env, void *blob, uint64_t meta[2], tt_stream_t stream);
+int tt_env_import_episode_log(tt_env *env, const void *blob, const uint64_t meta[2], tt_stream_t stream);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */
