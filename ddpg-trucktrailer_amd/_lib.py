@@ -142,15 +142,6 @@ _SIGNATURES = {
     "tt_mlp_forward_save": (C.c_int, [_I, _I, _P, _P, C.POINTER(TTMlpWeights), _P, C.POINTER(TTMlpSaved), _P, _P]),
     "tt_mlp_forward_multi": (C.c_int, [_I, _I, C.POINTER(TTFwdJob), _P]),
     "tt_mlp_forward_multi_sampled": (C.c_int, [_I, _I, C.POINTER(TTFwdJob), C.POINTER(TTSampleArgs), _P, _P]),
-    "tt_critic_state_forward": (C.c_int, [_I, _P, C.POINTER(TTMlpWeights), _P, _P]),
-    "tt_critic_head_td": (C.c_int, [_I, _P, _P, C.POINTER(TTMlpWeights), _P, _P, C.c_float, _P, _P, _P, _P]),
-    "tt_mlp_backward": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, C.POINTER(TTMlpWeights),
-                                  C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs), C.POINTER(TTMlpWeights), C.POINTER(TTTdInput),
-                                  _P]),
-    "tt_mlp_backward_adam": (C.c_int, [_I, _I, _I, C.c_float, _P, _P, _P, _P, _P, _P, C.POINTER(TTMlpWeights),
-                                       C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs), C.POINTER(TTMlpWeights), _I, _P, _P, _P,
-                                       _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                       C.POINTER(TTTdInput), _P]),
     "tt_mlp_backward_rows_pair": (C.c_int, [_I, C.c_float, _P, C.POINTER(TTMlpWeights), C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs),
                                             C.POINTER(TTTdInput), _P, C.POINTER(TTMlpWeights), C.POINTER(TTMlpSaved),
                                             C.POINTER(TTMlpBwdWs), C.POINTER(TTImageJob), _P]),
@@ -175,7 +166,6 @@ _SIGNATURES = {
                                           C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, _P]),
     "tt_mlp_fc2_image_bytes": (C.c_uint64, []),
     "tt_mlp_fc2_image_pack": (C.c_int, [C.POINTER(TTMlpWeights), _P]),
-    "tt_td_target": (C.c_int, [_I, _P, _P, _P, C.c_float, _P, _P, _P]),
     "tt_random_actions": (C.c_int, [_I, _U64, _U64, _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)

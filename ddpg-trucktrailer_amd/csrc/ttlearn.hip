@@ -5,13 +5,12 @@
 //   k_fwd_multi           learn()'s first phase: up to four forwards in one launch (target actor and the target critic's
 //                         state branch on s', Q(s,a) and mu(s) with what their backward needs: normalised
 //                         pre-activations, 1/sigma, post-ReLU activations); k_fwd_small<CRITIC> is one of them alone
-//   k_bwd_rows<CRITIC>    per-row backward: [critic: q' and the TD target for its rows ->] head -> ReLU -> LayerNorm2 ->
-//                         dH1 = dX2 * W2 (MFMA) -> ReLU -> LayerNorm1
+//   k_bwd_rows_pair       per-row backward of both nets on different workgroups: [critic: q' and the TD target for its
+//                         rows ->] head -> ReLU -> LayerNorm2 -> dH1 = dX2 * W2 (MFMA) -> ReLU -> LayerNorm1
 //   k_bwd_weights         dW2 = dX2^T * H1 and dW1 = dX1^T * S on the MFMA (K = batch), all bias / LayerNorm / head
 //                         gradients as deterministic column sums (no atomics), then (one rank) torch.optim.Adam's
 //                         update + the soft target update on each element just finished
-//   k_adam_soft           Adam + soft update as a launch of its own (data-parallel ranks: after the all-reduce);
-//   k_head_td, k_td_target  the TD target as launches of their own
+//   k_adam_soft           Adam + soft update as a launch of its own (data-parallel ranks: after the all-reduce)
 //
 // Small-batch geometry: a workgroup owns 16 rows; its 8 waves split the output COLUMNS (so a 256-row batch is 16
 // workgroups x 8 waves), and LayerNorm statistics are combined across the waves through LDS.
@@ -621,7 +620,7 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
         if (sv.rstd2 && lane == 0 && row < n) sv.rstd2[row] = rstd;
         if (CRITIC && z_state) {
             // state branch only (networks.py:55-61): z_state [B,300] = bn2(fc2(relu(bn1(fc1(s))))) before the action
-            // enters; the TD prologue of the critic's backward (or k_head_td) finishes q once the action is known, so
+            // enters; the TD prologue of the critic's backward finishes q once the action is known, so
             // this pass can run NEXT TO the actor pass that produces it
 #pragma unroll
             for (int i = 0; i < RV; ++i) {
@@ -785,13 +784,12 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi(const FwdJobs J) {
 }
 
 // ------------------------------------------------------------------------------------------------------
-// per-row backward of one net.  16 rows per workgroup.
-//   mode 0: d_out[b] is given (gradient w.r.t. `out`)
-//   mode 1: d_out[b] = scale * (out[b] - y[b])          critic MSE: d/dq mean((y - q)^2), scale = 2/B
-//   mode 2: d_out[b] = scale * aux[b]                    actor: d/dmu mean(-Q), aux = dQ/da, scale = -1/B
-//   mode 3: unit gradient 1 at the head's PRE-activation of every row (no tanh factor): the per-row gradients of a row are
-//           linear in that number, so the real ones are these times the row's d(loss)/d(pre) -- applied by k_bwd_weights
-// actor (CRITIC = false): `out` is mu = tanh(pre) and the head gradient is d_out * (1 - mu^2).
+// per-row backward of one net.  16 rows per workgroup.  The two forms k_bwd_rows_pair runs:
+//   critic (CRITIC = true):  dpre[b] = scale * (out[b] - y[b]), the MSE d/dq mean((y - q)^2) with scale = 2/B, against the
+//                            TD target y[b] that the prologue (TdIn) computes for the row first; out = q(s, a) of the forward
+//   actor (CRITIC = false):  unit gradient 1 at the head's PRE-activation of every row (no tanh factor): the per-row gradients
+//                            of a row are linear in that number, so the real ones are these times the row's d(loss)/d(pre)
+//                            -- applied by k_bwd_weights.  `scale`, `out` and `td` are not read.
 // Writes dpre [B], dz [B,300] (grad at the ReLU-masked LayerNorm2 output), dx2 [B,300] (grad at fc2's output),
 // dy1 [B,400] (grad at the ReLU-masked LayerNorm1 output), dx1 [B,400] (grad at fc1's output).
 constexpr int NG = 7;                         // 64-column groups covering the 400 columns of dH1 (the last is partial)
@@ -801,9 +799,9 @@ struct BwdOut {
 };
 
 
-// Optional prologue of the critic's backward: the rest of the TARGET critic once the target actor's action is known
-// (networks.py:62-68) and the TD target (DDPG_agent.py:89-93), for the rows this workgroup owns -- what k_head_td does
-// as a launch of its own.  q'[b] = q(relu(z_state[b] + action_value(mu'[b]))), y[b] = r[b] + gamma q'[b] (1 - done[b]).
+// Prologue of the critic's backward: the rest of the TARGET critic once the target actor's action is known
+// (networks.py:62-68) and the TD target (DDPG_agent.py:89-93), for the rows this workgroup owns.
+// q'[b] = q(relu(z_state[b] + action_value(mu'[b]))), y[b] = r[b] + gamma q'[b] (1 - done[b]).
 struct TdIn {
     const float *__restrict__ z_state, *__restrict__ mu_t, *__restrict__ r;
     const uint8_t *__restrict__ done;
@@ -831,9 +829,7 @@ __device__ inline void clock_tick(const TdIn &td) {
 }
 
 template <bool CRITIC>
-__device__ __forceinline__ void bwd_rows_body(const int n, const int mode, const float scale,
-                                              const float *__restrict__ d_out, const float *__restrict__ out,
-                                              const float *__restrict__ y, const float *__restrict__ aux,
+__device__ __forceinline__ void bwd_rows_body(const int n, const float scale, const float *__restrict__ out,
                                               const Weights &W, const Saved &sv, const BwdOut &o, const TdIn &td,
                                               float *__restrict__ dx2_s, float *__restrict__ red, float *__restrict__ rsc_s,
                                               const int row0) {
@@ -848,13 +844,12 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const int mode, const
     // so the compiler must assume a store may alias a later load and would otherwise serialise the two rows' round trips.
     constexpr int RPW = TR / NW;
     float4 w3c[RV], g2c[RV], h2v[RPW][RV], xh[RPW][RV], zt[RPW][RV], wat[RV], bat[RV], w3t[RV];
-    float rs[RPW], gin[RPW], yin[RPW], outv[RPW], mut[RPW], rt[RPW], b3t = 0.f;
+    float rs[RPW], outv[RPW], mut[RPW], rt[RPW], b3t = 0.f;
     bool dt[RPW];
-    const bool with_td = CRITIC && td.z_state;               // (uniform over the launch)
+    const bool with_td = CRITIC;                             // the TD prologue's loads: the critic's rows only
     // Every load below is unconditional, from a clamped row / column (a value that must be zero is zeroed afterwards; most uses
     // are guarded anyway): guarded loads made the compiler emit this phase as a chain of exec-masked blocks, each with its own
     // wait -- five dependent round trips to L2 in front of the first arithmetic (5.0 us for this phase in round 3's stamps).
-    // `with_td` is uniform over the launch: a scalar branch around loads that would dereference null pointers.
 #pragma unroll
     for (int i = 0; i < RV; ++i) {
         const int c = rv_col(lane, i), cc = c < H2 ? c : 0;
@@ -873,9 +868,7 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const int mode, const
     for (int rr = 0; rr < RPW; ++rr) {
         const int row = row0 + wave * RPW + rr, rowc = min(row, n - 1);
         rs[rr] = sv.rstd2[rowc];
-        outv[rr] = (mode != 0 || !CRITIC) ? out[rowc] : 0.f;
-        gin[rr] = mode == 0 ? d_out[rowc] : (mode == 2 ? aux[rowc] : 0.f);
-        yin[rr] = (mode == 1 && !with_td) ? y[rowc] : 0.f;
+        outv[rr] = CRITIC ? out[rowc] : 0.f;
         mut[rr] = 0.f; rt[rr] = 0.f; dt[rr] = false;
         if (with_td) { mut[rr] = td.mu_t[rowc]; rt[rr] = td.r[rowc]; dt[rr] = td.done[rowc] != 0; }
 #pragma unroll
@@ -929,13 +922,8 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const int mode, const
                 if (td.q_out) td.q_out[row] = q;
             }
         }
-        float dpre = 0.f;
-        if (ok) {
-            float g = mode == 0 ? gin[rr] : (mode == 1 ? scale * (outv[rr] - (with_td ? y_td : yin[rr])) : scale * gin[rr]);
-            if (!CRITIC) g *= (1.f - outv[rr] * outv[rr]);
-            if (mode == 3) g = 1.f;       // unit backward: every per-row gradient below is linear in g (see k_bwd_rows_pair)
-            dpre = g;
-        }
+        // (actor: the unit backward -- every per-row gradient below is linear in dpre, see k_bwd_rows_pair)
+        const float dpre = ok ? (CRITIC ? scale * (outv[rr] - y_td) : 1.f) : 0.f;
         float4 dxh[RV];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -1146,23 +1134,13 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const int mode, const
     STAMP(11);
 }
 
-template <bool CRITIC>
-__global__ __launch_bounds__(64 * NW) void k_bwd_rows(const int n, const int mode, const float scale,
-                                                      const float *__restrict__ d_out, const float *__restrict__ out,
-                                                      const float *__restrict__ y, const float *__restrict__ aux,
-                                                      const Weights W, const Saved sv, const BwdOut o, const TdIn td) {
-    __shared__ __attribute__((aligned(16))) float dx2_s[DXS_FLOATS];
-    __shared__ float red[2 * NW * TR];
-    __shared__ float rsc_s[TR];
-    bwd_rows_body<CRITIC>(n, mode, scale, d_out, out, y, aux, W, sv, o, td, dx2_s, red, rsc_s, blockIdx.x * TR);
-}
-
-// The critic's per-row backward (TD prologue, mode 1) and the ACTOR's unit backward (mode 3) in one launch, on different
+// The critic's per-row backward (with the TD prologue) and the ACTOR's unit backward in one launch, on different
 // workgroups.  The actor's per-row gradients are linear in the row's d(loss)/d(pre-tanh) = -(1/B) dQ/da (1 - mu^2), and dQ/da
 // needs the UPDATED critic (DDPG_agent.py:100-103) -- but everything else of the actor's backward (ReLU masks, both
 // LayerNorm backwards, dH1 = dX2 * W2) only needs what the forward saved.  So that part runs HERE, beside the critic's
 // backward, for a unit gradient, and k_bwd_weights multiplies row b by the real number once the critic has been updated and
-// dQ/da is known: the actor's backward is off the chain's critical path.
+// dQ/da is known: the actor's backward is off the chain's critical path.  (So mu_out is not read here: the factor that needs
+// mu is k_bwd_weights' RowScale.)
 // Optional rider: the pack of a vector step's policy image (csrc/ttnet_pack.h) on IMAGE_WGS further workgroups of this launch.
 struct ImageJob {
     ttnet::Weights W;
@@ -1193,11 +1171,9 @@ __global__ __launch_bounds__(64 * NW) void k_bwd_rows_pair(const int n, const fl
     }
     KBEGIN(1);
     if ((int)blockIdx.x < nb) {
-        bwd_rows_body<true>(n, 1, scale_c, nullptr, q_out, nullptr, nullptr, Wc, sv_c, o_c, td, dx2_s, red, rsc_s, blockIdx.x * TR);
+        bwd_rows_body<true>(n, scale_c, q_out, Wc, sv_c, o_c, td, dx2_s, red, rsc_s, blockIdx.x * TR);
     } else {
-        const TdIn none{};
-        bwd_rows_body<false>(n, 3, 1.f, nullptr, mu_out, nullptr, nullptr, Wa, sv_a, o_a, none, dx2_s, red, rsc_s,
-                             ((int)blockIdx.x - nb) * TR);
+        bwd_rows_body<false>(n, 0.f, nullptr, Wa, sv_a, o_a, TdIn{}, dx2_s, red, rsc_s, ((int)blockIdx.x - nb) * TR);
     }
     KEND(1);
 }
@@ -1279,7 +1255,7 @@ __device__ __forceinline__ void adam_finish(const AdamFused &A, const AdamPtrs &
     if (q.tgt) st_out(&q.tgt[i], fmaf(A.tau, p - e.tg, e.tg));
 }
 
-// Optional per-row factor of k_bwd_weights' inputs: row b of dpre / dz / dx2 / dy1 / dx1 (a unit backward, mode 3) counts
+// Optional per-row factor of k_bwd_weights' inputs: row b of dpre / dz / dx2 / dy1 / dx1 (the actor's unit backward of k_bwd_rows_pair) counts
 // f(b) = scale * dq_da[b] * (1 - mu[b]^2) times: the actor's d(loss)/d(pre-tanh) for loss = -mean Q(s, mu(s)).
 struct RowScale {
     const float *__restrict__ dq_da, *__restrict__ mu;
@@ -1950,47 +1926,6 @@ __global__ __launch_bounds__(256) void k_img_pack(const float *__restrict__ w2, 
     img_store(img, nn, k, w2[i], true);
 }
 
-// y = r + gamma * q' * (1 - done) (DDPG_agent.py:89-93) and the learn-step counter
-__global__ void k_td_target(const int n, const float *__restrict__ r, const float *__restrict__ q_next,
-                            const uint8_t *__restrict__ done, const float gamma, float *__restrict__ y,
-                            long long *__restrict__ step_dev) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i == 0 && step_dev) *step_dev += 1;
-    if (i < n) y[i] = done[i] ? r[i] : fmaf(gamma, q_next[i], r[i]);
-}
-
-// the rest of the critic once the action is known (networks.py:62-68) and the TD target (DDPG_agent.py:89-93) in one
-// launch: q'[b] = q(relu(z_state[b] + action_value(a[b]))), y[b] = r[b] + gamma * q'[b] * (1 - done[b]).  16 lanes per row.
-__global__ __launch_bounds__(256) void k_head_td(const int n, const float *__restrict__ z_state,
-                                                 const float *__restrict__ action, const Weights W,
-                                                 const float *__restrict__ r, const uint8_t *__restrict__ done,
-                                                 const float gamma, float *__restrict__ y, float *__restrict__ q_out,
-                                                 long long *__restrict__ step_dev) {
-    const int tid = threadIdx.x, l15 = tid & 15, row = blockIdx.x * 16 + (tid >> 4);
-    if (blockIdx.x == 0 && tid == 0 && step_dev) *step_dev += 1;
-    const bool ok = row < n;
-    const float a = ok ? action[row] : 0.f;
-    float dot = 0.f;
-    if (ok) {
-        float z[19], wa[19], ba[19], w3[19];
-#pragma unroll
-        for (int i = 0; i < 19; ++i) {
-            const int col = l15 + 16 * i;
-            const bool real = col < H2;
-            z[i] = real ? z_state[(size_t)row * H2 + col] : 0.f;
-            wa[i] = real ? W.wa[col] : 0.f; ba[i] = real ? W.ba[col] : 0.f; w3[i] = real ? W.w3[col] : 0.f;
-        }
-#pragma unroll
-        for (int i = 0; i < 19; ++i) dot = fmaf(fmaxf(z[i] + fmaf(a, wa[i], ba[i]), 0.f), w3[i], dot);
-    }
-    dot = row_sum16(dot);
-    if (ok && l15 == 0) {
-        const float q = dot + W.b3[0];
-        if (q_out) q_out[row] = q;
-        y[row] = done[row] ? r[row] : fmaf(gamma, q, r[row]);
-    }
-}
-
 Weights to_weights(const tt_mlp_weights *w) {
     return Weights{w->w1, w->b1, w->g1, w->be1, w->w2, w->b2, w->g2, w->be2, w->w3, w->b3, w->wa, w->ba,
                    reinterpret_cast<const _Float16 *>(w->fc2_img)};
@@ -1999,6 +1934,47 @@ Weights to_weights(const tt_mlp_weights *w) {
 bool ok_shape(const tt_mlp_weights *w, bool critic) {
     return w && w->in_dim == IN && w->fc1_dims == H1 && w->fc2_dims == H2 && w->w1 && w->b1 && w->g1 && w->be1 && w->w2 &&
            w->b2 && w->g2 && w->be2 && w->w3 && w->b3 && (!critic || (w->wa && w->ba));
+}
+
+// The C structs as the kernels take them; false (the caller returns TT_EINVAL) when an array is missing
+bool to_saved(const tt_mlp_saved *s, Saved &sv) {
+    if (!s || !s->xh1 || !s->h1 || !s->xh2 || !s->h2 || !s->rstd1 || !s->rstd2) return false;
+    sv = Saved{s->xh1, s->h1, s->xh2, s->h2, s->rstd1, s->rstd2};
+    return true;
+}
+
+bool to_bwd_out(const tt_mlp_bwd_ws *w, BwdOut &o) {
+    if (!w || !w->dpre || !w->dz || !w->dx2 || !w->dy1 || !w->dx1) return false;
+    o = BwdOut{w->dpre, w->dz, w->dx2, w->dy1, w->dx1};
+    return true;
+}
+
+Grads to_grads(const tt_mlp_weights *g) {
+    return Grads{const_cast<float *>(g->w1), const_cast<float *>(g->b1), const_cast<float *>(g->g1), const_cast<float *>(g->be1),
+                 const_cast<float *>(g->w2), const_cast<float *>(g->b2), const_cast<float *>(g->g2), const_cast<float *>(g->be2),
+                 const_cast<float *>(g->w3), const_cast<float *>(g->b3), const_cast<float *>(g->wa), const_cast<float *>(g->ba)};
+}
+
+// The optimizer step of one network inside a weight-gradient launch (arguments as tt_adam_soft_update; count: 12 tensors for
+// the critic, 10 for the actor); false when an argument is missing
+bool to_adam(bool critic, int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
+             const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+             const tt_fc2_images *images, const float *bias_corr, AdamFused &A) {
+    if (count != (critic ? 12 : 10) || !params || !exp_avg || !exp_avg_sq || !step_dev) return false;
+    A = AdamFused{};
+    for (int i = 0; i < count; ++i) {
+        if (!params[i] || !exp_avg[i] || !exp_avg_sq[i]) return false;
+        A.p[i] = params[i]; A.m[i] = exp_avg[i]; A.v[i] = exp_avg_sq[i]; A.tgt[i] = targets ? targets[i] : nullptr;
+    }
+    A.step_dev = reinterpret_cast<const long long *>(step_dev);
+    A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps; A.weight_decay = weight_decay; A.tau = tau;
+    A.on = 1;
+    A.bias_corr = bias_corr;
+    if (images) {
+        A.img_p = reinterpret_cast<_Float16 *>(images->net);
+        A.img_t = reinterpret_cast<_Float16 *>(images->target);
+    }
+    return true;
 }
 
 }  // namespace
@@ -2010,10 +1986,7 @@ int tt_mlp_forward_save(int n, int critic, const float *obs, const float *action
     if (n < 0 || !obs || !out || !ok_shape(w, critic != 0) || (critic && !action)) return TT_EINVAL;
     if (n == 0) return TT_OK;
     Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    if (saved) {
-        if (!saved->xh1 || !saved->h1 || !saved->xh2 || !saved->h2 || !saved->rstd1 || !saved->rstd2) return TT_EINVAL;
-        sv = Saved{saved->xh1, saved->h1, saved->xh2, saved->h2, saved->rstd1, saved->rstd2};
-    }
+    if (saved && !to_saved(saved, sv)) return TT_EINVAL;
     const dim3 grid((n + TR - 1) / TR), block(64 * NW);
     if (critic)
         hipLaunchKernelGGL(k_fwd_small<true>, grid, block, 0, stream, n, obs, action, w->w1, w->b1, w->g1, w->be1, to_weights(w), out, sv, dq_da,
@@ -2051,11 +2024,7 @@ static int forward_multi_impl(int n, int count, const tt_fwd_job *jobs, const tt
             if (q.obs == sample->s2_out && J.write_s2 < 0) J.write_s2 = i;
         }
         Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (q.saved) {
-            const tt_mlp_saved *p = q.saved;
-            if (!p->xh1 || !p->h1 || !p->xh2 || !p->h2 || !p->rstd1 || !p->rstd2) return TT_EINVAL;
-            sv = Saved{p->xh1, p->h1, p->xh2, p->h2, p->rstd1, p->rstd2};
-        }
+        if (q.saved && !to_saved(q.saved, sv)) return TT_EINVAL;
         J.j[i] = FwdJob{q.obs, q.action, to_weights(q.w), q.out, sv, q.dq_da, critic ? q.z_state : nullptr, critic ? 1 : 0};
     }
     if (sample && (J.write_s < 0 || J.write_s2 < 0)) return TT_EINVAL;      // the later launches need all five batch buffers
@@ -2071,98 +2040,6 @@ int tt_mlp_forward_multi_sampled(int n, int count, const tt_fwd_job *jobs, const
                                  tt_stream_t stream) {
     if (!sample) return TT_EINVAL;
     return forward_multi_impl(n, count, jobs, sample, k_snapshot, stream);
-}
-
-int tt_critic_state_forward(int n, const float *obs, const tt_mlp_weights *w, float *z_state, tt_stream_t stream) {
-    if (n < 0 || !obs || !z_state || !ok_shape(w, true)) return TT_EINVAL;
-    if (n == 0) return TT_OK;
-    const Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-    hipLaunchKernelGGL(k_fwd_small<true>, dim3((n + TR - 1) / TR), dim3(64 * NW), 0, stream, n, obs,
-                       static_cast<const float *>(nullptr), w->w1, w->b1, w->g1, w->be1, to_weights(w), static_cast<float *>(nullptr), sv,
-                       static_cast<float *>(nullptr), z_state);
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
-}
-
-int tt_critic_head_td(int n, const float *z_state, const float *action, const tt_mlp_weights *w, const float *reward,
-                      const uint8_t *done, float gamma, float *y, float *q_out, int64_t *step_dev, tt_stream_t stream) {
-    if (n <= 0 || !z_state || !action || !ok_shape(w, true) || !reward || !done || !y) return TT_EINVAL;
-    hipLaunchKernelGGL(k_head_td, dim3((n + 15) / 16), dim3(256), 0, stream, n, z_state, action, to_weights(w), reward, done,
-                       gamma, y, q_out, reinterpret_cast<long long *>(step_dev));
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
-}
-
-static int backward_impl(int n, int critic, int mode, float scale, const float *obs, const float *action, const float *d_out,
-                         const float *out, const float *y, const float *aux, const tt_mlp_weights *w,
-                         const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, const AdamFused &A,
-                         const tt_td_input *tdi, tt_stream_t stream) {
-    if (n <= 0 || !obs || !out || !ok_shape(w, critic != 0) || !ok_shape(grads, critic != 0) || !saved || !ws ||
-        (critic && !action) || mode < 0 || mode > 2 || (mode == 0 && !d_out) || (mode == 1 && !y && !tdi) || (mode == 2 && !aux))
-        return TT_EINVAL;
-    TdIn td{};
-    if (tdi) {
-        const tt_mlp_weights *tw = tdi->target_critic;
-        if (!critic || mode != 1 || !tdi->z_state || !tdi->mu_target || !ok_shape(tw, true) || !tdi->reward || !tdi->done ||
-            !tdi->y_out)
-            return TT_EINVAL;
-        td = TdIn{tdi->z_state, tdi->mu_target, tdi->reward, tdi->done, tw->wa, tw->ba, tw->w3, tw->b3, tdi->gamma,
-                  tdi->y_out, tdi->q_out, reinterpret_cast<long long *>(tdi->step_dev),
-                  reinterpret_cast<long long *>(tdi->window_dev), nullptr, 0.f, 0.f, 0};
-    }
-    if (!saved->xh1 || !saved->h1 || !saved->xh2 || !saved->h2 || !saved->rstd1 || !saved->rstd2 || !ws->dpre || !ws->dz ||
-        !ws->dx2 || !ws->dy1 || !ws->dx1)
-        return TT_EINVAL;
-    const Saved sv{saved->xh1, saved->h1, saved->xh2, saved->h2, saved->rstd1, saved->rstd2};
-    const BwdOut o{ws->dpre, ws->dz, ws->dx2, ws->dy1, ws->dx1};
-    const dim3 grid((n + TR - 1) / TR), block(256), block_rows(64 * NW);
-    if (critic)
-        hipLaunchKernelGGL(k_bwd_rows<true>, grid, block_rows, 0, stream, n, mode, scale, d_out, out, y, aux,
-                           to_weights(w), sv, o, td);
-    else
-        hipLaunchKernelGGL(k_bwd_rows<false>, grid, block_rows, 0, stream, n, mode, scale, d_out, out, y, aux,
-                           to_weights(w), sv, o, td);
-    if (hipGetLastError() != hipSuccess) return TT_EHIP;
-    const Grads G{const_cast<float *>(grads->w1), const_cast<float *>(grads->b1), const_cast<float *>(grads->g1),
-                  const_cast<float *>(grads->be1), const_cast<float *>(grads->w2), const_cast<float *>(grads->b2),
-                  const_cast<float *>(grads->g2), const_cast<float *>(grads->be2), const_cast<float *>(grads->w3),
-                  const_cast<float *>(grads->b3), const_cast<float *>(grads->wa), const_cast<float *>(grads->ba)};
-    const int sum_blocks = critic ? SUMB_CRITIC : SUMB_ACTOR;
-    const RowScale none{nullptr, nullptr, 1.f};
-    hipLaunchKernelGGL(k_bwd_weights<false>, dim3(NU2 + NU1 + sum_blocks), block, 0, stream, n, critic, obs, action, sv, o, G, A, none);
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
-}
-
-static bool saved_ok(const tt_mlp_saved *s) { return s && s->xh1 && s->h1 && s->xh2 && s->h2 && s->rstd1 && s->rstd2; }
-static bool ws_ok(const tt_mlp_bwd_ws *w) { return w && w->dpre && w->dz && w->dx2 && w->dy1 && w->dx1; }
-static Grads to_grads(const tt_mlp_weights *g) {
-    return Grads{const_cast<float *>(g->w1), const_cast<float *>(g->b1), const_cast<float *>(g->g1), const_cast<float *>(g->be1),
-                 const_cast<float *>(g->w2), const_cast<float *>(g->b2), const_cast<float *>(g->g2), const_cast<float *>(g->be2),
-                 const_cast<float *>(g->w3), const_cast<float *>(g->b3), const_cast<float *>(g->wa), const_cast<float *>(g->ba)};
-}
-
-int tt_mlp_backward(int n, int critic, int mode, float scale, const float *obs, const float *action, const float *d_out,
-                    const float *out, const float *y, const float *aux, const tt_mlp_weights *w,
-                    const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, const tt_td_input *td,
-                    tt_stream_t stream) {
-    AdamFused A{};
-    return backward_impl(n, critic, mode, scale, obs, action, d_out, out, y, aux, w, saved, ws, grads, A, td, stream);
-}
-
-int tt_mlp_backward_adam(int n, int critic, int mode, float scale, const float *obs, const float *action, const float *d_out,
-                         const float *out, const float *y, const float *aux, const tt_mlp_weights *w,
-                         const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, int count,
-                         float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
-                         const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay,
-                         float tau, const tt_td_input *td, tt_stream_t stream) {
-    if (count != (critic ? 12 : 10) || !params || !exp_avg || !exp_avg_sq || !step_dev) return TT_EINVAL;
-    AdamFused A{};
-    for (int i = 0; i < count; ++i) {
-        if (!params[i] || !exp_avg[i] || !exp_avg_sq[i]) return TT_EINVAL;
-        A.p[i] = params[i]; A.m[i] = exp_avg[i]; A.v[i] = exp_avg_sq[i]; A.tgt[i] = targets ? targets[i] : nullptr;
-    }
-    A.step_dev = reinterpret_cast<const long long *>(step_dev);
-    A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps; A.weight_decay = weight_decay; A.tau = tau;
-    A.on = 1;
-    return backward_impl(n, critic, mode, scale, obs, action, d_out, out, y, aux, w, saved, ws, grads, A, td, stream);
 }
 
 int tt_mlp_backward_rows_pair(int n, float scale_critic, const float *q_out, const tt_mlp_weights *critic,
@@ -2182,18 +2059,16 @@ int tt_mlp_backward_rows_pair(int n, float scale_critic, const float *q_out, con
         ij.cur = ttnet::RingCursor{reinterpret_cast<const long long *>(c->k_dev), c->slots, c->cursor};
         ij.on = 1;
     }
-    if (n <= 0 || !q_out || !mu_out || !ok_shape(critic, true) || !ok_shape(actor, false) || !saved_ok(saved_critic) ||
-        !saved_ok(saved_actor) || !ws_ok(ws_critic) || !ws_ok(ws_actor) || !tdi || ws_critic->dx2 == ws_actor->dx2)
+    Saved sc, sa;
+    BwdOut oc, oa;
+    if (n <= 0 || !q_out || !mu_out || !ok_shape(critic, true) || !ok_shape(actor, false) || !to_saved(saved_critic, sc) ||
+        !to_saved(saved_actor, sa) || !to_bwd_out(ws_critic, oc) || !to_bwd_out(ws_actor, oa) || !tdi || oc.dx2 == oa.dx2)
         return TT_EINVAL;
     const tt_mlp_weights *tw = tdi->target_critic;
     if (!tdi->z_state || !tdi->mu_target || !ok_shape(tw, true) || !tdi->reward || !tdi->done || !tdi->y_out) return TT_EINVAL;
     const TdIn td{tdi->z_state, tdi->mu_target, tdi->reward, tdi->done, tw->wa, tw->ba, tw->w3, tw->b3, tdi->gamma,
                   tdi->y_out, tdi->q_out, reinterpret_cast<long long *>(tdi->step_dev),
                   reinterpret_cast<long long *>(tdi->window_dev), tdi->bias_corr_out, tdi->adam_beta1, tdi->adam_beta2, 1};
-    const Saved sc{saved_critic->xh1, saved_critic->h1, saved_critic->xh2, saved_critic->h2, saved_critic->rstd1, saved_critic->rstd2};
-    const Saved sa{saved_actor->xh1, saved_actor->h1, saved_actor->xh2, saved_actor->h2, saved_actor->rstd1, saved_actor->rstd2};
-    const BwdOut oc{ws_critic->dpre, ws_critic->dz, ws_critic->dx2, ws_critic->dy1, ws_critic->dx1};
-    const BwdOut oa{ws_actor->dpre, ws_actor->dz, ws_actor->dx2, ws_actor->dy1, ws_actor->dx1};
     hipLaunchKernelGGL(k_bwd_rows_pair, dim3(2 * ((n + TR - 1) / TR) + 1 + (ij.on ? IMAGE_WGS : 0)), dim3(64 * NW), 0, stream, n,
                        scale_critic, q_out, to_weights(critic), sc, oc, td, mu_out, to_weights(actor), sa, oa, ij);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
@@ -2205,27 +2080,15 @@ int tt_mlp_backward_weights(int n, int critic, const float *obs, const float *ac
                             float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
                             float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
                             tt_stream_t stream) {
-    if (n <= 0 || !obs || (critic && !action) || !saved_ok(saved) || !ws_ok(ws) || !ok_shape(grads, critic != 0) ||
+    Saved sv;
+    BwdOut o;
+    if (n <= 0 || !obs || (critic && !action) || !to_saved(saved, sv) || !to_bwd_out(ws, o) || !ok_shape(grads, critic != 0) ||
         ((row_dq_da == nullptr) != (row_mu == nullptr)))
         return TT_EINVAL;
-    AdamFused A{};
-    if (count) {        // Adam + soft update applied in the same launch (one rank); count = 0: gradients only
-        if (count != (critic ? 12 : 10) || !params || !exp_avg || !exp_avg_sq || !step_dev) return TT_EINVAL;
-        for (int i = 0; i < count; ++i) {
-            if (!params[i] || !exp_avg[i] || !exp_avg_sq[i]) return TT_EINVAL;
-            A.p[i] = params[i]; A.m[i] = exp_avg[i]; A.v[i] = exp_avg_sq[i]; A.tgt[i] = targets ? targets[i] : nullptr;
-        }
-        A.step_dev = reinterpret_cast<const long long *>(step_dev);
-        A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps; A.weight_decay = weight_decay; A.tau = tau;
-        A.on = 1;
-        A.bias_corr = bias_corr;
-        if (images) {
-            A.img_p = reinterpret_cast<_Float16 *>(images->net);
-            A.img_t = reinterpret_cast<_Float16 *>(images->target);
-        }
-    }
-    const Saved sv{saved->xh1, saved->h1, saved->xh2, saved->h2, saved->rstd1, saved->rstd2};
-    const BwdOut o{ws->dpre, ws->dz, ws->dx2, ws->dy1, ws->dx1};
+    AdamFused A{};      // count = 0: gradients only; else Adam + soft update applied in the same launch (one rank)
+    if (count && !to_adam(critic != 0, count, params, exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau,
+                          images, bias_corr, A))
+        return TT_EINVAL;
     const RowScale rs{row_dq_da, row_mu, row_scale};
     const dim3 grid(NU2 + NU1 + (critic ? SUMB_CRITIC : SUMB_ACTOR));
     if (row_dq_da) {
@@ -2243,26 +2106,15 @@ int tt_mlp_actor_tail(int n, const float *obs, const float *mu, const tt_mlp_wei
                       const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                       const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
                       tt_stream_t stream) {
-    if (n <= 0 || n > MAXB || !obs || !mu || !q_out || !dq_da || !ok_shape(critic, true) || !saved_ok(saved) || !ws_ok(ws) ||
-        !ok_shape(grads, false) || count != 10 || !params || !exp_avg || !exp_avg_sq || !step_dev || !tail_words)
+    Saved sv;
+    BwdOut o;
+    AdamFused A;
+    if (n <= 0 || n > MAXB || !obs || !mu || !q_out || !dq_da || !ok_shape(critic, true) || !to_saved(saved, sv) || !to_bwd_out(ws, o) ||
+        !ok_shape(grads, false) || !to_adam(false, count, params, exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps,
+                                            weight_decay, tau, images, bias_corr, A) || !tail_words)
         return TT_EINVAL;
     const int nb = (n + TR - 1) / TR;
     if (nb > 64) return TT_EINVAL;                         // (one wave polls the producers' words)
-    AdamFused A{};
-    for (int i = 0; i < count; ++i) {
-        if (!params[i] || !exp_avg[i] || !exp_avg_sq[i]) return TT_EINVAL;
-        A.p[i] = params[i]; A.m[i] = exp_avg[i]; A.v[i] = exp_avg_sq[i]; A.tgt[i] = targets ? targets[i] : nullptr;
-    }
-    A.step_dev = reinterpret_cast<const long long *>(step_dev);
-    A.lr = lr; A.beta1 = beta1; A.beta2 = beta2; A.eps = eps; A.weight_decay = weight_decay; A.tau = tau;
-    A.on = 1;
-    A.bias_corr = bias_corr;
-    if (images) {
-        A.img_p = reinterpret_cast<_Float16 *>(images->net);
-        A.img_t = reinterpret_cast<_Float16 *>(images->target);
-    }
-    const Saved sv{saved->xh1, saved->h1, saved->xh2, saved->h2, saved->rstd1, saved->rstd2};
-    const BwdOut o{ws->dpre, ws->dz, ws->dx2, ws->dy1, ws->dx1};
     const RowScale rs{dq_da, mu, row_scale};
     // tail_words: [0, 64) the row workgroups' hints, [64, 64 + 2 n) the rows' 8-byte words
     const TailSync ts{tail_words, reinterpret_cast<unsigned long long *>(tail_words + 64), nb, gave_up_host};
@@ -2374,13 +2226,5 @@ int tt_debug_stamps(unsigned long long *out32) {
     return hipMemcpyFromSymbol(out32, HIP_SYMBOL(g_stamps), sizeof(unsigned long long) * 32) == hipSuccess ? 0 : -3;
 }
 #endif
-
-int tt_td_target(int n, const float *reward, const float *q_next, const uint8_t *done, float gamma, float *y,
-                 int64_t *step_dev, tt_stream_t stream) {
-    if (n <= 0 || !reward || !q_next || !done || !y) return TT_EINVAL;
-    hipLaunchKernelGGL(k_td_target, dim3((n + 255) / 256), dim3(256), 0, stream, n, reward, q_next, done, gamma, y,
-                       reinterpret_cast<long long *>(step_dev));
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
-}
 
 }  // extern "C"

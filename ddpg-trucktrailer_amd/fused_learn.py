@@ -201,24 +201,6 @@ class FusedLearner:
                                              C.byref(self.w(net)), _p(out), C.byref(saved) if saved else None,
                                              _p(dq_da), self._stream()))
 
-    def _bwd(self, st, mode, scale, obs, action, out, y=None, aux=None, td=None):
-        self._fresh()
-        L.check(self.lib.tt_mlp_backward(self.B, 1 if st.critic else 0, mode, float(scale), _p(obs), _p(action), None,
-                                         _p(out), _p(y), _p(aux), C.byref(self.w(st.net)), C.byref(st.saved),
-                                         C.byref(self.ws), C.byref(st.gstruct), C.byref(td) if td is not None else None,
-                                         self._stream()))
-
-    def _bwd_adam(self, st, hyp, tau, mode, scale, obs, action, out, y=None, aux=None, td=None):
-        """_bwd + _adam in the backward's own two launches (include/ttenv.h: tt_mlp_backward_adam)."""
-        lr, b1, b2, eps, wd = hyp
-        L.check(self.lib.tt_mlp_backward_adam(self.B, 1 if st.critic else 0, mode, float(scale), _p(obs), _p(action), None,
-                                              _p(out), _p(y), _p(aux), C.byref(self.w(st.net)),
-                                              C.byref(st.saved), C.byref(self.ws), C.byref(st.gstruct), st.count, st.a_p,
-                                              st.a_m, st.a_v, st.a_t, _p(self.step_dev), lr, b1, b2, eps, wd, tau,
-                                              C.byref(td) if td is not None else None, self._stream()))
-        if self.use_images:            # this (older) entry point does not maintain images: make them again before the next use
-            self._img_seen[id(st.net)] = self._img_seen[id(st.target)] = None
-
     def _adam(self, st, hyp, tau):
         lr, b1, b2, eps, wd = hyp
         if self.p2p is not None:       # the mean of the ranks' gradients is formed INSIDE this launch (include/ttenv.h: tt_p2p_*)
@@ -339,8 +321,14 @@ class FusedLearner:
                                                           self._stream()))
         else:
             L.check(self.lib.tt_mlp_forward_multi(B, 4, jobs, self._stream()))
+        self._rows(rewards, done_u8, window_dev, image)
+        self._weights(self.critic, self.hyp_critic, ag.tau, states, actions, self.ws, adam=fuse_adam)
+
+    def _rows(self, rewards, done_u8, window_dev=None, image=None):
+        """learn()'s per-row backward launch (tt_mlp_backward_rows_pair) after the forwards of phase_a."""
+        ag, B = self.agent, self.B
         # critic step (DDPG_agent.py:95-98); its backward launch first finishes q'(s', mu'(s')) and the TD target for its
-        # rows (tt_td_input: what tt_critic_head_td does as a launch of its own)
+        # rows (tt_td_input)
         td = L.TTTdInput(z_state=self.z_t.data_ptr(), mu_target=self.mu_t.data_ptr(),
                          target_critic=C.pointer(self.w(ag.target_critic)), reward=rewards.data_ptr(),
                          done=done_u8.data_ptr(), gamma=float(ag.gamma), y_out=self.y.data_ptr(),
@@ -355,7 +343,6 @@ class FusedLearner:
                                                    C.byref(self.ws_actor),
                                                    C.byref(L.TTImageJob(C.pointer(image[0]), C.pointer(image[1]))) if image is not None else None,
                                                    self._stream()))
-        self._weights(self.critic, self.hyp_critic, ag.tau, states, actions, self.ws, adam=fuse_adam)
 
     def _weights(self, st, hyp, tau, obs, action, ws, adam, row=None):
         """The weight-gradient launch (tt_mlp_backward_weights), with Adam + soft update in it when `adam`."""

@@ -272,7 +272,7 @@ int tt_random_actions(int n, uint64_t seed, uint64_t step, float *out, tt_stream
  * pieces; three f16 MFMAs with f32 accumulation per product block) when split_ws is set: a caller-owned
  * device workspace of tt_mlp_split_ws_bytes() bytes, one per network and per stream that may run it concurrently,
  * into which each call re-packs fc2 before it runs (never stale; the contents are private to the library).
- * split_ws = NULL always selects the exact-f32 kernel.  Structs of gradients (tt_mlp_backward) ignore it. */
+ * split_ws = NULL always selects the exact-f32 kernel.  Structs of gradients (tt_mlp_backward_weights) ignore it. */
 typedef struct tt_mlp_weights {
     const float *w1, *b1, *g1, *be1, *w2, *b2, *g2, *be2, *w3, *b3, *wa, *ba;
     int32_t in_dim, fc1_dims, fc2_dims;
@@ -288,7 +288,7 @@ typedef struct tt_mlp_weights {
                                image of the parity of the step it opens (split_ws: even steps, split_ws_alt: odd steps) and
                                tt_actor_act_ring reads the one of the running step's parity -- so the opening launch of step
                                t+1 may run beside the policy launches of step t */
-    void *fc2_img;          /* learn() kernels (tt_mlp_forward_save / _multi, tt_mlp_backward*): NULL = fc2 products on the exact-f32
+    void *fc2_img;          /* learn() kernels (tt_mlp_forward_save / _multi, tt_mlp_backward_rows_pair): NULL = fc2 products on the exact-f32
                                MFMA straight from w2; else a caller-owned device buffer of tt_mlp_fc2_image_bytes() bytes (zeroed
                                once, then tt_mlp_fc2_image_pack) that holds w2 as pre-split f16 pieces in both orientations, and
                                the products run on the f16 MFMA at f32 accuracy (three per block, as in the split-f16 forward).
@@ -404,9 +404,11 @@ typedef struct tt_mlp_saved {   /* what a forward keeps for its backward */
 int tt_mlp_forward_save(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
                         const tt_mlp_saved *saved, float *dq_da, tt_stream_t stream);
 
-/* Up to four tt_mlp_forward_save / tt_critic_state_forward jobs on n rows each in ONE launch (learn()'s first phase:
- * target actor on s', target critic's state branch on s', Q(s,a), mu(s)).  critic = 0: actor (action, dq_da, z_state
- * ignored); critic = 1 with z_state set: state branch only (action and out may be NULL); saved / dq_da may be NULL. */
+/* Up to four forwards on n rows each in ONE launch (learn()'s first phase: target actor on s', target critic's state branch
+ * on s', Q(s,a), mu(s)).  critic = 0: actor (action, dq_da, z_state ignored); critic = 1 with z_state set: the target
+ * critic's state branch only, z_state [n,300] = bn2(fc2(relu(bn1(fc1(s))))) (networks.py:55-61, before the action enters;
+ * action and out may be NULL) -- the TD prologue of tt_mlp_backward_rows_pair (tt_td_input) finishes it once the target
+ * actor's action is known; otherwise as tt_mlp_forward_save.  saved / dq_da may be NULL. */
 typedef struct tt_fwd_job {
     int32_t critic, reserved_;
     const float *obs, *action;
@@ -426,29 +428,22 @@ int tt_mlp_forward_multi(int n, int count, const tt_fwd_job *jobs, tt_stream_t s
 int tt_mlp_forward_multi_sampled(int n, int count, const tt_fwd_job *jobs, const tt_sample_args *sample, int64_t *k_snapshot,
                                  tt_stream_t stream);
 
-/* The target critic in two pieces, so that its state branch can run NEXT TO the target actor that produces its action:
- * tt_critic_state_forward: z_state [n,300] = bn2(fc2(relu(bn1(fc1(s))))) (networks.py:55-61, before the action enters);
- * tt_critic_head_td: q' = q(relu(z_state + action_value(a))) (networks.py:62-68) and the TD target
- * y = r + gamma * q' * (1 - done) (DDPG_agent.py:89-93) in one launch; also advances *step_dev (may be NULL) like
- * tt_td_target; q_out [n] may be NULL. */
-int tt_critic_state_forward(int n, const float *obs, const tt_mlp_weights *w, float *z_state, tt_stream_t stream);
-int tt_critic_head_td(int n, const float *z_state, const float *action, const tt_mlp_weights *w, const float *reward,
-                      const uint8_t *done, float gamma, float *y, float *q_out, int64_t *step_dev, tt_stream_t stream);
-
-/* Backward of one net on the batch (autograd of networks.py:55-68 / 138-147): workspace ws holds the per-row
- * gradients (dpre [B], dz, dx2 [B,300], dy1, dx1 [B,400]); grads has the layout of tt_mlp_weights and receives
- * d(loss)/d(parameter) for every parameter (overwritten, not accumulated).
- *   mode 0: d_out [B] = d(loss)/d(out) given;
- *   mode 1: d(loss)/d(out) = scale*(out - y)   (critic: loss = mse_loss(y, q), scale = 2/B; DDPG_agent.py:96-97);
- *   mode 2: d(loss)/d(out) = scale*aux         (actor: loss = -mean Q(s, mu(s)), aux = dQ/da from
- *                                               tt_mlp_forward_save on the critic, scale = -1/B; DDPG_agent.py:101-103). */
+/* learn()'s backward and optimizer step (autograd of networks.py:55-68 / 138-147, DDPG_agent.py:95-106), in the sequence
+ *   tt_mlp_forward_multi[_sampled]  target actor and target critic's state branch on s', Q(s,a) and mu(s) with saved activations
+ *   tt_mlp_backward_rows_pair       per-row backward of the critic (with the TD target in its prologue) and the actor
+ *   tt_mlp_backward_weights(critic) the critic's gradients (+ Adam and soft update on one rank)
+ *   tt_mlp_forward_save(critic on (s, mu(s)), dq_da) or, for both this and the next, tt_mlp_actor_tail
+ *   tt_mlp_backward_weights(actor)  the actor's gradients (+ Adam and soft update on one rank)
+ * and, with data-parallel ranks, each network's gradients all-reduced before tt_adam_soft_update[_p2p].
+ * Workspace ws holds a net's per-row gradients (dpre [B], dz, dx2 [B,300], dy1, dx1 [B,400]). */
 typedef struct tt_mlp_bwd_ws {
     float *dpre, *dz, *dx2, *dy1, *dx1;
 } tt_mlp_bwd_ws;
-/* td (optional, critic with mode 1 only; y may then be NULL): the work of tt_critic_head_td done as the prologue of the
- * critic's backward launch instead of a launch of its own -- q' from the target critic's state branch z_state [n,300] and
- * the target actor's action mu_target [n], y_out [n] = r + gamma q' (1 - done) (used as y and written out), q_out [n] or
- * NULL, *step_dev advanced by 1 (may be NULL). */
+/* The TD prologue of tt_mlp_backward_rows_pair (the rest of the target critic and the TD target, for the rows each
+ * workgroup of the critic's backward owns): q' = q(relu(z_state + action_value(mu_target))) (networks.py:62-68) from the
+ * target critic's state branch z_state [n,300] and the target actor's action mu_target [n]; y_out [n] = r + gamma q'
+ * (1 - done) (DDPG_agent.py:89-93), the critic's regression target; q_out [n] (q') or NULL; *step_dev advanced by 1 (may be
+ * NULL). */
 typedef struct tt_td_input {
     const float *z_state, *mu_target;
     const tt_mlp_weights *target_critic;
@@ -459,7 +454,7 @@ typedef struct tt_td_input {
     int64_t *step_dev;
     int64_t *window_dev;   /* optional: a second device counter advanced by 1 -- the sampling-window counter of a pipelined
                               loop (tt_ring_sample's k_dev), moved on by the last learn() of a vector step */
-    /* optional (tt_mlp_backward_rows_pair only): the launch that advances *step_dev also leaves Adam's bias corrections of
+    /* optional: the launch that advances *step_dev also leaves Adam's bias corrections of
      * the NEW step t for the pair (adam_beta1, adam_beta2) in bias_corr_out[0..4] = {t (int32 bits), beta1, beta2,
      * 1 - beta1^t, 1 - beta2^t}, evaluated once in f64 on a workgroup of its own; the optimizer launches given the same
      * buffer (tt_mlp_backward_weights / tt_adam_soft_update: bias_corr) use it when step and betas match and otherwise
@@ -468,33 +463,24 @@ typedef struct tt_td_input {
     float adam_beta1, adam_beta2;
 } tt_td_input;
 #define TT_BIAS_CORR_FLOATS 8
-int tt_mlp_backward(int n, int critic, int mode, float scale, const float *obs, const float *action, const float *d_out,
-                    const float *out, const float *y, const float *aux, const tt_mlp_weights *w,
-                    const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, const tt_td_input *td,
-                    tt_stream_t stream);
 
-/* tt_mlp_backward with the optimizer step of tt_adam_soft_update applied in the weight-gradient launch itself (each
- * gradient element is finished by exactly one workgroup, which then updates that parameter, its Adam moments and its
- * target): one launch less per network.  count = 10 (actor) / 12 (critic) tensors in tt_mlp_weights order; the arrays
- * are HOST arrays of device pointers; grads still receives the gradients.  For the single-rank path: with data-parallel
- * ranks the gradients are all-reduced between tt_mlp_backward and tt_adam_soft_update instead. */
-int tt_mlp_backward_adam(int n, int critic, int mode, float scale, const float *obs, const float *action, const float *d_out,
-                         const float *out, const float *y, const float *aux, const tt_mlp_weights *w,
-                         const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, int count,
-                         float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
-                         const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay,
-                         float tau, const tt_td_input *td, tt_stream_t stream);
-
-/* learn()'s second phase in the form the rollout loop uses.  The actor's per-row backward is linear in the row's
- * d(loss)/d(pre-tanh) = -(1/B) dQ/da (1 - mu^2), and only dQ/da needs the UPDATED critic (DDPG_agent.py:100-103): so
- *   tt_mlp_backward_rows_pair   runs the critic's per-row backward (mode 1, TD target in its prologue: tt_td_input) and, on
- *                               other workgroups of the SAME launch, the actor's per-row backward for a unit gradient
- *                               (ws_actor receives d(.)/d(pre-tanh) = 1 per row; ws_critic != ws_actor);
- *   tt_mlp_backward_weights     is the weight-gradient launch alone (what tt_mlp_backward[_adam] runs second): gradients of
- *                               every parameter from saved + ws, with row b of ws counted row_scale * row_dq_da[b] *
- *                               (1 - row_mu[b]^2) times when row_dq_da / row_mu are given (both or neither), and with
- *                               Adam + soft update in the same launch when count != 0 (arguments as tt_mlp_backward_adam).
- * Sequence of a learn(): tt_mlp_forward_multi, tt_mlp_backward_rows_pair, tt_mlp_backward_weights(critic), tt_mlp_forward_save
+/* The actor's per-row backward is linear in the row's d(loss)/d(pre-tanh) = -(1/B) dQ/da (1 - mu^2), and only dQ/da needs
+ * the UPDATED critic (DDPG_agent.py:100-103): so
+ *   tt_mlp_backward_rows_pair   runs the critic's per-row backward for loss = mse_loss(y, q) (d(loss)/dq = scale_critic *
+ *                               (q - y), scale_critic = 2/B; DDPG_agent.py:96-97; y from the TD prologue td, required;
+ *                               q_out = the critic's forward output) and, on other workgroups of the SAME launch, the
+ *                               actor's per-row backward for a unit gradient (ws_actor receives d(.)/d(pre-tanh) = 1 per
+ *                               row; ws_critic != ws_actor);
+ *   tt_mlp_backward_weights     is the weight-gradient launch: grads (the layout of tt_mlp_weights) receives d(loss)/d(parameter)
+ *                               for every parameter (overwritten, not accumulated) from saved + ws, with row b of ws counted
+ *                               row_scale * row_dq_da[b] * (1 - row_mu[b]^2) times when row_dq_da / row_mu are given (both or
+ *                               neither; n <= 1024).  count = 0: gradients only.  Else count = 10 (actor) / 12 (critic)
+ *                               tensors in tt_mlp_weights order (HOST arrays of device pointers, as tt_adam_soft_update):
+ *                               the optimizer step of tt_adam_soft_update applied in the same launch (each gradient element
+ *                               is finished by exactly one workgroup, which then updates that parameter, its Adam moments and
+ *                               its target); grads still receives the gradients.  For one rank: data-parallel ranks run
+ *                               count = 0, all-reduce the gradients, then tt_adam_soft_update.
+ * Single-rank learn(): tt_mlp_forward_multi, tt_mlp_backward_rows_pair, tt_mlp_backward_weights(critic), tt_mlp_forward_save
  * (critic on (s, mu(s)) with dq_da), tt_mlp_backward_weights(actor, row_dq_da = dq_da, row_mu = mu, row_scale = -1/B). */
 /* image (may be NULL): the pack of a vector step's policy image (tt_mlp_split_pack with a cursor: image of the step's parity,
  * ring cursor, image epoch) carried by THIS launch on workgroups of its own -- the actor's weights are not written before
@@ -579,11 +565,6 @@ int tt_adam_soft_update_p2p(tt_p2p *x, int site, int count, float *const *params
                             float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const int64_t *step_dev,
                             float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                             const tt_fc2_images *images, const float *bias_corr, tt_stream_t stream);
-
-/* target = rewards + gamma * critic_value_ with critic_value_[done] = 0 (DDPG_agent.py:89-93); also advances the
- * learn-step counter *step_dev (may be NULL) that tt_adam_soft_update reads. */
-int tt_td_target(int n, const float *reward, const float *q_next, const uint8_t *done, float gamma, float *y,
-                 int64_t *step_dev, tt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -3,8 +3,8 @@
 * BestModelTracker.update_many feeds drained episode-log records through trainv2.py's "save when best" rule
   (DDPG/trainv2.py:538-572), restated plainly here;
 * the k_step_log variants the loop launches keep k_step's occupancy (four waves per SIMD, no scratch, no spills), and every
-  kernel that existed before the episode log has the register / LDS / scratch row it had then (tests/golden/
-  kernel_resources_main.json: the table of the library before the log was added)."""
+  kernel of the golden table (tests/golden/kernel_resources_main.json: the library's kernels before the log was added, less
+  those retired since) still exists with the register / LDS / scratch row the table gives it."""
 import json
 import os
 
@@ -92,7 +92,7 @@ def test_logging_step_kernels_keep_four_waves_per_simd(ks):
         assert kr.waves_per_simd(v["vgpr"]) >= 4 and v["scratch"] == 0 and v["vgpr_spills"] == 0, (n, v)
 
 
-def test_kernels_that_existed_before_the_log_are_unchanged(ks):
+def test_kernels_of_the_golden_table_are_unchanged(ks):
     before = json.load(open(os.path.join(GOLDEN, "kernel_resources_main.json")))
     assert len(before) >= 40
     changed = {n: (v, ks.get(n)) for n, v in before.items() if ks.get(n) != v}

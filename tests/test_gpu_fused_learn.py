@@ -18,19 +18,48 @@ def _setup(dev, seed=0, B=256):
     return actor, critic, s, a, g
 
 
+def _fwd_job(net, critic, obs, action=None, out=None, saved=None, z_state=None):
+    """One job of tt_mlp_forward_multi (include/ttenv.h: tt_fwd_job)."""
+    import ctypes as C
+    from ddpg_trucktrailer_amd import _lib as L, fused
+    j = L.TTFwdJob()
+    j.critic, j.obs, j.action = critic, obs.data_ptr(), action.data_ptr() if action is not None else None
+    j.w, j.out = C.pointer(fused.weights_of(net)), out.data_ptr() if out is not None else None
+    j.saved = C.pointer(saved) if saved is not None else None
+    j.dq_da, j.z_state = None, z_state.data_ptr() if z_state is not None else None
+    return j
+
+
+def _ws(B, dev):
+    """A per-row gradient workspace: (its tensors -- keep them alive --, the tt_mlp_bwd_ws over them)."""
+    import torch
+    from ddpg_trucktrailer_amd import _lib as L
+    f = dict(dtype=torch.float32, device=dev)
+    t = dict(dpre=torch.empty(B, **f), dz=torch.empty((B, 300), **f), dx2=torch.empty((B, 300), **f),
+             dy1=torch.empty((B, 400), **f), dx1=torch.empty((B, 400), **f))
+    return t, L.TTMlpBwdWs(**{k: v.data_ptr() for k, v in t.items()})
+
+
 @pytest.mark.parametrize("B", [256, 100, 16])
-def test_forward_save_and_backward_match_autograd(gpu_device, B):
+def test_forward_save_and_learn_backward_match_autograd(gpu_device, B):
+    """tt_mlp_forward_save against torch (output, saved activations, dQ/da), then learn()'s backward as the loop launches it --
+    tt_mlp_backward_rows_pair (critic rows with the TD prologue, the actor's unit rows beside them) and tt_mlp_backward_weights
+    without the optimizer step -- against autograd, at full and partial batches.  Critic: loss = mse_loss(y, critic(s, a))
+    with y = r + gamma q'(s', mu'(s')) (1 - done) of a target pair; actor: loss = sum(c * actor(s)) for a random c per row,
+    whose d(loss)/d(pre-tanh) is the row factor c (1 - mu^2) that tt_mlp_backward_weights applies (row_dq_da = c, row_mu = mu,
+    row_scale = 1)."""
     import ctypes as C
     import torch
+    import torch.nn.functional as F
     from ddpg_trucktrailer_amd import _lib as L, fused
     from ddpg_trucktrailer_amd.fused_learn import _NetState, _p
+    from test_gpu_fused_net import _nets
     actor, critic, s, a, g = _setup(gpu_device, seed=B, B=B)
+    actor_t, critic_t = _nets(gpu_device, seed=B + 1000)
     lib = L.load()
     f = dict(dtype=torch.float32, device=gpu_device)
-    ws_t = dict(dpre=torch.empty(B, **f), dz=torch.empty((B, 300), **f), dx2=torch.empty((B, 300), **f),
-                dy1=torch.empty((B, 400), **f), dx1=torch.empty((B, 400), **f))
-    ws = L.TTMlpBwdWs(**{k: v.data_ptr() for k, v in ws_t.items()})
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    states = {}
     for net, act in ((actor, None), (critic, a)):
         st = _NetState(net, None, B, gpu_device)
         out = torch.empty(B, **f)
@@ -44,16 +73,38 @@ def test_forward_save_and_backward_match_autograd(gpu_device, B):
         x1 = net.fc1(s); h1 = torch.relu(net.bn1(x1))
         xh1 = (x1 - x1.mean(1, keepdim=True)) * torch.rsqrt(x1.var(1, unbiased=False, keepdim=True) + 1e-5)
         assert (st.saved_t["xh1"] - xh1).abs().max().item() <= 2e-5 and (st.saved_t["h1"] - h1).abs().max().item() <= 2e-5
-        d_out = torch.randn(B, generator=g, **f)
-        net.zero_grad(set_to_none=True)
-        ref.backward(d_out.view(-1, 1))
         if act is not None:
             assert (dq_da - torch.autograd.grad(net(s, a_req).sum(), a_req)[0].view(-1)).abs().max().item() <= 2e-5
-        L.check(lib.tt_mlp_backward(B, 1 if act is not None else 0, 0, 1.0, _p(s), _p(act), _p(d_out), _p(out), None, None,
-                                    C.byref(fused.weights_of(net)), C.byref(st.saved), C.byref(ws), C.byref(st.gstruct), None, None, stream))
+        states[net] = (st, out)
+    (st_a, mu), (st_c, q) = states[actor], states[critic]
+    # the TD prologue's inputs as learn()'s first launch leaves them: mu' and the target critic's state branch on s'
+    s2 = torch.rand((B, 23), device=gpu_device, generator=g) * 2 - 1
+    r = torch.randn(B, generator=g, **f)
+    done = (torch.rand(B, device=gpu_device, generator=g) < 0.3).to(torch.uint8)
+    mu_t, z, y = torch.empty(B, **f), torch.empty((B, 300), **f), torch.empty(B, **f)
+    jobs = (L.TTFwdJob * 2)(_fwd_job(actor_t, 0, s2, out=mu_t), _fwd_job(critic_t, 1, s2, z_state=z))
+    L.check(lib.tt_mlp_forward_multi(B, 2, jobs, stream))
+    td = L.TTTdInput(z_state=z.data_ptr(), mu_target=mu_t.data_ptr(), target_critic=C.pointer(fused.weights_of(critic_t)),
+                     reward=r.data_ptr(), done=done.data_ptr(), gamma=0.99, y_out=y.data_ptr())
+    c = torch.randn(B, generator=g, **f)
+    (ws_c_t, ws_c), (ws_a_t, ws_a) = _ws(B, gpu_device), _ws(B, gpu_device)
+    L.check(lib.tt_mlp_backward_rows_pair(B, 2.0 / B, _p(q), C.byref(fused.weights_of(critic)), C.byref(st_c.saved), C.byref(ws_c),
+                                          C.byref(td), _p(mu), C.byref(fused.weights_of(actor)), C.byref(st_a.saved), C.byref(ws_a),
+                                          None, stream))
+    for st, ws, act, row in ((st_c, ws_c, a, (None, None)), (st_a, ws_a, None, (c, mu))):
+        L.check(lib.tt_mlp_backward_weights(B, 1 if st.critic else 0, _p(s), _p(act), C.byref(st.saved), C.byref(ws),
+                                            C.byref(st.gstruct), _p(row[0]), _p(row[1]), 1.0, 0, None, None, None, None, None,
+                                            0.0, 0.0, 0.0, 0.0, 0.0, 0.0, None, None, stream))
+    with torch.no_grad():
+        y_torch = r + 0.99 * critic_t(s2, actor_t(s2)).view(-1) * (1 - done.float())
+    for net in (actor, critic):
+        net.zero_grad(set_to_none=True)
+    F.mse_loss(y_torch.view(-1, 1), critic(s, a)).backward()
+    (c.view(-1, 1) * actor(s)).sum().backward()
+    for st in (st_c, st_a):
         for p, gk in zip(st.params, st.grads):
             scale = max(1e-3, p.grad.abs().max().item())
-            assert (gk - p.grad).abs().max().item() <= 3e-5 * scale + 1e-6, (tuple(p.shape), (gk - p.grad).abs().max().item(), scale)
+            assert (gk - p.grad).abs().max().item() <= 3e-5 * scale + 1e-6, (st.critic, tuple(p.shape), (gk - p.grad).abs().max().item(), scale)
 
 
 def _agent(dev, z, capturable=False):
@@ -204,8 +255,9 @@ def test_fused_learn_in_hipgraph(gpu_device):
 
 
 def test_adam_inside_weight_gradient_launch_is_bit_identical(gpu_device):
-    """Single-rank learn() applies Adam + soft update inside k_bwd_weights (tt_mlp_backward_adam); ranks that all-reduce
-    their gradients run tt_mlp_backward, the collective, tt_adam_soft_update.  Same arithmetic: identical bits."""
+    """Single-rank learn() applies Adam + soft update inside k_bwd_weights (tt_mlp_backward_weights with count != 0); ranks
+    that all-reduce their gradients run tt_mlp_backward_weights with count = 0, the collective, tt_adam_soft_update.  Same
+    arithmetic: identical bits."""
     import torch
     from conftest import GOLDEN
     from ddpg_trucktrailer_amd.fused_learn import FusedLearner
@@ -226,13 +278,14 @@ def test_adam_inside_weight_gradient_launch_is_bit_identical(gpu_device):
     assert torch.equal(f1.critic.flat_grad, f2.critic.flat_grad)     # the gradients are still written
 
 
-def test_target_critic_in_two_pieces(gpu_device):
-    """tt_critic_state_forward + tt_critic_head_td (the state branch next to the target actor, then q' and the TD target
-    in one small launch) against the one-piece critic forward + tt_td_target."""
+def test_target_critic_in_forward_multi_and_td_prologue(gpu_device):
+    """learn()'s target critic in two pieces: its state branch as the z_state job of tt_mlp_forward_multi (beside the target
+    actor that produces its action), then q' and the TD target in the prologue of tt_mlp_backward_rows_pair -- against torch,
+    the step counter, and y = r + gamma q' (1 - done) from the launch's own q'."""
     import ctypes as C
     import torch
     from ddpg_trucktrailer_amd import _lib as L, fused
-    from ddpg_trucktrailer_amd.fused_learn import _p
+    from ddpg_trucktrailer_amd.fused_learn import _NetState, _p
     B = 200
     actor, critic, s, a, g = _setup(gpu_device, seed=9, B=B)
     lib = L.load()
@@ -240,20 +293,36 @@ def test_target_critic_in_two_pieces(gpu_device):
     stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
     r = torch.randn(B, generator=g, **f)
     done = (torch.rand(B, device=gpu_device, generator=g) < 0.3).to(torch.uint8)
-    z, y, q, y_ref, q_ref = torch.empty((B, 300), **f), torch.empty(B, **f), torch.empty(B, **f), torch.empty(B, **f), torch.empty(B, **f)
-    w = fused.weights_of(critic)
-    L.check(lib.tt_critic_state_forward(B, _p(s), C.byref(w), _p(z), stream))
+    s2 = torch.rand((B, 23), device=gpu_device, generator=g) * 2 - 1
+    st_c, st_a = _NetState(critic, None, B, gpu_device), _NetState(actor, None, B, gpu_device)
+    z, mu_t, q, mu, y, qt = torch.empty((B, 300), **f), *(torch.empty(B, **f) for _ in range(5))
+    # the launch as learn() makes it: target actor and the target critic's state branch on s', Q(s, a) and mu(s) for the backward
+    jobs = (L.TTFwdJob * 4)(_fwd_job(actor, 0, s2, out=mu_t), _fwd_job(critic, 1, s2, z_state=z),
+                            _fwd_job(critic, 1, s, a, out=q, saved=st_c.saved), _fwd_job(actor, 0, s, out=mu, saved=st_a.saved))
+    L.check(lib.tt_mlp_forward_multi(B, 4, jobs, stream))
     step = torch.zeros((), dtype=torch.int64, device=gpu_device)
-    L.check(lib.tt_critic_head_td(B, _p(z), _p(a), C.byref(w), _p(r), _p(done), 0.99, _p(y), _p(q), _p(step), stream))
-    L.check(lib.tt_mlp_forward_save(B, 1, _p(s), _p(a), C.byref(w), _p(q_ref), None, None, stream))
-    L.check(lib.tt_td_target(B, _p(r), _p(q_ref), _p(done), 0.99, _p(y_ref), None, stream))
+    td = L.TTTdInput(z_state=z.data_ptr(), mu_target=mu_t.data_ptr(), target_critic=C.pointer(fused.weights_of(critic)),
+                     reward=r.data_ptr(), done=done.data_ptr(), gamma=0.99, y_out=y.data_ptr(), q_out=qt.data_ptr(),
+                     step_dev=step.data_ptr())
+    (ws_c_t, ws_c), (ws_a_t, ws_a) = _ws(B, gpu_device), _ws(B, gpu_device)
+    L.check(lib.tt_mlp_backward_rows_pair(B, 2.0 / B, _p(q), C.byref(fused.weights_of(critic)), C.byref(st_c.saved), C.byref(ws_c),
+                                          C.byref(td), _p(mu), C.byref(fused.weights_of(actor)), C.byref(st_a.saved), C.byref(ws_a),
+                                          None, stream))
+    torch.cuda.synchronize()
     with torch.no_grad():
-        z_ref = critic.bn2(critic.fc2(torch.relu(critic.bn1(critic.fc1(s)))))
-        q_t = critic(s, a).view(-1)
+        z_ref = critic.bn2(critic.fc2(torch.relu(critic.bn1(critic.fc1(s2)))))
+        mu_ref = actor(s2).view(-1)
+        q_ref = critic(s2, mu_t.view(-1, 1)).view(-1)        # q'(s', mu') at the target actor's action of this launch
     assert (z - z_ref).abs().max().item() <= 2e-5
-    assert (q - q_ref).abs().max().item() <= 1e-5 and (q - q_t).abs().max().item() <= 2e-5 * max(1.0, q_t.abs().max().item())
-    assert (y - y_ref).abs().max().item() <= 1e-5 and int(step.item()) == 1
+    assert (mu_t - mu_ref).abs().max().item() <= 2e-5 * max(1.0, mu_ref.abs().max().item())
+    assert (qt - q_ref).abs().max().item() <= 2e-5 * max(1.0, q_ref.abs().max().item())
+    assert int(step.item()) == 1
     assert torch.equal(y[done.bool()], r[done.bool()])               # critic_value_[done] = 0 (DDPG_agent.py:89)
+    # y = fmaf(gamma, q', r): one rounding of the exact value, which f64 holds to 2^-53 (the f32 product exactly)
+    gamma = torch.tensor(0.99, dtype=torch.float32).item()
+    y_ref = (r.double() + gamma * qt.double() * (1 - done.double())).float()
+    ulp = torch.nextafter(y_ref.abs(), torch.full_like(y_ref, float("inf"))) - y_ref.abs()
+    assert ((y - y_ref).abs() <= ulp).all(), (y - y_ref).abs().max().item()
 
 
 def test_fc2_images_follow_the_weights(gpu_device):

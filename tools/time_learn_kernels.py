@@ -4,7 +4,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(
 import torch
 from ddpg_trucktrailer_amd import _lib as L, fused
 from ddpg_trucktrailer_amd.agent import Agent
-from ddpg_trucktrailer_amd.fused_learn import FusedLearner, _p
+from ddpg_trucktrailer_amd.fused_learn import FusedLearner
 dev = torch.device("cuda:0")
 B = 256
 ag = Agent(1e-4, 1e-3, (23,), 1e-3, 1, batch_size=B, device=dev, replay=False)
@@ -20,7 +20,9 @@ def timeit(fn, name, reps=200):
     print(f"{name:28s} {e0.elapsed_time(e1)/reps*1e3:8.1f} us")
 timeit(lambda: fl._fwd(ag.actor, s, None, fl.mu), "fwd actor (no save)")
 timeit(lambda: fl._fwd(ag.critic, s, a, fl.q, fl.critic.saved), "fwd critic (save)")
-timeit(lambda: fl._bwd(fl.critic, 1, 2.0 / B, s, a, fl.q, y=fl.y), "bwd critic (rows+weights)")
+fl.phase_a(s, a, r, s, d8, fuse_adam=False)          # the forwards the backward reads
+timeit(lambda: (fl._rows(r, d8), fl._weights(fl.critic, fl.hyp_critic, 1e-3, s, a, fl.ws, adam=False)),
+       "rows pair + critic weights")
 timeit(lambda: fl._adam(fl.critic, fl.hyp_critic, 1e-3), "adam+soft critic")
 timeit(lambda: fl.learn_batch(s, a, r, s, d8), "learn_batch (eager)", 100)
 big = torch.rand((65536, 23), device=dev); out = torch.empty(65536, device=dev)
