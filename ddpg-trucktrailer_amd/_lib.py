@@ -92,6 +92,21 @@ class TTMlpBwdWs(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("dpre", "dz", "dx2", "dy1", "dx1")]
 
 
+class TTPopNet(C.Structure):
+    _fields_ = [("ws", C.POINTER(TTMlpBwdWs)), ("grads", C.POINTER(TTMlpWeights)), ("count", C.c_int32), ("reserved_", C.c_int32),
+                ("params", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("targets", C.c_void_p)] + \
+               [(n, C.c_float) for n in ("lr", "beta1", "beta2", "eps", "weight_decay", "tau")] + [("images", C.POINTER(TTFc2Images))]
+
+
+class TTPopAgent(C.Structure):
+    _fields_ = [("sample", C.POINTER(TTSampleArgs)), ("jobs", C.POINTER(TTFwdJob)), ("td", C.POINTER(TTTdInput)),
+                ("critic", TTPopNet), ("actor", TTPopNet), ("q_pi", C.c_void_p), ("dq_da", C.c_void_p), ("tail_words", C.c_void_p),
+                ("gave_up_host", C.c_void_p)]
+
+
+POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
+
+
 class TTError(RuntimeError):
     pass
 
@@ -167,6 +182,9 @@ _SIGNATURES = {
     "tt_mlp_fc2_image_bytes": (C.c_uint64, []),
     "tt_mlp_fc2_image_pack": (C.c_int, [C.POINTER(TTMlpWeights), _P]),
     "tt_random_actions": (C.c_int, [_I, _U64, _U64, _P, _P]),
+    "tt_pop_learn_create": (C.c_int, [_I, _I, C.POINTER(TTPopAgent), C.POINTER(_P)]),
+    "tt_pop_learn": (C.c_int, [_P, _I, _P]),
+    "tt_pop_learn_destroy": (C.c_int, [_P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1706,3 +1706,8 @@ int tt_random_actions(int n, uint64_t seed, uint64_t step, float *out, tt_stream
 }
 
 }  // extern "C"
+
+// the library's message for a NULL handle (tt_last_error(NULL)), set by the entry points of the other sources (csrc/ttpop.hip)
+namespace tthost {
+int fail_library(int code, const char *msg) { return fail(nullptr, code, "%s", msg); }
+}  // namespace tthost

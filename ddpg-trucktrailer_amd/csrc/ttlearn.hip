@@ -12,6 +12,9 @@
 //                         update + the soft target update on each element just finished
 //   k_adam_soft           Adam + soft update as a launch of its own (data-parallel ranks: after the all-reduce)
 //
+// TT_LEARN_BODIES_ONLY (csrc/ttpop.hip includes this file with it): only the device bodies, structs and host conversions, no
+// kernel and no entry point -- the population's launches call the same bodies, and the kernels here compile as they always did.
+//
 // Small-batch geometry: a workgroup owns 16 rows; its 8 waves split the output COLUMNS (so a 256-row batch is 16
 // workgroups x 8 waves), and LayerNorm statistics are combined across the waves through LDS.
 #include <hip/hip_runtime.h>
@@ -677,6 +680,7 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
     STAMP(4);
 }
 
+#ifndef TT_LEARN_BODIES_ONLY
 template <bool CRITIC>
 __global__ __launch_bounds__(64 * NW) void k_fwd_small(const int n, const float *__restrict__ obs,
                                                    const float *__restrict__ action, const float *__restrict__ w1e,
@@ -697,6 +701,7 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_small(const int n, const float 
                                            0.f, nullptr, 0u, &E, hook);
     KEND(3);
 }
+#endif  // TT_LEARN_BODIES_ONLY
 
 // Up to four independent forwards on the same number of rows in ONE launch (workgroup b serves job b / blocks_per_job):
 // learn()'s first phase -- target actor on s', the target critic's state branch on s', Q(s,a) and mu(s) -- needs no
@@ -721,6 +726,7 @@ struct FwdJobs {
     ttnet::RingSample R;
     long long *k_snapshot;       // (sampled) *R.k_dev as this launch saw it, for a later launch (tt_image_job) or nullptr
 };
+#ifndef TT_LEARN_BODIES_ONLY
 __global__ __launch_bounds__(64 * NW) void k_fwd_multi(const FwdJobs J) {
     __shared__ __attribute__((aligned(16))) float h1_s[H1S_FLOATS];
     __shared__ __attribute__((aligned(16))) float z_s[TR * DS];
@@ -782,6 +788,7 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi(const FwdJobs J) {
         fwd_small_body<false>(J.n, q.obs, q.action, q.W, q.out, q.sv, nullptr, nullptr, h1_s, z_s, w1_s, row0, orow);
     KEND(0);
 }
+#endif  // TT_LEARN_BODIES_ONLY
 
 // ------------------------------------------------------------------------------------------------------
 // per-row backward of one net.  16 rows per workgroup.  The two forms k_bwd_rows_pair runs:
@@ -1150,6 +1157,7 @@ struct ImageJob {
 };
 constexpr int IMAGE_WGS = (ttnet::PACK_THREADS + 64 * NW - 1) / (64 * NW);
 
+#ifndef TT_LEARN_BODIES_ONLY
 __global__ __launch_bounds__(64 * NW) void k_bwd_rows_pair(const int n, const float scale_c, const float *__restrict__ q_out,
                                                            const Weights Wc, const Saved sv_c, const BwdOut o_c, const TdIn td,
                                                            const float *__restrict__ mu_out, const Weights Wa, const Saved sv_a,
@@ -1177,6 +1185,7 @@ __global__ __launch_bounds__(64 * NW) void k_bwd_rows_pair(const int n, const fl
     }
     KEND(1);
 }
+#endif  // TT_LEARN_BODIES_ONLY
 
 // ------------------------------------------------------------------------------------------------------
 // weight gradients.  Workgroup roles by blockIdx; K = batch in permuted k16 steps, SPLIT over the 4 waves of the
@@ -1710,6 +1719,7 @@ __device__ __forceinline__ void bwd_weights_body(const int blk, const int n, con
 }
 
 // (three workgroups per CU: beside the policy's grid ~85 CUs are free for the ~205 of this launch -- 168 registers, see above)
+#ifndef TT_LEARN_BODIES_ONLY
 template <bool ROWSCALE>
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_bwd_weights(const int n, const int critic, const float *__restrict__ obs,
                                                      const float *__restrict__ action, const Saved sv,
@@ -1721,6 +1731,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
     bwd_weights_body<ROWSCALE, false>(blockIdx.x, n, critic, obs, action, sv, d, G, A, RS, part, f_s, TailSync{nullptr, nullptr, 0, nullptr}, 0,
                                       stage_s);
 }
+#endif  // TT_LEARN_BODIES_ONLY
 
 // learn()'s last two launches in ONE grid (the single-rank chain where the policy launch is small or learn() repeats per step):
 // workgroups [0, nb) are k_fwd_small<critic> on (s, mu(s)) -- Q(s, mu(s)) and dQ/da through the UPDATED critic (DDPG_agent.py:100-103)
@@ -1729,6 +1740,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k
 // the kernel entry and the operand round trip of the weight-gradient launch leave learn()'s chain.  The row workgroups are
 // dispatched first, so they never wait for a CU behind the workgroups that wait for them.  512 threads per workgroup (the row
 // kernel's geometry); a weight-gradient workgroup uses the first 256.  LDS: the row kernel's tiles and the weight kernel's share it.
+#ifndef TT_LEARN_BODIES_ONLY
 __global__ __launch_bounds__(64 * NW) void k_actor_tail(const int n, const float *__restrict__ obs, const float *__restrict__ mu,
                                                         const Weights Wc, float *__restrict__ q_out, float *__restrict__ dq_da,
                                                         const Saved sv, const BwdOut d, const Grads G, const AdamFused A,
@@ -1754,6 +1766,7 @@ __global__ __launch_bounds__(64 * NW) void k_actor_tail(const int n, const float
     bwd_weights_body<true, true>((int)blockIdx.x - nb, n, 0, obs, nullptr, sv, d, G, A, RS, part, lds + 4 * 4 * 256, ts, epoch,
                                  reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB));
 }
+#endif  // TT_LEARN_BODIES_ONLY
 
 // ------------------------------------------------------------------------------------------------------
 // torch.optim.Adam (amsgrad off, weight decay added to the gradient: networks.py:49-50,133) for every parameter
@@ -1768,6 +1781,7 @@ struct AdamTable {
     _Float16 *img_p, *img_t;      // fc2 images kept current for tensor 4 (w2 [300,400]) and its target (or nullptr)
 };
 
+#ifndef TT_LEARN_BODIES_ONLY
 __global__ __launch_bounds__(256) void k_adam_soft(const AdamTable T, const long long *__restrict__ step_dev,
                                                    const float lr, const float beta1, const float beta2,
                                                    const float eps, const float weight_decay, const float tau,
@@ -1925,6 +1939,7 @@ __global__ __launch_bounds__(256) void k_img_pack(const float *__restrict__ w2, 
     const int nn = i / H1, k = i - nn * H1;
     img_store(img, nn, k, w2[i], true);
 }
+#endif  // TT_LEARN_BODIES_ONLY
 
 Weights to_weights(const tt_mlp_weights *w) {
     return Weights{w->w1, w->b1, w->g1, w->be1, w->w2, w->b2, w->g2, w->be2, w->w3, w->b3, w->wa, w->ba,
@@ -1979,6 +1994,7 @@ bool to_adam(bool critic, int count, float *const *params, float *const *exp_avg
 
 }  // namespace
 
+#ifndef TT_LEARN_BODIES_ONLY
 extern "C" {
 
 int tt_mlp_forward_save(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
@@ -2228,3 +2244,4 @@ int tt_debug_stamps(unsigned long long *out32) {
 #endif
 
 }  // extern "C"
+#endif  // TT_LEARN_BODIES_ONLY

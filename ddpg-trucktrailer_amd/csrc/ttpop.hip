@@ -1,0 +1,289 @@
+// ttpop.hip -- learn() of a POPULATION of K independent DDPG agents in the four launches of one agent's learn() (MI355X, gfx950).
+//
+// Agent a of a population is a lone serial-order loop of its own (its env, replay ring, OU noise, policy launch and env step); only
+// its learn() launches are shared: each launch below runs the workgroups of all K agents, and a workgroup finds its agent and its
+// block within the agent's grid from blockIdx.x.  The bodies are ttlearn.hip's, called with the arguments the lone launches pass:
+//
+//   k_pop_fwd_multi            k_fwd_multi, sampled: agent a's draw from agent a's ring (seed + u * seed_stride), its four forwards
+//   k_pop_bwd_rows_pair        k_bwd_rows_pair: TD prologue, critic rows, actor unit rows, the counter workgroup
+//   k_pop_bwd_weights<false>   k_bwd_weights<false> on the critic: gradients + Adam + soft update + fc2 image patch
+//   k_pop_actor_tail           k_actor_tail: Q(s, mu(s)) and dQ/da rows, then the actor's weight gradients + Adam
+//
+// So each agent's results are the bits of its lone learn() (tests/test_gpu_population.py).  Per-agent arguments live in device
+// memory (PopAgent), filled once at tt_pop_learn_create: a launch takes (K, B, descriptors, u) and is graph-capturable.
+// The descriptors are read through the CONSTANT address space, as kernel arguments are: the bodies index the Adam tables with a
+// run-time tensor number (an array copied into registers would go to scratch), and constant loads are scalar loads that the
+// compiler may issue as early as it likes (nothing in a launch writes them).
+#define TT_LEARN_BODIES_ONLY
+#include "ttlearn.hip"
+
+#include <cstdio>
+#include <vector>
+
+namespace tthost {
+int fail_library(int code, const char *msg);      // csrc/ttenv.hip: the message of tt_last_error(NULL)
+}
+
+namespace {
+
+struct PopAgent {
+    // k_pop_fwd_multi: the lone sampled launch's argument (R.seed: the key of update 0; update u adds u * R.seed_stride)
+    FwdJobs F;
+    // k_pop_bwd_rows_pair
+    float scale_c;                       // 2 / B
+    const float *q_out, *mu_out;         // Q(s, a), mu(s) of the forwards
+    Weights Wc, Wa;                      // critic, actor
+    Saved sv_c, sv_a;
+    BwdOut o_c, o_a;
+    TdIn td;
+    // k_pop_bwd_weights (critic) and the weight workgroups of k_pop_actor_tail (actor)
+    const float *s, *a;                  // the draw's batch buffers
+    Grads Gc, Ga;
+    AdamFused Ac, Aa;
+    RowScale RSa;                        // {dq_da, mu, -1 / B}
+    float *q_pi, *dq_da;
+    TailSync ts;                         // this agent's own tail words; its epoch is its own step count
+};
+
+constexpr int WG_CRITIC_WEIGHTS = NU2 + NU1 + SUMB_CRITIC;    // 210
+constexpr int WG_ACTOR_WEIGHTS = NU2 + NU1 + SUMB_ACTOR;      // 200
+
+// agent a's descriptor, as a reference into the constant address space (see the head of the file)
+__device__ __forceinline__ const PopAgent &agent_of(const PopAgent *D, const int a) {
+    return *(const PopAgent *)((const __attribute__((address_space(4))) PopAgent *)D + a);
+}
+
+// grid: K x 4 x nb, agent-major; within an agent, job-major as k_fwd_multi
+__global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi(const int K, const int n, const PopAgent *__restrict__ D, const int u) {
+    __shared__ __attribute__((aligned(16))) float h1_s[H1S_FLOATS];
+    __shared__ __attribute__((aligned(16))) float z_s[TR * DS];
+    __shared__ __attribute__((aligned(16))) float w1_s[H1 * IN];
+    const int nb = (n + TR - 1) / TR, ag = (int)blockIdx.x / (4 * nb);
+    if (ag >= K) return;
+    const int lb = (int)blockIdx.x - ag * 4 * nb, job = lb / nb, row0 = (lb - job * nb) * TR;
+    const PopAgent &P = agent_of(D, ag);
+    const FwdJob &q = P.F.j[job];
+    ttnet::RingSample R = P.F.R;
+    R.seed += (unsigned long long)u * R.seed_stride;        // DDPGRollout._sample_key(u)
+    static_assert(TR / NW == 2, "two rows per wave");
+    const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
+    const bool from_s = q.obs == R.s_out;
+    const float *orow;
+    {
+        const ttnet::RingPick p = ttnet::ring_sample_index(R, min(row0 + l15, n - 1));
+        orow = from_s ? ttnet::ring_pick_s(R, p) : ttnet::ring_pick_s2(R, p);
+    }
+    bool have_act = false;
+    float act_r0 = 0.f, act_r1 = 0.f;
+    if (q.critic && q.action) {
+        act_r0 = ttnet::ring_pick_a(R, ttnet::ring_sample_index(R, min(row0 + wave * 2, n - 1)));
+        act_r1 = ttnet::ring_pick_a(R, ttnet::ring_sample_index(R, min(row0 + wave * 2 + 1, n - 1)));
+        have_act = true;
+    }
+    if (job == P.F.write_s || job == P.F.write_s2) {        // the batch rows of this workgroup for the later launches
+        const int lr = tid / ttnet::IN, c = tid - lr * ttnet::IN, b = row0 + lr;
+        if (lr < TR && b < n) {
+            const ttnet::RingPick p = ttnet::ring_sample_index(R, b);
+            if (job == P.F.write_s) {
+                R.s_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s(R, p)[c];
+                if (c == 0) {
+                    R.a_out[b] = ttnet::ring_pick_a(R, p);
+                    if (R.idx_out) { R.idx_out[2 * b] = p.side ? -1 : p.t; R.idx_out[2 * b + 1] = p.side ? p.j : p.e; }
+                }
+            }
+            if (job == P.F.write_s2) {
+                R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s2(R, p)[c];
+                if (c == 0) { R.r_out[b] = ttnet::ring_pick_r(R, p); R.d_out[b] = ttnet::ring_pick_d(R, p); }
+            }
+        }
+    }
+    if (q.critic)
+        fwd_small_body<true>(n, q.obs, q.action, q.W, q.out, q.sv, q.dq_da, q.z_state, h1_s, z_s, w1_s, row0, orow, have_act, act_r0, act_r1);
+    else
+        fwd_small_body<false>(n, q.obs, q.action, q.W, q.out, q.sv, nullptr, nullptr, h1_s, z_s, w1_s, row0, orow);
+}
+
+// grid: K x (2 nb + 1), agent-major: critic rows, actor unit rows, the counter workgroup (k_bwd_rows_pair without the image rider)
+__global__ __launch_bounds__(64 * NW) void k_pop_bwd_rows_pair(const int K, const int n, const PopAgent *__restrict__ D) {
+    __shared__ __attribute__((aligned(16))) float dx2_s[DXS_FLOATS];
+    __shared__ float red[2 * NW * TR];
+    __shared__ float rsc_s[TR];
+    const int nb = (n + TR - 1) / TR, ag = (int)blockIdx.x / (2 * nb + 1);
+    if (ag >= K) return;
+    const int lb = (int)blockIdx.x - ag * (2 * nb + 1);
+    const PopAgent &P = agent_of(D, ag);
+    if (lb == 2 * nb) {
+        if (threadIdx.x == 0) clock_tick(P.td);
+        return;
+    }
+    if (lb < nb)
+        bwd_rows_body<true>(n, P.scale_c, P.q_out, P.Wc, P.sv_c, P.o_c, P.td, dx2_s, red, rsc_s, lb * TR);
+    else
+        bwd_rows_body<false>(n, 0.f, nullptr, P.Wa, P.sv_a, P.o_a, TdIn{}, dx2_s, red, rsc_s, (lb - nb) * TR);
+}
+
+// grid: K x 210, agent-major: the critic's weight gradients with its optimizer step
+template <bool ROWSCALE>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_pop_bwd_weights(const int K, const int n,
+                                                                                             const PopAgent *__restrict__ D) {
+    __shared__ __attribute__((aligned(16))) float part[4][4][256];
+    __shared__ float f_s[ROWSCALE ? MAXB : 1];
+    __shared__ __attribute__((aligned(16))) _Float16 stage_s[4 * 1024];
+    const int ag = (int)blockIdx.x / WG_CRITIC_WEIGHTS;
+    if (ag >= K) return;
+    const PopAgent &P = agent_of(D, ag);
+    bwd_weights_body<ROWSCALE, false>((int)blockIdx.x - ag * WG_CRITIC_WEIGHTS, n, 1, P.s, P.a, P.sv_c, P.o_c, P.Gc, P.Ac,
+                                      RowScale{nullptr, nullptr, 1.f}, part, f_s, TailSync{nullptr, nullptr, 0, nullptr}, 0, stage_s);
+}
+
+// grid: K x nb row workgroups FIRST (every agent's), then K x 200 weight workgroups.  A weight workgroup waits in device memory for
+// its agent's rows (TailSync), so every producer it may wait for is dispatched before any waiting workgroup: the row workgroups
+// never queue for a CU behind workgroups that wait for them.  Each agent keeps its own tail words, and its epoch is its own step.
+__global__ __launch_bounds__(64 * NW) void k_pop_actor_tail(const int K, const int n, const PopAgent *__restrict__ D) {
+    __shared__ __attribute__((aligned(16))) float lds[H1S_FLOATS + TR * DS + H1 * IN];
+    const int nb = (n + TR - 1) / TR, rows = K * nb;
+    if ((int)blockIdx.x < rows) {
+        const int ag = (int)blockIdx.x / nb, lb = (int)blockIdx.x - ag * nb;
+        const PopAgent &P = agent_of(D, ag);
+        const Saved none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const long long epoch = *P.Aa.step_dev;
+        fwd_small_body<true>(n, P.s, P.mu_out, P.Wc, P.q_pi, none, P.dq_da, nullptr, lds, lds + H1S_FLOATS,
+                             lds + H1S_FLOATS + TR * DS, lb * TR, nullptr, false, 0.f, 0.f, P.ts.rows, (unsigned)epoch);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave: its rows' words have been sent
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(P.ts.hints + lb, (int)epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const int ag = ((int)blockIdx.x - rows) / WG_ACTOR_WEIGHTS;
+    if (threadIdx.x >= 256 || ag >= K) return;
+    const PopAgent &P = agent_of(D, ag);
+    float (&part)[4][4][256] = *reinterpret_cast<float (*)[4][4][256]>(lds);
+    const long long epoch = *P.Aa.step_dev;
+    bwd_weights_body<true, true>((int)blockIdx.x - rows - ag * WG_ACTOR_WEIGHTS, n, 0, P.s, nullptr, P.sv_a, P.o_a, P.Ga, P.Aa, P.RSa,
+                                 part, lds + 4 * 4 * 256, P.ts, epoch, reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB));
+}
+
+char g_why[256];
+
+int einval(const char *fmt, int a = 0, int b = 0) {
+    snprintf(g_why, sizeof g_why, fmt, a, b);
+    return tthost::fail_library(TT_EINVAL, g_why);
+}
+
+// one agent's tt_pop_agent -> PopAgent (host checks only: no HIP call)
+int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
+    P = PopAgent{};
+    const tt_sample_args *smp = g.sample;
+    if (!smp) return einval("tt_pop_learn_create: agent %d has no sample (tt_sample_args)", a);
+    if (smp->batch != n) return einval("tt_pop_learn_create: agent %d draws batches of %d rows, not the population's B", a, smp->batch);
+    if (smp->step_progress || (smp->draws > 1)) return einval("tt_pop_learn_create: agent %d: step_progress / draws are not for populations", a);
+    if (smp->side && smp->side->count > 0) return einval("tt_pop_learn_create: agent %d has a side buffer (not in populations)", a);
+    if (ttnet::make_ring_sample(smp, P.F.R) != TT_OK) return einval("tt_pop_learn_create: agent %d: bad tt_sample_args", a);
+    P.F.R.seed_stride = smp->seed_stride;
+    P.F.n = n;
+    P.F.blocks_per_job = (n + TR - 1) / TR;
+    P.F.sampled = 1;
+    P.F.write_s = P.F.write_s2 = -1;
+    const tt_fwd_job *jobs = g.jobs;
+    if (!jobs) return einval("tt_pop_learn_create: agent %d has no forward jobs", a);
+    // the lone learn()'s four forwards, in their order: target actor on s', the target critic's state branch on s', Q(s, a), mu(s)
+    if (jobs[0].critic || jobs[0].obs != smp->s2_out || !jobs[1].critic || jobs[1].obs != smp->s2_out || !jobs[1].z_state ||
+        !jobs[2].critic || jobs[2].obs != smp->s_out || jobs[2].action != smp->a_out || !jobs[2].saved || jobs[3].critic ||
+        jobs[3].obs != smp->s_out || !jobs[3].saved)
+        return einval("tt_pop_learn_create: agent %d: the jobs are not learn()'s four forwards on its draw", a);
+    for (int i = 0; i < 4; ++i) {
+        const tt_fwd_job &q = jobs[i];
+        const bool critic = q.critic != 0;
+        if (!ok_shape(q.w, critic) || (!q.out && !q.z_state)) return einval("tt_pop_learn_create: agent %d: forward job %d is incomplete", a, i);
+        if (q.obs == smp->s_out && P.F.write_s < 0) P.F.write_s = i;
+        if (q.obs == smp->s2_out && P.F.write_s2 < 0) P.F.write_s2 = i;
+        Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        if (q.saved && !to_saved(q.saved, sv)) return einval("tt_pop_learn_create: agent %d: forward job %d has an incomplete tt_mlp_saved", a, i);
+        P.F.j[i] = FwdJob{q.obs, q.action, to_weights(q.w), q.out, sv, q.dq_da, critic ? q.z_state : nullptr, critic ? 1 : 0};
+    }
+    P.scale_c = (float)(2.0 / n);
+    P.q_out = jobs[2].out;
+    P.mu_out = jobs[3].out;
+    P.Wc = P.F.j[2].W;
+    P.Wa = P.F.j[3].W;
+    P.sv_c = P.F.j[2].sv;
+    P.sv_a = P.F.j[3].sv;
+    if (!P.q_out || !P.mu_out) return einval("tt_pop_learn_create: agent %d: Q(s, a) and mu(s) need outputs", a);
+    if (!to_bwd_out(g.critic.ws, P.o_c) || !to_bwd_out(g.actor.ws, P.o_a) || P.o_c.dx2 == P.o_a.dx2)
+        return einval("tt_pop_learn_create: agent %d: the per-row workspaces (tt_mlp_bwd_ws) are incomplete or shared", a);
+    const tt_td_input *tdi = g.td;
+    if (!tdi || !tdi->z_state || !tdi->mu_target || !ok_shape(tdi->target_critic, true) || !tdi->reward || !tdi->done || !tdi->y_out ||
+        !tdi->step_dev || tdi->window_dev)
+        return einval("tt_pop_learn_create: agent %d: bad tt_td_input (a step counter is required, a window counter is not for populations)", a);
+    const tt_mlp_weights *tw = tdi->target_critic;
+    P.td = TdIn{tdi->z_state, tdi->mu_target, tdi->reward, tdi->done, tw->wa, tw->ba, tw->w3, tw->b3, tdi->gamma, tdi->y_out, tdi->q_out,
+                reinterpret_cast<long long *>(tdi->step_dev), nullptr, tdi->bias_corr_out, tdi->adam_beta1, tdi->adam_beta2, 1};
+    P.s = smp->s_out;
+    P.a = smp->a_out;
+    for (int net = 0; net < 2; ++net) {
+        const tt_pop_net &t = net ? g.actor : g.critic;
+        const bool critic = net == 0;
+        if (!ok_shape(t.grads, critic)) return einval("tt_pop_learn_create: agent %d: network %d has no gradient buffers", a, net);
+        AdamFused &A = critic ? P.Ac : P.Aa;
+        if (!to_adam(critic, t.count, t.params, t.exp_avg, t.exp_avg_sq, t.targets, tdi->step_dev, t.lr, t.beta1, t.beta2, t.eps,
+                     t.weight_decay, t.tau, t.images, tdi->bias_corr_out, A))
+            return einval("tt_pop_learn_create: agent %d: network %d has an incomplete optimizer step", a, net);
+        (critic ? P.Gc : P.Ga) = to_grads(t.grads);
+    }
+    if (!g.q_pi || !g.dq_da || !g.tail_words) return einval("tt_pop_learn_create: agent %d: q_pi, dq_da and tail_words are required", a);
+    P.q_pi = g.q_pi;
+    P.dq_da = g.dq_da;
+    P.RSa = RowScale{g.dq_da, P.mu_out, (float)(-1.0 / n)};
+    P.ts = TailSync{g.tail_words, reinterpret_cast<unsigned long long *>(g.tail_words + 64), (n + TR - 1) / TR, g.gave_up_host};
+    return TT_OK;
+}
+
+}  // namespace
+
+struct tt_population {
+    int K = 0, n = 0;
+    PopAgent *dev = nullptr;
+};
+
+extern "C" {
+
+int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents, tt_population **out) {
+    if (!out) return einval("tt_pop_learn_create: out is NULL");
+    *out = nullptr;
+    if (count < 1 || count > TT_POP_MAX_AGENTS) return einval("tt_pop_learn_create: count = %d agents, not in [1, %d]", count, TT_POP_MAX_AGENTS);
+    if (batch < 1 || batch > MAXB) return einval("tt_pop_learn_create: batch = %d rows, not in [1, %d]", batch, MAXB);
+    if (!agents) return einval("tt_pop_learn_create: agents is NULL");
+    std::vector<PopAgent> host(count);
+    for (int a = 0; a < count; ++a) {
+        const int rc = to_pop_agent(agents[a], a, batch, host[a]);
+        if (rc != TT_OK) return rc;
+    }
+    PopAgent *dev = nullptr;
+    if (hipMalloc(&dev, sizeof(PopAgent) * count) != hipSuccess) return tthost::fail_library(TT_ENOMEM, "tt_pop_learn_create: hipMalloc");
+    if (hipMemcpy(dev, host.data(), sizeof(PopAgent) * count, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        return tthost::fail_library(TT_EHIP, "tt_pop_learn_create: hipMemcpy");
+    }
+    *out = new tt_population{count, batch, dev};
+    return TT_OK;
+}
+
+int tt_pop_learn(tt_population *h, int update, tt_stream_t stream) {
+    if (!h) return einval("tt_pop_learn: handle is NULL");
+    if (update < 0) return einval("tt_pop_learn: update = %d < 0", update);
+    const int K = h->K, n = h->n, nb = (n + TR - 1) / TR;
+    hipLaunchKernelGGL(k_pop_fwd_multi, dim3(K * 4 * nb), dim3(64 * NW), 0, stream, K, n, h->dev, update);
+    hipLaunchKernelGGL(k_pop_bwd_rows_pair, dim3(K * (2 * nb + 1)), dim3(64 * NW), 0, stream, K, n, h->dev);
+    hipLaunchKernelGGL(k_pop_bwd_weights<false>, dim3(K * WG_CRITIC_WEIGHTS), dim3(256), 0, stream, K, n, h->dev);
+    hipLaunchKernelGGL(k_pop_actor_tail, dim3(K * (nb + WG_ACTOR_WEIGHTS)), dim3(64 * NW), 0, stream, K, n, h->dev);
+    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_learn_destroy(tt_population *h) {
+    if (!h) return TT_OK;
+    const hipError_t e = hipFree(h->dev);
+    delete h;
+    return e == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+}  // extern "C"

@@ -1,0 +1,254 @@
+"""A population of K independent DDPG agents trained in one loop on one GPU (include/ttenv.h: tt_pop_learn_*).
+
+Agent a is exactly a lone serial-order DDPGRollout(pipeline=False) built with agent a's arguments -- its own env of n lanes, replay
+ring, OU noise, policy launch and env step -- except that its learn() launches are shared with the other K - 1 agents: one
+population update is four launches (csrc/ttpop.hip) that run every agent's workgroups.  Each agent's results are the bits of its
+lone loop with the actor tail in one launch (TT_ACTOR_TAIL=1).  Seeds, learning rates, tau and gamma are per agent; the network
+shape (23-400-300-1) and the batch size B are shared.
+
+Out of scope: the pipelined order, data-parallel populations, expert side buffers, whole-population checkpoints (an agent's
+weights save through agents[a].save_models())."""
+import ctypes as C
+
+import torch
+
+from ddpg_trucktrailer_amd import _lib as L
+from ddpg_trucktrailer_amd.fused_learn import FusedLearner
+from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, DDPGRollout
+
+
+class PopulationLearner:
+    """learn() of K agents, each with the state of a FusedLearner of its own (Adam moments, step_dev, bias corrections, tail words,
+    fc2 images), launched together.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys (update u of a vector
+    step draws with seed + u * _SEED_STRIDE, as DDPGRollout._sample_key(u)).  The device descriptors are made at the first learn():
+    every buffer and parameter storage must stay where it is from then on."""
+
+    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None):
+        self.K, self.B = len(agents), int(batch_size)
+        if not 1 <= self.K <= L.POP_MAX_AGENTS:
+            raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
+        if rings is None or seeds is None or len(rings) != self.K or len(seeds) != self.K:
+            raise ValueError("one ring and one seed per agent")
+        if any(r._side_struct() is not None for r in rings):
+            raise ValueError("expert side buffers are not supported in a population")
+        self.lib = L.load()
+        self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
+        self.learners = [FusedLearner(ag, self.B, fc2_images) for ag in self.agents]
+        for ag, fl in zip(self.agents, self.learners):
+            ag.fused_learner = fl          # (checkpoint.py exports the moments through it)
+        self._h = None
+        self._key = None
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and L._lib is not None:
+            torch.cuda.synchronize()
+            L._lib.tt_pop_learn_destroy(self._h)
+
+    def _storage_key(self):
+        return tuple(p.data_ptr() for ag in self.agents for n in (ag.actor, ag.critic, ag.target_actor, ag.target_critic)
+                     for p in n.parameters())
+
+    def _create(self):
+        B, keep = self.B, []
+        arr = (L.TTPopAgent * self.K)()
+        for a, (fl, ring, seed) in enumerate(zip(self.learners, self.rings, self.seeds)):
+            ag = fl.agent
+            sample = ring.sample_args(B, seed=seed, seed_stride=_SEED_STRIDE)
+            s, act, r, s2, d = ring._batch_bufs(B)[:5]
+            jobs = (L.TTFwdJob * 4)()
+            for j, (net, crit, obs, action, out, saved, zst) in enumerate((      # FusedLearner.phase_a's four forwards
+                    (ag.target_actor, 0, s2, None, fl.mu_t, None, None),
+                    (ag.target_critic, 1, s2, None, None, None, fl.z_t),
+                    (ag.critic, 1, s, act, fl.q, fl.critic.saved, None),
+                    (ag.actor, 0, s, None, fl.mu, fl.actor.saved, None))):
+                jobs[j].critic, jobs[j].obs = crit, obs.data_ptr()
+                jobs[j].action = action.data_ptr() if action is not None else None
+                jobs[j].w, jobs[j].out = C.pointer(fl.w(net)), out.data_ptr() if out is not None else None
+                jobs[j].saved = C.pointer(saved) if saved is not None else None
+                jobs[j].dq_da, jobs[j].z_state = None, zst.data_ptr() if zst is not None else None
+            td = L.TTTdInput(z_state=fl.z_t.data_ptr(), mu_target=fl.mu_t.data_ptr(), target_critic=C.pointer(fl.w(ag.target_critic)),
+                             reward=r.data_ptr(), done=d.data_ptr(), gamma=float(ag.gamma), y_out=fl.y.data_ptr(),
+                             q_out=fl.q_t.data_ptr(), step_dev=fl.step_dev.data_ptr(), window_dev=None,
+                             bias_corr_out=fl.bias_corr.data_ptr(), adam_beta1=fl.hyp_critic[1], adam_beta2=fl.hyp_critic[2])
+
+            def net(st, ws, hyp):
+                lr, b1, b2, eps, wd = hyp
+                return L.TTPopNet(C.pointer(ws), C.pointer(st.gstruct), st.count, 0, C.cast(st.a_p, C.c_void_p),
+                                  C.cast(st.a_m, C.c_void_p), C.cast(st.a_v, C.c_void_p), C.cast(st.a_t, C.c_void_p),
+                                  lr, b1, b2, eps, wd, ag.tau, C.pointer(st.images) if st.images is not None else None)
+            arr[a] = L.TTPopAgent(C.pointer(sample), jobs, C.pointer(td), net(fl.critic, fl.ws, fl.hyp_critic),
+                                  net(fl.actor, fl.ws_actor, fl.hyp_actor), fl.q_pi.data_ptr(), fl.dq_da.data_ptr(),
+                                  fl.tail_words.data_ptr(), fl.tail_gave_up_host.data_ptr())
+            keep += [sample, jobs, td]
+        h = C.c_void_p()
+        L.check(self.lib.tt_pop_learn_create(self.K, B, arr, C.byref(h)))      # (copies everything: `keep` may go now)
+        self._h, self._key = h, self._storage_key()
+
+    def refresh_images(self):
+        for fl in self.learners:
+            fl.refresh_images()
+
+    def learn(self, u=0):
+        """Update u of the running vector step for every agent, enqueued on the current stream (capturable once created)."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._h is None:
+            if capturing:
+                raise RuntimeError("PopulationLearner: run one eager learn() before capturing it")
+            self._create()
+        elif self._key != self._storage_key():
+            raise RuntimeError("PopulationLearner: a network's parameter storage moved since the descriptors were made")
+        if not capturing:
+            self.refresh_images()
+        L.check(self.lib.tt_pop_learn(self._h, int(u), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+
+    def tail_gave_up(self):
+        """[agent: 0, or the learn step whose tail hand-over was abandoned] (host memory only)."""
+        return [fl.tail_gave_up() for fl in self.learners]
+
+    def state_dict(self, a):
+        """Agent a's Adam moments and step count, in FusedLearner.state_dict()'s format."""
+        return self.learners[a].state_dict()
+
+
+def _per_agent(x, K, name):
+    if isinstance(x, (list, tuple)):
+        if len(x) != K:
+            raise ValueError(f"{name}: {len(x)} values for {K} agents")
+        return list(x)
+    return [x] * K
+
+
+class PopulationRollout:
+    """K DDPG loops of n_envs_per_agent envs each, one per seed, whose learn() launches are shared.  A vector step, in the serial
+    order of DDPGRollout.step(): every agent's opening pack, policy launch and env step, then updates_per_step population updates.
+    run(k) replays captured graphs of whole population steps (graph_steps and 1); step() launches the same step eagerly, with the
+    same bits.  alphas / betas / taus / gammas: one value for all agents or one per agent."""
+
+    def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
+                 updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
+                 pipeline=None, side_buffer=None):
+        from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+        if data_parallel or pipeline or side_buffer is not None:
+            raise ValueError("populations run the serial order on one GPU without expert side buffers (data-parallel populations, "
+                             "the pipelined order and side buffers are not supported)")
+        self.seeds = [int(s) for s in seeds]
+        K = self.K = len(self.seeds)
+        if not 1 <= K <= L.POP_MAX_AGENTS:
+            raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {K}")
+        alphas, betas, taus, gammas = (_per_agent(x, K, nm) for x, nm in ((alphas, "alphas"), (betas, "betas"), (taus, "taus"),
+                                                                           (gammas, "gammas")))
+        self.device = torch.device(device)
+        self.n, self.batch_size, self.updates_per_step = int(n_envs_per_agent), int(batch_size), int(updates_per_step)
+        self.loops = []
+        for a in range(K):
+            env = TruckTrailerVecEnv(self.n, device=self.device)
+            env.reset(seed=self.seeds[a])
+            # a lone serial-order loop whose own learner is not made: its learn() runs in the population's launches
+            lp = DDPGRollout(env, batch_size=self.batch_size, replay_slots=replay_slots, seed=self.seeds[a], alpha=alphas[a],
+                             beta=betas[a], tau=taus[a], gamma=gammas[a], fused_learn=False, graph_steps=0,
+                             updates_per_step=self.updates_per_step, pipeline=False, episode_log=episode_log)
+            if not lp.ring_mode:
+                raise RuntimeError("a population needs the fused policy and ring-addressed steps (reference-shaped actor on a GPU)")
+            self.loops.append(lp)
+        self.agents = [lp.agent for lp in self.loops]
+        self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
+                                         seeds=self.seeds)
+        self.graph_steps = int(graph_steps) if graph_steps else 0
+        self.graph1 = self.graphG = None
+        self._graph_epoch = None
+        self.vector_steps = 0
+
+    @property
+    def k(self):
+        return self.loops[0].ring.k
+
+    def _body(self):
+        """One population vector step's launches (no host work): what the graphs hold."""
+        for lp in self.loops:
+            lp._open_step(False)
+            lp._act_and_step()
+        for u in range(self.updates_per_step):
+            self.learner.learn(u)
+
+    def _check_handover(self):
+        """A launch that gave up waiting in device memory -- a tail weight workgroup for its dQ/da, or a policy launch for its image
+        -- went on with stale inputs: that agent's state is garbage.  Raised, never silent."""
+        for a, g in enumerate(self.learner.tail_gave_up()):
+            if g:
+                raise RuntimeError(f"agent {a}, learn step {g}: a weight-gradient workgroup of the population's tail launch gave up "
+                                   "waiting (0.25 s) for dQ/da from its agent's row workgroups and went on: that update is garbage")
+        for a, lp in enumerate(self.loops):
+            mark = lp.ring.gave_up_seen() if lp.ring.gave_up_host is not None else 0
+            if mark:
+                raise RuntimeError(f"agent {a}: a launch of vector step {mark - 1} gave up waiting for its step's policy image")
+
+    def step(self):
+        """One population vector step, launched eagerly."""
+        learn = self.k + 1 >= 2              # (DDPGRollout.learn(): no update before two steps are stored)
+        for lp in self.loops:
+            lp._open_step(False)
+            lp._act_and_step()
+            lp.ring.advance()
+            lp.vector_steps += 1
+        if learn:
+            for u in range(self.updates_per_step):
+                self.learner.learn(u)
+        self.vector_steps += 1
+        self._check_handover()
+
+    def invalidate_graphs(self):
+        self.graph1 = self.graphG = None
+
+    def _check_epoch(self):
+        from ddpg_trucktrailer_amd import fused
+        epoch = tuple((getattr(lp.env, "graph_epoch", 0), lp.ring.side_epoch, fused.packed_key_of(lp.agent.actor)) for lp in self.loops)
+        if self._graph_epoch != epoch:
+            self.invalidate_graphs()
+            self._graph_epoch = epoch
+
+    def _capture(self, steps):
+        import gc
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream())
+        g = torch.cuda.CUDAGraph()
+        gc.collect()
+        was_on = gc.isenabled()
+        gc.disable()         # (DDPGRollout._try_capture: no destructor of an earlier HIP object may run inside a capture)
+        try:
+            with torch.cuda.graph(g, stream=side, capture_error_mode=_CAPTURE_MODE):
+                for _ in range(steps):
+                    self._body()
+        finally:
+            if was_on:
+                gc.enable()
+        torch.cuda.current_stream().wait_stream(side)
+        return g
+
+    def run(self, k):
+        """k population vector steps: eager until every agent has stored 4 steps, then graph replays of graph_steps and 1 steps."""
+        self.learner.refresh_images()
+        while k > 0:
+            if self.graph_steps and self.k >= 4:
+                self._check_epoch()
+                if self.graph1 is None:
+                    self.graph1 = self._capture(1)
+                    self.graphG = self._capture(self.graph_steps) if self.graph_steps > 1 else None
+                if self.graphG is not None and k >= self.graph_steps:
+                    self.graphG.replay()
+                    done = self.graph_steps
+                else:
+                    self.graph1.replay()
+                    done = 1
+                for lp in self.loops:
+                    lp.ring.k += done                  # host mirror; the step kernels advanced k_dev
+                    lp.vector_steps += done
+                self.vector_steps += done
+                k -= done
+                self._check_handover()
+            else:
+                self.step()
+                k -= 1
+
+    def drain_episodes(self):
+        """[agent: its env's episode log since the last drain (DDPGRollout.drain_episodes)]."""
+        return [lp.drain_episodes() for lp in self.loops]

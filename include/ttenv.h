@@ -529,6 +529,46 @@ int tt_adam_soft_update(int count, float *const *params, const float *const *gra
                         const float *bias_corr /* tt_td_input.bias_corr_out or NULL */, tt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Population learn(): the learn() of K independent agents (K <= TT_POP_MAX_AGENTS, one batch size B <= 1024 for all, the
+ * reference-shaped networks) in the four launches of ONE agent's learn() with the tail in one grid -- tt_mlp_forward_multi_sampled,
+ * tt_mlp_backward_rows_pair, tt_mlp_backward_weights(critic, Adam), tt_mlp_actor_tail -- each launch running every agent's
+ * workgroups.  Agent a's results are the bits of those four lone launches made with agent a's arguments.  An agent is described by
+ * what its lone launches take; the library copies it into device memory at creation (every pointer must stay valid and fixed for the
+ * handle's life: rebuild the handle when a buffer moves), so tt_pop_learn makes no host work per call and can be captured.
+ *   sample      the agent's replay draw (batch == B, no side buffer, draws <= 1, no step_progress); update u draws with the key
+ *               seed + u * seed_stride (mod 2^64): a loop's update u of a vector step
+ *   jobs        [4] learn()'s forwards in the lone order: target actor on s', the target critic's state branch on s' (z_state),
+ *               the critic on (s, a) with saved activations, the actor on s with saved activations
+ *   td          the TD prologue; step_dev required (the agent's Adam step and its tail epoch), window_dev NULL
+ *   critic / actor  the per-row workspace, the flat gradient and the optimizer step (tt_mlp_backward_weights' count .. images;
+ *               the HOST arrays of device pointers are copied) of each network; the bias corrections come from td->bias_corr_out
+ *   q_pi, dq_da, tail_words, gave_up_host   as tt_mlp_actor_tail's q_out, dq_da, tail_words (64 + 2 B ints, -1 at creation and
+ *               whenever *step_dev is set back) and gave_up_host; the tail's row scale is -1/B, the critic's loss scale 2/B.
+ * Bad arguments return TT_EINVAL with a message in tt_last_error(NULL), before any HIP call.  The tail launch dispatches the row
+ * workgroups of ALL agents before any weight workgroup that waits for them (each agent's hand-over words are its own). */
+#define TT_POP_MAX_AGENTS 16
+typedef struct tt_population tt_population;
+typedef struct tt_pop_net {
+    const tt_mlp_bwd_ws *ws;
+    const tt_mlp_weights *grads;
+    int32_t count, reserved_;           /* 12 tensors (critic) / 10 (actor) */
+    float *const *params, *const *exp_avg, *const *exp_avg_sq, *const *targets;
+    float lr, beta1, beta2, eps, weight_decay, tau;
+    const tt_fc2_images *images;        /* may be NULL */
+} tt_pop_net;
+typedef struct tt_pop_agent {
+    const tt_sample_args *sample;
+    const tt_fwd_job *jobs;
+    const tt_td_input *td;
+    tt_pop_net critic, actor;
+    float *q_pi, *dq_da;
+    int32_t *tail_words, *gave_up_host;
+} tt_pop_agent;
+int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents /*[count]*/, tt_population **out);
+int tt_pop_learn(tt_population *pop, int update, tt_stream_t stream);      /* one update of every agent, enqueued on stream */
+int tt_pop_learn_destroy(tt_population *pop);                                /* the caller's stream work with it must be done */
+
+/* ------------------------------------------------------------------------------------------------------
  * Peer-to-peer gradient exchange of data-parallel ranks (one process per GPU of one node): the mean over the ranks of the
  * critic's / the actor's gradient at the reference's two optimizer sites (DDPG/DDPG_agent.py:95-104) WITHOUT a collective
  * launch on learn()'s chain.  Every rank owns two blocks of device memory -- per site a flat f32 gradient buffer

@@ -1,0 +1,141 @@
+#!/usr/bin/env python3
+"""GPU: what a population of K agents buys (ddpg_trucktrailer_amd/population.py).
+
+learn() alone, K in {1, 2, 4, 8, 16} at B = 256: per K a PopulationLearner on K filled rings, a captured graph of `per_graph`
+population updates replayed after warm-up, timed with device events over >= `updates` updates; `legs` legs with the K values in
+alternating order -> median and spread of us per population update and of aggregate agent-updates/s.  Beside them the lone
+FusedLearner's chain (the tail in one launch) timed the same way.
+Then the loop: K = 8 x n = 8192 envs at 8 updates per step (1024 env-steps per update per agent) against one agent at N = 65536
+with 64 updates per step, in the same process.
+Kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/time_population.py --no-loop` separately.
+Usage: time_population.py [--legs 5] [--updates 1000] [--no-loop] [--loop-steps 60]"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import torch  # noqa: E402
+
+from ddpg_trucktrailer_amd.agent import Agent  # noqa: E402
+from ddpg_trucktrailer_amd.fused_learn import FusedLearner  # noqa: E402
+from ddpg_trucktrailer_amd.population import PopulationLearner, PopulationRollout  # noqa: E402
+from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing  # noqa: E402
+from ddpg_trucktrailer_amd.rollout import DDPGRollout  # noqa: E402
+from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv  # noqa: E402
+
+DEV = torch.device("cuda:0")
+B = 256
+
+
+def ring(seed):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    r = TrajectoryRing(2048, 16, 23, DEV)
+    r.obs.copy_(torch.rand(r.obs.shape, device=DEV, generator=g) * 2 - 1)
+    r.act.copy_(torch.rand(r.act.shape, device=DEV, generator=g) * 2 - 1)
+    r.rew.copy_(torch.rand(r.rew.shape, device=DEV, generator=g) * 10 - 5)
+    r.done.copy_((torch.rand(r.done.shape, device=DEV, generator=g) < 0.05).to(torch.uint8))
+    r.k = 15
+    r.k_dev.fill_(15)
+    return r
+
+
+def agent(seed):
+    torch.manual_seed(seed)
+    return Agent(alpha=1e-4, beta=1e-3, input_dims=(23,), tau=1e-3, n_actions=1, batch_size=B, device=DEV, replay=False)
+
+
+def captured(fn, per_graph):
+    for _ in range(3):
+        fn(0)
+    torch.cuda.synchronize()
+    side = torch.cuda.Stream()
+    side.wait_stream(torch.cuda.current_stream())
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g, stream=side):
+        for i in range(per_graph):
+            fn(i % 8)
+    torch.cuda.current_stream().wait_stream(side)
+    for _ in range(2):
+        g.replay()
+    torch.cuda.synchronize()
+    return g
+
+
+def timed(g, replays):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(replays):
+        g.replay()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) * 1e3          # us
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--legs", type=int, default=5)
+    ap.add_argument("--updates", type=int, default=1000)
+    ap.add_argument("--per-graph", type=int, default=100)
+    ap.add_argument("--no-loop", action="store_true")
+    ap.add_argument("--loop-steps", type=int, default=60)
+    a = ap.parse_args()
+    Ks = (1, 2, 4, 8, 16)
+    replays = max(1, -(-a.updates // a.per_graph))
+    graphs = {}
+    for K in Ks:
+        pop = PopulationLearner([agent(100 + i) for i in range(K)], B, rings=[ring(200 + i) for i in range(K)],
+                                seeds=[300 + i for i in range(K)])
+        graphs[K] = (pop, captured(pop.learn, a.per_graph))
+    fl = FusedLearner(agent(1), B)
+    fl.fuse_tail = True
+    lone_ring = ring(2)
+    s, act, r, s2, d = lone_ring._batch_bufs(B)[:5]
+    args = [lone_ring.sample_args(B, seed=7 + u) for u in range(8)]
+    lone = captured(lambda u: fl.learn_batch(s, act, r, s2, d, sample=args[u]), a.per_graph)
+    res = {K: [] for K in Ks}
+    res["lone"] = []
+    for leg in range(a.legs):
+        order = list(Ks) if leg % 2 == 0 else list(reversed(Ks))
+        for K in order:
+            res[K].append(timed(graphs[K][1], replays) / (replays * a.per_graph))
+        res["lone"].append(timed(lone, replays) / (replays * a.per_graph))
+    for K, (pop, _) in graphs.items():
+        assert pop.tail_gave_up() == [0] * K
+    print(f"# learn() alone, B = {B}, {replays * a.per_graph} graph-replayed updates per leg, {a.legs} legs (K order alternating)")
+    print(f"# device {torch.cuda.get_device_name(0)}")
+    print(f"{'K':>6} {'us/pop update':>14} {'spread':>16} {'agent-updates/s':>16} {'vs K=1':>7}")
+    base = statistics.median(res[1])
+    for K in ("lone",) + Ks:
+        m = statistics.median(res[K])
+        k = 1 if K == "lone" else K
+        print(f"{K!s:>6} {m:14.2f} {min(res[K]):7.2f}-{max(res[K]):7.2f} {k * 1e6 / m:16.3e} {(k / m) / (1 / base):7.2f}")
+    if a.no_loop:
+        return
+    print()
+    print(f"# the loop, {a.loop_steps} graph-replayed vector steps after setup")
+    out = []
+    for name in ("population K=8 x n=8192, 8 upd/step", "one agent N=65536, 64 upd/step"):
+        if name.startswith("population"):
+            lp = PopulationRollout(8192, [11 + i for i in range(8)], batch_size=B, replay_slots=64, updates_per_step=8, graph_steps=20)
+            lp.run(24)
+            envs, upd = 8 * 8192, 8 * 8
+        else:
+            env = TruckTrailerVecEnv(65536, device=DEV)
+            env.reset(seed=27)
+            lp = DDPGRollout(env, batch_size=B, replay_slots=64, seed=27, updates_per_step=64, graph_steps=20)
+            lp.prepare()
+            lp.first_launches()
+            envs, upd = 65536, 64
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        lp.run(a.loop_steps)
+        torch.cuda.synchronize()
+        dt = (time.perf_counter() - t0) / a.loop_steps
+        out.append((name, dt))
+        print(f"{name:40s} {dt * 1e3:8.3f} ms/step  {envs / dt:10.3e} env-steps/s  {upd / dt:10.3e} agent-updates/s")
+
+
+if __name__ == "__main__":
+    main()
