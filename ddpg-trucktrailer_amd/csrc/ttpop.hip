@@ -2,7 +2,8 @@
 //
 // Agent a of a population is a lone serial-order loop of its own (its env, replay ring, OU noise, policy launch and env step); only
 // its learn() launches are shared: each launch below runs the workgroups of all K agents, and a workgroup finds its agent and its
-// block within the agent's grid from blockIdx.x.  The bodies are ttlearn.hip's, called with the arguments the lone launches pass:
+// block within the agent's grid from blockIdx.x.  The bodies are those of ttlearn_bodies.h, called with the arguments the lone
+// launches of ttlearn.hip pass:
 //
 //   k_pop_fwd_multi            k_fwd_multi, sampled: agent a's draw from agent a's ring (seed + u * seed_stride), its four forwards
 //   k_pop_bwd_rows_pair        k_bwd_rows_pair: TD prologue, critic rows, actor unit rows, the counter workgroup
@@ -14,8 +15,7 @@
 // The descriptors are read through the CONSTANT address space, as kernel arguments are: the bodies index the Adam tables with a
 // run-time tensor number (an array copied into registers would go to scratch), and constant loads are scalar loads that the
 // compiler may issue as early as it likes (nothing in a launch writes them).
-#define TT_LEARN_BODIES_ONLY
-#include "ttlearn.hip"
+#include "ttlearn_bodies.h"
 
 #include <cstdio>
 #include <vector>
@@ -44,9 +44,6 @@ struct PopAgent {
     float *q_pi, *dq_da;
     TailSync ts;                         // this agent's own tail words; its epoch is its own step count
 };
-
-constexpr int WG_CRITIC_WEIGHTS = NU2 + NU1 + SUMB_CRITIC;    // 210
-constexpr int WG_ACTOR_WEIGHTS = NU2 + NU1 + SUMB_ACTOR;      // 200
 
 // agent a's descriptor, as a reference into the constant address space (see the head of the file)
 __device__ __forceinline__ const PopAgent &agent_of(const PopAgent *D, const int a) {
@@ -191,16 +188,9 @@ int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
         !jobs[2].critic || jobs[2].obs != smp->s_out || jobs[2].action != smp->a_out || !jobs[2].saved || jobs[3].critic ||
         jobs[3].obs != smp->s_out || !jobs[3].saved)
         return einval("tt_pop_learn_create: agent %d: the jobs are not learn()'s four forwards on its draw", a);
-    for (int i = 0; i < 4; ++i) {
-        const tt_fwd_job &q = jobs[i];
-        const bool critic = q.critic != 0;
-        if (!ok_shape(q.w, critic) || (!q.out && !q.z_state)) return einval("tt_pop_learn_create: agent %d: forward job %d is incomplete", a, i);
-        if (q.obs == smp->s_out && P.F.write_s < 0) P.F.write_s = i;
-        if (q.obs == smp->s2_out && P.F.write_s2 < 0) P.F.write_s2 = i;
-        Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
-        if (q.saved && !to_saved(q.saved, sv)) return einval("tt_pop_learn_create: agent %d: forward job %d has an incomplete tt_mlp_saved", a, i);
-        P.F.j[i] = FwdJob{q.obs, q.action, to_weights(q.w), q.out, sv, q.dq_da, critic ? q.z_state : nullptr, critic ? 1 : 0};
-    }
+    for (int i = 0; i < 4; ++i)
+        if (!to_fwd_job(jobs[i], i, smp, P.F))
+            return einval("tt_pop_learn_create: agent %d: forward job %d is incomplete or has an action other than the draw's a on s", a, i);
     P.scale_c = (float)(2.0 / n);
     P.q_out = jobs[2].out;
     P.mu_out = jobs[3].out;
@@ -212,12 +202,8 @@ int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
     if (!to_bwd_out(g.critic.ws, P.o_c) || !to_bwd_out(g.actor.ws, P.o_a) || P.o_c.dx2 == P.o_a.dx2)
         return einval("tt_pop_learn_create: agent %d: the per-row workspaces (tt_mlp_bwd_ws) are incomplete or shared", a);
     const tt_td_input *tdi = g.td;
-    if (!tdi || !tdi->z_state || !tdi->mu_target || !ok_shape(tdi->target_critic, true) || !tdi->reward || !tdi->done || !tdi->y_out ||
-        !tdi->step_dev || tdi->window_dev)
+    if (!to_td(tdi, P.td) || !tdi->step_dev || tdi->window_dev)
         return einval("tt_pop_learn_create: agent %d: bad tt_td_input (a step counter is required, a window counter is not for populations)", a);
-    const tt_mlp_weights *tw = tdi->target_critic;
-    P.td = TdIn{tdi->z_state, tdi->mu_target, tdi->reward, tdi->done, tw->wa, tw->ba, tw->w3, tw->b3, tdi->gamma, tdi->y_out, tdi->q_out,
-                reinterpret_cast<long long *>(tdi->step_dev), nullptr, tdi->bias_corr_out, tdi->adam_beta1, tdi->adam_beta2, 1};
     P.s = smp->s_out;
     P.a = smp->a_out;
     for (int net = 0; net < 2; ++net) {

@@ -30,6 +30,10 @@ def _p(t):
     return None if t is None else C.c_void_p(t.data_ptr())
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
 def _no_sync():
     return None
 
@@ -303,18 +307,7 @@ class FusedLearner:
         # state branch on s', Q(s,a), mu(s), each filling 16 of the 256 CUs -- and the critic's backward then finishes
         # q'(s', mu'(s')) and the TD target.  The four are ONE launch (tt_mlp_forward_multi): a stream fork/join inside
         # a captured graph costs more than the kernel it would hide
-        def ptr(t):
-            return None if t is None else t.data_ptr()
-        jobs = (L.TTFwdJob * 4)()
-        for j, (net, crit, obs, act, out, saved, zst) in enumerate((
-                (ag.target_actor, 0, states_, None, self.mu_t, None, None),
-                (ag.target_critic, 1, states_, None, None, None, self.z_t),
-                (ag.critic, 1, states, actions, self.q, self.critic.saved, None),
-                (ag.actor, 0, states, None, self.mu, self.actor.saved, None))):
-            jobs[j].critic, jobs[j].obs, jobs[j].action = crit, ptr(obs), ptr(act)
-            jobs[j].w, jobs[j].out = C.pointer(self.w(net)), ptr(out)
-            jobs[j].saved = C.pointer(saved) if saved is not None else None
-            jobs[j].dq_da, jobs[j].z_state = None, ptr(zst)
+        jobs = self.fwd_jobs(states, actions, states_)
         if sample is not None:
             assert (sample.s_out, sample.a_out, sample.s2_out) == (states.data_ptr(), actions.data_ptr(), states_.data_ptr())
             L.check(self.lib.tt_mlp_forward_multi_sampled(B, 4, jobs, C.byref(sample), _p(image[2]) if image is not None else None,
@@ -324,17 +317,37 @@ class FusedLearner:
         self._rows(rewards, done_u8, window_dev, image)
         self._weights(self.critic, self.hyp_critic, ag.tau, states, actions, self.ws, adam=fuse_adam)
 
+    def fwd_jobs(self, states, actions, states_):
+        """learn()'s four forwards (tt_fwd_job[4]) on a batch, in their order: the target actor and the target critic's state
+        branch on s', Q(s, a) and mu(s) with what their backward needs.  (Also a population's: PopulationLearner.)"""
+        ag = self.agent
+        jobs = (L.TTFwdJob * 4)()
+        for j, (net, crit, obs, act, out, saved, zst) in enumerate((
+                (ag.target_actor, 0, states_, None, self.mu_t, None, None),
+                (ag.target_critic, 1, states_, None, None, None, self.z_t),
+                (ag.critic, 1, states, actions, self.q, self.critic.saved, None),
+                (ag.actor, 0, states, None, self.mu, self.actor.saved, None))):
+            jobs[j].critic, jobs[j].obs, jobs[j].action = crit, _ptr(obs), _ptr(act)
+            jobs[j].w, jobs[j].out = C.pointer(self.w(net)), _ptr(out)
+            jobs[j].saved = C.pointer(saved) if saved is not None else None
+            jobs[j].dq_da, jobs[j].z_state = None, _ptr(zst)
+        return jobs
+
+    def td_input(self, rewards, done_u8, window_dev=None):
+        """The input of the TD prologue of the critic's per-row backward (tt_td_input).  (Also a population's: PopulationLearner.)"""
+        ag = self.agent
+        return L.TTTdInput(z_state=self.z_t.data_ptr(), mu_target=self.mu_t.data_ptr(),
+                           target_critic=C.pointer(self.w(ag.target_critic)), reward=rewards.data_ptr(),
+                           done=done_u8.data_ptr(), gamma=float(ag.gamma), y_out=self.y.data_ptr(),
+                           q_out=self.q_t.data_ptr(), step_dev=self.step_dev.data_ptr(), window_dev=_ptr(window_dev),
+                           bias_corr_out=self.bias_corr.data_ptr(), adam_beta1=self.hyp_critic[1], adam_beta2=self.hyp_critic[2])
+
     def _rows(self, rewards, done_u8, window_dev=None, image=None):
         """learn()'s per-row backward launch (tt_mlp_backward_rows_pair) after the forwards of phase_a."""
         ag, B = self.agent, self.B
         # critic step (DDPG_agent.py:95-98); its backward launch first finishes q'(s', mu'(s')) and the TD target for its
         # rows (tt_td_input)
-        td = L.TTTdInput(z_state=self.z_t.data_ptr(), mu_target=self.mu_t.data_ptr(),
-                         target_critic=C.pointer(self.w(ag.target_critic)), reward=rewards.data_ptr(),
-                         done=done_u8.data_ptr(), gamma=float(ag.gamma), y_out=self.y.data_ptr(),
-                         q_out=self.q_t.data_ptr(), step_dev=self.step_dev.data_ptr(),
-                         window_dev=window_dev.data_ptr() if window_dev is not None else None,
-                         bias_corr_out=self.bias_corr.data_ptr(), adam_beta1=self.hyp_critic[1], adam_beta2=self.hyp_critic[2])
+        td = self.td_input(rewards, done_u8, window_dev)
         # ... and, on other workgroups of the same launch, the ACTOR's per-row backward for a unit gradient: it is linear in
         # the row's d(loss)/d(pre-tanh), which needs the updated critic and is applied in phase_b (include/ttenv.h)
         L.check(self.lib.tt_mlp_backward_rows_pair(B, 2.0 / B, _p(self.q), C.byref(self.w(ag.critic)),

@@ -14,7 +14,7 @@ import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner
-from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, DDPGRollout
+from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, DDPGRollout, _gc_off
 
 
 class PopulationLearner:
@@ -55,21 +55,7 @@ class PopulationLearner:
             ag = fl.agent
             sample = ring.sample_args(B, seed=seed, seed_stride=_SEED_STRIDE)
             s, act, r, s2, d = ring._batch_bufs(B)[:5]
-            jobs = (L.TTFwdJob * 4)()
-            for j, (net, crit, obs, action, out, saved, zst) in enumerate((      # FusedLearner.phase_a's four forwards
-                    (ag.target_actor, 0, s2, None, fl.mu_t, None, None),
-                    (ag.target_critic, 1, s2, None, None, None, fl.z_t),
-                    (ag.critic, 1, s, act, fl.q, fl.critic.saved, None),
-                    (ag.actor, 0, s, None, fl.mu, fl.actor.saved, None))):
-                jobs[j].critic, jobs[j].obs = crit, obs.data_ptr()
-                jobs[j].action = action.data_ptr() if action is not None else None
-                jobs[j].w, jobs[j].out = C.pointer(fl.w(net)), out.data_ptr() if out is not None else None
-                jobs[j].saved = C.pointer(saved) if saved is not None else None
-                jobs[j].dq_da, jobs[j].z_state = None, zst.data_ptr() if zst is not None else None
-            td = L.TTTdInput(z_state=fl.z_t.data_ptr(), mu_target=fl.mu_t.data_ptr(), target_critic=C.pointer(fl.w(ag.target_critic)),
-                             reward=r.data_ptr(), done=d.data_ptr(), gamma=float(ag.gamma), y_out=fl.y.data_ptr(),
-                             q_out=fl.q_t.data_ptr(), step_dev=fl.step_dev.data_ptr(), window_dev=None,
-                             bias_corr_out=fl.bias_corr.data_ptr(), adam_beta1=fl.hyp_critic[1], adam_beta2=fl.hyp_critic[2])
+            jobs, td = fl.fwd_jobs(s, act, s2), fl.td_input(r, d)
 
             def net(st, ws, hyp):
                 lr, b1, b2, eps, wd = hyp
@@ -207,20 +193,12 @@ class PopulationRollout:
             self._graph_epoch = epoch
 
     def _capture(self, steps):
-        import gc
         side = torch.cuda.Stream(device=self.device)
         side.wait_stream(torch.cuda.current_stream())
         g = torch.cuda.CUDAGraph()
-        gc.collect()
-        was_on = gc.isenabled()
-        gc.disable()         # (DDPGRollout._try_capture: no destructor of an earlier HIP object may run inside a capture)
-        try:
-            with torch.cuda.graph(g, stream=side, capture_error_mode=_CAPTURE_MODE):
-                for _ in range(steps):
-                    self._body()
-        finally:
-            if was_on:
-                gc.enable()
+        with _gc_off(), torch.cuda.graph(g, stream=side, capture_error_mode=_CAPTURE_MODE):
+            for _ in range(steps):
+                self._body()
         torch.cuda.current_stream().wait_stream(side)
         return g
 

@@ -29,6 +29,8 @@ launches of steps t-1 and t, on a second stream.  What this needs:
 Captured graphs hold the two chains with one edge each way per step (_capture_lagged); eager steps join the two streams at
 the end of every step, which is stricter; no launch reads what a concurrent one writes, so graphs, eager launches and a
 resumed run still agree bit for bit."""
+import contextlib
+import gc
 import math
 import os
 
@@ -49,6 +51,21 @@ _SEED_STRIDE = 0x9E3779B97F4A7C15     # sampling key of update u of a vector ste
 # Pipelined order: learn() of vector step t draws from the steps up to t-2 (lag 1: step t-1 may still be under way beside the
 # draw) and keeps off the two observation rows the env steps t-1 and t write meanwhile (reserve 2)
 _PIPE_LAG, _PIPE_RESERVE = 1, 2
+
+
+@contextlib.contextmanager
+def _gc_off():
+    """No garbage collection while a capture is open: a collected hipGraph, stream, event or env handle of some EARLIER
+    object runs HIP calls in its destructor that are illegal during capture (torch aborts the process).  Collect first,
+    then keep the collector off until the last graph of the block is captured."""
+    gc.collect()
+    was_on = gc.isenabled()
+    gc.disable()
+    try:
+        yield
+    finally:
+        if was_on:
+            gc.enable()
 
 
 class DDPGRollout:
@@ -548,25 +565,16 @@ class DDPGRollout:
             self.dp_graphs["c"].replay()
 
     def _try_capture(self):
-        import gc
-        # No garbage collection while a capture is open: a collected hipGraph, stream, event or env handle of some EARLIER
-        # object runs HIP calls in its destructor that are illegal during capture (torch aborts the process).  Collect
-        # first, then keep the collector off until the last graph is captured.
-        gc.collect()
-        was_on = gc.isenabled()
-        gc.disable()
-        try:
-            self._capture_step_graphs()
-            return True
-        except Exception as exc:        # capture refused (driver / library state): the eager path is the same bits.
-            import warnings             # (covers capture ERRORS only: a crash inside the runtime is not an exception)
-            warnings.warn(f"whole-step hipGraph capture failed ({exc!r}); continuing with eager steps")
-            self.invalidate_graphs()
-            self.graph_steps = 0
-            return False
-        finally:
-            if was_on:
-                gc.enable()
+        with _gc_off():
+            try:
+                self._capture_step_graphs()
+                return True
+            except Exception as exc:        # capture refused (driver / library state): the eager path is the same bits.
+                import warnings             # (covers capture ERRORS only: a crash inside the runtime is not an exception)
+                warnings.warn(f"whole-step hipGraph capture failed ({exc!r}); continuing with eager steps")
+                self.invalidate_graphs()
+                self.graph_steps = 0
+                return False
 
     def prepare(self):
         """Everything one-off that run() would otherwise do lazily inside its first calls (a few eager vector steps that
