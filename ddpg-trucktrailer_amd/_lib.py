@@ -19,6 +19,9 @@ NINFO = len(INFO_ROWS)
 # counters of the episode log (TT_LOG_NCOUNTS, include/ttenv.h: tt_env_set_episode_log), in their order
 LOG_COUNTS = ("episodes", "successes", "jackknife", "out_of_map", "max_steps", "goal_reached", "goal_passed",
               "excessive_back", "success_flag")
+# the detailed episode log (TT_LOG_DETAIL, include/ttenv.h: tt_env_set_episode_log2): one sum per reward term, INFO_ROWS[1:10]
+LOG_DETAIL = 1
+LOG_COMPONENTS = INFO_ROWS[1:10]
 
 
 class TTParams(C.Structure):
@@ -140,6 +143,8 @@ _SIGNATURES = {
     "tt_env_episode_log_bytes": (C.c_size_t, [_P]),
     "tt_env_export_episode_log": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 2), _P]),
     "tt_env_import_episode_log": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 2), _P]),
+    "tt_env_set_episode_log2": (C.c_int, [_P, C.c_int64, C.c_uint32, _P]),
+    "tt_env_drain_episode_log2": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "tt_env_rollout_random": (C.c_int, [_P, _I, _U64, _P, _P, _P, _P]),
     "tt_env_profile": (C.c_int, [_P, _I]),
     "tt_env_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -689,6 +689,26 @@ __host__ __device__ inline size_t log_records_bytes(unsigned long long cap) {
     return (sizeof(unsigned long long) * LOG_HDR + (2 * sizeof(double) + 2 * sizeof(int32_t) + 2) * (size_t)cap + 7) & ~(size_t)7;
 }
 
+// The detailed log (TT_LOG_DETAIL; k_step_tally) extends the same block:
+//   header  word LG_DETAIL holds the flags the log was enabled with, so that an exported blob says what it is
+//   records after the plain columns: comp f64 [TT_LOG_NCOMP, cap] (the episode's sum of each reward term, TT_I_PROGRESS ..
+//           TT_I_SMOOTH) | start f64 [3, cap] (the episode's start pose x, y, yaw)
+//   accumulators after the return's row [npad]: the term sums f64 [npad / TILE][TT_LOG_NCOMP][TILE] (tally_acc)
+// Nothing of the plain layout moves but the accumulator, which EpLog points at.
+constexpr int LG_DETAIL = LG_COUNTS + TT_LOG_NCOUNTS;
+static_assert(LG_DETAIL < LOG_HDR, "episode-log header");
+static_assert(TT_LOG_NCOMP == TT_I_SMOOTH - TT_I_PROGRESS + 1, "detailed episode log: one sum per reward term");
+__host__ __device__ inline size_t tally_records_bytes(unsigned long long cap) {
+    return sizeof(double) * (TT_LOG_NCOMP + 3) * (size_t)cap;
+}
+struct TallyCols {
+    double *comp, *start;
+};
+__host__ __device__ inline TallyCols tally_cols(const EpLog &lg) {
+    double *p = reinterpret_cast<double *>(reinterpret_cast<char *>(lg.hdr) + log_records_bytes(lg.capacity));
+    return TallyCols{p, p + TT_LOG_NCOMP * (size_t)lg.capacity};
+}
+
 __device__ __forceinline__ unsigned long long atomic_add_agent(unsigned long long *p, unsigned long long v) {
     return __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -696,14 +716,12 @@ __device__ __forceinline__ unsigned long long atomic_add_agent(unsigned long lon
 // The finishers of one wave append their records with ONE atomic on the write index (lane 0: the valid lanes of a wave are a
 // prefix, so lane 0 is active whenever any lane is); each finisher's slot is the base plus the number of finishers below it
 // (v_mbcnt).  Slots at or past the capacity are not stored, the index keeps counting.  Outcome counters: one integer atomic per
-// outcome that has a finisher in the wave.  Called by every active lane of the wave (the ballots need them all).
-// The record's end_step is the launch number, read here and at the workgroup's exit: both before the workgroup's exit ticket
-// (below, k_step_log), so before the last workgroup of the launch advances it.
-__device__ __forceinline__ void log_append(const EpLog &lg, int i, bool done, uint32_t flags, bool success, uint32_t len,
-                                           double ret) {
-    const unsigned long long fin = __ballot(done);
-    if (!fin) return;
-    const bool succ = done && success;
+// outcome that has a finisher in the wave.  Called by every active lane of the wave (the ballots need them all) when the wave
+// has finishers (fin = __ballot(done) != 0); returns the wave's base slot.
+// The record's end_step is the launch number, read in log_write and at the workgroup's exit: both before the workgroup's exit
+// ticket (below, k_step_log), so before the last workgroup of the launch advances it.
+__device__ __forceinline__ unsigned long long log_reserve(const EpLog &lg, unsigned long long fin, bool done, uint32_t flags,
+                                                          bool succ) {
     const bool lead = __lane_id() == 0;
     unsigned long long base = 0;
     if (lead) base = atomic_add_agent(lg.hdr + LG_WRITTEN, (unsigned long long)__popcll(fin));
@@ -716,20 +734,35 @@ __device__ __forceinline__ void log_append(const EpLog &lg, int i, bool done, ui
         const unsigned long long m = __ballot(done && ((flags >> f) & 1u));
         if (lead && m) atomic_add_agent(lg.hdr + LG_COUNTS + 2 + f, (unsigned long long)__popcll(m));
     }
-    base = ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
+    return ((unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)(base >> 32)) << 32) |
            (unsigned long long)__builtin_amdgcn_readfirstlane((uint32_t)base);
+}
+
+__device__ __forceinline__ unsigned long long log_slot(unsigned long long base, unsigned long long fin) {
+    return base + __builtin_amdgcn_mbcnt_hi((uint32_t)(fin >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fin, 0u));
+}
+
+// the plain columns of record `slot` (< capacity)
+__device__ __forceinline__ void log_write(const EpLog &lg, unsigned long long slot, int i, uint32_t flags, bool succ,
+                                          uint32_t len, double ret) {
+    const LogCols c = log_cols(lg);
+    c.ret[slot] = ret;
+    c.end_step[slot] = (long long)__hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    c.len[slot] = (int32_t)len;
+    c.lane[slot] = i;
+    c.flags[slot] = (uint8_t)flags;
+    c.success[slot] = succ ? 1 : 0;
+}
+
+__device__ __forceinline__ void log_append(const EpLog &lg, int i, bool done, uint32_t flags, bool success, uint32_t len,
+                                           double ret) {
+    const unsigned long long fin = __ballot(done);
+    if (!fin) return;
+    const bool succ = done && success;
+    const unsigned long long base = log_reserve(lg, fin, done, flags, succ);
     if (done) {
-        const unsigned long long slot =
-            base + __builtin_amdgcn_mbcnt_hi((uint32_t)(fin >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)fin, 0u));
-        if (slot < lg.capacity) {
-            const LogCols c = log_cols(lg);
-            c.ret[slot] = ret;
-            c.end_step[slot] = (long long)__hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            c.len[slot] = (int32_t)len;
-            c.lane[slot] = i;
-            c.flags[slot] = (uint8_t)flags;
-            c.success[slot] = succ ? 1 : 0;
-        }
+        const unsigned long long slot = log_slot(base, fin);
+        if (slot < lg.capacity) log_write(lg, slot, i, flags, succ, len, ret);
     }
 }
 
@@ -877,6 +910,125 @@ __global__ __launch_bounds__(BLOCK) void k_step_log(const KParams P, const int n
         const unsigned long long launch = __hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         const unsigned long long t = atomic_add_agent(lg.hdr + LG_TICKET, 1ull);
         if (t == gridDim.x - 1u) {    // the last workgroup of the launch; the next launch reads the count
+            __hip_atomic_store(lg.hdr + LG_TICKET, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            __hip_atomic_store(lg.hdr + LG_LAUNCHES, launch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        }
+    }
+}
+
+// The detailed log's part of a step (k_step_tally), called by every active lane after the reset and store_env, as log_append is:
+// the nine term sums are added into their accumulators (loaded here, not in the step's load burst: nine f64 held across step_env
+// do not fit the register budget) and a finisher's record gets the plain columns, the sums and the start pose (s0, s1, s2), read
+// by the kernel before the reset overwrote it.  Each sum is the f64 term added in step order, as the return is, and not contracted
+// into the products step_env forms the terms from: a sum equals the host's sum of that info.comp row.
+// The term accumulators are tiled like the hot rows, [npad / TILE][TT_LOG_NCOMP][TILE]: a lane's nine rows sit at constant offsets
+// (fewer address registers than nine rows of stride npad).
+__device__ __forceinline__ double *tally_acc(const EpLog &lg, int npad, int i) {
+    return lg.acc + npad + (size_t)(i >> 6) * (TT_LOG_NCOMP * TILE) + (i & (TILE - 1));
+}
+
+__device__ __forceinline__ void tally_append(const KParams &P, const EpLog &lg, int i, const StepOut &o, uint32_t len, double ret,
+                                             double s0, double s1, double s2) {
+#pragma clang fp contract(off)
+    double *acc = tally_acc(lg, P.npad, i);
+    double sum[TT_LOG_NCOMP];
+#pragma unroll
+    for (int c = 0; c < TT_LOG_NCOMP; ++c) sum[c] = acc[c * TILE];
+    const unsigned long long fin = __ballot(o.done);
+    const bool succ = o.done && o.final_bonus > 0.0;
+    unsigned long long slot = ~0ull;
+    if (fin) {
+        const unsigned long long base = log_reserve(lg, fin, o.done, o.flags, succ);
+        if (o.done) slot = log_slot(base, fin);
+    }
+    const double term[TT_LOG_NCOMP] = {o.c_prog, o.c_head, o.c_orient, o.staged, o.safety,
+                                       o.explore, o.final_bonus, o.back, o.c_smooth};
+#pragma unroll
+    for (int c = 0; c < TT_LOG_NCOMP; ++c) {
+        sum[c] += term[c];
+        acc[c * TILE] = o.done ? 0.0 : sum[c];
+    }
+    if (o.done && slot < lg.capacity) {
+        log_write(lg, slot, i, o.flags, succ, len, ret);
+        const TallyCols t = tally_cols(lg);
+        const size_t cap = (size_t)lg.capacity;
+#pragma unroll
+        for (int c = 0; c < TT_LOG_NCOMP; ++c) t.comp[c * cap + slot] = sum[c];
+        t.start[slot] = s0;
+        t.start[cap + slot] = s1;
+        t.start[2 * cap + slot] = s2;
+    }
+}
+
+// k_step_log with the detailed log on: the same step and the same return, launch count and exit ticket, with tally_append in
+// place of log_append.  Its own kernel for the reason k_step_log is: k_step and k_step_log keep
+// their code and their register allocation (DESIGN.md "Episode log").
+template <bool PER_ENV, bool INFO, bool AUTO_RESET, bool RANDOM_POLICY>
+__global__ __launch_bounds__(BLOCK) void k_step_tally(const KParams P, const int n, const Bufs b,
+                                                      const float *__restrict__ action, float *__restrict__ action_out,
+                                                      float *__restrict__ obs, float *__restrict__ reward,
+                                                      uint8_t *__restrict__ done, const Info info, const uint64_t seed,
+                                                      const uint64_t policy_seed, const int *__restrict__ cursor,
+                                                      const EpLog lg) {
+    __shared__ __attribute__((aligned(16))) float tile[BLOCK * OBS];
+    if (cursor) {
+        obs += (size_t)cursor[1] * n * OBS;
+        reward += (size_t)cursor[0] * n;
+        done += (size_t)cursor[0] * n;
+    }
+    const int block_first = blockIdx.x * BLOCK;
+    const int i = block_first + threadIdx.x;
+    const bool valid = i < n;
+    const int nv = min(BLOCK, n - block_first);
+    float of[OBS];
+
+    if (b.counter && i == 0) *b.counter += 1;
+    if (valid) {
+        Env e;
+        load_env<PER_ENV>(P, b, i, e);
+        float a = 0.f;
+        if (!RANDOM_POLICY) a = action[i];
+        double ret = lg.acc[i];
+        __builtin_amdgcn_sched_barrier(0);     // every load of the step in one burst (k_step)
+        if (RANDOM_POLICY) {
+            a = random_action(policy_seed, (uint32_t)i, pk_steps(e.pk), b.episodes[i]);
+            if (action_out) action_out[i] = a;
+        }
+        StepOut o;
+        step_env(P, e, a, of, o);
+        if (P.nt) {
+            __builtin_nontemporal_store((float)o.total, reward + i);
+            __builtin_nontemporal_store((uint8_t)(o.done ? 1 : 0), done + i);
+        } else {
+            reward[i] = (float)o.total;
+            done[i] = o.done ? 1 : 0;
+        }
+        if (INFO) write_info(info, (size_t)n, i, e, o);
+        ret += o.total;
+        lg.acc[i] = o.done ? 0.0 : ret;
+        const uint32_t len = pk_steps(e.pk);
+        double s0 = 0.0, s1 = 0.0, s2 = 0.0;
+        if (o.done) {           // the finished episode's start pose, before the reset places the next one (k_get_episode's rows)
+            const double *cold = b.cold + i;
+            const size_t S = (size_t)P.npad;
+            s0 = cold[C_SX * S]; s1 = cold[C_SY * S]; s2 = cold[C_SYAW * S];
+        }
+        if (AUTO_RESET && o.done) {
+            const uint32_t ep = b.episodes[i] + 1u;
+            b.episodes[i] = ep;
+            double sx, sy, syaw;
+            random_pose(P, seed, (uint32_t)i, ep, sx, sy, syaw);
+            const Goal g0{P.gx, P.gy, P.sg, P.cg};
+            place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);
+        }
+        store_env(b, i, e);
+        tally_append(P, lg, i, o, len, ret, s0, s1, s2);
+    }
+    store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
+    if (threadIdx.x == 0) {     // the launch count (k_step_log)
+        const unsigned long long launch = __hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        const unsigned long long t = atomic_add_agent(lg.hdr + LG_TICKET, 1ull);
+        if (t == gridDim.x - 1u) {
             __hip_atomic_store(lg.hdr + LG_TICKET, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             __hip_atomic_store(lg.hdr + LG_LAUNCHES, launch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
@@ -1101,6 +1253,31 @@ __global__ __launch_bounds__(BLOCK) void k_log_zero(const int n, const int k, co
     acc[i] = 0.0;
 }
 
+// k_log_zero for the detailed log: the lane's return and its nine term sums (tally_acc)
+__global__ __launch_bounds__(BLOCK) void k_tally_zero(const int n, const int k, const uint8_t *mask, const int32_t *idx,
+                                                      const EpLog lg, const int npad) {
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= k) return;
+    const int i = idx ? idx[j] : j;
+    if (i < 0 || i >= n || (mask && !mask[i])) return;
+    lg.acc[i] = 0.0;
+    double *acc = tally_acc(lg, npad, i);
+    for (int c = 0; c < TT_LOG_NCOMP; ++c) acc[c * TILE] = 0.0;
+}
+
+// the detailed columns of the first min(written, capacity) records into comp [TT_LOG_NCOMP, capacity] / start [3, capacity]
+// (either may be NULL); k_log_drain copies the plain ones
+__global__ __launch_bounds__(BLOCK) void k_tally_drain(const EpLog lg, double *comp, double *start) {
+    const unsigned long long j = (unsigned long long)blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= min(lg.hdr[LG_WRITTEN], lg.capacity)) return;
+    const TallyCols t = tally_cols(lg);
+    const size_t cap = (size_t)lg.capacity;
+    if (comp)
+        for (int c = 0; c < TT_LOG_NCOMP; ++c) comp[c * cap + j] = t.comp[c * cap + j];
+    if (start)
+        for (int c = 0; c < 3; ++c) start[c * cap + j] = t.start[c * cap + j];
+}
+
 __global__ __launch_bounds__(BLOCK) void k_log_drain(const EpLog lg, double *ret, int32_t *len, uint8_t *flags,
                                                      uint8_t *success, int32_t *lane, long long *end_step,
                                                      long long *n_out, unsigned long long *counts_out) {
@@ -1145,6 +1322,7 @@ struct tt_env {
     void *log_block = nullptr;
     size_t log_bytes = 0;
     EpLog log{};
+    uint32_t log_flags = 0;     // TT_LOG_DETAIL: the detailed log (k_step_tally)
     char err[256] = "";
 };
 
@@ -1220,7 +1398,14 @@ void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_
         e->ev_used += 1;
     }
     // hipExtLaunchKernelGGL with null events is a plain launch; with events they time this dispatch alone
-    if (e->log_bytes) {
+    if (e->log_flags & TT_LOG_DETAIL) {
+        if (auto_reset)
+            hipExtLaunchKernelGGL((k_step_tally<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
+                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
+        else
+            hipExtLaunchKernelGGL((k_step_tally<PER_ENV, INFO, false, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
+                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
+    } else if (e->log_bytes) {
         if (auto_reset)
             hipExtLaunchKernelGGL((k_step_log<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
                                   action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
@@ -1258,7 +1443,78 @@ int step_common(tt_env *env, const float *action, float *action_out, float *obs,
 }
 
 constexpr long long kLogMaxCapacity = 1ll << 28;
-size_t log_block_bytes(long long cap, int npad) { return log_records_bytes((unsigned long long)cap) + sizeof(double) * (size_t)npad; }
+// the accumulator rows of the log: the return's, and with TT_LOG_DETAIL one per reward term
+inline int log_acc_rows(uint32_t flags) { return (flags & TT_LOG_DETAIL) ? 1 + TT_LOG_NCOMP : 1; }
+size_t log_acc_offset(long long cap, uint32_t flags) {
+    return log_records_bytes((unsigned long long)cap) + ((flags & TT_LOG_DETAIL) ? tally_records_bytes((unsigned long long)cap) : 0);
+}
+size_t log_block_bytes(long long cap, int npad, uint32_t flags) {
+    return log_acc_offset(cap, flags) + sizeof(double) * (size_t)log_acc_rows(flags) * (size_t)npad;
+}
+const char *log_kind(uint64_t flags) { return (flags & TT_LOG_DETAIL) ? "detailed" : "plain"; }
+
+// a lane set starts new episodes outside the step kernel: entry j < k names lane idx[j] (idx NULL: lane j), counted where mask
+// is NULL or mask[lane] != 0
+int log_restart(tt_env *env, int k, const uint8_t *mask, const int32_t *idx, hipStream_t stream) {
+    if (env->log_flags & TT_LOG_DETAIL)
+        hipLaunchKernelGGL(k_tally_zero, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, mask, idx, env->log, env->npad);
+    else
+        hipLaunchKernelGGL(k_log_zero, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, mask, idx, env->log.acc);
+    TT_HIP(env, hipGetLastError());
+    return TT_OK;
+}
+
+int set_episode_log(tt_env *env, int64_t capacity, uint32_t flags, hipStream_t stream, const char *fn) {
+    if (capacity < 0 || capacity > kLogMaxCapacity)
+        return fail(env, TT_EINVAL, "%s: capacity %lld outside [0, %lld]", fn, (long long)capacity, kLogMaxCapacity);
+    TT_HIP(env, hipSetDevice(env->device));
+    if (env->log_block) {       // launches in flight may still write the old block
+        TT_HIP(env, hipStreamSynchronize(stream));
+        TT_HIP(env, hipDeviceSynchronize());
+        TT_HIP(env, hipFree(env->log_block));
+        env->log_block = nullptr;
+        env->log_bytes = 0;
+        env->log = EpLog{};
+        env->log_flags = 0;
+    }
+    if (capacity == 0) return TT_OK;
+    const size_t cap = (size_t)capacity, bytes = log_block_bytes(capacity, env->npad, flags);
+    void *blk = nullptr;
+    hipError_t err = hipMalloc(&blk, bytes);
+    if (err != hipSuccess)
+        return fail(env, err == hipErrorOutOfMemory ? TT_ENOMEM : TT_EHIP, "%s: %s", fn, hipGetErrorString(err));
+    EpLog lg{};
+    lg.hdr = static_cast<unsigned long long *>(blk);
+    lg.acc = reinterpret_cast<double *>(static_cast<char *>(blk) + log_acc_offset(capacity, flags));
+    lg.capacity = (unsigned long long)cap;
+    env->log_block = blk;
+    env->log_bytes = bytes;
+    env->log = lg;
+    env->log_flags = flags;
+    TT_HIP(env, hipMemsetAsync(blk, 0, bytes, stream));
+    if (flags) TT_HIP(env, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lg.hdr + LG_DETAIL), (int)flags, 1, stream));
+    return TT_OK;
+}
+
+int drain_episode_log(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, int32_t *lane, int64_t *end_step,
+                      double *comp, double *start, int64_t *n_out, uint64_t *counts_out, hipStream_t stream, const char *fn) {
+    if (!env) return fail(nullptr, TT_EINVAL, "%s: NULL handle", fn);
+    if (!env->log_bytes) return fail(env, TT_EINVAL, "%s: the episode log is off", fn);
+    if ((comp || start) && !(env->log_flags & TT_LOG_DETAIL))
+        return fail(env, TT_EINVAL, "%s: comp / start asked of a plain episode log (enable it with TT_LOG_DETAIL)", fn);
+    TT_HIP(env, hipSetDevice(env->device));
+    const dim3 g(grid_for((int)env->log.capacity));
+    hipLaunchKernelGGL(k_log_drain, g, dim3(BLOCK), 0, stream, env->log, ret, len, flags, success, lane,
+                       reinterpret_cast<long long *>(end_step), reinterpret_cast<long long *>(n_out),
+                       reinterpret_cast<unsigned long long *>(counts_out));
+    TT_HIP(env, hipGetLastError());
+    if (comp || start) {
+        hipLaunchKernelGGL(k_tally_drain, g, dim3(BLOCK), 0, stream, env->log, comp, start);
+        TT_HIP(env, hipGetLastError());
+    }
+    TT_HIP(env, hipMemsetAsync(env->log.hdr + LG_WRITTEN, 0, sizeof(unsigned long long), stream));
+    return TT_OK;
+}
 
 }  // namespace
 
@@ -1383,13 +1639,11 @@ int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out
     hipLaunchKernelGGL(k_reset, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
                        env->seed);
     TT_HIP(env, hipGetLastError());
-    if (env->log_bytes) {       // the reset lanes' episodes start from a zero return
+    if (env->log_bytes) {       // the reset lanes' episodes start from a zero return (and zero term sums)
         if (mask)
-            hipLaunchKernelGGL(k_log_zero, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->n, env->n, mask, nullptr,
-                               env->log.acc);
-        else
-            TT_HIP(env, hipMemsetAsync(env->log.acc, 0, sizeof(double) * (size_t)env->npad, stream));
-        TT_HIP(env, hipGetLastError());
+            return log_restart(env, env->n, mask, nullptr, stream);
+        TT_HIP(env, hipMemsetAsync(env->log.acc, 0, sizeof(double) * (size_t)log_acc_rows(env->log_flags) * (size_t)env->npad,
+                                   stream));
     }
     return TT_OK;
 }
@@ -1413,10 +1667,7 @@ int tt_env_set_pose(tt_env *env, const int32_t *idx, int k, const double *start,
     hipLaunchKernelGGL(k_set_pose, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, idx, k, start, goal,
                        L2, obs_out);
     TT_HIP(env, hipGetLastError());
-    if (env->log_bytes) {
-        hipLaunchKernelGGL(k_log_zero, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, nullptr, idx, env->log.acc);
-        TT_HIP(env, hipGetLastError());
-    }
+    if (env->log_bytes) return log_restart(env, k, nullptr, idx, stream);
     return TT_OK;
 }
 
@@ -1582,45 +1833,27 @@ int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stre
 
 int tt_env_set_episode_log(tt_env *env, int64_t capacity, tt_stream_t stream) {
     if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_episode_log: NULL handle");
-    if (capacity < 0 || capacity > kLogMaxCapacity)
-        return fail(env, TT_EINVAL, "tt_env_set_episode_log: capacity %lld outside [0, %lld]", (long long)capacity, kLogMaxCapacity);
-    TT_HIP(env, hipSetDevice(env->device));
-    if (env->log_block) {       // launches in flight may still write the old block
-        TT_HIP(env, hipStreamSynchronize(stream));
-        TT_HIP(env, hipDeviceSynchronize());
-        TT_HIP(env, hipFree(env->log_block));
-        env->log_block = nullptr;
-        env->log_bytes = 0;
-        env->log = EpLog{};
-    }
-    if (capacity == 0) return TT_OK;
-    const size_t cap = (size_t)capacity, bytes = log_block_bytes(capacity, env->npad);
-    void *blk = nullptr;
-    hipError_t err = hipMalloc(&blk, bytes);
-    if (err != hipSuccess)
-        return fail(env, err == hipErrorOutOfMemory ? TT_ENOMEM : TT_EHIP, "tt_env_set_episode_log: %s", hipGetErrorString(err));
-    EpLog lg{};
-    lg.hdr = static_cast<unsigned long long *>(blk);
-    lg.acc = reinterpret_cast<double *>(static_cast<char *>(blk) + log_records_bytes(cap));
-    lg.capacity = (unsigned long long)cap;
-    env->log_block = blk;
-    env->log_bytes = bytes;
-    env->log = lg;
-    TT_HIP(env, hipMemsetAsync(blk, 0, bytes, stream));
-    return TT_OK;
+    return set_episode_log(env, capacity, 0u, stream, "tt_env_set_episode_log");
+}
+
+int tt_env_set_episode_log2(tt_env *env, int64_t capacity, uint32_t flags, tt_stream_t stream) {
+    if (flags & ~(uint32_t)TT_LOG_DETAIL)
+        return fail(env, TT_EINVAL, "tt_env_set_episode_log2: unknown flag bits 0x%x", flags & ~(uint32_t)TT_LOG_DETAIL);
+    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_episode_log2: NULL handle");
+    return set_episode_log(env, capacity, flags, stream, "tt_env_set_episode_log2");
 }
 
 int tt_env_drain_episode_log(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, int32_t *lane,
                              int64_t *end_step, int64_t *n_out, uint64_t *counts_out, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_drain_episode_log: NULL handle");
-    if (!env->log_bytes) return fail(env, TT_EINVAL, "tt_env_drain_episode_log: the episode log is off");
-    TT_HIP(env, hipSetDevice(env->device));
-    hipLaunchKernelGGL(k_log_drain, dim3(grid_for((int)env->log.capacity)), dim3(BLOCK), 0, stream, env->log, ret, len, flags,
-                       success, lane, reinterpret_cast<long long *>(end_step), reinterpret_cast<long long *>(n_out),
-                       reinterpret_cast<unsigned long long *>(counts_out));
-    TT_HIP(env, hipGetLastError());
-    TT_HIP(env, hipMemsetAsync(env->log.hdr + LG_WRITTEN, 0, sizeof(unsigned long long), stream));
-    return TT_OK;
+    return drain_episode_log(env, ret, len, flags, success, lane, end_step, nullptr, nullptr, n_out, counts_out, stream,
+                             "tt_env_drain_episode_log");
+}
+
+int tt_env_drain_episode_log2(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, int32_t *lane,
+                              int64_t *end_step, double *comp, double *start, int64_t *n_out, uint64_t *counts_out,
+                              tt_stream_t stream) {
+    return drain_episode_log(env, ret, len, flags, success, lane, end_step, comp, start, n_out, counts_out, stream,
+                             "tt_env_drain_episode_log2");
 }
 
 size_t tt_env_episode_log_bytes(const tt_env *env) { return env ? env->log_bytes : 0; }
@@ -1641,6 +1874,14 @@ int tt_env_import_episode_log(tt_env *env, const void *blob, const uint64_t meta
                                     "capacity %llu (0 = off) and %d envs", (unsigned long long)meta[0],
                     (unsigned long long)meta[1], env->log.capacity, env->n);
     TT_HIP(env, hipSetDevice(env->device));
+    // the blob's own header says which kind of log wrote it (a plain blob is shorter than a detailed log's block)
+    uint64_t kind = 0;
+    TT_HIP(env, hipMemcpyAsync(&kind, static_cast<const unsigned long long *>(blob) + LG_DETAIL, sizeof(kind),
+                               hipMemcpyDeviceToHost, stream));
+    TT_HIP(env, hipStreamSynchronize(stream));
+    if (kind != env->log_flags)
+        return fail(env, TT_EINVAL, "tt_env_import_episode_log: the blob is of a %s episode log, the handle's log is %s",
+                    log_kind(kind), log_kind(env->log_flags));
     TT_HIP(env, hipMemcpyAsync(env->log_block, blob, env->log_bytes, hipMemcpyDeviceToDevice, stream));
     return TT_OK;
 }

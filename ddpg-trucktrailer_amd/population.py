@@ -112,7 +112,7 @@ class PopulationRollout:
 
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
-                 pipeline=None, side_buffer=None):
+                 pipeline=None, side_buffer=None, episode_log_detail=False):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
         if data_parallel or pipeline or side_buffer is not None:
             raise ValueError("populations run the serial order on one GPU without expert side buffers (data-parallel populations, "
@@ -132,7 +132,8 @@ class PopulationRollout:
             # a lone serial-order loop whose own learner is not made: its learn() runs in the population's launches
             lp = DDPGRollout(env, batch_size=self.batch_size, replay_slots=replay_slots, seed=self.seeds[a], alpha=alphas[a],
                              beta=betas[a], tau=taus[a], gamma=gammas[a], fused_learn=False, graph_steps=0,
-                             updates_per_step=self.updates_per_step, pipeline=False, episode_log=episode_log)
+                             updates_per_step=self.updates_per_step, pipeline=False, episode_log=episode_log,
+                             episode_log_detail=episode_log_detail)
             if not lp.ring_mode:
                 raise RuntimeError("a population needs the fused policy and ring-addressed steps (reference-shaped actor on a GPU)")
             self.loops.append(lp)

@@ -72,7 +72,7 @@ class DDPGRollout:
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99,
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
-                 policy_capped_grids=4, dp_exchange=None, episode_log=None):
+                 policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -88,10 +88,11 @@ class DDPGRollout:
         group at world size 1.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
         before any step or capture: every episode that ends in the loop is logged by the env step kernel, with end_step = the
-        loop's vector step; drain_episodes() collects the records."""
+        loop's vector step; drain_episodes() collects the records.  episode_log_detail: the detailed log (each record also
+        carries its episode's sum of every reward term and its start pose; episode_metrics.py reads them)."""
         self.env, self.n, self.device = env, env.n_envs, env.device
         if episode_log:
-            env.enable_episode_log(int(episode_log))
+            env.enable_episode_log(int(episode_log), detail=episode_log_detail)
         self.batch_size = batch_size
         self.updates_per_step = int(updates_per_step)
         assert self.updates_per_step >= 1

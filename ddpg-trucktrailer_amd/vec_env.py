@@ -249,21 +249,33 @@ class TruckTrailerVecEnv:
         """Records the episode log holds between drains (0: the log is off)."""
         return getattr(self, "_log_capacity", 0)
 
-    def enable_episode_log(self, capacity=65536):
+    @property
+    def episode_log_detail(self):
+        """True when the episode log is on with its per-term sums and start poses (enable_episode_log(detail=True))."""
+        return bool(self.episode_log_capacity) and getattr(self, "_log_detail", False)
+
+    def enable_episode_log(self, capacity=65536, detail=False):
         """Turn on the episode log (include/ttenv.h: tt_env_set_episode_log): from the next step on, every env that
         finishes an episode appends its f64 return, length, termination flags, success (final_success_bonus > 0, the
-        trainv2.py test), lane and end step, and exact counters by outcome are kept; drain_episodes() collects them.  A
-        fresh log each call.  Captured step graphs are re-captured (graph_epoch)."""
+        trainv2.py test), lane and end step, and exact counters by outcome are kept; drain_episodes() collects them.
+        detail=True (tt_env_set_episode_log2, TT_LOG_DETAIL) adds to every record the episode's sum of each reward term
+        (L.LOG_COMPONENTS) and its start pose.  A fresh log each call.  Captured step graphs are re-captured (graph_epoch)."""
         capacity = int(capacity)
         if capacity <= 0:
             raise ValueError("capacity must be positive (disable_episode_log() turns the log off)")
-        self._check(self.lib.tt_env_set_episode_log(self._h, capacity, self._stream()))
+        detail = bool(detail)
+        self._check(self.lib.tt_env_set_episode_log2(self._h, capacity, L.LOG_DETAIL if detail else 0, self._stream()))
         self._log_capacity = capacity
+        self._log_detail = detail
         self.graph_epoch += 1
         with torch.cuda.device(self.device):
             z = lambda dt: torch.zeros(capacity, dtype=dt, device=self.device)
             self._log_out = dict(ret=z(torch.float64), len=z(torch.int32), flags=z(torch.uint8), success=z(torch.uint8),
                                  lane=z(torch.int32), end_step=z(torch.int64))
+            if detail:
+                self._log_detail_out = dict(components=torch.zeros((len(L.LOG_COMPONENTS), capacity), dtype=torch.float64,
+                                                                   device=self.device),
+                                            start=torch.zeros((3, capacity), dtype=torch.float64, device=self.device))
             self._log_n = torch.zeros(1, dtype=torch.int64, device=self.device)
             self._log_counts = torch.zeros(len(L.LOG_COUNTS), dtype=torch.int64, device=self.device)
 
@@ -272,7 +284,8 @@ class TruckTrailerVecEnv:
         if self.episode_log_capacity:
             self._check(self.lib.tt_env_set_episode_log(self._h, 0, self._stream()))
         self._log_capacity = 0
-        self._log_out = None
+        self._log_detail = False
+        self._log_out = self._log_detail_out = None
         self.graph_epoch += 1
 
     def drain_episodes(self):
@@ -280,18 +293,24 @@ class TruckTrailerVecEnv:
         atomics --, as device tensors: ret f64, len i32, flags u8, success bool, lane i32, end_step i64; plus `counts`
         ({name: int}, cumulative since enable, include/ttenv.h TT_LOG_NCOUNTS order), `written` (records appended since the
         last drain) and `dropped` (those of them past the capacity, not stored).  end_step counts the logging step launches
-        since enable_episode_log (in a DDPGRollout that enables it at construction: the vector step)."""
+        since enable_episode_log (in a DDPGRollout that enables it at construction: the vector step).  A detailed log adds
+        `components` [m, 9] f64 (the episode's sum of each reward term, columns L.LOG_COMPONENTS) and `start` [m, 3] f64 (its
+        start pose x, y, yaw), in the same order."""
         if not self.episode_log_capacity:
             raise RuntimeError("the episode log is off (enable_episode_log)")
         o = self._log_out
-        self._check(self.lib.tt_env_drain_episode_log(self._h, _ptr(o["ret"]), _ptr(o["len"]), _ptr(o["flags"]),
-                                                      _ptr(o["success"]), _ptr(o["lane"]), _ptr(o["end_step"]),
-                                                      _ptr(self._log_n), _ptr(self._log_counts), self._stream()))
+        d = self._log_detail_out if self.episode_log_detail else None
+        self._check(self.lib.tt_env_drain_episode_log2(self._h, _ptr(o["ret"]), _ptr(o["len"]), _ptr(o["flags"]),
+                                                       _ptr(o["success"]), _ptr(o["lane"]), _ptr(o["end_step"]),
+                                                       _ptr(d["components"]) if d else None, _ptr(d["start"]) if d else None,
+                                                       _ptr(self._log_n), _ptr(self._log_counts), self._stream()))
         written = int(self._log_n.item())                 # (synchronises this stream)
         m = min(written, self.episode_log_capacity)
         key = o["end_step"][:m] * self.n_envs + o["lane"][:m].long()      # unique: one record per lane per launch
         order = torch.argsort(key)
         out = {k: v[:m][order] for k, v in o.items()}
+        if d:
+            out.update({k: v[:, :m].t()[order] for k, v in d.items()})
         out["success"] = out["success"].bool()
         out["counts"] = dict(zip(L.LOG_COUNTS, (int(x) for x in self._log_counts.tolist())))
         out["written"], out["dropped"] = written, written - m
@@ -302,11 +321,11 @@ class TruckTrailerVecEnv:
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 2)()
         self._check(self.lib.tt_env_export_episode_log(self._h, _ptr(blob), C.byref(meta), self._stream()))
-        return {"blob": blob.cpu(), "meta": [int(x) for x in meta]}
+        return {"blob": blob.cpu(), "meta": [int(x) for x in meta], "detail": self.episode_log_detail}
 
     def _load_episode_log_state(self, sd):
         cap = int(sd["meta"][0])
-        self.enable_episode_log(cap)
+        self.enable_episode_log(cap, detail=sd.get("detail", False))
         blob = sd["blob"].to(self.device)
         meta = (C.c_uint64 * 2)(*sd["meta"])
         self._check(self.lib.tt_env_import_episode_log(self._h, _ptr(blob), C.byref(meta), self._stream()))

@@ -246,6 +246,29 @@ size_t tt_env_episode_log_bytes(const tt_env *env);
 int tt_env_export_episode_log(tt_env *env, void *blob, uint64_t meta[2], tt_stream_t stream);
 int tt_env_import_episode_log(tt_env *env, const void *blob, const uint64_t meta[2], tt_stream_t stream);
 
+/* Detailed episode log (what DDPG/viz_how_agent_learn.py and pareto_analysis.py read of every episode: its reward by term, and
+ * trainv2.py's env_data start pose).  tt_env_set_episode_log2(env, capacity, flags, stream) with flags = 0 is exactly
+ * tt_env_set_episode_log; with TT_LOG_DETAIL the step launches the detailed form of the logging kernel, and every record also
+ * carries
+ *     comp f64 [TT_LOG_NCOMP]   the episode's sum of each reward term, rows TT_I_PROGRESS .. TT_I_SMOOTH of tt_info.comp in
+ *                               that order (progress, heading, orientation, staged, safety, exploration, final bonus, backward,
+ *                               smoothness), each added in step order in f64 as the return is: bit for bit the host's sum
+ *                               of that comp row over the episode
+ *     start f64 [3]             the start pose (x, y, yaw) tt_env_get_episode reported for the lane during the episode (with
+ *                               auto-reset: the finished episode's, not the one the same step places)
+ * The term sums restart where the return does.  The plain records, counters and their semantics are unchanged.  Unknown
+ * flag bits are TT_EINVAL.  The log's block (tt_env_episode_log_bytes) grows by 96 B per record and 72 B per env; its
+ * header records the flags, and tt_env_import_episode_log refuses (TT_EINVAL) a blob of the other kind of log. */
+#define TT_LOG_DETAIL 1
+#define TT_LOG_NCOMP 9
+int tt_env_set_episode_log2(tt_env *env, int64_t capacity, uint32_t flags, tt_stream_t stream);
+/* tt_env_drain_episode_log plus the detailed columns: comp [TT_LOG_NCOMP, capacity] f64 (row = term) and start [3, capacity]
+ * f64 (rows x, y, yaw), same record order as the plain columns; either may be NULL.  TT_EINVAL when comp or start is asked of
+ * a plain log. */
+int tt_env_drain_episode_log2(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, int32_t *lane,
+                              int64_t *end_step, double *comp, double *start, int64_t *n_out, uint64_t *counts_out,
+                              tt_stream_t stream);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */

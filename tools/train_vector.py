@@ -3,13 +3,20 @@
 and length of the episodes that ended in it and how many succeeded, read from the env step kernel's episode log (f64
 returns, the reference's success test final_success_bonus > 0: trainv2.py:541), with trainv2.py's 100-episode average,
 success rate and "best" decisions (checkpoint.BestModelTracker).  The loop runs whole-step graphs of `graph_steps`.
-Usage: train_vector.py n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+--objectives: the detailed episode log, and each line adds the 100-episode averages of viz_how_agent_learn.py's four objectives
+(efficiency, smoothness, precision, safety; episode_metrics.py).
+Usage: train_vector.py [--objectives] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
 from ddpg_trucktrailer_amd.rollout import DDPGRollout
 from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
 
+detail = "--objectives" in sys.argv[1:]
+if detail:
+    sys.argv.remove("--objectives")
+    from ddpg_trucktrailer_amd.episode_metrics import RunningObjectives
+    running = RunningObjectives()
 n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:7])
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 27
 graph_steps = int(sys.argv[8]) if len(sys.argv) > 8 else (20 if slots <= 1024 else 0)      # (as before: no graphs past 1024 slots)
@@ -17,7 +24,7 @@ env = TruckTrailerVecEnv(n)
 env.reset(seed=seed)
 # the log holds a report block's episodes: at most one per env and step
 loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates_per_step=upd, graph_steps=graph_steps,
-                   episode_log=min(n * every, 1 << 24))
+                   episode_log=min(n * every, 1 << 24), episode_log_detail=detail)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}", flush=True)
 tracker = BestModelTracker()
@@ -34,8 +41,12 @@ while s < total:
     episodes += m
     e = max(1, m)
     lost = f"  ({r['dropped']} records past the log's capacity)" if r["dropped"] else ""
+    objs = ""
+    if detail:                 # viz_how_agent_learn.py's objectives, 100-episode averages
+        running.update(r)
+        objs = "  " + "  ".join(f"{k[:4]}100 {v if v is not None else float('nan'):8.1f}" for k, v in running.last().items())
     print(f"vector steps {s:7d} ({s * n:.2e} env-steps, {int(loop.learner.step_dev.item())} updates): episodes {m:7d}  "
           f"mean length {r['len'].double().sum().item() / e:6.1f}  mean return {r['ret'].sum().item() / e:9.1f}  "
           f"successes {int(r['success'].sum().item()):6d} ({100 * r['success'].double().sum().item() / e:4.1f} %)  "
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
-          f"best x{len(best)}{lost}  {time.time() - t0:.0f}s", flush=True)
+          f"best x{len(best)}{objs}{lost}  {time.time() - t0:.0f}s", flush=True)
