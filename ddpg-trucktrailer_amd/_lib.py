@@ -107,6 +107,11 @@ class TTPopAgent(C.Structure):
                 ("gave_up_host", C.c_void_p)]
 
 
+class TTPopExploitPair(C.Structure):
+    _fields_ = [("dst", C.c_int32), ("src", C.c_int32), ("alpha", C.c_float), ("beta", C.c_float), ("tau", C.c_float),
+                ("gamma", C.c_float)]
+
+
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 
 
@@ -190,6 +195,8 @@ _SIGNATURES = {
     "tt_pop_learn_create": (C.c_int, [_I, _I, C.POINTER(TTPopAgent), C.POINTER(_P)]),
     "tt_pop_learn": (C.c_int, [_P, _I, _P]),
     "tt_pop_learn_destroy": (C.c_int, [_P]),
+    "tt_pop_exploit": (C.c_int, [_P, _I, C.POINTER(TTPopExploitPair), _P]),
+    "tt_pop_hyper": (C.c_int, [_P, _I, C.POINTER(C.c_float * 4)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

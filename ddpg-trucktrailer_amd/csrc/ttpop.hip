@@ -10,6 +10,8 @@
 //   k_pop_bwd_weights<false>   k_bwd_weights<false> on the critic: gradients + Adam + soft update + fc2 image patch
 //   k_pop_actor_tail           k_actor_tail: Q(s, mu(s)) and dQ/da rows, then the actor's weight gradients + Adam
 //
+// and, off the learn() path, k_pop_exploit (tt_pop_exploit): population-based training's exploit/explore step between vector steps.
+//
 // So each agent's results are the bits of its lone learn() (tests/test_gpu_population.py).  Per-agent arguments live in device
 // memory (PopAgent), filled once at tt_pop_learn_create: a launch takes (K, B, descriptors, u) and is graph-capturable.
 // The descriptors are read through the CONSTANT address space, as kernel arguments are: the bodies index the Adam tables with a
@@ -17,6 +19,7 @@
 // compiler may issue as early as it likes (nothing in a launch writes them).
 #include "ttlearn_bodies.h"
 
+#include <cmath>
 #include <cstdio>
 #include <vector>
 
@@ -160,6 +163,104 @@ __global__ __launch_bounds__(64 * NW) void k_pop_actor_tail(const int K, const i
                                  part, lds + 4 * 4 * 256, P.ts, epoch, reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB));
 }
 
+// ---- PBT exploit/explore (tt_pop_exploit): dst's learning state <- src's, then dst's hyperparameters, in one launch ----
+// A pair's copy is 92 regions: per network (critic 12 tensors, then actor 10) and tensor t, its parameters, Adam m, Adam v and
+// target parameters (4 t + {0, 1, 2, 3}), then the four fc2 images (critic net / target, actor net / target).  Each region is cut
+// into EX_CHUNK-byte pieces, one workgroup each; the shapes are the bodies' (23-400-300-1), so the pieces per pair are constants.
+// Nothing else is copied: dst's env, ring, noise, step_dev, bias corrections, tail words and scratch buffers stay its own.
+struct ExploitList {
+    int n;
+    tt_pop_exploit_pair p[TT_POP_MAX_AGENTS];
+};
+
+constexpr int EX_THREADS = 256, EX_UNROLL = 4;
+constexpr size_t EX_CHUNK = (size_t)EX_THREADS * EX_UNROLL * 16;        // bytes per workgroup: 16 KB
+constexpr int EX_TENSOR_REGIONS = 4 * (12 + 10), EX_REGIONS = EX_TENSOR_REGIONS + 4;
+
+__host__ __device__ constexpr int ex_numel(const int t) {                // tensor t of tt_mlp_weights' order
+    return t == 0 ? H1 * IN : t < 4 ? H1 : t == 4 ? H2 * H1 : t < 9 ? H2 : t == 9 ? 1 : H2;
+}
+__host__ __device__ constexpr size_t ex_region_bytes(const int r) {
+    return r < EX_TENSOR_REGIONS ? (size_t)ex_numel((r < 48 ? r : r - 48) >> 2) * 4 : IMG_HALVES * 2;
+}
+__host__ __device__ constexpr int ex_region_chunks(const int r) { return (int)((ex_region_bytes(r) + EX_CHUNK - 1) / EX_CHUNK); }
+constexpr int ex_chunks_per_pair() {
+    int s = 0;
+    for (int r = 0; r < EX_REGIONS; ++r) s += ex_region_chunks(r);
+    return s;
+}
+constexpr int EX_CHUNKS = ex_chunks_per_pair();
+
+__device__ __forceinline__ float *ex_tensor(const AdamFused &A, const int kind, const int t) {
+    return kind == 0 ? A.p[t] : kind == 1 ? A.m[t] : kind == 2 ? A.v[t] : A.tgt[t];
+}
+
+// grid: pairs x EX_CHUNKS, pair-major.  No pair's dst is another pair's src (tt_pop_exploit checks), so every byte a workgroup reads
+// is written by no workgroup of the launch.  The descriptors' pointers are read, never written; the hyperparameter words are written
+// with plain global stores and read by the later launches on the stream (the same contract as the copy at tt_pop_learn_create).
+__global__ __launch_bounds__(EX_THREADS) void k_pop_exploit(const ExploitList L, PopAgent *__restrict__ D) {
+    const int pair = (int)blockIdx.x / EX_CHUNKS, piece = (int)blockIdx.x - pair * EX_CHUNKS;
+    if (pair >= L.n) return;
+    const tt_pop_exploit_pair q = L.p[pair];
+    if (piece == 0 && threadIdx.x == 0) {
+        PopAgent &W = D[q.dst];
+        W.Aa.lr = q.alpha;
+        W.Ac.lr = q.beta;
+        W.Aa.tau = q.tau;
+        W.Ac.tau = q.tau;
+        W.td.gamma = q.gamma;
+    }
+    if (q.dst == q.src) return;
+    int r = 0, c = piece;
+    while (r < EX_REGIONS - 1 && c >= ex_region_chunks(r)) c -= ex_region_chunks(r++);
+    const PopAgent &S = agent_of(D, q.src), &T = agent_of(D, q.dst);
+    const char *from;
+    char *to;
+    if (r < EX_TENSOR_REGIONS) {
+        const bool actor = r >= 48;
+        const int local = actor ? r - 48 : r, t = local >> 2, kind = local & 3;
+        from = reinterpret_cast<const char *>(ex_tensor(actor ? S.Aa : S.Ac, kind, t));
+        to = reinterpret_cast<char *>(ex_tensor(actor ? T.Aa : T.Ac, kind, t));
+    } else {
+        const int i = r - EX_TENSOR_REGIONS;
+        const AdamFused &As = i < 2 ? S.Ac : S.Aa, &At = i < 2 ? T.Ac : T.Aa;
+        from = reinterpret_cast<const char *>((i & 1) ? As.img_t : As.img_p);
+        to = reinterpret_cast<char *>((i & 1) ? At.img_t : At.img_p);
+    }
+    if (!from || !to) return;                      // (images off)
+    const size_t bytes = ex_region_bytes(r), lo = (size_t)c * EX_CHUNK, hi = min(bytes, lo + EX_CHUNK);
+    const int tid = threadIdx.x;
+    const size_t mis = reinterpret_cast<uintptr_t>(to) & 15;
+    if (mis != (reinterpret_cast<uintptr_t>(from) & 15)) {         // no common 16-byte alignment: dwords
+        for (size_t o = lo + 4 * tid; o < hi; o += 4 * EX_THREADS)
+            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
+        return;
+    }
+    // 16-byte accesses over [head, head + body) of the region (head: the dwords before the first 16-byte boundary), dwords around
+    const size_t head = (16 - mis) & 15, body = bytes >= head ? (bytes - head) & ~(size_t)15 : 0;
+    if (c == 0) {
+        const size_t tail0 = head + body;
+        for (size_t o = 4 * tid; o < min(head, bytes); o += 4 * EX_THREADS)
+            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
+        for (size_t o = tail0 + 4 * tid; o < bytes; o += 4 * EX_THREADS)
+            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
+    }
+    const f32x4 *src4 = reinterpret_cast<const f32x4 *>(from + head);
+    f32x4 *dst4 = reinterpret_cast<f32x4 *>(to + head);
+    const size_t v_lo = lo / 16, v_hi = min(body, hi) / 16;
+    f32x4 x[EX_UNROLL];
+#pragma unroll
+    for (int u = 0; u < EX_UNROLL; ++u) {
+        const size_t i = v_lo + (size_t)u * EX_THREADS + tid;
+        if (i < v_hi) x[u] = src4[i];
+    }
+#pragma unroll
+    for (int u = 0; u < EX_UNROLL; ++u) {
+        const size_t i = v_lo + (size_t)u * EX_THREADS + tid;
+        if (i < v_hi) dst4[i] = x[u];
+    }
+}
+
 char g_why[256];
 
 int einval(const char *fmt, int a = 0, int b = 0) {
@@ -263,6 +364,49 @@ int tt_pop_learn(tt_population *h, int update, tt_stream_t stream) {
     hipLaunchKernelGGL(k_pop_bwd_weights<false>, dim3(K * WG_CRITIC_WEIGHTS), dim3(256), 0, stream, K, n, h->dev);
     hipLaunchKernelGGL(k_pop_actor_tail, dim3(K * (nb + WG_ACTOR_WEIGHTS)), dim3(64 * NW), 0, stream, K, n, h->dev);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_exploit(tt_population *h, int pairs, const tt_pop_exploit_pair *list, tt_stream_t stream) {
+    if (!h) return einval("tt_pop_exploit: handle is NULL");
+    if (!list) return einval("tt_pop_exploit: list is NULL");
+    const int K = h->K;
+    if (pairs < 1 || pairs > K) return einval("tt_pop_exploit: pairs = %d, not in [1, K = %d]", pairs, K);
+    ExploitList L{};
+    L.n = pairs;
+    for (int i = 0; i < pairs; ++i) {
+        const tt_pop_exploit_pair &q = list[i];
+        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K)
+            return einval("tt_pop_exploit: pair %d names an agent outside [0, K = %d)", i, K);
+        for (int j = 0; j < pairs; ++j) {
+            if (j == i) continue;
+            if (list[j].dst == q.dst) return einval("tt_pop_exploit: pairs %d and %d have the same dst", i, j);
+            if (list[j].src == q.dst) return einval("tt_pop_exploit: the dst of pair %d is the src of pair %d", i, j);
+        }
+        const float h4[4] = {q.alpha, q.beta, q.tau, q.gamma};
+        for (const float x : h4)
+            if (!std::isfinite(x)) return einval("tt_pop_exploit: pair %d has a non-finite hyperparameter", i);
+        if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
+            return einval("tt_pop_exploit: pair %d: alpha and beta must lie in (0, 1]", i);
+        if (!(q.tau > 0.f && q.tau <= 1.f)) return einval("tt_pop_exploit: pair %d: tau must lie in (0, 1]", i);
+        if (!(q.gamma > 0.f && q.gamma < 1.f)) return einval("tt_pop_exploit: pair %d: gamma must lie in (0, 1)", i);
+        L.p[i] = q;
+    }
+    hipLaunchKernelGGL(k_pop_exploit, dim3(pairs * EX_CHUNKS), dim3(EX_THREADS), 0, stream, L, h->dev);
+    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
+    if (!h) return einval("tt_pop_hyper: handle is NULL");
+    if (!out) return einval("tt_pop_hyper: out is NULL");
+    if (agent < 0 || agent >= h->K) return einval("tt_pop_hyper: agent %d is not in [0, K = %d)", agent, h->K);
+    PopAgent P;
+    if (hipMemcpy(&P, h->dev + agent, sizeof P, hipMemcpyDeviceToHost) != hipSuccess)
+        return tthost::fail_library(TT_EHIP, "tt_pop_hyper: hipMemcpy");
+    out[0] = P.Aa.lr;
+    out[1] = P.Ac.lr;
+    out[2] = P.Aa.tau;
+    out[3] = P.td.gamma;
+    return TT_OK;
 }
 
 int tt_pop_learn_destroy(tt_population *h) {

@@ -1,0 +1,139 @@
+"""Population-based training (PBT; Jaderberg et al., 2017) for a PopulationRollout: a host-side controller that, every `ready`
+vector steps, ranks the agents by their recent episodes, lets the worst take a copy of a better agent's networks and optimizer
+state ("exploit") and perturbs the hyperparameters they inherit ("explore").  The copy is one launch on the device
+(PopulationRollout.exploit, include/ttenv.h: tt_pop_exploit); everything here is host logic on drained episode records.
+
+    pbt = PBT(K, ready=200)
+    ...
+    pop.run(k)
+    decisions = pbt.step(pop, pop.drain_episodes())
+
+Rules:
+  - per agent, the last `window` episodes that ENDED since that agent's last exploit (or since the start) count;
+  - a round is due once `ready` vector steps have passed since the last round; it needs two or more eligible agents (>= min_episodes
+    such episodes, default `window`) -- otherwise it is tried again at the next call;
+  - ranking: "return" = mean return; "success" = success rate, then mean return (checkpoint.BestModelTracker's order); ties go to
+    the lower agent index;
+  - truncation selection: m = min(max(1, floor(quantile * E)), E // 2) of the E eligible agents; each of the bottom m (worst
+    first) takes a src drawn uniformly from the top m with the controller's own np.random.RandomState(seed);
+  - explore: each hyperparameter in `explore` takes a factor drawn from `factors` (in the order alpha, beta, tau, gamma): alpha,
+    beta and tau are multiplied by it, gamma is perturbed in 1 - gamma space (1 - gamma' = f (1 - gamma)); each value is clamped
+    to `bounds`; the others are src's unchanged.  dst's window is cleared."""
+import collections
+import math
+
+import numpy as np
+
+HYPERS = ("alpha", "beta", "tau", "gamma")
+BOUNDS = {"alpha": (1e-6, 1e-2), "beta": (1e-6, 1e-1), "tau": (1e-5, 1e-1), "gamma": (0.9, 0.9999)}
+METRICS = ("return", "success")
+
+
+class PBT:
+    def __init__(self, K, ready, seed=0, quantile=0.25, metric="return", window=100, min_episodes=None, explore=HYPERS,
+                 factors=(0.8, 1.2), bounds=None):
+        self.K, self.ready = int(K), int(ready)
+        if self.K < 1 or self.ready < 1:
+            raise ValueError(f"PBT: K = {K} and ready = {ready} must be >= 1")
+        if metric not in METRICS:
+            raise ValueError(f"PBT: metric {metric!r} is not one of {METRICS}")
+        if not 0.0 < float(quantile) <= 0.5:
+            raise ValueError(f"PBT: quantile = {quantile} is not in (0, 0.5]")
+        bad = [h for h in explore if h not in HYPERS]
+        if bad:
+            raise ValueError(f"PBT: cannot explore {bad} (only {HYPERS})")
+        self.quantile, self.metric, self.window = float(quantile), metric, int(window)
+        self.min_episodes = self.window if min_episodes is None else int(min_episodes)
+        if self.window < 1 or not 1 <= self.min_episodes <= self.window:
+            raise ValueError(f"PBT: window = {window}, min_episodes = {min_episodes}: need 1 <= min_episodes <= window")
+        self.explore = tuple(h for h in HYPERS if h in explore)
+        self.factors = tuple(float(f) for f in factors)
+        if not self.factors or any(not f > 0.0 for f in self.factors):
+            raise ValueError(f"PBT: factors {factors} must be positive")
+        self.bounds = dict(BOUNDS)
+        self.bounds.update(bounds or {})
+        self.rng = np.random.RandomState(seed)
+        self.windows = [collections.deque(maxlen=self.window) for _ in range(self.K)]
+        self.last_round = 0
+        self.history = []
+
+    # ------------------------------------------------------------------------------------------------- episodes
+    def observe(self, drained):
+        """drained: PopulationRollout.drain_episodes() -- per agent a dict with "ret" and "success" tensors (or sequences)."""
+        if len(drained) != self.K:
+            raise ValueError(f"PBT.observe: {len(drained)} records for {self.K} agents")
+        for w, r in zip(self.windows, drained):
+            ret, ok = _host(r["ret"]), _host(r["success"])
+            if len(ret) != len(ok):
+                raise ValueError("PBT.observe: ret and success differ in length")
+            w.extend((float(x), bool(s)) for x, s in zip(ret, ok))
+
+    def score(self, a):
+        """Agent a's ranking key over its window (larger is better), or None while it has fewer than min_episodes episodes."""
+        w = self.windows[a]
+        if len(w) < self.min_episodes:
+            return None
+        mean = sum(x for x, _ in w) / len(w)
+        if self.metric == "return":
+            return (mean,)
+        return (sum(1 for _, s in w if s) / len(w), mean)
+
+    # ------------------------------------------------------------------------------------------------- a round
+    def decide(self, vector_step, hypers):
+        """hypers: per agent {"alpha", "beta", "tau", "gamma"} as they are now.  Returns the round's decisions (possibly none):
+        [{"step", "dst", "src", "dst_score", "src_score", "old", "new"}] -- "new" is what dst takes."""
+        if len(hypers) != self.K:
+            raise ValueError(f"PBT.decide: {len(hypers)} hyperparameter sets for {self.K} agents")
+        if vector_step - self.last_round < self.ready:
+            return []
+        scores = {a: s for a in range(self.K) for s in (self.score(a),) if s is not None}
+        E = len(scores)
+        if E < 2:
+            return []                  # (tried again at the next call)
+        # best first; ties: the lower index ranks higher
+        ranked = sorted(scores, key=lambda a: tuple(-x for x in scores[a]) + (a,))
+        m = min(max(1, int(math.floor(self.quantile * E))), E // 2)
+        top, bottom = ranked[:m], ranked[E - m:][::-1]
+        out = []
+        for dst in bottom:
+            src = top[self.rng.randint(m)]
+            new = {k: float(hypers[src][k]) for k in HYPERS}
+            for k in self.explore:
+                f = self.factors[self.rng.randint(len(self.factors))]
+                x = 1.0 - (1.0 - new[k]) * f if k == "gamma" else new[k] * f
+                lo, hi = self.bounds[k]
+                new[k] = min(max(x, lo), hi)
+            out.append({"step": int(vector_step), "dst": dst, "src": src, "dst_score": scores[dst], "src_score": scores[src],
+                        "old": {k: float(hypers[dst][k]) for k in HYPERS}, "new": new})
+            self.windows[dst].clear()
+        self.last_round = int(vector_step)
+        self.history.extend(out)
+        return out
+
+    def step(self, pop, drained):
+        """observe(drained), decide at pop.vector_steps, and apply the decisions with one pop.exploit launch."""
+        self.observe(drained)
+        hypers = [{k: float(getattr(ag, k)) for k in HYPERS} for ag in pop.agents]
+        out = self.decide(pop.vector_steps, hypers)
+        if out:
+            pop.exploit([(d["dst"], d["src"], d["new"]) for d in out])
+        return out
+
+    # ------------------------------------------------------------------------------------------------- checkpoint
+    def state_dict(self):
+        return {"rng": self.rng.get_state(), "windows": [list(w) for w in self.windows], "last_round": self.last_round,
+                "history": [dict(d) for d in self.history]}
+
+    def load_state_dict(self, sd):
+        if len(sd["windows"]) != self.K:
+            raise ValueError(f"PBT.load_state_dict: {len(sd['windows'])} windows for {self.K} agents")
+        self.rng.set_state(sd["rng"])
+        self.windows = [collections.deque(w, maxlen=self.window) for w in sd["windows"]]
+        self.last_round = int(sd["last_round"])
+        self.history = [dict(d) for d in sd["history"]]
+
+
+def _host(x):
+    if hasattr(x, "detach"):
+        return x.detach().cpu().tolist()
+    return list(x)

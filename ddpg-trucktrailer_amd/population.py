@@ -6,6 +6,9 @@ population update is four launches (csrc/ttpop.hip) that run every agent's workg
 lone loop with the actor tail in one launch (TT_ACTOR_TAIL=1).  Seeds, learning rates, tau and gamma are per agent; the network
 shape (23-400-300-1) and the batch size B are shared.
 
+exploit() is population-based training's exploit/explore step (pbt.py decides it): between vector steps one launch copies an
+agent's networks, Adam moments and fc2 images over another's and sets new hyperparameters in the descriptors, in place.
+
 Out of scope: the pipelined order, data-parallel populations, expert side buffers, whole-population checkpoints (an agent's
 weights save through agents[a].save_models())."""
 import ctypes as C
@@ -94,6 +97,47 @@ class PopulationLearner:
     def state_dict(self, a):
         """Agent a's Adam moments and step count, in FusedLearner.state_dict()'s format."""
         return self.learners[a].state_dict()
+
+    def exploit(self, pairs):
+        """Population-based training's exploit/explore step (include/ttenv.h: tt_pop_exploit), one launch on the current stream:
+        pairs = [(dst, src, {"alpha", "beta", "tau", "gamma"})].  dst != src: dst's four networks, Adam moments and fc2 images
+        become src's; every dst then takes the given hyperparameters (a missing key: src's value).  The host mirrors --
+        agent.alpha / beta / tau / gamma, the torch optimizers' lr, FusedLearner.hyp_actor / hyp_critic -- follow, so a checkpoint
+        or a later _create sees the new values.  Captured launches stay valid: the descriptors change in place."""
+        if self._h is None:
+            raise RuntimeError("PopulationLearner.exploit: no learn() has made the population's descriptors yet")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("PopulationLearner.exploit: not while capturing (it runs between vector steps)")
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= self.K:
+            raise ValueError(f"exploit: 1 to {self.K} pairs, not {len(pairs)}")
+        self.refresh_images()          # (src's images must hold its weights: they are copied with them)
+        arr = (L.TTPopExploitPair * len(pairs))()
+        new = []
+        for i, (dst, src, hyp) in enumerate(pairs):
+            dst, src = int(dst), int(src)
+            if not (0 <= dst < self.K and 0 <= src < self.K):
+                raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
+            h = {k: float(hyp.get(k, getattr(self.agents[src], k))) for k in ("alpha", "beta", "tau", "gamma")}
+            arr[i] = L.TTPopExploitPair(dst, src, h["alpha"], h["beta"], h["tau"], h["gamma"])
+            new.append((dst, h))
+        L.check(self.lib.tt_pop_exploit(self._h, len(pairs), arr, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        for dst, h in new:
+            ag, fl = self.agents[dst], self.learners[dst]
+            ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
+            ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
+            ag.critic.optimizer.param_groups[0]["lr"] = h["beta"]
+            fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
+            fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
+
+    def hyper(self, a):
+        """Agent a's {"alpha", "beta", "tau", "gamma"} as the device descriptors hold them (synchronises)."""
+        if self._h is None:
+            raise RuntimeError("PopulationLearner.hyper: no learn() has made the population's descriptors yet")
+        out = (C.c_float * 4)()
+        torch.cuda.synchronize()
+        L.check(self.lib.tt_pop_hyper(self._h, int(a), C.byref(out)))
+        return dict(zip(("alpha", "beta", "tau", "gamma"), (float(x) for x in out)))
 
 
 def _per_agent(x, K, name):
@@ -231,3 +275,12 @@ class PopulationRollout:
     def drain_episodes(self):
         """[agent: its env's episode log since the last drain (DDPGRollout.drain_episodes)]."""
         return [lp.drain_episodes() for lp in self.loops]
+
+    def exploit(self, pairs):
+        """PBT's exploit/explore step between vector steps, eagerly (PopulationLearner.exploit): pairs = [(dst, src, {"alpha",
+        "beta", "tau", "gamma"})].  The captured graphs stay as they are: the descriptors they read change in place, no storage
+        moves, and dst's fc2 images arrive with its weights."""
+        self.learner.exploit(pairs)
+
+    def hyper(self, a):
+        return self.learner.hyper(a)

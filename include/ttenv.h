@@ -591,6 +591,24 @@ int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents /*[coun
 int tt_pop_learn(tt_population *pop, int update, tt_stream_t stream);      /* one update of every agent, enqueued on stream */
 int tt_pop_learn_destroy(tt_population *pop);                                /* the caller's stream work with it must be done */
 
+/* Population-based training's exploit/explore step (Jaderberg et al., 2017) on a live population: ONE launch for a list of pairs.
+ * For each pair with dst != src, dst's learning state becomes src's: the parameters of its four networks (actor, critic and both
+ * targets), both networks' Adam moments m and v, and -- when the optimizer steps keep fc2 images -- the four fc2 images.  For every
+ * pair (dst == src: hyperparameters only) dst's actor learning rate becomes alpha, its critic's beta, both soft updates' tau, and
+ * its TD discount gamma.  Nothing else of dst moves: its ring, env, noise and episode log are the caller's, and its step counter,
+ * bias corrections and tail words stay (all agents of a population take their Adam steps in lockstep, so the step counts agree).
+ * The new values live in the descriptors tt_pop_learn reads, in place: launches captured before stay valid and see them.
+ * Enqueued on `stream`, ordered before the next tt_pop_learn on it.  list is a HOST array, copied into the launch's arguments.
+ * TT_EINVAL with a message, before any HIP call: a NULL handle or list, pairs outside [1, K], an agent index out of range, two
+ * pairs with the same dst, a dst that is the src of another pair, a non-finite value, alpha, beta or tau outside (0, 1], gamma
+ * outside (0, 1).  tt_pop_hyper reads agent a's {alpha, beta, tau, gamma} back from the device (synchronous). */
+typedef struct tt_pop_exploit_pair {
+    int32_t dst, src;
+    float alpha, beta, tau, gamma;
+} tt_pop_exploit_pair;
+int tt_pop_exploit(tt_population *pop, int pairs, const tt_pop_exploit_pair *list /*[pairs], host*/, tt_stream_t stream);
+int tt_pop_hyper(tt_population *pop, int agent, float out[4]);
+
 /* ------------------------------------------------------------------------------------------------------
  * Peer-to-peer gradient exchange of data-parallel ranks (one process per GPU of one node): the mean over the ranks of the
  * critic's / the actor's gradient at the reference's two optimizer sites (DDPG/DDPG_agent.py:95-104) WITHOUT a collective

@@ -4,8 +4,12 @@ progress line per block of vector steps from its own episode log and checkpoint.
 average, success rate and "best" decisions; the best agent's networks are saved through agents[a].save_models()).  At the end one
 training-state file per agent, with the keys of trainv2.py's save_training_state (training_states/<name>_training_state.pkl), so
 the reference's multi_training_state_plotter.py overlays the K runs.  --objectives: the detailed episode log, and each agent's line
-adds the 100-episode averages of viz_how_agent_learn.py's four objectives (episode_metrics.py).
-Usage: train_population.py [--objectives] K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
+adds the 100-episode averages of viz_how_agent_learn.py's four objectives (episode_metrics.py).  --pbt READY: population-based
+training (pbt.py) -- after each block, the records just drained go to the controller, which every READY vector steps lets the
+bottom agents copy a top agent's networks and optimizer state and perturb its hyperparameters; one line per decision
+(--pbt-quantile, default 0.25; --pbt-metric return | success, default return).
+Usage: train_population.py [--objectives] [--pbt READY [--pbt-quantile Q] [--pbt-metric M]] K n_envs_per_agent ring_slots
+       updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
 import pickle
 import sys
@@ -19,6 +23,20 @@ detail = "--objectives" in sys.argv[1:]
 if detail:
     sys.argv.remove("--objectives")
     from ddpg_trucktrailer_amd.episode_metrics import RunningObjectives  # noqa: E402
+
+
+def _option(name, cast, default=None):
+    if name not in sys.argv[1:]:
+        return default
+    i = sys.argv.index(name)
+    value = cast(sys.argv[i + 1])
+    del sys.argv[i:i + 2]
+    return value
+
+
+pbt_ready = _option("--pbt", int)
+pbt_quantile = _option("--pbt-quantile", float, 0.25)
+pbt_metric = _option("--pbt-metric", str, "return")
 K, n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:8])
 seed0 = int(sys.argv[8]) if len(sys.argv) > 8 else 27
 graph_steps = int(sys.argv[9]) if len(sys.argv) > 9 else 20
@@ -33,6 +51,12 @@ for a, ag in enumerate(pop.agents):       # each agent saves its best networks i
     for net in ag._nets():
         net.checkpoint_dir, net.checkpoint_file = d, os.path.join(d, os.path.basename(net.checkpoint_file))
 trackers = [BestModelTracker() for _ in range(K)]
+pbt = None
+if pbt_ready is not None:
+    from ddpg_trucktrailer_amd.pbt import PBT  # noqa: E402
+    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric)
+    print(f"PBT: a round every {pbt_ready} vector steps, bottom/top quantile {pbt_quantile}, ranked by {pbt_metric} over the "
+          f"last {pbt.window} episodes since an agent's last exploit", flush=True)
 running = [RunningObjectives() for _ in range(K)] if detail else None
 episodes = [0] * K
 t0 = time.time()
@@ -41,7 +65,8 @@ while s < total:
     k = min(every, total - s)
     pop.run(k)
     s += k
-    for a, r in enumerate(pop.drain_episodes()):
+    drained = pop.drain_episodes()
+    for a, r in enumerate(drained):
         m = len(r["ret"])
         best, avg, rate = trackers[a].update_many(r, episodes[a])
         episodes[a] += m
@@ -57,6 +82,11 @@ while s < total:
               f"{'BEST ' if best else ''}{objs}{lost}", flush=True)
         if best:
             pop.agents[a].save_models()
+    if pbt is not None:
+        for d in pbt.step(pop, drained):
+            hyp = "  ".join(f"{k} {d['old'][k]:.4g} -> {d['new'][k]:.4g}" for k in d["new"])
+            print(f"PBT step {d['step']}: agent {d['dst']} (score {d['dst_score'][0]:.1f}) <- agent {d['src']} "
+                  f"(score {d['src_score'][0]:.1f}): {hyp}", flush=True)
     print(f"  {time.time() - t0:8.1f} s, {s * n * K / max(1e-9, time.time() - t0):.3e} env-steps/s over the population", flush=True)
 
 os.makedirs("training_states", exist_ok=True)
