@@ -113,6 +113,7 @@ class TTPopExploitPair(C.Structure):
 
 
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
+NSTEP_MAX = 16          # TT_NSTEP_MAX
 
 
 class TTError(RuntimeError):
@@ -167,6 +168,8 @@ _SIGNATURES = {
     "tt_mlp_forward_save": (C.c_int, [_I, _I, _P, _P, C.POINTER(TTMlpWeights), _P, C.POINTER(TTMlpSaved), _P, _P]),
     "tt_mlp_forward_multi": (C.c_int, [_I, _I, C.POINTER(TTFwdJob), _P]),
     "tt_mlp_forward_multi_sampled": (C.c_int, [_I, _I, C.POINTER(TTFwdJob), C.POINTER(TTSampleArgs), _P, _P]),
+    "tt_ring_sample_nstep": (C.c_int, [C.POINTER(TTSampleArgs), _I, C.c_float, _P]),
+    "tt_mlp_forward_multi_sampled_nstep": (C.c_int, [_I, _I, C.POINTER(TTFwdJob), C.POINTER(TTSampleArgs), _I, C.c_float, _P, _P]),
     "tt_mlp_backward_rows_pair": (C.c_int, [_I, C.c_float, _P, C.POINTER(TTMlpWeights), C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs),
                                             C.POINTER(TTTdInput), _P, C.POINTER(TTMlpWeights), C.POINTER(TTMlpSaved),
                                             C.POINTER(TTMlpBwdWs), C.POINTER(TTImageJob), _P]),

@@ -110,7 +110,9 @@ class Agent():
         states, actions, rewards, states_, done = self.memory.sample_buffer(self.batch_size)
         self.learn_batch(states, actions, rewards, states_, done)
 
-    def learn_batch(self, states, actions, rewards, states_, done):
+    def learn_batch(self, states, actions, rewards, states_, done, discount=None):
+        # discount: what multiplies q' in the target (default gamma); gamma ** n for a batch of n-step tuples (TrajectoryRing.sample)
+        discount = self.gamma if discount is None else discount
         with T.no_grad():
             if self.fused_targets:      # one fused f32-MFMA launch per target net (csrc/ttnet.hip)
                 from ddpg_trucktrailer_amd import fused
@@ -120,7 +122,7 @@ class Agent():
                 target_actions = self.target_actor.forward(states_)
                 critic_value_ = self.target_critic.forward(states_, target_actions)
             critic_value_ = critic_value_.masked_fill(done.view(-1, 1), 0.0).view(-1)      # critic_value_[done] = 0.0
-            target = (rewards + self.gamma * critic_value_).view(-1, 1)
+            target = (rewards + discount * critic_value_).view(-1, 1)
         critic_value = self.critic.forward(states, actions)
 
         # Gradients through torch.autograd.grad, not .backward(): backward() delivers them through each parameter's

@@ -293,14 +293,20 @@ class FusedLearner:
 
     # learn() in the three pieces the two gradient all-reduces cut it into (each piece is pure kernel launches on the
     # current stream, so a data-parallel loop can capture each as a hipGraph and keep only the collectives eager)
-    def phase_a(self, states, actions, rewards, states_, done_u8, fuse_adam, window_dev=None, sample=None, image=None):
+    def phase_a(self, states, actions, rewards, states_, done_u8, fuse_adam, window_dev=None, sample=None, image=None, n_step=1):
         """Forwards, TD target, critic backward (+ the critic's Adam/soft update in the same launch when fuse_adam).
         sample: a tt_sample_args (TrajectoryRing.sample_args) whose batch buffers ARE the five tensors given -- the forward
         launch then makes the replay draw itself (tt_mlp_forward_multi_sampled) instead of reading a batch drawn before.
         image: (packed actor weights struct, tt_ring_cursor whose k_dev is a snapshot word, that word's tensor) -- the critic's
         backward launch then also packs the vector step's policy image (tt_image_job; needs `sample`: the forward launch leaves
-        the step number in the snapshot word)."""
+        the step number in the snapshot word).
+        n_step > 1: n-step returns (include/ttenv.h: tt_ring_sample_nstep).  With `sample` the forward launch makes the n-step
+        draw (tt_mlp_forward_multi_sampled_nstep); without it the five tensors must hold a batch drawn with the same n_step
+        (TrajectoryRing.sample_fused).  Either way the TD target discounts q' by gamma ** n_step."""
         ag, B = self.agent, self.B
+        n_step = int(n_step)
+        if not 1 <= n_step <= L.NSTEP_MAX:
+            raise ValueError(f"n_step = {n_step} is outside 1 .. {L.NSTEP_MAX}")
         self._fresh()
         # DDPG_agent.py:85-93 and :87, :101.  Only the target critic's LAST step needs the target actor's action (it enters
         # after LayerNorm2, networks.py:62-66), so four passes run side by side -- target actor on s', the target critic's
@@ -310,11 +316,15 @@ class FusedLearner:
         jobs = self.fwd_jobs(states, actions, states_)
         if sample is not None:
             assert (sample.s_out, sample.a_out, sample.s2_out) == (states.data_ptr(), actions.data_ptr(), states_.data_ptr())
-            L.check(self.lib.tt_mlp_forward_multi_sampled(B, 4, jobs, C.byref(sample), _p(image[2]) if image is not None else None,
-                                                          self._stream()))
+            snap = _p(image[2]) if image is not None else None
+            if n_step > 1:
+                L.check(self.lib.tt_mlp_forward_multi_sampled_nstep(B, 4, jobs, C.byref(sample), n_step, float(ag.gamma), snap,
+                                                                    self._stream()))
+            else:
+                L.check(self.lib.tt_mlp_forward_multi_sampled(B, 4, jobs, C.byref(sample), snap, self._stream()))
         else:
             L.check(self.lib.tt_mlp_forward_multi(B, 4, jobs, self._stream()))
-        self._rows(rewards, done_u8, window_dev, image)
+        self._rows(rewards, done_u8, window_dev, image, n_step)
         self._weights(self.critic, self.hyp_critic, ag.tau, states, actions, self.ws, adam=fuse_adam)
 
     def fwd_jobs(self, states, actions, states_):
@@ -333,21 +343,23 @@ class FusedLearner:
             jobs[j].dq_da, jobs[j].z_state = None, _ptr(zst)
         return jobs
 
-    def td_input(self, rewards, done_u8, window_dev=None):
-        """The input of the TD prologue of the critic's per-row backward (tt_td_input).  (Also a population's: PopulationLearner.)"""
+    def td_input(self, rewards, done_u8, window_dev=None, n_step=1):
+        """The input of the TD prologue of the critic's per-row backward (tt_td_input).  (Also a population's: PopulationLearner.)
+        n_step > 1: the rows are n-step tuples, and every row that the prologue discounts has the discount gamma ** n_step."""
         ag = self.agent
+        gamma = float(ag.gamma) if n_step == 1 else float(ag.gamma) ** int(n_step)      # (f64; the struct member rounds it to f32)
         return L.TTTdInput(z_state=self.z_t.data_ptr(), mu_target=self.mu_t.data_ptr(),
                            target_critic=C.pointer(self.w(ag.target_critic)), reward=rewards.data_ptr(),
-                           done=done_u8.data_ptr(), gamma=float(ag.gamma), y_out=self.y.data_ptr(),
+                           done=done_u8.data_ptr(), gamma=gamma, y_out=self.y.data_ptr(),
                            q_out=self.q_t.data_ptr(), step_dev=self.step_dev.data_ptr(), window_dev=_ptr(window_dev),
                            bias_corr_out=self.bias_corr.data_ptr(), adam_beta1=self.hyp_critic[1], adam_beta2=self.hyp_critic[2])
 
-    def _rows(self, rewards, done_u8, window_dev=None, image=None):
+    def _rows(self, rewards, done_u8, window_dev=None, image=None, n_step=1):
         """learn()'s per-row backward launch (tt_mlp_backward_rows_pair) after the forwards of phase_a."""
         ag, B = self.agent, self.B
         # critic step (DDPG_agent.py:95-98); its backward launch first finishes q'(s', mu'(s')) and the TD target for its
         # rows (tt_td_input)
-        td = self.td_input(rewards, done_u8, window_dev)
+        td = self.td_input(rewards, done_u8, window_dev, n_step)
         # ... and, on other workgroups of the same launch, the ACTOR's per-row backward for a unit gradient: it is linear in
         # the row's d(loss)/d(pre-tanh), which needs the updated critic and is applied in phase_b (include/ttenv.h)
         L.check(self.lib.tt_mlp_backward_rows_pair(B, 2.0 / B, _p(self.q), C.byref(self.w(ag.critic)),
@@ -391,14 +403,15 @@ class FusedLearner:
     def phase_c(self):
         self._adam(self.actor, self.hyp_actor, self.agent.tau)
 
-    def learn_batch(self, states, actions, rewards, states_, done_u8, window_dev=None, sample=None, image=None):
+    def learn_batch(self, states, actions, rewards, states_, done_u8, window_dev=None, sample=None, image=None, n_step=1):
         """states, states_ [B,23] f32; actions [B,1] f32; rewards [B] f32; done_u8 [B] uint8 -- all contiguous.
         window_dev: device int64 advanced by the critic's backward launch (a pipelined loop's sampling window).
-        sample: see phase_a (the five tensors are then the draw's batch buffers, filled by learn()'s first launch)."""
+        sample: see phase_a (the five tensors are then the draw's batch buffers, filled by learn()'s first launch).
+        n_step: see phase_a (n-step returns; 1 = the one-step learn(), launch for launch)."""
         assert states.shape[0] == self.B and done_u8.dtype == torch.uint8
         dp = self.grad_sync_critic is not None
         assert image is None or sample is not None
-        self.phase_a(states, actions, rewards, states_, done_u8, fuse_adam=not dp, window_dev=window_dev, sample=sample, image=image)
+        self.phase_a(states, actions, rewards, states_, done_u8, fuse_adam=not dp, window_dev=window_dev, sample=sample, image=image, n_step=n_step)
         if dp:
             self.grad_sync_critic()
         self.phase_b(states, separate_adam=dp)

@@ -156,8 +156,11 @@ class PopulationRollout:
 
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
-                 pipeline=None, side_buffer=None, episode_log_detail=False):
+                 pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+        if int(n_step) != 1:
+            raise ValueError("n-step returns (n_step > 1) are not supported in a population: its learn() launches take one-step draws, and "
+                             "the agents' own gamma ** n would have to travel with their hyperparameters")
         if data_parallel or pipeline or side_buffer is not None:
             raise ValueError("populations run the serial order on one GPU without expert side buffers (data-parallel populations, "
                              "the pipelined order and side buffers are not supported)")

@@ -71,6 +71,7 @@ class TrajectoryRing:
         self.side = None
         self.side_count = 0
         self.side_epoch = 0
+        self.n_step = 1              # > 1: the loop that owns the ring draws n-step tuples (DDPGRollout(n_step=...)): no side tuples
         # {t, t+1, t-1, t > 0}: ring slots of the running vector step, written on the device by the step's opening launch
         # (include/ttenv.h: tt_ring_view / tt_ring_cursor) so that captured launches need no per-position pointers
         # [4..7] / [8..11]: the cursors {t, t+1, t-1, t > 0} of even / odd steps, [0..3]: the running step's (include/ttenv.h)
@@ -116,6 +117,9 @@ class TrajectoryRing:
         """Append k stand-alone transitions (obs [k,23], act [k] or [k,1], rew [k], obs2 [k,23], done [k]) to the side
         buffer the sampler mixes into its uniform draw: the bulk form of the reference's `agent.remember` loop over
         stored expert transitions (trainv2.py:457-466).  The first call fixes the capacity (default: k)."""
+        if self.n_step > 1:
+            raise ValueError(f"side tuples in a ring that is drawn with n_step = {self.n_step} are not supported: they are single "
+                             "steps, and their rows would need a discount of their own in the TD launch")
         f = dict(dtype=torch.float32, device=self.device)
         obs = torch.as_tensor(obs, **f).reshape(-1, self.obs.shape[2])
         k = obs.shape[0]
@@ -248,14 +252,34 @@ class TrajectoryRing:
                               max(1, int(draws)), int(seed_stride) & (2 ** 64 - 1),
                               self.cursor_dev.data_ptr() + 4 * 16 if wait_for_steps else None)
 
-    def sample_fused(self, batch_size, seed=0, return_index=False, done_as_bool=True, k_dev=None, reserve=0, lag=0):
+    @staticmethod
+    def _check_n_step(n_step, gamma):
+        n_step = int(n_step)
+        if not 1 <= n_step <= 16:                        # TT_NSTEP_MAX
+            raise ValueError(f"n_step = {n_step} is outside 1 .. 16")
+        if n_step > 1 and (gamma is None or not 0.0 < float(gamma) < 1.0):
+            raise ValueError(f"n_step = {n_step} needs gamma in (0, 1), not {gamma}")
+        return n_step
+
+    def sample_fused(self, batch_size, seed=0, return_index=False, done_as_bool=True, k_dev=None, reserve=0, lag=0, n_step=1,
+                     gamma=None):
         """sample() as ONE HIP launch (tt_ring_sample): Philox indices keyed by (seed, k_dev) + gather.
         done_as_bool=False returns the raw uint8 flags (no conversion launch; what the fused learner takes).
         k_dev / reserve / lag: another device step counter, the number of newest slots to keep out of the window and the
         number of counted steps that may still be under way (a pipelined loop samples BESIDE the env steps of the running
-        and of the previous vector step: include/ttenv.h, tt_ring_sample)."""
+        and of the previous vector step: include/ttenv.h, tt_ring_sample).
+        n_step > 1 (with gamma): n-step tuples (tt_ring_sample_nstep) -- r is the discounted sum of up to n rewards from a base
+        step that has its n steps inside the window, s2 the observation where the sum stops and done whether an episode's end
+        stopped it; the TD target then discounts q' by gamma ** n_step."""
         import ctypes as C
         from ddpg_trucktrailer_amd import _lib as L
+        if self._check_n_step(n_step, gamma) > 1:
+            args = self.sample_args(batch_size, seed=seed, k_dev=k_dev, reserve=reserve, lag=lag)
+            s, a, r, s2, dn, idx = self._bufs
+            L.check(L.load().tt_ring_sample_nstep(C.byref(args), int(n_step), float(gamma),
+                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+            out = (s, a, r, s2, dn.bool() if done_as_bool else dn)
+            return out + (idx,) if return_index else out
         s, a, r, s2, dn, idx = self._batch_bufs(batch_size)
         p = lambda t: C.c_void_p(t.data_ptr())
         side = self._side_struct()
@@ -267,10 +291,15 @@ class TrajectoryRing:
         out = (s, a, r, s2, dn.bool() if done_as_bool else dn)
         return out + (idx,) if return_index else out
 
-    def sample(self, batch_size, generator=None):
+    def sample(self, batch_size, generator=None, n_step=1, gamma=None, return_index=False):
         """Uniform with replacement over the stored transitions; index math on the device (k_dev), so the call
-        can sit inside a captured hipGraph."""
+        can sit inside a captured hipGraph.
+        n_step > 1 (with gamma): the torch twin of tt_ring_sample_nstep -- the same window and the same walk in f32 (a multiply
+        and an add where the kernel has one fused multiply-add), with torch's random numbers for the step and the env.
+        return_index: also the (slot, env) of every row's base step, [batch, 2] int64 (side rows: (-1, j))."""
         dev = self.device
+        if self._check_n_step(n_step, gamma) > 1:
+            return self._sample_nstep(batch_size, generator, int(n_step), float(gamma), return_index)
         u = torch.rand((2, batch_size), device=dev, generator=generator)
         avail = torch.clamp(self.k_dev, max=self.slots - 1)                          # complete transitions, in steps
         back = (u[0] * avail).long().clamp_(max=self.slots - 2)                      # 0 = newest
@@ -287,4 +316,37 @@ class TrajectoryRing:
             for i, src in enumerate((sd["obs"][j], sd["act"][j].unsqueeze(1), sd["rew"][j], sd["obs2"][j], sd["done"][j].bool())):
                 sel = pick.view(-1, *([1] * (src.dim() - 1)))
                 out[i] = torch.where(sel, src, out[i])
+            if return_index:
+                return tuple(out) + (torch.where(pick.unsqueeze(1), torch.stack((torch.full_like(j, -1), j), 1), torch.stack((t, n), 1)),)
+        if return_index:
+            return tuple(out) + (torch.stack((t, n), 1),)
         return tuple(out)
+
+    def _sample_nstep(self, batch_size, generator, n_step, gamma, return_index):
+        if self.side is not None and self.side_count > 0:
+            raise ValueError("an n-step draw (n_step > 1) from a ring with side tuples is not supported")
+        if self.slots < 3 + (n_step - 1):
+            raise ValueError(f"a ring of {self.slots} slots has no window for n_step = {n_step}")
+        dev = self.device
+        u = torch.rand((2, batch_size), device=dev, generator=generator)
+        avail = torch.clamp(self.k_dev, max=self.slots - 1)
+        avail_n = torch.clamp(avail - (n_step - 1), min=1)             # base steps with their n steps in the window
+        back = (n_step - 1) + torch.minimum((u[0] * avail_n).long(), avail_n - 1)
+        t0 = self.k_dev - 1 - back
+        e = (u[1] * self.n).long().clamp_(max=self.n - 1)
+        ret = torch.zeros(batch_size, dtype=torch.float32, device=dev)
+        g = torch.ones((), dtype=torch.float32, device=dev)
+        gam = torch.tensor(gamma, dtype=torch.float32, device=dev)
+        open_ = torch.ones(batch_size, dtype=torch.bool, device=dev)   # no done met yet
+        m = torch.full((batch_size,), n_step, dtype=torch.int64, device=dev)
+        for j in range(n_step):
+            tj = torch.remainder(t0 + j, self.slots)
+            ret = torch.where(open_, ret + g * self.rew[tj, e], ret)
+            ends = open_ & (self.done[tj, e] != 0)
+            m = torch.where(ends, torch.full_like(m, j + 1), m)
+            open_ = open_ & ~ends
+            g = g * gam
+        t = torch.remainder(t0, self.slots)
+        t2 = torch.remainder(t0 + m, self.slots)
+        out = (self.obs[t, e], self.act[t, e].unsqueeze(1), ret, self.obs[t2, e], ~open_)
+        return out + (torch.stack((t, e), 1),) if return_index else out

@@ -51,6 +51,7 @@ _SEED_STRIDE = 0x9E3779B97F4A7C15     # sampling key of update u of a vector ste
 # Pipelined order: learn() of vector step t draws from the steps up to t-2 (lag 1: step t-1 may still be under way beside the
 # draw) and keeps off the two observation rows the env steps t-1 and t write meanwhile (reserve 2)
 _PIPE_LAG, _PIPE_RESERVE = 1, 2
+_NSTEP_MAX = 16                         # TT_NSTEP_MAX (include/ttenv.h)
 
 
 @contextlib.contextmanager
@@ -72,7 +73,7 @@ class DDPGRollout:
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99,
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
-                 policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False):
+                 policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -89,17 +90,29 @@ class DDPGRollout:
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
         before any step or capture: every episode that ends in the loop is logged by the env step kernel, with end_step = the
         loop's vector step; drain_episodes() collects the records.  episode_log_detail: the detailed log (each record also
-        carries its episode's sum of every reward term and its start pose; episode_metrics.py reads them)."""
+        carries its episode's sum of every reward term and its start pose; episode_metrics.py reads them).
+        n_step: 1 = the one-step TD target, launch for launch what the loop did before the option existed.  n > 1 (up to
+        TT_NSTEP_MAX): n-step returns from the ring (include/ttenv.h: tt_ring_sample_nstep) -- every update
+        makes its own draw in learn()'s first launch, and learn() starts once a base step with all its n steps is in the window.
+        Not together with side (expert) tuples, data-parallel ranks or a ring too short for the window."""
         self.env, self.n, self.device = env, env.n_envs, env.device
         if episode_log:
             env.enable_episode_log(int(episode_log), detail=episode_log_detail)
         self.batch_size = batch_size
+        self.n_step = int(n_step)
+        if not 1 <= self.n_step <= _NSTEP_MAX:
+            raise ValueError(f"n_step = {n_step} is outside 1 .. {_NSTEP_MAX}")
+        if self.n_step > 1 and replay_slots < 3 + (self.n_step - 1):
+            raise ValueError(f"n_step = {self.n_step} with replay_slots = {replay_slots} is not supported: the window of base steps "
+                             f"with their n steps intact needs at least {3 + self.n_step - 1} slots")
         self.updates_per_step = int(updates_per_step)
         assert self.updates_per_step >= 1
         torch.manual_seed(seed)
         self.gen = torch.Generator(device=self.device)
         self.gen.manual_seed(seed)
         self.dp = (world_size > 1) if data_parallel is None else bool(data_parallel)
+        if self.n_step > 1 and self.dp:
+            raise ValueError("n_step > 1 with data-parallel ranks is not supported (the ranks' segments draw through the one-step sampler)")
         self.agent = agent if agent is not None else Agent(
             alpha=alpha, beta=beta, input_dims=(env.observation_dim,), tau=tau, n_actions=1, gamma=gamma,
             fc1_dims=fc1_dims, fc2_dims=fc2_dims, batch_size=batch_size, device=self.device,
@@ -119,6 +132,7 @@ class DDPGRollout:
         self.ring = TrajectoryRing(self.n, replay_slots, env.observation_dim, self.device)
         if self.device.type == "cuda":
             self.ring.attach(env)                          # the step kernel advances the ring's device counter
+        self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
         self.noise = VecOUNoise(self.n, self.device)
         self.high = float(np.float32(math.pi / 4))       # env.action_space.high (f32 pi/4, simv2.py:86-91)
         self.scaled = torch.zeros(self.n, dtype=torch.float32, device=self.device)
@@ -159,6 +173,16 @@ class DDPGRollout:
         can_pipe = self.learner is not None and self.fused_act and self.device.type == "cuda" and replay_slots >= 3 + _PIPE_RESERVE \
             and self.ring._env_counts
         self.pipeline = can_pipe if pipeline is None else (bool(pipeline) and can_pipe)
+        # the window of base steps with all their n steps intact: slots - 1 - reserve - (n - 1) >= 1, as the kernels ask
+        need = 3 + (_PIPE_RESERVE if self.pipeline else 0) + (self.n_step - 1)
+        if self.n_step > 1 and replay_slots < need:
+            raise ValueError(f"n_step = {self.n_step} with replay_slots = {replay_slots} is not supported: this order needs {need} slots")
+        if self.n_step > 1 and os.environ.get("TT_FORCE_DP") == "1":
+            raise ValueError("n_step > 1 with the data-parallel launch structure (TT_FORCE_DP) is not supported")
+        # learn() starts at the vector step whose window holds a base step with its n steps (both orders; n = 1: step 2), and
+        # whole-step graphs, which always learn, after the eager steps that warm the loop up
+        self._learn_from = 1 + self.n_step
+        self._warm_steps = max(4, self._learn_from)
         self.policy_workgroups = int(os.environ.get("TT_POLICY_WG", policy_workgroups))     # (env: A/B measurements)
         # learn() is over after about four of the policy's capped grids (~100 us): the tiles left then (N > 98304 envs) go out
         # in one grid over all CUs
@@ -217,12 +241,13 @@ class DDPGRollout:
     # -------------------------------------------------------------- learning
     def _sample(self, u):
         key = self._sample_key(u)
+        ns = dict(n_step=self.n_step, gamma=float(self.agent.gamma)) if self.n_step > 1 else {}
         if self.device.type == "cuda":
             if self.pipeline:      # beside the env step of the same vector step: its slot is not part of the window
                 return self.ring.sample_fused(self.batch_size, seed=key, done_as_bool=False, k_dev=self.k_pipe_dev,
-                                              reserve=_PIPE_RESERVE, lag=_PIPE_LAG)
-            return self.ring.sample_fused(self.batch_size, seed=key, done_as_bool=self.learner is None)
-        return self.ring.sample(self.batch_size)
+                                              reserve=_PIPE_RESERVE, lag=_PIPE_LAG, **ns)
+            return self.ring.sample_fused(self.batch_size, seed=key, done_as_bool=self.learner is None, **ns)
+        return self.ring.sample(self.batch_size, **ns)
 
     def _sample_key(self, u):
         return (self.seed + u * _SEED_STRIDE) & (2 ** 64 - 1)
@@ -254,7 +279,9 @@ class DDPGRollout:
             # (pipelined order) the last update of a vector step moves the sampling window on
             last = self.pipeline and u == self.updates_per_step - 1
             self.learner.learn_batch(s, a, r, s2, d, window_dev=self.k_pipe_dev if last else None, sample=sample,
-                                     image=self._image_job() if with_image else None)   # raw uint8 done flags
+                                     image=self._image_job() if with_image else None, n_step=self.n_step)   # raw uint8 done flags
+        elif self.n_step > 1:
+            self.agent.learn_batch(s, a, r, s2, d, discount=float(self.agent.gamma) ** self.n_step)
         else:
             self.agent.learn_batch(s, a, r, s2, d)
 
@@ -262,18 +289,20 @@ class DDPGRollout:
         """Batches the opening launch of a pipelined step draws: all of the step's updates' (tt_sample_args.draws) -- each the
         draw its own update would make (same window, seed of update u), but made once per step, so that no update waits for
         the ring's rows on the learn chain (2.9 us per update).  Data-parallel ranks and the
-        torch learner keep one draw per opening launch."""
-        multi = (self.updates_per_step > 1 and self.pipeline and self.learner is not None and not self.dp
+        torch learner keep one draw per opening launch, and so does n_step > 1, where the opening launch draws nothing at all:
+        every update's first launch makes its own n-step draw."""
+        multi = (self.n_step == 1 and self.updates_per_step > 1 and self.pipeline and self.learner is not None and not self.dp
                  and self.device.type == "cuda" and os.environ.get("TT_MULTI_DRAW", "1") == "1")
         return self.updates_per_step if multi else 1
 
     def _learn_all(self, presampled=False, with_image=False, wait_for_steps=False):
+        presampled = presampled and self.n_step == 1       # (n-step draws are made by learn()'s first launch, never by the opening one)
         draws = self._draws_per_opening() if presampled else 1
         for u in range(self.updates_per_step):
             self._learn_once(u, presampled and u < draws, with_image and u == 0, wait_for_steps and u == 0)
 
     def learn(self):
-        if self.ring.k < 2:
+        if self.ring.k < self._learn_from:
             return
         # Only the fused learner's launches are captured.  The torch-autograd learner stays eager: its backward runs on
         # the autograd engine's thread and synchronises with whatever stream each parameter's gradient accumulator was
@@ -308,7 +337,7 @@ class DDPGRollout:
     def _open_step(self, learn):
         """The launch that opens a vector step: the policy's image from the actor's current weights and the ring cursor of
         the step -- in the pipelined order also the first batch of the step's learn()."""
-        if self.pipeline and learn:
+        if self.pipeline and learn and self.n_step == 1:
             fused.pack_and_sample(self.agent.actor, 0, self.ring.sample_args(
                 self.batch_size, seed=self._sample_key(0), k_dev=self.k_pipe_dev, reserve=_PIPE_RESERVE, lag=_PIPE_LAG,
                 draws=self._draws_per_opening(), seed_stride=_SEED_STRIDE), cursor=self.ring.cursor(self.k_pipe_dev))
@@ -415,11 +444,17 @@ class DDPGRollout:
         self._act_and_step()
         cur.wait_stream(side)
 
+    def _check_n_step(self):
+        if self.n_step > 1 and self.ring.side_count > 0:
+            raise ValueError("n_step > 1 with a side buffer is not supported: side tuples are single steps, and their rows would "
+                             "need a discount of their own in the TD launch")
+
     def step(self):
+        self._check_n_step()
         k = self.ring.k
         if self.pipeline:
             self._check_epoch()
-            self._pipelined(k, k >= 2)
+            self._pipelined(k, k >= self._learn_from)
             self.ring.advance()
         else:
             if self.ring_mode:
@@ -581,7 +616,7 @@ class DDPGRollout:
         """Everything one-off that run() would otherwise do lazily inside its first calls (a few eager vector steps that
         warm up allocators / kernel attributes / Adam state, then the graph captures), so that a timed region holds
         steady-state steps only.  Advances the loop by 4 vector steps."""
-        while self.ring.k < 4:
+        while self.ring.k < self._warm_steps:
             self.step()
         self._check_handover(exact=True)
         if self.graph_steps and not self._graphs_current():
@@ -600,12 +635,13 @@ class DDPGRollout:
         """k vector steps, every one a graph replay once the loop is warm (4 eager steps) when whole-step graphs are on:
         the graph of graph_steps steps while that many remain, the single-step graph for the rest; eager step() otherwise."""
         ring = self.ring
+        self._check_n_step()
         if self.learner is not None:
             self.learner.refresh_images()      # fc2 written by anyone but the learner's own launches since the last look?
         while k > 0:
             self._check_handover()             # (a host-memory read; a give-up drops the graphs: captured again just below)
             G = self.graph_steps
-            if G and ring.k >= 4 and (self._graphs_current() or self._try_capture()):
+            if G and ring.k >= self._warm_steps and (self._graphs_current() or self._try_capture()):
                 if self.dp and not self.dp_single_graph:
                     self._dp_step()
                     done = 1
@@ -642,7 +678,7 @@ class DDPGRollout:
         ag = self.agent
         sd = {"format": 2, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
               "handover_gave_up": [int(x) for x in self.handover_gave_up],
-              "batch_size": int(self.batch_size), "updates_per_step": self.updates_per_step,
+              "batch_size": int(self.batch_size), "updates_per_step": self.updates_per_step, "n_step": int(self.n_step),
               "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()}
                        for n in ("actor", "critic", "target_actor", "target_critic")},
               "ring": self.ring.state_dict(), "ou": self.noise.x.detach().cpu().clone(),
@@ -656,6 +692,8 @@ class DDPGRollout:
     def load_state_dict(self, sd):
         ag = self.agent
         assert int(sd["batch_size"]) == int(self.batch_size), "batch size differs"
+        if int(sd.get("n_step", 1)) != self.n_step:
+            raise ValueError(f"the checkpoint was written with n_step = {int(sd.get('n_step', 1))}, this loop has n_step = {self.n_step}")
         with torch.no_grad():
             for n, net_sd in sd["nets"].items():
                 for k, v in getattr(ag, n).state_dict().items():      # in place: captured graphs keep the addresses

@@ -451,6 +451,34 @@ int tt_mlp_forward_multi(int n, int count, const tt_fwd_job *jobs, tt_stream_t s
 int tt_mlp_forward_multi_sampled(int n, int count, const tt_fwd_job *jobs, const tt_sample_args *sample, int64_t *k_snapshot,
                                  tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * N-step returns in the replay draw (csrc/ttnstep.hip).  The ring is time-major, so the steps of an env after a stored
+ * transition are next to it; the draw can hand learn() the n-step tuple
+ *     (s_t, a_t, R = r_t + gamma r_(t+1) + ... + gamma^(m-1) r_(t+m-1), s_(t+m), D)
+ * for the target y = R + gamma^m q'(s_(t+m)) (1 - D).  Semantics, beyond tt_ring_sample's (n_step in 1 .. TT_NSTEP_MAX, gamma
+ * f32 in (0, 1)): with k = max(*k_dev - lag, 0), avail = min(k, slots - 1 - reserve), avail_n = avail - (n_step - 1):
+ *   - Philox call, key and counter of tt_ring_sample; back = (n_step - 1) + ((u64)r[0] * avail_n >> 32),
+ *     e = (u64)r[1] * n_envs >> 32, base step t0 = k - 1 - back -- only positions whose n steps lie inside the intact window; all
+ *     slots are taken mod `slots`.  n_step = 1 is tt_ring_sample's draw bit for bit.
+ *   - the walk j = 0 .. n_step - 1 over step t0 + j of env e: R = fmaf(g_j, rew, R) in f32, g_0 = 1, g_(j+1) = g_j * gamma in f32;
+ *     it stops after the first j with done != 0 (m = j + 1, D = 1); else m = n_step, D = 0.
+ *   - the batch row: s_out = obs[t0], a_out = act[t0], r_out = R, s2_out = obs[t0 + m], d_out = D, idx_out = {t0 mod slots, e}.
+ *     (For D = 1, s2 is the first observation of the next episode and never enters the target, as in tt_ring_sample.)
+ *   - avail_n < 1 counts as 1: an early launch reads in-bounds, meaningless rows, as tt_ring_sample does at *k_dev = 0.
+ * So a row either has no done among its n steps -- discount gamma^n, THE SAME FOR EVERY SUCH ROW: pass
+ * tt_td_input.gamma = (float)pow((double)gamma, n_step) -- or D = 1, and the TD prologue of tt_mlp_backward_rows_pair ignores q' and
+ * the discount for it: every launch of learn() behind the draw is the one-step learn()'s.
+ * TT_EINVAL with a message (tt_last_error(NULL)), before any HIP call: n_step outside 1 .. TT_NSTEP_MAX, gamma outside (0, 1),
+ * slots < 3 + reserve + (n_step - 1), a side buffer with count > 0 when n_step > 1 (side tuples are single steps: their rows
+ * would need a discount of their own), draws > 1, and whatever tt_ring_sample / tt_mlp_forward_multi_sampled refuse. */
+#define TT_NSTEP_MAX 16
+/* the lone draw into sample's batch buffers (sample->step_progress is not waited for) */
+int tt_ring_sample_nstep(const tt_sample_args *sample, int n_step, float gamma, tt_stream_t stream);
+/* tt_mlp_forward_multi_sampled with that draw made by the launch: the jobs on s read the rows at t0, the jobs on s' at t0 + m;
+ * step_progress and k_snapshot as there. */
+int tt_mlp_forward_multi_sampled_nstep(int n, int count, const tt_fwd_job *jobs, const tt_sample_args *sample, int n_step,
+                                       float gamma, int64_t *k_snapshot, tt_stream_t stream);
+
 /* learn()'s backward and optimizer step (autograd of networks.py:55-68 / 138-147, DDPG_agent.py:95-106), in the sequence
  *   tt_mlp_forward_multi[_sampled]  target actor and target critic's state branch on s', Q(s,a) and mu(s) with saved activations
  *   tt_mlp_backward_rows_pair       per-row backward of the critic (with the TD target in its prologue) and the actor

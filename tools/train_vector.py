@@ -5,7 +5,8 @@ returns, the reference's success test final_success_bonus > 0: trainv2.py:541), 
 success rate and "best" decisions (checkpoint.BestModelTracker).  The loop runs whole-step graphs of `graph_steps`.
 --objectives: the detailed episode log, and each line adds the 100-episode averages of viz_how_agent_learn.py's four objectives
 (efficiency, smoothness, precision, safety; episode_metrics.py).
-Usage: train_vector.py [--objectives] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+--n-step N: n-step returns in the replay draw (DDPGRollout(n_step=N); default 1, the one-step target).
+Usage: train_vector.py [--objectives] [--n-step N] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -17,6 +18,11 @@ if detail:
     sys.argv.remove("--objectives")
     from ddpg_trucktrailer_amd.episode_metrics import RunningObjectives
     running = RunningObjectives()
+n_step = 1
+if "--n-step" in sys.argv[1:]:
+    at = sys.argv.index("--n-step")
+    n_step = int(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
 n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:7])
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 27
 graph_steps = int(sys.argv[8]) if len(sys.argv) > 8 else (20 if slots <= 1024 else 0)      # (as before: no graphs past 1024 slots)
@@ -24,9 +30,9 @@ env = TruckTrailerVecEnv(n)
 env.reset(seed=seed)
 # the log holds a report block's episodes: at most one per env and step
 loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates_per_step=upd, graph_steps=graph_steps,
-                   episode_log=min(n * every, 1 << 24), episode_log_detail=detail)
+                   episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
-      f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}", flush=True)
+      f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}", flush=True)
 tracker = BestModelTracker()
 episodes = 0
 t0 = time.time()
