@@ -1139,6 +1139,11 @@ struct RowScale {
     const float *__restrict__ dq_da, *__restrict__ mu;
     float scale;
 };
+__device__ __forceinline__ float row_factor_of(const float scale, const float dq, const float m) {
+#pragma clang fp contract(off)
+    const float mm = m * m;
+    return (scale * dq) * (1.f - mm);
+}
 constexpr int MAXB = 1024;     // rows whose factors fit the LDS table of k_bwd_weights<true> (tt_mlp_backward_weights checks)
 
 struct Grads {
@@ -1208,6 +1213,12 @@ __device__ __forceinline__ void bwd_weights_body(const int blk, const int n, con
                                                  float *__restrict__ f_s, const TailSync &ts, const long long tail_epoch,
                                                  _Float16 *__restrict__ stage_s) {
     // stage_s: 4 x 1024 halves of LDS (8 KB) of the workgroup's own: the forward-image pieces of a dW2 workgroup's patch
+    // f(b) = (scale dQ/da[b]) (1 - mu[b]^2), every product and the difference rounded on its own (row_factor_of, contraction off):
+    // left to the compiler, the loops below came out with 1 - mu^2 as ONE fma in their unrolled trips and as a product and a
+    // difference in the others -- which rows got which depended on the batch size and on the variant (tail / no tail /
+    // population), so from 257 rows on the same learn() gave different bits on different paths.  (Up to 256 rows every variant
+    // took the unfused form: those bits stay.)
+    auto factor = [&](const float dq, const float m) -> float { return row_factor_of(RS.scale, dq, m); };
     auto fill_factors = [&]() __attribute__((always_inline)) {       // every thread of the workgroup calls this once
         if (ROWSCALE) {
             if (TAIL && ts.hints) {
@@ -1216,12 +1227,12 @@ __device__ __forceinline__ void bwd_weights_body(const int blk, const int n, con
                 lds_barrier();
                 for (int b = threadIdx.x; b < n; b += 256) {
                     const float m = RS.mu[b];
-                    f_s[b] = RS.scale * tail_row(ts, b, (int)tail_epoch) * (1.f - m * m);
+                    f_s[b] = factor(tail_row(ts, b, (int)tail_epoch), m);
                 }
             } else {
                 for (int b = threadIdx.x; b < n; b += 256) {
                     const float m = RS.mu[b];
-                    f_s[b] = RS.scale * RS.dq_da[b] * (1.f - m * m);
+                    f_s[b] = factor(RS.dq_da[b], m);
                 }
             }
             lds_barrier();
