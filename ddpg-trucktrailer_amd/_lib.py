@@ -112,6 +112,10 @@ class TTPopExploitPair(C.Structure):
                 ("gamma", C.c_float)]
 
 
+class TTPopNstep(C.Structure):
+    _fields_ = [("n_step", C.c_int32), ("gamma", C.c_float), ("discount", C.c_float)]
+
+
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 NSTEP_MAX = 16          # TT_NSTEP_MAX
 
@@ -200,6 +204,9 @@ _SIGNATURES = {
     "tt_pop_learn_destroy": (C.c_int, [_P]),
     "tt_pop_exploit": (C.c_int, [_P, _I, C.POINTER(TTPopExploitPair), _P]),
     "tt_pop_hyper": (C.c_int, [_P, _I, C.POINTER(C.c_float * 4)]),
+    "tt_pop_learn_set_nstep": (C.c_int, [_P, C.POINTER(TTPopNstep)]),
+    "tt_pop_exploit_nstep": (C.c_int, [_P, _I, C.POINTER(TTPopExploitPair), C.POINTER(TTPopNstep), _P]),
+    "tt_pop_nstep": (C.c_int, [_P, _I, C.POINTER(TTPopNstep)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

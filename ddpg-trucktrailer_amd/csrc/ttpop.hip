@@ -11,15 +11,18 @@
 //   k_pop_actor_tail           k_actor_tail: Q(s, mu(s)) and dQ/da rows, then the actor's weight gradients + Adam
 //
 // and, off the learn() path, k_pop_exploit (tt_pop_exploit): population-based training's exploit/explore step between vector steps.
+// With per-agent n-step returns (tt_pop_learn_set_nstep) the first launch is k_pop_fwd_multi_nstep of csrc/ttpop_nstep.hip instead;
+// the other three are the same, an agent's td.gamma then holding its discount gamma ** n.
 //
 // So each agent's results are the bits of its lone learn() (tests/test_gpu_population.py).  Per-agent arguments live in device
 // memory (PopAgent), filled once at tt_pop_learn_create: a launch takes (K, B, descriptors, u) and is graph-capturable.
 // The descriptors are read through the CONSTANT address space, as kernel arguments are: the bodies index the Adam tables with a
 // run-time tensor number (an array copied into registers would go to scratch), and constant loads are scalar loads that the
 // compiler may issue as early as it likes (nothing in a launch writes them).
-#include "ttlearn_bodies.h"
+#include "ttpop.h"
 
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <vector>
 
@@ -28,30 +31,6 @@ int fail_library(int code, const char *msg);      // csrc/ttenv.hip: the message
 }
 
 namespace {
-
-struct PopAgent {
-    // k_pop_fwd_multi: the lone sampled launch's argument (R.seed: the key of update 0; update u adds u * R.seed_stride)
-    FwdJobs F;
-    // k_pop_bwd_rows_pair
-    float scale_c;                       // 2 / B
-    const float *q_out, *mu_out;         // Q(s, a), mu(s) of the forwards
-    Weights Wc, Wa;                      // critic, actor
-    Saved sv_c, sv_a;
-    BwdOut o_c, o_a;
-    TdIn td;
-    // k_pop_bwd_weights (critic) and the weight workgroups of k_pop_actor_tail (actor)
-    const float *s, *a;                  // the draw's batch buffers
-    Grads Gc, Ga;
-    AdamFused Ac, Aa;
-    RowScale RSa;                        // {dq_da, mu, -1 / B}
-    float *q_pi, *dq_da;
-    TailSync ts;                         // this agent's own tail words; its epoch is its own step count
-};
-
-// agent a's descriptor, as a reference into the constant address space (see the head of the file)
-__device__ __forceinline__ const PopAgent &agent_of(const PopAgent *D, const int a) {
-    return *(const PopAgent *)((const __attribute__((address_space(4))) PopAgent *)D + a);
-}
 
 // grid: K x 4 x nb, agent-major; within an agent, job-major as k_fwd_multi
 __global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi(const int K, const int n, const PopAgent *__restrict__ D, const int u) {
@@ -325,12 +304,70 @@ int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
     return TT_OK;
 }
 
+
+// the device address of agent P's td.gamma (its TD discount)
+float *td_gamma_of(PopAgent *P) { return reinterpret_cast<float *>(reinterpret_cast<char *>(P) + offsetof(PopAgent, td) + offsetof(TdIn, gamma)); }
+
+// what tt_pop_learn_set_nstep ("agent" i) and tt_pop_exploit_nstep ("pair" i) refuse in one tt_pop_nstep, for a ring of `slots`
+// slots (host only: no HIP call)
+int check_pop_nstep(const char *who, const char *what, const int i, const struct tt_pop_nstep &q, const int slots, const int reserve) {
+    const char *why = nullptr;
+    char buf[160];
+    if (q.n_step < 1 || q.n_step > TT_NSTEP_MAX) {
+        snprintf(buf, sizeof buf, "n_step %d is outside 1 .. %d", q.n_step, TT_NSTEP_MAX);
+        why = buf;
+    } else if (!(q.gamma > 0.f && q.gamma < 1.f)) why = "gamma is outside (0, 1)";
+    else if (q.n_step == 1 && q.discount != q.gamma) why = "discount is not gamma although n_step is 1";
+    else if (q.n_step > 1 && !(q.discount > 0.f && q.discount < q.gamma)) why = "discount is outside (0, gamma) although n_step > 1";
+    else if (slots < 3 + reserve + (q.n_step - 1)) {
+        snprintf(buf, sizeof buf, "a ring of %d slots has no window for n_step %d with this reserve", slots, q.n_step);
+        why = buf;
+    }
+    if (!why) return TT_OK;
+    snprintf(g_why, sizeof g_why, "%s: %s %d: %s", who, what, i, why);
+    return tthost::fail_library(TT_EINVAL, g_why);
+}
+
 }  // namespace
 
 struct tt_population {
     int K = 0, n = 0;
     PopAgent *dev = nullptr;
+    PopNstep *table = nullptr;           // per-agent {n_step, gamma}: made by tt_pop_learn_set_nstep, then there for good
+    std::vector<int> slots, reserve;     // each agent's ring, for the window check of a later n_step
 };
+
+// what tt_pop_exploit and tt_pop_exploit_nstep (`who`) refuse in a list of pairs, which goes into L (host only: no HIP call)
+static int check_pairs(const char *who, const tt_population *h, const int pairs, const tt_pop_exploit_pair *list, ExploitList &L) {
+    char fmt[200];
+    const auto refuse = [&](const char *what, int a = 0, int b = 0) {
+        snprintf(fmt, sizeof fmt, "%s: %s", who, what);
+        return einval(fmt, a, b);
+    };
+    if (!h) return refuse("handle is NULL");
+    if (!list) return refuse("list is NULL");
+    const int K = h->K;
+    if (pairs < 1 || pairs > K) return refuse("pairs = %d, not in [1, K = %d]", pairs, K);
+    L.n = pairs;
+    for (int i = 0; i < pairs; ++i) {
+        const tt_pop_exploit_pair &q = list[i];
+        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K) return refuse("pair %d names an agent outside [0, K = %d)", i, K);
+        for (int j = 0; j < pairs; ++j) {
+            if (j == i) continue;
+            if (list[j].dst == q.dst) return refuse("pairs %d and %d have the same dst", i, j);
+            if (list[j].src == q.dst) return refuse("the dst of pair %d is the src of pair %d", i, j);
+        }
+        const float h4[4] = {q.alpha, q.beta, q.tau, q.gamma};
+        for (const float x : h4)
+            if (!std::isfinite(x)) return refuse("pair %d has a non-finite hyperparameter", i);
+        if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
+            return refuse("pair %d: alpha and beta must lie in (0, 1]", i);
+        if (!(q.tau > 0.f && q.tau <= 1.f)) return refuse("pair %d: tau must lie in (0, 1]", i);
+        if (!(q.gamma > 0.f && q.gamma < 1.f)) return refuse("pair %d: gamma must lie in (0, 1)", i);
+        L.p[i] = q;
+    }
+    return TT_OK;
+}
 
 extern "C" {
 
@@ -351,7 +388,12 @@ int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents, tt_pop
         (void)hipFree(dev);
         return tthost::fail_library(TT_EHIP, "tt_pop_learn_create: hipMemcpy");
     }
-    *out = new tt_population{count, batch, dev};
+    tt_population *h = new tt_population{count, batch, dev};
+    for (int a = 0; a < count; ++a) {
+        h->slots.push_back(agents[a].sample->slots);
+        h->reserve.push_back(agents[a].sample->reserve);
+    }
+    *out = h;
     return TT_OK;
 }
 
@@ -359,7 +401,8 @@ int tt_pop_learn(tt_population *h, int update, tt_stream_t stream) {
     if (!h) return einval("tt_pop_learn: handle is NULL");
     if (update < 0) return einval("tt_pop_learn: update = %d < 0", update);
     const int K = h->K, n = h->n, nb = (n + TR - 1) / TR;
-    hipLaunchKernelGGL(k_pop_fwd_multi, dim3(K * 4 * nb), dim3(64 * NW), 0, stream, K, n, h->dev, update);
+    if (h->table) ttpop::launch_fwd_multi_nstep(K, n, h->dev, h->table, update, stream);
+    else hipLaunchKernelGGL(k_pop_fwd_multi, dim3(K * 4 * nb), dim3(64 * NW), 0, stream, K, n, h->dev, update);
     hipLaunchKernelGGL(k_pop_bwd_rows_pair, dim3(K * (2 * nb + 1)), dim3(64 * NW), 0, stream, K, n, h->dev);
     hipLaunchKernelGGL(k_pop_bwd_weights<false>, dim3(K * WG_CRITIC_WEIGHTS), dim3(256), 0, stream, K, n, h->dev);
     hipLaunchKernelGGL(k_pop_actor_tail, dim3(K * (nb + WG_ACTOR_WEIGHTS)), dim3(64 * NW), 0, stream, K, n, h->dev);
@@ -367,32 +410,75 @@ int tt_pop_learn(tt_population *h, int update, tt_stream_t stream) {
 }
 
 int tt_pop_exploit(tt_population *h, int pairs, const tt_pop_exploit_pair *list, tt_stream_t stream) {
-    if (!h) return einval("tt_pop_exploit: handle is NULL");
-    if (!list) return einval("tt_pop_exploit: list is NULL");
-    const int K = h->K;
-    if (pairs < 1 || pairs > K) return einval("tt_pop_exploit: pairs = %d, not in [1, K = %d]", pairs, K);
     ExploitList L{};
-    L.n = pairs;
-    for (int i = 0; i < pairs; ++i) {
-        const tt_pop_exploit_pair &q = list[i];
-        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K)
-            return einval("tt_pop_exploit: pair %d names an agent outside [0, K = %d)", i, K);
-        for (int j = 0; j < pairs; ++j) {
-            if (j == i) continue;
-            if (list[j].dst == q.dst) return einval("tt_pop_exploit: pairs %d and %d have the same dst", i, j);
-            if (list[j].src == q.dst) return einval("tt_pop_exploit: the dst of pair %d is the src of pair %d", i, j);
-        }
-        const float h4[4] = {q.alpha, q.beta, q.tau, q.gamma};
-        for (const float x : h4)
-            if (!std::isfinite(x)) return einval("tt_pop_exploit: pair %d has a non-finite hyperparameter", i);
-        if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
-            return einval("tt_pop_exploit: pair %d: alpha and beta must lie in (0, 1]", i);
-        if (!(q.tau > 0.f && q.tau <= 1.f)) return einval("tt_pop_exploit: pair %d: tau must lie in (0, 1]", i);
-        if (!(q.gamma > 0.f && q.gamma < 1.f)) return einval("tt_pop_exploit: pair %d: gamma must lie in (0, 1)", i);
-        L.p[i] = q;
-    }
+    const int rc = check_pairs("tt_pop_exploit", h, pairs, list, L);
+    if (rc != TT_OK) return rc;
+    if (h->table)
+        return einval("tt_pop_exploit: this population has an n-step table, where an agent's discount is gamma ** n_step and not the "
+                      "pair's gamma: use tt_pop_exploit_nstep");
     hipLaunchKernelGGL(k_pop_exploit, dim3(pairs * EX_CHUNKS), dim3(EX_THREADS), 0, stream, L, h->dev);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_learn_set_nstep(tt_population *h, const struct tt_pop_nstep *per_agent) {
+    static const char who[] = "tt_pop_learn_set_nstep";
+    if (!h) return einval("tt_pop_learn_set_nstep: handle is NULL");
+    if (!per_agent) return einval("tt_pop_learn_set_nstep: per_agent is NULL");
+    const int K = h->K;
+    std::vector<PopNstep> host(K);
+    for (int a = 0; a < K; ++a) {
+        const int rc = check_pop_nstep(who, "agent", a, per_agent[a], h->slots[a], h->reserve[a]);
+        if (rc != TT_OK) return rc;
+        host[a] = PopNstep{per_agent[a].n_step, per_agent[a].gamma};
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return tthost::fail_library(TT_EHIP, "tt_pop_learn_set_nstep: hipDeviceSynchronize");
+    if (!h->table && hipMalloc(&h->table, sizeof(PopNstep) * K) != hipSuccess) {
+        h->table = nullptr;
+        return tthost::fail_library(TT_ENOMEM, "tt_pop_learn_set_nstep: hipMalloc");
+    }
+    bool ok = hipMemcpy(h->table, host.data(), sizeof(PopNstep) * K, hipMemcpyHostToDevice) == hipSuccess;
+    for (int a = 0; a < K && ok; ++a)
+        ok = hipMemcpy(td_gamma_of(h->dev + a), &per_agent[a].discount, sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
+    return ok ? TT_OK : tthost::fail_library(TT_EHIP, "tt_pop_learn_set_nstep: hipMemcpy");
+}
+
+int tt_pop_exploit_nstep(tt_population *h, int pairs, const tt_pop_exploit_pair *list, const struct tt_pop_nstep *ns, tt_stream_t stream) {
+    static const char who[] = "tt_pop_exploit_nstep";
+    ExploitList L{};
+    const int rc = check_pairs(who, h, pairs, list, L);
+    if (rc != TT_OK) return rc;
+    if (!ns) return einval("tt_pop_exploit_nstep: ns is NULL");
+    if (!h->table) return einval("tt_pop_exploit_nstep: this population has no n-step table (tt_pop_learn_set_nstep makes it)");
+    ttpop::NstepWrites W{};
+    W.n = pairs;
+    for (int i = 0; i < pairs; ++i) {
+        const int dst = list[i].dst, rc2 = check_pop_nstep(who, "pair", i, ns[i], h->slots[dst], h->reserve[dst]);
+        if (rc2 != TT_OK) return rc2;
+        if (ns[i].gamma != list[i].gamma) return einval("tt_pop_exploit_nstep: pair %d: ns.gamma is not the pair's gamma", i);
+        L.p[i].gamma = ns[i].discount;      // k_pop_exploit stores the pair's gamma into dst's td.gamma: the discount's place
+        W.dst[i] = dst;
+        W.n_step[i] = ns[i].n_step;
+        W.gamma[i] = ns[i].gamma;
+    }
+    hipLaunchKernelGGL(k_pop_exploit, dim3(pairs * EX_CHUNKS), dim3(EX_THREADS), 0, stream, L, h->dev);
+    ttpop::launch_set_nstep(W, h->table, stream);
+    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_nstep(tt_population *h, int agent, struct tt_pop_nstep *out) {
+    if (!h) return einval("tt_pop_nstep: handle is NULL");
+    if (!out) return einval("tt_pop_nstep: out is NULL");
+    if (agent < 0 || agent >= h->K) return einval("tt_pop_nstep: agent %d is not in [0, K = %d)", agent, h->K);
+    float discount;
+    if (hipMemcpy(&discount, td_gamma_of(h->dev + agent), sizeof discount, hipMemcpyDeviceToHost) != hipSuccess)
+        return tthost::fail_library(TT_EHIP, "tt_pop_nstep: hipMemcpy");
+    PopNstep e{1, discount};                // (no table: the one-step draw)
+    if (h->table && hipMemcpy(&e, h->table + agent, sizeof e, hipMemcpyDeviceToHost) != hipSuccess)
+        return tthost::fail_library(TT_EHIP, "tt_pop_nstep: hipMemcpy");
+    out->n_step = e.n_step;
+    out->gamma = e.gamma;
+    out->discount = discount;
+    return TT_OK;
 }
 
 int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
@@ -406,14 +492,20 @@ int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
     out[1] = P.Ac.lr;
     out[2] = P.Aa.tau;
     out[3] = P.td.gamma;
+    if (h->table) {                         // (td.gamma is the discount gamma ** n_step there)
+        PopNstep e;
+        if (hipMemcpy(&e, h->table + agent, sizeof e, hipMemcpyDeviceToHost) != hipSuccess)
+            return tthost::fail_library(TT_EHIP, "tt_pop_hyper: hipMemcpy");
+        out[3] = e.gamma;
+    }
     return TT_OK;
 }
 
 int tt_pop_learn_destroy(tt_population *h) {
     if (!h) return TT_OK;
-    const hipError_t e = hipFree(h->dev);
+    const hipError_t e = hipFree(h->dev), e2 = h->table ? hipFree(h->table) : hipSuccess;
     delete h;
-    return e == hipSuccess ? TT_OK : TT_EHIP;
+    return e == hipSuccess && e2 == hipSuccess ? TT_OK : TT_EHIP;
 }
 
 }  // extern "C"

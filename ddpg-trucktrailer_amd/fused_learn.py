@@ -100,6 +100,12 @@ class _NetState:
         self.a_g = (C.c_void_p * len(self.params))(*[t.data_ptr() for t in self.grads])
 
 
+def nstep_discount(gamma, n_step):
+    """The TD discount of n-step tuples, gamma ** n_step, in f64 (the C structs round it to f32): the one expression behind the lone
+    learner's tt_td_input.gamma and a population's tt_pop_nstep.discount, so both hold the same bits."""
+    return float(gamma) if n_step == 1 else float(gamma) ** int(n_step)
+
+
 class FusedLearner:
     def __init__(self, agent, batch_size, fc2_images=None):
         """fc2_images (None = on unless TT_LEARN_F32=1): the 400 x 300 products of learn() on the f16 MFMA from pre-split
@@ -347,7 +353,7 @@ class FusedLearner:
         """The input of the TD prologue of the critic's per-row backward (tt_td_input).  (Also a population's: PopulationLearner.)
         n_step > 1: the rows are n-step tuples, and every row that the prologue discounts has the discount gamma ** n_step."""
         ag = self.agent
-        gamma = float(ag.gamma) if n_step == 1 else float(ag.gamma) ** int(n_step)      # (f64; the struct member rounds it to f32)
+        gamma = nstep_discount(ag.gamma, n_step)         # (f64; the struct member rounds it to f32)
         return L.TTTdInput(z_state=self.z_t.data_ptr(), mu_target=self.mu_t.data_ptr(),
                            target_critic=C.pointer(self.w(ag.target_critic)), reward=rewards.data_ptr(),
                            done=done_u8.data_ptr(), gamma=gamma, y_out=self.y.data_ptr(),

@@ -18,7 +18,11 @@ Rules:
     first) takes a src drawn uniformly from the top m with the controller's own np.random.RandomState(seed);
   - explore: each hyperparameter in `explore` takes a factor drawn from `factors` (in the order alpha, beta, tau, gamma): alpha,
     beta and tau are multiplied by it, gamma is perturbed in 1 - gamma space (1 - gamma' = f (1 - gamma)); each value is clamped
-    to `bounds`; the others are src's unchanged.  dst's window is cleared."""
+    to `bounds`; the others are src's unchanged.  dst's window is cleared;
+  - n_step_choices (e.g. (1, 3, 5, 8); None: n is not PBT's business, and every decision and draw is as without the option): dst also
+    inherits src's n-step horizon, and explore moves it to a neighbour in the sorted choices or keeps it -- one more draw of the
+    same RNG (0, 1, 2: down, keep, up; clamped at the ends), taken after the pair's src and factor draws: the first pair of a
+    run takes the same src, alpha, beta, tau and gamma with the option as without, and every later draw comes one per pair later."""
 import collections
 import math
 
@@ -31,7 +35,7 @@ METRICS = ("return", "success")
 
 class PBT:
     def __init__(self, K, ready, seed=0, quantile=0.25, metric="return", window=100, min_episodes=None, explore=HYPERS,
-                 factors=(0.8, 1.2), bounds=None):
+                 factors=(0.8, 1.2), bounds=None, n_step_choices=None):
         self.K, self.ready = int(K), int(ready)
         if self.K < 1 or self.ready < 1:
             raise ValueError(f"PBT: K = {K} and ready = {ready} must be >= 1")
@@ -50,6 +54,11 @@ class PBT:
         self.factors = tuple(float(f) for f in factors)
         if not self.factors or any(not f > 0.0 for f in self.factors):
             raise ValueError(f"PBT: factors {factors} must be positive")
+        self.n_step_choices = None
+        if n_step_choices is not None:
+            self.n_step_choices = tuple(sorted({int(n) for n in n_step_choices}))
+            if not self.n_step_choices or self.n_step_choices[0] < 1:
+                raise ValueError(f"PBT: n_step_choices {n_step_choices} must be positive step counts")
         self.bounds = dict(BOUNDS)
         self.bounds.update(bounds or {})
         self.rng = np.random.RandomState(seed)
@@ -80,8 +89,9 @@ class PBT:
 
     # ------------------------------------------------------------------------------------------------- a round
     def decide(self, vector_step, hypers):
-        """hypers: per agent {"alpha", "beta", "tau", "gamma"} as they are now.  Returns the round's decisions (possibly none):
-        [{"step", "dst", "src", "dst_score", "src_score", "old", "new"}] -- "new" is what dst takes."""
+        """hypers: per agent {"alpha", "beta", "tau", "gamma"} (and "n_step" with n_step_choices) as they are now.  Returns the
+        round's decisions (possibly none): [{"step", "dst", "src", "dst_score", "src_score", "old", "new"}] -- "new" is what dst
+        takes."""
         if len(hypers) != self.K:
             raise ValueError(f"PBT.decide: {len(hypers)} hyperparameter sets for {self.K} agents")
         if vector_step - self.last_round < self.ready:
@@ -103,17 +113,33 @@ class PBT:
                 x = 1.0 - (1.0 - new[k]) * f if k == "gamma" else new[k] * f
                 lo, hi = self.bounds[k]
                 new[k] = min(max(x, lo), hi)
+            old = {k: float(hypers[dst][k]) for k in HYPERS}
+            if self.n_step_choices is not None:
+                old["n_step"] = int(hypers[dst]["n_step"])
+                new["n_step"] = self._explore_n(int(hypers[src]["n_step"]))
             out.append({"step": int(vector_step), "dst": dst, "src": src, "dst_score": scores[dst], "src_score": scores[src],
-                        "old": {k: float(hypers[dst][k]) for k in HYPERS}, "new": new})
+                        "old": old, "new": new})
             self.windows[dst].clear()
         self.last_round = int(vector_step)
         self.history.extend(out)
         return out
 
+    def _explore_n(self, n):
+        """A neighbour of n in the sorted choices, or n itself (one draw).  An n that is no choice moves from the nearest one."""
+        c = self.n_step_choices
+        i = min(range(len(c)), key=lambda j: (abs(c[j] - n), j))
+        move = int(self.rng.randint(3)) - 1
+        if move == 0:
+            return n
+        return c[min(max(i + move, 0), len(c) - 1)]
+
     def step(self, pop, drained):
         """observe(drained), decide at pop.vector_steps, and apply the decisions with one pop.exploit launch."""
         self.observe(drained)
         hypers = [{k: float(getattr(ag, k)) for k in HYPERS} for ag in pop.agents]
+        if self.n_step_choices is not None:
+            for h, n in zip(hypers, pop.n_steps):
+                h["n_step"] = int(n)
         out = self.decide(pop.vector_steps, hypers)
         if out:
             pop.exploit([(d["dst"], d["src"], d["new"]) for d in out])

@@ -9,14 +9,20 @@ shape (23-400-300-1) and the batch size B are shared.
 exploit() is population-based training's exploit/explore step (pbt.py decides it): between vector steps one launch copies an
 agent's networks, Adam moments and fc2 images over another's and sets new hyperparameters in the descriptors, in place.
 
-Out of scope: the pipelined order, data-parallel populations, expert side buffers, whole-population checkpoints (an agent's
-weights save through agents[a].save_models())."""
+N-step returns are per agent too (n_steps= / n_step=): agent a draws n-step tuples with its own n and
+gamma inside the shared first launch (csrc/ttpop_nstep.hip), from a table in device memory beside the descriptors; its TD
+discount gamma ** n travels by value (fused_learn.nstep_discount, the lone learner's expression).  Once a population has the
+table its first launch is the n-step kernel for good -- also at n = 1, the one-step draw bit for bit -- so exploit() may change
+an agent's n under captured graphs.  A population built without n-step arguments launches the four one-step kernels.
+
+Out of scope: the pipelined order, data-parallel populations, expert side buffers (with any n), whole-population checkpoints
+(an agent's weights save through agents[a].save_models())."""
 import ctypes as C
 
 import torch
 
 from ddpg_trucktrailer_amd import _lib as L
-from ddpg_trucktrailer_amd.fused_learn import FusedLearner
+from ddpg_trucktrailer_amd.fused_learn import FusedLearner, nstep_discount
 from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, DDPGRollout, _gc_off
 
 
@@ -24,9 +30,12 @@ class PopulationLearner:
     """learn() of K agents, each with the state of a FusedLearner of its own (Adam moments, step_dev, bias corrections, tail words,
     fc2 images), launched together.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys (update u of a vector
     step draws with seed + u * _SEED_STRIDE, as DDPGRollout._sample_key(u)).  The device descriptors are made at the first learn():
-    every buffer and parameter storage must stay where it is from then on."""
+    every buffer and parameter storage must stay where it is from then on.
+    n_steps: None = the one-step population, launch for launch; one int or one value per agent = n-step returns (include/ttenv.h:
+    tt_pop_learn_set_nstep).  Any n > 1, or a list (also of ones), makes the per-agent table, and learn()'s first launch is then the
+    n-step kernel for good.  Host mirrors: self.n_steps, and each agent's ring.n_step."""
 
-    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None):
+    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None):
         self.K, self.B = len(agents), int(batch_size)
         if not 1 <= self.K <= L.POP_MAX_AGENTS:
             raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
@@ -34,8 +43,16 @@ class PopulationLearner:
             raise ValueError("one ring and one seed per agent")
         if any(r._side_struct() is not None for r in rings):
             raise ValueError("expert side buffers are not supported in a population")
+        self.n_steps = [_check_n(n) for n in _per_agent(1 if n_steps is None else n_steps, self.K, "n_steps")]
+        self.nstep_table = isinstance(n_steps, (list, tuple)) or any(n > 1 for n in self.n_steps)
+        for a, (ring, n) in enumerate(zip(rings, self.n_steps)):
+            if ring.slots < 3 + (n - 1):
+                raise ValueError(f"agent {a}: n_step = {n} with a ring of {ring.slots} slots is not supported: the window of base "
+                                 f"steps with their n steps intact needs at least {3 + n - 1} slots")
         self.lib = L.load()
         self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
+        for ring, n in zip(self.rings, self.n_steps):
+            ring.n_step = n                # (load_side refuses tuples an n-step draw cannot use)
         self.learners = [FusedLearner(ag, self.B, fc2_images) for ag in self.agents]
         for ag, fl in zip(self.agents, self.learners):
             ag.fused_learner = fl          # (checkpoint.py exports the moments through it)
@@ -58,7 +75,7 @@ class PopulationLearner:
             ag = fl.agent
             sample = ring.sample_args(B, seed=seed, seed_stride=_SEED_STRIDE)
             s, act, r, s2, d = ring._batch_bufs(B)[:5]
-            jobs, td = fl.fwd_jobs(s, act, s2), fl.td_input(r, d)
+            jobs, td = fl.fwd_jobs(s, act, s2), fl.td_input(r, d, n_step=self.n_steps[a])
 
             def net(st, ws, hyp):
                 lr, b1, b2, eps, wd = hyp
@@ -72,6 +89,13 @@ class PopulationLearner:
         h = C.c_void_p()
         L.check(self.lib.tt_pop_learn_create(self.K, B, arr, C.byref(h)))      # (copies everything: `keep` may go now)
         self._h, self._key = h, self._storage_key()
+        if self.nstep_table:
+            ns = (L.TTPopNstep * self.K)(*[self._nstep_struct(ag.gamma, n) for ag, n in zip(self.agents, self.n_steps)])
+            L.check(self.lib.tt_pop_learn_set_nstep(h, ns))
+
+    @staticmethod
+    def _nstep_struct(gamma, n):
+        return L.TTPopNstep(int(n), float(gamma), nstep_discount(gamma, n))
 
     def refresh_images(self):
         for fl in self.learners:
@@ -103,7 +127,9 @@ class PopulationLearner:
         pairs = [(dst, src, {"alpha", "beta", "tau", "gamma"})].  dst != src: dst's four networks, Adam moments and fc2 images
         become src's; every dst then takes the given hyperparameters (a missing key: src's value).  The host mirrors --
         agent.alpha / beta / tau / gamma, the torch optimizers' lr, FusedLearner.hyp_actor / hyp_critic -- follow, so a checkpoint
-        or a later _create sees the new values.  Captured launches stay valid: the descriptors change in place."""
+        or a later _create sees the new values.  Captured launches stay valid: the descriptors change in place.
+        A pair's dict may also hold "n_step" (missing: src's): on an n-step population dst then draws with that n and the pair's
+        gamma and discounts with gamma ** n (tt_pop_exploit_nstep); a population without the table refuses an n other than 1."""
         if self._h is None:
             raise RuntimeError("PopulationLearner.exploit: no learn() has made the population's descriptors yet")
         if torch.cuda.is_current_stream_capturing():
@@ -113,16 +139,30 @@ class PopulationLearner:
             raise ValueError(f"exploit: 1 to {self.K} pairs, not {len(pairs)}")
         self.refresh_images()          # (src's images must hold its weights: they are copied with them)
         arr = (L.TTPopExploitPair * len(pairs))()
+        ns = (L.TTPopNstep * len(pairs))()
         new = []
         for i, (dst, src, hyp) in enumerate(pairs):
             dst, src = int(dst), int(src)
             if not (0 <= dst < self.K and 0 <= src < self.K):
                 raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
             h = {k: float(hyp.get(k, getattr(self.agents[src], k))) for k in ("alpha", "beta", "tau", "gamma")}
+            n = _check_n(hyp.get("n_step", self.n_steps[src]))
+            if not self.nstep_table and n != 1:
+                raise ValueError(f"exploit: pair {i} sets n_step = {n}, but this population was built without n-step returns "
+                                 "(PopulationLearner(n_steps=...))")
+            if self.rings[dst].slots < 3 + (n - 1):
+                raise ValueError(f"exploit: pair {i}: n_step = {n} needs a ring of {3 + n - 1} slots, agent {dst}'s has "
+                                 f"{self.rings[dst].slots}")
             arr[i] = L.TTPopExploitPair(dst, src, h["alpha"], h["beta"], h["tau"], h["gamma"])
-            new.append((dst, h))
-        L.check(self.lib.tt_pop_exploit(self._h, len(pairs), arr, C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-        for dst, h in new:
+            ns[i] = self._nstep_struct(h["gamma"], n)
+            new.append((dst, h, n))
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        if self.nstep_table:
+            L.check(self.lib.tt_pop_exploit_nstep(self._h, len(pairs), arr, ns, stream))
+        else:
+            L.check(self.lib.tt_pop_exploit(self._h, len(pairs), arr, stream))
+        for dst, h, n in new:
+            self.n_steps[dst] = self.rings[dst].n_step = n
             ag, fl = self.agents[dst], self.learners[dst]
             ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
             ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
@@ -139,6 +179,15 @@ class PopulationLearner:
         L.check(self.lib.tt_pop_hyper(self._h, int(a), C.byref(out)))
         return dict(zip(("alpha", "beta", "tau", "gamma"), (float(x) for x in out)))
 
+    def n_step_of(self, a):
+        """Agent a's (n_step, gamma, discount) as the device holds them (include/ttenv.h: tt_pop_nstep; synchronises)."""
+        if self._h is None:
+            raise RuntimeError("PopulationLearner.n_step_of: no learn() has made the population's descriptors yet")
+        out = L.TTPopNstep()
+        torch.cuda.synchronize()
+        L.check(self.lib.tt_pop_nstep(self._h, int(a), C.byref(out)))
+        return int(out.n_step), float(out.gamma), float(out.discount)
+
 
 def _per_agent(x, K, name):
     if isinstance(x, (list, tuple)):
@@ -148,19 +197,27 @@ def _per_agent(x, K, name):
     return [x] * K
 
 
+def _check_n(n):
+    n = int(n)
+    if not 1 <= n <= L.NSTEP_MAX:
+        raise ValueError(f"n_step = {n} is outside 1 .. {L.NSTEP_MAX}")
+    return n
+
+
 class PopulationRollout:
     """K DDPG loops of n_envs_per_agent envs each, one per seed, whose learn() launches are shared.  A vector step, in the serial
     order of DDPGRollout.step(): every agent's opening pack, policy launch and env step, then updates_per_step population updates.
     run(k) replays captured graphs of whole population steps (graph_steps and 1); step() launches the same step eagerly, with the
-    same bits.  alphas / betas / taus / gammas: one value for all agents or one per agent."""
+    same bits.  alphas / betas / taus / gammas: one value for all agents or one per agent.
+    n_step: one value or one per agent (1: the one-step population, launch for launch).  With n_max the largest of them, every
+    agent starts learning at vector step 1 + n_max -- an agent with a smaller n later than its lone loop would -- and graph
+    replay starts after max(4, 1 + n_max) eager steps.  n_step_max: the largest n an exploit() may give an agent later (PBT over
+    n); the ring check and the start use it."""
 
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
-                 pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1):
+                 pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
-        if int(n_step) != 1:
-            raise ValueError("n-step returns (n_step > 1) are not supported in a population: its learn() launches take one-step draws, and "
-                             "the agents' own gamma ** n would have to travel with their hyperparameters")
         if data_parallel or pipeline or side_buffer is not None:
             raise ValueError("populations run the serial order on one GPU without expert side buffers (data-parallel populations, "
                              "the pipelined order and side buffers are not supported)")
@@ -168,6 +225,17 @@ class PopulationRollout:
         K = self.K = len(self.seeds)
         if not 1 <= K <= L.POP_MAX_AGENTS:
             raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {K}")
+        n_steps = [_check_n(n) for n in _per_agent(n_step, K, "n_step")]
+        self.n_step_max = max(n_steps) if n_step_max is None else _check_n(n_step_max)
+        if self.n_step_max < max(n_steps):
+            raise ValueError(f"n_step_max = {self.n_step_max} is below the largest n_step, {max(n_steps)}")
+        nstep = isinstance(n_step, (list, tuple)) or self.n_step_max > 1
+        if self.n_step_max > 1 and torch.device(device).type != "cuda":
+            raise ValueError(f"n_step = {n_step} is not supported on a CPU device: the population's n-step draw exists only as a HIP "
+                             "kernel")
+        if replay_slots < 3 + (self.n_step_max - 1):
+            raise ValueError(f"n_step = {self.n_step_max} with replay_slots = {replay_slots} is not supported: the window of base "
+                             f"steps with their n steps intact needs at least {3 + self.n_step_max - 1} slots")
         alphas, betas, taus, gammas = (_per_agent(x, K, nm) for x, nm in ((alphas, "alphas"), (betas, "betas"), (taus, "taus"),
                                                                            (gammas, "gammas")))
         self.device = torch.device(device)
@@ -186,7 +254,9 @@ class PopulationRollout:
             self.loops.append(lp)
         self.agents = [lp.agent for lp in self.loops]
         self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
-                                         seeds=self.seeds)
+                                         seeds=self.seeds, n_steps=n_steps if nstep else None)
+        self._learn_from = 1 + self.n_step_max     # (DDPGRollout._learn_from / _warm_steps, for the largest n)
+        self._warm_steps = max(4, self._learn_from)
         self.graph_steps = int(graph_steps) if graph_steps else 0
         self.graph1 = self.graphG = None
         self._graph_epoch = None
@@ -218,7 +288,7 @@ class PopulationRollout:
 
     def step(self):
         """One population vector step, launched eagerly."""
-        learn = self.k + 1 >= 2              # (DDPGRollout.learn(): no update before two steps are stored)
+        learn = self.k + 1 >= self._learn_from      # (DDPGRollout.learn(): no update before 1 + n steps are stored)
         for lp in self.loops:
             lp._open_step(False)
             lp._act_and_step()
@@ -251,10 +321,11 @@ class PopulationRollout:
         return g
 
     def run(self, k):
-        """k population vector steps: eager until every agent has stored 4 steps, then graph replays of graph_steps and 1 steps."""
+        """k population vector steps: eager until every agent has stored max(4, 1 + n_step_max) steps, then graph replays of
+        graph_steps and 1 steps."""
         self.learner.refresh_images()
         while k > 0:
-            if self.graph_steps and self.k >= 4:
+            if self.graph_steps and self.k >= self._warm_steps:
                 self._check_epoch()
                 if self.graph1 is None:
                     self.graph1 = self._capture(1)
@@ -281,9 +352,19 @@ class PopulationRollout:
 
     def exploit(self, pairs):
         """PBT's exploit/explore step between vector steps, eagerly (PopulationLearner.exploit): pairs = [(dst, src, {"alpha",
-        "beta", "tau", "gamma"})].  The captured graphs stay as they are: the descriptors they read change in place, no storage
-        moves, and dst's fc2 images arrive with its weights."""
+        "beta", "tau", "gamma"[, "n_step"]})].  The captured graphs stay as they are: the descriptors and the n-step table they
+        read change in place, no storage moves, and dst's fc2 images arrive with its weights."""
+        pairs = list(pairs)
+        for i, (dst, src, hyp) in enumerate(pairs):
+            n = int(hyp.get("n_step", self.learner.n_steps[int(src)]))
+            if n > self.n_step_max:
+                raise ValueError(f"exploit: pair {i} sets n_step = {n} above this loop's n_step_max = {self.n_step_max}")
         self.learner.exploit(pairs)
 
     def hyper(self, a):
         return self.learner.hyper(a)
+
+    @property
+    def n_steps(self):
+        """Per agent, the n of its draws now (the host mirror of the device table)."""
+        return list(self.learner.n_steps)

@@ -637,6 +637,34 @@ typedef struct tt_pop_exploit_pair {
 int tt_pop_exploit(tt_population *pop, int pairs, const tt_pop_exploit_pair *list /*[pairs], host*/, tt_stream_t stream);
 int tt_pop_hyper(tt_population *pop, int agent, float out[4]);
 
+/* N-step returns in a population: each agent draws n-step tuples (tt_ring_sample_nstep's semantics) with ITS OWN n_step and gamma
+ * inside the shared first launch (csrc/ttpop_nstep.hip: k_pop_fwd_multi_nstep, k_pop_fwd_multi's grid and per-update key).  The
+ * library keeps a per-agent table {n_step, gamma} in device memory; an agent's TD discount gamma ** n_step takes the place of
+ * gamma in its tt_td_input, so the three launches behind the draw are unchanged.
+ *   discount    gamma ** n_step AS THE CALLER ROUNDS IT TO f32: it travels by value and the library never recomputes it, so an
+ *               agent's bits do not depend on any pow() here.  n_step == 1: discount == gamma.
+ * tt_pop_learn_set_nstep (synchronous: it waits for the device; call it before any capture) makes the table on first use, writes
+ * every agent's entry and stores discount into its TD input.  FROM THEN ON tt_pop_learn's first launch is the n-step kernel, also
+ * when every n_step is 1 (bit for bit the one-step draw): a later change of an agent's n_step changes no launch, so a captured
+ * graph stays valid.  A population on which it was never called launches exactly the four one-step kernels.
+ * tt_pop_exploit_nstep is tt_pop_exploit (its checks, its copy, alpha, beta and tau) followed on `stream` by the table writes:
+ * dst of pair i takes ns[i].n_step, draws with ns[i].gamma (which must equal list[i].gamma) and discounts with ns[i].discount.
+ * Plain tt_pop_exploit on a population with a table is TT_EINVAL: it would store gamma where gamma ** n_step belongs.
+ * tt_pop_hyper reports gamma from the table when there is one.  tt_pop_nstep reads agent a's {n_step, gamma, discount} back from
+ * the device (synchronous; without a table {1, gamma, gamma}).
+ * TT_EINVAL with a message naming the entry point and the agent or pair, before any HIP call: a NULL handle or array; n_step outside
+ * 1 .. TT_NSTEP_MAX; gamma outside (0, 1); discount != gamma when n_step == 1; discount outside (0, gamma) when n_step > 1; an agent
+ * whose ring has fewer than 3 + reserve + (n_step - 1) slots; tt_pop_exploit_nstep without a table; whatever tt_pop_exploit refuses.
+ * Not supported: side buffers (tt_pop_learn_create refuses them for every population). */
+struct tt_pop_nstep {        /* (a tag without a typedef: the read-back function below has the same name) */
+    int32_t n_step;
+    float gamma, discount;
+};
+int tt_pop_learn_set_nstep(tt_population *pop, const struct tt_pop_nstep *per_agent /*[K], host*/);
+int tt_pop_exploit_nstep(tt_population *pop, int pairs, const tt_pop_exploit_pair *list /*[pairs], host*/,
+                         const struct tt_pop_nstep *ns /*[pairs], host*/, tt_stream_t stream);
+int tt_pop_nstep(tt_population *pop, int agent, struct tt_pop_nstep *out);
+
 /* ------------------------------------------------------------------------------------------------------
  * Peer-to-peer gradient exchange of data-parallel ranks (one process per GPU of one node): the mean over the ranks of the
  * critic's / the actor's gradient at the reference's two optimizer sites (DDPG/DDPG_agent.py:95-104) WITHOUT a collective

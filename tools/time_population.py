@@ -8,8 +8,14 @@ FusedLearner's chain (the tail in one launch) timed the same way.
 Then the loop: K = 8 x n = 8192 envs at 8 updates per step (1024 env-steps per update per agent) against one agent at N = 65536
 with 64 updates per step, in the same process.
 Kernel times: run this under `rocprofv3 --kernel-trace --stats -- python tools/time_population.py --no-loop` separately.
-Usage: time_population.py [--legs 5] [--updates 1000] [--no-loop] [--loop-steps 60]"""
+--n-step N: instead of all that, what per-agent n-step returns cost: at K in {1, 4, 8}, us per population
+update of the one-step population (no table; two populations, two series), of n = 1 through the n-step table and of n = N, the
+variants interleaved within each leg; with --baseline-lib PATH (a libttenv.so built from another commit, loaded beside this one)
+that library's one-step population as well, also twice: the distance between two series of one library is the run-to-run spread
+the no-table path is held to.
+Usage: time_population.py [--legs 5] [--updates 1000] [--no-loop] [--loop-steps 60] [--n-step N [--ks 1,4,8] [--baseline-lib PATH]]"""
 import argparse
+import ctypes as C
 import os
 import statistics
 import sys
@@ -18,6 +24,7 @@ import time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch  # noqa: E402
 
+from ddpg_trucktrailer_amd import _lib as L  # noqa: E402
 from ddpg_trucktrailer_amd.agent import Agent  # noqa: E402
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner  # noqa: E402
 from ddpg_trucktrailer_amd.population import PopulationLearner, PopulationRollout  # noqa: E402
@@ -73,6 +80,48 @@ def timed(g, replays):
     return e0.elapsed_time(e1) * 1e3          # us
 
 
+def nstep_cost(a):
+    """--n-step: the variants of one K are timed back to back within a leg, their order alternating from leg to leg."""
+    Ks, N = tuple(a.ks), a.n_step
+    replays = max(1, -(-a.updates // a.per_graph))
+    base = None
+    if a.baseline_lib:
+        base = C.CDLL(a.baseline_lib)
+        for name in ("tt_pop_learn_create", "tt_pop_learn", "tt_pop_learn_destroy", "tt_last_error"):
+            getattr(base, name).restype, getattr(base, name).argtypes = L._SIGNATURES[name]
+    variants = [("one-step, no table", None, None), ("one-step, no table again", None, None), ("n = 1 through the table", [1], None),
+                (f"n = {N}", [N], None)]
+    if base is not None:       # (made alternately with this library's one-step populations: placement in memory is part of the spread)
+        variants = [("baseline library", None, base), variants[0], ("baseline library again", None, base)] + variants[1:]
+    pops = {}
+    for K in Ks:
+        for name, n_steps, lib in variants:
+            pop = PopulationLearner([agent(100 + i) for i in range(K)], B, rings=[ring(200 + i) for i in range(K)],
+                                    seeds=[300 + i for i in range(K)], n_steps=n_steps * K if n_steps else None)
+            if lib is not None:
+                pop.lib = lib              # (the descriptors are made at the first learn(): by this library)
+            pops[K, name] = (pop, captured(pop.learn, a.per_graph))
+    res = {key: [] for key in pops}
+    for leg in range(a.legs):
+        for K in (Ks if leg % 2 == 0 else Ks[::-1]):
+            for name, _, _ in (variants if leg % 2 == 0 else variants[::-1]):
+                res[K, name].append(timed(pops[K, name][1], replays) / (replays * a.per_graph))
+    print(f"# learn() alone, B = {B}, {replays * a.per_graph} graph-replayed updates per leg, {a.legs} legs (variants interleaved, order "
+          f"alternating), rings of 16 slots x 2048 envs, 5 % done flags")
+    print(f"# device {torch.cuda.get_device_name(0)}")
+    print(f"{'K':>3} {'variant':>26} {'us/pop update':>14} {'spread':>16} {'vs no table':>12}")
+    for K in Ks:
+        ref = statistics.median(res[K, "one-step, no table"])
+        for name, _, lib in variants:
+            pop, x = pops[K, name][0], res[K, name]
+            assert pop.tail_gave_up() == [0] * K
+            print(f"{K:3d} {name:>26} {statistics.median(x):14.2f} {min(x):7.2f}-{max(x):7.2f} {statistics.median(x) - ref:+12.2f}")
+            if lib is not None:            # its handle has that library's layout: it goes the way it came
+                torch.cuda.synchronize()
+                lib.tt_pop_learn_destroy(pop._h)
+                pop._h = None
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", type=int, default=5)
@@ -80,7 +129,12 @@ def main():
     ap.add_argument("--per-graph", type=int, default=100)
     ap.add_argument("--no-loop", action="store_true")
     ap.add_argument("--loop-steps", type=int, default=60)
+    ap.add_argument("--n-step", type=int, default=None)
+    ap.add_argument("--baseline-lib", default=None)
+    ap.add_argument("--ks", type=lambda t: [int(x) for x in t.split(",")], default=[1, 4, 8], help="with --n-step: the K values")
     a = ap.parse_args()
+    if a.n_step is not None:
+        return nstep_cost(a)
     Ks = (1, 2, 4, 8, 16)
     replays = max(1, -(-a.updates // a.per_graph))
     graphs = {}

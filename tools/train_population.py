@@ -7,9 +7,10 @@ the reference's multi_training_state_plotter.py overlays the K runs.  --objectiv
 adds the 100-episode averages of viz_how_agent_learn.py's four objectives (episode_metrics.py).  --pbt READY: population-based
 training (pbt.py) -- after each block, the records just drained go to the controller, which every READY vector steps lets the
 bottom agents copy a top agent's networks and optimizer state and perturb its hyperparameters; one line per decision
-(--pbt-quantile, default 0.25; --pbt-metric return | success, default return).
-Usage: train_population.py [--objectives] [--pbt READY [--pbt-quantile Q] [--pbt-metric M]] K n_envs_per_agent ring_slots
-       updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
+(--pbt-quantile, default 0.25; --pbt-metric return | success, default return).  --n-step N[,N...]: n-step returns, one n for all
+agents or one per agent; with --pbt, --pbt-n-steps a,b,c lets the controller move an agent's n among those choices.
+Usage: train_population.py [--objectives] [--n-step N[,N...]] [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]]
+       K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
 import pickle
 import sys
@@ -37,14 +38,24 @@ def _option(name, cast, default=None):
 pbt_ready = _option("--pbt", int)
 pbt_quantile = _option("--pbt-quantile", float, 0.25)
 pbt_metric = _option("--pbt-metric", str, "return")
+_ints = lambda text: [int(x) for x in text.split(",")]
+n_step = _option("--n-step", _ints, [1])
+pbt_n_steps = _option("--pbt-n-steps", _ints)
+if pbt_n_steps is not None and pbt_ready is None:
+    sys.exit("--pbt-n-steps needs --pbt")
 K, n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:8])
 seed0 = int(sys.argv[8]) if len(sys.argv) > 8 else 27
 graph_steps = int(sys.argv[9]) if len(sys.argv) > 9 else 20
 seeds = [seed0 + a for a in range(K)]
+nstep_kw = {}
+if n_step != [1] or pbt_n_steps is not None:
+    nstep_kw["n_step"] = n_step * K if len(n_step) == 1 else n_step      # (a list: the population keeps an n-step table)
+    if pbt_n_steps is not None:
+        nstep_kw["n_step_max"] = max(pbt_n_steps + n_step)
 pop = PopulationRollout(n, seeds, batch_size=batch, replay_slots=slots, updates_per_step=upd, graph_steps=graph_steps,
-                        episode_log=min(n * every, 1 << 24), episode_log_detail=detail)
+                        episode_log=min(n * every, 1 << 24), episode_log_detail=detail, **nstep_kw)
 print(f"K = {K} agents x N = {n} envs, ring {slots} steps, {upd} learn() per vector step = {n / upd:.1f} env-steps per update "
-      f"per agent, batch {batch}, seeds {seeds}", flush=True)
+      f"per agent, batch {batch}, seeds {seeds}, n_step {pop.n_steps}", flush=True)
 for a, ag in enumerate(pop.agents):       # each agent saves its best networks into a directory of its own
     d = os.path.join("tmp", "ddpg", f"seed{seeds[a]}")
     os.makedirs(d, exist_ok=True)
@@ -54,9 +65,10 @@ trackers = [BestModelTracker() for _ in range(K)]
 pbt = None
 if pbt_ready is not None:
     from ddpg_trucktrailer_amd.pbt import PBT  # noqa: E402
-    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric)
+    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric, n_step_choices=pbt_n_steps)
     print(f"PBT: a round every {pbt_ready} vector steps, bottom/top quantile {pbt_quantile}, ranked by {pbt_metric} over the "
-          f"last {pbt.window} episodes since an agent's last exploit", flush=True)
+          f"last {pbt.window} episodes since an agent's last exploit"
+          + (f", n_step explored among {list(pbt.n_step_choices)}" if pbt_n_steps is not None else ""), flush=True)
 running = [RunningObjectives() for _ in range(K)] if detail else None
 episodes = [0] * K
 t0 = time.time()
