@@ -40,6 +40,7 @@
 #include <vector>
 
 #include "ttenv.h"
+#include "tthost.h"
 
 #ifndef TT_TABLE
 #define TT_TABLE 0  // 1: polynomial / tableau constants come from the kernarg table instead of literals
@@ -1948,7 +1949,17 @@ int tt_random_actions(int n, uint64_t seed, uint64_t step, float *out, tt_stream
 
 }  // extern "C"
 
-// the library's message for a NULL handle (tt_last_error(NULL)), set by the entry points of the other sources (csrc/ttpop.hip)
+// the library's message for a NULL handle (tt_last_error(NULL)), set by the entry points of the other sources (csrc/tthost.h)
 namespace tthost {
 int fail_library(int code, const char *msg) { return fail(nullptr, code, "%s", msg); }
+int einval(const char *fmt, int a, int b) { return fail(nullptr, TT_EINVAL, fmt, a, b); }
+int refuse_nstep(const char *who, int n_step, float gamma) {
+    if (n_step < 1 || n_step > TT_NSTEP_MAX) return fail(nullptr, TT_EINVAL, "%s: n_step %d is outside 1 .. %d", who, n_step, TT_NSTEP_MAX);
+    if (!(gamma > 0.f && gamma < 1.f)) return fail(nullptr, TT_EINVAL, "%s: gamma is outside (0, 1)", who);
+    return TT_OK;
+}
+int refuse_nstep_window(const char *who, int n_step, int slots, int reserve) {
+    if (slots >= 3 + reserve + (n_step - 1)) return TT_OK;
+    return fail(nullptr, TT_EINVAL, "%s: a ring of %d slots has no window for n_step %d with this reserve", who, slots, n_step);
+}
 }  // namespace tthost

@@ -8,14 +8,13 @@
 // A batch row is (s, a) of the base step t0, R = the discounted sum of up to n rewards, s' = the observation m steps later and
 // D = 1 when a done ended the walk (csrc/ttnstep.h: nstep_pick).  Rows without a done all have the discount gamma^n, so the TD
 // prologue of k_bwd_rows_pair takes it by value in tt_td_input.gamma and nothing behind this launch changes.
+#include "tthost.h"
 #include "ttlearn_bodies.h"
 #include "ttnstep.h"
 
 #include <cstdio>
 
-namespace tthost {
-int fail_library(int code, const char *msg);      // csrc/ttenv.hip: the message of tt_last_error(NULL)
-}
+using tthost::einval;
 
 namespace {
 
@@ -95,31 +94,19 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi_nstep(const FwdJobs J, co
         fwd_small_body<false>(J.n, q.obs, q.action, q.W, q.out, q.sv, nullptr, nullptr, h1_s, z_s, w1_s, row0, orow);
 }
 
-char g_why[256];
-int einval(const char *fmt, int a = 0, int b = 0) {
-    snprintf(g_why, sizeof g_why, fmt, a, b);
-    return tthost::fail_library(TT_EINVAL, g_why);
-}
-
 // what both entry points refuse beyond make_ring_sample's own checks (host only: no HIP call); `who` names the entry point
 int check_nstep(const char *who, const tt_sample_args *a, const int n_step, const float gamma, ttnet::RingSample &R) {
     char fmt[200];
-    if (!a) { snprintf(fmt, sizeof fmt, "%s: no sample (tt_sample_args)", who); return einval(fmt); }
-    if (n_step < 1 || n_step > TT_NSTEP_MAX) {
-        snprintf(fmt, sizeof fmt, "%s: n_step %%d is outside 1 .. %%d", who);
-        return einval(fmt, n_step, TT_NSTEP_MAX);
-    }
-    if (!(gamma > 0.f && gamma < 1.f)) { snprintf(fmt, sizeof fmt, "%s: gamma is outside (0, 1)", who); return einval(fmt); }
-    if (ttnet::make_ring_sample(a, R) != TT_OK) { snprintf(fmt, sizeof fmt, "%s: bad tt_sample_args", who); return einval(fmt); }
-    if (a->slots < 3 + a->reserve + (n_step - 1)) {
-        snprintf(fmt, sizeof fmt, "%s: a ring of %%d slots has no window for n_step %%d with this reserve", who);
-        return einval(fmt, a->slots, n_step);
-    }
-    if (n_step > 1 && R.side.count > 0) {
-        snprintf(fmt, sizeof fmt, "%s: a side buffer (%%d tuples) with n_step %%d: side tuples are single steps", who);
-        return einval(fmt, R.side.count, n_step);
-    }
-    if (a->draws > 1) { snprintf(fmt, sizeof fmt, "%s: draws = %%d: one draw per launch", who); return einval(fmt, a->draws); }
+    const auto refuse = [&](const char *what, int x = 0, int y = 0) {
+        snprintf(fmt, sizeof fmt, "%s: %s", who, what);
+        return einval(fmt, x, y);
+    };
+    if (!a) return refuse("no sample (tt_sample_args)");
+    if (const int rc = tthost::refuse_nstep(who, n_step, gamma)) return rc;
+    if (ttnet::make_ring_sample(a, R) != TT_OK) return refuse("bad tt_sample_args");
+    if (const int rc = tthost::refuse_nstep_window(who, n_step, a->slots, a->reserve)) return rc;
+    if (n_step > 1 && R.side.count > 0) return refuse("a side buffer (%d tuples) with n_step %d: side tuples are single steps", R.side.count, n_step);
+    if (a->draws > 1) return refuse("draws = %d: one draw per launch", a->draws);
     return TT_OK;
 }
 

@@ -19,6 +19,7 @@
 // The descriptors are read through the CONSTANT address space, as kernel arguments are: the bodies index the Adam tables with a
 // run-time tensor number (an array copied into registers would go to scratch), and constant loads are scalar loads that the
 // compiler may issue as early as it likes (nothing in a launch writes them).
+#include "tthost.h"
 #include "ttpop.h"
 
 #include <cmath>
@@ -26,9 +27,7 @@
 #include <cstdio>
 #include <vector>
 
-namespace tthost {
-int fail_library(int code, const char *msg);      // csrc/ttenv.hip: the message of tt_last_error(NULL)
-}
+using tthost::einval;
 
 namespace {
 
@@ -240,13 +239,6 @@ __global__ __launch_bounds__(EX_THREADS) void k_pop_exploit(const ExploitList L,
     }
 }
 
-char g_why[256];
-
-int einval(const char *fmt, int a = 0, int b = 0) {
-    snprintf(g_why, sizeof g_why, fmt, a, b);
-    return tthost::fail_library(TT_EINVAL, g_why);
-}
-
 // one agent's tt_pop_agent -> PopAgent (host checks only: no HIP call)
 int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
     P = PopAgent{};
@@ -311,21 +303,15 @@ float *td_gamma_of(PopAgent *P) { return reinterpret_cast<float *>(reinterpret_c
 // what tt_pop_learn_set_nstep ("agent" i) and tt_pop_exploit_nstep ("pair" i) refuse in one tt_pop_nstep, for a ring of `slots`
 // slots (host only: no HIP call)
 int check_pop_nstep(const char *who, const char *what, const int i, const struct tt_pop_nstep &q, const int slots, const int reserve) {
+    char at[200];
+    snprintf(at, sizeof at, "%s: %s %d", who, what, i);
+    if (const int rc = tthost::refuse_nstep(at, q.n_step, q.gamma)) return rc;
     const char *why = nullptr;
-    char buf[160];
-    if (q.n_step < 1 || q.n_step > TT_NSTEP_MAX) {
-        snprintf(buf, sizeof buf, "n_step %d is outside 1 .. %d", q.n_step, TT_NSTEP_MAX);
-        why = buf;
-    } else if (!(q.gamma > 0.f && q.gamma < 1.f)) why = "gamma is outside (0, 1)";
-    else if (q.n_step == 1 && q.discount != q.gamma) why = "discount is not gamma although n_step is 1";
-    else if (q.n_step > 1 && !(q.discount > 0.f && q.discount < q.gamma)) why = "discount is outside (0, gamma) although n_step > 1";
-    else if (slots < 3 + reserve + (q.n_step - 1)) {
-        snprintf(buf, sizeof buf, "a ring of %d slots has no window for n_step %d with this reserve", slots, q.n_step);
-        why = buf;
-    }
-    if (!why) return TT_OK;
-    snprintf(g_why, sizeof g_why, "%s: %s %d: %s", who, what, i, why);
-    return tthost::fail_library(TT_EINVAL, g_why);
+    if (q.n_step == 1 && q.discount != q.gamma) why = "discount is not gamma although n_step is 1";
+    if (q.n_step > 1 && !(q.discount > 0.f && q.discount < q.gamma)) why = "discount is outside (0, gamma) although n_step > 1";
+    if (!why) return tthost::refuse_nstep_window(at, q.n_step, slots, reserve);
+    snprintf(at, sizeof at, "%s: %s %%d: %s", who, what, why);
+    return einval(at, i);
 }
 
 }  // namespace

@@ -12,6 +12,7 @@ import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd import fused
+from ddpg_trucktrailer_amd.replay_buffer import check_n_step
 
 _ORDER = ("fc1.weight", "fc1.bias", "bn1.weight", "bn1.bias", "fc2.weight", "fc2.bias", "bn2.weight", "bn2.bias")
 _FIELDS = ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2", "w3", "b3", "wa", "ba")
@@ -310,9 +311,7 @@ class FusedLearner:
         draw (tt_mlp_forward_multi_sampled_nstep); without it the five tensors must hold a batch drawn with the same n_step
         (TrajectoryRing.sample_fused).  Either way the TD target discounts q' by gamma ** n_step."""
         ag, B = self.agent, self.B
-        n_step = int(n_step)
-        if not 1 <= n_step <= L.NSTEP_MAX:
-            raise ValueError(f"n_step = {n_step} is outside 1 .. {L.NSTEP_MAX}")
+        n_step = check_n_step(n_step)
         self._fresh()
         # DDPG_agent.py:85-93 and :87, :101.  Only the target critic's LAST step needs the target actor's action (it enters
         # after LayerNorm2, networks.py:62-66), so four passes run side by side -- target actor on s', the target critic's

@@ -1,10 +1,10 @@
 """A population of K independent DDPG agents trained in one loop on one GPU (include/ttenv.h: tt_pop_learn_*).
 
-Agent a is exactly a lone serial-order DDPGRollout(pipeline=False) built with agent a's arguments -- its own env of n lanes, replay
-ring, OU noise, policy launch and env step -- except that its learn() launches are shared with the other K - 1 agents: one
-population update is four launches (csrc/ttpop.hip) that run every agent's workgroups.  Each agent's results are the bits of its
-lone loop with the actor tail in one launch (TT_ACTOR_TAIL=1).  Seeds, learning rates, tau and gamma are per agent; the network
-shape (23-400-300-1) and the batch size B are shared.
+Agent a is a VectorStepper (stepper.py) built with agent a's arguments -- the acting half of a lone loop: its own env of n lanes,
+networks, replay ring, OU noise, policy launch and env step -- stepped in the lone loop's serial order.  The learn() launches are
+shared: one population update is four launches (csrc/ttpop.hip) that run every agent's workgroups.  Each agent's results are the
+bits of its lone serial-order loop (rollout.py, pipeline=False) with the actor tail in one launch (TT_ACTOR_TAIL=1).  Seeds,
+learning rates, tau and gamma are per agent; the network shape (23-400-300-1) and the batch size B are shared.
 
 exploit() is population-based training's exploit/explore step (pbt.py decides it): between vector steps one launch copies an
 agent's networks, Adam moments and fc2 images over another's and sets new hyperparameters in the descriptors, in place.
@@ -23,13 +23,15 @@ import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner, nstep_discount
-from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, DDPGRollout, _gc_off
+from ddpg_trucktrailer_amd.replay_buffer import check_n_step, learn_start, slots_needed
+from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, _gc_off
+from ddpg_trucktrailer_amd.stepper import VectorStepper
 
 
 class PopulationLearner:
     """learn() of K agents, each with the state of a FusedLearner of its own (Adam moments, step_dev, bias corrections, tail words,
     fc2 images), launched together.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys (update u of a vector
-    step draws with seed + u * _SEED_STRIDE, as DDPGRollout._sample_key(u)).  The device descriptors are made at the first learn():
+    step draws with seed + u * _SEED_STRIDE, the lone loop's sampling key).  The device descriptors are made at the first learn():
     every buffer and parameter storage must stay where it is from then on.
     n_steps: None = the one-step population, launch for launch; one int or one value per agent = n-step returns (include/ttenv.h:
     tt_pop_learn_set_nstep).  Any n > 1, or a list (also of ones), makes the per-agent table, and learn()'s first launch is then the
@@ -43,12 +45,12 @@ class PopulationLearner:
             raise ValueError("one ring and one seed per agent")
         if any(r._side_struct() is not None for r in rings):
             raise ValueError("expert side buffers are not supported in a population")
-        self.n_steps = [_check_n(n) for n in _per_agent(1 if n_steps is None else n_steps, self.K, "n_steps")]
+        self.n_steps = [check_n_step(n) for n in _per_agent(1 if n_steps is None else n_steps, self.K, "n_steps")]
         self.nstep_table = isinstance(n_steps, (list, tuple)) or any(n > 1 for n in self.n_steps)
         for a, (ring, n) in enumerate(zip(rings, self.n_steps)):
-            if ring.slots < 3 + (n - 1):
+            if ring.slots < slots_needed(n):
                 raise ValueError(f"agent {a}: n_step = {n} with a ring of {ring.slots} slots is not supported: the window of base "
-                                 f"steps with their n steps intact needs at least {3 + n - 1} slots")
+                                 f"steps with their n steps intact needs at least {slots_needed(n)} slots")
         self.lib = L.load()
         self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
         for ring, n in zip(self.rings, self.n_steps):
@@ -146,12 +148,12 @@ class PopulationLearner:
             if not (0 <= dst < self.K and 0 <= src < self.K):
                 raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
             h = {k: float(hyp.get(k, getattr(self.agents[src], k))) for k in ("alpha", "beta", "tau", "gamma")}
-            n = _check_n(hyp.get("n_step", self.n_steps[src]))
+            n = check_n_step(hyp.get("n_step", self.n_steps[src]))
             if not self.nstep_table and n != 1:
                 raise ValueError(f"exploit: pair {i} sets n_step = {n}, but this population was built without n-step returns "
                                  "(PopulationLearner(n_steps=...))")
-            if self.rings[dst].slots < 3 + (n - 1):
-                raise ValueError(f"exploit: pair {i}: n_step = {n} needs a ring of {3 + n - 1} slots, agent {dst}'s has "
+            if self.rings[dst].slots < slots_needed(n):
+                raise ValueError(f"exploit: pair {i}: n_step = {n} needs a ring of {slots_needed(n)} slots, agent {dst}'s has "
                                  f"{self.rings[dst].slots}")
             arr[i] = L.TTPopExploitPair(dst, src, h["alpha"], h["beta"], h["tau"], h["gamma"])
             ns[i] = self._nstep_struct(h["gamma"], n)
@@ -197,16 +199,9 @@ def _per_agent(x, K, name):
     return [x] * K
 
 
-def _check_n(n):
-    n = int(n)
-    if not 1 <= n <= L.NSTEP_MAX:
-        raise ValueError(f"n_step = {n} is outside 1 .. {L.NSTEP_MAX}")
-    return n
-
-
 class PopulationRollout:
-    """K DDPG loops of n_envs_per_agent envs each, one per seed, whose learn() launches are shared.  A vector step, in the serial
-    order of DDPGRollout.step(): every agent's opening pack, policy launch and env step, then updates_per_step population updates.
+    """K steppers of n_envs_per_agent envs each, one per seed, whose learn() launches are shared.  A vector step, in the serial
+    order of a lone loop's step(): every agent's opening pack, policy launch and env step, then updates_per_step population updates.
     run(k) replays captured graphs of whole population steps (graph_steps and 1); step() launches the same step eagerly, with the
     same bits.  alphas / betas / taus / gammas: one value for all agents or one per agent.
     n_step: one value or one per agent (1: the one-step population, launch for launch).  With n_max the largest of them, every
@@ -225,17 +220,17 @@ class PopulationRollout:
         K = self.K = len(self.seeds)
         if not 1 <= K <= L.POP_MAX_AGENTS:
             raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {K}")
-        n_steps = [_check_n(n) for n in _per_agent(n_step, K, "n_step")]
-        self.n_step_max = max(n_steps) if n_step_max is None else _check_n(n_step_max)
+        n_steps = [check_n_step(n) for n in _per_agent(n_step, K, "n_step")]
+        self.n_step_max = max(n_steps) if n_step_max is None else check_n_step(n_step_max)
         if self.n_step_max < max(n_steps):
             raise ValueError(f"n_step_max = {self.n_step_max} is below the largest n_step, {max(n_steps)}")
         nstep = isinstance(n_step, (list, tuple)) or self.n_step_max > 1
         if self.n_step_max > 1 and torch.device(device).type != "cuda":
             raise ValueError(f"n_step = {n_step} is not supported on a CPU device: the population's n-step draw exists only as a HIP "
                              "kernel")
-        if replay_slots < 3 + (self.n_step_max - 1):
+        if replay_slots < slots_needed(self.n_step_max):
             raise ValueError(f"n_step = {self.n_step_max} with replay_slots = {replay_slots} is not supported: the window of base "
-                             f"steps with their n steps intact needs at least {3 + self.n_step_max - 1} slots")
+                             f"steps with their n steps intact needs at least {slots_needed(self.n_step_max)} slots")
         alphas, betas, taus, gammas = (_per_agent(x, K, nm) for x, nm in ((alphas, "alphas"), (betas, "betas"), (taus, "taus"),
                                                                            (gammas, "gammas")))
         self.device = torch.device(device)
@@ -244,35 +239,36 @@ class PopulationRollout:
         for a in range(K):
             env = TruckTrailerVecEnv(self.n, device=self.device)
             env.reset(seed=self.seeds[a])
-            # a lone serial-order loop whose own learner is not made: its learn() runs in the population's launches
-            lp = DDPGRollout(env, batch_size=self.batch_size, replay_slots=replay_slots, seed=self.seeds[a], alpha=alphas[a],
-                             beta=betas[a], tau=taus[a], gamma=gammas[a], fused_learn=False, graph_steps=0,
-                             updates_per_step=self.updates_per_step, pipeline=False, episode_log=episode_log,
-                             episode_log_detail=episode_log_detail)
+            lp = VectorStepper(env, batch_size=self.batch_size, replay_slots=replay_slots, seed=self.seeds[a], alpha=alphas[a],
+                               beta=betas[a], tau=taus[a], gamma=gammas[a], episode_log=episode_log,
+                               episode_log_detail=episode_log_detail)
             if not lp.ring_mode:
                 raise RuntimeError("a population needs the fused policy and ring-addressed steps (reference-shaped actor on a GPU)")
             self.loops.append(lp)
         self.agents = [lp.agent for lp in self.loops]
         self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
                                          seeds=self.seeds, n_steps=n_steps if nstep else None)
-        self._learn_from = 1 + self.n_step_max     # (DDPGRollout._learn_from / _warm_steps, for the largest n)
-        self._warm_steps = max(4, self._learn_from)
+        self._learn_from, self._warm_steps = learn_start(self.n_step_max)      # (the largest n decides for every agent)
         self.graph_steps = int(graph_steps) if graph_steps else 0
-        self.graph1 = self.graphG = None
-        self._graph_epoch = None
+        self.graph1 = self.graphG = self._graph_key = None
         self.vector_steps = 0
 
     @property
     def k(self):
         return self.loops[0].ring.k
 
-    def _body(self):
+    def _body(self, learn=True):
         """One population vector step's launches (no host work): what the graphs hold."""
         for lp in self.loops:
-            lp._open_step(False)
-            lp._act_and_step()
-        for u in range(self.updates_per_step):
+            lp.open_step()
+            lp.act_and_step()
+        for u in range(self.updates_per_step if learn else 0):
             self.learner.learn(u)
+
+    def _advance(self, steps):
+        for lp in self.loops:
+            lp.advance(steps)
+        self.vector_steps += steps
 
     def _check_handover(self):
         """A launch that gave up waiting in device memory -- a tail weight workgroup for its dQ/da, or a policy launch for its image
@@ -288,27 +284,18 @@ class PopulationRollout:
 
     def step(self):
         """One population vector step, launched eagerly."""
-        learn = self.k + 1 >= self._learn_from      # (DDPGRollout.learn(): no update before 1 + n steps are stored)
-        for lp in self.loops:
-            lp._open_step(False)
-            lp._act_and_step()
-            lp.ring.advance()
-            lp.vector_steps += 1
-        if learn:
-            for u in range(self.updates_per_step):
-                self.learner.learn(u)
-        self.vector_steps += 1
+        self._body(learn=self.k + 1 >= self._learn_from)      # (as a lone loop's learn(): no update before 1 + n steps are stored)
+        self._advance(1)
         self._check_handover()
 
     def invalidate_graphs(self):
         self.graph1 = self.graphG = None
 
     def _check_epoch(self):
-        from ddpg_trucktrailer_amd import fused
-        epoch = tuple((getattr(lp.env, "graph_epoch", 0), lp.ring.side_epoch, fused.packed_key_of(lp.agent.actor)) for lp in self.loops)
-        if self._graph_epoch != epoch:
+        key = tuple(lp.graph_key() for lp in self.loops)
+        if self._graph_key != key:
             self.invalidate_graphs()
-            self._graph_epoch = epoch
+            self._graph_key = key
 
     def _capture(self, steps):
         side = torch.cuda.Stream(device=self.device)
@@ -336,10 +323,7 @@ class PopulationRollout:
                 else:
                     self.graph1.replay()
                     done = 1
-                for lp in self.loops:
-                    lp.ring.k += done                  # host mirror; the step kernels advanced k_dev
-                    lp.vector_steps += done
-                self.vector_steps += done
+                self._advance(done)
                 k -= done
                 self._check_handover()
             else:
@@ -347,7 +331,7 @@ class PopulationRollout:
                 k -= 1
 
     def drain_episodes(self):
-        """[agent: its env's episode log since the last drain (DDPGRollout.drain_episodes)]."""
+        """[agent: its env's episode log since the last drain (VectorStepper.drain_episodes)]."""
         return [lp.drain_episodes() for lp in self.loops]
 
     def exploit(self, pairs):

@@ -3,8 +3,32 @@
 ReplayBuffer mirrors DDPG/replay_buffer.py:3-34 (store_transition / sample_buffer, uniform sampling WITH
 replacement through numpy's global RNG) with the storage on the device in float32 instead of float64 host
 arrays.  TrajectoryRing is the vector form used by the N-env loop: the env kernel writes straight into it."""
+import ctypes as C
+
 import numpy as np
 import torch
+
+from ddpg_trucktrailer_amd import _lib as L
+
+
+def check_n_step(n):
+    """int(n) when an n-step draw can have that n, 1 .. TT_NSTEP_MAX (include/ttenv.h); a ValueError otherwise."""
+    n = int(n)
+    if not 1 <= n <= L.NSTEP_MAX:
+        raise ValueError(f"n_step = {n} is outside 1 .. {L.NSTEP_MAX}")
+    return n
+
+
+def slots_needed(n_step, reserve=0):
+    """Ring slots an n-step draw needs, as the kernels ask: a base step with all its n steps inside the window, which leaves out
+    the slot being written and the `reserve` newest ones (a pipelined draw's)."""
+    return 3 + reserve + (n_step - 1)
+
+
+def learn_start(n_step):
+    """(learn_from, warm_steps): learn() starts at the vector step whose window holds a base step with its n steps (n = 1:
+    step 2), and whole-step graphs, which always learn, after the eager steps that warm the loop up."""
+    return 1 + n_step, max(4, 1 + n_step)
 
 
 class ReplayBuffer:
@@ -107,10 +131,10 @@ class TrajectoryRing:
     def slot(self, k=None):
         return (self.k if k is None else k) % self.slots
 
-    def advance(self):
-        self.k += 1
-        if not self._env_counts:
-            self.k_dev += 1
+    def advance(self, steps=1):
+        self.k += steps                         # host mirror
+        if not self._env_counts:                # (else the env's step kernels advanced k_dev, under graph replays too)
+            self.k_dev += steps
 
     # ---- expert / stand-alone transitions ---------------------------------------------------------------
     def load_side(self, obs, act, rew, obs2, done, capacity=None):
@@ -143,7 +167,6 @@ class TrajectoryRing:
         return k
 
     def _side_struct(self):
-        from ddpg_trucktrailer_amd import _lib as L
         if self.side is None or self.side_count == 0:
             return None
         sd = self.side
@@ -210,7 +233,6 @@ class TrajectoryRing:
             self._gave_up_np[0] = 0
 
     def view(self):
-        from ddpg_trucktrailer_amd import _lib as L
         return L.TTRingView(self.cursor_dev.data_ptr(), self.obs.data_ptr(), self.act.data_ptr(), self.rew.data_ptr(),
                             self.done.data_ptr(), self.n, self.slots)
 
@@ -218,7 +240,6 @@ class TrajectoryRing:
         """tt_ring_cursor for a step's opening launch; counter: the device step counter to take the step number from (default:
         the ring's own; a loop whose opening launch may run before the previous env step has advanced that one passes its
         own count of opened steps)."""
-        from ddpg_trucktrailer_amd import _lib as L
         return L.TTRingCursor((self.k_dev if counter is None else counter).data_ptr(), self.slots, 0, self.cursor_dev.data_ptr())
 
     def _batch_bufs(self, batch_size):
@@ -240,12 +261,10 @@ class TrajectoryRing:
         into rows [u * batch_size, (u + 1) * batch_size) of the buffers _batch_bufs(draws * batch_size).
         wait_for_steps (tt_mlp_forward_multi_sampled only): the launch first waits, in device memory, until the step chain has
         reached step *k_dev - 1 (cursor word 16, written by every ring-addressed policy launch): tt_sample_args.step_progress."""
-        from ddpg_trucktrailer_amd import _lib as L
         s, a, r, s2, dn, idx = self._batch_bufs(batch_size * max(1, int(draws)))
         p = lambda t: t.data_ptr()
         side = self._side_struct()
         self._side_keep = side
-        import ctypes as C
         return L.TTSampleArgs(batch_size, self.n, self.slots, int(reserve), p(self.k_dev if k_dev is None else k_dev),
                               p(self.obs), p(self.act), p(self.rew), p(self.done), int(seed) & (2 ** 64 - 1),
                               C.pointer(side) if side is not None else None, p(s), p(a), p(r), p(s2), p(dn), p(idx), int(lag),
@@ -254,9 +273,7 @@ class TrajectoryRing:
 
     @staticmethod
     def _check_n_step(n_step, gamma):
-        n_step = int(n_step)
-        if not 1 <= n_step <= 16:                        # TT_NSTEP_MAX
-            raise ValueError(f"n_step = {n_step} is outside 1 .. 16")
+        n_step = check_n_step(n_step)
         if n_step > 1 and (gamma is None or not 0.0 < float(gamma) < 1.0):
             raise ValueError(f"n_step = {n_step} needs gamma in (0, 1), not {gamma}")
         return n_step
@@ -271,8 +288,6 @@ class TrajectoryRing:
         n_step > 1 (with gamma): n-step tuples (tt_ring_sample_nstep) -- r is the discounted sum of up to n rewards from a base
         step that has its n steps inside the window, s2 the observation where the sum stops and done whether an episode's end
         stopped it; the TD target then discounts q' by gamma ** n_step."""
-        import ctypes as C
-        from ddpg_trucktrailer_amd import _lib as L
         if self._check_n_step(n_step, gamma) > 1:
             args = self.sample_args(batch_size, seed=seed, k_dev=k_dev, reserve=reserve, lag=lag)
             s, a, r, s2, dn, idx = self._bufs
@@ -325,7 +340,7 @@ class TrajectoryRing:
     def _sample_nstep(self, batch_size, generator, n_step, gamma, return_index):
         if self.side is not None and self.side_count > 0:
             raise ValueError("an n-step draw (n_step > 1) from a ring with side tuples is not supported")
-        if self.slots < 3 + (n_step - 1):
+        if self.slots < slots_needed(n_step):
             raise ValueError(f"a ring of {self.slots} slots has no window for n_step = {n_step}")
         dev = self.device
         u = torch.rand((2, batch_size), device=dev, generator=generator)

@@ -7,6 +7,8 @@ Per vector step, for all N envs of this rank at once:
     remember(obs, a, r, obs', done)                (a = the UNCLIPPED noisy action, trainv2.py:525):
                                                    obs', r, done are written by the kernel straight into the ring
     learn() x updates_per_step                     (gradient steps, each on a fresh batch from the ring)
+The acting half of a step (env, networks, ring, noise; the opening pack, the policy launch, the env step) is the VectorStepper this
+loop inherits (stepper.py).  Here: the learner and its draws, both orders, the data-parallel segments, the graphs, the checkpoint.
 Everything stays on the device.  run(k) replays hipGraphs of whole vector steps (policy, env step and learn(): seven to
 nine launches per step with no host in between): graphs of `graph_steps`, 4 and 1 steps serve every
 ring position (the launches find the step's ring slots through a device cursor), so that no step of a run() is launched
@@ -31,16 +33,13 @@ the end of every step, which is stricter; no launch reads what a concurrent one 
 resumed run still agree bit for bit."""
 import contextlib
 import gc
-import math
 import os
 
-import numpy as np
 import torch
 
 from ddpg_trucktrailer_amd import fused
-from ddpg_trucktrailer_amd.agent import Agent
-from ddpg_trucktrailer_amd.noise import VecOUNoise
-from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
+from ddpg_trucktrailer_amd.replay_buffer import check_n_step, learn_start, slots_needed
+from ddpg_trucktrailer_amd.stepper import VectorStepper
 
 
 # every launch of a capture comes from the capturing thread; "thread_local" keeps another thread's runtime calls (the
@@ -51,7 +50,6 @@ _SEED_STRIDE = 0x9E3779B97F4A7C15     # sampling key of update u of a vector ste
 # Pipelined order: learn() of vector step t draws from the steps up to t-2 (lag 1: step t-1 may still be under way beside the
 # draw) and keeps off the two observation rows the env steps t-1 and t write meanwhile (reserve 2)
 _PIPE_LAG, _PIPE_RESERVE = 1, 2
-_NSTEP_MAX = 16                         # TT_NSTEP_MAX (include/ttenv.h)
 
 
 @contextlib.contextmanager
@@ -69,7 +67,7 @@ def _gc_off():
             gc.enable()
 
 
-class DDPGRollout:
+class DDPGRollout(VectorStepper):
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99,
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
@@ -87,36 +85,25 @@ class DDPGRollout:
         buffers itself through IPC-opened device memory behind a flag barrier (include/ttenv.h: tt_p2p_*; fused learner only).
         A step is then one hipGraph of plain kernel launches on any backend, and data_parallel=True works without a process
         group at world size 1.
-        episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
-        before any step or capture: every episode that ends in the loop is logged by the env step kernel, with end_step = the
-        loop's vector step; drain_episodes() collects the records.  episode_log_detail: the detailed log (each record also
-        carries its episode's sum of every reward term and its start pose; episode_metrics.py reads them).
+        agent, policy_workgroups, policy_capped_grids, episode_log, episode_log_detail: the stepper's (stepper.py).
         n_step: 1 = the one-step TD target, launch for launch what the loop did before the option existed.  n > 1 (up to
         TT_NSTEP_MAX): n-step returns from the ring (include/ttenv.h: tt_ring_sample_nstep) -- every update
         makes its own draw in learn()'s first launch, and learn() starts once a base step with all its n steps is in the window.
         Not together with side (expert) tuples, data-parallel ranks or a ring too short for the window."""
-        self.env, self.n, self.device = env, env.n_envs, env.device
-        if episode_log:
-            env.enable_episode_log(int(episode_log), detail=episode_log_detail)
-        self.batch_size = batch_size
-        self.n_step = int(n_step)
-        if not 1 <= self.n_step <= _NSTEP_MAX:
-            raise ValueError(f"n_step = {n_step} is outside 1 .. {_NSTEP_MAX}")
-        if self.n_step > 1 and replay_slots < 3 + (self.n_step - 1):
+        self.n_step = check_n_step(n_step)
+        if self.n_step > 1 and replay_slots < slots_needed(self.n_step):
             raise ValueError(f"n_step = {self.n_step} with replay_slots = {replay_slots} is not supported: the window of base steps "
-                             f"with their n steps intact needs at least {3 + self.n_step - 1} slots")
+                             f"with their n steps intact needs at least {slots_needed(self.n_step)} slots")
         self.updates_per_step = int(updates_per_step)
         assert self.updates_per_step >= 1
-        torch.manual_seed(seed)
-        self.gen = torch.Generator(device=self.device)
-        self.gen.manual_seed(seed)
         self.dp = (world_size > 1) if data_parallel is None else bool(data_parallel)
         if self.n_step > 1 and self.dp:
             raise ValueError("n_step > 1 with data-parallel ranks is not supported (the ranks' segments draw through the one-step sampler)")
-        self.agent = agent if agent is not None else Agent(
-            alpha=alpha, beta=beta, input_dims=(env.observation_dim,), tau=tau, n_actions=1, gamma=gamma,
-            fc1_dims=fc1_dims, fc2_dims=fc2_dims, batch_size=batch_size, device=self.device,
-            capturable=use_graph, replay=False)
+        super().__init__(env, batch_size=batch_size, replay_slots=replay_slots, seed=seed, alpha=alpha, beta=beta, tau=tau, gamma=gamma,
+                         fc1_dims=fc1_dims, fc2_dims=fc2_dims, agent=agent, capturable=use_graph, policy_workgroups=policy_workgroups,
+                         policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail)
+        self.batch_size = batch_size
+        self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
         self.dp_exchange = dp_exchange or os.environ.get("TT_DP_EXCHANGE", "collective")
         assert self.dp_exchange in ("collective", "p2p"), self.dp_exchange
         if self.dp and self._have_group():
@@ -129,18 +116,6 @@ class DDPGRollout:
         if self.dp and graph_collectives:
             import torch.distributed as dist
             self.dp_single_graph = dist.is_initialized() and dist.get_backend() == "nccl"
-        self.ring = TrajectoryRing(self.n, replay_slots, env.observation_dim, self.device)
-        if self.device.type == "cuda":
-            self.ring.attach(env)                          # the step kernel advances the ring's device counter
-        self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
-        self.noise = VecOUNoise(self.n, self.device)
-        self.high = float(np.float32(math.pi / 4))       # env.action_space.high (f32 pi/4, simv2.py:86-91)
-        self.scaled = torch.zeros(self.n, dtype=torch.float32, device=self.device)
-        # the first observation of every env goes into slot 0
-        env.observe(out=self.ring.obs[0])
-        self.seed = seed
-        self.fused_act = fused.supported(self.agent.actor)      # csrc/ttnet.hip: reference-shaped 23-400-300-1 actor
-        self.agent.fused_targets = self.fused_act and fused.supported(self.agent.target_critic)
         # hand-fused learn() (csrc/ttlearn.hip) when the networks have the reference's shapes; else torch autograd
         self.learner = None
         if fused_learn and self.fused_act and fused.supported(self.agent.critic):
@@ -173,33 +148,20 @@ class DDPGRollout:
         can_pipe = self.learner is not None and self.fused_act and self.device.type == "cuda" and replay_slots >= 3 + _PIPE_RESERVE \
             and self.ring._env_counts
         self.pipeline = can_pipe if pipeline is None else (bool(pipeline) and can_pipe)
-        # the window of base steps with all their n steps intact: slots - 1 - reserve - (n - 1) >= 1, as the kernels ask
-        need = 3 + (_PIPE_RESERVE if self.pipeline else 0) + (self.n_step - 1)
+        need = slots_needed(self.n_step, _PIPE_RESERVE if self.pipeline else 0)
         if self.n_step > 1 and replay_slots < need:
             raise ValueError(f"n_step = {self.n_step} with replay_slots = {replay_slots} is not supported: this order needs {need} slots")
         if self.n_step > 1 and os.environ.get("TT_FORCE_DP") == "1":
             raise ValueError("n_step > 1 with the data-parallel launch structure (TT_FORCE_DP) is not supported")
-        # learn() starts at the vector step whose window holds a base step with its n steps (both orders; n = 1: step 2), and
-        # whole-step graphs, which always learn, after the eager steps that warm the loop up
-        self._learn_from = 1 + self.n_step
-        self._warm_steps = max(4, self._learn_from)
-        self.policy_workgroups = int(os.environ.get("TT_POLICY_WG", policy_workgroups))     # (env: A/B measurements)
-        # learn() is over after about four of the policy's capped grids (~100 us): the tiles left then (N > 98304 envs) go out
-        # in one grid over all CUs
-        self.policy_capped_grids = int(os.environ.get("TT_POLICY_CAPPED_GRIDS", policy_capped_grids))
+        self._learn_from, self._warm_steps = learn_start(self.n_step)
+        self.two_images = self.pipeline         # (stepper.py: the policy reads the image its step's opening launch packed)
         self.k_pipe_dev = torch.zeros((), dtype=torch.int64, device=self.device)   # steps completed before the running one
         self._k_snap_dev = torch.zeros((), dtype=torch.int64, device=self.device)  # its value as a learn()'s first launch saw it
         self._pipe_side = None
         if self.pipeline:
             self._pipe_side = torch.cuda.Stream(device=self.device)
-        self.vector_steps = 0
-        # ring addressing: the policy and env launches find the step's ring slots through a device cursor that the step's
-        # opening pack launch writes (include/ttenv.h: tt_ring_view), not through per-slot pointers -- so ONE captured
-        # graph serves every ring position: a single-step graph and a graph of `graph_steps` steps are all there is
-        self.ring_mode = self.fused_act and self.device.type == "cuda" and self.ring._env_counts
-        self._view = self.ring.view() if self.ring_mode else None
         if self.ring_mode and self.pipeline:     # both policy images exist before the first opening launch writes one of them
-            fused.packed_weights_of(self.agent.actor, 0, self.policy_workgroups, self.policy_capped_grids, two_images=True)
+            self._image()
         ok = self.use_graph and self.learner is not None and graph_steps and self.ring_mode
         self.graph_steps = int(graph_steps) if ok else 0
         if self.graph_steps and self.dp and not self.dp_single_graph:
@@ -208,7 +170,7 @@ class DDPGRollout:
         self.graph1 = None              # one vector step (data-parallel: up to the critic's gradient)
         self.graphG = None              # graph_steps vector steps (one rank)
         self.dp_graphs = None
-        self._graph_epoch = None        # env.graph_epoch the captures were made under
+        self._graph_key = None          # the stepper's graph_key() the captures were made under
         # hand-overs through device memory (policy image, step progress) are bounded waits: a launch that gives up goes on with
         # stale inputs.  The loop notices (_check_handover), falls back to graph edges once, and raises the second time
         self.handover_gave_up = []      # steps (+1) at which a launch gave up, in the order they were noticed
@@ -218,25 +180,6 @@ class DDPGRollout:
     def _have_group():
         import torch.distributed as dist
         return dist.is_available() and dist.is_initialized()
-
-    # -------------------------------------------------------------- acting
-    @torch.no_grad()
-    def act(self, obs, act_out, done_prev=None, k=None):
-        if self.fused_act:     # actor forward + OU noise + clip*high in ONE launch (tt_actor_act)
-            w = None
-            if self.pipeline:  # the image packed at the start of this step, never the live weights learn() is updating
-                w = fused.packed_weights_of(self.agent.actor, 0, self.policy_workgroups, self.policy_capped_grids, two_images=True)
-            if self.ring._env_counts:      # noise keyed by the DEVICE step counter: the launch is graph-replayable
-                return fused.actor_act(self.agent.actor, obs, self.noise.x, act_out, self.scaled, seed=self.seed,
-                                       step=0, step_dev=self.ring.k_dev, done_prev=done_prev, high=self.high, weights=w)
-            return fused.actor_act(self.agent.actor, obs, self.noise.x, act_out, self.scaled, seed=self.seed,
-                                   step=self.vector_steps, done_prev=done_prev, high=self.high, weights=w)
-        if done_prev is not None:
-            self.noise.reset(done_prev)
-        mu = self.agent.actor(obs).view(-1)
-        torch.add(mu, self.noise.sample(), out=act_out)                   # stored action: unclipped mu + noise
-        torch.clamp(act_out, -1.0, 1.0, out=self.scaled).mul_(self.high)  # what the env is driven with
-        return self.scaled
 
     # -------------------------------------------------------------- learning
     def _sample(self, u):
@@ -255,7 +198,7 @@ class DDPGRollout:
     def _image_job(self):
         """What lets learn()'s second launch carry the pack of the step's policy image (fused_learn.phase_a: image)."""
         from ddpg_trucktrailer_amd import _lib as L
-        w = fused.packed_weights_of(self.agent.actor, 0, self.policy_workgroups, self.policy_capped_grids, two_images=True)
+        w = self._image()
         cur = L.TTRingCursor(self._k_snap_dev.data_ptr(), self.ring.slots, 0, self.ring.cursor_dev.data_ptr())
         return (w, cur, self._k_snap_dev)
 
@@ -337,14 +280,12 @@ class DDPGRollout:
     def _open_step(self, learn):
         """The launch that opens a vector step: the policy's image from the actor's current weights and the ring cursor of
         the step -- in the pipelined order also the first batch of the step's learn()."""
+        sample = None
         if self.pipeline and learn and self.n_step == 1:
-            fused.pack_and_sample(self.agent.actor, 0, self.ring.sample_args(
+            sample = self.ring.sample_args(
                 self.batch_size, seed=self._sample_key(0), k_dev=self.k_pipe_dev, reserve=_PIPE_RESERVE, lag=_PIPE_LAG,
-                draws=self._draws_per_opening(), seed_stride=_SEED_STRIDE), cursor=self.ring.cursor(self.k_pipe_dev))
-        elif self.pipeline:
-            fused.pack(self.agent.actor, 0, cursor=self.ring.cursor(self.k_pipe_dev))
-        else:
-            fused.pack(self.agent.actor, 0, cursor=self.ring.cursor())
+                draws=self._draws_per_opening(), seed_stride=_SEED_STRIDE)
+        self.open_step(sample, self.k_pipe_dev if self.pipeline else None)
 
     def policy_edge(self):
         """How the policy launch of a captured step learns that its image is complete: "flag" (device memory, the default) or
@@ -401,27 +342,6 @@ class DDPGRollout:
         self.invalidate_graphs()
         return int(mark)
 
-    def policy_launch(self):
-        """The policy launch of the running step alone (ring mode; after _open_step): bench.py times it."""
-        w = fused.packed_weights_of(self.agent.actor, 0, self.policy_workgroups if self.pipeline else 0,
-                                    self.policy_capped_grids, two_images=self.pipeline)
-        return fused.actor_act_ring(self.agent.actor, self._view, w, self.noise.x, self.scaled, seed=self.seed, step=0,
-                                    step_dev=self.ring.k_dev, high=self.high)
-
-    def _act_and_step(self, k=None):
-        """The policy + env launches of the running vector step.  Ring mode: everything that selects the slots is on the
-        device (after _open_step).  Otherwise (CPU, torch actor) k selects them."""
-        if self.ring_mode:
-            self.policy_launch()
-            self.env.step_ring(self.scaled, self._view, auto_reset=True)
-            return
-        ring = self.ring
-        t, t1 = ring.slot(k), ring.slot(k + 1)
-        # the noise of an env whose episode ended at the previous step restarts at 0 (trainv2.py:492)
-        done_prev = ring.done[ring.slot(k - 1)] if k > 0 else None
-        scaled = self.act(ring.obs[t], ring.act[t], done_prev, k=k)
-        self.env.step(scaled, auto_reset=True, obs_out=ring.obs[t1], reward_out=ring.rew[t], done_out=ring.done[t])
-
     def _pipelined(self, k, learn, dp_capture=False):
         """The running vector step (number k) in the pipelined order with a JOIN at its end -- the eager form of a step, and
         the first of the three graph segments of the data-parallel fallback (captured graphs of whole steps use
@@ -441,7 +361,7 @@ class DDPGRollout:
                 self._learn_all(presampled=True)
             else:
                 self.k_pipe_dev.add_(1)                     # no learn() yet: the window still moves with the steps
-        self._act_and_step()
+        self.act_and_step()
         cur.wait_stream(side)
 
     def _check_n_step(self):
@@ -455,14 +375,13 @@ class DDPGRollout:
         if self.pipeline:
             self._check_epoch()
             self._pipelined(k, k >= self._learn_from)
-            self.ring.advance()
+            self.advance()
         else:
             if self.ring_mode:
                 self._open_step(False)
-            self._act_and_step(k)
-            self.ring.advance()
+            self.act_and_step(k)
+            self.advance()
             self.learn()
-        self.vector_steps += 1
 
     # -------------------------------------------------------------- many vector steps
     def invalidate_graphs(self):
@@ -472,13 +391,10 @@ class DDPGRollout:
         self.graph = self.graph1 = self.graphG = self.graphM = self.dp_graphs = None
 
     def _check_epoch(self):
-        # (the actor's parameter storages are part of it: the policy's packed-image struct is keyed on them, fused.py)
-        epoch = (getattr(self.env, "graph_epoch", 0), self.ring.side_epoch,
-                 fused.packed_key_of(self.agent.actor) if self.fused_act else None)
-        if self._graph_epoch != epoch:
-            if self._graph_epoch is not None:
-                self.invalidate_graphs()
-            self._graph_epoch = epoch
+        key = self.graph_key()
+        if self._graph_key != key:              # (the first look: nothing is captured yet)
+            self.invalidate_graphs()
+            self._graph_key = key
 
     def _graphs_current(self):
         self._check_epoch()
@@ -491,7 +407,7 @@ class DDPGRollout:
             self._pipelined(None, True, dp_capture=segments)
             return
         self._open_step(False)
-        self._act_and_step()
+        self.act_and_step()
         if segments:
             s, a, r, s2, d = self._sample(0)
             self.learner.phase_a(s, a, r, s2, d, fuse_adam=False)
@@ -552,7 +468,7 @@ class DDPGRollout:
                     self._learn_all(presampled=False, with_image=True, wait_for_steps=True)
             if edge:
                 cur.wait_event(opened)
-            self._act_and_step()
+            self.act_and_step()
             ev = torch.cuda.Event()
             ev.record(cur)
             stepped.append(ev)
@@ -634,14 +550,13 @@ class DDPGRollout:
     def run(self, k):
         """k vector steps, every one a graph replay once the loop is warm (4 eager steps) when whole-step graphs are on:
         the graph of graph_steps steps while that many remain, the single-step graph for the rest; eager step() otherwise."""
-        ring = self.ring
         self._check_n_step()
         if self.learner is not None:
             self.learner.refresh_images()      # fc2 written by anyone but the learner's own launches since the last look?
         while k > 0:
             self._check_handover()             # (a host-memory read; a give-up drops the graphs: captured again just below)
             G = self.graph_steps
-            if G and ring.k >= self._warm_steps and (self._graphs_current() or self._try_capture()):
+            if G and self.ring.k >= self._warm_steps and (self._graphs_current() or self._try_capture()):
                 if self.dp and not self.dp_single_graph:
                     self._dp_step()
                     done = 1
@@ -654,18 +569,12 @@ class DDPGRollout:
                 else:
                     self.graph1.replay()
                     done = 1
-                ring.k += done                  # host mirror; the step kernels advanced k_dev
-                self.vector_steps += done
+                self.advance(done)
                 k -= done
             else:
                 self.step()
                 k -= 1
         self._check_handover()
-
-    def drain_episodes(self):
-        """The env's episode log since the last drain (TruckTrailerVecEnv.drain_episodes): records sorted by (end_step, lane),
-        end_step = the vector step the episode ended in."""
-        return self.env.drain_episodes()
 
     # -------------------------------------------------------------- checkpoint / resume of the whole loop
     def state_dict(self):

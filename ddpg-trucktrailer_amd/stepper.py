@@ -1,0 +1,119 @@
+"""The acting half of a vector DDPG loop (rollout.py's docstring has the step): one agent's env of N lanes, four networks, replay
+ring and OU noise, and the launches that fill the ring -- the opening pack, the policy launch, the env step.  Nothing here learns or
+schedules: DDPGRollout (rollout.py) is a stepper with a learner and a lone loop's orders, PopulationRollout holds K steppers."""
+import math
+import os
+
+import numpy as np
+import torch
+
+from ddpg_trucktrailer_amd import fused
+from ddpg_trucktrailer_amd.agent import Agent
+from ddpg_trucktrailer_amd.noise import VecOUNoise
+from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
+
+
+class VectorStepper:
+    def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
+                 fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
+                 episode_log_detail=False):
+        """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold).
+        episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
+        before any step or capture: the env step kernel logs every episode that ends in the loop, end_step = the loop's vector
+        step, and drain_episodes() collects the records.  episode_log_detail: the detailed log (episode_metrics.py)."""
+        self.env, self.n, self.device, self.seed = env, env.n_envs, env.device, seed
+        if episode_log:
+            env.enable_episode_log(int(episode_log), detail=episode_log_detail)
+        # the order that decides the bits: the seed, the networks, the ring, the noise, the first observation
+        torch.manual_seed(seed)
+        self.agent = agent if agent is not None else Agent(
+            alpha=alpha, beta=beta, input_dims=(env.observation_dim,), tau=tau, n_actions=1, gamma=gamma,
+            fc1_dims=fc1_dims, fc2_dims=fc2_dims, batch_size=batch_size, device=self.device,
+            capturable=capturable, replay=False)
+        self.ring = TrajectoryRing(self.n, replay_slots, env.observation_dim, self.device)
+        if self.device.type == "cuda":
+            self.ring.attach(env)                          # the step kernel advances the ring's device counter
+        self.noise = VecOUNoise(self.n, self.device)
+        self.high = float(np.float32(math.pi / 4))       # env.action_space.high (f32 pi/4, simv2.py:86-91)
+        self.scaled = torch.zeros(self.n, dtype=torch.float32, device=self.device)
+        # the first observation of every env goes into slot 0
+        env.observe(out=self.ring.obs[0])
+        self.fused_act = fused.supported(self.agent.actor)      # csrc/ttnet.hip: reference-shaped 23-400-300-1 actor
+        self.agent.fused_targets = self.fused_act and fused.supported(self.agent.target_critic)
+        self.policy_workgroups = int(os.environ.get("TT_POLICY_WG", policy_workgroups))     # (env: A/B measurements)
+        # learn() is over after about four of the policy's capped grids (~100 us): the tiles left then (N > 98304 envs) go out
+        # in one grid over all CUs
+        self.policy_capped_grids = int(os.environ.get("TT_POLICY_CAPPED_GRIDS", policy_capped_grids))
+        # the policy reads one of two packed images of the actor, by the step's parity, under a capped grid: set by an owner
+        # that runs the pipelined order (rollout.py), where a step's opening launch may run beside the previous step's policy
+        self.two_images = False
+        self.vector_steps = 0
+        # ring addressing: the policy and env launches find the step's ring slots through a device cursor that the step's
+        # opening pack launch writes (include/ttenv.h: tt_ring_view), not through per-slot pointers -- so ONE captured
+        # graph serves every ring position: a single-step graph and a graph of `graph_steps` steps are all there is
+        self.ring_mode = self.fused_act and self.device.type == "cuda" and self.ring._env_counts
+        self._view = self.ring.view() if self.ring_mode else None
+
+    def _image(self):
+        """The packed actor under two_images: the image packed at the start of the step, never the live weights learn() updates."""
+        return fused.packed_weights_of(self.agent.actor, 0, self.policy_workgroups, self.policy_capped_grids, two_images=True)
+
+    @torch.no_grad()
+    def act(self, obs, act_out, done_prev=None):
+        if self.fused_act:     # actor forward + OU noise + clip*high in ONE launch (tt_actor_act)
+            w = self._image() if self.two_images else None
+            dev = self.ring._env_counts    # noise keyed by the DEVICE step counter: the launch is graph-replayable
+            return fused.actor_act(self.agent.actor, obs, self.noise.x, act_out, self.scaled, seed=self.seed,
+                                   step=0 if dev else self.vector_steps, step_dev=self.ring.k_dev if dev else None,
+                                   done_prev=done_prev, high=self.high, weights=w)
+        if done_prev is not None:
+            self.noise.reset(done_prev)
+        mu = self.agent.actor(obs).view(-1)
+        torch.add(mu, self.noise.sample(), out=act_out)                   # stored action: unclipped mu + noise
+        torch.clamp(act_out, -1.0, 1.0, out=self.scaled).mul_(self.high)  # what the env is driven with
+        return self.scaled
+
+    def open_step(self, sample=None, counter=None):
+        """The launch that opens a vector step (ring mode): the policy's image from the actor's current weights and the step's ring
+        cursor, taken from the device step count `counter` (default: the ring's own); with a tt_sample_args also that draw."""
+        cursor = self.ring.cursor(counter)
+        if sample is not None:
+            fused.pack_and_sample(self.agent.actor, 0, sample, cursor=cursor)
+        else:
+            fused.pack(self.agent.actor, 0, cursor=cursor)
+
+    def policy_launch(self):
+        """The policy launch of the running step alone (ring mode; after open_step): bench.py times it."""
+        w = fused.packed_weights_of(self.agent.actor, 0, self.policy_workgroups if self.two_images else 0,
+                                    self.policy_capped_grids, two_images=self.two_images)
+        return fused.actor_act_ring(self.agent.actor, self._view, w, self.noise.x, self.scaled, seed=self.seed, step=0,
+                                    step_dev=self.ring.k_dev, high=self.high)
+
+    def act_and_step(self, k=None):
+        """The policy + env launches of the running vector step.  Ring mode: everything that selects the slots is on the
+        device (after open_step).  Otherwise (CPU, torch actor) k selects them."""
+        if self.ring_mode:
+            self.policy_launch()
+            self.env.step_ring(self.scaled, self._view, auto_reset=True)
+            return
+        ring = self.ring
+        t, t1 = ring.slot(k), ring.slot(k + 1)
+        # the noise of an env whose episode ended at the previous step restarts at 0 (trainv2.py:492)
+        done_prev = ring.done[ring.slot(k - 1)] if k > 0 else None
+        scaled = self.act(ring.obs[t], ring.act[t], done_prev)
+        self.env.step(scaled, auto_reset=True, obs_out=ring.obs[t1], reward_out=ring.rew[t], done_out=ring.done[t])
+
+    def advance(self, steps=1):
+        """The host mirrors of `steps` launched vector steps."""
+        self.ring.advance(steps)
+        self.vector_steps += steps
+
+    def graph_key(self):
+        """What captured launches of this stepper bake in: env.graph_epoch (reset seed, per-env-goal mode, pose pool), the ring's
+        side-buffer count, and the actor's parameter storages (the policy's packed-image struct is keyed on them, fused.py)."""
+        return (getattr(self.env, "graph_epoch", 0), self.ring.side_epoch,
+                fused.packed_key_of(self.agent.actor) if self.fused_act else None)
+
+    def drain_episodes(self):
+        """The env's episode log since the last drain: records sorted by (end_step, lane), end_step = the vector step it ended in."""
+        return self.env.drain_episodes()

@@ -22,12 +22,12 @@ def timeit(fn, reps=100):
     return e0.elapsed_time(e1) / reps * 1e3
 
 def body_serial(k):
-    loop._act_and_step(k); loop._learn_all()
+    loop.act_and_step(k); loop._learn_all()
 
 def body_fork(k, s_main, s_side):
     s_side.wait_stream(s_main)
     with torch.cuda.stream(s_side):
-        loop._act_and_step(k)
+        loop.act_and_step(k)
     loop._learn_all()
     s_main.wait_stream(s_side)
 
@@ -41,7 +41,7 @@ with torch.cuda.graph(gf, stream=main, capture_error_mode="thread_local"):
     for i in range(G): body_fork(64 + 8 + i, main, side)
 ga = torch.cuda.CUDAGraph()
 with torch.cuda.graph(ga, stream=main, capture_error_mode="thread_local"):
-    for i in range(G): loop._act_and_step(64 + 8 + i)
+    for i in range(G): loop.act_and_step(64 + 8 + i)
 gl = torch.cuda.CUDAGraph()
 with torch.cuda.graph(gl, stream=main, capture_error_mode="thread_local"):
     for i in range(G): loop._learn_all()
@@ -65,7 +65,7 @@ def body_fork_rev(k, s_main, s_side):          # learn on the forked stream, pol
     s_side.wait_stream(s_main)
     with torch.cuda.stream(s_side):
         loop._learn_all()
-    loop._act_and_step(k)
+    loop.act_and_step(k)
     s_main.wait_stream(s_side)
 
 main.wait_stream(torch.cuda.current_stream())
@@ -79,7 +79,7 @@ g = capture(lambda: [body_fork_rev(64 + 8 + i, main, hi) for i in range(4)])
 print(f"forked graph, learn on a high-priority side stream: {timeit(g.replay) / 4:.1f} us/step")
 # host-driven: one graph per branch per step on two streams, events between them
 sa, sb = torch.cuda.Stream(), torch.cuda.Stream(priority=-1)
-ga1 = capture(lambda: loop._act_and_step(72))
+ga1 = capture(lambda: loop.act_and_step(72))
 gl1 = capture(lambda: loop._learn_all())
 torch.cuda.current_stream().wait_stream(main)
 ea, eb = torch.cuda.Event(), torch.cuda.Event()

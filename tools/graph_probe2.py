@@ -27,20 +27,20 @@ def variant(kind, k):
         fused.pack(loop.agent.actor, 0)
         side.wait_stream(cur)
         with torch.cuda.stream(side): loop._learn_all()
-        loop._act_and_step(k)
+        loop.act_and_step(k)
         cur.wait_stream(side)
     elif kind == "event":                 # fork, pack on the policy branch, event into the middle of learn()
         side.wait_stream(cur)
         fused.pack(loop.agent.actor, 0)
         ev = torch.cuda.Event(); ev.record(cur)
         with torch.cuda.stream(side): loop._learn_all(before_actor=lambda: side.wait_event(ev))
-        loop._act_and_step(k)
+        loop.act_and_step(k)
         cur.wait_stream(side)
     elif kind == "no_edge":               # as "event" without the edge (NOT race-free; timing only)
         side.wait_stream(cur)
         fused.pack(loop.agent.actor, 0)
         with torch.cuda.stream(side): loop._learn_all()
-        loop._act_and_step(k)
+        loop.act_and_step(k)
         cur.wait_stream(side)
 
 main.wait_stream(torch.cuda.current_stream())
