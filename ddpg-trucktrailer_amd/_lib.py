@@ -116,6 +116,16 @@ class TTPopNstep(C.Structure):
     _fields_ = [("n_step", C.c_int32), ("gamma", C.c_float), ("discount", C.c_float)]
 
 
+class TTLearnLogJob(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
+               [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
+
+
+# the values of a learn-log record (TT_LEARN_LOG_NVALUES, include/ttenv.h: tt_learn_log_drain), in their order
+LEARN_LOG_VALUES = ("critic_loss", "actor_loss", "q_mean", "q_min", "q_max", "y_mean", "y_min", "y_max", "td_abs_mean", "td_abs_max",
+                    "dq_da_abs_mean", "dq_da_abs_max", "mu_abs_mean", "gate_mean", "grad_norm_critic", "grad_norm_actor")
+LEARN_LOG_CHUNKS = 16                   # TT_LEARN_LOG_CHUNKS
+LEARN_LOG_MAX_CAPACITY = 1 << 22        # TT_LEARN_LOG_MAX_CAPACITY
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 NSTEP_MAX = 16          # TT_NSTEP_MAX
 
@@ -207,6 +217,11 @@ _SIGNATURES = {
     "tt_pop_learn_set_nstep": (C.c_int, [_P, C.POINTER(TTPopNstep)]),
     "tt_pop_exploit_nstep": (C.c_int, [_P, _I, C.POINTER(TTPopExploitPair), C.POINTER(TTPopNstep), _P]),
     "tt_pop_nstep": (C.c_int, [_P, _I, C.POINTER(TTPopNstep)]),
+    "tt_learn_log_create": (C.c_int, [_I, _I, C.POINTER(TTLearnLogJob), C.c_int64, C.c_int32, C.POINTER(_P)]),
+    "tt_learn_log_append": (C.c_int, [_P, _P]),
+    "tt_learn_log_drain": (C.c_int, [_P, _I, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
+    "tt_learn_log_clear": (C.c_int, [_P, _P]),
+    "tt_learn_log_destroy": (C.c_int, [_P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

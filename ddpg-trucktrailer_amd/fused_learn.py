@@ -107,6 +107,84 @@ def nstep_discount(gamma, n_step):
     return float(gamma) if n_step == 1 else float(gamma) ** int(n_step)
 
 
+def check_learn_log(capacity, every=1):
+    """The (capacity, every) of a learn log, or ValueError: what every constructor that takes learn_log= / learn_log_every= refuses."""
+    capacity, every = int(capacity), int(every)
+    if not 1 <= capacity <= L.LEARN_LOG_MAX_CAPACITY:
+        raise ValueError(f"learn_log = {capacity} records is not in [1, {L.LEARN_LOG_MAX_CAPACITY}]")
+    if every < 1:
+        raise ValueError(f"learn_log_every = {every} is not >= 1")
+    return capacity, every
+
+
+class LearnLog:
+    """The learn log of one or more FusedLearners that take their updates together (include/ttenv.h: tt_learn_log_*): one record
+    per update and agent with the losses, the Q / TD-target / dQ/da / mu statistics, both gradient norms and a non-finite count,
+    reduced on the device by one capturable launch behind the update.  A ring of the latest `capacity` records per agent; an update
+    whose step count is no multiple of `every` leaves none.  Not part of any checkpoint."""
+
+    def __init__(self, learners, capacity, every=1):
+        import numpy as np
+        self._np = np
+        self.capacity, self.every = check_learn_log(capacity, every)
+        self.learners = list(learners)
+        self.lib = L.load()
+        jobs = (L.TTLearnLogJob * len(self.learners))()
+        for j, fl in zip(jobs, self.learners):
+            if fl.grad_sync_critic is not None or fl.p2p is not None:
+                raise ValueError("a learn log with data-parallel ranks is not supported: a rank's own gradient buffer is not what "
+                                 "its optimizer applies")
+            j.y, j.q, j.q_pi, j.dq_da, j.mu = (t.data_ptr() for t in (fl.y, fl.q, fl.q_pi, fl.dq_da, fl.mu))
+            j.grad_critic, j.grad_actor = fl.critic.flat_grad.data_ptr(), fl.actor.flat_grad.data_ptr()
+            j.numel_critic, j.numel_actor = fl.critic.flat_grad.numel(), fl.actor.flat_grad.numel()
+            j.step_dev = fl.step_dev.data_ptr()
+        h = C.c_void_p()
+        L.check(self.lib.tt_learn_log_create(len(self.learners), self.learners[0].B, jobs, self.capacity, self.every, C.byref(h)))
+        self._h = h
+        self.reset_cursors()
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and L._lib is not None:
+            torch.cuda.synchronize()
+            L._lib.tt_learn_log_destroy(self._h)
+            self._h = None
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.learners[0].dev).cuda_stream)
+
+    def append(self):
+        """The one launch, on the current stream (capturable): a record of what the update before it on this stream left."""
+        L.check(self.lib.tt_learn_log_append(self._h, self._stream()))
+
+    def reset_cursors(self):
+        """Each agent's drain cursor to its step count now (synchronises)."""
+        self.cursor = [int(fl.step_dev.item()) for fl in self.learners]
+
+    def clear(self):
+        """Every slot empty and every drain cursor at its agent's step count now: after a step counter was set back."""
+        L.check(self.lib.tt_learn_log_clear(self._h, self._stream()))
+        self.reset_cursors()
+
+    def drain(self, a=0):
+        """Agent a's records newer than its last drain, oldest first: {"step": int64[n], "nonfinite": int32[n], one float64[n] per
+        name of _lib.LEARN_LOG_VALUES, "dropped": int} -- dropped = the updates since the last drain that should have left a record
+        (steps divisible by `every`) minus the records found: overwritten in the ring before anyone drained them.  Synchronises."""
+        np = self._np
+        cap, after = self.capacity, self.cursor[a]
+        step, bad = np.empty(cap, np.int64), np.empty(cap, np.int32)
+        vals = np.empty((len(L.LEARN_LOG_VALUES), cap), np.float64)
+        n = C.c_int64(0)
+        L.check(self.lib.tt_learn_log_drain(self._h, int(a), after, cap, step.ctypes.data, vals.ctypes.data, bad.ctypes.data, C.byref(n)))
+        n = int(n.value)
+        now = int(self.learners[a].step_dev.item())         # (the drain waited for the device: every update up to `now` is in)
+        out = {"step": step[:n].copy(), "nonfinite": bad[:n].copy()}
+        for name, col in zip(L.LEARN_LOG_VALUES, vals):
+            out[name] = col[:n].copy()
+        out["dropped"] = max(0, now // self.every - after // self.every) - n
+        self.cursor[a] = max(now, after)
+        return out
+
+
 class FusedLearner:
     def __init__(self, agent, batch_size, fc2_images=None):
         """fc2_images (None = on unless TT_LEARN_F32=1): the 400 x 300 products of learn() on the f16 MFMA from pre-split
@@ -141,6 +219,7 @@ class FusedLearner:
         self.z_t = torch.empty((B, 300), **f)          # the target critic's state branch on s' (before the action enters)
         self.grad_sync_critic = self.grad_sync_actor = None
         self.p2p = None                    # the peer-to-peer gradient exchange (enable_p2p), a tt_p2p handle
+        self.learn_log = None              # the learn log (enable_learn_log), a LearnLog of this one learner
         # learn()'s last two launches in ONE grid (tt_mlp_actor_tail): dQ/da is handed to the actor's weight-gradient workgroups in
         # device memory.  For the configurations learn() bounds (a small policy launch, several updates per step): its 200 waiting
         # workgroups would crowd a policy launch that owns 171 CUs.  Set by the loop (DDPGRollout), off by default.
@@ -228,6 +307,7 @@ class FusedLearner:
         """Mean of the flat gradient buffers over the ranks at the reference's two optimizer sites (RCCL: one AVG
         all-reduce per site, straight on the flat buffer; other backends: SUM, then a divide)."""
         import torch.distributed as dist
+        self._refuse_ranks_with_learn_log()
         world = dist.get_world_size(group)
         avg = dist.get_backend(group) == "nccl"
 
@@ -249,6 +329,7 @@ class FusedLearner:
         (no process group needed) runs the same launches against this rank's own block.  Call before anything is captured."""
         import os
         import torch.distributed as dist
+        self._refuse_ranks_with_learn_log()
         if timeout_s is None:      # (default here: 10 s -- the first launches of a process load its kernels, and the ranks do that at
             timeout_s = float(os.environ.get("TT_P2P_TIMEOUT_S", "10"))      # their own pace; the library's own default is 2 s)
         have = dist.is_available() and dist.is_initialized()
@@ -274,6 +355,34 @@ class FusedLearner:
         for site, st in enumerate((self.critic, self.actor)):
             st.bind_flat_grad(_device_view(self.lib.tt_p2p_grad(h, site), st.flat_grad.numel(), self.dev, owner=self))
         self.grad_sync_critic = self.grad_sync_actor = _no_sync       # (learn_batch's data-parallel order: separate Adam launches)
+
+    # ---- learn log -----------------------------------------------------------------------------------------------
+    def _refuse_ranks_with_learn_log(self):
+        if self.learn_log is not None:
+            raise ValueError("data-parallel ranks with a learn log are not supported: a rank's own gradient buffer is not what its "
+                             "optimizer applies")
+
+    def enable_learn_log(self, capacity, every=1):
+        """Turn the learn log on (LearnLog; include/ttenv.h: tt_learn_log_*): from now on learn_batch ends with one more launch
+        that leaves a record of the update -- critic and actor loss, Q / TD-target / |TD| / |dQ/da| / mu statistics, both gradient
+        norms, a non-finite count -- in a ring of the latest `capacity` records in device memory, for every update whose step
+        count is a multiple of `every`.  Capturable: call it before anything is captured.  drain_learn_log() collects the records.
+        The log is NOT part of a checkpoint (state_dict): load_state_dict empties it.  Not with data-parallel ranks."""
+        if self.learn_log is not None:
+            raise ValueError("the learn log is already on")
+        self.learn_log = LearnLog([self], capacity, every)
+
+    def append_learn_log(self):
+        """The learn log's launch alone, on the current stream: a record of whatever the learner's buffers hold now."""
+        if self.learn_log is None:
+            raise ValueError("the learn log is off (enable_learn_log)")
+        self.learn_log.append()
+
+    def drain_learn_log(self):
+        """The records newer than the last drain as a dict of numpy columns, and "dropped" (LearnLog.drain).  Synchronises."""
+        if self.learn_log is None:
+            raise ValueError("the learn log is off (enable_learn_log)")
+        return self.learn_log.drain(0)
 
     def tail_gave_up(self):
         """0, or the learn step at which a weight-gradient workgroup of tt_mlp_actor_tail stopped waiting for dQ/da (that learn() is
@@ -415,6 +524,8 @@ class FusedLearner:
         n_step: see phase_a (n-step returns; 1 = the one-step learn(), launch for launch)."""
         assert states.shape[0] == self.B and done_u8.dtype == torch.uint8
         dp = self.grad_sync_critic is not None
+        if dp:
+            self._refuse_ranks_with_learn_log()
         assert image is None or sample is not None
         self.phase_a(states, actions, rewards, states_, done_u8, fuse_adam=not dp, window_dev=window_dev, sample=sample, image=image, n_step=n_step)
         if dp:
@@ -423,10 +534,12 @@ class FusedLearner:
         if dp:
             self.grad_sync_actor()
             self.phase_c()
+        if self.learn_log is not None:
+            self.learn_log.append()
 
     # ---- checkpoint ---------------------------------------------------------------------------------------------
     def state_dict(self):
-        """Adam moments of both networks (flat, tt_mlp_weights order) and the learn-step count."""
+        """Adam moments of both networks (flat, tt_mlp_weights order) and the learn-step count.  (The learn log is not in it.)"""
         return {"step": int(self.step_dev.item()),
                 "actor": {"m": self.actor.m.cpu(), "v": self.actor.v.cpu()},
                 "critic": {"m": self.critic.m.cpu(), "v": self.critic.v.cpu()}}
@@ -438,6 +551,8 @@ class FusedLearner:
         self.step_dev.fill_(int(sd["step"]))
         self.tail_words.fill_(-1)          # (tt_mlp_actor_tail: words of an earlier run must not match a step number set back)
         self.p2p_reset()
+        if self.learn_log is not None:     # (a step counter set back must not meet records from its future)
+            self.learn_log.clear()
 
     # ---- checkpoint interoperability with the torch optimizers ------------------------------------------
     def export_to_optimizers(self):
@@ -453,3 +568,5 @@ class FusedLearner:
                 if s:
                     m.copy_(s["exp_avg"].reshape(-1)); v.copy_(s["exp_avg_sq"].reshape(-1))
                     self.step_dev.fill_(int(float(s["step"])))
+        if self.learn_log is not None:
+            self.learn_log.clear()

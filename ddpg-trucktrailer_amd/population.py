@@ -22,7 +22,7 @@ import ctypes as C
 import torch
 
 from ddpg_trucktrailer_amd import _lib as L
-from ddpg_trucktrailer_amd.fused_learn import FusedLearner, nstep_discount
+from ddpg_trucktrailer_amd.fused_learn import FusedLearner, LearnLog, check_learn_log, nstep_discount
 from ddpg_trucktrailer_amd.replay_buffer import check_n_step, learn_start, slots_needed
 from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, _gc_off
 from ddpg_trucktrailer_amd.stepper import VectorStepper
@@ -35,9 +35,12 @@ class PopulationLearner:
     every buffer and parameter storage must stay where it is from then on.
     n_steps: None = the one-step population, launch for launch; one int or one value per agent = n-step returns (include/ttenv.h:
     tt_pop_learn_set_nstep).  Any n > 1, or a list (also of ones), makes the per-agent table, and learn()'s first launch is then the
-    n-step kernel for good.  Host mirrors: self.n_steps, and each agent's ring.n_step."""
+    n-step kernel for good.  Host mirrors: self.n_steps, and each agent's ring.n_step.
+    learn_log: None, or the capacity per agent of the learn log (fused_learn.LearnLog; include/ttenv.h: tt_learn_log_*): learn()
+    then ends with one more launch that leaves a record of every agent's update whose step count is a multiple of learn_log_every,
+    and drain_learn_log() collects them.  One K-agent handle, made with the descriptors.  Not part of any checkpoint."""
 
-    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None):
+    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1):
         self.K, self.B = len(agents), int(batch_size)
         if not 1 <= self.K <= L.POP_MAX_AGENTS:
             raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
@@ -51,6 +54,8 @@ class PopulationLearner:
             if ring.slots < slots_needed(n):
                 raise ValueError(f"agent {a}: n_step = {n} with a ring of {ring.slots} slots is not supported: the window of base "
                                  f"steps with their n steps intact needs at least {slots_needed(n)} slots")
+        self._learn_log_args = check_learn_log(learn_log, learn_log_every) if learn_log is not None else None
+        self.learn_log = None
         self.lib = L.load()
         self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
         for ring, n in zip(self.rings, self.n_steps):
@@ -94,6 +99,8 @@ class PopulationLearner:
         if self.nstep_table:
             ns = (L.TTPopNstep * self.K)(*[self._nstep_struct(ag.gamma, n) for ag, n in zip(self.agents, self.n_steps)])
             L.check(self.lib.tt_pop_learn_set_nstep(h, ns))
+        if self._learn_log_args is not None:       # (rebuilt with the descriptors: a fresh, empty ring)
+            self.learn_log = LearnLog(self.learners, *self._learn_log_args)
 
     @staticmethod
     def _nstep_struct(gamma, n):
@@ -115,6 +122,17 @@ class PopulationLearner:
         if not capturing:
             self.refresh_images()
         L.check(self.lib.tt_pop_learn(self._h, int(u), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        if self.learn_log is not None:
+            self.learn_log.append()
+
+    def drain_learn_log(self):
+        """[agent: its learn-log records since the last drain, a dict of numpy columns and "dropped" (fused_learn.LearnLog.drain)].
+        Before the first learn() there is no log yet: no records."""
+        if self._learn_log_args is None:
+            raise ValueError("the learn log is off (PopulationLearner(learn_log=...))")
+        if self.learn_log is None:
+            return [_no_records() for _ in range(self.K)]
+        return [self.learn_log.drain(a) for a in range(self.K)]
 
     def tail_gave_up(self):
         """[agent: 0, or the learn step whose tail hand-over was abandoned] (host memory only)."""
@@ -191,6 +209,13 @@ class PopulationLearner:
         return int(out.n_step), float(out.gamma), float(out.discount)
 
 
+def _no_records():
+    import numpy as np
+    out = {"step": np.empty(0, np.int64), "nonfinite": np.empty(0, np.int32), "dropped": 0}
+    out.update({name: np.empty(0, np.float64) for name in L.LEARN_LOG_VALUES})
+    return out
+
+
 def _per_agent(x, K, name):
     if isinstance(x, (list, tuple)):
         if len(x) != K:
@@ -207,12 +232,18 @@ class PopulationRollout:
     n_step: one value or one per agent (1: the one-step population, launch for launch).  With n_max the largest of them, every
     agent starts learning at vector step 1 + n_max -- an agent with a smaller n later than its lone loop would -- and graph
     replay starts after max(4, 1 + n_max) eager steps.  n_step_max: the largest n an exploit() may give an agent later (PBT over
-    n); the ring check and the start use it."""
+    n); the ring check and the start use it.
+    learn_log / learn_log_every: the learn log's capacity per agent and its stride in updates (PopulationLearner); drain_learn_log()."""
 
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
-                 pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None):
+                 pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
+                 learn_log_every=1):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+        if learn_log is not None:
+            check_learn_log(learn_log, learn_log_every)
+            if torch.device(device).type != "cuda":
+                raise ValueError("learn_log is not supported on a CPU device: the learn log is a launch of the fused learner")
         if data_parallel or pipeline or side_buffer is not None:
             raise ValueError("populations run the serial order on one GPU without expert side buffers (data-parallel populations, "
                              "the pipelined order and side buffers are not supported)")
@@ -247,7 +278,8 @@ class PopulationRollout:
             self.loops.append(lp)
         self.agents = [lp.agent for lp in self.loops]
         self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
-                                         seeds=self.seeds, n_steps=n_steps if nstep else None)
+                                         seeds=self.seeds, n_steps=n_steps if nstep else None, learn_log=learn_log,
+                                         learn_log_every=learn_log_every)
         self._learn_from, self._warm_steps = learn_start(self.n_step_max)      # (the largest n decides for every agent)
         self.graph_steps = int(graph_steps) if graph_steps else 0
         self.graph1 = self.graphG = self._graph_key = None
@@ -333,6 +365,10 @@ class PopulationRollout:
     def drain_episodes(self):
         """[agent: its env's episode log since the last drain (VectorStepper.drain_episodes)]."""
         return [lp.drain_episodes() for lp in self.loops]
+
+    def drain_learn_log(self):
+        """[agent: its learn-log records since the last drain (PopulationLearner.drain_learn_log)]."""
+        return self.learner.drain_learn_log()
 
     def exploit(self, pairs):
         """PBT's exploit/explore step between vector steps, eagerly (PopulationLearner.exploit): pairs = [(dst, src, {"alpha",

@@ -71,7 +71,8 @@ class DDPGRollout(VectorStepper):
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99,
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
-                 policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1):
+                 policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
+                 learn_log_every=1):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -89,8 +90,16 @@ class DDPGRollout(VectorStepper):
         n_step: 1 = the one-step TD target, launch for launch what the loop did before the option existed.  n > 1 (up to
         TT_NSTEP_MAX): n-step returns from the ring (include/ttenv.h: tt_ring_sample_nstep) -- every update
         makes its own draw in learn()'s first launch, and learn() starts once a base step with all its n steps is in the window.
-        Not together with side (expert) tuples, data-parallel ranks or a ring too short for the window."""
+        Not together with side (expert) tuples, data-parallel ranks or a ring too short for the window.
+        learn_log: None, or the capacity of the fused learner's learn log (FusedLearner.enable_learn_log), turned on here: every
+        update whose step count is a multiple of learn_log_every then leaves a record of its losses, Q / TD statistics and gradient
+        norms in device memory -- also inside replayed graphs, at no host work per step -- and drain_learn_log() collects the
+        records.  With updates_per_step > 1 every update is a step of its own.  Needs the fused learner (reference-shaped networks
+        on a GPU); not with data-parallel ranks."""
         self.n_step = check_n_step(n_step)
+        if learn_log is not None:
+            from ddpg_trucktrailer_amd.fused_learn import check_learn_log
+            learn_log, learn_log_every = check_learn_log(learn_log, learn_log_every)
         if self.n_step > 1 and replay_slots < slots_needed(self.n_step):
             raise ValueError(f"n_step = {self.n_step} with replay_slots = {replay_slots} is not supported: the window of base steps "
                              f"with their n steps intact needs at least {slots_needed(self.n_step)} slots")
@@ -135,6 +144,14 @@ class DDPGRollout(VectorStepper):
             self.learner.fuse_tail = (tail == "1") if tail in ("0", "1") else (self.n <= 16384 or self.updates_per_step > 1)
         if self.dp and self.dp_exchange == "p2p" and self.learner is None:
             raise RuntimeError("dp_exchange='p2p' needs the fused learner (reference-shaped networks on a GPU)")
+        if learn_log is not None:
+            if self.learner is None or self.device.type != "cuda":
+                raise ValueError("learn_log needs the fused learner (reference-shaped networks on a GPU): the torch path keeps "
+                                 "Agent.last_critic_loss / last_actor_loss instead")
+            if self.dp or os.environ.get("TT_FORCE_DP") == "1":
+                raise ValueError("learn_log with data-parallel ranks is not supported: a rank's own gradient buffer is not what its "
+                                 "optimizer applies")
+            self.learner.enable_learn_log(learn_log, learn_log_every)
         self.use_graph = use_graph and self.device.type == "cuda"
         if os.environ.get("TT_FORCE_DP") == "1" and self.learner is not None and not self.dp:
             # measurement aid: the data-parallel launch structure (three graph segments, separate Adam launches) on ONE
@@ -597,6 +614,12 @@ class DDPGRollout(VectorStepper):
         else:
             sd["optim"] = {"actor": ag.actor.optimizer.state_dict(), "critic": ag.critic.optimizer.state_dict()}
         return sd
+
+    def drain_learn_log(self):
+        """The learn log's records since the last drain: a dict of numpy columns and "dropped" (FusedLearner.drain_learn_log)."""
+        if self.learner is None or self.learner.learn_log is None:
+            raise ValueError("the learn log is off (DDPGRollout(learn_log=...))")
+        return self.learner.drain_learn_log()
 
     def load_state_dict(self, sd):
         ag = self.agent

@@ -666,6 +666,57 @@ int tt_pop_exploit_nstep(tt_population *pop, int pairs, const tt_pop_exploit_pai
 int tt_pop_nstep(tt_population *pop, int agent, struct tt_pop_nstep *out);
 
 /* ------------------------------------------------------------------------------------------------------
+ * Learn log: one record per learn() update and agent -- the losses, the Q / TD-target / dQ/da / mu statistics and the two gradient
+ * norms of that update -- reduced ON THE DEVICE by one launch (csrc/ttlearnlog.hip: k_learn_log) from the buffers learn() leaves
+ * behind, so that replayed graphs keep a history of what the learner did (the episode log's counterpart on the learner's side).
+ * A handle serves `agents` agents with one batch size: a lone learner is one agent, a population K.  The job descriptors are copied
+ * into device memory at creation (every pointer must stay valid and fixed for the handle's life: rebuild the handle when a buffer
+ * moves), so tt_learn_log_append is one launch with no host work and can be captured.  Enqueue it behind the update's last launch.
+ *   step        *step_dev as the launch reads it: the Adam step t of the update just made (learn()'s second launch advances it)
+ *   slot        (step / every) % capacity of the agent's ring of `capacity` records: derived from step alone -- no write index, no
+ *               atomics -- so a replayed graph lands right and the ring holds the latest `capacity` records.  A launch whose
+ *               step % every != 0 returns at once.
+ * The values of a record, all arithmetic in f64 from the f32 inputs, in the order of tt_learn_log_drain's `values` rows:
+ *    0 critic_loss      mean (q - y)^2, q from the critic BEFORE its step (DDPG_agent.py:96)
+ *    1 actor_loss       -mean q_pi, the UPDATED critic on (s, mu(s)) (DDPG_agent.py:101-102)
+ *    2..4  q_mean, q_min, q_max            5..7  y_mean, y_min, y_max
+ *    8, 9  td_abs_mean, td_abs_max         over |y - q|
+ *   10, 11 dq_da_abs_mean, dq_da_abs_max   over |dq_da|
+ *   12 mu_abs_mean      mean |mu|          13 gate_mean   mean (1 - mu^2), the factor every actor row gradient carries
+ *   14 grad_norm_critic, 15 grad_norm_actor   the L2 norm of each flat gradient as the optimizer launch saw it (no weight decay)
+ * and nonfinite, the number of non-finite values among the 5 B row values and both gradients.  A record with nonfinite > 0 has
+ * only step and nonfinite specified.  Every sum is taken in one fixed order that depends on batch and numel alone (no float atomics):
+ * the same inputs give the same bits eagerly, replayed, alone or as agent a of a population.  No workgroup waits for or reads
+ * another's result: each gradient is cut into TT_LEARN_LOG_CHUNKS fixed chunks whose workgroups leave an f64 sum of squares each,
+ * and tt_learn_log_drain adds them in index order on the host and takes the root.
+ * tt_learn_log_drain is synchronous (it waits for the device): agent `agent`'s complete records with step > after_step, oldest
+ * first, at most `max` of them (the oldest); it does not modify the device block.  step_out [max], values_out
+ * [TT_LEARN_LOG_NVALUES][max] (value v of record i at v * max + i), nonfinite_out [max], all host memory.  tt_learn_log_clear
+ * invalidates every slot (step = -1), enqueued on `stream`: call it when *step_dev is set back, so that a step count does not meet
+ * records from its future.
+ * TT_EINVAL with a message naming the entry point, before any HIP call: a NULL handle, array or pointer; agents outside
+ * 1 .. TT_POP_MAX_AGENTS; batch outside 1 .. 1024; capacity outside 1 .. TT_LEARN_LOG_MAX_CAPACITY; every < 1; numel <= 0; a
+ * gradient that is not 16-byte aligned; an agent outside [0, agents); max < 0.
+ * Not supported: data-parallel ranks (a rank's own gradient buffer is not what its optimizer applies). */
+#define TT_LEARN_LOG_NVALUES 16
+#define TT_LEARN_LOG_CHUNKS 16
+#define TT_LEARN_LOG_MAX_CAPACITY (1 << 22)
+typedef struct tt_learn_log tt_learn_log;
+typedef struct tt_learn_log_job {          /* one agent; every pointer fixed for the handle's life */
+    const float *y, *q, *q_pi, *dq_da, *mu;            /* [batch] */
+    const float *grad_critic, *grad_actor;            /* flat, tt_mlp_weights order */
+    int32_t numel_critic, numel_actor;
+    const int64_t *step_dev;
+} tt_learn_log_job;
+int tt_learn_log_create(int agents, int batch, const tt_learn_log_job *jobs /*[agents], host*/, int64_t capacity, int32_t every,
+                        tt_learn_log **out);
+int tt_learn_log_append(tt_learn_log *log, tt_stream_t stream);               /* the one launch; capturable */
+int tt_learn_log_drain(tt_learn_log *log, int agent, int64_t after_step, int64_t max, int64_t *step_out, double *values_out,
+                       int32_t *nonfinite_out, int64_t *count);
+int tt_learn_log_clear(tt_learn_log *log, tt_stream_t stream);
+int tt_learn_log_destroy(tt_learn_log *log);                                 /* the caller's stream work with it must be done */
+
+/* ------------------------------------------------------------------------------------------------------
  * Peer-to-peer gradient exchange of data-parallel ranks (one process per GPU of one node): the mean over the ranks of the
  * critic's / the actor's gradient at the reference's two optimizer sites (DDPG/DDPG_agent.py:95-104) WITHOUT a collective
  * launch on learn()'s chain.  Every rank owns two blocks of device memory -- per site a flat f32 gradient buffer

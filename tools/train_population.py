@@ -9,7 +9,9 @@ training (pbt.py) -- after each block, the records just drained go to the contro
 bottom agents copy a top agent's networks and optimizer state and perturb its hyperparameters; one line per decision
 (--pbt-quantile, default 0.25; --pbt-metric return | success, default return).  --n-step N[,N...]: n-step returns, one n for all
 agents or one per agent; with --pbt, --pbt-n-steps a,b,c lets the controller move an agent's n among those choices.
-Usage: train_population.py [--objectives] [--n-step N[,N...]] [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]]
+--learn-log EVERY: the learn log (PopulationRollout(learn_log=...)), one record per agent and EVERY updates; each agent's line adds
+the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient norms, and the block's non-finite total.
+Usage: train_population.py [--objectives] [--n-step N[,N...]] [--learn-log EVERY] [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]]
        K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
 import pickle
@@ -41,6 +43,7 @@ pbt_metric = _option("--pbt-metric", str, "return")
 _ints = lambda text: [int(x) for x in text.split(",")]
 n_step = _option("--n-step", _ints, [1])
 pbt_n_steps = _option("--pbt-n-steps", _ints)
+learn_every = _option("--learn-log", int)
 if pbt_n_steps is not None and pbt_ready is None:
     sys.exit("--pbt-n-steps needs --pbt")
 K, n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:8])
@@ -53,7 +56,10 @@ if n_step != [1] or pbt_n_steps is not None:
     if pbt_n_steps is not None:
         nstep_kw["n_step_max"] = max(pbt_n_steps + n_step)
 pop = PopulationRollout(n, seeds, batch_size=batch, replay_slots=slots, updates_per_step=upd, graph_steps=graph_steps,
-                        episode_log=min(n * every, 1 << 24), episode_log_detail=detail, **nstep_kw)
+                        episode_log=min(n * every, 1 << 24), episode_log_detail=detail,
+                        # the log holds a report block's records: one per learn_every updates
+                        learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
+                        learn_log_every=learn_every or 1, **nstep_kw)
 print(f"K = {K} agents x N = {n} envs, ring {slots} steps, {upd} learn() per vector step = {n / upd:.1f} env-steps per update "
       f"per agent, batch {batch}, seeds {seeds}, n_step {pop.n_steps}", flush=True)
 for a, ag in enumerate(pop.agents):       # each agent saves its best networks into a directory of its own
@@ -61,6 +67,18 @@ for a, ag in enumerate(pop.agents):       # each agent saves its best networks i
     os.makedirs(d, exist_ok=True)
     for net in ag._nets():
         net.checkpoint_dir, net.checkpoint_file = d, os.path.join(d, os.path.basename(net.checkpoint_file))
+
+
+def learn_line(rec):
+    """The latest record of a drained learn log and the block's non-finite total, for a report line."""
+    if not len(rec["step"]):
+        return "  learn log: no record"
+    bad = int(rec["nonfinite"].sum())
+    return (f"  update {int(rec['step'][-1])}: critic loss {rec['critic_loss'][-1]:.4g}  actor loss {rec['actor_loss'][-1]:.4g}  "
+            f"Q mean {rec['q_mean'][-1]:.4g}  |TD| mean {rec['td_abs_mean'][-1]:.4g}  |grad| critic {rec['grad_norm_critic'][-1]:.4g} "
+            f"actor {rec['grad_norm_actor'][-1]:.4g}  non-finite {bad}" + (f"  ({rec['dropped']} records overwritten)" if rec["dropped"] else ""))
+
+
 trackers = [BestModelTracker() for _ in range(K)]
 pbt = None
 if pbt_ready is not None:
@@ -78,6 +96,7 @@ while s < total:
     pop.run(k)
     s += k
     drained = pop.drain_episodes()
+    learned = pop.drain_learn_log() if learn_every is not None else None
     for a, r in enumerate(drained):
         m = len(r["ret"])
         best, avg, rate = trackers[a].update_many(r, episodes[a])
@@ -91,7 +110,7 @@ while s < total:
         print(f"agent {a} seed {seeds[a]}  vector steps {s:7d} ({s * n:.2e} env-steps): episodes {m:7d}  "
               f"mean return {r['ret'].sum().item() / e:9.1f}  successes {int(r['success'].sum().item()):6d}  "
               f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
-              f"{'BEST ' if best else ''}{objs}{lost}", flush=True)
+              f"{'BEST ' if best else ''}{objs}{lost}{learn_line(learned[a]) if learned is not None else ''}", flush=True)
         if best:
             pop.agents[a].save_models()
     if pbt is not None:

@@ -6,7 +6,9 @@ success rate and "best" decisions (checkpoint.BestModelTracker).  The loop runs 
 --objectives: the detailed episode log, and each line adds the 100-episode averages of viz_how_agent_learn.py's four objectives
 (efficiency, smoothness, precision, safety; episode_metrics.py).
 --n-step N: n-step returns in the replay draw (DDPGRollout(n_step=N); default 1, the one-step target).
-Usage: train_vector.py [--objectives] [--n-step N] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+--learn-log EVERY: the fused learner's learn log (DDPGRollout(learn_log=...)), one record per EVERY updates, and each line adds
+the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient norms, and the block's non-finite total.
+Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -23,6 +25,11 @@ if "--n-step" in sys.argv[1:]:
     at = sys.argv.index("--n-step")
     n_step = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+learn_every = None
+if "--learn-log" in sys.argv[1:]:
+    at = sys.argv.index("--learn-log")
+    learn_every = int(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
 n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:7])
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 27
 graph_steps = int(sys.argv[8]) if len(sys.argv) > 8 else (20 if slots <= 1024 else 0)      # (as before: no graphs past 1024 slots)
@@ -30,9 +37,24 @@ env = TruckTrailerVecEnv(n)
 env.reset(seed=seed)
 # the log holds a report block's episodes: at most one per env and step
 loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates_per_step=upd, graph_steps=graph_steps,
-                   episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step)
+                   episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
+                   # the log holds a report block's records: one per learn_every updates
+                   learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
+                   learn_log_every=learn_every or 1)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}", flush=True)
+
+
+def learn_line(rec):
+    """The latest record of a drained learn log and the block's non-finite total, for a report line."""
+    if not len(rec["step"]):
+        return "  learn log: no record"
+    bad = int(rec["nonfinite"].sum())
+    return (f"  update {int(rec['step'][-1])}: critic loss {rec['critic_loss'][-1]:.4g}  actor loss {rec['actor_loss'][-1]:.4g}  "
+            f"Q mean {rec['q_mean'][-1]:.4g}  |TD| mean {rec['td_abs_mean'][-1]:.4g}  |grad| critic {rec['grad_norm_critic'][-1]:.4g} "
+            f"actor {rec['grad_norm_actor'][-1]:.4g}  non-finite {bad}" + (f"  ({rec['dropped']} records overwritten)" if rec["dropped"] else ""))
+
+
 tracker = BestModelTracker()
 episodes = 0
 t0 = time.time()
@@ -55,4 +77,5 @@ while s < total:
           f"mean length {r['len'].double().sum().item() / e:6.1f}  mean return {r['ret'].sum().item() / e:9.1f}  "
           f"successes {int(r['success'].sum().item()):6d} ({100 * r['success'].double().sum().item() / e:4.1f} %)  "
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
-          f"best x{len(best)}{objs}{lost}  {time.time() - t0:.0f}s", flush=True)
+          f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}  "
+          f"{time.time() - t0:.0f}s", flush=True)
