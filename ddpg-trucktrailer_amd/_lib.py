@@ -248,6 +248,17 @@ def load():
     return _lib
 
 
+def ptr(t):
+    """A tensor's device address as the `void *` of a call or of a struct field (None: NULL)."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def stream(device=None):
+    """torch's current stream on `device` (None: the current device) as a tt_stream_t."""
+    import torch
+    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(rc, handle=None):
     if rc != TT_OK:
         msg = load().tt_last_error(handle)

@@ -37,14 +37,12 @@
 #include <cstdlib>
 #include <cstring>
 #include <new>
+#include <type_traits>
 #include <vector>
 
 #include "ttenv.h"
 #include "tthost.h"
-
-#ifndef TT_TABLE
-#define TT_TABLE 0  // 1: polynomial / tableau constants come from the kernarg table instead of literals
-#endif
+#include "ttphilox.h"
 
 namespace {
 
@@ -139,17 +137,9 @@ struct KParams {
     int pool_m;          // > 0: resets draw from pool[pool_m][3] instead of the box rlo..rhi
     int nt;              // 1: obs / reward / done leave as non-temporal stores (set by N: see nt_stores_for)
     const double *pool;
-#if TT_TABLE
-    KTable t;
-#endif
 };
 
-#if TT_TABLE
-#define TT_T(P) ((P).t)
-#else
 __device__ constexpr KTable kTable = make_table();
-#define TT_T(P) kTable
-#endif
 
 struct Info {
     double *comp;
@@ -172,19 +162,8 @@ __device__ __forceinline__ const double *hot_ptr(const double *hot, int i) {
 }
 
 // ------------------------------------------------------------------------------------------
-// counter-based RNG (Philox4x32-10, Salmon et al. 2011)
-__device__ inline void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                  uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+// counter-based RNG (csrc/ttphilox.h)
+using ttrng::philox4x32;
 __device__ inline double u01(uint32_t x) { return ((double)x + 0.5) * (1.0 / 4294967296.0); }
 
 // ------------------------------------------------------------------------------------------
@@ -391,7 +370,7 @@ __device__ __forceinline__ void store_env(const Bufs &b, int i, const Env &e) {
 // `of` (may be NULL) receives the first observation (steering 0).
 __device__ inline void place_env(const KParams &P, const Bufs &b, int i, Env &e, double sx, double sy, double syaw,
                                  const Goal &g, double gyaw, double L2, float *of) {
-    const KTable &T = TT_T(P);
+    const KTable &T = kTable;
     double ss, cs;
     tt_sincos(T, syaw, ss, cs);
     e.psi1 = e.psi2 = (double)(float)syaw;
@@ -450,7 +429,7 @@ struct StepOut {
 
 // env.step for one env held in registers (simv2.py:499-545 + reward_functionv1.py:442-506)
 __device__ __forceinline__ void step_env(const KParams &P, Env &e, float action, float *of, StepOut &o) {
-    const KTable &T = TT_T(P);
+    const KTable &T = kTable;
     // ---- simv2.py:504-505: clip in f64 against np.radians(45)
     const double delta = fmin(fmax((double)action, -P.max_steer), P.max_steer);
     double sd, cd;
@@ -1120,7 +1099,7 @@ __global__ __launch_bounds__(BLOCK) void k_set_pose(const KParams P, const int n
     double gyaw;
     if (goal) {
         g.gx = goal[3 * j]; g.gy = goal[3 * j + 1]; gyaw = goal[3 * j + 2];
-        tt_sincos(TT_T(P), gyaw, g.sg, g.cg);
+        tt_sincos(kTable, gyaw, g.sg, g.cg);
     } else {
         g.gx = c[C_GX * S]; g.gy = c[C_GY * S]; gyaw = c[C_GYAW * S]; g.sg = c[C_SG * S]; g.cg = c[C_CG * S];
     }
@@ -1147,7 +1126,7 @@ __global__ __launch_bounds__(BLOCK) void k_set_attrs(const KParams P, const int 
     }
     if (goal) {
         double sg, cg;
-        tt_sincos(TT_T(P), goal[3 * j + 2], sg, cg);
+        tt_sincos(kTable, goal[3 * j + 2], sg, cg);
         c[C_GX * S] = goal[3 * j]; c[C_GY * S] = goal[3 * j + 1]; c[C_GYAW * S] = goal[3 * j + 2];
         c[C_SG * S] = sg; c[C_CG * S] = cg;
     }
@@ -1220,7 +1199,7 @@ __global__ __launch_bounds__(BLOCK) void k_observe(const KParams P, const int n,
     const bool valid = i < n;
     float of[OBS];
     if (valid) {
-        const KTable &T = TT_T(P);
+        const KTable &T = kTable;
         Env e;
         load_env<PER_ENV>(P, b, i, e);
         double s1, c1, s2, c2, sd = 0.0, cd = 1.0;
@@ -1300,7 +1279,7 @@ __global__ __launch_bounds__(BLOCK) void k_log_drain(const EpLog lg, double *ret
     }
 }
 
-char g_err[256] = "";
+char g_err[tthost::ERR_BYTES] = "";
 
 }  // namespace
 
@@ -1324,19 +1303,31 @@ struct tt_env {
     size_t log_bytes = 0;
     EpLog log{};
     uint32_t log_flags = 0;     // TT_LOG_DETAIL: the detailed log (k_step_tally)
-    char err[256] = "";
+    char err[tthost::ERR_BYTES] = "";
 };
 
 namespace {
 
-int fail(tt_env *e, int code, const char *fmt, ...) {
-    char *dst = e ? e->err : g_err;
+__attribute__((format(printf, 3, 4))) int fail(tt_env *e, int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(dst, 256, fmt, ap);
+    tthost::vfail(e ? e->err : g_err, code, fmt, ap);
     va_end(ap);
     return code;
 }
+
+// The opening the handle entry points share: a NULL handle is refused in the entry point's own name (an extern "C" function's
+// __func__ is its symbol), and TT_ENTER then makes the handle's device current.  Entry points with refusals or an early TT_OK
+// between the two keep them there, and those that word the refusal differently ("NULL argument") keep their own.
+#define TT_HANDLE(env)                                                                       \
+    do {                                                                                     \
+        if (!(env)) return fail(nullptr, TT_EINVAL, "%s: NULL handle", __func__);            \
+    } while (0)
+#define TT_ENTER(env)                                                                        \
+    do {                                                                                     \
+        TT_HANDLE(env);                                                                      \
+        TT_HIP(env, hipSetDevice(env->device));                                              \
+    } while (0)
 
 #define TT_HIP(e, call)                                                                      \
     do {                                                                                     \
@@ -1380,13 +1371,17 @@ KParams make_kparams(const tt_params &p, int npad) {
     k.pool_m = 0;
     k.pool = nullptr;
     k.nt = nt_stores_for(npad);
-#if TT_TABLE
-    k.t = make_table();
-#endif
     return k;
 }
 
 inline int grid_for(int n) { return (n + BLOCK - 1) / BLOCK; }
+
+// the kernels' PER_ENV template argument from the handle: f(std::true_type{}) when envs carry goals / trailer lengths of their own
+template <class F>
+void by_per_env(const tt_env *env, F &&f) {
+    if (env->per_env) f(std::true_type{});
+    else f(std::false_type{});
+}
 
 template <bool PER_ENV, bool INFO, bool RANDOM_POLICY>
 void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_out, float *obs, float *reward,
@@ -1398,27 +1393,22 @@ void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_
         t1 = e->ev_stop[e->ev_used];
         e->ev_used += 1;
     }
-    // hipExtLaunchKernelGGL with null events is a plain launch; with events they time this dispatch alone
+    // hipExtLaunchKernelGGL with null events is a plain launch; with events they time this dispatch alone.  The argument list is
+    // stated once: `kernel` is the chosen instantiation, `log` the trailing EpLog of the two log kernels (nothing for k_step)
+    const auto launch = [&](auto kernel, const auto &...log) {
+        hipExtLaunchKernelGGL(kernel, g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b, action, action_out, obs, reward, done, info, e->seed,
+                              policy_seed, cursor, log...);
+    };
     if (e->log_flags & TT_LOG_DETAIL) {
-        if (auto_reset)
-            hipExtLaunchKernelGGL((k_step_tally<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
-                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
-        else
-            hipExtLaunchKernelGGL((k_step_tally<PER_ENV, INFO, false, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
-                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
+        if (auto_reset) launch(k_step_tally<PER_ENV, INFO, true, RANDOM_POLICY>, e->log);
+        else launch(k_step_tally<PER_ENV, INFO, false, RANDOM_POLICY>, e->log);
     } else if (e->log_bytes) {
-        if (auto_reset)
-            hipExtLaunchKernelGGL((k_step_log<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
-                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
-        else
-            hipExtLaunchKernelGGL((k_step_log<PER_ENV, INFO, false, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
-                                  action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor, e->log);
+        if (auto_reset) launch(k_step_log<PER_ENV, INFO, true, RANDOM_POLICY>, e->log);
+        else launch(k_step_log<PER_ENV, INFO, false, RANDOM_POLICY>, e->log);
     } else if (auto_reset)
-        hipExtLaunchKernelGGL((k_step<PER_ENV, INFO, true, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
-                              action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor);
+        launch(k_step<PER_ENV, INFO, true, RANDOM_POLICY>);
     else
-        hipExtLaunchKernelGGL((k_step<PER_ENV, INFO, false, RANDOM_POLICY>), g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b,
-                              action, action_out, obs, reward, done, info, e->seed, policy_seed, cursor);
+        launch(k_step<PER_ENV, INFO, false, RANDOM_POLICY>);
 }
 
 template <bool RANDOM_POLICY>
@@ -1430,14 +1420,14 @@ int step_common(tt_env *env, const float *action, float *action_out, float *obs,
         ki.comp = info->comp; ki.violation = info->violation; ki.flags = info->flags;
         want_info = ki.comp || ki.violation || ki.flags;
     }
-    const bool ar = auto_reset != 0;
-    if (env->per_env) {
-        if (want_info) launch_step<true, true, RANDOM_POLICY>(env, ar, action, action_out, obs, reward, done, ki, policy_seed, stream, cursor);
-        else launch_step<true, false, RANDOM_POLICY>(env, ar, action, action_out, obs, reward, done, ki, policy_seed, stream, cursor);
-    } else {
-        if (want_info) launch_step<false, true, RANDOM_POLICY>(env, ar, action, action_out, obs, reward, done, ki, policy_seed, stream, cursor);
-        else launch_step<false, false, RANDOM_POLICY>(env, ar, action, action_out, obs, reward, done, ki, policy_seed, stream, cursor);
-    }
+    const auto launch = [&](auto per_env, auto with_info) {
+        launch_step<decltype(per_env)::value, decltype(with_info)::value, RANDOM_POLICY>(env, auto_reset != 0, action, action_out, obs,
+                                                                                         reward, done, ki, policy_seed, stream, cursor);
+    };
+    by_per_env(env, [&](auto per_env) {
+        if (want_info) launch(per_env, std::true_type{});
+        else launch(per_env, std::false_type{});
+    });
     hipError_t err = hipGetLastError();
     if (err != hipSuccess) return fail(env, TT_EHIP, "tt_env_step launch: %s", hipGetErrorString(err));
     return TT_OK;
@@ -1462,6 +1452,18 @@ int log_restart(tt_env *env, int k, const uint8_t *mask, const int32_t *idx, hip
     else
         hipLaunchKernelGGL(k_log_zero, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, mask, idx, env->log.acc);
     TT_HIP(env, hipGetLastError());
+    return TT_OK;
+}
+
+// The packed counters hold 12 bits: tt_env_set_max_steps and tt_env_set_steps refuse what they cannot represent instead of
+// clamping (setters, not hot calls).  `values` [k] is device memory; `fn` and `what` name the entry point and its array.
+int check_counter_range(tt_env *env, const int32_t *values, int k, hipStream_t stream, const char *fn, const char *what) {
+    std::vector<int32_t> host((size_t)k);
+    TT_HIP(env, hipMemcpyAsync(host.data(), values, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, stream));
+    TT_HIP(env, hipStreamSynchronize(stream));
+    for (int j = 0; j < k; ++j)
+        if (host[(size_t)j] < 0 || host[(size_t)j] > TT_MAX_EPISODE_STEPS)
+            return fail(env, TT_EINVAL, "%s: %s[%d] = %d outside [0, %d]", fn, what, j, host[(size_t)j], TT_MAX_EPISODE_STEPS);
     return TT_OK;
 }
 
@@ -1634,8 +1636,7 @@ int tt_env_destroy(tt_env *env) {
 int tt_env_num_envs(const tt_env *env) { return env ? env->n : TT_EINVAL; }
 
 int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_reset: NULL handle");
-    TT_HIP(env, hipSetDevice(env->device));
+    TT_ENTER(env);
     env->seed = seed;
     hipLaunchKernelGGL(k_reset, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
                        env->seed);
@@ -1650,7 +1651,7 @@ int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out
 }
 
 int tt_env_set_reset_pool(tt_env *env, const double *pool, int m) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_reset_pool: NULL handle");
+    TT_HANDLE(env);
     if (m < 0) return fail(env, TT_EINVAL, "tt_env_set_reset_pool: m=%d", m);
     env->kp.pool_m = pool ? m : 0;
     env->kp.pool = env->kp.pool_m > 0 ? pool : nullptr;
@@ -1659,7 +1660,7 @@ int tt_env_set_reset_pool(tt_env *env, const double *pool, int m) {
 
 int tt_env_set_pose(tt_env *env, const int32_t *idx, int k, const double *start, const double *goal, const double *L2,
                     float *obs_out, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_pose: NULL handle");
+    TT_HANDLE(env);
     if (k < 0 || k > env->n || (k > 0 && !start))
         return fail(env, TT_EINVAL, "tt_env_set_pose: k=%d outside [0,%d] or start NULL", k, env->n);
     if (k == 0) return TT_OK;
@@ -1674,7 +1675,7 @@ int tt_env_set_pose(tt_env *env, const int32_t *idx, int k, const double *start,
 
 int tt_env_set_attrs(tt_env *env, const int32_t *idx, int k, const double *start, const double *goal, const double *L2,
                      tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_attrs: NULL handle");
+    TT_HANDLE(env);
     if (k < 0 || k > env->n) return fail(env, TT_EINVAL, "tt_env_set_attrs: k=%d outside [0,%d]", k, env->n);
     if (k == 0 || (!start && !goal && !L2)) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
@@ -1686,7 +1687,7 @@ int tt_env_set_attrs(tt_env *env, const int32_t *idx, int k, const double *start
 }
 
 int tt_env_set_state(tt_env *env, const int32_t *idx, int k, const double *state, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_state: NULL handle");
+    TT_HANDLE(env);
     if (k < 0 || k > env->n || (k > 0 && !state))
         return fail(env, TT_EINVAL, "tt_env_set_state: k=%d outside [0,%d] or state NULL", k, env->n);
     if (k == 0) return TT_OK;
@@ -1705,40 +1706,24 @@ int tt_env_get_state(tt_env *env, double *state_out, tt_stream_t stream) {
 }
 
 int tt_env_set_max_steps(tt_env *env, const int32_t *idx, int k, const int32_t *max_steps, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_max_steps: NULL handle");
+    TT_HANDLE(env);
     if (k < 0 || k > env->n || (k > 0 && !max_steps))
         return fail(env, TT_EINVAL, "tt_env_set_max_steps: k=%d outside [0,%d] or max_steps NULL", k, env->n);
     if (k == 0) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
-    {   // the packed counters hold 12 bits: refuse what they cannot represent instead of clamping (not a hot call)
-        std::vector<int32_t> host((size_t)k);
-        TT_HIP(env, hipMemcpyAsync(host.data(), max_steps, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, stream));
-        TT_HIP(env, hipStreamSynchronize(stream));
-        for (int j = 0; j < k; ++j)
-            if (host[(size_t)j] < 0 || host[(size_t)j] > TT_MAX_EPISODE_STEPS)
-                return fail(env, TT_EINVAL, "tt_env_set_max_steps: max_steps[%d] = %d outside [0, %d]", j, host[(size_t)j],
-                            TT_MAX_EPISODE_STEPS);
-    }
+    if (const int rc = check_counter_range(env, max_steps, k, stream, __func__, "max_steps")) return rc;
     hipLaunchKernelGGL(k_set_max_steps, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, env->b, idx, k, max_steps);
     TT_HIP(env, hipGetLastError());
     return TT_OK;
 }
 
 int tt_env_set_steps(tt_env *env, const int32_t *idx, int k, const int32_t *steps, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_steps: NULL handle");
+    TT_HANDLE(env);
     if (k < 0 || k > env->n || (k > 0 && !steps))
         return fail(env, TT_EINVAL, "tt_env_set_steps: k=%d outside [0,%d] or steps NULL", k, env->n);
     if (k == 0) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
-    {   // 12-bit packed counter, as for tt_env_set_max_steps: refuse instead of clamping (a setter, not a hot call)
-        std::vector<int32_t> host((size_t)k);
-        TT_HIP(env, hipMemcpyAsync(host.data(), steps, sizeof(int32_t) * (size_t)k, hipMemcpyDeviceToHost, stream));
-        TT_HIP(env, hipStreamSynchronize(stream));
-        for (int j = 0; j < k; ++j)
-            if (host[(size_t)j] < 0 || host[(size_t)j] > TT_MAX_EPISODE_STEPS)
-                return fail(env, TT_EINVAL, "tt_env_set_steps: steps[%d] = %d outside [0, %d]", j, host[(size_t)j],
-                            TT_MAX_EPISODE_STEPS);
-    }
+    if (const int rc = check_counter_range(env, steps, k, stream, __func__, "steps")) return rc;
     hipLaunchKernelGGL(k_set_steps, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, env->b, idx, k, steps);
     TT_HIP(env, hipGetLastError());
     return TT_OK;
@@ -1746,7 +1731,7 @@ int tt_env_set_steps(tt_env *env, const int32_t *idx, int k, const int32_t *step
 
 int tt_env_get_episode(tt_env *env, int32_t *steps, int32_t *max_steps, double *start, double *goal, double *L2,
                        tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_get_episode: NULL handle");
+    TT_HANDLE(env);
     if (!steps && !max_steps && !start && !goal && !L2) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
     hipLaunchKernelGGL(k_get_episode, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, steps,
@@ -1758,24 +1743,23 @@ int tt_env_get_episode(tt_env *env, int32_t *steps, int32_t *max_steps, double *
 int tt_env_observe(tt_env *env, const float *steering, float *obs_out, tt_stream_t stream) {
     if (!env || !obs_out) return fail(env, TT_EINVAL, "tt_env_observe: NULL argument");
     TT_HIP(env, hipSetDevice(env->device));
-    const dim3 g(grid_for(env->n)), b(BLOCK);
-    if (env->per_env)
-        hipLaunchKernelGGL(k_observe<true>, g, b, 0, stream, env->kp, env->n, env->b, steering, obs_out);
-    else
-        hipLaunchKernelGGL(k_observe<false>, g, b, 0, stream, env->kp, env->n, env->b, steering, obs_out);
+    by_per_env(env, [&](auto per_env) {
+        hipLaunchKernelGGL(k_observe<decltype(per_env)::value>, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b,
+                           steering, obs_out);
+    });
     TT_HIP(env, hipGetLastError());
     return TT_OK;
 }
 
 int tt_env_set_step_counter(tt_env *env, int64_t *counter) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_step_counter: NULL handle");
+    TT_HANDLE(env);
     env->b.counter = reinterpret_cast<long long *>(counter);
     return TT_OK;
 }
 
 int tt_env_step(tt_env *env, const float *action, float *obs, float *reward, uint8_t *done, const tt_info *info,
                 int auto_reset, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_step: NULL handle");
+    TT_HANDLE(env);
     if (!action || !obs || !reward || !done)
         return fail(env, TT_EINVAL, "tt_env_step: action, obs, reward and done are required");
     TT_HIP(env, hipSetDevice(env->device));
@@ -1783,7 +1767,7 @@ int tt_env_step(tt_env *env, const float *action, float *obs, float *reward, uin
 }
 
 int tt_env_step_ring(tt_env *env, const float *action, const tt_ring_view *ring, int auto_reset, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_step_ring: NULL handle");
+    TT_HANDLE(env);
     if (!action || !ring || !ring->cursor || !ring->obs || !ring->rew || !ring->done || ring->n_envs != env->n)
         return fail(env, TT_EINVAL, "tt_env_step_ring: action and a ring view of this handle's %d envs are required", env->n);
     TT_HIP(env, hipSetDevice(env->device));
@@ -1792,7 +1776,7 @@ int tt_env_step_ring(tt_env *env, const float *action, const tt_ring_view *ring,
 
 int tt_env_step_random(tt_env *env, uint64_t policy_seed, float *action_out, float *obs, float *reward, uint8_t *done,
                        const tt_info *info, int auto_reset, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_step_random: NULL handle");
+    TT_HANDLE(env);
     if (!obs || !reward || !done) return fail(env, TT_EINVAL, "tt_env_step_random: obs, reward and done are required");
     TT_HIP(env, hipSetDevice(env->device));
     return step_common<true>(env, nullptr, action_out, obs, reward, done, info, auto_reset, policy_seed, stream);
@@ -1833,14 +1817,14 @@ int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stre
 }
 
 int tt_env_set_episode_log(tt_env *env, int64_t capacity, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_episode_log: NULL handle");
+    TT_HANDLE(env);
     return set_episode_log(env, capacity, 0u, stream, "tt_env_set_episode_log");
 }
 
 int tt_env_set_episode_log2(tt_env *env, int64_t capacity, uint32_t flags, tt_stream_t stream) {
     if (flags & ~(uint32_t)TT_LOG_DETAIL)
         return fail(env, TT_EINVAL, "tt_env_set_episode_log2: unknown flag bits 0x%x", flags & ~(uint32_t)TT_LOG_DETAIL);
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_set_episode_log2: NULL handle");
+    TT_HANDLE(env);
     return set_episode_log(env, capacity, flags, stream, "tt_env_set_episode_log2");
 }
 
@@ -1889,25 +1873,21 @@ int tt_env_import_episode_log(tt_env *env, const void *blob, const uint64_t meta
 
 int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float *obs_out, float *reward_sum,
                           int32_t *episodes_done, tt_stream_t stream) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_rollout_random: NULL handle");
+    TT_HANDLE(env);
     if (k_steps < 0) return fail(env, TT_EINVAL, "tt_env_rollout_random: k_steps=%d", k_steps);
     if (env->log_bytes) return fail(env, TT_EINVAL, "tt_env_rollout_random: the episode log does not follow k_rollout; disable it first");
     if (k_steps == 0) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
-    const dim3 g(grid_for(env->n)), b(BLOCK);
-    if (env->per_env)
-        hipLaunchKernelGGL(k_rollout<true>, g, b, 0, stream, env->kp, env->n, env->b, k_steps, obs_out, reward_sum,
-                           episodes_done, env->seed, policy_seed);
-    else
-        hipLaunchKernelGGL(k_rollout<false>, g, b, 0, stream, env->kp, env->n, env->b, k_steps, obs_out, reward_sum,
-                           episodes_done, env->seed, policy_seed);
+    by_per_env(env, [&](auto per_env) {
+        hipLaunchKernelGGL(k_rollout<decltype(per_env)::value>, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b,
+                           k_steps, obs_out, reward_sum, episodes_done, env->seed, policy_seed);
+    });
     TT_HIP(env, hipGetLastError());
     return TT_OK;
 }
 
 int tt_env_profile(tt_env *env, int max_launches) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_profile: NULL handle");
-    TT_HIP(env, hipSetDevice(env->device));
+    TT_ENTER(env);
     env->profiling = max_launches > 0;
     env->ev_used = 0;
     env->prof_ms = 0.0;
@@ -1923,8 +1903,7 @@ int tt_env_profile(tt_env *env, int max_launches) {
 }
 
 int tt_env_profile_read(tt_env *env, double *total_ms, int64_t *launches) {
-    if (!env) return fail(nullptr, TT_EINVAL, "tt_env_profile_read: NULL handle");
-    TT_HIP(env, hipSetDevice(env->device));
+    TT_ENTER(env);
     for (size_t i = 0; i < env->ev_used; ++i) {
         TT_HIP(env, hipEventSynchronize(env->ev_stop[i]));
         float ms = 0.f;
@@ -1949,17 +1928,26 @@ int tt_random_actions(int n, uint64_t seed, uint64_t step, float *out, tt_stream
 
 }  // extern "C"
 
-// the library's message for a NULL handle (tt_last_error(NULL)), set by the entry points of the other sources (csrc/tthost.h)
+// the refusals of the other sources (csrc/tthost.h): the library's message (tt_last_error(NULL))
 namespace tthost {
-int fail_library(int code, const char *msg) { return fail(nullptr, code, "%s", msg); }
-int einval(const char *fmt, int a, int b) { return fail(nullptr, TT_EINVAL, fmt, a, b); }
+int vfail(char *dst, int code, const char *fmt, va_list ap) {
+    vsnprintf(dst, ERR_BYTES, fmt, ap);
+    return code;
+}
+int fail(int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vfail(g_err, code, fmt, ap);
+    va_end(ap);
+    return code;
+}
 int refuse_nstep(const char *who, int n_step, float gamma) {
-    if (n_step < 1 || n_step > TT_NSTEP_MAX) return fail(nullptr, TT_EINVAL, "%s: n_step %d is outside 1 .. %d", who, n_step, TT_NSTEP_MAX);
-    if (!(gamma > 0.f && gamma < 1.f)) return fail(nullptr, TT_EINVAL, "%s: gamma is outside (0, 1)", who);
+    if (n_step < 1 || n_step > TT_NSTEP_MAX) return fail(TT_EINVAL, "%s: n_step %d is outside 1 .. %d", who, n_step, TT_NSTEP_MAX);
+    if (!(gamma > 0.f && gamma < 1.f)) return fail(TT_EINVAL, "%s: gamma is outside (0, 1)", who);
     return TT_OK;
 }
 int refuse_nstep_window(const char *who, int n_step, int slots, int reserve) {
     if (slots >= 3 + reserve + (n_step - 1)) return TT_OK;
-    return fail(nullptr, TT_EINVAL, "%s: a ring of %d slots has no window for n_step %d with this reserve", who, slots, n_step);
+    return fail(TT_EINVAL, "%s: a ring of %d slots has no window for n_step %d with this reserve", who, slots, n_step);
 }
 }  // namespace tthost

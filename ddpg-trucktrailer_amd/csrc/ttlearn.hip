@@ -476,28 +476,39 @@ int tt_mlp_actor_tail(int n, const float *obs, const float *mu, const tt_mlp_wei
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
 }
 
-int tt_adam_soft_update(int count, float *const *params, const float *const *grads, float *const *exp_avg,
-                        float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const int64_t *step_dev,
-                        float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
-                        const tt_fc2_images *images, const float *bias_corr, tt_stream_t stream) {
-    if (count <= 0 || count > MAXT || !params || !grads || !exp_avg || !exp_avg_sq || !numel || !step_dev) return TT_EINVAL;
-    AdamTable T{};
+// The table of both optimizer launches: the tensors, the fc2 images and each tensor's first workgroup at `per_block` elements per
+// workgroup.  grads NULL: the peer-to-peer step, whose gradients come from the exchange.  Returns the launch's workgroups, or -1
+// for a missing tensor or images that do not go with the list.
+static int fill_adam_table(AdamTable &T, int per_block, int count, float *const *params, const float *const *grads,
+                           float *const *exp_avg, float *const *exp_avg_sq, float *const *targets, const int32_t *numel,
+                           const tt_fc2_images *images) {
     if (images && (images->net || images->target)) {       // tensors must then be in tt_mlp_weights order: w2 is number 4
-        if (count < 5 || numel[4] != H2 * H1) return TT_EINVAL;
+        if (count < 5 || numel[4] != H2 * H1) return -1;
         T.img_p = reinterpret_cast<_Float16 *>(images->net);
         T.img_t = reinterpret_cast<_Float16 *>(images->target);
     }
     T.count = count;
     int blocks = 0;
     for (int i = 0; i < count; ++i) {
-        if (!params[i] || !grads[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] <= 0) return TT_EINVAL;
-        T.p[i] = params[i]; T.g[i] = grads[i]; T.m[i] = exp_avg[i]; T.v[i] = exp_avg_sq[i];
+        if (!params[i] || (grads && !grads[i]) || !exp_avg[i] || !exp_avg_sq[i] || numel[i] <= 0) return -1;
+        T.p[i] = params[i]; T.g[i] = grads ? grads[i] : nullptr; T.m[i] = exp_avg[i]; T.v[i] = exp_avg_sq[i];
         T.tgt[i] = targets ? targets[i] : nullptr;
         T.numel[i] = numel[i];
         T.block_start[i] = blocks;
-        blocks += (numel[i] + 255) / 256;
+        blocks += (numel[i] + per_block - 1) / per_block;
     }
     T.block_start[count] = blocks;
+    return blocks;
+}
+
+int tt_adam_soft_update(int count, float *const *params, const float *const *grads, float *const *exp_avg,
+                        float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const int64_t *step_dev,
+                        float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                        const tt_fc2_images *images, const float *bias_corr, tt_stream_t stream) {
+    if (count <= 0 || count > MAXT || !params || !grads || !exp_avg || !exp_avg_sq || !numel || !step_dev) return TT_EINVAL;
+    AdamTable T{};
+    const int blocks = fill_adam_table(T, 256, count, params, grads, exp_avg, exp_avg_sq, targets, numel, images);
+    if (blocks < 0) return TT_EINVAL;
     hipLaunchKernelGGL(k_adam_soft, dim3(blocks), dim3(256), 0, stream, T, reinterpret_cast<const long long *>(step_dev), lr,
                        beta1, beta2, eps, weight_decay, tau, bias_corr);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
@@ -511,25 +522,13 @@ int tt_adam_soft_update_p2p(tt_p2p *x, int site, int count, float *const *params
         return TT_EINVAL;
     AdamTable T{};
     ttp2p::Args X{};
-    if (images && (images->net || images->target)) {       // tensors must then be in tt_mlp_weights order: w2 is number 4
-        if (count < 5 || numel[4] != H2 * H1) return TT_EINVAL;
-        T.img_p = reinterpret_cast<_Float16 *>(images->net);
-        T.img_t = reinterpret_cast<_Float16 *>(images->target);
-    }
-    T.count = count;
-    int blocks = 0;
+    const int blocks = fill_adam_table(T, 256 * P2P_EPT, count, params, nullptr, exp_avg, exp_avg_sq, targets, numel, images);
+    if (blocks < 0) return TT_EINVAL;
     size_t off = 0;
     for (int i = 0; i < count; ++i) {
-        if (!params[i] || !exp_avg[i] || !exp_avg_sq[i] || numel[i] <= 0) return TT_EINVAL;
-        T.p[i] = params[i]; T.m[i] = exp_avg[i]; T.v[i] = exp_avg_sq[i];
         X.tensor_offset[i] = (unsigned)off;
-        T.tgt[i] = targets ? targets[i] : nullptr;
-        T.numel[i] = numel[i];
-        T.block_start[i] = blocks;
-        blocks += (numel[i] + 256 * P2P_EPT - 1) / (256 * P2P_EPT);
         off += (size_t)numel[i];
     }
-    T.block_start[count] = blocks;
     if (off != (size_t)x->numel[site]) return TT_EINVAL;      // the tensors must tile the site's buffer exactly
     X.world = x->world; X.me = x->rank; X.site = site;
     for (int r = 0; r < x->world; ++r) {

@@ -124,7 +124,6 @@ __device__ __forceinline__ void kernarg_touch_all(const void *ka, unsigned (&t)[
 }
 template <int BYTES>
 __device__ __forceinline__ void kernarg_warm() {
-#ifndef TT_DBG_NO_KERNARG_WARM
     constexpr int LINES = (BYTES + 63) / 64;
     const void *ka = (const void *)__builtin_amdgcn_kernarg_segment_ptr();
     unsigned t[LINES];
@@ -132,7 +131,6 @@ __device__ __forceinline__ void kernarg_warm() {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
     for (int i = 0; i < LINES; ++i) asm volatile("" ::"s"(t[i]));      // (the destinations stay allocated until the loads are back)
-#endif
 }
 // The same in two halves, for kernels whose FIRST loads go through pointers that are leading scalar kernel arguments: those
 // arrive in SGPRs with the wave (kernarg preload, -mllvm -amdgpu-kernarg-preload-count=16 in build.py: up to 16 dwords of leading
@@ -143,16 +141,12 @@ struct KernargWarm {
     static constexpr int LINES = (BYTES + 63) / 64;
     unsigned t[LINES];
     __device__ __forceinline__ void issue() {
-#ifndef TT_DBG_NO_KERNARG_WARM
         kernarg_touch_all<0, LINES>((const void *)__builtin_amdgcn_kernarg_segment_ptr(), t);
-#endif
     }
     __device__ __forceinline__ void wait() {
-#ifndef TT_DBG_NO_KERNARG_WARM
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
 #pragma unroll
         for (int i = 0; i < LINES; ++i) asm volatile("" ::"s"(t[i]));
-#endif
     }
 };
 struct NoHook {
@@ -212,10 +206,6 @@ __device__ __forceinline__ float wave_max64(float v) {
 // No launch here hands global data from one wave to another of the same workgroup; loads in flight stay tracked by the
 // compiler (it waits at their first use).
 __device__ __forceinline__ void lds_barrier() {
-#ifdef TT_DBG_FULL_BARRIER
-    __syncthreads();
-    return;
-#endif
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");

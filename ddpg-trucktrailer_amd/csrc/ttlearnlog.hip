@@ -27,7 +27,7 @@
 #include <cstdint>
 #include <vector>
 
-using tthost::einval;
+using tthost::fail;
 
 namespace {
 
@@ -237,41 +237,41 @@ struct tt_learn_log {
 extern "C" {
 
 int tt_learn_log_create(int agents, int batch, const tt_learn_log_job *jobs, int64_t capacity, int32_t every, tt_learn_log **out) {
-    if (!out) return einval("tt_learn_log_create: out is NULL");
+    if (!out) return fail(TT_EINVAL, "tt_learn_log_create: out is NULL");
     *out = nullptr;
-    if (agents < 1 || agents > TT_POP_MAX_AGENTS) return einval("tt_learn_log_create: agents = %d, not in [1, %d]", agents, TT_POP_MAX_AGENTS);
-    if (batch < 1 || batch > MAXB) return einval("tt_learn_log_create: batch = %d rows, not in [1, %d]", batch, MAXB);
-    if (!jobs) return einval("tt_learn_log_create: jobs is NULL");
+    if (agents < 1 || agents > TT_POP_MAX_AGENTS) return fail(TT_EINVAL, "tt_learn_log_create: agents = %d, not in [1, %d]", agents, TT_POP_MAX_AGENTS);
+    if (batch < 1 || batch > MAXB) return fail(TT_EINVAL, "tt_learn_log_create: batch = %d rows, not in [1, %d]", batch, MAXB);
+    if (!jobs) return fail(TT_EINVAL, "tt_learn_log_create: jobs is NULL");
     if (capacity < 1 || capacity > TT_LEARN_LOG_MAX_CAPACITY)
-        return einval("tt_learn_log_create: capacity = %d records, not in [1, %d]", (int)std::clamp<int64_t>(capacity, INT32_MIN, INT32_MAX),
+        return fail(TT_EINVAL, "tt_learn_log_create: capacity = %d records, not in [1, %d]", (int)std::clamp<int64_t>(capacity, INT32_MIN, INT32_MAX),
                       TT_LEARN_LOG_MAX_CAPACITY);
-    if (every < 1) return einval("tt_learn_log_create: every = %d < 1", every);
+    if (every < 1) return fail(TT_EINVAL, "tt_learn_log_create: every = %d < 1", every);
     std::vector<LogJob> host(agents);
     for (int a = 0; a < agents; ++a) {
         const tt_learn_log_job &j = jobs[a];
         if (!j.y || !j.q || !j.q_pi || !j.dq_da || !j.mu || !j.grad_critic || !j.grad_actor || !j.step_dev)
-            return einval("tt_learn_log_create: agent %d has a NULL pointer", a);
+            return fail(TT_EINVAL, "tt_learn_log_create: agent %d has a NULL pointer", a);
         if (j.numel_critic <= 0 || j.numel_actor <= 0)
-            return einval("tt_learn_log_create: agent %d: numel <= 0 (numel_critic = %d)", a, j.numel_critic);
+            return fail(TT_EINVAL, "tt_learn_log_create: agent %d: numel <= 0 (numel_critic = %d)", a, j.numel_critic);
         if ((reinterpret_cast<uintptr_t>(j.grad_critic) | reinterpret_cast<uintptr_t>(j.grad_actor)) & 15)
-            return einval("tt_learn_log_create: agent %d: a gradient is not 16-byte aligned", a);
+            return fail(TT_EINVAL, "tt_learn_log_create: agent %d: a gradient is not 16-byte aligned", a);
         host[a] = LogJob{j.y, j.q, j.q_pi, j.dq_da, j.mu, {j.grad_critic, j.grad_actor}, {j.numel_critic, j.numel_actor},
                          reinterpret_cast<const long long *>(j.step_dev)};
     }
     LogJob *dj = nullptr;
     Record *ring = nullptr;
     const size_t ring_bytes = sizeof(Record) * (size_t)agents * (size_t)capacity;
-    if (hipMalloc(&dj, sizeof(LogJob) * agents) != hipSuccess) return tthost::fail_library(TT_ENOMEM, "tt_learn_log_create: hipMalloc");
+    if (hipMalloc(&dj, sizeof(LogJob) * agents) != hipSuccess) return fail(TT_ENOMEM, "tt_learn_log_create: hipMalloc");
     if (hipMalloc(&ring, ring_bytes) != hipSuccess) {
         (void)hipFree(dj);
-        return tthost::fail_library(TT_ENOMEM, "tt_learn_log_create: hipMalloc");
+        return fail(TT_ENOMEM, "tt_learn_log_create: hipMalloc");
     }
     // every byte 0xff: step = -1 in every head and part
     if (hipMemcpy(dj, host.data(), sizeof(LogJob) * agents, hipMemcpyHostToDevice) != hipSuccess ||
         hipMemset(ring, 0xff, ring_bytes) != hipSuccess || hipDeviceSynchronize() != hipSuccess) {
         (void)hipFree(dj);
         (void)hipFree(ring);
-        return tthost::fail_library(TT_EHIP, "tt_learn_log_create: filling the device block");
+        return fail(TT_EHIP, "tt_learn_log_create: filling the device block");
     }
     tt_learn_log *h = new tt_learn_log;
     h->K = agents; h->B = batch; h->capacity = (int)capacity; h->every = every;
@@ -281,23 +281,23 @@ int tt_learn_log_create(int agents, int batch, const tt_learn_log_job *jobs, int
 }
 
 int tt_learn_log_append(tt_learn_log *h, tt_stream_t stream) {
-    if (!h) return einval("tt_learn_log_append: handle is NULL");
+    if (!h) return fail(TT_EINVAL, "tt_learn_log_append: handle is NULL");
     hipLaunchKernelGGL(k_learn_log, dim3(h->K * (1 + 2 * G)), dim3(NT), 0, stream, h->jobs, h->ring, h->B, h->capacity, h->every);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
 }
 
 int tt_learn_log_drain(tt_learn_log *h, int agent, int64_t after_step, int64_t max, int64_t *step_out, double *values_out,
                        int32_t *nonfinite_out, int64_t *count) {
-    if (!h) return einval("tt_learn_log_drain: handle is NULL");
-    if (!count) return einval("tt_learn_log_drain: count is NULL");
+    if (!h) return fail(TT_EINVAL, "tt_learn_log_drain: handle is NULL");
+    if (!count) return fail(TT_EINVAL, "tt_learn_log_drain: count is NULL");
     *count = 0;
-    if (agent < 0 || agent >= h->K) return einval("tt_learn_log_drain: agent %d is not in [0, agents = %d)", agent, h->K);
-    if (max < 0) return einval("tt_learn_log_drain: max < 0");
-    if (max > 0 && (!step_out || !values_out || !nonfinite_out)) return einval("tt_learn_log_drain: an output array is NULL");
+    if (agent < 0 || agent >= h->K) return fail(TT_EINVAL, "tt_learn_log_drain: agent %d is not in [0, agents = %d)", agent, h->K);
+    if (max < 0) return fail(TT_EINVAL, "tt_learn_log_drain: max < 0");
+    if (max > 0 && (!step_out || !values_out || !nonfinite_out)) return fail(TT_EINVAL, "tt_learn_log_drain: an output array is NULL");
     std::vector<Record> host(h->capacity);
-    if (hipDeviceSynchronize() != hipSuccess) return tthost::fail_library(TT_EHIP, "tt_learn_log_drain: hipDeviceSynchronize");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(TT_EHIP, "tt_learn_log_drain: hipDeviceSynchronize");
     if (hipMemcpy(host.data(), h->ring + (size_t)agent * h->capacity, sizeof(Record) * host.size(), hipMemcpyDeviceToHost) != hipSuccess)
-        return tthost::fail_library(TT_EHIP, "tt_learn_log_drain: hipMemcpy");
+        return fail(TT_EHIP, "tt_learn_log_drain: hipMemcpy");
     std::vector<const Record *> found;
     for (int s = 0; s < h->capacity; ++s) {
         const Record &r = host[s];
@@ -328,14 +328,14 @@ int tt_learn_log_drain(tt_learn_log *h, int agent, int64_t after_step, int64_t m
 }
 
 int tt_learn_log_clear(tt_learn_log *h, tt_stream_t stream) {
-    if (!h) return einval("tt_learn_log_clear: handle is NULL");
+    if (!h) return fail(TT_EINVAL, "tt_learn_log_clear: handle is NULL");
     return hipMemsetAsync(h->ring, 0xff, sizeof(Record) * (size_t)h->K * (size_t)h->capacity, stream) == hipSuccess
                ? TT_OK
-               : tthost::fail_library(TT_EHIP, "tt_learn_log_clear: hipMemsetAsync");
+               : fail(TT_EHIP, "tt_learn_log_clear: hipMemsetAsync");
 }
 
 int tt_learn_log_destroy(tt_learn_log *h) {
-    if (!h) return einval("tt_learn_log_destroy: handle is NULL");
+    if (!h) return fail(TT_EINVAL, "tt_learn_log_destroy: handle is NULL");
     const hipError_t e = hipFree(h->jobs), e2 = hipFree(h->ring);
     delete h;
     return e == hipSuccess && e2 == hipSuccess ? TT_OK : TT_EHIP;

@@ -134,11 +134,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_forward_v2(const int n, const fl
     f32x4 acc2[NT2];
 #pragma unroll
     for (int t = 0; t < NT2; ++t) acc2[t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#ifdef TT_DBG_SHORT_K
-    constexpr int SS = 2, NSS = 1;     // timing experiment only: 2 of the 25 k16 steps
-#else
     constexpr int SS = 2, NSS = (H1 / 16 + SS - 1) / SS;          // 25 k16 steps -> 13 super-steps (the last holds 1)
-#endif
     struct BFrag { float4 v[SS][NT2]; };
     const float *wbase = W.w2 + (size_t)l15 * H1 + 4 * l4;        // + t*16*H1 per tile
     auto load_b = [&](int ss) {
@@ -315,26 +311,24 @@ int tt_actor_forward(int n, const float *obs, const tt_mlp_weights *w, float *mu
     return launch<false>(n, obs, nullptr, w, mu_out, act, stream);
 }
 
+// the choose_action epilogue's arguments of both tt_actor_act* entry points (the ring's adds its cursor)
+static ActArgs act_args(float *ou_state, const uint8_t *done_prev, float *act_raw, float *act_scaled, const int64_t *step_dev,
+                        uint64_t seed, uint64_t step, float theta_dt, float sigma_sqrt_dt, float high) {
+    ActArgs act{};
+    act.ou = ou_state; act.done_prev = done_prev; act.act_raw = act_raw; act.act_scaled = act_scaled;
+    act.step_dev = reinterpret_cast<const long long *>(step_dev);
+    act.seed = seed; act.step = step;
+    act.decay = 1.0f - theta_dt; act.scale = sigma_sqrt_dt; act.high = high;
+    return act;
+}
+
 int tt_actor_act(int n, const float *obs, const tt_mlp_weights *w, float *ou_state, const uint8_t *done_prev,
                  uint64_t seed, uint64_t step, const int64_t *step_dev, float theta_dt, float sigma_sqrt_dt, float high,
                  float *mu_out, float *act_raw_out, float *act_scaled_out, tt_stream_t stream) {
     if (n < 0 || !obs || !ou_state || !act_raw_out || !act_scaled_out || !check_ptrs(w, false)) return TT_EINVAL;
     if (n == 0) return TT_OK;
-    ActArgs act{};
-    act.ou = ou_state; act.done_prev = done_prev; act.act_raw = act_raw_out; act.act_scaled = act_scaled_out;
-    act.step_dev = reinterpret_cast<const long long *>(step_dev);
-    act.seed = seed; act.step = step;
-    act.decay = 1.0f - theta_dt; act.scale = sigma_sqrt_dt; act.high = high;
+    const ActArgs act = act_args(ou_state, done_prev, act_raw_out, act_scaled_out, step_dev, seed, step, theta_dt, sigma_sqrt_dt, high);
     return launch<false>(n, obs, nullptr, w, mu_out, act, stream);
-}
-
-static int make_sample(int batch, int n_envs, int slots, const int64_t *k_dev, const float *obs, const float *act,
-                       const float *rew, const uint8_t *done, uint64_t seed, int reserve, int lag, const tt_side_buffer *side,
-                       float *s_out, float *a_out, float *r_out, float *s2_out, uint8_t *d_out, int32_t *idx_out,
-                       RingSample &R) {
-    const tt_sample_args a{batch, n_envs, slots, reserve, k_dev, obs, act, rew, done, seed, side, s_out, a_out, r_out, s2_out,
-                           d_out, idx_out, lag, 1, 0, nullptr};
-    return make_ring_sample(&a, R);
 }
 
 int tt_actor_act_ring(int n, const tt_ring_view *ring, const tt_mlp_weights *w, float *ou_state, uint64_t seed, uint64_t step,
@@ -343,11 +337,7 @@ int tt_actor_act_ring(int n, const tt_ring_view *ring, const tt_mlp_weights *w, 
     if (n <= 0 || !ring || !ring->cursor || !ring->obs || !ring->act || !ring->done || ring->n_envs != n || !ou_state ||
         !step_dev || !act_scaled_out || !check_ptrs(w, false) || !w->split_ws || !w->ws_packed)
         return TT_EINVAL;          // (ring addressing goes with a caller-kept image: the pack launch writes the cursor)
-    ActArgs act{};
-    act.ou = ou_state; act.done_prev = ring->done; act.act_raw = ring->act; act.act_scaled = act_scaled_out;
-    act.step_dev = reinterpret_cast<const long long *>(step_dev);
-    act.seed = seed; act.step = step;
-    act.decay = 1.0f - theta_dt; act.scale = sigma_sqrt_dt; act.high = high;
+    ActArgs act = act_args(ou_state, ring->done, ring->act, act_scaled_out, step_dev, seed, step, theta_dt, sigma_sqrt_dt, high);
     act.cursor = ring->cursor; act.ring_n = n; act.ring_slots = ring->slots;
     return launch<false>(n, ring->obs, nullptr, w, nullptr, act, stream);
 }
@@ -356,9 +346,10 @@ int tt_ring_sample(int batch, int n_envs, int slots, const int64_t *k_dev, const
                    const float *rew, const uint8_t *done, uint64_t seed, int reserve, int lag, const tt_side_buffer *side,
                    float *s_out, float *a_out, float *r_out, float *s2_out, uint8_t *d_out, int32_t *idx_out,
                    tt_stream_t stream) {
+    const tt_sample_args a{batch, n_envs, slots, reserve, k_dev, obs, act, rew, done, seed, side, s_out, a_out, r_out, s2_out,
+                           d_out, idx_out, lag, 1, 0, nullptr};
     RingSample R;
-    const int rc = make_sample(batch, n_envs, slots, k_dev, obs, act, rew, done, seed, reserve, lag, side, s_out, a_out, r_out,
-                               s2_out, d_out, idx_out, R);
+    const int rc = make_ring_sample(&a, R);
     if (rc != TT_OK || batch == 0) return rc;
     hipLaunchKernelGGL(k_ring_sample, dim3(batch), dim3(64), 0, stream, R);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
@@ -368,8 +359,7 @@ int tt_mlp_split_pack_and_sample(const tt_mlp_weights *w, int critic, void *ws, 
                                  const tt_ring_cursor *cursor, tt_stream_t stream) {
     if (!ws || !a || !check_ptrs(w, critic != 0)) return TT_EINVAL;
     RingSample R;
-    const int rc = make_sample(a->batch, a->n_envs, a->slots, a->k_dev, a->obs, a->act, a->rew, a->done, a->seed, a->reserve,
-                               a->lag, a->side, a->s_out, a->a_out, a->r_out, a->s2_out, a->d_out, a->idx_out, R);
+    const int rc = make_ring_sample(a, R);      // (leaves one draw and no progress word whatever `a` says)
     if (rc != TT_OK) return rc;
     if (a->draws < 0 || (long long)(a->draws > 1 ? a->draws : 1) * a->batch > (1 << 24)) return TT_EINVAL;
     if (a->draws > 1) { R.draws = a->draws; R.seed_stride = a->seed_stride; }

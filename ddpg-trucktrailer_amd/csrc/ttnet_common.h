@@ -1,12 +1,13 @@
 // ttnet_common.h -- what the inference kernels of csrc/ttnet.hip (exact-f32 MFMA) and csrc/ttnet_split.hip (split-bf16
 // MFMA) share: the network shapes of trainv2.py:404-407, the kernel-side weight / choose_action argument structs, the
-// Philox generator and the per-row tail of the forward (head output -> tanh -> OU noise -> clip*high).
+// Philox generator (csrc/ttphilox.h) and the per-row tail of the forward (head output -> tanh -> OU noise -> clip*high).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <cstdint>
 
 #include "ttenv.h"
+#include "ttphilox.h"
 
 namespace ttnet {
 
@@ -47,18 +48,7 @@ __device__ __forceinline__ const float *resolve_obs(const ActArgs &act, const fl
     return act.cursor ? obs + (size_t)cursor_of(act)[0] * act.ring_n * IN : obs;
 }
 
-__device__ inline void philox4x32(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0, uint32_t k1,
-                                  uint32_t out[4]) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
-        const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
-        const uint32_t n0 = hi1 ^ c1 ^ k0, n2 = hi0 ^ c3 ^ k1;
-        c0 = n0; c1 = lo1; c2 = n2; c3 = lo0;
-        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
-    }
-    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
-}
+using ttrng::philox4x32;
 
 // The tail of one row once the head's pre-activation v is known.  Critic: out[row] = v.  Actor: mu = tanh(v)
 // (networks.py:145) and, when act.ou is set, DDPG_agent.choose_action + trainv2.py:516: OU noise (noise.py:13-17:

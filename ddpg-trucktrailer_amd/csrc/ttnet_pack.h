@@ -14,12 +14,7 @@ using h2 = __attribute__((ext_vector_type(2))) _Float16;
 constexpr int ROWS = 128, WROWS = 32;       // envs per workgroup / per wave
 constexpr int T1 = 13, H1P = 32 * T1;       // layer-1 neuron tiles (416 >= 400)
 constexpr int T2 = 10, H2P = 32 * T2;       // layer-2 neuron tiles (320 >= 300)
-#ifdef TT_DBG_STEPS                         // timing experiments only (wrong results): fewer k16 steps of layer 2
-constexpr int STEPS = TT_DBG_STEPS;
-#else
 constexpr int STEPS = H1 / 16;              // 25 k16 steps of layer 2
-#endif
-constexpr int STEPS_FULL = H1 / 16;         // the h1 pieces always cover all 25 steps
 constexpr int S1 = 2;                       // k16 steps of layer 1: inputs 0..22 = observation, 23 = 1 (bias), 24..31 = 0
 constexpr int PIECES = 2 * T2;              // one k16 step of packed fc2 = 10 tiles x 2 planes of 64 lanes x 16 B: 5 per wave
 constexpr int CHUNK_U4 = PIECES * 64;

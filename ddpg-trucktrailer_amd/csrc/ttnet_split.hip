@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
         __builtin_amdgcn_s_barrier();
 #pragma unroll
         for (int i = 10; i < 5 * (AHEAD + 1); ++i) issue_step_piece(wsl_cur, ldsw_w2, i / 5, i % 5);
-        uint32_t hb[STEPS_FULL][4], mb[STEPS_FULL][4];
+        uint32_t hb[STEPS][4], mb[STEPS][4];
         // LayerNorm(400) (biased variance, eps 1e-5) on the SCALED pre-activations: mean and deviations scale with them,
         // 1/sigma absorbs the scale; then gamma*SX, beta*SX and ReLU give the layer-2 operand already scaled by SX.
         // Tile 12 holds neurons 384..399 in v < 8.
@@ -390,9 +390,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
                         case 1: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
                         default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
                     }
-#ifndef TT_DBG_NOBAR
                     __builtin_amdgcn_s_barrier();
-#endif
                     SB;
                 }
                 const bool more = u + 2 < T2 || s + 1 < STEPS;                // is there a tile two ahead to prefetch
@@ -405,9 +403,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
                 if (more) c2m = lds_frag(LB, nx + 1024);
                 SB;
                 acc2[u] = mfma_f16(c0h, vh, acc2[u]); SB;
-#ifndef TT_DBG_NODMA
                 if (u >= 5 && s + RING - 1 < STEPS) issue_step_piece(wsl_s, lds_s, s + RING - 1, u - 5);
-#endif
                 SB;
                 c0h = c1h; c0m = c1m; c1h = c2h; c1m = c2m;
             }

@@ -73,4 +73,15 @@ __device__ __forceinline__ NstepPick nstep_pick(const RingSample &R, const int b
     return p;
 }
 
+// the picked row's pieces: s and a at the base step, s' m steps later
+__device__ __forceinline__ const float *nstep_s(const RingSample &R, const NstepPick &p) {
+    return R.obs + ((size_t)p.t0 * R.n_envs + p.e) * IN;
+}
+__device__ __forceinline__ const float *nstep_s2(const RingSample &R, const NstepPick &p) {
+    return R.obs + ((size_t)p.t2 * R.n_envs + p.e) * IN;
+}
+__device__ __forceinline__ float nstep_a(const RingSample &R, const NstepPick &p) {
+    return R.act[(size_t)p.t0 * R.n_envs + p.e];
+}
+
 }  // namespace ttnet

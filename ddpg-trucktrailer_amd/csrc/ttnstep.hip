@@ -12,32 +12,20 @@
 #include "ttlearn_bodies.h"
 #include "ttnstep.h"
 
-#include <cstdio>
-
-using tthost::einval;
+using tthost::fail;
 
 namespace {
-
-__device__ __forceinline__ const float *nstep_s(const ttnet::RingSample &R, const ttnet::NstepPick &p) {
-    return R.obs + ((size_t)p.t0 * R.n_envs + p.e) * ttnet::IN;
-}
-__device__ __forceinline__ const float *nstep_s2(const ttnet::RingSample &R, const ttnet::NstepPick &p) {
-    return R.obs + ((size_t)p.t2 * R.n_envs + p.e) * ttnet::IN;
-}
-__device__ __forceinline__ float nstep_a(const ttnet::RingSample &R, const ttnet::NstepPick &p) {
-    return R.act[(size_t)p.t0 * R.n_envs + p.e];
-}
 
 // one wave per batch row, the lanes as in ring_sample_row: 0..22 copy s, 32..54 copy s', 63 the scalars
 __global__ __launch_bounds__(64) void k_ring_sample_nstep(const ttnet::RingSample R, const int n_step, const float gamma) {
     const int b = blockIdx.x, lane = threadIdx.x;
     if (b >= R.batch) return;
     const ttnet::NstepPick p = ttnet::nstep_pick(R, b, n_step, gamma);
-    const float *src = nstep_s(R, p), *src2 = nstep_s2(R, p);
+    const float *src = ttnet::nstep_s(R, p), *src2 = ttnet::nstep_s2(R, p);
     if (lane < ttnet::IN) R.s_out[(size_t)b * ttnet::IN + lane] = src[lane];
     else if (lane >= 32 && lane < 32 + ttnet::IN) R.s2_out[(size_t)b * ttnet::IN + lane - 32] = src2[lane - 32];
     if (lane == 63) {
-        R.a_out[b] = nstep_a(R, p);
+        R.a_out[b] = ttnet::nstep_a(R, p);
         R.r_out[b] = p.R;
         R.d_out[b] = (uint8_t)p.D;
         if (R.idx_out) { R.idx_out[2 * b] = p.t0; R.idx_out[2 * b + 1] = p.e; }
@@ -61,13 +49,13 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi_nstep(const FwdJobs J, co
     const bool from_s = q.obs == J.R.s_out;                  // this job reads s (else s')
     const float *orow;
     // (a branch, not a select: only the rows at t0 + m need the walk's done flags)
-    if (from_s) orow = nstep_s(J.R, ttnet::nstep_pick(J.R, min(row0 + l15, J.n - 1), n_step, gamma));
-    else orow = nstep_s2(J.R, ttnet::nstep_pick(J.R, min(row0 + l15, J.n - 1), n_step, gamma));
+    if (from_s) orow = ttnet::nstep_s(J.R, ttnet::nstep_pick(J.R, min(row0 + l15, J.n - 1), n_step, gamma));
+    else orow = ttnet::nstep_s2(J.R, ttnet::nstep_pick(J.R, min(row0 + l15, J.n - 1), n_step, gamma));
     bool have_act = false;
     float act_r0 = 0.f, act_r1 = 0.f;
     if (q.critic && q.action) {
-        act_r0 = nstep_a(J.R, ttnet::nstep_pick(J.R, min(row0 + wave * 2, J.n - 1), n_step, gamma));
-        act_r1 = nstep_a(J.R, ttnet::nstep_pick(J.R, min(row0 + wave * 2 + 1, J.n - 1), n_step, gamma));
+        act_r0 = ttnet::nstep_a(J.R, ttnet::nstep_pick(J.R, min(row0 + wave * 2, J.n - 1), n_step, gamma));
+        act_r1 = ttnet::nstep_a(J.R, ttnet::nstep_pick(J.R, min(row0 + wave * 2 + 1, J.n - 1), n_step, gamma));
         have_act = true;
     }
     if (job == J.write_s || job == J.write_s2) {
@@ -76,14 +64,14 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi_nstep(const FwdJobs J, co
         if (lr < TR && b < J.n) {
             const ttnet::NstepPick p = ttnet::nstep_pick(J.R, b, n_step, gamma);
             if (job == J.write_s) {
-                J.R.s_out[(size_t)b * ttnet::IN + c] = nstep_s(J.R, p)[c];
+                J.R.s_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s(J.R, p)[c];
                 if (c == 0) {
-                    J.R.a_out[b] = nstep_a(J.R, p);
+                    J.R.a_out[b] = ttnet::nstep_a(J.R, p);
                     if (J.R.idx_out) { J.R.idx_out[2 * b] = p.t0; J.R.idx_out[2 * b + 1] = p.e; }
                 }
             }
             if (job == J.write_s2) {
-                J.R.s2_out[(size_t)b * ttnet::IN + c] = nstep_s2(J.R, p)[c];
+                J.R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s2(J.R, p)[c];
                 if (c == 0) { J.R.r_out[b] = p.R; J.R.d_out[b] = (uint8_t)p.D; }
             }
         }
@@ -96,17 +84,12 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi_nstep(const FwdJobs J, co
 
 // what both entry points refuse beyond make_ring_sample's own checks (host only: no HIP call); `who` names the entry point
 int check_nstep(const char *who, const tt_sample_args *a, const int n_step, const float gamma, ttnet::RingSample &R) {
-    char fmt[200];
-    const auto refuse = [&](const char *what, int x = 0, int y = 0) {
-        snprintf(fmt, sizeof fmt, "%s: %s", who, what);
-        return einval(fmt, x, y);
-    };
-    if (!a) return refuse("no sample (tt_sample_args)");
+    if (!a) return fail(TT_EINVAL, "%s: no sample (tt_sample_args)", who);
     if (const int rc = tthost::refuse_nstep(who, n_step, gamma)) return rc;
-    if (ttnet::make_ring_sample(a, R) != TT_OK) return refuse("bad tt_sample_args");
+    if (ttnet::make_ring_sample(a, R) != TT_OK) return fail(TT_EINVAL, "%s: bad tt_sample_args", who);
     if (const int rc = tthost::refuse_nstep_window(who, n_step, a->slots, a->reserve)) return rc;
-    if (n_step > 1 && R.side.count > 0) return refuse("a side buffer (%d tuples) with n_step %d: side tuples are single steps", R.side.count, n_step);
-    if (a->draws > 1) return refuse("draws = %d: one draw per launch", a->draws);
+    if (n_step > 1 && R.side.count > 0) return fail(TT_EINVAL, "%s: a side buffer (%d tuples) with n_step %d: side tuples are single steps", who, R.side.count, n_step);
+    if (a->draws > 1) return fail(TT_EINVAL, "%s: draws = %d: one draw per launch", who, a->draws);
     return TT_OK;
 }
 
@@ -126,11 +109,11 @@ int tt_mlp_forward_multi_sampled_nstep(int n, int count, const tt_fwd_job *jobs,
                                        float gamma, int64_t *k_snapshot, tt_stream_t stream) {
     static const char who[] = "tt_mlp_forward_multi_sampled_nstep";
     if (n < 0 || count < 1 || count > 4 || !jobs)
-        return einval("tt_mlp_forward_multi_sampled_nstep: n = %d, count = %d or no jobs", n, count);
+        return fail(TT_EINVAL, "tt_mlp_forward_multi_sampled_nstep: n = %d, count = %d or no jobs", n, count);
     FwdJobs J{};
     const int rc = check_nstep(who, sample, n_step, gamma, J.R);
     if (rc != TT_OK) return rc;
-    if (sample->batch != n) return einval("tt_mlp_forward_multi_sampled_nstep: the draw has %d rows, the forwards %d", sample->batch, n);
+    if (sample->batch != n) return fail(TT_EINVAL, "tt_mlp_forward_multi_sampled_nstep: the draw has %d rows, the forwards %d", sample->batch, n);
     J.n = n;
     J.blocks_per_job = (n + TR - 1) / TR;
     J.write_s = J.write_s2 = -1;
@@ -139,9 +122,9 @@ int tt_mlp_forward_multi_sampled_nstep(int n, int count, const tt_fwd_job *jobs,
     J.k_snapshot = reinterpret_cast<long long *>(k_snapshot);
     for (int i = 0; i < count; ++i)
         if (!to_fwd_job(jobs[i], i, sample, J))
-            return einval("tt_mlp_forward_multi_sampled_nstep: forward job %d is incomplete or does not read the draw's buffers", i);
+            return fail(TT_EINVAL, "tt_mlp_forward_multi_sampled_nstep: forward job %d is incomplete or does not read the draw's buffers", i);
     if (J.write_s < 0 || J.write_s2 < 0)      // the later launches need all five batch buffers
-        return einval("tt_mlp_forward_multi_sampled_nstep: the jobs need at least one on s and one on s'");
+        return fail(TT_EINVAL, "tt_mlp_forward_multi_sampled_nstep: the jobs need at least one on s and one on s'");
     if (n == 0) return TT_OK;
     hipLaunchKernelGGL(k_fwd_multi_nstep, dim3(count * J.blocks_per_job), dim3(64 * NW), 0, stream, J, n_step, gamma);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;

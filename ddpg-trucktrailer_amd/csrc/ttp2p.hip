@@ -13,16 +13,17 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "tthost.h"
 #include "ttp2p.h"
 
 namespace {
 
-char g_err[256] = "";
+char g_err[tthost::ERR_BYTES] = "";      // tt_p2p_last_error(NULL): a channel of its own beside tt_last_error(NULL)
 
-int fail(tt_p2p *x, int code, const char *fmt, ...) {
+__attribute__((format(printf, 3, 4))) int fail(tt_p2p *x, int code, const char *fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
-    vsnprintf(x ? x->err : g_err, 256, fmt, ap);
+    tthost::vfail(x ? x->err : g_err, code, fmt, ap);
     va_end(ap);
     return code;
 }
@@ -45,6 +46,7 @@ int tt_p2p_create(int device, int rank, int world, int sites, const int32_t *num
                     sites, ttp2p::MAXS);
     static_assert(2 * sizeof(hipIpcMemHandle_t) == TT_P2P_HANDLE_BYTES, "TT_P2P_HANDLE_BYTES");
     static_assert(sizeof(int) * ttp2p::MAXS * ttp2p::MAXR <= ttp2p::FLAG_BYTES, "arrival words fit the flag block");
+    static_assert(sizeof(tt_p2p::err) == tthost::ERR_BYTES, "a handle's message buffer is tthost::vfail's");
     tt_p2p *x = new tt_p2p();
     memset(x, 0, sizeof(*x));
     x->device = device; x->rank = rank; x->world = world; x->sites = sites;

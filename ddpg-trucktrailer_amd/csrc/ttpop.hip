@@ -27,7 +27,7 @@
 #include <cstdio>
 #include <vector>
 
-using tthost::einval;
+using tthost::fail;
 
 namespace {
 
@@ -243,26 +243,26 @@ __global__ __launch_bounds__(EX_THREADS) void k_pop_exploit(const ExploitList L,
 int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
     P = PopAgent{};
     const tt_sample_args *smp = g.sample;
-    if (!smp) return einval("tt_pop_learn_create: agent %d has no sample (tt_sample_args)", a);
-    if (smp->batch != n) return einval("tt_pop_learn_create: agent %d draws batches of %d rows, not the population's B", a, smp->batch);
-    if (smp->step_progress || (smp->draws > 1)) return einval("tt_pop_learn_create: agent %d: step_progress / draws are not for populations", a);
-    if (smp->side && smp->side->count > 0) return einval("tt_pop_learn_create: agent %d has a side buffer (not in populations)", a);
-    if (ttnet::make_ring_sample(smp, P.F.R) != TT_OK) return einval("tt_pop_learn_create: agent %d: bad tt_sample_args", a);
+    if (!smp) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d has no sample (tt_sample_args)", a);
+    if (smp->batch != n) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d draws batches of %d rows, not the population's B", a, smp->batch);
+    if (smp->step_progress || (smp->draws > 1)) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: step_progress / draws are not for populations", a);
+    if (smp->side && smp->side->count > 0) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d has a side buffer (not in populations)", a);
+    if (ttnet::make_ring_sample(smp, P.F.R) != TT_OK) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: bad tt_sample_args", a);
     P.F.R.seed_stride = smp->seed_stride;
     P.F.n = n;
     P.F.blocks_per_job = (n + TR - 1) / TR;
     P.F.sampled = 1;
     P.F.write_s = P.F.write_s2 = -1;
     const tt_fwd_job *jobs = g.jobs;
-    if (!jobs) return einval("tt_pop_learn_create: agent %d has no forward jobs", a);
+    if (!jobs) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d has no forward jobs", a);
     // the lone learn()'s four forwards, in their order: target actor on s', the target critic's state branch on s', Q(s, a), mu(s)
     if (jobs[0].critic || jobs[0].obs != smp->s2_out || !jobs[1].critic || jobs[1].obs != smp->s2_out || !jobs[1].z_state ||
         !jobs[2].critic || jobs[2].obs != smp->s_out || jobs[2].action != smp->a_out || !jobs[2].saved || jobs[3].critic ||
         jobs[3].obs != smp->s_out || !jobs[3].saved)
-        return einval("tt_pop_learn_create: agent %d: the jobs are not learn()'s four forwards on its draw", a);
+        return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: the jobs are not learn()'s four forwards on its draw", a);
     for (int i = 0; i < 4; ++i)
         if (!to_fwd_job(jobs[i], i, smp, P.F))
-            return einval("tt_pop_learn_create: agent %d: forward job %d is incomplete or has an action other than the draw's a on s", a, i);
+            return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: forward job %d is incomplete or has an action other than the draw's a on s", a, i);
     P.scale_c = (float)(2.0 / n);
     P.q_out = jobs[2].out;
     P.mu_out = jobs[3].out;
@@ -270,25 +270,25 @@ int to_pop_agent(const tt_pop_agent &g, const int a, const int n, PopAgent &P) {
     P.Wa = P.F.j[3].W;
     P.sv_c = P.F.j[2].sv;
     P.sv_a = P.F.j[3].sv;
-    if (!P.q_out || !P.mu_out) return einval("tt_pop_learn_create: agent %d: Q(s, a) and mu(s) need outputs", a);
+    if (!P.q_out || !P.mu_out) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: Q(s, a) and mu(s) need outputs", a);
     if (!to_bwd_out(g.critic.ws, P.o_c) || !to_bwd_out(g.actor.ws, P.o_a) || P.o_c.dx2 == P.o_a.dx2)
-        return einval("tt_pop_learn_create: agent %d: the per-row workspaces (tt_mlp_bwd_ws) are incomplete or shared", a);
+        return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: the per-row workspaces (tt_mlp_bwd_ws) are incomplete or shared", a);
     const tt_td_input *tdi = g.td;
     if (!to_td(tdi, P.td) || !tdi->step_dev || tdi->window_dev)
-        return einval("tt_pop_learn_create: agent %d: bad tt_td_input (a step counter is required, a window counter is not for populations)", a);
+        return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: bad tt_td_input (a step counter is required, a window counter is not for populations)", a);
     P.s = smp->s_out;
     P.a = smp->a_out;
     for (int net = 0; net < 2; ++net) {
         const tt_pop_net &t = net ? g.actor : g.critic;
         const bool critic = net == 0;
-        if (!ok_shape(t.grads, critic)) return einval("tt_pop_learn_create: agent %d: network %d has no gradient buffers", a, net);
+        if (!ok_shape(t.grads, critic)) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: network %d has no gradient buffers", a, net);
         AdamFused &A = critic ? P.Ac : P.Aa;
         if (!to_adam(critic, t.count, t.params, t.exp_avg, t.exp_avg_sq, t.targets, tdi->step_dev, t.lr, t.beta1, t.beta2, t.eps,
                      t.weight_decay, t.tau, t.images, tdi->bias_corr_out, A))
-            return einval("tt_pop_learn_create: agent %d: network %d has an incomplete optimizer step", a, net);
+            return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: network %d has an incomplete optimizer step", a, net);
         (critic ? P.Gc : P.Ga) = to_grads(t.grads);
     }
-    if (!g.q_pi || !g.dq_da || !g.tail_words) return einval("tt_pop_learn_create: agent %d: q_pi, dq_da and tail_words are required", a);
+    if (!g.q_pi || !g.dq_da || !g.tail_words) return fail(TT_EINVAL, "tt_pop_learn_create: agent %d: q_pi, dq_da and tail_words are required", a);
     P.q_pi = g.q_pi;
     P.dq_da = g.dq_da;
     P.RSa = RowScale{g.dq_da, P.mu_out, (float)(-1.0 / n)};
@@ -303,15 +303,13 @@ float *td_gamma_of(PopAgent *P) { return reinterpret_cast<float *>(reinterpret_c
 // what tt_pop_learn_set_nstep ("agent" i) and tt_pop_exploit_nstep ("pair" i) refuse in one tt_pop_nstep, for a ring of `slots`
 // slots (host only: no HIP call)
 int check_pop_nstep(const char *who, const char *what, const int i, const struct tt_pop_nstep &q, const int slots, const int reserve) {
-    char at[200];
+    char at[200];       // "<who>: agent <i>", the name every message starts with (a "%s" argument, never a format)
     snprintf(at, sizeof at, "%s: %s %d", who, what, i);
     if (const int rc = tthost::refuse_nstep(at, q.n_step, q.gamma)) return rc;
-    const char *why = nullptr;
-    if (q.n_step == 1 && q.discount != q.gamma) why = "discount is not gamma although n_step is 1";
-    if (q.n_step > 1 && !(q.discount > 0.f && q.discount < q.gamma)) why = "discount is outside (0, gamma) although n_step > 1";
-    if (!why) return tthost::refuse_nstep_window(at, q.n_step, slots, reserve);
-    snprintf(at, sizeof at, "%s: %s %%d: %s", who, what, why);
-    return einval(at, i);
+    if (q.n_step == 1 && q.discount != q.gamma) return fail(TT_EINVAL, "%s: discount is not gamma although n_step is 1", at);
+    if (q.n_step > 1 && !(q.discount > 0.f && q.discount < q.gamma))
+        return fail(TT_EINVAL, "%s: discount is outside (0, gamma) although n_step > 1", at);
+    return tthost::refuse_nstep_window(at, q.n_step, slots, reserve);
 }
 
 }  // namespace
@@ -325,31 +323,26 @@ struct tt_population {
 
 // what tt_pop_exploit and tt_pop_exploit_nstep (`who`) refuse in a list of pairs, which goes into L (host only: no HIP call)
 static int check_pairs(const char *who, const tt_population *h, const int pairs, const tt_pop_exploit_pair *list, ExploitList &L) {
-    char fmt[200];
-    const auto refuse = [&](const char *what, int a = 0, int b = 0) {
-        snprintf(fmt, sizeof fmt, "%s: %s", who, what);
-        return einval(fmt, a, b);
-    };
-    if (!h) return refuse("handle is NULL");
-    if (!list) return refuse("list is NULL");
+    if (!h) return fail(TT_EINVAL, "%s: handle is NULL", who);
+    if (!list) return fail(TT_EINVAL, "%s: list is NULL", who);
     const int K = h->K;
-    if (pairs < 1 || pairs > K) return refuse("pairs = %d, not in [1, K = %d]", pairs, K);
+    if (pairs < 1 || pairs > K) return fail(TT_EINVAL, "%s: pairs = %d, not in [1, K = %d]", who, pairs, K);
     L.n = pairs;
     for (int i = 0; i < pairs; ++i) {
         const tt_pop_exploit_pair &q = list[i];
-        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K) return refuse("pair %d names an agent outside [0, K = %d)", i, K);
+        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K) return fail(TT_EINVAL, "%s: pair %d names an agent outside [0, K = %d)", who, i, K);
         for (int j = 0; j < pairs; ++j) {
             if (j == i) continue;
-            if (list[j].dst == q.dst) return refuse("pairs %d and %d have the same dst", i, j);
-            if (list[j].src == q.dst) return refuse("the dst of pair %d is the src of pair %d", i, j);
+            if (list[j].dst == q.dst) return fail(TT_EINVAL, "%s: pairs %d and %d have the same dst", who, i, j);
+            if (list[j].src == q.dst) return fail(TT_EINVAL, "%s: the dst of pair %d is the src of pair %d", who, i, j);
         }
         const float h4[4] = {q.alpha, q.beta, q.tau, q.gamma};
         for (const float x : h4)
-            if (!std::isfinite(x)) return refuse("pair %d has a non-finite hyperparameter", i);
+            if (!std::isfinite(x)) return fail(TT_EINVAL, "%s: pair %d has a non-finite hyperparameter", who, i);
         if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
-            return refuse("pair %d: alpha and beta must lie in (0, 1]", i);
-        if (!(q.tau > 0.f && q.tau <= 1.f)) return refuse("pair %d: tau must lie in (0, 1]", i);
-        if (!(q.gamma > 0.f && q.gamma < 1.f)) return refuse("pair %d: gamma must lie in (0, 1)", i);
+            return fail(TT_EINVAL, "%s: pair %d: alpha and beta must lie in (0, 1]", who, i);
+        if (!(q.tau > 0.f && q.tau <= 1.f)) return fail(TT_EINVAL, "%s: pair %d: tau must lie in (0, 1]", who, i);
+        if (!(q.gamma > 0.f && q.gamma < 1.f)) return fail(TT_EINVAL, "%s: pair %d: gamma must lie in (0, 1)", who, i);
         L.p[i] = q;
     }
     return TT_OK;
@@ -358,21 +351,21 @@ static int check_pairs(const char *who, const tt_population *h, const int pairs,
 extern "C" {
 
 int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents, tt_population **out) {
-    if (!out) return einval("tt_pop_learn_create: out is NULL");
+    if (!out) return fail(TT_EINVAL, "tt_pop_learn_create: out is NULL");
     *out = nullptr;
-    if (count < 1 || count > TT_POP_MAX_AGENTS) return einval("tt_pop_learn_create: count = %d agents, not in [1, %d]", count, TT_POP_MAX_AGENTS);
-    if (batch < 1 || batch > MAXB) return einval("tt_pop_learn_create: batch = %d rows, not in [1, %d]", batch, MAXB);
-    if (!agents) return einval("tt_pop_learn_create: agents is NULL");
+    if (count < 1 || count > TT_POP_MAX_AGENTS) return fail(TT_EINVAL, "tt_pop_learn_create: count = %d agents, not in [1, %d]", count, TT_POP_MAX_AGENTS);
+    if (batch < 1 || batch > MAXB) return fail(TT_EINVAL, "tt_pop_learn_create: batch = %d rows, not in [1, %d]", batch, MAXB);
+    if (!agents) return fail(TT_EINVAL, "tt_pop_learn_create: agents is NULL");
     std::vector<PopAgent> host(count);
     for (int a = 0; a < count; ++a) {
         const int rc = to_pop_agent(agents[a], a, batch, host[a]);
         if (rc != TT_OK) return rc;
     }
     PopAgent *dev = nullptr;
-    if (hipMalloc(&dev, sizeof(PopAgent) * count) != hipSuccess) return tthost::fail_library(TT_ENOMEM, "tt_pop_learn_create: hipMalloc");
+    if (hipMalloc(&dev, sizeof(PopAgent) * count) != hipSuccess) return fail(TT_ENOMEM, "tt_pop_learn_create: hipMalloc");
     if (hipMemcpy(dev, host.data(), sizeof(PopAgent) * count, hipMemcpyHostToDevice) != hipSuccess) {
         (void)hipFree(dev);
-        return tthost::fail_library(TT_EHIP, "tt_pop_learn_create: hipMemcpy");
+        return fail(TT_EHIP, "tt_pop_learn_create: hipMemcpy");
     }
     tt_population *h = new tt_population{count, batch, dev};
     for (int a = 0; a < count; ++a) {
@@ -384,8 +377,8 @@ int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents, tt_pop
 }
 
 int tt_pop_learn(tt_population *h, int update, tt_stream_t stream) {
-    if (!h) return einval("tt_pop_learn: handle is NULL");
-    if (update < 0) return einval("tt_pop_learn: update = %d < 0", update);
+    if (!h) return fail(TT_EINVAL, "tt_pop_learn: handle is NULL");
+    if (update < 0) return fail(TT_EINVAL, "tt_pop_learn: update = %d < 0", update);
     const int K = h->K, n = h->n, nb = (n + TR - 1) / TR;
     if (h->table) ttpop::launch_fwd_multi_nstep(K, n, h->dev, h->table, update, stream);
     else hipLaunchKernelGGL(k_pop_fwd_multi, dim3(K * 4 * nb), dim3(64 * NW), 0, stream, K, n, h->dev, update);
@@ -400,7 +393,7 @@ int tt_pop_exploit(tt_population *h, int pairs, const tt_pop_exploit_pair *list,
     const int rc = check_pairs("tt_pop_exploit", h, pairs, list, L);
     if (rc != TT_OK) return rc;
     if (h->table)
-        return einval("tt_pop_exploit: this population has an n-step table, where an agent's discount is gamma ** n_step and not the "
+        return fail(TT_EINVAL, "tt_pop_exploit: this population has an n-step table, where an agent's discount is gamma ** n_step and not the "
                       "pair's gamma: use tt_pop_exploit_nstep");
     hipLaunchKernelGGL(k_pop_exploit, dim3(pairs * EX_CHUNKS), dim3(EX_THREADS), 0, stream, L, h->dev);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
@@ -408,8 +401,8 @@ int tt_pop_exploit(tt_population *h, int pairs, const tt_pop_exploit_pair *list,
 
 int tt_pop_learn_set_nstep(tt_population *h, const struct tt_pop_nstep *per_agent) {
     static const char who[] = "tt_pop_learn_set_nstep";
-    if (!h) return einval("tt_pop_learn_set_nstep: handle is NULL");
-    if (!per_agent) return einval("tt_pop_learn_set_nstep: per_agent is NULL");
+    if (!h) return fail(TT_EINVAL, "tt_pop_learn_set_nstep: handle is NULL");
+    if (!per_agent) return fail(TT_EINVAL, "tt_pop_learn_set_nstep: per_agent is NULL");
     const int K = h->K;
     std::vector<PopNstep> host(K);
     for (int a = 0; a < K; ++a) {
@@ -417,15 +410,15 @@ int tt_pop_learn_set_nstep(tt_population *h, const struct tt_pop_nstep *per_agen
         if (rc != TT_OK) return rc;
         host[a] = PopNstep{per_agent[a].n_step, per_agent[a].gamma};
     }
-    if (hipDeviceSynchronize() != hipSuccess) return tthost::fail_library(TT_EHIP, "tt_pop_learn_set_nstep: hipDeviceSynchronize");
+    if (hipDeviceSynchronize() != hipSuccess) return fail(TT_EHIP, "tt_pop_learn_set_nstep: hipDeviceSynchronize");
     if (!h->table && hipMalloc(&h->table, sizeof(PopNstep) * K) != hipSuccess) {
         h->table = nullptr;
-        return tthost::fail_library(TT_ENOMEM, "tt_pop_learn_set_nstep: hipMalloc");
+        return fail(TT_ENOMEM, "tt_pop_learn_set_nstep: hipMalloc");
     }
     bool ok = hipMemcpy(h->table, host.data(), sizeof(PopNstep) * K, hipMemcpyHostToDevice) == hipSuccess;
     for (int a = 0; a < K && ok; ++a)
         ok = hipMemcpy(td_gamma_of(h->dev + a), &per_agent[a].discount, sizeof(float), hipMemcpyHostToDevice) == hipSuccess;
-    return ok ? TT_OK : tthost::fail_library(TT_EHIP, "tt_pop_learn_set_nstep: hipMemcpy");
+    return ok ? TT_OK : fail(TT_EHIP, "tt_pop_learn_set_nstep: hipMemcpy");
 }
 
 int tt_pop_exploit_nstep(tt_population *h, int pairs, const tt_pop_exploit_pair *list, const struct tt_pop_nstep *ns, tt_stream_t stream) {
@@ -433,14 +426,14 @@ int tt_pop_exploit_nstep(tt_population *h, int pairs, const tt_pop_exploit_pair 
     ExploitList L{};
     const int rc = check_pairs(who, h, pairs, list, L);
     if (rc != TT_OK) return rc;
-    if (!ns) return einval("tt_pop_exploit_nstep: ns is NULL");
-    if (!h->table) return einval("tt_pop_exploit_nstep: this population has no n-step table (tt_pop_learn_set_nstep makes it)");
+    if (!ns) return fail(TT_EINVAL, "tt_pop_exploit_nstep: ns is NULL");
+    if (!h->table) return fail(TT_EINVAL, "tt_pop_exploit_nstep: this population has no n-step table (tt_pop_learn_set_nstep makes it)");
     ttpop::NstepWrites W{};
     W.n = pairs;
     for (int i = 0; i < pairs; ++i) {
         const int dst = list[i].dst, rc2 = check_pop_nstep(who, "pair", i, ns[i], h->slots[dst], h->reserve[dst]);
         if (rc2 != TT_OK) return rc2;
-        if (ns[i].gamma != list[i].gamma) return einval("tt_pop_exploit_nstep: pair %d: ns.gamma is not the pair's gamma", i);
+        if (ns[i].gamma != list[i].gamma) return fail(TT_EINVAL, "tt_pop_exploit_nstep: pair %d: ns.gamma is not the pair's gamma", i);
         L.p[i].gamma = ns[i].discount;      // k_pop_exploit stores the pair's gamma into dst's td.gamma: the discount's place
         W.dst[i] = dst;
         W.n_step[i] = ns[i].n_step;
@@ -452,15 +445,15 @@ int tt_pop_exploit_nstep(tt_population *h, int pairs, const tt_pop_exploit_pair 
 }
 
 int tt_pop_nstep(tt_population *h, int agent, struct tt_pop_nstep *out) {
-    if (!h) return einval("tt_pop_nstep: handle is NULL");
-    if (!out) return einval("tt_pop_nstep: out is NULL");
-    if (agent < 0 || agent >= h->K) return einval("tt_pop_nstep: agent %d is not in [0, K = %d)", agent, h->K);
+    if (!h) return fail(TT_EINVAL, "tt_pop_nstep: handle is NULL");
+    if (!out) return fail(TT_EINVAL, "tt_pop_nstep: out is NULL");
+    if (agent < 0 || agent >= h->K) return fail(TT_EINVAL, "tt_pop_nstep: agent %d is not in [0, K = %d)", agent, h->K);
     float discount;
     if (hipMemcpy(&discount, td_gamma_of(h->dev + agent), sizeof discount, hipMemcpyDeviceToHost) != hipSuccess)
-        return tthost::fail_library(TT_EHIP, "tt_pop_nstep: hipMemcpy");
+        return fail(TT_EHIP, "tt_pop_nstep: hipMemcpy");
     PopNstep e{1, discount};                // (no table: the one-step draw)
     if (h->table && hipMemcpy(&e, h->table + agent, sizeof e, hipMemcpyDeviceToHost) != hipSuccess)
-        return tthost::fail_library(TT_EHIP, "tt_pop_nstep: hipMemcpy");
+        return fail(TT_EHIP, "tt_pop_nstep: hipMemcpy");
     out->n_step = e.n_step;
     out->gamma = e.gamma;
     out->discount = discount;
@@ -468,12 +461,12 @@ int tt_pop_nstep(tt_population *h, int agent, struct tt_pop_nstep *out) {
 }
 
 int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
-    if (!h) return einval("tt_pop_hyper: handle is NULL");
-    if (!out) return einval("tt_pop_hyper: out is NULL");
-    if (agent < 0 || agent >= h->K) return einval("tt_pop_hyper: agent %d is not in [0, K = %d)", agent, h->K);
+    if (!h) return fail(TT_EINVAL, "tt_pop_hyper: handle is NULL");
+    if (!out) return fail(TT_EINVAL, "tt_pop_hyper: out is NULL");
+    if (agent < 0 || agent >= h->K) return fail(TT_EINVAL, "tt_pop_hyper: agent %d is not in [0, K = %d)", agent, h->K);
     PopAgent P;
     if (hipMemcpy(&P, h->dev + agent, sizeof P, hipMemcpyDeviceToHost) != hipSuccess)
-        return tthost::fail_library(TT_EHIP, "tt_pop_hyper: hipMemcpy");
+        return fail(TT_EHIP, "tt_pop_hyper: hipMemcpy");
     out[0] = P.Aa.lr;
     out[1] = P.Ac.lr;
     out[2] = P.Aa.tau;
@@ -481,7 +474,7 @@ int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
     if (h->table) {                         // (td.gamma is the discount gamma ** n_step there)
         PopNstep e;
         if (hipMemcpy(&e, h->table + agent, sizeof e, hipMemcpyDeviceToHost) != hipSuccess)
-            return tthost::fail_library(TT_EHIP, "tt_pop_hyper: hipMemcpy");
+            return fail(TT_EHIP, "tt_pop_hyper: hipMemcpy");
         out[3] = e.gamma;
     }
     return TT_OK;

@@ -15,16 +15,6 @@
 
 namespace {
 
-__device__ __forceinline__ const float *nstep_s(const ttnet::RingSample &R, const ttnet::NstepPick &p) {
-    return R.obs + ((size_t)p.t0 * R.n_envs + p.e) * ttnet::IN;
-}
-__device__ __forceinline__ const float *nstep_s2(const ttnet::RingSample &R, const ttnet::NstepPick &p) {
-    return R.obs + ((size_t)p.t2 * R.n_envs + p.e) * ttnet::IN;
-}
-__device__ __forceinline__ float nstep_a(const ttnet::RingSample &R, const ttnet::NstepPick &p) {
-    return R.act[(size_t)p.t0 * R.n_envs + p.e];
-}
-
 // grid: K x 4 x nb, agent-major; within an agent, job-major as k_fwd_multi.  The jobs on s read their rows at t0, the jobs on s' at
 // t0 + m; the workgroups of job write_s leave s, a (and the index), those of job write_s2 leave s', R, D in the batch buffers.
 __global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi_nstep(const int K, const int n, const PopAgent *__restrict__ D,
@@ -47,13 +37,13 @@ __global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi_nstep(const int K, co
     const bool from_s = q.obs == R.s_out;                    // this job reads s (else s')
     const float *orow;
     // (a branch, not a select: only the rows at t0 + m need the walk's done flags)
-    if (from_s) orow = nstep_s(R, ttnet::nstep_pick(R, min(row0 + l15, n - 1), n_step, gamma));
-    else orow = nstep_s2(R, ttnet::nstep_pick(R, min(row0 + l15, n - 1), n_step, gamma));
+    if (from_s) orow = ttnet::nstep_s(R, ttnet::nstep_pick(R, min(row0 + l15, n - 1), n_step, gamma));
+    else orow = ttnet::nstep_s2(R, ttnet::nstep_pick(R, min(row0 + l15, n - 1), n_step, gamma));
     bool have_act = false;
     float act_r0 = 0.f, act_r1 = 0.f;
     if (q.critic && q.action) {
-        act_r0 = nstep_a(R, ttnet::nstep_pick(R, min(row0 + wave * 2, n - 1), n_step, gamma));
-        act_r1 = nstep_a(R, ttnet::nstep_pick(R, min(row0 + wave * 2 + 1, n - 1), n_step, gamma));
+        act_r0 = ttnet::nstep_a(R, ttnet::nstep_pick(R, min(row0 + wave * 2, n - 1), n_step, gamma));
+        act_r1 = ttnet::nstep_a(R, ttnet::nstep_pick(R, min(row0 + wave * 2 + 1, n - 1), n_step, gamma));
         have_act = true;
     }
     if (job == P.F.write_s || job == P.F.write_s2) {        // the batch rows of this workgroup for the later launches
@@ -61,14 +51,14 @@ __global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi_nstep(const int K, co
         if (lr < TR && b < n) {
             const ttnet::NstepPick p = ttnet::nstep_pick(R, b, n_step, gamma);
             if (job == P.F.write_s) {
-                R.s_out[(size_t)b * ttnet::IN + c] = nstep_s(R, p)[c];
+                R.s_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s(R, p)[c];
                 if (c == 0) {
-                    R.a_out[b] = nstep_a(R, p);
+                    R.a_out[b] = ttnet::nstep_a(R, p);
                     if (R.idx_out) { R.idx_out[2 * b] = p.t0; R.idx_out[2 * b + 1] = p.e; }
                 }
             }
             if (job == P.F.write_s2) {
-                R.s2_out[(size_t)b * ttnet::IN + c] = nstep_s2(R, p)[c];
+                R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s2(R, p)[c];
                 if (c == 0) { R.r_out[b] = p.R; R.d_out[b] = (uint8_t)p.D; }
             }
         }

@@ -176,7 +176,7 @@ def _child_p2p():
     ref = [dict(p=torch.zeros(n, **f), m=torch.zeros(n, **f), v=torch.zeros(n, **f), g=torch.zeros(n, **f)) for n in sizes]
     step_dev = torch.zeros((), dtype=torch.int64, device=dev)
     ptr = lambda t: (C.c_void_p * 1)(t.data_ptr())
-    stream = lambda: C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+    stream = lambda: L.stream(dev)
 
     def fill(site, step):            # this rank's "gradient": different on every rank, different every step
         i = torch.arange(sizes[site], **f)

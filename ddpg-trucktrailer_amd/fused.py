@@ -13,10 +13,6 @@ import torch
 from ddpg_trucktrailer_amd import _lib as L
 
 
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
 def supported(net):
     if not all(hasattr(net, a) for a in ("fc1", "fc2", "bn1", "bn2")) or not (hasattr(net, "mu") or hasattr(net, "q")):
         return False          # a module of another structure: the callers use it through torch
@@ -31,7 +27,7 @@ def pack_and_sample(net, index, sample_args, cursor=None):
     dev = net.fc2.weight.device
     L.check(L.load().tt_mlp_split_pack_and_sample(C.byref(w), 1 if hasattr(net, "action_value") else 0, C.c_void_p(w.split_ws),
                                                   C.byref(sample_args), C.byref(cursor) if cursor is not None else None,
-                                                  C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                                  L.stream(dev)))
 
 
 def actor_act_ring(net, ring_view, weights, ou_state, act_scaled, seed, step=0, step_dev=None, theta=0.2, sigma=0.15, dt=1e-2,
@@ -39,10 +35,10 @@ def actor_act_ring(net, ring_view, weights, ou_state, act_scaled, seed, step=0, 
     """actor_act on the ring slot the device cursor names (tt_actor_act_ring): observations from slot t, stored action
     into slot t, noise restarted where slot t-1 says done."""
     dev = net.fc2.weight.device
-    L.check(L.load().tt_actor_act_ring(int(ring_view.n_envs), C.byref(ring_view), C.byref(weights), _ptr(ou_state),
-                                       int(seed) & (2 ** 64 - 1), int(step), _ptr(step_dev), float(theta * dt),
-                                       float(sigma * math.sqrt(dt)), float(high), _ptr(act_scaled),
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    L.check(L.load().tt_actor_act_ring(int(ring_view.n_envs), C.byref(ring_view), C.byref(weights), L.ptr(ou_state),
+                                       int(seed) & (2 ** 64 - 1), int(step), L.ptr(step_dev), float(theta * dt),
+                                       float(sigma * math.sqrt(dt)), float(high), L.ptr(act_scaled),
+                                       L.stream(dev)))
     return act_scaled
 
 
@@ -118,8 +114,8 @@ def pack(net, index, bump=None, cursor=None):
     w = packed_weights_of(net, index)
     dev = net.fc2.weight.device
     L.check(L.load().tt_mlp_split_pack(C.byref(w), 1 if hasattr(net, "action_value") else 0, C.c_void_p(w.split_ws),
-                                       _ptr(bump), C.byref(cursor) if cursor is not None else None,
-                                       C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                       L.ptr(bump), C.byref(cursor) if cursor is not None else None,
+                                       L.stream(dev)))
 
 
 @contextlib.contextmanager
@@ -135,14 +131,14 @@ def exact_f32(net):
 
 
 def _stream(t):
-    return C.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+    return L.stream(t.device)
 
 
 def actor_forward(net, obs, out=None):
     """ActorNetwork.forward without autograd: obs [n,23] f32 -> mu [n,1]."""
     n = obs.shape[0]
     out = torch.empty(n, dtype=torch.float32, device=obs.device) if out is None else out
-    L.check(L.load().tt_actor_forward(n, _ptr(obs), C.byref(weights_of(net)), _ptr(out), _stream(obs)))
+    L.check(L.load().tt_actor_forward(n, L.ptr(obs), C.byref(weights_of(net)), L.ptr(out), _stream(obs)))
     return out.view(n, 1)
 
 
@@ -150,7 +146,7 @@ def critic_forward(net, obs, action, out=None):
     """CriticNetwork.forward without autograd: obs [n,23], action [n,1] -> q [n,1]."""
     n = obs.shape[0]
     out = torch.empty(n, dtype=torch.float32, device=obs.device) if out is None else out
-    L.check(L.load().tt_critic_forward(n, _ptr(obs), _ptr(action), C.byref(weights_of(net)), _ptr(out), _stream(obs)))
+    L.check(L.load().tt_critic_forward(n, L.ptr(obs), L.ptr(action), C.byref(weights_of(net)), L.ptr(out), _stream(obs)))
     return out.view(n, 1)
 
 
@@ -159,10 +155,10 @@ def actor_act(net, obs, ou_state, act_raw, act_scaled, seed, step=0, step_dev=No
     """choose_action + OU noise + clip*high for all rows in one launch (see include/ttenv.h: tt_actor_act).
     weights: a packed_weights_of() struct (the caller keeps its image current); default: re-pack on every call."""
     n = obs.shape[0]
-    L.check(L.load().tt_actor_act(n, _ptr(obs), C.byref(weights if weights is not None else weights_of(net)), _ptr(ou_state), _ptr(done_prev),
-                                  int(seed) & (2 ** 64 - 1), int(step), _ptr(step_dev), float(theta * dt),
-                                  float(sigma * math.sqrt(dt)), float(high), _ptr(mu_out), _ptr(act_raw),
-                                  _ptr(act_scaled), _stream(obs)))
+    L.check(L.load().tt_actor_act(n, L.ptr(obs), C.byref(weights if weights is not None else weights_of(net)), L.ptr(ou_state), L.ptr(done_prev),
+                                  int(seed) & (2 ** 64 - 1), int(step), L.ptr(step_dev), float(theta * dt),
+                                  float(sigma * math.sqrt(dt)), float(high), L.ptr(mu_out), L.ptr(act_raw),
+                                  L.ptr(act_scaled), _stream(obs)))
     return act_scaled
 
 

@@ -14,6 +14,8 @@ from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd import fused
 from ddpg_trucktrailer_amd.replay_buffer import check_n_step
 
+_p = L.ptr        # (the name this module's callers import)
+
 _ORDER = ("fc1.weight", "fc1.bias", "bn1.weight", "bn1.bias", "fc2.weight", "fc2.bias", "bn2.weight", "bn2.bias")
 _FIELDS = ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2", "w3", "b3", "wa", "ba")
 
@@ -25,14 +27,6 @@ def _named(net):
     if hasattr(net, "action_value"):
         names += ["action_value.weight", "action_value.bias"]
     return [d[n] for n in names]
-
-
-def _p(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
-
-
-def _ptr(t):
-    return None if t is None else t.data_ptr()
 
 
 def _no_sync():
@@ -150,7 +144,7 @@ class LearnLog:
             self._h = None
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.learners[0].dev).cuda_stream)
+        return L.stream(self.learners[0].dev)
 
     def append(self):
         """The one launch, on the current stream (capturable): a record of what the update before it on this stream left."""
@@ -279,7 +273,7 @@ class FusedLearner:
 
     # -------------------------------------------------------------------------------------------------
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
+        return L.stream(self.dev)
 
     def _fresh(self):
         if self.use_images and not torch.cuda.is_current_stream_capturing():
@@ -287,21 +281,21 @@ class FusedLearner:
 
     def _fwd(self, net, obs, action, out, saved=None, dq_da=None):
         self._fresh()
-        L.check(self.lib.tt_mlp_forward_save(self.B, 1 if action is not None else 0, _p(obs), _p(action),
-                                             C.byref(self.w(net)), _p(out), C.byref(saved) if saved else None,
-                                             _p(dq_da), self._stream()))
+        L.check(self.lib.tt_mlp_forward_save(self.B, 1 if action is not None else 0, L.ptr(obs), L.ptr(action),
+                                             C.byref(self.w(net)), L.ptr(out), C.byref(saved) if saved else None,
+                                             L.ptr(dq_da), self._stream()))
 
     def _adam(self, st, hyp, tau):
         lr, b1, b2, eps, wd = hyp
         if self.p2p is not None:       # the mean of the ranks' gradients is formed INSIDE this launch (include/ttenv.h: tt_p2p_*)
             L.check_p2p(self.lib.tt_adam_soft_update_p2p(self.p2p, 0 if st.critic else 1, st.count, st.a_p, st.a_m, st.a_v, st.a_t, st.a_n,
-                                                         _p(self.step_dev), lr, b1, b2, eps, wd, tau,
+                                                         L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau,
                                                          C.byref(st.images) if st.images is not None else None,
-                                                         _p(self.bias_corr), self._stream()), self.p2p)
+                                                         L.ptr(self.bias_corr), self._stream()), self.p2p)
             return
-        L.check(self.lib.tt_adam_soft_update(st.count, st.a_p, st.a_g, st.a_m, st.a_v, st.a_t, st.a_n, _p(self.step_dev),
+        L.check(self.lib.tt_adam_soft_update(st.count, st.a_p, st.a_g, st.a_m, st.a_v, st.a_t, st.a_n, L.ptr(self.step_dev),
                                              lr, b1, b2, eps, wd, tau, C.byref(st.images) if st.images is not None else None,
-                                             _p(self.bias_corr), self._stream()))
+                                             L.ptr(self.bias_corr), self._stream()))
 
     def enable_data_parallel(self, group=None):
         """Mean of the flat gradient buffers over the ranks at the reference's two optimizer sites (RCCL: one AVG
@@ -430,7 +424,7 @@ class FusedLearner:
         jobs = self.fwd_jobs(states, actions, states_)
         if sample is not None:
             assert (sample.s_out, sample.a_out, sample.s2_out) == (states.data_ptr(), actions.data_ptr(), states_.data_ptr())
-            snap = _p(image[2]) if image is not None else None
+            snap = L.ptr(image[2]) if image is not None else None
             if n_step > 1:
                 L.check(self.lib.tt_mlp_forward_multi_sampled_nstep(B, 4, jobs, C.byref(sample), n_step, float(ag.gamma), snap,
                                                                     self._stream()))
@@ -451,10 +445,10 @@ class FusedLearner:
                 (ag.target_critic, 1, states_, None, None, None, self.z_t),
                 (ag.critic, 1, states, actions, self.q, self.critic.saved, None),
                 (ag.actor, 0, states, None, self.mu, self.actor.saved, None))):
-            jobs[j].critic, jobs[j].obs, jobs[j].action = crit, _ptr(obs), _ptr(act)
-            jobs[j].w, jobs[j].out = C.pointer(self.w(net)), _ptr(out)
+            jobs[j].critic, jobs[j].obs, jobs[j].action = crit, L.ptr(obs), L.ptr(act)
+            jobs[j].w, jobs[j].out = C.pointer(self.w(net)), L.ptr(out)
             jobs[j].saved = C.pointer(saved) if saved is not None else None
-            jobs[j].dq_da, jobs[j].z_state = None, _ptr(zst)
+            jobs[j].dq_da, jobs[j].z_state = None, L.ptr(zst)
         return jobs
 
     def td_input(self, rewards, done_u8, window_dev=None, n_step=1):
@@ -465,7 +459,7 @@ class FusedLearner:
         return L.TTTdInput(z_state=self.z_t.data_ptr(), mu_target=self.mu_t.data_ptr(),
                            target_critic=C.pointer(self.w(ag.target_critic)), reward=rewards.data_ptr(),
                            done=done_u8.data_ptr(), gamma=gamma, y_out=self.y.data_ptr(),
-                           q_out=self.q_t.data_ptr(), step_dev=self.step_dev.data_ptr(), window_dev=_ptr(window_dev),
+                           q_out=self.q_t.data_ptr(), step_dev=self.step_dev.data_ptr(), window_dev=L.ptr(window_dev),
                            bias_corr_out=self.bias_corr.data_ptr(), adam_beta1=self.hyp_critic[1], adam_beta2=self.hyp_critic[2])
 
     def _rows(self, rewards, done_u8, window_dev=None, image=None, n_step=1):
@@ -476,8 +470,8 @@ class FusedLearner:
         td = self.td_input(rewards, done_u8, window_dev, n_step)
         # ... and, on other workgroups of the same launch, the ACTOR's per-row backward for a unit gradient: it is linear in
         # the row's d(loss)/d(pre-tanh), which needs the updated critic and is applied in phase_b (include/ttenv.h)
-        L.check(self.lib.tt_mlp_backward_rows_pair(B, 2.0 / B, _p(self.q), C.byref(self.w(ag.critic)),
-                                                   C.byref(self.critic.saved), C.byref(self.ws), C.byref(td), _p(self.mu),
+        L.check(self.lib.tt_mlp_backward_rows_pair(B, 2.0 / B, L.ptr(self.q), C.byref(self.w(ag.critic)),
+                                                   C.byref(self.critic.saved), C.byref(self.ws), C.byref(td), L.ptr(self.mu),
                                                    C.byref(self.w(ag.actor)), C.byref(self.actor.saved),
                                                    C.byref(self.ws_actor),
                                                    C.byref(L.TTImageJob(C.pointer(image[0]), C.pointer(image[1]))) if image is not None else None,
@@ -487,11 +481,11 @@ class FusedLearner:
         """The weight-gradient launch (tt_mlp_backward_weights), with Adam + soft update in it when `adam`."""
         lr, b1, b2, eps, wd = hyp
         dq, mu, sc = row if row is not None else (None, None, 1.0)
-        L.check(self.lib.tt_mlp_backward_weights(self.B, 1 if st.critic else 0, _p(obs), _p(action), C.byref(st.saved), C.byref(ws),
-                                                 C.byref(st.gstruct), _p(dq), _p(mu), float(sc), st.count if adam else 0,
-                                                 st.a_p, st.a_m, st.a_v, st.a_t, _p(self.step_dev), lr, b1, b2, eps, wd, tau,
+        L.check(self.lib.tt_mlp_backward_weights(self.B, 1 if st.critic else 0, L.ptr(obs), L.ptr(action), C.byref(st.saved), C.byref(ws),
+                                                 C.byref(st.gstruct), L.ptr(dq), L.ptr(mu), float(sc), st.count if adam else 0,
+                                                 st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau,
                                                  C.byref(st.images) if (adam and st.images is not None) else None,
-                                                 _p(self.bias_corr), self._stream()))
+                                                 L.ptr(self.bias_corr), self._stream()))
 
     def phase_b(self, states, separate_adam):
         """[critic Adam/soft update when not already applied,] then the actor step through the UPDATED critic
@@ -504,11 +498,11 @@ class FusedLearner:
             self._fresh()
             st = self.actor
             lr, b1, b2, eps, wd = self.hyp_actor
-            L.check(self.lib.tt_mlp_actor_tail(B, _p(states), _p(self.mu), C.byref(self.w(ag.critic)), _p(self.q_pi), _p(self.dq_da),
+            L.check(self.lib.tt_mlp_actor_tail(B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi), L.ptr(self.dq_da),
                                                C.byref(st.saved), C.byref(self.ws_actor), C.byref(st.gstruct), -1.0 / B, st.count,
-                                               st.a_p, st.a_m, st.a_v, st.a_t, _p(self.step_dev), lr, b1, b2, eps, wd, ag.tau,
-                                               C.byref(st.images) if st.images is not None else None, _p(self.bias_corr),
-                                               _p(self.tail_words), C.c_void_p(self.tail_gave_up_host.data_ptr()), self._stream()))
+                                               st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1, b2, eps, wd, ag.tau,
+                                               C.byref(st.images) if st.images is not None else None, L.ptr(self.bias_corr),
+                                               L.ptr(self.tail_words), C.c_void_p(self.tail_gave_up_host.data_ptr()), self._stream()))
             return
         self._fwd(ag.critic, states, self.mu, self.q_pi, dq_da=self.dq_da)
         self._weights(self.actor, self.hyp_actor, ag.tau, states, None, self.ws_actor, adam=not separate_adam,

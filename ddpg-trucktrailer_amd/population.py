@@ -121,7 +121,7 @@ class PopulationLearner:
             raise RuntimeError("PopulationLearner: a network's parameter storage moved since the descriptors were made")
         if not capturing:
             self.refresh_images()
-        L.check(self.lib.tt_pop_learn(self._h, int(u), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
+        L.check(self.lib.tt_pop_learn(self._h, int(u), L.stream()))
         if self.learn_log is not None:
             self.learn_log.append()
 
@@ -176,7 +176,7 @@ class PopulationLearner:
             arr[i] = L.TTPopExploitPair(dst, src, h["alpha"], h["beta"], h["tau"], h["gamma"])
             ns[i] = self._nstep_struct(h["gamma"], n)
             new.append((dst, h, n))
-        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        stream = L.stream()
         if self.nstep_table:
             L.check(self.lib.tt_pop_exploit_nstep(self._h, len(pairs), arr, ns, stream))
         else:

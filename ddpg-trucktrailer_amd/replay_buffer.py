@@ -292,17 +292,17 @@ class TrajectoryRing:
             args = self.sample_args(batch_size, seed=seed, k_dev=k_dev, reserve=reserve, lag=lag)
             s, a, r, s2, dn, idx = self._bufs
             L.check(L.load().tt_ring_sample_nstep(C.byref(args), int(n_step), float(gamma),
-                                                  C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                                  L.stream(self.device)))
             out = (s, a, r, s2, dn.bool() if done_as_bool else dn)
             return out + (idx,) if return_index else out
         s, a, r, s2, dn, idx = self._batch_bufs(batch_size)
-        p = lambda t: C.c_void_p(t.data_ptr())
+        p = L.ptr
         side = self._side_struct()
         L.check(L.load().tt_ring_sample(batch_size, self.n, self.slots, p(self.k_dev if k_dev is None else k_dev), p(self.obs),
                                         p(self.act), p(self.rew), p(self.done), int(seed) & (2 ** 64 - 1), int(reserve), int(lag),
                                         C.byref(side) if side is not None else None,
                                         p(s), p(a), p(r), p(s2), p(dn), p(idx),
-                                        C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                        L.stream(self.device)))
         out = (s, a, r, s2, dn.bool() if done_as_bool else dn)
         return out + (idx,) if return_index else out
 

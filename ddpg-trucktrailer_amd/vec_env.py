@@ -11,9 +11,7 @@ import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 
-
-def _ptr(t):
-    return None if t is None else C.c_void_p(t.data_ptr())
+_ptr = L.ptr      # (the name this module's callers import)
 
 
 class TruckTrailerVecEnv:
@@ -65,7 +63,7 @@ class TruckTrailerVecEnv:
             pass
 
     def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        return L.stream(self.device)
 
     def _check(self, rc):
         L.check(rc, self._h)
@@ -93,7 +91,7 @@ class TruckTrailerVecEnv:
         obs = self.obs if out is None else out
         m = self._as(mask, torch.uint8)
         self.graph_epoch += 1
-        self._check(self.lib.tt_env_reset(self._h, _ptr(m), int(seed) & (2 ** 64 - 1), _ptr(obs), self._stream()))
+        self._check(self.lib.tt_env_reset(self._h, L.ptr(m), int(seed) & (2 ** 64 - 1), L.ptr(obs), self._stream()))
         return obs
 
     def set_reset_pool(self, poses):
@@ -104,7 +102,7 @@ class TruckTrailerVecEnv:
             self._check(self.lib.tt_env_set_reset_pool(self._h, None, 0))
             return
         self._pool = self._as(poses, torch.float64).reshape(-1, 3)      # kept alive here: the library only borrows it
-        self._check(self.lib.tt_env_set_reset_pool(self._h, _ptr(self._pool), self._pool.shape[0]))
+        self._check(self.lib.tt_env_set_reset_pool(self._h, L.ptr(self._pool), self._pool.shape[0]))
 
     def set_pose(self, start, goal=None, L2=None, idx=None, out=None):
         """Pose override: start [k,3] (x, y, yaw), optional goal [k,3], L2 [k], idx [k] (default 0..k-1)."""
@@ -116,7 +114,7 @@ class TruckTrailerVecEnv:
         obs = self.obs if out is None else out
         if goal is not None or L2 is not None:
             self.graph_epoch += 1          # switches the handle to per-env goals / trailer lengths
-        self._check(self.lib.tt_env_set_pose(self._h, _ptr(idx), k, _ptr(start), _ptr(goal), _ptr(L2), _ptr(obs),
+        self._check(self.lib.tt_env_set_pose(self._h, L.ptr(idx), k, L.ptr(start), L.ptr(goal), L.ptr(L2), L.ptr(obs),
                                              self._stream()))
         return obs
 
@@ -133,38 +131,38 @@ class TruckTrailerVecEnv:
         idx = self._as(idx, torch.int32, (k,)) if idx is not None else None
         if goal is not None or L2 is not None:
             self.graph_epoch += 1
-        self._check(self.lib.tt_env_set_attrs(self._h, _ptr(idx), k, _ptr(start), _ptr(goal), _ptr(L2), self._stream()))
+        self._check(self.lib.tt_env_set_attrs(self._h, L.ptr(idx), k, L.ptr(start), L.ptr(goal), L.ptr(L2), self._stream()))
 
     def set_state(self, state, idx=None):
         state = self._as(state, torch.float64).reshape(-1, 6)
         k = state.shape[0]
         idx = self._as(idx, torch.int32, (k,)) if idx is not None else None
-        self._check(self.lib.tt_env_set_state(self._h, _ptr(idx), k, _ptr(state), self._stream()))
+        self._check(self.lib.tt_env_set_state(self._h, L.ptr(idx), k, L.ptr(state), self._stream()))
 
-    def set_max_steps(self, max_steps, idx=None):
-        m = self._as(max_steps, torch.int32).reshape(-1)
+    def _counters(self, values, idx, what):
+        """values [k] as int32 within the 12-bit packed counters (ValueError otherwise, naming `what`), idx [k] or None, k."""
+        m = self._as(values, torch.int32).reshape(-1)
         k = m.shape[0]
         if k and (int(m.min()) < 0 or int(m.max()) > L.MAX_EPISODE_STEPS):
-            raise ValueError(f"max_episode_steps must lie in [0, {L.MAX_EPISODE_STEPS}] (12-bit packed counters)")
-        idx = self._as(idx, torch.int32, (k,)) if idx is not None else None
-        self._check(self.lib.tt_env_set_max_steps(self._h, _ptr(idx), k, _ptr(m), self._stream()))
+            raise ValueError(f"{what} must lie in [0, {L.MAX_EPISODE_STEPS}] (12-bit packed counters)")
+        return m, self._as(idx, torch.int32, (k,)) if idx is not None else None, k
+
+    def set_max_steps(self, max_steps, idx=None):
+        m, idx, k = self._counters(max_steps, idx, "max_episode_steps")
+        self._check(self.lib.tt_env_set_max_steps(self._h, L.ptr(idx), k, L.ptr(m), self._stream()))
 
     def set_steps(self, steps, idx=None):
         """`env.episode_steps = ...` for envs idx (default 0..k-1): the step counter alone, the reward carry stays
         (include/ttenv.h: tt_env_set_steps)."""
-        m = self._as(steps, torch.int32).reshape(-1)
-        k = m.shape[0]
-        if k and (int(m.min()) < 0 or int(m.max()) > L.MAX_EPISODE_STEPS):
-            raise ValueError(f"episode_steps must lie in [0, {L.MAX_EPISODE_STEPS}] (12-bit packed counters)")
-        idx = self._as(idx, torch.int32, (k,)) if idx is not None else None
-        self._check(self.lib.tt_env_set_steps(self._h, _ptr(idx), k, _ptr(m), self._stream()))
+        m, idx, k = self._counters(steps, idx, "episode_steps")
+        self._check(self.lib.tt_env_set_steps(self._h, L.ptr(idx), k, L.ptr(m), self._stream()))
 
     # ------------------------------------------------------------------ read-back
     @property
     def state(self):
         """[N,6] f64 (psi1, psi2, x1, y1, x2, y2), a fresh copy."""
         buf = torch.empty((6, self.n_envs), dtype=torch.float64, device=self.device)
-        self._check(self.lib.tt_env_get_state(self._h, _ptr(buf), self._stream()))
+        self._check(self.lib.tt_env_get_state(self._h, L.ptr(buf), self._stream()))
         return buf.t().contiguous()
 
     def episode(self):
@@ -174,17 +172,28 @@ class TruckTrailerVecEnv:
         start = torch.empty((3, n), dtype=torch.float64, device=self.device)
         goal = torch.empty((3, n), dtype=torch.float64, device=self.device)
         L2 = torch.empty(n, dtype=torch.float64, device=self.device)
-        self._check(self.lib.tt_env_get_episode(self._h, _ptr(steps), _ptr(maxs), _ptr(start), _ptr(goal), _ptr(L2),
+        self._check(self.lib.tt_env_get_episode(self._h, L.ptr(steps), L.ptr(maxs), L.ptr(start), L.ptr(goal), L.ptr(L2),
                                                 self._stream()))
         return dict(steps=steps, max_episode_steps=maxs, start=start.t().contiguous(), goal=goal.t().contiguous(), L2=L2)
 
     def observe(self, steering=None, out=None):
         obs = self.obs if out is None else out
         s = self._as(steering, torch.float32, (self.n_envs,)) if steering is not None else None
-        self._check(self.lib.tt_env_observe(self._h, _ptr(s), _ptr(obs), self._stream()))
+        self._check(self.lib.tt_env_observe(self._h, L.ptr(s), L.ptr(obs), self._stream()))
         return obs
 
     # ------------------------------------------------------------------ step
+    def _step_outputs(self, obs_out, reward_out, done_out, info):
+        """What step() and step_random() write and return: the env's own buffers or the caller's, the info dict (None without
+        info) and the tt_info argument of the call."""
+        obs = self.obs if obs_out is None else obs_out
+        rew = self.reward if reward_out is None else reward_out
+        done = self.done if done_out is None else done_out
+        if not info:
+            return obs, rew, done, None, None
+        comp, viol, flags, ti = self._info()
+        return obs, rew, done, dict(comp=comp, violation=viol, flags=flags), C.byref(ti)
+
     def step(self, action, auto_reset=True, info=False, obs_out=None, reward_out=None, done_out=None):
         """action [N] f32 radians (already scaled by action_space.high, trainv2.py:516).
 
@@ -195,22 +204,15 @@ class TruckTrailerVecEnv:
                        and action.device == self.device) else self._as(action, torch.float32)
         if a.numel() != self.n_envs:
             raise ValueError(f"action has {a.numel()} elements, expected {self.n_envs}")
-        obs = self.obs if obs_out is None else obs_out
-        rew = self.reward if reward_out is None else reward_out
-        done = self.done if done_out is None else done_out
-        inf = None
-        ti = None
-        if info:
-            comp, viol, flags, ti = self._info()
-            inf = dict(comp=comp, violation=viol, flags=flags)
-        self._check(self.lib.tt_env_step(self._h, _ptr(a), _ptr(obs), _ptr(rew), _ptr(done),
-                                         C.byref(ti) if ti is not None else None, 1 if auto_reset else 0, self._stream()))
+        obs, rew, done, inf, ti = self._step_outputs(obs_out, reward_out, done_out, info)
+        self._check(self.lib.tt_env_step(self._h, L.ptr(a), L.ptr(obs), L.ptr(rew), L.ptr(done), ti, 1 if auto_reset else 0,
+                                         self._stream()))
         return obs, rew, done, inf
 
     def step_ring(self, action, ring_view, auto_reset=True):
         """step() with its outputs addressed through a trajectory ring's device cursor (tt_env_step_ring): obs into slot
         t+1, reward and done into slot t -- one captured launch serves every ring position."""
-        self._check(self.lib.tt_env_step_ring(self._h, _ptr(action), C.byref(ring_view), 1 if auto_reset else 0, self._stream()))
+        self._check(self.lib.tt_env_step_ring(self._h, L.ptr(action), C.byref(ring_view), 1 if auto_reset else 0, self._stream()))
 
     def set_step_counter(self, counter):
         """counter: device int64 scalar tensor that every step launch advances by 1 (None detaches); see
@@ -219,28 +221,21 @@ class TruckTrailerVecEnv:
             assert counter.dtype == torch.int64 and counter.device == self.device and counter.numel() == 1
         self._step_counter = counter
         self.graph_epoch += 1
-        self._check(self.lib.tt_env_set_step_counter(self._h, _ptr(counter) if counter is not None else None))
+        self._check(self.lib.tt_env_set_step_counter(self._h, L.ptr(counter) if counter is not None else None))
 
     def step_random(self, policy_seed=123, auto_reset=True, info=False, action_out=None, obs_out=None, reward_out=None,
                     done_out=None):
         """step() with the random policy of BASELINE.json config 2 drawn inside the kernel (graph-capturable)."""
-        obs = self.obs if obs_out is None else obs_out
-        rew = self.reward if reward_out is None else reward_out
-        done = self.done if done_out is None else done_out
-        inf, ti = None, None
-        if info:
-            comp, viol, flags, ti = self._info()
-            inf = dict(comp=comp, violation=viol, flags=flags)
-        self._check(self.lib.tt_env_step_random(self._h, int(policy_seed) & (2 ** 64 - 1), _ptr(action_out), _ptr(obs),
-                                                _ptr(rew), _ptr(done), C.byref(ti) if ti is not None else None,
-                                                1 if auto_reset else 0, self._stream()))
+        obs, rew, done, inf, ti = self._step_outputs(obs_out, reward_out, done_out, info)
+        self._check(self.lib.tt_env_step_random(self._h, int(policy_seed) & (2 ** 64 - 1), L.ptr(action_out), L.ptr(obs),
+                                                L.ptr(rew), L.ptr(done), ti, 1 if auto_reset else 0, self._stream()))
         return obs, rew, done, inf
 
     def rollout_random(self, k_steps, policy_seed=123, obs_out=None, reward_sum=None, episodes_done=None):
         """k_steps random-policy steps in one launch (state stays in registers); returns the last obs buffer."""
         obs = self.obs if obs_out is None else obs_out
-        self._check(self.lib.tt_env_rollout_random(self._h, int(k_steps), int(policy_seed) & (2 ** 64 - 1), _ptr(obs),
-                                                   _ptr(reward_sum), _ptr(episodes_done), self._stream()))
+        self._check(self.lib.tt_env_rollout_random(self._h, int(k_steps), int(policy_seed) & (2 ** 64 - 1), L.ptr(obs),
+                                                   L.ptr(reward_sum), L.ptr(episodes_done), self._stream()))
         return obs
 
     # ------------------------------------------------------------------ episode log
@@ -300,10 +295,10 @@ class TruckTrailerVecEnv:
             raise RuntimeError("the episode log is off (enable_episode_log)")
         o = self._log_out
         d = self._log_detail_out if self.episode_log_detail else None
-        self._check(self.lib.tt_env_drain_episode_log2(self._h, _ptr(o["ret"]), _ptr(o["len"]), _ptr(o["flags"]),
-                                                       _ptr(o["success"]), _ptr(o["lane"]), _ptr(o["end_step"]),
-                                                       _ptr(d["components"]) if d else None, _ptr(d["start"]) if d else None,
-                                                       _ptr(self._log_n), _ptr(self._log_counts), self._stream()))
+        self._check(self.lib.tt_env_drain_episode_log2(self._h, L.ptr(o["ret"]), L.ptr(o["len"]), L.ptr(o["flags"]),
+                                                       L.ptr(o["success"]), L.ptr(o["lane"]), L.ptr(o["end_step"]),
+                                                       L.ptr(d["components"]) if d else None, L.ptr(d["start"]) if d else None,
+                                                       L.ptr(self._log_n), L.ptr(self._log_counts), self._stream()))
         written = int(self._log_n.item())                 # (synchronises this stream)
         m = min(written, self.episode_log_capacity)
         key = o["end_step"][:m] * self.n_envs + o["lane"][:m].long()      # unique: one record per lane per launch
@@ -320,7 +315,7 @@ class TruckTrailerVecEnv:
         nbytes = int(self.lib.tt_env_episode_log_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 2)()
-        self._check(self.lib.tt_env_export_episode_log(self._h, _ptr(blob), C.byref(meta), self._stream()))
+        self._check(self.lib.tt_env_export_episode_log(self._h, L.ptr(blob), C.byref(meta), self._stream()))
         return {"blob": blob.cpu(), "meta": [int(x) for x in meta], "detail": self.episode_log_detail}
 
     def _load_episode_log_state(self, sd):
@@ -328,7 +323,7 @@ class TruckTrailerVecEnv:
         self.enable_episode_log(cap, detail=sd.get("detail", False))
         blob = sd["blob"].to(self.device)
         meta = (C.c_uint64 * 2)(*sd["meta"])
-        self._check(self.lib.tt_env_import_episode_log(self._h, _ptr(blob), C.byref(meta), self._stream()))
+        self._check(self.lib.tt_env_import_episode_log(self._h, L.ptr(blob), C.byref(meta), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()      # blob is a temporary
 
     def state_dict(self):
@@ -337,7 +332,7 @@ class TruckTrailerVecEnv:
         nbytes = int(self.lib.tt_env_state_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 4)()
-        self._check(self.lib.tt_env_export(self._h, _ptr(blob), C.byref(meta), self._stream()))
+        self._check(self.lib.tt_env_export(self._h, L.ptr(blob), C.byref(meta), self._stream()))
         sd = {"blob": blob.cpu(), "meta": [int(x) for x in meta], "variant": self.variant,
               "pool": None if getattr(self, "_pool", None) is None else self._pool.cpu()}
         if self.episode_log_capacity:
@@ -348,7 +343,7 @@ class TruckTrailerVecEnv:
         blob = sd["blob"].to(self.device)
         meta = (C.c_uint64 * 4)(*sd["meta"])
         self.graph_epoch += 1              # reset seed and per-env-goal mode come back with the blob
-        self._check(self.lib.tt_env_import(self._h, _ptr(blob), C.byref(meta), self._stream()))
+        self._check(self.lib.tt_env_import(self._h, L.ptr(blob), C.byref(meta), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()      # blob is a temporary
         if sd.get("pool") is not None:
             self.set_reset_pool(sd["pool"])
@@ -367,5 +362,5 @@ class TruckTrailerVecEnv:
 
     def random_actions(self, seed, step, out=None):
         out = torch.empty(self.n_envs, dtype=torch.float32, device=self.device) if out is None else out
-        L.check(self.lib.tt_random_actions(self.n_envs, int(seed), int(step), _ptr(out), self._stream()))
+        L.check(self.lib.tt_random_actions(self.n_envs, int(seed), int(step), L.ptr(out), self._stream()))
         return out
