@@ -116,6 +116,15 @@ class TTPopNstep(C.Structure):
     _fields_ = [("n_step", C.c_int32), ("gamma", C.c_float), ("discount", C.c_float)]
 
 
+class TTTd3Agent(C.Structure):
+    _fields_ = [("sample", C.POINTER(TTSampleArgs)), ("jobs", C.POINTER(TTFwdJob)), ("td", C.POINTER(TTTdInput)),
+                ("critic", TTPopNet), ("critic_2", TTPopNet), ("actor", TTPopNet), ("z_state_2", C.c_void_p),
+                ("target_critic_2", C.POINTER(TTMlpWeights)), ("target_noise", C.c_float), ("noise_clip", C.c_float),
+                ("noise_seed", C.c_uint64), ("eps_out", C.c_void_p), ("y2_out", C.c_void_p), ("q2t_out", C.c_void_p),
+                ("step_snapshot", C.c_void_p), ("actor_step_dev", C.c_void_p), ("actor_bias_corr_out", C.c_void_p),
+                ("q_pi", C.c_void_p), ("dq_da", C.c_void_p), ("tail_words", C.c_void_p), ("gave_up_host", C.c_void_p)]
+
+
 class TTLearnLogJob(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
                [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
@@ -128,6 +137,7 @@ LEARN_LOG_CHUNKS = 16                   # TT_LEARN_LOG_CHUNKS
 LEARN_LOG_MAX_CAPACITY = 1 << 22        # TT_LEARN_LOG_MAX_CAPACITY
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 NSTEP_MAX = 16          # TT_NSTEP_MAX
+TD3_NOISE_TAG = 0x7D3E  # the Philox domain of TD3's target-smoothing noise (csrc/tttd3.hip)
 
 
 class TTError(RuntimeError):
@@ -222,6 +232,10 @@ _SIGNATURES = {
     "tt_learn_log_drain": (C.c_int, [_P, _I, C.c_int64, C.c_int64, _P, _P, _P, C.POINTER(C.c_int64)]),
     "tt_learn_log_clear": (C.c_int, [_P, _P]),
     "tt_learn_log_destroy": (C.c_int, [_P]),
+    "tt_td3_create": (C.c_int, [_I, C.POINTER(TTTd3Agent), C.POINTER(_P)]),
+    "tt_td3_update": (C.c_int, [_P, C.POINTER(TTTd3Agent)]),
+    "tt_td3_learn": (C.c_int, [_P, _I, _I, _P]),
+    "tt_td3_destroy": (C.c_int, [_P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -44,7 +44,9 @@ class GradAllReduce:
 class Agent():
     def __init__(self, alpha, beta, input_dims, tau, n_actions, gamma=0.99,
                  max_size=1000000, fc1_dims=400, fc2_dims=300,
-                 batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True):
+                 batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True, td3=None):
+        """td3: None = DDPG, line for line; a td3.TD3Config = TD3 (Fujimoto et al., 2018): a second critic `critic_2` with its target
+        `target_critic_2`, target-policy smoothing, and the actor and all targets updated on every policy_delay-th update only."""
         self.gamma, self.tau, self.batch_size, self.alpha, self.beta = gamma, tau, batch_size, alpha, beta
         self.device = T.device(device) if device is not None else T.device('cuda:0' if T.cuda.is_available() else 'cpu')
         self.memory = ReplayBuffer(max_size, input_dims, n_actions, device=self.device) if replay else None
@@ -56,6 +58,15 @@ class Agent():
                                          name='target_actor', **kw)
         self.target_critic = CriticNetwork(beta, input_dims, fc1_dims, fc2_dims, n_actions=n_actions,
                                            name='target_critic', **kw)
+        self.td3 = td3
+        if td3 is not None:
+            self.critic_2 = CriticNetwork(beta, input_dims, fc1_dims, fc2_dims, n_actions=n_actions, name='critic_2', **kw)
+            self.target_critic_2 = CriticNetwork(beta, input_dims, fc1_dims, fc2_dims, n_actions=n_actions,
+                                                 name='target_critic_2', **kw)
+            self._critic_2_params = list(self.critic_2.parameters())
+            self.td3_updates = 0                 # critic updates done (a full update is every policy_delay-th)
+            self._td3_gen = T.Generator(device=self.device)
+            self.seed_td3_noise(0)
         self.update_network_parameters(tau=1)
         self._critic_params = list(self.critic.parameters())
         self._actor_params = list(self.actor.parameters())
@@ -80,7 +91,8 @@ class Agent():
 
     # ------------------------------------------------------------------ checkpoints (DDPG_agent.py:54-70)
     def _nets(self):
-        return (self.actor, self.target_actor, self.critic, self.target_critic)
+        nets = (self.actor, self.target_actor, self.critic, self.target_critic)
+        return nets + (self.critic_2, self.target_critic_2) if self.td3 is not None else nets
 
     def save_models(self):
         for net in self._nets():
@@ -110,9 +122,12 @@ class Agent():
         states, actions, rewards, states_, done = self.memory.sample_buffer(self.batch_size)
         self.learn_batch(states, actions, rewards, states_, done)
 
-    def learn_batch(self, states, actions, rewards, states_, done, discount=None):
+    def learn_batch(self, states, actions, rewards, states_, done, discount=None, eps=None, full=None):
         # discount: what multiplies q' in the target (default gamma); gamma ** n for a batch of n-step tuples (TrajectoryRing.sample)
+        # eps, full: TD3 only (see _learn_batch_td3)
         discount = self.gamma if discount is None else discount
+        if self.td3 is not None:
+            return self._learn_batch_td3(states, actions, rewards, states_, done, discount, eps, full)
         with T.no_grad():
             if self.fused_targets:      # one fused f32-MFMA launch per target net (csrc/ttnet.hip)
                 from ddpg_trucktrailer_amd import fused
@@ -149,12 +164,59 @@ class Agent():
         self.update_network_parameters()
         self.last_critic_loss, self.last_actor_loss = critic_loss.detach(), actor_loss.detach()
 
+    def seed_td3_noise(self, seed):
+        """Seed the generator of the torch path's target-smoothing noise (a loop seeds it with its own seed); its state is
+        td3_noise_state() / set_td3_noise_state() for a checkpoint."""
+        self._td3_gen.manual_seed((int(seed) ^ 0x7D3E) & (2 ** 63 - 1))
+
+    def td3_noise_state(self):
+        return self._td3_gen.get_state().clone()
+
+    def set_td3_noise_state(self, state):
+        self._td3_gen.set_state(state.cpu().to(T.uint8))
+
+    def _learn_batch_td3(self, states, actions, rewards, states_, done, discount, eps=None, full=None):
+        """One TD3 update in torch (the CPU path, and the twin the fused TD3 learner is tested against).
+        eps [B]: the target-smoothing noise to use, in the actor's normalised action units (None: clip(target_noise * N(0, 1),
+        +-noise_clip) from the agent's own generator).  full: None = every policy_delay-th update is a full one (actor step through
+        the updated critic 1, then the soft update of all three targets); else this update is full or critic-only as told."""
+        cfg = self.td3
+        with T.no_grad():
+            mu_t = self.target_actor.forward(states_)
+            if eps is None:
+                nrm = T.randn(mu_t.shape, generator=self._td3_gen, device=mu_t.device, dtype=mu_t.dtype)
+                eps = (cfg.target_noise * nrm).clamp(-cfg.noise_clip, cfg.noise_clip)
+            a2 = (mu_t + eps.to(mu_t).view_as(mu_t)).clamp(-1.0, 1.0)
+            q_next = T.min(self.target_critic.forward(states_, a2), self.target_critic_2.forward(states_, a2))
+            q_next = q_next.masked_fill(done.view(-1, 1), 0.0).view(-1)
+            target = (rewards + discount * q_next).view(-1, 1)
+        for net, params in ((self.critic, self._critic_params), (self.critic_2, self._critic_2_params)):
+            loss = F.mse_loss(target, net.forward(states, actions))
+            for p, g in zip(params, T.autograd.grad(loss, params)):
+                p.grad = g
+            net.optimizer.step()
+            if net is self.critic:
+                self.last_critic_loss = loss.detach()
+        self.td3_updates += 1
+        if full is None:
+            full = self.td3_updates % cfg.policy_delay == 0
+        if full:
+            actor_loss = T.mean(-self.critic.forward(states, self.actor.forward(states)))
+            for p, g in zip(self._actor_params, T.autograd.grad(actor_loss, self._actor_params)):
+                p.grad = g
+            self.actor.optimizer.step()
+            self.update_network_parameters()
+            self.last_actor_loss = actor_loss.detach()
+
     def update_network_parameters(self, tau=None):
         """theta' <- tau*theta + (1 - tau)*theta' over every named parameter (DDPG_agent.py:108-131)."""
         if tau is None:
             tau = self.tau
         with T.no_grad():
-            for net, target in ((self.critic, self.target_critic), (self.actor, self.target_actor)):
+            pairs = ((self.critic, self.target_critic), (self.actor, self.target_actor))
+            if getattr(self, "td3", None) is not None:
+                pairs += ((self.critic_2, self.target_critic_2),)
+            for net, target in pairs:
                 src = [p.data for p in net.parameters()]
                 dst = [p.data for p in target.parameters()]
                 if tau == 1:

@@ -37,6 +37,11 @@ def save_training_checkpoint(path, agent, env=None, ring=None, noise=None, train
           "hyper": dict(alpha=agent.alpha, beta=agent.beta, tau=agent.tau, gamma=agent.gamma, batch_size=agent.batch_size),
           "training_state": training_state or {},
           "rng": _rng_state()}
+    if getattr(agent, "td3", None) is not None:          # TD3: the second critic, its target and its optimizer state
+        for n in ("critic_2", "target_critic_2"):
+            ck["nets"][n] = getattr(agent, n).state_dict()
+        ck["optim"]["critic_2"] = agent.critic_2.optimizer.state_dict()
+        ck["td3"] = list(agent.td3.as_tuple())
     if env is not None:
         ck["env"] = env.state_dict()
     if noise is not None:
@@ -52,10 +57,16 @@ def load_training_checkpoint(path, agent, env=None, ring=None, noise=None):
     graphs, or through DDPGRollout.load_state_dict (which re-captures): a captured step launch bakes the env's reset
     seed and modes by value."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
+    has_td3 = getattr(agent, "td3", None) is not None
+    if ("td3" in ck) != has_td3:
+        raise ValueError("the checkpoint was written with td3, this agent has none" if "td3" in ck else
+                         "the checkpoint was written without td3, this agent has td3 (no second critic in it)")
     for n, sd in ck["nets"].items():
         getattr(agent, n).load_state_dict(sd)
     agent.actor.optimizer.load_state_dict(ck["optim"]["actor"])
     agent.critic.optimizer.load_state_dict(ck["optim"]["critic"])
+    if has_td3:
+        agent.critic_2.optimizer.load_state_dict(ck["optim"]["critic_2"])
     if getattr(agent, "fused_learner", None) is not None:
         agent.fused_learner.import_from_optimizers()
     if env is not None and "env" in ck:

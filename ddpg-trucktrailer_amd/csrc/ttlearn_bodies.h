@@ -731,11 +731,13 @@ __device__ inline void clock_tick(const TdIn &td) {
     }
 }
 
-template <bool CRITIC>
+// YGIVEN (critic only; csrc/tttd3.hip): the caller has formed the TD targets of this wave's two rows itself (y_given[0], [1]) --
+// the prologue's loads and dot product are compiled out and `td` is not read.
+template <bool CRITIC, bool YGIVEN = false>
 __device__ __forceinline__ void bwd_rows_body(const int n, const float scale, const float *__restrict__ out,
                                               const Weights &W, const Saved &sv, const BwdOut &o, const TdIn &td,
                                               float *__restrict__ dx2_s, float *__restrict__ red, float *__restrict__ rsc_s,
-                                              const int row0) {
+                                              const int row0, const float *y_given = nullptr) {
     // dx2_s [16][308]: A operand of phase B (with an fc2 image: its two f16 planes [2][16][328], each row scaled by a power
     // of two whose inverse / 64 goes to rsc_s [16]); red [2][NW][16]: cross-wave reductions
     const bool img = W.img != nullptr;                     // (uniform over the launch)
@@ -749,7 +751,7 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const float scale, co
     float4 w3c[RV], g2c[RV], h2v[RPW][RV], xh[RPW][RV], zt[RPW][RV], wat[RV], bat[RV], w3t[RV];
     float rs[RPW], outv[RPW], mut[RPW], rt[RPW], b3t = 0.f;
     bool dt[RPW];
-    const bool with_td = CRITIC;                             // the TD prologue's loads: the critic's rows only
+    const bool with_td = CRITIC && !YGIVEN;                  // the TD prologue's loads: the critic's rows only
     // Every load below is unconditional, from a clamped row / column (a value that must be zero is zeroed afterwards; most uses
     // are guarded anyway): guarded loads made the compiler emit this phase as a chain of exec-masked blocks, each with its own
     // wait -- five dependent round trips to L2 in front of the first arithmetic (5.0 us for this phase in round 3's stamps).
@@ -825,6 +827,7 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const float scale, co
                 if (td.q_out) td.q_out[row] = q;
             }
         }
+        if (YGIVEN) y_td = y_given[rr];
         // (actor: the unit backward -- every per-row gradient below is linear in dpre, see k_bwd_rows_pair)
         const float dpre = ok ? (CRITIC ? scale * (outv[rr] - y_td) : 1.f) : 0.f;
         float4 dxh[RV];

@@ -194,7 +194,7 @@ class FusedLearner:
         self.use_images = (os.environ.get("TT_LEARN_F32") != "1") if fc2_images is None else bool(fc2_images)
         # this learner's own weight structs of the four networks (the module-level ones of fused.weights_of serve inference)
         self._wstruct, self._img, self._img_seen = {}, {}, {}
-        for net in (agent.actor, agent.critic, agent.target_actor, agent.target_critic):
+        for net in self._nets():
             self._make_weights(net)
         for st in (self.actor, self.critic):
             st.images = L.TTFc2Images(net=self._img_ptr(st.net), target=self._img_ptr(st.target)) if self.use_images else None
@@ -224,6 +224,15 @@ class FusedLearner:
         self.hyp_actor = (ga["lr"], ga["betas"][0], ga["betas"][1], ga["eps"], ga["weight_decay"])
         self.hyp_critic = (gc["lr"], gc["betas"][0], gc["betas"][1], gc["eps"], gc["weight_decay"])
 
+    def _nets(self):
+        """The networks this learner keeps weight structs and fc2 images of (a subclass with more networks overrides this)."""
+        ag = self.agent
+        return (ag.actor, ag.critic, ag.target_actor, ag.target_critic)
+
+    def _states(self):
+        """The trained networks' _NetStates (a subclass with more networks overrides this)."""
+        return (self.actor, self.critic)
+
     # ------------------------------------------------------------------------------------------------- fc2 images
     def _make_weights(self, net):
         w = fused._fill_weights(net, L.TTMlpWeights())
@@ -243,7 +252,7 @@ class FusedLearner:
         key, w = self._wstruct[id(net)]
         if key != tuple(p.data_ptr() for p in net.parameters()):      # parameter storage replaced: rebuild
             self._make_weights(net)
-            for st in (self.actor, self.critic):
+            for st in self._states():
                 if self.use_images:
                     st.images = L.TTFc2Images(net=self._img_ptr(st.net), target=self._img_ptr(st.target))
             w = self._wstruct[id(net)][1]
@@ -254,9 +263,7 @@ class FusedLearner:
         made?  (torch counts in-place writes per tensor; the learner's kernels update weights AND images together.)"""
         if not self.use_images:
             return True
-        ag = self.agent
-        return all(self._img_seen[id(n)] == (n.fc2.weight._version, n.fc2.weight.data_ptr())
-                   for n in (ag.actor, ag.critic, ag.target_actor, ag.target_critic))
+        return all(self._img_seen[id(n)] == (n.fc2.weight._version, n.fc2.weight.data_ptr()) for n in self._nets())
 
     def refresh_images(self, force=False):
         """(Re)make the image of every network whose fc2 was written by anyone else -- load_state_dict, a torch optimizer,
@@ -264,8 +271,7 @@ class FusedLearner:
         captured graphs calls it before it replays (DDPGRollout.run)."""
         if not self.use_images:
             return
-        ag = self.agent
-        for n in (ag.actor, ag.critic, ag.target_actor, ag.target_critic):
+        for n in self._nets():
             seen = (n.fc2.weight._version, n.fc2.weight.data_ptr())
             if force or self._img_seen[id(n)] != seen:
                 L.check(self.lib.tt_mlp_fc2_image_pack(C.byref(self.w(n)), self._stream()))

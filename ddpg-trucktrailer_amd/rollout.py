@@ -72,7 +72,7 @@ class DDPGRollout(VectorStepper):
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
-                 learn_log_every=1):
+                 learn_log_every=1, td3=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -95,8 +95,22 @@ class DDPGRollout(VectorStepper):
         update whose step count is a multiple of learn_log_every then leaves a record of its losses, Q / TD statistics and gradient
         norms in device memory -- also inside replayed graphs, at no host work per step -- and drain_learn_log() collects the
         records.  With updates_per_step > 1 every update is a step of its own.  Needs the fused learner (reference-shaped networks
-        on a GPU); not with data-parallel ranks."""
+        on a GPU); not with data-parallel ranks.
+        td3: None = DDPG.  A td3.TD3Config = TD3: the agent gets a second critic, and with the reference-shaped
+        networks on a GPU learn() runs on the TD3 launches (td3.TD3Learner), update u of a vector step being a full one when
+        (u + 1) % policy_delay == 0 -- the same pattern in every step, so one captured step serves them all.  Serial order only
+        (pipeline=None resolves to False); td3.check_td3 names what is refused."""
         self.n_step = check_n_step(n_step)
+        self.td3 = None
+        if td3 is not None:
+            from ddpg_trucktrailer_amd.td3 import check_td3
+            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
+            self.td3 = check_td3(td3, updates_per_step, self.n_step, ranks or dp_exchange == "p2p", pipeline, learn_log)
+            pipeline = False
+            if agent is not None and getattr(agent, "td3", None) is None:
+                raise ValueError("td3: the agent passed in was built without td3 (Agent(td3=...))")
+        elif agent is not None and getattr(agent, "td3", None) is not None:
+            raise ValueError("td3: the agent passed in was built with td3, the loop without")
         if learn_log is not None:
             from ddpg_trucktrailer_amd.fused_learn import check_learn_log
             learn_log, learn_log_every = check_learn_log(learn_log, learn_log_every)
@@ -110,7 +124,8 @@ class DDPGRollout(VectorStepper):
             raise ValueError("n_step > 1 with data-parallel ranks is not supported (the ranks' segments draw through the one-step sampler)")
         super().__init__(env, batch_size=batch_size, replay_slots=replay_slots, seed=seed, alpha=alpha, beta=beta, tau=tau, gamma=gamma,
                          fc1_dims=fc1_dims, fc2_dims=fc2_dims, agent=agent, capturable=use_graph, policy_workgroups=policy_workgroups,
-                         policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail)
+                         policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail,
+                         td3=self.td3)
         self.batch_size = batch_size
         self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
         self.dp_exchange = dp_exchange or os.environ.get("TT_DP_EXCHANGE", "collective")
@@ -129,14 +144,19 @@ class DDPGRollout(VectorStepper):
         self.learner = None
         if fused_learn and self.fused_act and fused.supported(self.agent.critic):
             from ddpg_trucktrailer_amd.fused_learn import FusedLearner
-            self.learner = FusedLearner(self.agent, batch_size)
+            if self.td3 is not None and self.device.type == "cuda":
+                from ddpg_trucktrailer_amd.td3 import TD3Learner
+                self.learner = TD3Learner(self.agent, batch_size, self.ring, self.seed)
+            elif self.td3 is None:
+                self.learner = FusedLearner(self.agent, batch_size)
             self.agent.fused_learner = self.learner
             if self.dp and self.dp_exchange == "p2p":
                 self.learner.enable_p2p()
                 self.dp_single_graph = True              # nothing but kernel launches in a step: one graph, any backend
             elif self.dp:
                 self.learner.enable_data_parallel()
-        if self.learner is not None and not self.dp and self.device.type == "cuda":
+        if self.learner is not None and not self.dp and self.device.type == "cuda" and self.td3 is None:
+            # (TD3's full updates always end with the tail in one grid: neither this choice nor TT_ACTOR_TAIL applies there)
             # learn()'s last two launches as one grid where learn() bounds the step (include/ttenv.h: tt_mlp_actor_tail): a policy
             # launch of at most one round of 128 tiles, or several updates per step (at N = 65536 with one update per step the grid's 200
             # waiting workgroups meet a policy launch that owns 171 CUs: 0.084 -> 0.094 ms per step).  TT_ACTOR_TAIL=0/1 overrides.
@@ -153,7 +173,7 @@ class DDPGRollout(VectorStepper):
                                  "optimizer applies")
             self.learner.enable_learn_log(learn_log, learn_log_every)
         self.use_graph = use_graph and self.device.type == "cuda"
-        if os.environ.get("TT_FORCE_DP") == "1" and self.learner is not None and not self.dp:
+        if os.environ.get("TT_FORCE_DP") == "1" and self.learner is not None and not self.dp and self.td3 is None:
             # measurement aid: the data-parallel launch structure (three graph segments, separate Adam launches) on ONE
             # rank with no-op collectives -- what a rank's step costs before any time on the wire
             self.dp = True
@@ -221,6 +241,10 @@ class DDPGRollout(VectorStepper):
 
     def _learn_once(self, u=0, presampled=False, with_image=False, wait_for_steps=False):
         sample = None
+        if self.td3 is not None and self.learner is not None:
+            # the TD3 launches make the draw of update u themselves; the delay is counted inside the vector step
+            self.learner.learn_batch(u=u, full=(u + 1) % self.td3.policy_delay == 0)
+            return
         if presampled:         # the step's opening launch already drew this batch into the ring's buffers
             B, draws = self.batch_size, self._draws_per_opening()
             s, a, r, s2, d = (x[u * B:(u + 1) * B] for x in self.ring._batch_bufs(B * draws)[:5])
@@ -335,7 +359,8 @@ class DDPGRollout(VectorStepper):
         if self.learner is not None and self.learner.tail_gave_up():
             raise RuntimeError(f"learn step {self.learner.tail_gave_up()}: a weight-gradient workgroup of learn()'s last launch gave up waiting "
                                "(0.25 s) for dQ/da from the row workgroups of the same launch (include/ttenv.h: tt_mlp_actor_tail) and "
-                               "went on: that update is garbage.  TT_ACTOR_TAIL=0 runs the two launches apart")
+                               "went on: that update is garbage." +
+                               ("" if self.td3 is not None else "  TT_ACTOR_TAIL=0 runs the two launches apart"))
         if self.learner is not None and self.learner.p2p_gave_up():
             raise RuntimeError(f"learn step {self.learner.p2p_gave_up()}: this rank's optimizer launch gave up waiting for a peer's gradients "
                                "(peer-to-peer exchange, include/ttenv.h: tt_p2p_*) and used whatever the buffers held: the ranks have "
@@ -606,13 +631,19 @@ class DDPGRollout(VectorStepper):
               "handover_gave_up": [int(x) for x in self.handover_gave_up],
               "batch_size": int(self.batch_size), "updates_per_step": self.updates_per_step, "n_step": int(self.n_step),
               "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()}
-                       for n in ("actor", "critic", "target_actor", "target_critic")},
+                       for n in ("actor", "critic", "target_actor", "target_critic") + (("critic_2", "target_critic_2") if self.td3 else ())},
               "ring": self.ring.state_dict(), "ou": self.noise.x.detach().cpu().clone(),
               "env": self.env.state_dict() if hasattr(self.env, "state_dict") else None}
         if self.learner is not None:
             sd["fused_adam"] = self.learner.state_dict()
         else:
             sd["optim"] = {"actor": ag.actor.optimizer.state_dict(), "critic": ag.critic.optimizer.state_dict()}
+            if self.td3 is not None:
+                sd["optim"]["critic_2"] = ag.critic_2.optimizer.state_dict()
+                sd["td3_updates"] = int(ag.td3_updates)
+                sd["td3_noise"] = ag.td3_noise_state()               # (the torch path's generator; the fused path's noise is counter-based)
+        if self.td3 is not None:
+            sd["td3"] = list(self.td3.as_tuple())
         return sd
 
     def drain_learn_log(self):
@@ -626,6 +657,9 @@ class DDPGRollout(VectorStepper):
         assert int(sd["batch_size"]) == int(self.batch_size), "batch size differs"
         if int(sd.get("n_step", 1)) != self.n_step:
             raise ValueError(f"the checkpoint was written with n_step = {int(sd.get('n_step', 1))}, this loop has n_step = {self.n_step}")
+        if ("td3" in sd) != (self.td3 is not None):
+            raise ValueError("the checkpoint was written with td3, this loop has none" if "td3" in sd else
+                             "the checkpoint was written without td3, this loop has td3 (no second critic in it)")
         with torch.no_grad():
             for n, net_sd in sd["nets"].items():
                 for k, v in getattr(ag, n).state_dict().items():      # in place: captured graphs keep the addresses
@@ -635,6 +669,11 @@ class DDPGRollout(VectorStepper):
         elif "optim" in sd:
             ag.actor.optimizer.load_state_dict(sd["optim"]["actor"])
             ag.critic.optimizer.load_state_dict(sd["optim"]["critic"])
+            if self.td3 is not None:
+                ag.critic_2.optimizer.load_state_dict(sd["optim"]["critic_2"])
+                ag.td3_updates = int(sd.get("td3_updates", 0))
+                if "td3_noise" in sd:
+                    ag.set_td3_noise_state(sd["td3_noise"])
             self.graph = None                                         # optimizer state tensors were replaced
         self.ring.load_state_dict(sd["ring"])
         self.noise.x.copy_(sd["ou"].to(self.noise.x.device))
@@ -644,6 +683,8 @@ class DDPGRollout(VectorStepper):
         if int(sd["seed"]) != int(self.seed):
             self.invalidate_graphs()                                  # the Philox keys are kernel arguments
         self.seed = int(sd["seed"])
+        if self.td3 is not None and self.learner is not None:
+            self.learner.set_seed(self.seed)                          # (the descriptor holds the sampling and noise keys)
         self.handover_gave_up = [int(x) for x in sd.get("handover_gave_up", [])]
         self.vector_steps = int(sd["vector_steps"])
         self.updates_per_step = int(sd.get("updates_per_step", self.updates_per_step))

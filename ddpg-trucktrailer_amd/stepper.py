@@ -16,8 +16,9 @@ from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 class VectorStepper:
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
-                 episode_log_detail=False):
-        """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold).
+                 episode_log_detail=False, td3=None):
+        """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold);
+        td3: its TD3Config (Agent(td3=)), whose torch path draws its smoothing noise from a generator seeded with `seed`.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
         before any step or capture: the env step kernel logs every episode that ends in the loop, end_step = the loop's vector
         step, and drain_episodes() collects the records.  episode_log_detail: the detailed log (episode_metrics.py)."""
@@ -29,7 +30,9 @@ class VectorStepper:
         self.agent = agent if agent is not None else Agent(
             alpha=alpha, beta=beta, input_dims=(env.observation_dim,), tau=tau, n_actions=1, gamma=gamma,
             fc1_dims=fc1_dims, fc2_dims=fc2_dims, batch_size=batch_size, device=self.device,
-            capturable=capturable, replay=False)
+            capturable=capturable, replay=False, td3=td3)
+        if getattr(self.agent, "td3", None) is not None:
+            self.agent.seed_td3_noise(seed)
         self.ring = TrajectoryRing(self.n, replay_slots, env.observation_dim, self.device)
         if self.device.type == "cuda":
             self.ring.attach(env)                          # the step kernel advances the ring's device counter

@@ -754,6 +754,60 @@ int tt_adam_soft_update_p2p(tt_p2p *x, int site, int count, float *const *params
                             float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                             const tt_fc2_images *images, const float *bias_corr, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * TD3 (Fujimoto, van Hoof, Meger 2018) in the fused learner (csrc/tttd3.hip): twin critics, target-policy smoothing, delayed
+ * actor and target updates, for one agent with the reference-shaped networks and a batch B <= 1024 drawn from its ring.
+ * One update, with t = the critic updates done before it (*td->step_dev when the update starts):
+ *   mu' = target_actor(s');  eps_b = clip(target_noise * N_b, -noise_clip, noise_clip), N_b standard normal from Philox4x32-10 and
+ *   Box-Muller (the recipe of the OU noise) keyed by (row b, t, the domain tag 0x7D3E, noise_seed);  a'_b = clip(mu'_b + eps_b, -1, 1)
+ *   (the actor's normalised action units);  y_b = r_b + gamma min(q1'(s', a'), q2'(s', a')), y_b = r_b exactly where done_b;
+ *   both critics take an MSE step (scale 2/B) towards y with their own Adam moments and the shared step count t + 1;
+ *   full != 0: then the actor's step on -mean Q1(s, mu(s)) through the updated critic 1, counted by the actor's OWN step counter
+ *   (actor_step_dev, as torch.optim.Adam counts when step() is called every d-th time), and the soft update of all three targets;
+ *   full == 0: nothing but the two critics, their moments and *td->step_dev changes -- the actor, its moments and step count, the
+ *   three targets and their fc2 images keep their bits.
+ * The agent is described by what the launches take (as tt_pop_agent; the library copies it into device memory at creation, every
+ * pointer must stay valid and fixed for the handle's life), so tt_td3_learn makes no host work per call and can be captured:
+ *   sample      the replay draw (batch == B, no side buffer, draws <= 1, no step_progress); update u draws with seed + u * seed_stride
+ *   jobs        [6] target actor on s', the state branches (z_state) of target critic 1 and of target critic 2 on s', critic 1 and
+ *               critic 2 on (s, a) with saved activations, the actor on s with saved activations (not run when full == 0)
+ *   td          critic 1's side of the prologue: z_state, mu_target, target_critic (1), reward, done, gamma, y_out (y of critic 1's
+ *               workgroups), q_out (q1', required), step_dev and bias_corr_out (both required; shared by the critics), window_dev NULL
+ *   z_state_2, target_critic_2, y2_out, q2t_out   the second target head, y as critic 2's workgroups formed it (the same bits), q2'
+ *   eps_out     [B] the smoothing noise of the update, always written
+ *   step_snapshot   one int64 of device memory: t as the first launch saw it (the second launch advances *step_dev)
+ *   actor_step_dev, actor_bias_corr_out   the actor's step count (int64) and its 8 floats of bias corrections, advanced by full updates
+ *   critic, critic_2, actor   as tt_pop_agent's networks; the critics' tau applies on full updates only
+ *   q_pi, dq_da, tail_words, gave_up_host   as tt_mlp_actor_tail's (the hand-over's epoch is *actor_step_dev)
+ * (full == 0 rewrites every target element t as fmaf(0, p - t, t): t itself for every finite p - t, with -0.0 becoming +0.0.)
+ * TT_EINVAL with a message in tt_last_error(NULL), before any HIP call: batch outside 1 .. 1024; target_noise or noise_clip
+ * negative or not finite; a missing pointer; a side buffer, draws > 1 or step_progress in the sample; window_dev set; two networks
+ * that share a per-row workspace, or the two critics a gradient buffer; td / z_state_2 / target_critic_2 that are not the outputs
+ * and networks of jobs 0 .. 2, or td->reward / td->done that are not the draw's r_out / d_out.
+ * tt_td3_update checks a new description of the same agent as tt_td3_create does and copies it over the handle's descriptor IN
+ * PLACE (it waits for the device first): a parameter storage moved, or another seed.  Launches captured before stay valid and
+ * read the new description. */
+typedef struct tt_td3 tt_td3;
+typedef struct tt_td3_agent {
+    const tt_sample_args *sample;
+    const tt_fwd_job *jobs;              /* [6] */
+    const tt_td_input *td;
+    tt_pop_net critic, critic_2, actor;
+    const float *z_state_2;
+    const tt_mlp_weights *target_critic_2;
+    float target_noise, noise_clip;
+    uint64_t noise_seed;
+    float *eps_out, *y2_out, *q2t_out;
+    int64_t *step_snapshot, *actor_step_dev;
+    float *actor_bias_corr_out;
+    float *q_pi, *dq_da;
+    int32_t *tail_words, *gave_up_host;
+} tt_td3_agent;
+int tt_td3_create(int batch, const tt_td3_agent *agent, tt_td3 **out);
+int tt_td3_update(tt_td3 *h, const tt_td3_agent *agent);
+int tt_td3_learn(tt_td3 *h, int update, int full, tt_stream_t stream);       /* one update, enqueued on stream */
+int tt_td3_destroy(tt_td3 *h);                                               /* the caller's stream work with it must be done */
+
 #ifdef __cplusplus
 }
 #endif

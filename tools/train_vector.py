@@ -8,7 +8,10 @@ success rate and "best" decisions (checkpoint.BestModelTracker).  The loop runs 
 --n-step N: n-step returns in the replay draw (DDPGRollout(n_step=N); default 1, the one-step target).
 --learn-log EVERY: the fused learner's learn log (DDPGRollout(learn_log=...)), one record per EVERY updates, and each line adds
 the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient norms, and the block's non-finite total.
-Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+--td3 [DELAY[,SIGMA[,CLIP]]]: TD3 instead of DDPG (DDPGRollout(td3=TD3Config(...)); defaults 2, 0.2, 0.5): twin critics, target-policy
+smoothing, the actor and the targets updated every DELAY-th update.  The token after --td3 is its value when it holds a comma; a
+lone DELAY is written --td3=DELAY.  updates_per_step must be a multiple of DELAY; not with --n-step > 1 or --learn-log.
+Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -30,6 +33,17 @@ if "--learn-log" in sys.argv[1:]:
     at = sys.argv.index("--learn-log")
     learn_every = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+td3 = None
+for at, arg in enumerate(sys.argv):
+    if at and (arg == "--td3" or arg.startswith("--td3=")):
+        from ddpg_trucktrailer_amd.td3 import TD3Config
+        spec = arg[6:] if arg.startswith("--td3=") else ""
+        if arg == "--td3" and at + 1 < len(sys.argv) and "," in sys.argv[at + 1]:
+            spec = sys.argv.pop(at + 1)
+        del sys.argv[at]
+        parts = [x for x in spec.split(",") if x]
+        td3 = TD3Config(*([int(parts[0])] + [float(x) for x in parts[1:3]])) if parts else TD3Config()
+        break
 n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:7])
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 27
 graph_steps = int(sys.argv[8]) if len(sys.argv) > 8 else (20 if slots <= 1024 else 0)      # (as before: no graphs past 1024 slots)
@@ -40,9 +54,9 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                   learn_log_every=learn_every or 1)
+                   learn_log_every=learn_every or 1, td3=td3)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
-      f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}", flush=True)
+      f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else ""), flush=True)
 
 
 def learn_line(rec):
