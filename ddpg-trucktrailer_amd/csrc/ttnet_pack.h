@@ -24,9 +24,14 @@ constexpr int RING = 7;                     // an LDS-DMA piece lands ~1 us afte
 constexpr int AHEAD = RING - 2;
 constexpr int RING_BYTES = RING * CHUNK_BYTES;                        // 143,360
 constexpr int W1_PIECES = S1 * T1 * 2;      // 52 pieces of packed fc1: 13 per wave
-constexpr int W1_BYTES = W1_PIECES * 1024;  // 53,248: lives in ring slots 2..4 until layer 1 is done
-constexpr int W1_OFF = 2 * CHUNK_BYTES;
-static_assert(W1_OFF + W1_BYTES <= AHEAD * CHUNK_BYTES, "packed fc1 must fit in the ring slots that are filled after layer 1");
+constexpr int W1_BYTES = W1_PIECES * 1024;  // 53,248: lives in ring slots 4..6 until layer 1 is done -- the slots the tail of
+                                            // layer 2 frees first (steps 18, 19, 20), so the NEXT tile's fc1 is requested under
+                                            // steps 19..21 of the running tile; piece p goes to W1_OFF + p KB, wave w moves the
+                                            // pieces 4 i + w: piece i of every wave lies in the same slot (20 / 20 / 12 pieces)
+constexpr int W1_OFF = 4 * CHUNK_BYTES;
+constexpr int W1_WAVE_PIECES = W1_PIECES / 4;                         // 13
+static_assert(W1_OFF + W1_BYTES <= RING_BYTES, "packed fc1 must fit in ring slots 4..6");
+static_assert(W1_OFF % CHUNK_BYTES == 0 && CHUNK_BYTES % 4096 == 0, "a slot holds whole rows of four pieces (one per wave)");
 constexpr int VEC_FLOATS = 2 * H1P + 6 * H2P;                         // g1' | be1' | b2 | g2 | be2 | w3 | wa | ba = 2,752
 constexpr int VEC_PIECES = 12;              // 11,008 B padded to 12 KB: 3 DMA pieces per wave
 constexpr int VEC_BYTES = VEC_PIECES * 1024;

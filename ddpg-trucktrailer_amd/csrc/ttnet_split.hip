@@ -27,6 +27,8 @@
 //   steps ahead of its use.
 //   Layer 1 (K = 23 + the bias as a 24th input that is always 1) runs on the same three-product scheme from pre-split
 //   fc1 fragments, also brought into LDS by DMA.
+//   EVERY request of the tile loop is issued behind an MFMA (the matrix pipe hides most of a piece's issue cost; between
+//   vector phases a piece costs 100-185 cycles): the schedule is the table above l2_job below, the counted waits follow from it.
 #include "ttnet_common.h"
 #include "ttnet_pack.h"
 #include "ttstamps.h"
@@ -73,6 +75,85 @@ __global__ __launch_bounds__(256) void k_pack_and_sample(const Weights W, const 
     if (b < R.batch * R.draws) ring_sample_row(R, b, threadIdx.x & 63);
 }
 
+// ---- Where a wave issues its LDS-DMA pieces inside the tile loop, and what the counted waits may leave in flight.
+// Ring slot of k16 step s: s % RING.  At a tile's top the ring holds packed fc1 in slots 4..6 (W1_OFF) and -- from the second
+// tile of a workgroup on -- steps 0, 1 in slots 0, 1.
+//   layer 1, behind the third MFMA of product q = 2 t + s (26 products):
+//     q 0..9   steps 0, 1 -> slots 0, 1     FIRST tile only (later tiles got them from the previous tile's tail)
+//     q 10..19 steps 2, 3 -> slots 2, 3     held steps 23, 24 of the previous tile: every wave is past the tile's top barrier,
+//                                           which it reaches after its last fragment read of the previous tile
+//   layer 2, behind the third MFMA of tile u of step s (l2_job):
+//     s = 0           steps 4 (u < 5), 5 (u >= 5) -> slots 4, 5   held fc1: every wave is past the barrier in front of layer 2,
+//     s = 1, u < 5    step 6 -> slot 6                            which it reaches after its layer 1
+//     s = 1..18, u >= 5   step s + 6 -> the slot of step s - 1    every wave is past the mid-step barrier of step s, i.e. past
+//                                                                 tile 4 of step s: its reads of step s - 1 ended in step s - 1
+//     s = 19..21, u >= 5  the NEXT tile's fc1 pieces 5 (s - 19) + u - 5 < 13 -> slots 4, 5, 6 = the slots of steps 18, 19, 20:
+//                         the slot of step s - 1 again, by the same barrier
+//     s = 22, 23, u >= 5  the NEXT tile's steps 0, 1 -> slots 0, 1 = the slots of steps 21, 22: likewise
+// In EVERY layer-2 row the rule is the same: behind the mid-step barrier of step s a piece may overwrite the slot of step
+// s - 1 (static_asserts below).  The tail requests are unconditional -- the image is the same for every tile -- so the counts
+// are compile-time; a workgroup's last tile fetches 23 pieces per wave that nobody reads and drains them before it ends.
+constexpr int JOB_NONE = -1, JOB_FC1 = 100, JOB_NEXT = 200;      // a job: fc2 step 0..24 of this tile | fc1 piece | next tile's step
+constexpr int TAIL0 = STEPS - (RING - 1);                         // 19: the first step whose u >= 5 slots carry no fc2 step
+constexpr int l2_job(const int s, const int u) {
+    if (s == 0) return AHEAD - 1 + u / 5;
+    if (s == 1 && u < 5) return RING - 1;
+    if (u < 5) return JOB_NONE;
+    if (s < TAIL0) return s + RING - 1;
+    const int i = 5 * (s - TAIL0) + u - 5;
+    if (i < W1_WAVE_PIECES) return JOB_FC1 + i;
+    if (s == TAIL0 + 3 || s == TAIL0 + 4) return JOB_NEXT + s - (TAIL0 + 3);
+    return JOB_NONE;
+}
+constexpr int l2_piece(const int u) { return u % 5; }             // which of the wave's five pieces of a step
+// the ring slot a job of layer 2 writes (fc1 piece i of every wave lies in row i of W1_OFF: 5 rows per slot)
+constexpr int job_slot(const int j) { return j >= JOB_NEXT ? j - JOB_NEXT : (j >= JOB_FC1 ? W1_OFF / CHUNK_BYTES + (j - JOB_FC1) / 5 : j % RING); }
+constexpr bool l2_slots_free() {
+    for (int s = 0; s < STEPS; ++s)
+        for (int u = 0; u < T2; ++u) {
+            const int j = l2_job(s, u);
+            if (j == JOB_NONE) continue;
+            if (s == 0 || (s == 1 && u < 5)) { if (job_slot(j) < W1_OFF / CHUNK_BYTES) return false; }      // fc1's slots only
+            else if (u < 5 || job_slot(j) != (s - 1) % RING) return false;
+        }
+    return true;
+}
+static_assert(l2_slots_free(), "a piece of layer 2 overwrites a slot that may still be read");
+// Pieces a wave has issued before the mid-step barrier of step s that are YOUNGER than its pieces of step s + 1: what the
+// s_waitcnt there may leave in flight (pieces retire in issue order; nothing else is outstanding inside a tile: the top of the
+// tile waits for 0).  Counted over the order of issue: layer 1's steps 2, 3 (steps 0, 1 are older in either form of the tile),
+// then l2_job row by row.
+constexpr int mid_allowed(const int s) {
+    int n = 10, after = s + 1 == 2 ? 5 : (s + 1 == 3 ? 10 : -1000);
+    for (int ss = 0; ss < STEPS; ++ss)
+        for (int u = 0; u < T2; ++u) {
+            if (ss == s && u == T2 / 2) return n - after;
+            const int j = l2_job(ss, u);
+            if (j != JOB_NONE) { ++n; if (j == s + 1) after = n; }
+        }
+    return -1;
+}
+// steps 1..21: four younger steps, or the rest of them plus the next tile's fc1 so far (15 + 5, 10 + 10): 20.  Steps 22, 23:
+// step 24 (5) + fc1 (13), fc1 (13) + the next tile's step 0 (5): 18.  Steps 0 and 24 wait for nothing (see the loop).
+constexpr bool mid_counts_ok() {
+    for (int s = 1; s + 1 < STEPS; ++s) if (mid_allowed(s) != (s < TAIL0 + 3 ? 20 : 18)) return false;
+    return true;
+}
+static_assert(mid_counts_ok(), "the counted waits of layer 2 do not match the issue schedule");
+// (tables: the kernel's unrolled loops index them with constants)
+struct L2Schedule {
+    int job[STEPS][T2], mid[STEPS];
+};
+constexpr L2Schedule make_l2_schedule() {
+    L2Schedule t{};
+    for (int s = 0; s < STEPS; ++s) {
+        t.mid[s] = mid_allowed(s);
+        for (int u = 0; u < T2; ++u) t.job[s][u] = l2_job(s, u);
+    }
+    return t;
+}
+constexpr L2Schedule L2S = make_l2_schedule();
+
 // LDS reads through laundered address-space-3 bases.  The ring + vectors span 152 KB and a ds_read's immediate offset reaches
 // 64 KB, so three byte bases (0, 64 KB, 128 KB; + this lane's 16 bytes) cover every fragment with an immediate; the bases pass
 // through an empty asm at the top of every tile so that the compiler can neither hoist the ~300 fragment addresses of a tile out
@@ -89,8 +170,8 @@ __device__ __forceinline__ uint4 lds_frag(const LdsBases &L, const int off) {   
 }
 
 // One workgroup = 4 waves = 128 envs per TILE; a workgroup takes the tiles tile0 + blockIdx.x, + gridDim.x, ... < tile_end in
-// turn.  From the second tile on, the tile's observations, packed fc1 and the first two k16 steps of fc2 are requested before
-// the PREVIOUS tile's epilogue and land behind it; the per-neuron vectors stay in LDS.
+// turn.  From the second tile on, the tile's packed fc1 and the first two k16 steps of fc2 are requested under the last steps
+// of the PREVIOUS tile's layer 2 and its observations before that tile's epilogue; the per-neuron vectors stay in LDS.
 template <bool CRITIC>
 __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int tile0, const int tile_end,
                                                       int *__restrict__ cursor_e, const long long *__restrict__ step_e,
@@ -129,7 +210,9 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
     const long long kstep = cursor_e ? *step_e : 0;
     const bool odd = act.cursor && (kstep & 1);
     const bool local = act.cursor && act.ring_slots > 0;
-    const int slot_t = local ? (int)(kstep % act.ring_slots) : 0;
+    // (the 64-bit modulo is a software loop in front of every launch's observation loads: 32 bits while the counter fits)
+    const int slot_t = !local ? 0 : ((unsigned long long)kstep >> 32) == 0ull ? (int)((unsigned)kstep % (unsigned)act.ring_slots)
+                                                                             : (int)(kstep % act.ring_slots);
     const float *obs_base = local ? obs + (size_t)slot_t * act.ring_n * IN : obs;      // (re-read from the cursor below when !local)
     // LDS is filled by LDS-DMA (global_load_lds_dwordx4: 64 lanes x 16 B = one 1 KB piece per wave-instruction, no
     // staging registers).  The statements are inline asm, so hipcc neither counts them nor drains them at a barrier:
@@ -146,13 +229,12 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
                      : "=&s"(keep) : "v"(voff), "s"(base), "s"(lds_wave), "s"(dst_const) : "memory", "scc");
     };
     const unsigned voff_w2 = lane * 16 + wave * 5120 + WS_W2;                              // this wave's 5 pieces of a k16 step
-    const unsigned voff_w1 = lane * 16 + wave * (W1_PIECES / 4) * 1024 + WS_W1;            // ... 13 pieces of packed fc1
+    const unsigned voff_w1 = lane * 16 + wave * 1024 + WS_W1;                              // ... 13 pieces of packed fc1: 4 i + wave
     const unsigned voff_vec = lane * 16 + wave * (VEC_PIECES / 4) * 1024 + WS_VEC;         // ... 3 pieces of the vectors
-    const unsigned ldsw_w2_0 = lds_base0 + wave * 5120, ldsw_w1_0 = lds_base0 + W1_OFF + wave * (W1_PIECES / 4) * 1024;
+    const unsigned ldsw_w2_0 = lds_base0 + wave * 5120, ldsw_w1_0 = lds_base0 + W1_OFF + wave * 1024;
     // this wave's share of packed fc1 (13 pieces) / of k16 step s of fc2 (5 pieces), from image `w`
-    auto issue_fc1 = [&](const unsigned char *w, const unsigned ldsw_w1) __attribute__((always_inline)) {
-#pragma unroll
-        for (int i = 0; i < W1_PIECES / 4; ++i) dma_piece(w, voff_w1 + i * 1024, ldsw_w1, i * 1024);
+    auto issue_fc1_piece = [&](const unsigned char *w, const unsigned ldsw_w1, const int i) __attribute__((always_inline)) {
+        dma_piece(w, voff_w1 + i * 4096, ldsw_w1, i * 4096);
     };
     auto issue_step_piece = [&](const unsigned char *w, const unsigned ldsw_w2, const int s, const int i) __attribute__((always_inline)) {
         dma_piece(w, voff_w2 + s * CHUNK_BYTES + i * 1024, ldsw_w2, (s % RING) * CHUNK_BYTES + i * 1024);
@@ -187,7 +269,8 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
 
     NSTAMP(0);
     // ---- prologue of the FIRST tile: this lane's observation features first (ordinary loads: the compiler waits for them on
-    // its own count), then packed fc1 + the per-neuron vectors, then k16 steps 0 and 1 of fc2 by DMA
+    // its own count), then packed fc1 + the per-neuron vectors by DMA; fc2 steps 0 and 1 are not needed before layer 2 and are
+    // requested inside layer 1
     int tile = tile0 + (int)blockIdx.x;
     if (tile >= tile_end) return;
     if (local) {                          // the ring's slots of this step follow from the step counter: no look at the cursor
@@ -215,12 +298,11 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
                                  : (tid == 0 ? slot_t : tid == 1 ? (slot_t + 1 == sl ? 0 : slot_t + 1)
                                                       : tid == 2 ? (slot_t == 0 ? sl - 1 : slot_t - 1) : (kstep > 0 ? 1 : 0));
     }
-    issue_fc1(wsl, ldsw_w1_0);
+#pragma unroll
+    for (int i = 0; i < W1_WAVE_PIECES; ++i) issue_fc1_piece(wsl, ldsw_w1_0, i);
 #pragma unroll
     for (int i = 0; i < VEC_PIECES / 4; ++i)
         dma_piece(wsl, voff_vec + i * 1024, lds_base0 + RING_BYTES + wave * (VEC_PIECES / 4) * 1024, i * 1024);
-#pragma unroll
-    for (int i = 0; i < 10; ++i) issue_step_piece(wsl, ldsw_w2_0, i / 5, i % 5);
     bool first = true;
 #ifdef TT_STAMPS
     int round = 0;
@@ -257,33 +339,53 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
             xb[s][0] = make_uint4(ph[0], ph[1], ph[2], ph[3]);
             xb[s][1] = make_uint4(pm[0], pm[1], pm[2], pm[3]);
         }
-        // first tile: fc1 + vectors landed, fc2 steps 0, 1 may still fly.  Later tiles: everything of this tile was requested
-        // before the previous tile's epilogue; that epilogue's stores are among the outstanding operations and stores and
-        // loads retire in no fixed order, so nothing short of 0 tells that the DMA pieces have landed
-        if (first) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // Nothing younger than this tile's operands is in flight.  First tile: fc1 + the vectors, nothing requested after them.
+        // Later tiles: fc1 and fc2 steps 0, 1 were requested under the previous tile's layer 2, before its observation loads
+        // and its epilogue's stores; stores and loads retire in no fixed order, so nothing short of 0 tells that the DMA
+        // pieces have landed -- and nothing of this tile has been requested yet that 0 would wait for in vain.
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // publishes fc1 (and steps 0, 1); every wave is past the previous tile's layer 2: slots 2, 3 are free
         __builtin_amdgcn_s_barrier();
         if (first) NSTAMP(1);
 
         // ---- layer 1: acc1[t][v] = SX*SW * (pre-activation + bias) of neuron 32t + 8(v>>2) + 4h + (v&3), env `row`
+        // The same pinned issue order as layer 2 below: behind the three MFMAs of product q = (tile t, step s) go the two
+        // fragment reads of product q + 2 and one LDS-DMA piece (l1 rows of the schedule above).
+#define SB __builtin_amdgcn_sched_barrier(0)
         f32x16 acc1[T1];
+        {
+            auto w1_frag = [&](const int q, const int plane) __attribute__((always_inline)) {
+                return lds_frag(LB, W1_OFF + (((q % S1) * T1 + q / S1) * 2 + plane) * 1024);
+            };
+            // (the image base opaque once more for this layer, as layer 2 does per step: the layer's piece addresses are formed here.
+            // It costs the critic variant two SGPRs, 96 as before this schedule; every other entry of the kernels' resource table is
+            // what it was -- tests/golden/kernel_resources_main.json)
+            const unsigned char *wsl_1 = wsl_cur;
+            asm volatile("" : "+s"(wsl_1));
+            uint4 a0h = w1_frag(0, 0), a0m = w1_frag(0, 1), a1h = w1_frag(1, 0), a1m = w1_frag(1, 1), a2h = a0h, a2m = a0m;
+            SB;
 #pragma unroll
-        for (int t = 0; t < T1; ++t) {
+            for (int q = 0; q < S1 * T1; ++q) {
+                const int t = q / S1, s = q % S1;
+                if (s == 0) {
 #pragma unroll
-            for (int v = 0; v < 16; ++v) acc1[t][v] = 0.f;
-#pragma unroll
-            for (int s = 0; s < S1; ++s) {
-                const uint4 ah = lds_frag(LB, W1_OFF + ((s * T1 + t) * 2) * 1024), am = lds_frag(LB, W1_OFF + ((s * T1 + t) * 2 + 1) * 1024);
-                acc1[t] = mfma_f16(am, xb[s][0], acc1[t]);                    // small terms first
-                acc1[t] = mfma_f16(ah, xb[s][1], acc1[t]);
-                acc1[t] = mfma_f16(ah, xb[s][0], acc1[t]);
+                    for (int v = 0; v < 16; ++v) acc1[t][v] = 0.f;
+                }
+                acc1[t] = mfma_f16(a0m, xb[s][0], acc1[t]); SB;                // small terms first
+                if (q + 2 < S1 * T1) a2h = w1_frag(q + 2, 0);
+                SB;
+                acc1[t] = mfma_f16(a0h, xb[s][1], acc1[t]); SB;
+                if (q + 2 < S1 * T1) a2m = w1_frag(q + 2, 1);
+                SB;
+                acc1[t] = mfma_f16(a0h, xb[s][0], acc1[t]); SB;
+                if (q < 10) { if (first) issue_step_piece(wsl_1, ldsw_w2, q / 5, q % 5); }
+                else if (q < 20) issue_step_piece(wsl_1, ldsw_w2, 2 + (q - 10) / 5, q % 5);
+                SB;
+                a0h = a1h; a0m = a1m; a1h = a2h; a1m = a2m;
             }
         }
         if (first) NSTAMP(2);
-        // every wave is done with packed fc1: its slots now take k16 steps 2..5 of fc2 (they land during LayerNorm 1)
-        __builtin_amdgcn_s_barrier();
-#pragma unroll
-        for (int i = 10; i < 5 * (AHEAD + 1); ++i) issue_step_piece(wsl_cur, ldsw_w2, i / 5, i % 5);
+        // (no barrier and no request here: fc1's slots are written again only behind the barrier in front of layer 2)
         uint32_t hb[STEPS][4], mb[STEPS][4];
         // LayerNorm(400) (biased variance, eps 1e-5) on the SCALED pre-activations: mean and deviations scale with them,
         // 1/sigma absorbs the scale; then gamma*SX, beta*SX and ReLU give the layer-2 operand already scaled by SX.
@@ -361,34 +463,33 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
         // LDS-DMA piece of step s + 6 -- and, behind the first MFMA of every tile, one chunk of LayerNorm 1's last pass for the B
         // operand of step s + 2 (a tenth of a step's worth: 3-4 vector instructions).
         // One barrier per step, in the middle (before tile 5): it publishes step s + 1 (every wave has waited for its own
-        // pieces of it with a COUNTED vmcnt that leaves the four younger steps in flight) and tells that every wave is past
-        // step s - 1, whose slot the DMA of step s + 6 overwrites.  Fragments are read TWO tiles ahead
+        // pieces of it with a COUNTED vmcnt that leaves the younger pieces in flight: mid_allowed) and tells that every wave is
+        // past step s - 1, whose slot the pieces behind it overwrite (l2_job).  Fragments are read TWO tiles ahead
         // (tiles 0, 1 of step s + 1 during tiles 8, 9 of step s, after that barrier), so a read has six MFMAs to land.
-#define SB __builtin_amdgcn_sched_barrier(0)
-        asm volatile("s_waitcnt vmcnt(20)" ::: "memory");      // steps 0 and 1 (this wave's pieces); 2..5 may still fly
+        // Step 0 has no such barrier: step 1 is published by the barrier in front of the loop and its pieces go to fc1's
+        // slots.  Step 24 has none either: nothing is read after it and nothing is issued in it.
+        asm volatile("s_waitcnt vmcnt(10)" ::: "memory");      // steps 0 and 1 (this wave's pieces); 2 and 3 (layer 1) may still fly
+        // publishes steps 0, 1; every wave is past its layer 1: fc1's slots 4..6 are free for steps 4, 5, 6
         __builtin_amdgcn_s_barrier();
         // A fragments (h, m) of three consecutive tiles: the current one, the next, and the one being read (two ahead);
         // rotated by renaming at the end of every tile (the loops are fully unrolled: no moves)
         uint4 c0h = lds_frag(LB, 0), c0m = lds_frag(LB, 1024), c1h = lds_frag(LB, 2048), c1m = lds_frag(LB, 3072), c2h = c0h, c2m = c0m;
         SB;
-#pragma unroll
-        for (int s = 0; s < STEPS; ++s) {
+        auto l2_step = [&](const int s) __attribute__((always_inline)) {
             const uint4 vh = make_uint4(hb[s][0], hb[s][1], hb[s][2], hb[s][3]), vm = make_uint4(mb[s][0], mb[s][1], mb[s][2], mb[s][3]);
             const int slot = (s % RING) * CHUNK_BYTES, nslot = ((s + 1) % RING) * CHUNK_BYTES;
             // (per step, so that the step's five DMA addresses are formed here and not all 125 at the top of the tile)
             const unsigned char *wsl_s = wsl_cur;
-            unsigned lds_s = ldsw_w2;
+            unsigned lds_s = ldsw_w2, lds1_s = ldsw_w1;
             asm volatile("" : "+s"(wsl_s), "+s"(lds_s));
+            if (s >= TAIL0 && s < TAIL0 + 3) asm volatile("" : "+s"(lds1_s));
 #pragma unroll
             for (int u = 0; u < T2; ++u) {
-                if (u == T2 / 2) {
-                    // step s + 1 must have landed; the steps issued after it (up to four) may still be in flight
-                    switch (STEPS - 2 - s < 4 ? STEPS - 2 - s : 4) {
-                        case 4: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
-                        case 3: asm volatile("s_waitcnt vmcnt(15)" ::: "memory"); break;
-                        case 2: asm volatile("s_waitcnt vmcnt(10)" ::: "memory"); break;
-                        case 1: asm volatile("s_waitcnt vmcnt(5)" ::: "memory"); break;
-                        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+                if (u == T2 / 2 && s >= 1 && s + 1 < STEPS) {
+                    // step s + 1 must have landed; the pieces issued after it may still be in flight (mid_counts_ok: 20 or 18)
+                    switch (L2S.mid[s]) {
+                        case 20: asm volatile("s_waitcnt vmcnt(20)" ::: "memory"); break;
+                        default: asm volatile("s_waitcnt vmcnt(18)" ::: "memory"); break;
                     }
                     __builtin_amdgcn_s_barrier();
                     SB;
@@ -403,25 +504,34 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
                 if (more) c2m = lds_frag(LB, nx + 1024);
                 SB;
                 acc2[u] = mfma_f16(c0h, vh, acc2[u]); SB;
-                if (u >= 5 && s + RING - 1 < STEPS) issue_step_piece(wsl_s, lds_s, s + RING - 1, u - 5);
+                {
+                    // (one request statement, its operands selected by the job: all constants once s and u are)
+                    const int j = L2S.job[s][u];
+                    const bool f1 = j >= JOB_FC1 && j < JOB_NEXT;
+                    const int st = j >= JOB_NEXT ? j - JOB_NEXT : j, i1 = j - JOB_FC1;
+                    if (j != JOB_NONE)
+                        dma_piece(wsl_s, f1 ? voff_w1 + i1 * 4096 : voff_w2 + st * CHUNK_BYTES + l2_piece(u) * 1024, f1 ? lds1_s : lds_s,
+                                  f1 ? i1 * 4096 : (st % RING) * CHUNK_BYTES + l2_piece(u) * 1024);
+                }
                 SB;
                 c0h = c1h; c0m = c1m; c1h = c2h; c1m = c2m;
             }
-        }
+        };
+        // (three loops, not one: the unroller takes a loop only up to a size, and it sizes the body before s is a constant)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) l2_step(s);
+#pragma unroll
+        for (int s = 2; s < TAIL0; ++s) l2_step(s);
+#pragma unroll
+        for (int s = TAIL0; s < STEPS; ++s) l2_step(s);
 #undef SB
 
         if (first) NSTAMP(4);
-        // ---- the next tile of this workgroup: its observations, packed fc1 and fc2 steps 0, 1 are requested NOW (every wave is
-        // past its last fragment read: the ring is free) and land behind the epilogue below
+        // ---- the next tile of this workgroup: its packed fc1 and fc2 steps 0, 1 are on their way (layer 2's tail); its
+        // observations are requested NOW and land behind the epilogue below (they go to registers: no barrier)
         const int next = tile + (int)gridDim.x;
         const bool more_tiles = next < tile_end;
-        if (more_tiles) {
-            __builtin_amdgcn_s_barrier();
-            load_obs(next);
-            issue_fc1(wsl_cur, ldsw_w1);
-#pragma unroll
-            for (int i = 0; i < 10; ++i) issue_step_piece(wsl_cur, ldsw_w2, i / 5, i % 5);
-        }
+        if (more_tiles) load_obs(next);
         // ---- epilogue: scale back + bias, LayerNorm(300), (critic: + action_value(a)), ReLU, head; acc2[u][v] is neuron
         // 32u + 8(v>>2) + 4h + (v&3); 300 = 9*32 + 12, so groups of four are all real or all padding
         // (the per-neuron vectors are read from LDS one tile ahead of their use, as in LayerNorm 1)
@@ -519,6 +629,9 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
         tile = next;
         first = false;
     }
+    // the last tile's tail requested a next tile's operands like every other: no piece may be in flight when the wave ends
+    // (the LDS goes to another workgroup).  They were issued an epilogue ago: the wait is over before it begins.
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 }  // namespace
