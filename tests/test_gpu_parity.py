@@ -235,7 +235,9 @@ def test_n4096_random_policy_vs_c_oracle(torch_mod):
         if not alive.any():
             break
     assert not alive.any(), "some episode never ended within 260 steps"
-    assert causes[0] > 0 and causes[1] > 0, f"termination causes seen: {causes}"   # jackknife, out of map at least
+    # jackknife, out of map at least; a random policy reaches no goal: the goal-side causes (goal reached, success, both stage
+    # latches, past the goal, excessive backward) are held to the oracle by tests/test_gpu_goal_zone.py
+    assert causes[0] > 0 and causes[1] > 0, f"termination causes seen: {causes}"
     env.close()
 
 
