@@ -125,6 +125,11 @@ class TTTd3Agent(C.Structure):
                 ("q_pi", C.c_void_p), ("dq_da", C.c_void_p), ("tail_words", C.c_void_p), ("gave_up_host", C.c_void_p)]
 
 
+class TTPopTd3Pair(C.Structure):
+    _fields_ = [("dst", C.c_int32), ("src", C.c_int32)] + \
+               [(n, C.c_float) for n in ("alpha", "beta", "tau", "gamma", "target_noise", "noise_clip")]
+
+
 class TTLearnLogJob(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
                [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
@@ -137,7 +142,7 @@ LEARN_LOG_CHUNKS = 16                   # TT_LEARN_LOG_CHUNKS
 LEARN_LOG_MAX_CAPACITY = 1 << 22        # TT_LEARN_LOG_MAX_CAPACITY
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 NSTEP_MAX = 16          # TT_NSTEP_MAX
-TD3_NOISE_TAG = 0x7D3E  # the Philox domain of TD3's target-smoothing noise (csrc/tttd3.hip)
+TD3_NOISE_TAG = 0x7D3E  # the Philox domain of TD3's target-smoothing noise (csrc/tttd3.h)
 
 
 class TTError(RuntimeError):
@@ -236,6 +241,11 @@ _SIGNATURES = {
     "tt_td3_update": (C.c_int, [_P, C.POINTER(TTTd3Agent)]),
     "tt_td3_learn": (C.c_int, [_P, _I, _I, _P]),
     "tt_td3_destroy": (C.c_int, [_P]),
+    "tt_pop_td3_create": (C.c_int, [_I, _I, C.POINTER(TTTd3Agent), C.POINTER(_P)]),
+    "tt_pop_td3_learn": (C.c_int, [_P, _I, _I, _P]),
+    "tt_pop_td3_exploit": (C.c_int, [_P, _I, C.POINTER(TTPopTd3Pair), _P]),
+    "tt_pop_td3_hyper": (C.c_int, [_P, _I, C.POINTER(C.c_float * 6)]),
+    "tt_pop_td3_destroy": (C.c_int, [_P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -1,0 +1,375 @@
+// ttpop_td3.hip -- TD3's learn() for a POPULATION of K independent agents in the launches of one agent's TD3 update (MI355X, gfx950).
+//
+// What csrc/ttpop.hip is to csrc/ttlearn.hip, this file is to csrc/tttd3.hip: agent a is a lone TD3 loop of its own, only its
+// learn() launches are shared.  Each launch below runs the workgroups of all K agents; a workgroup finds its agent and its block
+// within the agent's grid from blockIdx.x and then does exactly what the lone launch's workgroup does, with the arguments the lone
+// launch passes (the bodies of ttlearn_bodies.h, the prologue and the descriptor of tttd3.h):
+//
+//   k_pop_td3_fwd_multi        K x (full ? 6 : 5) x nb, agent-major; inside an agent job-major: k_td3_fwd_multi.  The agent's first
+//                              workgroup leaves its step_snap.
+//   k_pop_td3_bwd_rows         K x ((full ? 3 : 2) x nb + 1), agent-major: critic 1's rows, critic 2's rows, [the actor's unit rows,]
+//                              then that agent's counter workgroup: k_td3_bwd_rows.
+//   k_pop_td3_bwd_weights      K x 2 x 210, agent-major, critic-major inside: k_td3_bwd_weights (the tau = 0 variant on critic-only
+//                              updates).
+//   k_pop_td3_actor_tail       full updates only: the K x nb row workgroups of ALL agents first, then the K x 200 weight workgroups:
+//                              no workgroup that waits in device memory has a lower flat index than any producer (the dispatch-order
+//                              rule of k_pop_actor_tail).  Each agent has its own TailSync words and gave_up_host, and its epoch is
+//                              its own ACTOR step count.  The tail's bounded wait is the only wait in device memory here.
+//
+// and, off the learn() path, k_pop_td3_exploit (tt_pop_td3_exploit): PBT's exploit/explore step for six networks.
+//
+// So each agent's results are the bits of its lone TD3 update (tests/test_gpu_population_td3.py).  The descriptors are Td3Agent[K]
+// in device memory, filled once at tt_pop_td3_create and read through the constant address space: a launch takes
+// (K, descriptors, u, full) and is graph-capturable.  `full` is a launch argument, so policy_delay is one value for the whole
+// population; sigma, clip, alpha, beta, tau and gamma are each agent's own.  The sampled-row prologue of the first launch is written
+// out a third time here (k_pop_fwd_multi, k_td3_fwd_multi): the kernels that hold it keep their instructions that way.
+#include "tttd3.h"
+
+#include <cstddef>
+#include <vector>
+
+namespace {
+
+// grid: K x (full ? 6 : 5) x nb, agent-major; within an agent job-major as k_td3_fwd_multi
+__global__ __launch_bounds__(64 * NW) void k_pop_td3_fwd_multi(const int K, const Td3Agent *__restrict__ D, const int u, const int full) {
+    __shared__ __attribute__((aligned(16))) float h1_s[H1S_FLOATS];
+    __shared__ __attribute__((aligned(16))) float z_s[TR * DS];
+    __shared__ __attribute__((aligned(16))) float w1_s[H1 * IN];
+    const int n = td3_of(D).n, nb = (n + TR - 1) / TR, per = (full ? 6 : 5) * nb, ag = (int)blockIdx.x / per;      // (one B for all)
+    if (ag >= K) return;
+    const Td3Agent &P = td3_of(D + ag);
+    const int lb = (int)blockIdx.x - ag * per, job = lb / nb, row0 = (lb - job * nb) * TR;
+    if (lb == 0 && threadIdx.x == 0) *P.step_snap = *P.step_dev;      // (the next launch ticks step_dev)
+    const FwdJob &q = P.j[job];
+    ttnet::RingSample R = P.R;
+    R.seed += (unsigned long long)u * R.seed_stride;
+    static_assert(TR / NW == 2, "two rows per wave");
+    const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
+    const bool from_s = q.obs == R.s_out;
+    const float *orow;
+    {
+        const ttnet::RingPick p = ttnet::ring_sample_index(R, min(row0 + l15, n - 1));
+        orow = from_s ? ttnet::ring_pick_s(R, p) : ttnet::ring_pick_s2(R, p);
+    }
+    bool have_act = false;
+    float act_r0 = 0.f, act_r1 = 0.f;
+    if (q.critic && q.action) {
+        act_r0 = ttnet::ring_pick_a(R, ttnet::ring_sample_index(R, min(row0 + wave * 2, n - 1)));
+        act_r1 = ttnet::ring_pick_a(R, ttnet::ring_sample_index(R, min(row0 + wave * 2 + 1, n - 1)));
+        have_act = true;
+    }
+    if (job == P.write_s || job == P.write_s2) {        // the batch rows of this workgroup for the later launches
+        const int lr = tid / ttnet::IN, c = tid - lr * ttnet::IN, b = row0 + lr;
+        if (lr < TR && b < n) {
+            const ttnet::RingPick p = ttnet::ring_sample_index(R, b);
+            if (job == P.write_s) {
+                R.s_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s(R, p)[c];
+                if (c == 0) {
+                    R.a_out[b] = ttnet::ring_pick_a(R, p);
+                    if (R.idx_out) { R.idx_out[2 * b] = p.side ? -1 : p.t; R.idx_out[2 * b + 1] = p.side ? p.j : p.e; }
+                }
+            }
+            if (job == P.write_s2) {
+                R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s2(R, p)[c];
+                if (c == 0) { R.r_out[b] = ttnet::ring_pick_r(R, p); R.d_out[b] = ttnet::ring_pick_d(R, p); }
+            }
+        }
+    }
+    if (q.critic)
+        fwd_small_body<true>(n, q.obs, q.action, q.W, q.out, q.sv, q.dq_da, q.z_state, h1_s, z_s, w1_s, row0, orow, have_act, act_r0, act_r1);
+    else
+        fwd_small_body<false>(n, q.obs, q.action, q.W, q.out, q.sv, nullptr, nullptr, h1_s, z_s, w1_s, row0, orow);
+}
+
+// grid: K x ((full ? 3 : 2) x nb + 1), agent-major: critic 1's rows, critic 2's rows, [the actor's unit rows,] the agent's counter
+// workgroup
+__global__ __launch_bounds__(64 * NW) void k_pop_td3_bwd_rows(const int K, const Td3Agent *__restrict__ D, const int u, const int full) {
+    __shared__ __attribute__((aligned(16))) float dx2_s[DXS_FLOATS];
+    __shared__ float red[2 * NW * TR];
+    __shared__ float rsc_s[TR];
+    const int n = td3_of(D).n, nb = (n + TR - 1) / TR, groups = full ? 3 : 2, per = groups * nb + 1, ag = (int)blockIdx.x / per;
+    if (ag >= K) return;
+    const Td3Agent &P = td3_of(D + ag);
+    const int lb = (int)blockIdx.x - ag * per;
+    if (lb == groups * nb) {
+        if (threadIdx.x == 0) {
+            clock_tick(P.tick_c);
+            if (full) clock_tick(P.tick_a);
+        }
+        return;
+    }
+    if (lb < 2 * nb) {
+        const int c = lb / nb, row0 = (lb - c * nb) * TR;
+        float y[TR / NW];
+        td3_prologue(P, c, row0, y);
+        bwd_rows_body<true, true>(n, P.scale_c, P.q_out[c], P.Wc[c], P.sv_c[c], P.o_c[c], TdIn{}, dx2_s, red, rsc_s, row0, y);
+    } else {
+        bwd_rows_body<false>(n, 0.f, nullptr, P.Wa, P.sv_a, P.o_a, TdIn{}, dx2_s, red, rsc_s, (lb - 2 * nb) * TR);
+    }
+}
+
+// grid: K x 2 x 210, agent-major, critic-major inside: a critic's weight gradients with its optimizer step
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void k_pop_td3_bwd_weights(const int K,
+                                                                                                 const Td3Agent *__restrict__ D,
+                                                                                                 const int u, const int full) {
+    __shared__ __attribute__((aligned(16))) float part[4][4][256];
+    __shared__ float f_s[1];
+    __shared__ __attribute__((aligned(16))) _Float16 stage_s[4 * 1024];
+    const int ag = (int)blockIdx.x / (2 * WG_CRITIC_WEIGHTS);
+    if (ag >= K) return;
+    const int lb = (int)blockIdx.x - ag * 2 * WG_CRITIC_WEIGHTS, c = lb / WG_CRITIC_WEIGHTS;
+    const Td3Agent &P = td3_of(D + ag);
+    bwd_weights_body<false, false>(lb - c * WG_CRITIC_WEIGHTS, P.n, 1, P.s, P.a, P.sv_c[c], P.o_c[c], P.Gc[c], P.Ac[c][full ? 0 : 1],
+                                   RowScale{nullptr, nullptr, 1.f}, part, f_s, TailSync{nullptr, nullptr, 0, nullptr}, 0, stage_s);
+}
+
+// grid: K x nb row workgroups FIRST (every agent's), then K x 200 weight workgroups: Q1(s, mu(s)) and dQ/da through each agent's
+// updated critic 1, then its actor's weight gradients + Adam + soft update.  A weight workgroup waits in device memory for its agent's
+// rows (TailSync, bounded), so every producer is dispatched before any workgroup that may wait for it.
+__global__ __launch_bounds__(64 * NW) void k_pop_td3_actor_tail(const int K, const Td3Agent *__restrict__ D, const int u, const int full) {
+    __shared__ __attribute__((aligned(16))) float lds[H1S_FLOATS + TR * DS + H1 * IN];
+    const int n = td3_of(D).n, nb = (n + TR - 1) / TR, rows = K * nb;
+    if ((int)blockIdx.x < rows) {
+        const int ag = (int)blockIdx.x / nb, lb = (int)blockIdx.x - ag * nb;
+        const Td3Agent &P = td3_of(D + ag);
+        const Saved none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+        const long long epoch = *P.Aa.step_dev;
+        fwd_small_body<true>(n, P.s, P.mu_out, P.Wc[0], P.q_pi, none, P.dq_da, nullptr, lds, lds + H1S_FLOATS,
+                             lds + H1S_FLOATS + TR * DS, lb * TR, nullptr, false, 0.f, 0.f, P.ts.rows, (unsigned)epoch);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave: its rows' words have been sent
+        __syncthreads();
+        if (threadIdx.x == 0) __hip_atomic_store(P.ts.hints + lb, (int)epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        return;
+    }
+    const int ag = ((int)blockIdx.x - rows) / WG_ACTOR_WEIGHTS;
+    if (threadIdx.x >= 256 || ag >= K) return;
+    const Td3Agent &P = td3_of(D + ag);
+    float (&part)[4][4][256] = *reinterpret_cast<float (*)[4][4][256]>(lds);
+    const long long epoch = *P.Aa.step_dev;
+    bwd_weights_body<true, true>((int)blockIdx.x - rows - ag * WG_ACTOR_WEIGHTS, n, 0, P.s, nullptr, P.sv_a, P.o_a, P.Ga, P.Aa, P.RSa,
+                                 part, lds + 4 * 4 * 256, P.ts, epoch, reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB));
+}
+
+// ---- PBT exploit/explore (tt_pop_td3_exploit): dst's learning state <- src's, then dst's hyperparameters, in one launch ----
+// k_pop_exploit's shape for six networks.  A pair's copy is 142 regions: per trained network (critic 1 and critic 2 with 12 tensors
+// each, then the actor with 10) and tensor t, its parameters, Adam m, Adam v and target parameters (4 t + {0, 1, 2, 3}), then the six
+// fc2 images (network / target of critic 1, critic 2, the actor), each whole: its forward and its backward halves.  Each region is
+// cut into X3_CHUNK-byte pieces, one workgroup each.  Nothing else is copied: dst's env, ring, noise seed, both step counts, both
+// bias-correction buffers, step_snap, tail words and scratch buffers stay its own.
+struct Exploit3List {
+    int n;
+    tt_pop_td3_pair p[TT_POP_MAX_AGENTS];
+};
+
+constexpr int X3_THREADS = 256, X3_UNROLL = 4;
+constexpr size_t X3_CHUNK = (size_t)X3_THREADS * X3_UNROLL * 16;        // bytes per workgroup: 16 KB
+constexpr int X3_CRITIC = 4 * 12, X3_TENSOR_REGIONS = 2 * X3_CRITIC + 4 * 10, X3_REGIONS = X3_TENSOR_REGIONS + 6;
+
+__host__ __device__ constexpr int x3_numel(const int t) {                // tensor t of tt_mlp_weights' order
+    return t == 0 ? H1 * IN : t < 4 ? H1 : t == 4 ? H2 * H1 : t < 9 ? H2 : t == 9 ? 1 : H2;
+}
+__host__ __device__ constexpr size_t x3_region_bytes(const int r) {
+    return r < X3_TENSOR_REGIONS ? (size_t)x3_numel((r % X3_CRITIC) >> 2) * 4 : IMG_HALVES * 2;
+}
+__host__ __device__ constexpr int x3_region_chunks(const int r) { return (int)((x3_region_bytes(r) + X3_CHUNK - 1) / X3_CHUNK); }
+constexpr int x3_chunks_per_pair() {
+    int s = 0;
+    for (int r = 0; r < X3_REGIONS; ++r) s += x3_region_chunks(r);
+    return s;
+}
+constexpr int X3_CHUNKS = x3_chunks_per_pair();
+
+__device__ __forceinline__ float *x3_tensor(const AdamFused &A, const int kind, const int t) {
+    return kind == 0 ? A.p[t] : kind == 1 ? A.m[t] : kind == 2 ? A.v[t] : A.tgt[t];
+}
+// trained network i of a descriptor (0, 1: the critics; 2: the actor).  Both variants of a critic hold the same tensors and images.
+__device__ __forceinline__ const AdamFused &x3_net(const Td3Agent &P, const int i) { return i < 2 ? P.Ac[i][0] : P.Aa; }
+
+// grid: pairs x X3_CHUNKS, pair-major.  No pair's dst is another pair's src (tt_pop_td3_exploit checks), so every byte a workgroup
+// reads is written by no workgroup of the launch.  The descriptors' pointers are read, never written; the hyperparameter words are
+// written with plain global stores and read by the later launches on the stream.
+__global__ __launch_bounds__(X3_THREADS) void k_pop_td3_exploit(const Exploit3List L, Td3Agent *__restrict__ D) {
+    const int pair = (int)blockIdx.x / X3_CHUNKS, piece = (int)blockIdx.x - pair * X3_CHUNKS;
+    if (pair >= L.n) return;
+    const tt_pop_td3_pair q = L.p[pair];
+    if (piece == 0 && threadIdx.x == 0) {
+        Td3Agent &W = D[q.dst];
+        W.Aa.lr = q.alpha;
+        W.Aa.tau = q.tau;
+        for (int c = 0; c < 2; ++c) {
+            W.Ac[c][0].lr = q.beta;
+            W.Ac[c][1].lr = q.beta;
+            W.Ac[c][0].tau = q.tau;        // (the tau = 0 variant of critic-only updates stays 0)
+        }
+        W.gamma = q.gamma;
+        W.sigma = q.target_noise;
+        W.clip = q.noise_clip;
+    }
+    if (q.dst == q.src) return;
+    int r = 0, c = piece;
+    while (r < X3_REGIONS - 1 && c >= x3_region_chunks(r)) c -= x3_region_chunks(r++);
+    const Td3Agent &S = td3_of(D + q.src), &T = td3_of(D + q.dst);
+    const char *from;
+    char *to;
+    if (r < X3_TENSOR_REGIONS) {
+        const int net = r / X3_CRITIC, local = r - net * X3_CRITIC, t = local >> 2, kind = local & 3;
+        from = reinterpret_cast<const char *>(x3_tensor(x3_net(S, net), kind, t));
+        to = reinterpret_cast<char *>(x3_tensor(x3_net(T, net), kind, t));
+    } else {
+        const int i = r - X3_TENSOR_REGIONS;
+        const AdamFused &As = x3_net(S, i >> 1), &At = x3_net(T, i >> 1);
+        from = reinterpret_cast<const char *>((i & 1) ? As.img_t : As.img_p);
+        to = reinterpret_cast<char *>((i & 1) ? At.img_t : At.img_p);
+    }
+    if (!from || !to) return;                      // (images off)
+    const size_t bytes = x3_region_bytes(r), lo = (size_t)c * X3_CHUNK, hi = min(bytes, lo + X3_CHUNK);
+    const int tid = threadIdx.x;
+    const size_t mis = reinterpret_cast<uintptr_t>(to) & 15;
+    if (mis != (reinterpret_cast<uintptr_t>(from) & 15)) {         // no common 16-byte alignment: dwords
+        for (size_t o = lo + 4 * tid; o < hi; o += 4 * X3_THREADS)
+            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
+        return;
+    }
+    // 16-byte accesses over [head, head + body) of the region (head: the dwords before the first 16-byte boundary), dwords around
+    const size_t head = (16 - mis) & 15, body = bytes >= head ? (bytes - head) & ~(size_t)15 : 0;
+    if (c == 0) {
+        const size_t tail0 = head + body;
+        for (size_t o = 4 * tid; o < min(head, bytes); o += 4 * X3_THREADS)
+            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
+        for (size_t o = tail0 + 4 * tid; o < bytes; o += 4 * X3_THREADS)
+            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
+    }
+    const f32x4 *src4 = reinterpret_cast<const f32x4 *>(from + head);
+    f32x4 *dst4 = reinterpret_cast<f32x4 *>(to + head);
+    const size_t v_lo = lo / 16, v_hi = min(body, hi) / 16;
+    f32x4 x[X3_UNROLL];
+#pragma unroll
+    for (int k = 0; k < X3_UNROLL; ++k) {
+        const size_t i = v_lo + (size_t)k * X3_THREADS + tid;
+        if (i < v_hi) x[k] = src4[i];
+    }
+#pragma unroll
+    for (int k = 0; k < X3_UNROLL; ++k) {
+        const size_t i = v_lo + (size_t)k * X3_THREADS + tid;
+        if (i < v_hi) dst4[i] = x[k];
+    }
+}
+
+// what two agents of one population may not share (host only: no HIP call): each list holds one agent's addresses of a kind
+struct Owned {
+    const void *steps[2], *tail, *rows[3], *grads[3];
+};
+Owned owned_of(const Td3Agent &P) {
+    return Owned{{P.step_dev, P.tick_a.step_dev}, P.ts.hints, {P.o_c[0].dx2, P.o_c[1].dx2, P.o_a.dx2}, {P.Gc[0].w1, P.Gc[1].w1, P.Ga.w1}};
+}
+template <int NA, int NB>
+bool overlap(const void *const (&x)[NA], const void *const (&y)[NB]) {
+    for (const void *p : x)
+        for (const void *q : y)
+            if (p == q) return true;
+    return false;
+}
+
+}  // namespace
+
+struct tt_pop_td3 {
+    int K = 0, n = 0;
+    Td3Agent *dev = nullptr;
+};
+
+extern "C" {
+
+int tt_pop_td3_create(int count, int batch, const tt_td3_agent *agents, tt_pop_td3 **out) {
+    if (!out) return fail(TT_EINVAL, "tt_pop_td3_create: out is NULL");
+    *out = nullptr;
+    if (count < 1 || count > TT_POP_MAX_AGENTS) return fail(TT_EINVAL, "tt_pop_td3_create: count = %d agents, not in [1, %d]", count, TT_POP_MAX_AGENTS);
+    if (batch < 1 || batch > MAXB) return fail(TT_EINVAL, "tt_pop_td3_create: batch = %d rows, not in [1, %d]", batch, MAXB);
+    if (!agents) return fail(TT_EINVAL, "tt_pop_td3_create: agents is NULL");
+    std::vector<Td3Agent> host(count);
+    for (int a = 0; a < count; ++a) {
+        const int rc = to_td3_agent(agents[a], a, batch, host[a]);
+        if (rc != TT_OK) return rc;
+    }
+    for (int a = 0; a < count; ++a)
+        for (int b = a + 1; b < count; ++b) {
+            const Owned x = owned_of(host[a]), y = owned_of(host[b]);
+            if (overlap(x.steps, y.steps)) return fail(TT_EINVAL, "tt_pop_td3_create: agents %d and %d share a step counter", a, b);
+            if (x.tail == y.tail) return fail(TT_EINVAL, "tt_pop_td3_create: agents %d and %d share their tail words", a, b);
+            if (overlap(x.rows, y.rows)) return fail(TT_EINVAL, "tt_pop_td3_create: agents %d and %d share a per-row workspace", a, b);
+            if (overlap(x.grads, y.grads)) return fail(TT_EINVAL, "tt_pop_td3_create: agents %d and %d share a gradient buffer", a, b);
+        }
+    Td3Agent *dev = nullptr;
+    if (hipMalloc(&dev, sizeof(Td3Agent) * count) != hipSuccess) return fail(TT_ENOMEM, "tt_pop_td3_create: hipMalloc");
+    if (hipMemcpy(dev, host.data(), sizeof(Td3Agent) * count, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(dev);
+        return fail(TT_EHIP, "tt_pop_td3_create: hipMemcpy");
+    }
+    *out = new tt_pop_td3{count, batch, dev};
+    return TT_OK;
+}
+
+int tt_pop_td3_learn(tt_pop_td3 *h, int update, int full, tt_stream_t stream) {
+    if (update < 0) return fail(TT_EINVAL, "tt_pop_td3_learn: update = %d < 0", update);
+    if (!h) return fail(TT_EINVAL, "tt_pop_td3_learn: handle is NULL");
+    const int K = h->K, nb = (h->n + TR - 1) / TR, f = full ? 1 : 0;
+    hipLaunchKernelGGL(k_pop_td3_fwd_multi, dim3(K * (f ? 6 : 5) * nb), dim3(64 * NW), 0, stream, K, h->dev, update, f);
+    hipLaunchKernelGGL(k_pop_td3_bwd_rows, dim3(K * ((f ? 3 : 2) * nb + 1)), dim3(64 * NW), 0, stream, K, h->dev, update, f);
+    hipLaunchKernelGGL(k_pop_td3_bwd_weights, dim3(K * 2 * WG_CRITIC_WEIGHTS), dim3(256), 0, stream, K, h->dev, update, f);
+    if (f) hipLaunchKernelGGL(k_pop_td3_actor_tail, dim3(K * nb + K * WG_ACTOR_WEIGHTS), dim3(64 * NW), 0, stream, K, h->dev, update, f);
+    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_td3_exploit(tt_pop_td3 *h, int pairs, const tt_pop_td3_pair *list, tt_stream_t stream) {
+    static const char who[] = "tt_pop_td3_exploit";
+    if (!h) return fail(TT_EINVAL, "%s: handle is NULL", who);
+    if (!list) return fail(TT_EINVAL, "%s: list is NULL", who);
+    const int K = h->K;
+    if (pairs < 1 || pairs > K) return fail(TT_EINVAL, "%s: pairs = %d, not in [1, K = %d]", who, pairs, K);
+    Exploit3List L{};
+    L.n = pairs;
+    for (int i = 0; i < pairs; ++i) {
+        const tt_pop_td3_pair &q = list[i];
+        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K) return fail(TT_EINVAL, "%s: pair %d names an agent outside [0, K = %d)", who, i, K);
+        for (int j = 0; j < pairs; ++j) {
+            if (j == i) continue;
+            if (list[j].dst == q.dst) return fail(TT_EINVAL, "%s: pairs %d and %d have the same dst", who, i, j);
+            if (list[j].src == q.dst) return fail(TT_EINVAL, "%s: the dst of pair %d is the src of pair %d", who, i, j);
+        }
+        const float h6[6] = {q.alpha, q.beta, q.tau, q.gamma, q.target_noise, q.noise_clip};
+        for (const float x : h6)
+            if (!std::isfinite(x)) return fail(TT_EINVAL, "%s: pair %d has a non-finite hyperparameter", who, i);
+        if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
+            return fail(TT_EINVAL, "%s: pair %d: alpha and beta must lie in (0, 1]", who, i);
+        if (!(q.tau > 0.f && q.tau <= 1.f)) return fail(TT_EINVAL, "%s: pair %d: tau must lie in (0, 1]", who, i);
+        if (!(q.gamma > 0.f && q.gamma < 1.f)) return fail(TT_EINVAL, "%s: pair %d: gamma must lie in (0, 1)", who, i);
+        if (q.target_noise < 0.f || q.noise_clip < 0.f) return fail(TT_EINVAL, "%s: pair %d: target_noise and noise_clip must not be negative", who, i);
+        L.p[i] = q;
+    }
+    hipLaunchKernelGGL(k_pop_td3_exploit, dim3(pairs * X3_CHUNKS), dim3(X3_THREADS), 0, stream, L, h->dev);
+    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+int tt_pop_td3_hyper(tt_pop_td3 *h, int agent, float out[6]) {
+    if (!h) return fail(TT_EINVAL, "tt_pop_td3_hyper: handle is NULL");
+    if (!out) return fail(TT_EINVAL, "tt_pop_td3_hyper: out is NULL");
+    if (agent < 0 || agent >= h->K) return fail(TT_EINVAL, "tt_pop_td3_hyper: agent %d is not in [0, K = %d)", agent, h->K);
+    Td3Agent P;
+    if (hipMemcpy(&P, h->dev + agent, sizeof P, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TT_EHIP, "tt_pop_td3_hyper: hipMemcpy");
+    out[0] = P.Aa.lr;
+    out[1] = P.Ac[0][0].lr;
+    out[2] = P.Aa.tau;
+    out[3] = P.gamma;
+    out[4] = P.sigma;
+    out[5] = P.clip;
+    return TT_OK;
+}
+
+int tt_pop_td3_destroy(tt_pop_td3 *h) {
+    if (!h) return TT_OK;
+    const hipError_t e = hipFree(h->dev);
+    delete h;
+    return e == hipSuccess ? TT_OK : TT_EHIP;
+}
+
+}  // extern "C"

@@ -15,6 +15,11 @@ discount gamma ** n travels by value (fused_learn.nstep_discount, the lone learn
 table its first launch is the n-step kernel for good -- also at n = 1, the one-step draw bit for bit -- so exploit() may change
 an agent's n under captured graphs.  A population built without n-step arguments launches the four one-step kernels.
 
+With td3= (one td3.TD3Config, or one per agent with equal policy_delay) every agent is a TD3 agent -- six networks, its own
+target_noise and noise_clip -- and a population update is the shared TD3 launches of csrc/ttpop_td3.hip (td3.PopulationTD3Learner,
+DESIGN.md section 17): update u of a vector step is a full one when (u + 1) % policy_delay == 0, as in a lone TD3 loop, whose bits
+agent a keeps.  exploit() then also copies the second critic and carries the two noise values.  Not with n-step returns or a learn log.
+
 Out of scope: the pipelined order, data-parallel populations, expert side buffers (with any n), whole-population checkpoints
 (an agent's weights save through agents[a].save_models())."""
 import ctypes as C
@@ -216,6 +221,10 @@ def _no_records():
     return out
 
 
+def _listed(x):
+    return list(x) if isinstance(x, (list, tuple)) else [x]
+
+
 def _per_agent(x, K, name):
     if isinstance(x, (list, tuple)):
         if len(x) != K:
@@ -238,8 +247,13 @@ class PopulationRollout:
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
-                 learn_log_every=1):
+                 learn_log_every=1, td3=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+        if td3 is not None:            # (before anything else: each refusal names its option)
+            from ddpg_trucktrailer_amd.td3 import check_population_td3
+            td3 = check_population_td3(td3, len(seeds), updates_per_step, _listed(n_step), 1 if n_step_max is None else n_step_max,
+                                       learn_log, device)
+        self.td3 = td3                 # None, or the K TD3Configs
         if learn_log is not None:
             check_learn_log(learn_log, learn_log_every)
             if torch.device(device).type != "cuda":
@@ -272,14 +286,21 @@ class PopulationRollout:
             env.reset(seed=self.seeds[a])
             lp = VectorStepper(env, batch_size=self.batch_size, replay_slots=replay_slots, seed=self.seeds[a], alpha=alphas[a],
                                beta=betas[a], tau=taus[a], gamma=gammas[a], episode_log=episode_log,
-                               episode_log_detail=episode_log_detail)
+                               episode_log_detail=episode_log_detail, td3=None if td3 is None else td3[a])
             if not lp.ring_mode:
                 raise RuntimeError("a population needs the fused policy and ring-addressed steps (reference-shaped actor on a GPU)")
             self.loops.append(lp)
         self.agents = [lp.agent for lp in self.loops]
-        self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
-                                         seeds=self.seeds, n_steps=n_steps if nstep else None, learn_log=learn_log,
-                                         learn_log_every=learn_log_every)
+        if td3 is not None:
+            from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner
+            self.policy_delay = td3[0].policy_delay
+            # (agent a's smoothing noise is keyed by seeds[a], what a lone loop uses)
+            self.learner = PopulationTD3Learner(self.agents, self.batch_size, [lp.ring for lp in self.loops], self.seeds,
+                                                fc2_images=fc2_images)
+        else:
+            self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
+                                             seeds=self.seeds, n_steps=n_steps if nstep else None, learn_log=learn_log,
+                                             learn_log_every=learn_log_every)
         self._learn_from, self._warm_steps = learn_start(self.n_step_max)      # (the largest n decides for every agent)
         self.graph_steps = int(graph_steps) if graph_steps else 0
         self.graph1 = self.graphG = self._graph_key = None
@@ -295,7 +316,10 @@ class PopulationRollout:
             lp.open_step()
             lp.act_and_step()
         for u in range(self.updates_per_step if learn else 0):
-            self.learner.learn(u)
+            if self.td3 is not None:       # (the delay is counted inside the vector step, as in a lone TD3 loop)
+                self.learner.learn(u, full=(u + 1) % self.policy_delay == 0)
+            else:
+                self.learner.learn(u)
 
     def _advance(self, steps):
         for lp in self.loops:
@@ -368,13 +392,21 @@ class PopulationRollout:
 
     def drain_learn_log(self):
         """[agent: its learn-log records since the last drain (PopulationLearner.drain_learn_log)]."""
+        if self.td3 is not None:
+            raise ValueError("the learn log is off (td3: learn_log is not supported)")
         return self.learner.drain_learn_log()
 
     def exploit(self, pairs):
         """PBT's exploit/explore step between vector steps, eagerly (PopulationLearner.exploit): pairs = [(dst, src, {"alpha",
         "beta", "tau", "gamma"[, "n_step"]})].  The captured graphs stay as they are: the descriptors and the n-step table they
-        read change in place, no storage moves, and dst's fc2 images arrive with its weights."""
+        read change in place, no storage moves, and dst's fc2 images arrive with its weights.
+        With td3 a pair's dict may hold six keys -- the four above, "target_noise" and "noise_clip" (a missing key: src's value) --
+        and the copy is of six networks and three moment pairs (td3.PopulationTD3Learner.exploit); an "n_step" other than 1 is a
+        ValueError there: n-step returns are not supported with td3, so n_step_max has nothing to check."""
         pairs = list(pairs)
+        if self.td3 is not None:       # (PopulationTD3Learner.exploit: six networks, and the noise values travel with src's)
+            self.learner.exploit(pairs)
+            return
         for i, (dst, src, hyp) in enumerate(pairs):
             n = int(hyp.get("n_step", self.learner.n_steps[int(src)]))
             if n > self.n_step_max:
@@ -387,4 +419,4 @@ class PopulationRollout:
     @property
     def n_steps(self):
         """Per agent, the n of its draws now (the host mirror of the device table)."""
-        return list(self.learner.n_steps)
+        return [1] * self.K if self.td3 is not None else list(self.learner.n_steps)

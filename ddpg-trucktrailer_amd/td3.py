@@ -4,6 +4,8 @@
     TD3Config      policy_delay, target_noise, noise_clip -- the noise in the actor's normalised action units (mu in [-1, 1])
     check_td3      every combination the loop refuses with TD3, as one pure function
     TD3Learner     FusedLearner for six networks and two critics: one update is three launches (critic-only) or four (full)
+    PopulationTD3Learner   K TD3Learners whose updates share those launches (csrc/ttpop_td3.hip), with PBT's
+                   exploit step for six networks
 
 The torch form of the same update is Agent(td3=cfg).learn_batch (agent.py): the CPU path, and the twin the kernels are tested against."""
 import ctypes as C
@@ -116,9 +118,9 @@ class TD3Learner(FusedLearner):
         return tuple(p.data_ptr() for n in self._nets() for p in n.parameters())
 
     # ---- the descriptor ------------------------------------------------------------------------------------------
-    def _create(self):
-        """Make the descriptor, or -- when there is one -- write the new description over it IN PLACE (tt_td3_update): captured
-        launches hold the descriptor's device address by value, so it is never freed while the learner lives."""
+    def _describe(self):
+        """(the TTTd3Agent description of this learner, the ctypes objects it points into): what tt_td3_create / tt_td3_update and
+        a population's tt_pop_td3_create copy.  The second value must live until that call has returned."""
         from ddpg_trucktrailer_amd.rollout import _SEED_STRIDE
         ag, B = self.agent, self.B
         sample = self.ring.sample_args(B, seed=self.seed, seed_stride=_SEED_STRIDE)
@@ -151,12 +153,19 @@ class TD3Learner(FusedLearner):
                             self.eps.data_ptr(), self.y2.data_ptr(), self.q2t.data_ptr(), self.step_snap.data_ptr(),
                             self.actor_step_dev.data_ptr(), self.actor_bias_corr.data_ptr(), self.q_pi.data_ptr(),
                             self.dq_da.data_ptr(), self.tail_words.data_ptr(), self.tail_gave_up_host.data_ptr())
+        return desc, (sample, jobs, td, nets)
+
+    def _create(self):
+        """Make the descriptor, or -- when there is one -- write the new description over it IN PLACE (tt_td3_update): captured
+        launches hold the descriptor's device address by value, so it is never freed while the learner lives."""
+        desc, keep = self._describe()
         if self._h is None:
             h = C.c_void_p()
-            L.check(self.lib.tt_td3_create(B, C.byref(desc), C.byref(h)))      # (copies everything)
+            L.check(self.lib.tt_td3_create(self.B, C.byref(desc), C.byref(h)))      # (copies everything)
             self._h = h
         else:
             L.check(self.lib.tt_td3_update(self._h, C.byref(desc)))            # (waits for the device, then copies)
+        del keep
         self._key = self._storage_key()
 
     def set_noise_seed(self, noise_seed):
@@ -238,3 +247,170 @@ class TD3Learner(FusedLearner):
                     m.copy_(s["exp_avg"].reshape(-1)); v.copy_(s["exp_avg_sq"].reshape(-1))
                     step_dev.fill_(int(float(s["step"])))
         self.tail_words.fill_(-1)
+
+
+HYPERS6 = ("alpha", "beta", "tau", "gamma", "target_noise", "noise_clip")
+
+
+class PopulationTD3Learner:
+    """The TD3 updates of K agents launched together (include/ttenv.h: tt_pop_td3_*): each agent has the state of a TD3Learner of
+    its own -- buffers, Adam moments, both step counts, tail words, fc2 images, checkpoint format -- and those learners never make
+    lone descriptors; the population's one handle is made at the first eager learn(), from then on every buffer and parameter
+    storage must stay where it is.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys; noise_seeds: the
+    seeds of the smoothing noise (None: the sampling seeds, as in a lone loop).  agents[a].td3 holds agent a's target_noise and
+    noise_clip; policy_delay is one value for all, since `full` is an argument of the shared launches."""
+
+    def __init__(self, agents, batch_size, rings, seeds, noise_seeds=None, fc2_images=None):
+        self.K, self.B = len(agents), int(batch_size)
+        if not 1 <= self.K <= L.POP_MAX_AGENTS:
+            raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
+        if rings is None or seeds is None or len(rings) != self.K or len(seeds) != self.K:
+            raise ValueError("one ring and one seed per agent")
+        if noise_seeds is not None and len(noise_seeds) != self.K:
+            raise ValueError("one noise seed per agent")
+        if any(getattr(ag, "td3", None) is None for ag in agents):
+            raise ValueError("PopulationTD3Learner needs agents built with Agent(td3=TD3Config(...))")
+        self.policy_delay = same_policy_delay([ag.td3 for ag in agents])
+        self.lib = L.load()
+        self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
+        self.learners = [TD3Learner(ag, self.B, ring, seed, fc2_images, None if noise_seeds is None else noise_seeds[a])
+                         for a, (ag, ring, seed) in enumerate(zip(self.agents, self.rings, self.seeds))]
+        for ag, fl in zip(self.agents, self.learners):
+            ag.fused_learner = fl          # (checkpoint.py exports the moments through it)
+        self.updates = 0                   # learn() calls, for the delay when `full` is left to this learner
+        self._h = self._key = None
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and L._lib is not None:
+            torch.cuda.synchronize()
+            L._lib.tt_pop_td3_destroy(self._h)
+        self._h = None
+
+    def _storage_key(self):
+        return tuple(k for fl in self.learners for k in fl._storage_key())
+
+    def _create(self):
+        arr, keep = (L.TTTd3Agent * self.K)(), []
+        for a, fl in enumerate(self.learners):
+            desc, objs = fl._describe()
+            arr[a] = desc
+            keep += [desc, objs]
+        h = C.c_void_p()
+        L.check(self.lib.tt_pop_td3_create(self.K, self.B, arr, C.byref(h)))      # (copies everything: `keep` may go now)
+        self._h, self._key = h, self._storage_key()
+
+    def refresh_images(self):
+        for fl in self.learners:
+            FusedLearner.refresh_images(fl)        # (the images alone: TD3Learner's own would make a lone descriptor)
+
+    def learn(self, u=0, full=None):
+        """Update u of the running vector step for every agent, enqueued on the current stream (capturable once created).  full:
+        None = every policy_delay-th learn() by this learner's own count, as TD3Learner counts; else this update is full (True) or
+        critic-only (False) for the whole population."""
+        capturing = torch.cuda.is_current_stream_capturing()
+        if self._h is None:
+            if capturing:
+                raise RuntimeError("PopulationTD3Learner: run one eager learn() before capturing it")
+            self.refresh_images()
+            self._create()
+        else:
+            if self._key != self._storage_key():
+                raise RuntimeError("PopulationTD3Learner: a network's parameter storage moved since the descriptors were made")
+            if not capturing:
+                self.refresh_images()
+        self.updates += 1
+        if full is None:
+            full = self.updates % self.policy_delay == 0
+        L.check(self.lib.tt_pop_td3_learn(self._h, int(u), 1 if full else 0, L.stream()))
+
+    def tail_gave_up(self):
+        """[agent: 0, or the actor step whose tail hand-over was abandoned] (host memory only)."""
+        return [fl.tail_gave_up() for fl in self.learners]
+
+    def state_dict(self, a):
+        """Agent a's Adam moments and step counts, in TD3Learner.state_dict()'s format."""
+        return self.learners[a].state_dict()
+
+    def _need_handle(self, what):
+        if self._h is None:
+            raise RuntimeError(f"PopulationTD3Learner.{what}: no learn() has made the population's descriptors yet")
+
+    def exploit(self, pairs):
+        """PBT's exploit/explore step (include/ttenv.h: tt_pop_td3_exploit), one launch on the current stream: pairs = [(dst, src,
+        {"alpha", "beta", "tau", "gamma", "target_noise", "noise_clip"})].  dst != src: dst's six networks, three Adam moment pairs
+        and fc2 images become src's; every dst then takes the given hyperparameters (a missing key: src's value).  The host mirrors
+        -- agent.alpha / beta / tau / gamma, the three torch optimizers' lr, hyp_actor / hyp_critic / hyp_critic_2 and the
+        learner's TD3Config noise values -- follow.  Captured launches stay valid: the descriptors change in place."""
+        self._need_handle("exploit")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("PopulationTD3Learner.exploit: not while capturing (it runs between vector steps)")
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= self.K:
+            raise ValueError(f"exploit: 1 to {self.K} pairs, not {len(pairs)}")
+        self.refresh_images()          # (src's images must hold its weights: they are copied with them)
+        arr, new = (L.TTPopTd3Pair * len(pairs))(), []
+        for i, (dst, src, hyp) in enumerate(pairs):
+            dst, src = int(dst), int(src)
+            if not (0 <= dst < self.K and 0 <= src < self.K):
+                raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
+            if int(hyp.get("n_step", 1)) != 1:
+                raise ValueError(f"exploit: pair {i} sets n_step = {hyp['n_step']}: n-step returns are not supported with td3")
+            of_src = {k: getattr(self.agents[src], k) for k in HYPERS6[:4]}
+            of_src["target_noise"], of_src["noise_clip"] = self.learners[src].cfg.target_noise, self.learners[src].cfg.noise_clip
+            h = {k: float(hyp.get(k, of_src[k])) for k in HYPERS6}
+            arr[i] = L.TTPopTd3Pair(dst, src, *[h[k] for k in HYPERS6])
+            new.append((dst, h))
+        L.check(self.lib.tt_pop_td3_exploit(self._h, len(pairs), arr, L.stream()))
+        for dst, h in new:
+            ag, fl = self.agents[dst], self.learners[dst]
+            ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
+            ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
+            ag.critic.optimizer.param_groups[0]["lr"] = ag.critic_2.optimizer.param_groups[0]["lr"] = h["beta"]
+            fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
+            fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
+            fl.hyp_critic_2 = (h["beta"],) + tuple(fl.hyp_critic_2[1:])
+            fl.cfg = ag.td3 = TD3Config(self.policy_delay, h["target_noise"], h["noise_clip"])
+
+    def hyper(self, a):
+        """Agent a's {"alpha", "beta", "tau", "gamma", "target_noise", "noise_clip"} as the device descriptors hold them
+        (synchronises)."""
+        self._need_handle("hyper")
+        out = (C.c_float * 6)()
+        torch.cuda.synchronize()
+        L.check(self.lib.tt_pop_td3_hyper(self._h, int(a), C.byref(out)))
+        return dict(zip(HYPERS6, (float(x) for x in out)))
+
+
+def same_policy_delay(cfgs):
+    """The one policy_delay of a population's TD3Configs, or ValueError: `full` is an argument of the shared launches."""
+    delays = sorted({c.policy_delay for c in cfgs})
+    if len(delays) != 1:
+        raise ValueError(f"td3: a population has one policy_delay, not {delays} (target_noise and noise_clip may differ per agent)")
+    return delays[0]
+
+
+def check_population_td3(td3, K, updates_per_step=1, n_steps=(1,), n_step_max=1, learn_log=None, device="cuda:0"):
+    """What PopulationRollout(td3=...) refuses, each a ValueError that names the option; returns the K TD3Configs.  td3: one
+    TD3Config for every agent, or a list of K with equal policy_delay."""
+    if isinstance(td3, (list, tuple)):
+        if len(td3) != K:
+            raise ValueError(f"td3: {len(td3)} configurations for {K} agents")
+        cfgs = list(td3)
+    else:
+        cfgs = [td3] * K
+    for c in cfgs:
+        if not isinstance(c, TD3Config):
+            raise ValueError(f"td3 = {c!r} is not a TD3Config")
+    delay = same_policy_delay(cfgs)
+    if int(updates_per_step) % delay != 0:
+        raise ValueError(f"td3: updates_per_step = {updates_per_step} is not a multiple of policy_delay = {delay} (the delay is "
+                         "counted inside a vector step)")
+    if any(int(n) > 1 for n in n_steps):
+        raise ValueError(f"td3: n_step = {list(n_steps)} > 1 is not supported")
+    if int(n_step_max) > 1:
+        raise ValueError(f"td3: n_step_max = {n_step_max} > 1 is not supported")
+    if learn_log is not None:
+        raise ValueError("td3: learn_log is not supported")
+    if torch.device(device).type != "cuda":
+        raise ValueError(f"td3: device = {device!r} is not supported: a population's TD3 update exists only as HIP kernels")
+    return cfgs

@@ -755,7 +755,7 @@ int tt_adam_soft_update_p2p(tt_p2p *x, int site, int count, float *const *params
                             const tt_fc2_images *images, const float *bias_corr, tt_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------------------
- * TD3 (Fujimoto, van Hoof, Meger 2018) in the fused learner (csrc/tttd3.hip): twin critics, target-policy smoothing, delayed
+ * TD3 (Fujimoto, van Hoof, Meger 2018) in the fused learner (csrc/tttd3.hip, csrc/tttd3.h): twin critics, target-policy smoothing, delayed
  * actor and target updates, for one agent with the reference-shaped networks and a batch B <= 1024 drawn from its ring.
  * One update, with t = the critic updates done before it (*td->step_dev when the update starts):
  *   mu' = target_actor(s');  eps_b = clip(target_noise * N_b, -noise_clip, noise_clip), N_b standard normal from Philox4x32-10 and
@@ -807,6 +807,40 @@ int tt_td3_create(int batch, const tt_td3_agent *agent, tt_td3 **out);
 int tt_td3_update(tt_td3 *h, const tt_td3_agent *agent);
 int tt_td3_learn(tt_td3 *h, int update, int full, tt_stream_t stream);       /* one update, enqueued on stream */
 int tt_td3_destroy(tt_td3 *h);                                               /* the caller's stream work with it must be done */
+
+/* ------------------------------------------------------------------------------------------------------
+ * TD3 for a population (csrc/ttpop_td3.hip): the TD3 updates of K independent agents (K <= TT_POP_MAX_AGENTS, one batch size
+ * B <= 1024 for all) in the launches of ONE agent's tt_td3_learn -- three on a critic-only update, four on a full one -- each
+ * launch running every agent's workgroups.  Agent a's results are the bits of tt_td3_learn made with agent a's description.
+ * agents[a] is a tt_td3_agent as tt_td3_create takes it, and every check of tt_td3_create is made per agent; the library copies the
+ * descriptions into device memory (every pointer must stay valid and fixed for the handle's life), so tt_pop_td3_learn makes no
+ * host work per call and can be captured.  `full` is an argument of the launches: the delay is one value for the whole population.
+ * target_noise, noise_clip, the learning rates, tau and gamma are each agent's own.  The tail launch of a full update dispatches the
+ * row workgroups of ALL agents before any weight workgroup that waits for them; each agent's hand-over words and gave_up_host are
+ * its own, and its epoch is its own *actor_step_dev.
+ * tt_pop_td3_exploit is tt_pop_exploit for six networks, ONE launch for a list of pairs.  dst != src: dst's six networks, the three
+ * Adam moment pairs (critic 1, critic 2, actor) and every fc2 image the descriptions hold become src's.  Every dst then takes the
+ * pair's six hyperparameters: alpha (the actor's learning rate), beta (both critics'), tau (all three soft updates; the tau = 0 of
+ * critic-only updates stays 0), gamma, target_noise and noise_clip.  Nothing else of dst moves: both step counts, both
+ * bias-correction buffers, step_snapshot, tail words, batch buffers, ring, env and noise seed stay its own.  The new values live in
+ * the descriptors tt_pop_td3_learn reads, in place: launches captured before stay valid and see them.  list is a HOST array, copied
+ * into the launch's arguments.  tt_pop_td3_hyper reads agent a's {alpha, beta, tau, gamma, target_noise, noise_clip} back from
+ * the device (synchronous).
+ * TT_EINVAL with a message that names the entry point and the agent or pair, before any HIP call: a NULL handle, array or out;
+ * count outside 1 .. TT_POP_MAX_AGENTS; batch outside 1 .. 1024; whatever tt_td3_create refuses in an agent; two agents that share
+ * a step counter, their tail words, a per-row workspace or a gradient buffer; update < 0; pairs outside [1, K]; an agent index out
+ * of range; two pairs with the same dst; a dst that is the src of another pair; a non-finite value; alpha, beta or tau outside
+ * (0, 1]; gamma outside (0, 1); a negative target_noise or noise_clip. */
+typedef struct tt_pop_td3 tt_pop_td3;
+typedef struct tt_pop_td3_pair {
+    int32_t dst, src;
+    float alpha, beta, tau, gamma, target_noise, noise_clip;
+} tt_pop_td3_pair;
+int tt_pop_td3_create(int count, int batch, const tt_td3_agent *agents /*[count]*/, tt_pop_td3 **out);
+int tt_pop_td3_learn(tt_pop_td3 *pop, int update, int full, tt_stream_t stream);   /* one update of every agent, enqueued on stream */
+int tt_pop_td3_exploit(tt_pop_td3 *pop, int pairs, const tt_pop_td3_pair *list /*[pairs], host*/, tt_stream_t stream);
+int tt_pop_td3_hyper(tt_pop_td3 *pop, int agent, float out[6]);
+int tt_pop_td3_destroy(tt_pop_td3 *pop);                                     /* the caller's stream work with it must be done */
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,383 @@
+"""GPU (-m gpu): TD3 for populations (csrc/ttpop_td3.hip, td3.PopulationTD3Learner, PopulationRollout(td3=)) against lone TD3.
+
+A population update must give every agent the bits of a lone TD3Learner's update (csrc/tttd3.hip) -- first, middle and last agent,
+a partial last row block, critic-only and full updates, per-agent smoothing noise; the population loop must give every agent the
+bits of a lone DDPGRollout(td3=); an exploit must copy six networks, three moment pairs and every fc2 image and nothing else, under
+graphs captured before it; and pbt.PBT must drive a TD3 population unchanged.  The shapes are the smallest that exercise the index
+arithmetic; no test waits for anything."""
+import types
+
+import pytest
+
+import learn_ref as R
+import td3_ref as T
+
+pytestmark = pytest.mark.gpu
+
+
+def _cfg(*a, **kw):
+    from ddpg_trucktrailer_amd.td3 import TD3Config
+    return TD3Config(*a, **kw)
+
+
+def _equal(x, y):
+    import torch
+    return len(x) == len(y) and all(torch.equal(a, b) for a, b in zip(x, y))
+
+
+def _first_difference(x, y):
+    import torch
+    return next((i for i, (a, b) in enumerate(zip(x, y)) if not torch.equal(a, b)), None)
+
+
+@pytest.fixture(scope="module")
+def trained_states():
+    """Three trained-scale TD3 states (learn_ref's scale 20, three warm steps, critic step 999, actor step 499; distinct critics)
+    from three seeds, made once and never written to."""
+    out = []
+    for seed in (T.SEED, T.SEED + 10, T.SEED + 20):
+        st = T.make_td3_state(seed, 20.0, 3)
+        st["step"], st["actor_step"] = 999, 499
+        out.append(st)
+    return out
+
+
+def _fresh_state(seed):
+    st = T.make_td3_state(seed, 1.0, 0)
+    st["step"], st["actor_step"] = 0, 0
+    return st
+
+
+def _batch(B, seed):
+    import torch
+    return R._candidates(B, torch.Generator().manual_seed(seed))
+
+
+def _nets_of(fl):
+    return fl._nets()
+
+
+def _learning_state(fl):
+    """What an exploit copies: six networks, three moment pairs, every fc2 image."""
+    out = [p.detach().clone() for n in _nets_of(fl) for p in n.parameters()]
+    out += [t.clone() for st in (fl.actor, fl.critic, fl.critic_2) for t in (st.m, st.v)]
+    if fl.use_images:
+        out += [fl._img[id(n)].clone() for n in _nets_of(fl)]
+    return out
+
+
+def _frozen_on_critic_only(fl):
+    """What a critic-only update leaves alone: the actor, its moments and step, the three targets (and their images)."""
+    ag = fl.agent
+    targets = (ag.target_actor, ag.target_critic, ag.target_critic_2)
+    out = [p.detach().clone() for n in (ag.actor,) + targets for p in n.parameters()]
+    out += [fl.actor.m.clone(), fl.actor.v.clone(), fl.actor_step_dev.clone()]
+    if fl.use_images:
+        out += [fl._img[id(n)].clone() for n in targets]
+    return out
+
+
+def _results(fl, full):
+    """Everything an update leaves: _learning_state, three flat gradients, the per-row outputs, both step counts.  mu, q_pi and
+    dq_da are written by full updates only."""
+    out = _learning_state(fl) + [st.flat_grad.clone() for st in (fl.critic, fl.critic_2, fl.actor)]
+    out += [t.clone() for t in (fl.y, fl.y2, fl.q, fl.q2, fl.q1t, fl.q2t, fl.eps, fl.step_dev, fl.actor_step_dev)]
+    if full:
+        out += [t.clone() for t in (fl.mu, fl.q_pi, fl.dq_da)]
+    return out
+
+
+def _lone(dev, state, hyper, cfg, batch, images, noise_seed):
+    from test_gpu_td3 import _td3_learner
+    return _td3_learner(dev, state, hyper, cfg, batch, images, noise_seed=noise_seed)[1]
+
+
+def _population(dev, states, hyper, cfgs, batches, images, noise_seeds):
+    """A PopulationTD3Learner whose agent a holds states[a] and draws batches[a] (tests/test_gpu_td3.py's _td3_learner, per agent)."""
+    import torch
+    from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner
+    from test_gpu_learn_shapes import _ring_with_batch
+    agents, rings, seeds = [], [], []
+    for state, cfg, batch in zip(states, cfgs, batches):
+        ring, seed = _ring_with_batch(dev, batch[0].shape[0], [t.to(dev).contiguous() for t in batch])
+        agents.append(T.load_td3_agent(state, hyper, cfg, dev, torch.float32))
+        rings.append(ring)
+        seeds.append(seed)
+    pop = PopulationTD3Learner(agents, batches[0][0].shape[0], rings, seeds, noise_seeds=noise_seeds, fc2_images=images)
+    for fl, state in zip(pop.learners, states):
+        fl.import_from_optimizers()
+        assert int(fl.step_dev.item()) == state["step"] and int(fl.actor_step_dev.item()) == state["actor_step"]
+        assert fl._h is None
+    return pop
+
+
+@pytest.mark.parametrize("K, B, images", [(3, 33, True), (1, 1, False)], ids=["K3-B33-images", "K1-B1-f32"])
+def test_a_population_update_is_k_lone_updates_bit_for_bit(gpu_device, trained_states, K, B, images):
+    """Delay 2, per-agent (sigma, c) = (0.2, 0.5), (0, 0.5), (0.1, 0.05): learn(0) (critic-only) and learn(1) (full) on the
+    population and on K lone TD3Learners from the same states, batches and noise seeds.  After each update everything the update
+    leaves is torch.equal, agent by agent; after the first the actor, its moments and step and the three targets keep their bits."""
+    import torch
+    dev = gpu_device
+    cfgs = [_cfg(2, 0.2, 0.5), _cfg(2, 0.0, 0.5), _cfg(2, 0.1, 0.05)][:K]
+    states, hyper = trained_states[:K], R.TRAINED_HYPER
+    batches = [_batch(B, 500 + a) for a in range(K)]
+    noise_seeds = [5 + a for a in range(K)]
+    pop = _population(dev, states, hyper, cfgs, batches, images, noise_seeds)
+    lone = [_lone(dev, states[a], hyper, cfgs[a], batches[a], images, noise_seeds[a]) for a in range(K)]
+    pop.refresh_images()
+    torch.cuda.synchronize()
+    start = [_frozen_on_critic_only(fl) for fl in pop.learners]
+    critics = [[p.detach().clone() for p in fl.agent.critic.parameters()] for fl in pop.learners]
+    for u, full in ((0, False), (1, True)):
+        pop.learn(u)
+        for fl in lone:
+            fl.learn_batch(u=u)
+        torch.cuda.synchronize()
+        assert pop.tail_gave_up() == [0] * K and [fl.tail_gave_up() for fl in lone] == [0] * K
+        for a in range(K):
+            got, want = _results(pop.learners[a], full), _results(lone[a], full)
+            assert all(torch.isfinite(t.float()).all() for t in want)
+            assert _equal(got, want), (u, a, _first_difference(got, want))
+            assert int(pop.learners[a].step_dev.item()) == 1000 + u and int(pop.learners[a].actor_step_dev.item()) == 499 + u
+            assert pop.learners[a]._h is None, "a population's learner made a lone descriptor"
+        if not full:
+            for a in range(K):
+                assert _equal(_frozen_on_critic_only(pop.learners[a]), start[a]), a
+                assert not any(torch.equal(x, y) for x, y in zip(pop.learners[a].agent.critic.parameters(), critics[a]))
+    if K > 1:      # the agents are apart: nobody read a neighbour's descriptor
+        assert not _equal(_learning_state(pop.learners[0]), _learning_state(pop.learners[1]))
+        assert pop.learners[1].eps.eq(0).all() and pop.learners[2].eps.abs().max().item() <= 0.05 + 1e-7
+        assert pop.learners[0].eps.abs().max().item() > 0.05
+    h = pop.hyper(K - 1)
+    assert h["target_noise"] == pytest.approx(cfgs[K - 1].target_noise) and h["noise_clip"] == pytest.approx(cfgs[K - 1].noise_clip)
+    assert pop.state_dict(0)["actor_step"] == 500 and pop.state_dict(0)["step"] == 1001
+
+
+def test_sixteen_agents_with_a_partial_block(gpu_device):
+    """K = 16, B = 17 (two row blocks, the second with one row), delay 1, one update: the largest agent-major grids.  Agents 0, 7
+    and 15 equal their lone learners bit for bit; all 16 results are finite."""
+    import torch
+    from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner, TD3Learner
+    from test_gpu_population import _ring
+    dev, K, B = gpu_device, 16, 17
+    cfg, hyper = _cfg(1, 0.2, 0.5), R.DEFAULT_HYPER
+    states = [_fresh_state(T.SEED + 3 * a) for a in range(K)]
+    seeds = [40 + a for a in range(K)]
+    agents = [T.load_td3_agent(st, hyper, cfg, dev, torch.float32) for st in states]
+    pop = PopulationTD3Learner(agents, B, [_ring(dev, 100 + a) for a in range(K)], seeds, fc2_images=True)
+    pop.learn(0)
+    torch.cuda.synchronize()
+    assert pop.tail_gave_up() == [0] * K
+    for a in (0, 7, 15):
+        fl = TD3Learner(T.load_td3_agent(states[a], hyper, cfg, dev, torch.float32), B, _ring(dev, 100 + a), seeds[a], fc2_images=True)
+        fl.learn_batch(u=0)
+        torch.cuda.synchronize()
+        got, want = _results(pop.learners[a], True), _results(fl, True)
+        assert fl.tail_gave_up() == 0 and _equal(got, want), (a, _first_difference(got, want))
+    for a, fl in enumerate(pop.learners):
+        assert all(torch.isfinite(t.float()).all() for t in _results(fl, True)), a
+        assert int(fl.step_dev.item()) == 1 and int(fl.actor_step_dev.item()) == 1
+
+
+# ---- the loop -------------------------------------------------------------------------------------------------------
+SEEDS = [11, 12, 13]
+LOOP = dict(batch_size=32, replay_slots=8, updates_per_step=2)
+
+
+def _pop_loop(graph_steps, n=64, **kw):
+    from ddpg_trucktrailer_amd.population import PopulationRollout
+    return PopulationRollout(n, SEEDS, graph_steps=graph_steps, td3=_cfg(2, 0.2, 0.5), **dict(LOOP, **kw))
+
+
+def _agent_state(pop, a):
+    """Agent a of a population as tests/test_gpu_td3.py's _loop_state sees a lone loop, and the ring's device cursor."""
+    from test_gpu_td3 import _loop_state
+    lp = pop.loops[a]
+    view = types.SimpleNamespace(agent=lp.agent, learner=pop.learner.learners[a], ring=lp.ring, noise=lp.noise, env=lp.env)
+    return _loop_state(view) + [lp.ring.k_dev]
+
+
+def test_population_loop_equals_lone_td3_loops_and_its_own_eager_steps(gpu_device):
+    """Ten vector steps: agent a of the graph-replayed population == DDPGRollout(pipeline=False, td3=) with seed a and the same
+    sizes -- six networks, three moment pairs, both counters, ring, OU noise, env -- and == the population stepped eagerly."""
+    import torch
+    from ddpg_trucktrailer_amd.rollout import DDPGRollout
+    from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner
+    from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+    from test_gpu_td3 import _loop_state
+    graphs, eager = _pop_loop(2), _pop_loop(0)
+    assert isinstance(graphs.learner, PopulationTD3Learner) and graphs.policy_delay == 2
+    graphs.run(10)
+    for _ in range(10):
+        eager.step()
+    torch.cuda.synchronize()
+    assert graphs.graph1 is not None and graphs.graphG is not None and eager.graph1 is None
+    assert graphs.learner.tail_gave_up() == [0] * 3 and graphs.vector_steps == graphs.k == 10
+    for a, seed in enumerate(SEEDS):
+        env = TruckTrailerVecEnv(64, device=gpu_device)
+        env.reset(seed=seed)
+        lone = DDPGRollout(env, seed=seed, graph_steps=2, pipeline=False, td3=_cfg(2, 0.2, 0.5), **LOOP)
+        lone.run(10)
+        torch.cuda.synchronize()
+        want = _loop_state(lone) + [lone.ring.k_dev]
+        got, stepped = _agent_state(graphs, a), _agent_state(eager, a)
+        assert all(torch.isfinite(t.float()).all() for t in want)
+        assert int(lone.learner.step_dev.item()) == 18 and int(lone.learner.actor_step_dev.item()) == 9
+        assert _equal(got, want), (a, "graphs against the lone loop", _first_difference(got, want))
+        assert _equal(got, stepped), (a, "graphs against eager steps", _first_difference(got, stepped))
+        env.close()
+
+
+def _own_state(pop, a):
+    """What an exploit must not touch of agent a: both step counts, both bias corrections, the snapshot, tail words, ring, env,
+    OU noise and the noise seed."""
+    lp, fl = pop.loops[a], pop.learner.learners[a]
+    return [t.clone() for t in (fl.step_dev, fl.actor_step_dev, fl.bias_corr, fl.actor_bias_corr, fl.step_snap, fl.tail_words,
+                                lp.ring.obs, lp.ring.act, lp.ring.rew, lp.ring.done, lp.ring.k_dev, lp.env.state, lp.noise.x)], fl.noise_seed
+
+
+def _f32(x):
+    import numpy as np
+    return float(np.float32(x))
+
+
+def test_exploit_copies_six_networks_under_captured_graphs(gpu_device):
+    """After 6 steps: exploit([(2, 0, {alpha, target_noise}), (1, 1, {gamma})]).  Agent 2 then holds agent 0's six networks,
+    moments and images and its own counters, ring, env and noise seed; hyper() and the host mirrors agree; agents 0 and 1 keep their
+    parameters; four more steps on the graphs captured BEFORE the exploit equal four eager steps of a twin with the same exploit."""
+    import torch
+    pairs = [(2, 0, {"alpha": 3e-4, "target_noise": 0.1}), (1, 1, {"gamma": 0.98})]
+    graphs, eager = _pop_loop(2), _pop_loop(0)
+    graphs.run(6)
+    for _ in range(6):
+        eager.step()
+    torch.cuda.synchronize()
+    g1, gG = graphs.graph1, graphs.graphG
+    assert g1 is not None and gG is not None
+    learners = graphs.learner.learners
+    before = [_learning_state(fl) for fl in learners]
+    own = [_own_state(graphs, a) for a in range(3)]
+    hyp = [graphs.hyper(a) for a in range(3)]
+    assert not _equal(before[2], before[0])
+    graphs.exploit(pairs)
+    eager.exploit(pairs)
+    torch.cuda.synchronize()
+    after = [_learning_state(fl) for fl in learners]
+    assert _equal(after[2], before[0]), ("dst is not src bit for bit", _first_difference(after[2], before[0]))
+    assert _equal(after[0], before[0]) and _equal(after[1], before[1]), "src, or a hyperparameters-only pair, moved tensors"
+    for a in range(3):
+        got, seed = _own_state(graphs, a)
+        assert _equal(got, own[a][0]) and seed == own[a][1] == SEEDS[a], a
+    want2 = dict(hyp[0], alpha=_f32(3e-4), target_noise=_f32(0.1))
+    assert graphs.hyper(2) == want2 and graphs.hyper(1) == dict(hyp[1], gamma=_f32(0.98)) and graphs.hyper(0) == hyp[0]
+    for a in (1, 2):        # the host mirrors
+        ag, fl, h = graphs.agents[a], learners[a], graphs.hyper(a)
+        for key in ("alpha", "beta", "tau", "gamma"):
+            assert _f32(getattr(ag, key)) == h[key], (a, key)
+        assert _f32(ag.actor.optimizer.param_groups[0]["lr"]) == h["alpha"] == _f32(fl.hyp_actor[0])
+        for net, hy in ((ag.critic, fl.hyp_critic), (ag.critic_2, fl.hyp_critic_2)):
+            assert _f32(net.optimizer.param_groups[0]["lr"]) == h["beta"] == _f32(hy[0])
+        assert (_f32(fl.cfg.target_noise), _f32(fl.cfg.noise_clip)) == (h["target_noise"], h["noise_clip"]) and fl.cfg.policy_delay == 2
+    graphs.run(4)
+    for _ in range(4):
+        eager.step()
+    torch.cuda.synchronize()
+    assert graphs.graph1 is g1 and graphs.graphG is gG, "an exploit made run() capture again"
+    assert graphs.learner.tail_gave_up() == [0] * 3 and eager.learner.tail_gave_up() == [0] * 3
+    for a in range(3):
+        got, want = _agent_state(graphs, a), _agent_state(eager, a)
+        assert all(torch.isfinite(t.float()).all() for t in got)
+        assert _equal(got, want), (a, _first_difference(got, want))
+    assert [graphs.hyper(a) for a in range(3)] == [eager.hyper(a) for a in range(3)]
+    assert not _equal(_learning_state(learners[2]), _learning_state(learners[0])), "agent 2 did not go its own way after the copy"
+
+
+def test_exploit_arguments_are_checked_on_a_live_handle(gpu_device):
+    """Every host refusal of tt_pop_td3_exploit and tt_pop_td3_hyper on a live K = 3 population: TT_EINVAL with a message that
+    starts with the entry point, before any launch -- afterwards every agent's learning state and hyperparameters are what they
+    were.  exploit() and hyper() before the first learn() raise."""
+    import ctypes as C
+    import torch
+    from ddpg_trucktrailer_amd import _lib as L
+    from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner
+    from test_gpu_population import _ring
+    dev, K, B = gpu_device, 3, 17
+    agents = [T.load_td3_agent(_fresh_state(T.SEED + a), R.DEFAULT_HYPER, _cfg(1, 0.2, 0.5), dev, torch.float32) for a in range(K)]
+    pop = PopulationTD3Learner(agents, B, [_ring(dev, 100 + a) for a in range(K)], [40 + a for a in range(K)])
+    ok = dict(alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, target_noise=0.2, noise_clip=0.5)
+    with pytest.raises(RuntimeError):
+        pop.exploit([(1, 0, ok)])
+    with pytest.raises(RuntimeError):
+        pop.hyper(0)
+    pop.learn(0)
+    torch.cuda.synchronize()
+    before, hyp = [_learning_state(fl) for fl in pop.learners], [pop.hyper(a) for a in range(K)]
+    dll, stream = pop.lib, L.stream()
+
+    def P(dst, src, **kw):
+        h = dict(ok, **kw)
+        return L.TTPopTd3Pair(dst, src, *[h[k] for k in ("alpha", "beta", "tau", "gamma", "target_noise", "noise_clip")])
+    inf, nan = float("inf"), float("nan")
+    bad = [([P(1, 0), P(2, 0), P(0, 0), P(0, 1)], "pairs = 4"),                               # pairs = K + 1
+           ([P(3, 0)], "outside"), ([P(1, -1)], "outside"), ([P(-1, 0)], "outside"),            # an index out of range
+           ([P(1, 0), P(1, 2)], "same dst"),                                                    # a duplicate dst
+           ([P(1, 0), P(2, 1)], "is the src"), ([P(1, 1), P(2, 1)], "is the src"),              # a dst that is another pair's src
+           ([P(1, 0, alpha=nan)], "non-finite"), ([P(1, 0, gamma=inf)], "non-finite"), ([P(1, 0, tau=-inf)], "non-finite"),
+           ([P(1, 0, target_noise=nan)], "non-finite"), ([P(1, 0, noise_clip=inf)], "non-finite"),
+           ([P(1, 0, alpha=0.0)], "alpha"), ([P(1, 0, beta=2.0)], "beta"), ([P(1, 0, tau=0.0)], "tau"), ([P(1, 0, tau=1.01)], "tau"),
+           ([P(1, 0, gamma=1.0)], "gamma"), ([P(1, 0, gamma=0.0)], "gamma"),
+           ([P(1, 0, target_noise=-0.1)], "target_noise"), ([P(1, 0, noise_clip=-0.5)], "noise_clip")]
+    for lst, word in bad:
+        arr = (L.TTPopTd3Pair * len(lst))(*lst)
+        assert dll.tt_pop_td3_exploit(pop._h, len(lst), arr, stream) == L.TT_EINVAL, word
+        msg = dll.tt_last_error(None).decode()
+        assert msg.startswith("tt_pop_td3_exploit: ") and word in msg, (word, msg)
+    one = (L.TTPopTd3Pair * 1)(P(1, 0))
+    assert dll.tt_pop_td3_exploit(pop._h, 0, one, stream) == L.TT_EINVAL and b"pairs = 0" in dll.tt_last_error(None)
+    assert dll.tt_pop_td3_exploit(pop._h, 1, None, stream) == L.TT_EINVAL and b"list is NULL" in dll.tt_last_error(None)
+    out = (C.c_float * 6)()
+    assert dll.tt_pop_td3_hyper(pop._h, K, C.byref(out)) == L.TT_EINVAL and b"agent 3" in dll.tt_last_error(None)
+    assert dll.tt_pop_td3_hyper(pop._h, -1, C.byref(out)) == L.TT_EINVAL
+    assert dll.tt_pop_td3_hyper(pop._h, 0, None) == L.TT_EINVAL and b"out is NULL" in dll.tt_last_error(None)
+    with pytest.raises(ValueError, match="n_step"):
+        pop.exploit([(1, 0, dict(ok, n_step=3))])
+    with pytest.raises(ValueError, match="outside"):
+        pop.exploit([(3, 0, ok)])
+    torch.cuda.synchronize()
+    assert all(_equal(x, _learning_state(fl)) for x, fl in zip(before, pop.learners))
+    assert [pop.hyper(a) for a in range(K)] == hyp and pop.tail_gave_up() == [0] * K
+
+
+def test_pbt_runs_on_a_td3_population(gpu_device):
+    """pbt.PBT(K = 3, ready = 4) over 12 steps of the loop above with the episode log on.  An episode's step budget is at least 75
+    steps and no start pose fails within 12, so left alone no episode ends in this test (measured: none of 3 x 64, none of
+    3 x 4096).  Every env's step counter is therefore set 3 short of its own budget before the first step
+    (TruckTrailerVecEnv.set_steps, the reference's `env.episode_steps = ...`): each agent's 64 first episodes end at vector step 3,
+    with returns of its own.  min_episodes = 16 of a window of 64 makes all three agents eligible at the first round (step 4),
+    and quantile 0.5 of three agents is one pair: the worst agent takes the best one's state.  dst then holds src's learning
+    state and explored hyperparameters with src's noise values, every agent stays finite and no hand-over is given up."""
+    import torch
+    from ddpg_trucktrailer_amd.pbt import PBT
+    pop = _pop_loop(2, episode_log=1 << 12)
+    for lp in pop.loops:
+        lp.env.set_steps((lp.env.episode()["max_episode_steps"] - 3).clamp_min(0))
+    pbt = PBT(3, 4, seed=1, quantile=0.5, window=64, min_episodes=16)
+    checked = 0
+    for _ in range(3):
+        pop.run(4)
+        out = pbt.step(pop, pop.drain_episodes())
+        print("PBT td3 population: step", pop.vector_steps, "episodes in the windows", [len(w) for w in pbt.windows], "decisions", len(out))
+        if out:
+            torch.cuda.synchronize()
+            for d in out:
+                s, t = pop.learner.learners[d["src"]], pop.learner.learners[d["dst"]]
+                assert _equal(_learning_state(t), _learning_state(s)), d
+                h = pop.hyper(d["dst"])
+                assert {k: h[k] for k in d["new"]} == {k: _f32(v) for k, v in d["new"].items()}
+                assert (h["target_noise"], h["noise_clip"]) == (_f32(0.2), _f32(0.5))
+            checked += len(out)
+    torch.cuda.synchronize()
+    assert checked >= 1 and len(pbt.history) == checked
+    assert pop.vector_steps == 12 and pop.learner.tail_gave_up() == [0] * 3
+    for ag in pop.agents:
+        assert all(torch.isfinite(p).all() for n in ag._nets() for p in n.parameters())

@@ -13,7 +13,12 @@ update of the one-step population (no table; two populations, two series), of n 
 variants interleaved within each leg; with --baseline-lib PATH (a libttenv.so built from another commit, loaded beside this one)
 that library's one-step population as well, also twice: the distance between two series of one library is the run-to-run spread
 the no-table path is held to.
-Usage: time_population.py [--legs 5] [--updates 1000] [--no-loop] [--loop-steps 60] [--n-step N [--ks 1,4,8] [--baseline-lib PATH]]"""
+--td3 [DELAY]: instead of all that, TD3 populations: K in {1, 2, 4, 8, 16} PopulationTD3Learners at B = 256
+and policy_delay DELAY (default 2: critic-only and full updates in alternation, the average update), beside the lone TD3Learner
+(tools/td3_cost.py's leg), all timed the same way in alternating legs; every leg is printed and, with --out, written to a file.
+Section 13's rule at K = 1: is the population's median within the lone median plus the lone legs' own max - min?
+Usage: time_population.py [--legs 5] [--updates 1000] [--no-loop] [--loop-steps 60] [--n-step N [--ks 1,4,8] [--baseline-lib PATH]]
+       time_population.py --td3 [DELAY] [--legs 3] [--updates 1000] [--per-graph 100] [--out profiles/population_td3_scaling.txt]"""
 import argparse
 import ctypes as C
 import os
@@ -122,6 +127,52 @@ def nstep_cost(a):
                 pop._h = None
 
 
+def td3_scaling(a):
+    """--td3: us per population update and agent-updates/s of TD3 populations, and the lone TD3Learner beside them."""
+    from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner, TD3Config, TD3Learner
+    delay, Ks = a.td3, (1, 2, 4, 8, 16)
+    assert a.per_graph % delay == 0, "whole delay periods per graph: the same share of full updates in every graph"
+    cfg = TD3Config(policy_delay=delay)
+    replays = max(1, -(-a.updates // a.per_graph))
+
+    def td3_agent(seed):
+        torch.manual_seed(seed)
+        return Agent(alpha=1e-4, beta=1e-3, input_dims=(23,), tau=1e-3, n_actions=1, batch_size=B, device=DEV, replay=False, td3=cfg)
+    made = {}
+    for K in Ks:
+        pop = PopulationTD3Learner([td3_agent(100 + i) for i in range(K)], B, [ring(200 + i) for i in range(K)],
+                                   [300 + i for i in range(K)])
+        made[K] = (pop, captured(lambda u, pop=pop: pop.learn(u, full=(u + 1) % delay == 0), a.per_graph))
+    fl = TD3Learner(td3_agent(100), B, ring(200), 300)
+    made["lone"] = (fl, captured(lambda u: fl.learn_batch(u=u, full=(u + 1) % delay == 0), a.per_graph))
+    names = ("lone",) + Ks
+    res = {k: [] for k in names}
+    for leg in range(a.legs):
+        for k in (names if leg % 2 == 0 else names[::-1]):
+            res[k].append(timed(made[k][1], replays) / (replays * a.per_graph))
+    for K in Ks:
+        assert made[K][0].tail_gave_up() == [0] * K
+    assert fl.tail_gave_up() == 0
+    lines = [f"# TD3 learn() alone, B = {B}, policy_delay {delay}, {replays * a.per_graph} graph-replayed updates per leg ({a.per_graph} per "
+             f"graph), {a.legs} legs (order alternating), rings of 16 slots x 2048 envs, 5 % done flags",
+             f"# device {torch.cuda.get_device_name(0)}",
+             f"{'K':>6} {'us/pop update':>14} {'max - min':>10} {'agent-updates/s':>16} {'vs K=1':>7}  legs"]
+    base = statistics.median(res[1])
+    for k in names:
+        x, n = res[k], 1 if k == "lone" else k
+        m = statistics.median(x)
+        lines.append(f"{k!s:>6} {m:14.2f} {max(x) - min(x):10.2f} {n * 1e6 / m:16.3e} {(n / m) / (1 / base):7.2f}  "
+                     + "  ".join(f"{v:.2f}" for v in x))
+    lone = res["lone"]
+    limit = statistics.median(lone) + (max(lone) - min(lone))
+    lines.append(f"# K = 1 median {base:.2f} us against the lone TD3Learner's median + its legs' max - min = {limit:.2f} us: "
+                 + ("within" if base <= limit else "NOT within"))
+    print("\n".join(lines))
+    if a.out:
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--legs", type=int, default=5)
@@ -132,7 +183,11 @@ def main():
     ap.add_argument("--n-step", type=int, default=None)
     ap.add_argument("--baseline-lib", default=None)
     ap.add_argument("--ks", type=lambda t: [int(x) for x in t.split(",")], default=[1, 4, 8], help="with --n-step: the K values")
+    ap.add_argument("--td3", type=int, nargs="?", const=2, default=None, help="TD3 populations at this policy_delay (default 2)")
+    ap.add_argument("--out", default=None, help="with --td3: also write the table to this file")
     a = ap.parse_args()
+    if a.td3 is not None:
+        return td3_scaling(a)
     if a.n_step is not None:
         return nstep_cost(a)
     Ks = (1, 2, 4, 8, 16)

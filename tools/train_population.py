@@ -11,7 +11,11 @@ bottom agents copy a top agent's networks and optimizer state and perturb its hy
 agents or one per agent; with --pbt, --pbt-n-steps a,b,c lets the controller move an agent's n among those choices.
 --learn-log EVERY: the learn log (PopulationRollout(learn_log=...)), one record per agent and EVERY updates; each agent's line adds
 the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient norms, and the block's non-finite total.
-Usage: train_population.py [--objectives] [--n-step N[,N...]] [--learn-log EVERY] [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]]
+--td3 [DELAY[,SIGMA[,CLIP]]]: a population of TD3 agents (PopulationRollout(td3=TD3Config(...)); defaults 2, 0.2, 0.5), with the
+syntax of tools/train_vector.py: the token after --td3 is its value when it holds a comma; a lone DELAY is written --td3=DELAY.
+updates_per_step must be a multiple of DELAY; not with --n-step > 1, --pbt-n-steps or --learn-log.  --pbt works unchanged.
+Usage: train_population.py [--objectives] [--n-step N[,N...]] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]]
+       [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]]
        K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
 import pickle
@@ -44,6 +48,17 @@ _ints = lambda text: [int(x) for x in text.split(",")]
 n_step = _option("--n-step", _ints, [1])
 pbt_n_steps = _option("--pbt-n-steps", _ints)
 learn_every = _option("--learn-log", int)
+td3 = None
+for at, arg in enumerate(sys.argv):
+    if at and (arg == "--td3" or arg.startswith("--td3=")):
+        from ddpg_trucktrailer_amd.td3 import TD3Config  # noqa: E402
+        spec = arg[6:] if arg.startswith("--td3=") else ""
+        if arg == "--td3" and at + 1 < len(sys.argv) and "," in sys.argv[at + 1]:
+            spec = sys.argv.pop(at + 1)
+        del sys.argv[at]
+        parts = [x for x in spec.split(",") if x]
+        td3 = TD3Config(*([int(parts[0])] + [float(x) for x in parts[1:3]])) if parts else TD3Config()
+        break
 if pbt_n_steps is not None and pbt_ready is None:
     sys.exit("--pbt-n-steps needs --pbt")
 K, n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:8])
@@ -59,9 +74,9 @@ pop = PopulationRollout(n, seeds, batch_size=batch, replay_slots=slots, updates_
                         episode_log=min(n * every, 1 << 24), episode_log_detail=detail,
                         # the log holds a report block's records: one per learn_every updates
                         learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                        learn_log_every=learn_every or 1, **nstep_kw)
+                        learn_log_every=learn_every or 1, td3=td3, **nstep_kw)
 print(f"K = {K} agents x N = {n} envs, ring {slots} steps, {upd} learn() per vector step = {n / upd:.1f} env-steps per update "
-      f"per agent, batch {batch}, seeds {seeds}, n_step {pop.n_steps}", flush=True)
+      f"per agent, batch {batch}, seeds {seeds}, n_step {pop.n_steps}" + (f", {td3}" if td3 is not None else ""), flush=True)
 for a, ag in enumerate(pop.agents):       # each agent saves its best networks into a directory of its own
     d = os.path.join("tmp", "ddpg", f"seed{seeds[a]}")
     os.makedirs(d, exist_ok=True)
