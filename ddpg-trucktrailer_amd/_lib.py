@@ -130,6 +130,11 @@ class TTPopTd3Pair(C.Structure):
                [(n, C.c_float) for n in ("alpha", "beta", "tau", "gamma", "target_noise", "noise_clip")]
 
 
+class TTLossShape(C.Structure):
+    """tt_loss_shape (include/ttenv.h): huber_delta (0 = MSE with the caller's scale), pre_scale = 2c/B, pre [n]."""
+    _fields_ = [("huber_delta", C.c_float), ("pre_scale", C.c_float), ("pre", C.c_void_p)]
+
+
 class TTLearnLogJob(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
                [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
@@ -246,6 +251,17 @@ _SIGNATURES = {
     "tt_pop_td3_exploit": (C.c_int, [_P, _I, C.POINTER(TTPopTd3Pair), _P]),
     "tt_pop_td3_hyper": (C.c_int, [_P, _I, C.POINTER(C.c_float * 6)]),
     "tt_pop_td3_destroy": (C.c_int, [_P]),
+    "tt_mlp_backward_rows_pair_shaped": (C.c_int, [_I, C.c_float, _P, C.POINTER(TTMlpWeights), C.POINTER(TTMlpSaved),
+                                                   C.POINTER(TTMlpBwdWs), C.POINTER(TTTdInput), _P, C.POINTER(TTMlpWeights),
+                                                   C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs), C.POINTER(TTImageJob),
+                                                   C.POINTER(TTLossShape), _P]),
+    "tt_mlp_backward_weights_shaped": (C.c_int, [_I, _I, _P, _P, C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs), C.POINTER(TTMlpWeights),
+                                                 _P, _P, C.c_float, _I, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                 C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, C.POINTER(TTLossShape), _P]),
+    "tt_mlp_actor_tail_shaped": (C.c_int, [_I, _P, _P, C.POINTER(TTMlpWeights), _P, _P, C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs),
+                                           C.POINTER(TTMlpWeights), C.c_float, _I, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
+                                           C.c_float, C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, _P, _P,
+                                           C.POINTER(TTLossShape), _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -44,9 +44,15 @@ class GradAllReduce:
 class Agent():
     def __init__(self, alpha, beta, input_dims, tau, n_actions, gamma=0.99,
                  max_size=1000000, fc1_dims=400, fc2_dims=300,
-                 batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True, td3=None):
+                 batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True, td3=None, loss_shape=None):
         """td3: None = DDPG, line for line; a td3.TD3Config = TD3 (Fujimoto et al., 2018): a second critic `critic_2` with its target
-        `target_critic_2`, target-policy smoothing, and the actor and all targets updated on every policy_delay-th update only."""
+        `target_critic_2`, target-policy smoothing, and the actor and all targets updated on every policy_delay-th update only.
+        loss_shape: None = the MSE critic loss and the plain actor loss; a loss_shape.LossShape = the Huber critic loss and / or the
+        actor's pre-activation penalty c mean(pre^2) in learn_batch.  Not with td3."""
+        if loss_shape is not None:
+            from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
+            check_loss_shape(loss_shape, td3=td3)
+        self.loss_shape = loss_shape
         self.gamma, self.tau, self.batch_size, self.alpha, self.beta = gamma, tau, batch_size, alpha, beta
         self.device = T.device(device) if device is not None else T.device('cuda:0' if T.cuda.is_available() else 'cpu')
         self.memory = ReplayBuffer(max_size, input_dims, n_actions, device=self.device) if replay else None
@@ -144,7 +150,11 @@ class Agent():
         # AccumulateGrad node, which is pinned to the stream it was first used on -- a node kept alive from another stream
         # (e.g. by a clone of the parameter that still carries its grad_fn) forks a hipGraph capture of this function and
         # HIP's EndCapture then crashes the process.  grad() returns the same numbers without touching those nodes.
-        critic_loss = F.mse_loss(target, critic_value)
+        shape = self.loss_shape
+        if shape is not None and shape.huber_delta is not None:
+            critic_loss = F.huber_loss(critic_value, target, delta=shape.huber_delta)      # (half the MSE gradient inside the zone)
+        else:
+            critic_loss = F.mse_loss(target, critic_value)
         for p, g in zip(self._critic_params, T.autograd.grad(critic_loss, self._critic_params)):
             p.grad = g                                       # zero_grad(set_to_none=True) + backward()
         if self.grad_sync_critic is not None:
@@ -154,7 +164,11 @@ class Agent():
         # The actor step differentiates -Q(s, mu(s)) through the ALREADY UPDATED critic.  The reference lets
         # that backward also deposit gradients in the critic's parameters and throws them away at the next
         # zero_grad (DDPG_agent.py:95,100-104); asking for the actor's gradients only changes nothing the optimizers see.
-        actor_loss = T.mean(-self.critic.forward(states, self.actor.forward(states)))
+        if shape is not None and shape.pre_penalty > 0:
+            mu, pre = self.actor.forward_pre(states)
+            actor_loss = T.mean(-self.critic.forward(states, mu)) + shape.pre_penalty * T.mean(pre * pre)
+        else:
+            actor_loss = T.mean(-self.critic.forward(states, self.actor.forward(states)))
         for p, g in zip(self._actor_params, T.autograd.grad(actor_loss, self._actor_params)):
             p.grad = g
         if self.grad_sync_actor is not None:

@@ -733,11 +733,15 @@ __device__ inline void clock_tick(const TdIn &td) {
 
 // YGIVEN (critic only; csrc/tttd3.hip): the caller has formed the TD targets of this wave's two rows itself (y_given[0], [1]) --
 // the prologue's loads and dot product are compiled out and `td` is not read.
-template <bool CRITIC, bool YGIVEN = false>
+// SHAPED (csrc/ttshape.hip): the critic's TD error is clamped to [-huber_delta, huber_delta] when huber_delta > 0 (the Huber loss'
+// d/dq with scale = 1/B); the actor's workgroups also form the head's pre-activation pre[b] = b3 + sum_j h2[b][j] w3[j] from the
+// h2 and w3 they hold -- the TD prologue's fma order and wave_sum64 -- and leave it in pre_out (when given).
+template <bool CRITIC, bool YGIVEN = false, bool SHAPED = false>
 __device__ __forceinline__ void bwd_rows_body(const int n, const float scale, const float *__restrict__ out,
                                               const Weights &W, const Saved &sv, const BwdOut &o, const TdIn &td,
                                               float *__restrict__ dx2_s, float *__restrict__ red, float *__restrict__ rsc_s,
-                                              const int row0, const float *y_given = nullptr) {
+                                              const int row0, const float *y_given = nullptr, const float huber_delta = 0.f,
+                                              float *__restrict__ pre_out = nullptr) {
     // dx2_s [16][308]: A operand of phase B (with an fc2 image: its two f16 planes [2][16][328], each row scaled by a power
     // of two whose inverse / 64 goes to rsc_s [16]); red [2][NW][16]: cross-wave reductions
     const bool img = W.img != nullptr;                     // (uniform over the launch)
@@ -769,6 +773,7 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const float scale, co
         }
         b3t = td.b3[0];
     }
+    if (SHAPED && !CRITIC) b3t = W.b3[0];
 #pragma unroll
     for (int rr = 0; rr < RPW; ++rr) {
         const int row = row0 + wave * RPW + rr, rowc = min(row, n - 1);
@@ -828,8 +833,23 @@ __device__ __forceinline__ void bwd_rows_body(const int n, const float scale, co
             }
         }
         if (YGIVEN) y_td = y_given[rr];
+        if (SHAPED && !CRITIC) {
+            float dot = 0.f;
+#pragma unroll
+            for (int i = 0; i < RV; ++i) {
+                const float4 w = rv_col(lane, i) < H2 ? w3c[i] : f4_zero();      // (a column beyond 299 was loaded from column 0)
+                dot = fmaf(h2v[rr][i].x, w.x, dot);
+                dot = fmaf(h2v[rr][i].y, w.y, dot);
+                dot = fmaf(h2v[rr][i].z, w.z, dot);
+                dot = fmaf(h2v[rr][i].w, w.w, dot);
+            }
+            const float pre = wave_sum64(dot) + b3t;
+            if (pre_out && ok && lane == 0) pre_out[row] = pre;
+        }
+        float err = outv[rr] - y_td;
+        if (SHAPED && CRITIC && huber_delta > 0.f) err = err > huber_delta ? huber_delta : (err < -huber_delta ? -huber_delta : err);
         // (actor: the unit backward -- every per-row gradient below is linear in dpre, see k_bwd_rows_pair)
-        const float dpre = ok ? (CRITIC ? scale * (outv[rr] - y_td) : 1.f) : 0.f;
+        const float dpre = ok ? (CRITIC ? scale * err : 1.f) : 0.f;
         float4 dxh[RV];
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
@@ -1199,12 +1219,15 @@ __device__ __forceinline__ float tail_row(const TailSync &ts, const int b, const
     return __uint_as_float((unsigned)w);
 }
 
-template <bool ROWSCALE, bool TAIL>
+// PREPEN (csrc/ttshape.hip): the actor's pre-activation penalty c mean(pre^2) -- row b's factor becomes
+// fmaf(pre_scale, pre[b], f(b)) with pre_scale = 2c/B and pre[] as the shaped rows launch left it (pre NULL: pre[b] = 0).
+template <bool ROWSCALE, bool TAIL, bool PREPEN = false>
 __device__ __forceinline__ void bwd_weights_body(const int blk, const int n, const int critic, const float *__restrict__ obs,
                                                  const float *__restrict__ action, const Saved &sv, const BwdOut &d, const Grads &G,
                                                  const AdamFused &A, const RowScale &RS, float (&part)[4][4][256],
                                                  float *__restrict__ f_s, const TailSync &ts, const long long tail_epoch,
-                                                 _Float16 *__restrict__ stage_s) {
+                                                 _Float16 *__restrict__ stage_s, const float pre_scale = 0.f,
+                                                 const float *__restrict__ pre = nullptr) {
     // stage_s: 4 x 1024 halves of LDS (8 KB) of the workgroup's own: the forward-image pieces of a dW2 workgroup's patch
     // f(b) = (scale dQ/da[b]) (1 - mu[b]^2), every product and the difference rounded on its own (row_factor_of, contraction off):
     // left to the compiler, the loops below came out with 1 - mu^2 as ONE fma in their unrolled trips and as a product and a
@@ -1220,12 +1243,22 @@ __device__ __forceinline__ void bwd_weights_body(const int blk, const int n, con
                 lds_barrier();
                 for (int b = threadIdx.x; b < n; b += 256) {
                     const float m = RS.mu[b];
-                    f_s[b] = factor(tail_row(ts, b, (int)tail_epoch), m);
+                    if constexpr (PREPEN) {
+                        const float pb = pre ? pre[b] : 0.f;
+                        f_s[b] = fmaf(pre_scale, pb, factor(tail_row(ts, b, (int)tail_epoch), m));
+                    } else {
+                        f_s[b] = factor(tail_row(ts, b, (int)tail_epoch), m);
+                    }
                 }
             } else {
                 for (int b = threadIdx.x; b < n; b += 256) {
                     const float m = RS.mu[b];
-                    f_s[b] = factor(RS.dq_da[b], m);
+                    if constexpr (PREPEN) {
+                        const float pb = pre ? pre[b] : 0.f;
+                        f_s[b] = fmaf(pre_scale, pb, factor(RS.dq_da[b], m));
+                    } else {
+                        f_s[b] = factor(RS.dq_da[b], m);
+                    }
                 }
             }
             lds_barrier();

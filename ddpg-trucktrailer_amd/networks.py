@@ -108,3 +108,10 @@ class ActorNetwork(_Checkpointed):
         x = F.relu(self.bn1(self.fc1(state)))
         x = F.relu(self.bn2(self.fc2(x)))
         return T.tanh(self.mu(x))
+
+    def forward_pre(self, state):
+        """(mu(s), pre(s)): the action and the head's value before tanh (the pre-activation penalty of a LossShape)."""
+        x = F.relu(self.bn1(self.fc1(state)))
+        x = F.relu(self.bn2(self.fc2(x)))
+        pre = self.mu(x)
+        return T.tanh(pre), pre

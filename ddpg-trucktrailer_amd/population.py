@@ -33,6 +33,14 @@ from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, _gc_off
 from ddpg_trucktrailer_amd.stepper import VectorStepper
 
 
+def _refuse_loss_shape(loss_shape, agents=()):
+    """A population has no loss shape (loss_shape.check_loss_shape): neither as an option nor on an agent it is given."""
+    from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
+    for shape in [loss_shape] + [getattr(ag, "loss_shape", None) for ag in agents]:
+        if shape is not None:
+            check_loss_shape(shape, population=True)
+
+
 class PopulationLearner:
     """learn() of K agents, each with the state of a FusedLearner of its own (Adam moments, step_dev, bias corrections, tail words,
     fc2 images), launched together.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys (update u of a vector
@@ -45,7 +53,9 @@ class PopulationLearner:
     then ends with one more launch that leaves a record of every agent's update whose step count is a multiple of learn_log_every,
     and drain_learn_log() collects them.  One K-agent handle, made with the descriptors.  Not part of any checkpoint."""
 
-    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1):
+    def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1,
+                 loss_shape=None):
+        _refuse_loss_shape(loss_shape, agents)
         self.K, self.B = len(agents), int(batch_size)
         if not 1 <= self.K <= L.POP_MAX_AGENTS:
             raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
@@ -247,8 +257,9 @@ class PopulationRollout:
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
-                 learn_log_every=1, td3=None):
+                 learn_log_every=1, td3=None, loss_shape=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+        _refuse_loss_shape(loss_shape)
         if td3 is not None:            # (before anything else: each refusal names its option)
             from ddpg_trucktrailer_amd.td3 import check_population_td3
             td3 = check_population_td3(td3, len(seeds), updates_per_step, _listed(n_step), 1 if n_step_max is None else n_step_max,

@@ -72,7 +72,7 @@ class DDPGRollout(VectorStepper):
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
-                 learn_log_every=1, td3=None):
+                 learn_log_every=1, td3=None, loss_shape=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -99,8 +99,22 @@ class DDPGRollout(VectorStepper):
         td3: None = DDPG.  A td3.TD3Config = TD3: the agent gets a second critic, and with the reference-shaped
         networks on a GPU learn() runs on the TD3 launches (td3.TD3Learner), update u of a vector step being a full one when
         (u + 1) % policy_delay == 0 -- the same pattern in every step, so one captured step serves them all.  Serial order only
-        (pipeline=None resolves to False); td3.check_td3 names what is refused."""
+        (pipeline=None resolves to False); td3.check_td3 names what is refused.
+        loss_shape: None, or a loss_shape.LossShape: a Huber critic loss and / or a pre-activation penalty on the
+        actor, inside the launches learn() makes anyway -- in the serial and the pipelined order, with n_step, learn_log and graphs.
+        loss_shape.check_loss_shape names what is refused (td3, data-parallel ranks, the p2p exchange, TT_FORCE_DP)."""
         self.n_step = check_n_step(n_step)
+        self.loss_shape = None
+        if loss_shape is not None:
+            from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
+            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
+            self.loss_shape = check_loss_shape(loss_shape, td3=td3, data_parallel=ranks or dp_exchange == "p2p",
+                                               force_dp=os.environ.get("TT_FORCE_DP") == "1")
+            if agent is not None and getattr(agent, "loss_shape", None) != self.loss_shape:
+                raise ValueError(f"loss_shape: the agent passed in was built with loss_shape = {getattr(agent, 'loss_shape', None)!r}, "
+                                 f"the loop with {self.loss_shape!r}")
+        elif agent is not None and getattr(agent, "loss_shape", None) is not None:
+            raise ValueError("loss_shape: the agent passed in was built with a loss_shape, the loop without")
         self.td3 = None
         if td3 is not None:
             from ddpg_trucktrailer_amd.td3 import check_td3
@@ -127,6 +141,7 @@ class DDPGRollout(VectorStepper):
                          policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail,
                          td3=self.td3)
         self.batch_size = batch_size
+        self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
         self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
         self.dp_exchange = dp_exchange or os.environ.get("TT_DP_EXCHANGE", "collective")
         assert self.dp_exchange in ("collective", "p2p"), self.dp_exchange
@@ -148,7 +163,7 @@ class DDPGRollout(VectorStepper):
                 from ddpg_trucktrailer_amd.td3 import TD3Learner
                 self.learner = TD3Learner(self.agent, batch_size, self.ring, self.seed)
             elif self.td3 is None:
-                self.learner = FusedLearner(self.agent, batch_size)
+                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape)
             self.agent.fused_learner = self.learner
             if self.dp and self.dp_exchange == "p2p":
                 self.learner.enable_p2p()
@@ -644,6 +659,8 @@ class DDPGRollout(VectorStepper):
                 sd["td3_noise"] = ag.td3_noise_state()               # (the torch path's generator; the fused path's noise is counter-based)
         if self.td3 is not None:
             sd["td3"] = list(self.td3.as_tuple())
+        if self.loss_shape is not None:
+            sd["loss_shape"] = list(self.loss_shape.as_tuple())
         return sd
 
     def drain_learn_log(self):
@@ -660,6 +677,10 @@ class DDPGRollout(VectorStepper):
         if ("td3" in sd) != (self.td3 is not None):
             raise ValueError("the checkpoint was written with td3, this loop has none" if "td3" in sd else
                              "the checkpoint was written without td3, this loop has td3 (no second critic in it)")
+        have = tuple(sd["loss_shape"]) if sd.get("loss_shape") is not None else None
+        mine = self.loss_shape.as_tuple() if self.loss_shape is not None else None
+        if have != mine:
+            raise ValueError(f"the checkpoint was written with loss_shape = {have}, this loop has loss_shape = {mine}")
         with torch.no_grad():
             for n, net_sd in sd["nets"].items():
                 for k, v in getattr(ag, n).state_dict().items():      # in place: captured graphs keep the addresses

@@ -842,6 +842,52 @@ int tt_pop_td3_exploit(tt_pop_td3 *pop, int pairs, const tt_pop_td3_pair *list /
 int tt_pop_td3_hyper(tt_pop_td3 *pop, int agent, float out[6]);
 int tt_pop_td3_destroy(tt_pop_td3 *pop);                                     /* the caller's stream work with it must be done */
 
+/* ------------------------------------------------------------------------------------------------------
+ * Loss shape of the lone learn() (csrc/ttshape.hip): a Huber critic loss and a pre-activation penalty on the actor, inside the
+ * launches learn() makes anyway -- the three entry points below stand in for tt_mlp_backward_rows_pair, the ACTOR's
+ * tt_mlp_backward_weights and tt_mlp_actor_tail, with the same grids, the same dispatch order and the same hand-over in device
+ * memory (no wait added, the bounded one unchanged).
+ *   critic   huber_delta = d > 0: loss = huber_loss(q, y, delta = d), mean over the rows (torch.nn.functional.huber_loss), so
+ *            d(loss)/dq[b] = scale_critic * clamp(q[b] - y[b], -d, d) with the caller's scale_critic = 1/B.  Inside the
+ *            quadratic zone that is HALF the gradient of mse_loss (torch's definition of the Huber loss: 0.5 e^2).
+ *            huber_delta = 0: no clamp -- d(loss)/dq[b] = scale_critic * (q[b] - y[b]), the MSE launch with scale_critic = 2/B.
+ *   actor    loss = -mean Q(s, mu(s)) + c mean(pre^2), pre [n] = the head's value before tanh, pre[b] = b3 + sum_j h2[b][j] w3[j]:
+ *            recomputed in f32 from the saved h2 by the actor's row workgroups of tt_mlp_backward_rows_pair_shaped (the TD
+ *            prologue's fma order and wave sum; accurate to f32 against f64, NOT the forward's bits, which are not kept) and
+ *            written to shape->pre.  Row b of the weight launch then counts
+ *                fmaf(pre_scale, pre[b], row_scale * dq_da[b] * (1 - mu[b]^2))        pre_scale = (float)(2 c / B), formed in f64
+ *            times: the penalty's gradient 2 c pre / B does not vanish where tanh saturates.
+ * With huber_delta = 0 and pre_scale = 0 the three give the bits of the entry points they stand in for: fmaf(0, pre, f) is f for
+ * every finite pre -- except that a factor f = -0.0 can come back as +0.0 (equal as a number) and a non-finite pre makes it NaN.
+ * shape->pre may be NULL when pre_scale = 0 (the row launch then stores no pre; the weight launches read none).
+ * The learn log (tt_learn_log_*) is unchanged by a loss shape: its critic loss stays the mean square of the TD error and its actor
+ * loss stays -mean q_pi, whatever loss the gradients came from.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL shape; huber_delta or pre_scale negative or not
+ * finite; pre NULL with pre_scale > 0; the critic (or no row_dq_da / row_mu) passed to tt_mlp_backward_weights_shaped; count other
+ * than 0 or 10 there; and whatever the entry point it stands in for refuses. */
+typedef struct tt_loss_shape {
+    float huber_delta;   /* 0 = MSE with the caller's scale */
+    float pre_scale;     /* k = 2c/B, >= 0 */
+    float *pre;          /* [n], required when pre_scale > 0 */
+} tt_loss_shape;
+int tt_mlp_backward_rows_pair_shaped(int n, float scale_critic, const float *q_out, const tt_mlp_weights *critic,
+                                     const tt_mlp_saved *saved_critic, const tt_mlp_bwd_ws *ws_critic, const tt_td_input *td,
+                                     const float *mu_out, const tt_mlp_weights *actor, const tt_mlp_saved *saved_actor,
+                                     const tt_mlp_bwd_ws *ws_actor, const tt_image_job *image, const tt_loss_shape *shape,
+                                     tt_stream_t stream);
+int tt_mlp_backward_weights_shaped(int n, int critic /* must be 0 */, const float *obs, const float *action, const tt_mlp_saved *saved,
+                                   const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, const float *row_dq_da, const float *row_mu,
+                                   float row_scale, int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq,
+                                   float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
+                                   float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
+                                   const tt_loss_shape *shape, tt_stream_t stream);
+int tt_mlp_actor_tail_shaped(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                             const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale,
+                             int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
+                             const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                             const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
+                             const tt_loss_shape *shape, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

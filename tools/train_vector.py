@@ -11,7 +11,10 @@ the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient
 --td3 [DELAY[,SIGMA[,CLIP]]]: TD3 instead of DDPG (DDPGRollout(td3=TD3Config(...)); defaults 2, 0.2, 0.5): twin critics, target-policy
 smoothing, the actor and the targets updated every DELAY-th update.  The token after --td3 is its value when it holds a comma; a
 lone DELAY is written --td3=DELAY.  updates_per_step must be a multiple of DELAY; not with --n-step > 1 or --learn-log.
-Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+--huber D / --pre-penalty C: the loss shape (DDPGRollout(loss_shape=LossShape(D, C))): a Huber critic loss
+with delta D (torch's definition: half the MSE gradient inside the zone) and / or the penalty C mean(pre^2) on the actor head's
+pre-activation.  Not with --td3.
+Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -33,6 +36,19 @@ if "--learn-log" in sys.argv[1:]:
     at = sys.argv.index("--learn-log")
     learn_every = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+huber, pre_penalty = None, 0.0
+if "--huber" in sys.argv[1:]:
+    at = sys.argv.index("--huber")
+    huber = float(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+if "--pre-penalty" in sys.argv[1:]:
+    at = sys.argv.index("--pre-penalty")
+    pre_penalty = float(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+loss_shape = None
+if huber is not None or pre_penalty:
+    from ddpg_trucktrailer_amd.loss_shape import LossShape
+    loss_shape = LossShape(huber, pre_penalty)
 td3 = None
 for at, arg in enumerate(sys.argv):
     if at and (arg == "--td3" or arg.startswith("--td3=")):
@@ -54,9 +70,10 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                   learn_log_every=learn_every or 1, td3=td3)
+                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
-      f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else ""), flush=True)
+      f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else "") +
+      (f", {loss_shape}" if loss_shape is not None else ""), flush=True)
 
 
 def learn_line(rec):
