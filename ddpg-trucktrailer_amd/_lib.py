@@ -185,6 +185,10 @@ _SIGNATURES = {
     "tt_env_import_episode_log": (C.c_int, [_P, _P, C.POINTER(C.c_uint64 * 2), _P]),
     "tt_env_set_episode_log2": (C.c_int, [_P, C.c_int64, C.c_uint32, _P]),
     "tt_env_drain_episode_log2": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "tt_env_set_hold": (C.c_int, [_P, _I, _P]),
+    "tt_env_hold_begin": (C.c_int, [_P, _P]),
+    "tt_env_step_hold": (C.c_int, [_P, _P, C.c_float, _P, _P]),
+    "tt_env_hold_read": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "tt_env_rollout_random": (C.c_int, [_P, _I, _U64, _P, _P, _P, _P]),
     "tt_env_profile": (C.c_int, [_P, _I]),
     "tt_env_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),

@@ -31,7 +31,10 @@ def _violation_label(flags, success):
 @torch.no_grad()
 def generate_heatmap_data(actor, grid_resolution=2.0, trials_per_cell=5, map_x_range=(-40, 40), map_y_range=(-30, 40),
                           start_orientation_range_deg=(45, 120), goal_pose=(0.0, -30.0, 90.0), L2_range=(5, 7),
-                          seed=66, device=None, max_steps_cap=1024):
+                          seed=66, device=None, max_steps_cap=1024, hold=False):
+    """hold=True: the episodes run through TruckTrailerVecEnv.step_hold (finished lanes hold still and keep their record on the
+    device; one look at the live count every 32 steps instead of a host-masked step with info and a synchronize per step);
+    the seven objects are the same."""
     x_coords = np.arange(map_x_range[0], map_x_range[1], grid_resolution)
     y_coords = np.arange(map_y_range[0], map_y_range[1], grid_resolution)
     ny, nx, nt = len(y_coords), len(x_coords), trials_per_cell
@@ -58,7 +61,22 @@ def generate_heatmap_data(actor, grid_resolution=2.0, trials_per_cell=5, map_x_r
     # launch at f32 accuracy); any other module, or the CPU, through torch
     use_fused = dev.type == "cuda" and fused.supported(actor)
     mu = torch.empty(n, dtype=torch.float32, device=dev)
-    for _ in range(max_steps_cap):
+    if hold:
+        env.enable_hold()
+        env.hold_begin()
+        traj = [env.state[first][:, 4:6]]
+        for t in range(max_steps_cap):
+            mu_now = fused.actor_forward(actor, obs, mu).view(-1) if use_fused else mu.copy_(actor(obs).view(-1))
+            obs = env.step_hold(mu_now, high)                                  # evaluate=True: no noise (heatmap.py:138)
+            traj.append(env.state[first][:, 4:6])
+            if t % 32 == 31 and int(env.hold_count_live().item()) == 0:
+                break
+        rec = env.hold_records()
+        score, end_flags, end_xy = rec["ret"], rec["flags"], rec["end"][:, :2]
+        # a lane that is still live at the cap has no record: what the masked loop leaves for it
+        traj_len = torch.where(rec["len"][first] > 0, rec["len"][first].long() + 1, torch.full_like(traj_len, len(traj)))
+        traj = [x.cpu().numpy() for x in traj]
+    for _ in range(0 if hold else max_steps_cap):
         mu_now = fused.actor_forward(actor, obs, mu).view(-1) if use_fused else actor(obs).view(-1)
         action = torch.clamp(mu_now, -1.0, 1.0) * high                     # evaluate=True: no noise (heatmap.py:138)
         obs, _, done, info = env.step(action, auto_reset=False, info=True)

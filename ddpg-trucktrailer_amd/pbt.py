@@ -12,6 +12,9 @@ Rules:
   - per agent, the last `window` episodes that ENDED since that agent's last exploit (or since the start) count;
   - a round is due once `ready` vector steps have passed since the last round; it needs two or more eligible agents (>= min_episodes
     such episodes, default `window`) -- otherwise it is tried again at the next call;
+  - step(..., evaluation=records) ranks a round on the records of a greedy evaluation (evaluation.Evaluator: every agent from the same
+    start poses, no noise) instead: every agent with >= min_episodes records is eligible, the windows are not consulted, and
+    the rest of the round -- truncation, the draws and their order, exploit -- is the same;
   - ranking: "return" = mean return; "success" = success rate, then mean return (checkpoint.BestModelTracker's order); ties go to
     the lower agent index;
   - truncation selection: m = min(max(1, floor(quantile * E)), E // 2) of the E eligible agents; each of the bottom m (worst
@@ -79,7 +82,22 @@ class PBT:
 
     def score(self, a):
         """Agent a's ranking key over its window (larger is better), or None while it has fewer than min_episodes episodes."""
-        w = self.windows[a]
+        return self._score_of(self.windows[a])
+
+    def evaluation_scores(self, evaluation):
+        """Per agent, the ranking key over ALL the records of an evaluation (evaluation.Evaluator.run: per agent a dict with "ret"
+        and "success"), or None for an agent with fewer than min_episodes of them.  The windows are not read."""
+        if len(evaluation) != self.K:
+            raise ValueError(f"PBT: {len(evaluation)} evaluation records for {self.K} agents")
+        out = []
+        for r in evaluation:
+            ret, ok = _host(r["ret"]), _host(r["success"])
+            if len(ret) != len(ok):
+                raise ValueError("PBT: an evaluation's ret and success differ in length")
+            out.append(self._score_of([(float(x), bool(s)) for x, s in zip(ret, ok)]))
+        return out
+
+    def _score_of(self, w):
         if len(w) < self.min_episodes:
             return None
         mean = sum(x for x, _ in w) / len(w)
@@ -88,15 +106,17 @@ class PBT:
         return (sum(1 for _, s in w if s) / len(w), mean)
 
     # ------------------------------------------------------------------------------------------------- a round
-    def decide(self, vector_step, hypers):
+    def decide(self, vector_step, hypers, evaluation=None):
         """hypers: per agent {"alpha", "beta", "tau", "gamma"} (and "n_step" with n_step_choices) as they are now.  Returns the
         round's decisions (possibly none): [{"step", "dst", "src", "dst_score", "src_score", "old", "new"}] -- "new" is what dst
-        takes."""
+        takes.  evaluation: the K record dicts of an evaluation -- the round then ranks on those records alone
+        (evaluation_scores), everything after the ranking is the same."""
         if len(hypers) != self.K:
             raise ValueError(f"PBT.decide: {len(hypers)} hyperparameter sets for {self.K} agents")
         if vector_step - self.last_round < self.ready:
             return []
-        scores = {a: s for a in range(self.K) for s in (self.score(a),) if s is not None}
+        every = [self.score(a) for a in range(self.K)] if evaluation is None else self.evaluation_scores(evaluation)
+        scores = {a: s for a, s in enumerate(every) if s is not None}
         E = len(scores)
         if E < 2:
             return []                  # (tried again at the next call)
@@ -133,14 +153,16 @@ class PBT:
             return n
         return c[min(max(i + move, 0), len(c) - 1)]
 
-    def step(self, pop, drained):
-        """observe(drained), decide at pop.vector_steps, and apply the decisions with one pop.exploit launch."""
+    def step(self, pop, drained, evaluation=None):
+        """observe(drained), decide at pop.vector_steps, and apply the decisions with one pop.exploit launch.  evaluation: None, or
+        what evaluation.Evaluator.run returned for pop's actors (the same start poses for every agent, no noise): the round
+        ranks on it instead of on the training windows."""
         self.observe(drained)
         hypers = [{k: float(getattr(ag, k)) for k in HYPERS} for ag in pop.agents]
         if self.n_step_choices is not None:
             for h, n in zip(hypers, pop.n_steps):
                 h["n_step"] = int(n)
-        out = self.decide(pop.vector_steps, hypers)
+        out = self.decide(pop.vector_steps, hypers, evaluation)
         if out:
             pop.exploit([(d["dst"], d["src"], d["new"]) for d in out])
         return out

@@ -397,6 +397,12 @@ class PopulationRollout:
                 self.step()
                 k -= 1
 
+    def evaluate(self, ev):
+        """A greedy evaluation of the K current actors between two population steps, on this stream: ev is an
+        evaluation.Evaluator of K agents (every agent from the same start poses).  Returns its K records (what
+        pbt.PBT.step(..., evaluation=) ranks on).  Nothing of the loops is touched -- envs, rings, noise, RNG."""
+        return ev.run([ag.actor for ag in self.agents])
+
     def drain_episodes(self):
         """[agent: its env's episode log since the last drain (VectorStepper.drain_episodes)]."""
         return [lp.drain_episodes() for lp in self.loops]

@@ -633,6 +633,12 @@ class DDPGRollout(VectorStepper):
                 k -= 1
         self._check_handover()
 
+    def evaluate(self, ev):
+        """A greedy evaluation of the current actor between two vector steps, on this stream: ev is an evaluation.Evaluator of one
+        agent.  Returns its records (Evaluator.run).  Nothing of the loop is touched -- env, ring, noise, RNG: the evaluator has
+        an env of its own, and the forward reads the live weights through the module's own workspace."""
+        return ev.run([self.agent.actor])[0]
+
     # -------------------------------------------------------------- checkpoint / resume of the whole loop
     def state_dict(self):
         """Everything the next vector step depends on: the four networks, both optimizers' state (the

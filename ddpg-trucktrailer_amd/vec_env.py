@@ -238,6 +238,52 @@ class TruckTrailerVecEnv:
                                                    L.ptr(reward_sum), L.ptr(episodes_done), self._stream()))
         return obs
 
+    # ------------------------------------------------------------------ held lanes (greedy evaluation)
+    def enable_hold(self):
+        """Allocate the handle's evaluation block (include/ttenv.h: tt_env_set_hold) and the tensors hold_records() fills.
+        Outside a graph capture.  step() and the episode log ignore the block."""
+        self._check(self.lib.tt_env_set_hold(self._h, 1, self._stream()))
+        n = self.n_envs
+        with torch.cuda.device(self.device):
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=self.device)
+            self._hold_out = dict(ret=z(n, torch.float64), len=z(n, torch.int32), flags=z(n, torch.uint8), success=z(n, torch.uint8),
+                                  end=z((3, n), torch.float64))
+            self.hold_live = z(1, torch.int64)
+
+    def disable_hold(self):
+        self._check(self.lib.tt_env_set_hold(self._h, 0, self._stream()))
+        self._hold_out = self.hold_live = None
+
+    def hold_begin(self):
+        """Every lane live, every record zero: after set_pose / reset, before the first step_hold.  Capturable."""
+        self._check(self.lib.tt_env_hold_begin(self._h, self._stream()))
+
+    def step_hold(self, mu, action_scale, obs_out=None):
+        """One step of every live lane with the action mu * action_scale (mu [N] f32 on this device); finished lanes hold still
+        (include/ttenv.h: tt_env_step_hold).  Returns the observation buffer.  Capturable."""
+        if not (torch.is_tensor(mu) and mu.dtype == torch.float32 and mu.is_contiguous() and mu.device == self.device
+                and mu.numel() == self.n_envs):
+            raise ValueError(f"step_hold: mu must be a contiguous f32 tensor of {self.n_envs} elements on {self.device}")
+        obs = self.obs if obs_out is None else obs_out
+        self._check(self.lib.tt_env_step_hold(self._h, L.ptr(mu), float(action_scale), L.ptr(obs), self._stream()))
+        return obs
+
+    def hold_count_live(self):
+        """The number of lanes still live into the device int64 self.hold_live (stream-ordered, capturable); returns the tensor."""
+        self._check(self.lib.tt_env_hold_read(self._h, None, None, None, None, None, L.ptr(self.hold_live), self._stream()))
+        return self.hold_live
+
+    def hold_records(self):
+        """Every lane's record, in lane order, as device tensors (fresh copies): ret f64, len i32, flags u8, success bool,
+        end [N,3] f64 (x2, y2, psi2 at the done step); `live`: the number of lanes not finished yet (synchronises)."""
+        o = self._hold_out
+        self._check(self.lib.tt_env_hold_read(self._h, L.ptr(o["ret"]), L.ptr(o["len"]), L.ptr(o["flags"]), L.ptr(o["success"]),
+                                              L.ptr(o["end"]), L.ptr(self.hold_live), self._stream()))
+        out = dict(ret=o["ret"].clone(), len=o["len"].clone(), flags=o["flags"].clone(), success=o["success"].bool(),
+                   end=o["end"].t().contiguous())
+        out["live"] = int(self.hold_live.item())
+        return out
+
     # ------------------------------------------------------------------ episode log
     @property
     def episode_log_capacity(self):

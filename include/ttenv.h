@@ -269,6 +269,29 @@ int tt_env_drain_episode_log2(tt_env *env, double *ret, int32_t *len, uint8_t *f
                               int64_t *end_step, double *comp, double *start, int64_t *n_out, uint64_t *counts_out,
                               tt_stream_t stream);
 
+/* Greedy evaluation: an env step in which a finished lane holds still (the reference evaluates with
+ * evaluate=True from fixed poses: DDPG/test.py:96-115, heatmap.py:79-193).  tt_env_set_hold(env, on != 0) allocates (on = 0:
+ * frees) the handle's evaluation block -- like the episode log's, an allocation: call it outside a graph capture -- with, per
+ * lane,
+ *     live u8      ret f64 (the f64 TT_I_TOTAL rewards summed in step order: the episode log's return)
+ *     len i32      flags u8 (TT_F_* bits, unmasked)      success u8 (final_success_bonus > 0)
+ *     end f64 [3]  (x2, y2, psi2 at the done step)
+ * tt_env_hold_begin (after tt_env_set_pose or tt_env_reset) makes every lane live and zeroes the records.  tt_env_step_hold steps
+ * every LIVE lane with the action mu[i] * action_scale (one f32 multiply; the step clips as always), without reset, adds the
+ * reward to the lane's return, stores state and observation row as tt_env_step does and, where the lane is done, writes its
+ * record and clears its live byte.  A lane that is not live is HELD: nothing of it changes -- state, counters, episode number,
+ * observation row, record.  No reward / done arrays, no info; the step counter (tt_env_set_step_counter), the episode log and
+ * the ring are not touched, and tt_env_step*, the episode log and tt_env_export ignore the block.  Every record sits in its
+ * lane's slot and nothing is counted with atomics: the same poses and actions give the same bits.
+ * tt_env_hold_read copies the records, stream-ordered, into the caller's device arrays of n entries (end: [3, n]; any may be
+ * NULL) and writes the number of lanes still live to *live_out (device int64, may be NULL).  begin, step and read are
+ * capturable into a hipGraph.  TT_EINVAL: a NULL handle, hold not enabled, NULL mu or obs, a non-finite action_scale. */
+int tt_env_set_hold(tt_env *env, int on, tt_stream_t stream);
+int tt_env_hold_begin(tt_env *env, tt_stream_t stream);
+int tt_env_step_hold(tt_env *env, const float *mu, float action_scale, float *obs, tt_stream_t stream);
+int tt_env_hold_read(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, double *end, int64_t *live_out,
+                     tt_stream_t stream);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */

@@ -14,8 +14,11 @@ the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient
 --td3 [DELAY[,SIGMA[,CLIP]]]: a population of TD3 agents (PopulationRollout(td3=TD3Config(...)); defaults 2, 0.2, 0.5), with the
 syntax of tools/train_vector.py: the token after --td3 is its value when it holds a comma; a lone DELAY is written --td3=DELAY.
 updates_per_step must be a multiple of DELAY; not with --n-step > 1, --pbt-n-steps or --learn-log.  --pbt works unchanged.
+--eval-every R --eval-lanes M: after every R-th report block a greedy evaluation (evaluation.Evaluator: no noise, the same M start
+poses for every agent, drawn once from first_seed), one summary line per agent; --pbt-on-eval: the block's PBT round ranks on those
+records instead of on the training episodes (PBT.step(..., evaluation=); with --pbt, whose window becomes M).
 Usage: train_population.py [--objectives] [--n-step N[,N...]] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]]
-       [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]]
+       [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]] [--eval-every R --eval-lanes M [--pbt-on-eval]]
        K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
 import pickle
@@ -48,6 +51,11 @@ _ints = lambda text: [int(x) for x in text.split(",")]
 n_step = _option("--n-step", _ints, [1])
 pbt_n_steps = _option("--pbt-n-steps", _ints)
 learn_every = _option("--learn-log", int)
+eval_every = _option("--eval-every", int)
+eval_lanes = _option("--eval-lanes", int, 256)
+pbt_on_eval = "--pbt-on-eval" in sys.argv[1:]
+if pbt_on_eval:
+    sys.argv.remove("--pbt-on-eval")
 td3 = None
 for at, arg in enumerate(sys.argv):
     if at and (arg == "--td3" or arg.startswith("--td3=")):
@@ -61,6 +69,8 @@ for at, arg in enumerate(sys.argv):
         break
 if pbt_n_steps is not None and pbt_ready is None:
     sys.exit("--pbt-n-steps needs --pbt")
+if pbt_on_eval and (pbt_ready is None or eval_every is None):
+    sys.exit("--pbt-on-eval needs --pbt and --eval-every")
 K, n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:8])
 seed0 = int(sys.argv[8]) if len(sys.argv) > 8 else 27
 graph_steps = int(sys.argv[9]) if len(sys.argv) > 9 else 20
@@ -98,11 +108,20 @@ trackers = [BestModelTracker() for _ in range(K)]
 pbt = None
 if pbt_ready is not None:
     from ddpg_trucktrailer_amd.pbt import PBT  # noqa: E402
-    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric, n_step_choices=pbt_n_steps)
+    # (ranked on evaluations: all of an evaluation's M records count, whatever an agent's training window holds)
+    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric, n_step_choices=pbt_n_steps,
+              **(dict(window=eval_lanes) if pbt_on_eval else {}))
     print(f"PBT: a round every {pbt_ready} vector steps, bottom/top quantile {pbt_quantile}, ranked by {pbt_metric} over the "
           f"last {pbt.window} episodes since an agent's last exploit"
           + (f", n_step explored among {list(pbt.n_step_choices)}" if pbt_n_steps is not None else ""), flush=True)
 running = [RunningObjectives() for _ in range(K)] if detail else None
+evaluator = None
+if eval_every is not None:
+    from ddpg_trucktrailer_amd.evaluation import Evaluator, summary  # noqa: E402
+    evaluator = Evaluator(eval_lanes, agents=K, seed=seed0, device=pop.device)
+    print(f"evaluation: every {eval_every} blocks, {eval_lanes} start poses shared by the {K} agents"
+          + (", PBT ranks on it" if pbt_on_eval else ""), flush=True)
+blocks = 0
 episodes = [0] * K
 t0 = time.time()
 s = 0
@@ -128,8 +147,19 @@ while s < total:
               f"{'BEST ' if best else ''}{objs}{lost}{learn_line(learned[a]) if learned is not None else ''}", flush=True)
         if best:
             pop.agents[a].save_models()
-    if pbt is not None:
-        for d in pbt.step(pop, drained):
+    blocks += 1
+    evaluation = None
+    if evaluator is not None and blocks % eval_every == 0:
+        evaluation = pop.evaluate(evaluator)
+        for a, r in enumerate(evaluation):
+            e = summary(r)
+            ends = "  ".join(f"{k} {v}" for k, v in e["flags"].items() if v)
+            print(f"evaluation  agent {a} seed {seeds[a]}  vector steps {s:7d}: mean return {e['mean_return']:9.1f}  success rate "
+                  f"{e['success_rate']:5.2f}  mean length {e['mean_len']:6.1f}  {ends}  ({evaluator.steps_run} steps)", flush=True)
+    if pbt is not None and pbt_on_eval and evaluation is None:
+        pbt.observe(drained)           # (no round without an evaluation to rank on)
+    elif pbt is not None:
+        for d in pbt.step(pop, drained, evaluation if pbt_on_eval else None):
             hyp = "  ".join(f"{k} {d['old'][k]:.4g} -> {d['new'][k]:.4g}" for k in d["new"])
             print(f"PBT step {d['step']}: agent {d['dst']} (score {d['dst_score'][0]:.1f}) <- agent {d['src']} "
                   f"(score {d['src_score'][0]:.1f}): {hyp}", flush=True)

@@ -14,7 +14,11 @@ lone DELAY is written --td3=DELAY.  updates_per_step must be a multiple of DELAY
 --huber D / --pre-penalty C: the loss shape (DDPGRollout(loss_shape=LossShape(D, C))): a Huber critic loss
 with delta D (torch's definition: half the MSE gradient inside the zone) and / or the penalty C mean(pre^2) on the actor head's
 pre-activation.  Not with --td3.
-Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+--eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
+poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
+far by (success rate, mean return).
+Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
+       [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -44,6 +48,15 @@ if "--huber" in sys.argv[1:]:
 if "--pre-penalty" in sys.argv[1:]:
     at = sys.argv.index("--pre-penalty")
     pre_penalty = float(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+eval_every, eval_lanes = None, 256
+if "--eval-every" in sys.argv[1:]:
+    at = sys.argv.index("--eval-every")
+    eval_every = int(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+if "--eval-lanes" in sys.argv[1:]:
+    at = sys.argv.index("--eval-lanes")
+    eval_lanes = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
 loss_shape = None
 if huber is not None or pre_penalty:
@@ -87,6 +100,10 @@ def learn_line(rec):
 
 
 tracker = BestModelTracker()
+evaluator, best_eval, blocks = None, None, 0
+if eval_every is not None:
+    from ddpg_trucktrailer_amd.evaluation import Evaluator, summary
+    evaluator = Evaluator(eval_lanes, seed=seed, device=env.device)
 episodes = 0
 t0 = time.time()
 s = 0
@@ -110,3 +127,15 @@ while s < total:
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
           f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
+    blocks += 1
+    if evaluator is not None and blocks % eval_every == 0:
+        e = summary(loop.evaluate(evaluator))
+        key = (e["success_rate"], e["mean_return"])
+        is_best = best_eval is None or key > best_eval
+        if is_best:
+            best_eval = key
+            loop.agent.save_models()
+        ends = "  ".join(f"{k} {v}" for k, v in e["flags"].items() if v)
+        print(f"evaluation  vector steps {s:7d}: {eval_lanes} episodes  mean return {e['mean_return']:9.1f}  success rate "
+              f"{e['success_rate']:5.2f}  mean length {e['mean_len']:6.1f}  {ends}  ({evaluator.steps_run} steps)"
+              f"{'  BEST: networks saved' if is_best else ''}", flush=True)
