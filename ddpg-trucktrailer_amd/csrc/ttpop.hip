@@ -21,6 +21,7 @@
 // compiler may issue as early as it likes (nothing in a launch writes them).
 #include "tthost.h"
 #include "ttpop.h"
+#include "ttpop_exploit.h"
 
 #include <cmath>
 #include <cstddef>
@@ -144,34 +145,25 @@ __global__ __launch_bounds__(64 * NW) void k_pop_actor_tail(const int K, const i
 // ---- PBT exploit/explore (tt_pop_exploit): dst's learning state <- src's, then dst's hyperparameters, in one launch ----
 // A pair's copy is 92 regions: per network (critic 12 tensors, then actor 10) and tensor t, its parameters, Adam m, Adam v and
 // target parameters (4 t + {0, 1, 2, 3}), then the four fc2 images (critic net / target, actor net / target).  Each region is cut
-// into EX_CHUNK-byte pieces, one workgroup each; the shapes are the bodies' (23-400-300-1), so the pieces per pair are constants.
+// into EX_CHUNK-byte pieces, one workgroup each (csrc/ttpop_exploit.h: the piece copy, shared with k_pop_td3_exploit).
 // Nothing else is copied: dst's env, ring, noise, step_dev, bias corrections, tail words and scratch buffers stay its own.
 struct ExploitList {
     int n;
     tt_pop_exploit_pair p[TT_POP_MAX_AGENTS];
 };
 
-constexpr int EX_THREADS = 256, EX_UNROLL = 4;
-constexpr size_t EX_CHUNK = (size_t)EX_THREADS * EX_UNROLL * 16;        // bytes per workgroup: 16 KB
 constexpr int EX_TENSOR_REGIONS = 4 * (12 + 10), EX_REGIONS = EX_TENSOR_REGIONS + 4;
 
-__host__ __device__ constexpr int ex_numel(const int t) {                // tensor t of tt_mlp_weights' order
-    return t == 0 ? H1 * IN : t < 4 ? H1 : t == 4 ? H2 * H1 : t < 9 ? H2 : t == 9 ? 1 : H2;
-}
 __host__ __device__ constexpr size_t ex_region_bytes(const int r) {
     return r < EX_TENSOR_REGIONS ? (size_t)ex_numel((r < 48 ? r : r - 48) >> 2) * 4 : IMG_HALVES * 2;
 }
-__host__ __device__ constexpr int ex_region_chunks(const int r) { return (int)((ex_region_bytes(r) + EX_CHUNK - 1) / EX_CHUNK); }
+__host__ __device__ constexpr int ex_region_chunks(const int r) { return ex_chunks(ex_region_bytes(r)); }
 constexpr int ex_chunks_per_pair() {
     int s = 0;
     for (int r = 0; r < EX_REGIONS; ++r) s += ex_region_chunks(r);
     return s;
 }
 constexpr int EX_CHUNKS = ex_chunks_per_pair();
-
-__device__ __forceinline__ float *ex_tensor(const AdamFused &A, const int kind, const int t) {
-    return kind == 0 ? A.p[t] : kind == 1 ? A.m[t] : kind == 2 ? A.v[t] : A.tgt[t];
-}
 
 // grid: pairs x EX_CHUNKS, pair-major.  No pair's dst is another pair's src (tt_pop_exploit checks), so every byte a workgroup reads
 // is written by no workgroup of the launch.  The descriptors' pointers are read, never written; the hyperparameter words are written
@@ -206,37 +198,7 @@ __global__ __launch_bounds__(EX_THREADS) void k_pop_exploit(const ExploitList L,
         to = reinterpret_cast<char *>((i & 1) ? At.img_t : At.img_p);
     }
     if (!from || !to) return;                      // (images off)
-    const size_t bytes = ex_region_bytes(r), lo = (size_t)c * EX_CHUNK, hi = min(bytes, lo + EX_CHUNK);
-    const int tid = threadIdx.x;
-    const size_t mis = reinterpret_cast<uintptr_t>(to) & 15;
-    if (mis != (reinterpret_cast<uintptr_t>(from) & 15)) {         // no common 16-byte alignment: dwords
-        for (size_t o = lo + 4 * tid; o < hi; o += 4 * EX_THREADS)
-            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
-        return;
-    }
-    // 16-byte accesses over [head, head + body) of the region (head: the dwords before the first 16-byte boundary), dwords around
-    const size_t head = (16 - mis) & 15, body = bytes >= head ? (bytes - head) & ~(size_t)15 : 0;
-    if (c == 0) {
-        const size_t tail0 = head + body;
-        for (size_t o = 4 * tid; o < min(head, bytes); o += 4 * EX_THREADS)
-            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
-        for (size_t o = tail0 + 4 * tid; o < bytes; o += 4 * EX_THREADS)
-            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
-    }
-    const f32x4 *src4 = reinterpret_cast<const f32x4 *>(from + head);
-    f32x4 *dst4 = reinterpret_cast<f32x4 *>(to + head);
-    const size_t v_lo = lo / 16, v_hi = min(body, hi) / 16;
-    f32x4 x[EX_UNROLL];
-#pragma unroll
-    for (int u = 0; u < EX_UNROLL; ++u) {
-        const size_t i = v_lo + (size_t)u * EX_THREADS + tid;
-        if (i < v_hi) x[u] = src4[i];
-    }
-#pragma unroll
-    for (int u = 0; u < EX_UNROLL; ++u) {
-        const size_t i = v_lo + (size_t)u * EX_THREADS + tid;
-        if (i < v_hi) dst4[i] = x[u];
-    }
+    ex_copy_piece(from, to, ex_region_bytes(r), c);
 }
 
 // one agent's tt_pop_agent -> PopAgent (host checks only: no HIP call)
@@ -323,50 +285,22 @@ struct tt_population {
 
 // what tt_pop_exploit and tt_pop_exploit_nstep (`who`) refuse in a list of pairs, which goes into L (host only: no HIP call)
 static int check_pairs(const char *who, const tt_population *h, const int pairs, const tt_pop_exploit_pair *list, ExploitList &L) {
-    if (!h) return fail(TT_EINVAL, "%s: handle is NULL", who);
-    if (!list) return fail(TT_EINVAL, "%s: list is NULL", who);
-    const int K = h->K;
-    if (pairs < 1 || pairs > K) return fail(TT_EINVAL, "%s: pairs = %d, not in [1, K = %d]", who, pairs, K);
-    L.n = pairs;
-    for (int i = 0; i < pairs; ++i) {
-        const tt_pop_exploit_pair &q = list[i];
-        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K) return fail(TT_EINVAL, "%s: pair %d names an agent outside [0, K = %d)", who, i, K);
-        for (int j = 0; j < pairs; ++j) {
-            if (j == i) continue;
-            if (list[j].dst == q.dst) return fail(TT_EINVAL, "%s: pairs %d and %d have the same dst", who, i, j);
-            if (list[j].src == q.dst) return fail(TT_EINVAL, "%s: the dst of pair %d is the src of pair %d", who, i, j);
-        }
-        const float h4[4] = {q.alpha, q.beta, q.tau, q.gamma};
-        for (const float x : h4)
-            if (!std::isfinite(x)) return fail(TT_EINVAL, "%s: pair %d has a non-finite hyperparameter", who, i);
-        if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
-            return fail(TT_EINVAL, "%s: pair %d: alpha and beta must lie in (0, 1]", who, i);
-        if (!(q.tau > 0.f && q.tau <= 1.f)) return fail(TT_EINVAL, "%s: pair %d: tau must lie in (0, 1]", who, i);
-        if (!(q.gamma > 0.f && q.gamma < 1.f)) return fail(TT_EINVAL, "%s: pair %d: gamma must lie in (0, 1)", who, i);
-        L.p[i] = q;
-    }
-    return TT_OK;
+    return check_pairs(who, h, pairs, list, L, [](const tt_pop_exploit_pair &) { return true; },
+                       [](const tt_pop_exploit_pair &, int) { return TT_OK; });
 }
 
 extern "C" {
 
 int tt_pop_learn_create(int count, int batch, const tt_pop_agent *agents, tt_population **out) {
-    if (!out) return fail(TT_EINVAL, "tt_pop_learn_create: out is NULL");
-    *out = nullptr;
-    if (count < 1 || count > TT_POP_MAX_AGENTS) return fail(TT_EINVAL, "tt_pop_learn_create: count = %d agents, not in [1, %d]", count, TT_POP_MAX_AGENTS);
-    if (batch < 1 || batch > MAXB) return fail(TT_EINVAL, "tt_pop_learn_create: batch = %d rows, not in [1, %d]", batch, MAXB);
-    if (!agents) return fail(TT_EINVAL, "tt_pop_learn_create: agents is NULL");
+    static const char who[] = "tt_pop_learn_create";
+    if (const int rc = check_create(who, count, batch, agents, out)) return rc;
     std::vector<PopAgent> host(count);
     for (int a = 0; a < count; ++a) {
         const int rc = to_pop_agent(agents[a], a, batch, host[a]);
         if (rc != TT_OK) return rc;
     }
     PopAgent *dev = nullptr;
-    if (hipMalloc(&dev, sizeof(PopAgent) * count) != hipSuccess) return fail(TT_ENOMEM, "tt_pop_learn_create: hipMalloc");
-    if (hipMemcpy(dev, host.data(), sizeof(PopAgent) * count, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dev);
-        return fail(TT_EHIP, "tt_pop_learn_create: hipMemcpy");
-    }
+    if (const int rc = upload_descriptors(who, host, dev)) return rc;
     tt_population *h = new tt_population{count, batch, dev};
     for (int a = 0; a < count; ++a) {
         h->slots.push_back(agents[a].sample->slots);

@@ -23,6 +23,7 @@
 // (K, descriptors, u, full) and is graph-capturable.  `full` is a launch argument, so policy_delay is one value for the whole
 // population; sigma, clip, alpha, beta, tau and gamma are each agent's own.  The sampled-row prologue of the first launch is written
 // out a third time here (k_pop_fwd_multi, k_td3_fwd_multi): the kernels that hold it keep their instructions that way.
+#include "ttpop_exploit.h"
 #include "tttd3.h"
 
 #include <cstddef>
@@ -154,24 +155,20 @@ __global__ __launch_bounds__(64 * NW) void k_pop_td3_actor_tail(const int K, con
 // k_pop_exploit's shape for six networks.  A pair's copy is 142 regions: per trained network (critic 1 and critic 2 with 12 tensors
 // each, then the actor with 10) and tensor t, its parameters, Adam m, Adam v and target parameters (4 t + {0, 1, 2, 3}), then the six
 // fc2 images (network / target of critic 1, critic 2, the actor), each whole: its forward and its backward halves.  Each region is
-// cut into X3_CHUNK-byte pieces, one workgroup each.  Nothing else is copied: dst's env, ring, noise seed, both step counts, both
-// bias-correction buffers, step_snap, tail words and scratch buffers stay its own.
+// cut into EX_CHUNK-byte pieces, one workgroup each (csrc/ttpop_exploit.h: the piece copy, shared with k_pop_exploit).  Nothing else
+// is copied: dst's env, ring, noise seed, both step counts, both bias-correction buffers, step_snap, tail words and scratch buffers
+// stay its own.
 struct Exploit3List {
     int n;
     tt_pop_td3_pair p[TT_POP_MAX_AGENTS];
 };
 
-constexpr int X3_THREADS = 256, X3_UNROLL = 4;
-constexpr size_t X3_CHUNK = (size_t)X3_THREADS * X3_UNROLL * 16;        // bytes per workgroup: 16 KB
 constexpr int X3_CRITIC = 4 * 12, X3_TENSOR_REGIONS = 2 * X3_CRITIC + 4 * 10, X3_REGIONS = X3_TENSOR_REGIONS + 6;
 
-__host__ __device__ constexpr int x3_numel(const int t) {                // tensor t of tt_mlp_weights' order
-    return t == 0 ? H1 * IN : t < 4 ? H1 : t == 4 ? H2 * H1 : t < 9 ? H2 : t == 9 ? 1 : H2;
-}
 __host__ __device__ constexpr size_t x3_region_bytes(const int r) {
-    return r < X3_TENSOR_REGIONS ? (size_t)x3_numel((r % X3_CRITIC) >> 2) * 4 : IMG_HALVES * 2;
+    return r < X3_TENSOR_REGIONS ? (size_t)ex_numel((r % X3_CRITIC) >> 2) * 4 : IMG_HALVES * 2;
 }
-__host__ __device__ constexpr int x3_region_chunks(const int r) { return (int)((x3_region_bytes(r) + X3_CHUNK - 1) / X3_CHUNK); }
+__host__ __device__ constexpr int x3_region_chunks(const int r) { return ex_chunks(x3_region_bytes(r)); }
 constexpr int x3_chunks_per_pair() {
     int s = 0;
     for (int r = 0; r < X3_REGIONS; ++r) s += x3_region_chunks(r);
@@ -179,16 +176,13 @@ constexpr int x3_chunks_per_pair() {
 }
 constexpr int X3_CHUNKS = x3_chunks_per_pair();
 
-__device__ __forceinline__ float *x3_tensor(const AdamFused &A, const int kind, const int t) {
-    return kind == 0 ? A.p[t] : kind == 1 ? A.m[t] : kind == 2 ? A.v[t] : A.tgt[t];
-}
 // trained network i of a descriptor (0, 1: the critics; 2: the actor).  Both variants of a critic hold the same tensors and images.
 __device__ __forceinline__ const AdamFused &x3_net(const Td3Agent &P, const int i) { return i < 2 ? P.Ac[i][0] : P.Aa; }
 
 // grid: pairs x X3_CHUNKS, pair-major.  No pair's dst is another pair's src (tt_pop_td3_exploit checks), so every byte a workgroup
 // reads is written by no workgroup of the launch.  The descriptors' pointers are read, never written; the hyperparameter words are
 // written with plain global stores and read by the later launches on the stream.
-__global__ __launch_bounds__(X3_THREADS) void k_pop_td3_exploit(const Exploit3List L, Td3Agent *__restrict__ D) {
+__global__ __launch_bounds__(EX_THREADS) void k_pop_td3_exploit(const Exploit3List L, Td3Agent *__restrict__ D) {
     const int pair = (int)blockIdx.x / X3_CHUNKS, piece = (int)blockIdx.x - pair * X3_CHUNKS;
     if (pair >= L.n) return;
     const tt_pop_td3_pair q = L.p[pair];
@@ -213,8 +207,8 @@ __global__ __launch_bounds__(X3_THREADS) void k_pop_td3_exploit(const Exploit3Li
     char *to;
     if (r < X3_TENSOR_REGIONS) {
         const int net = r / X3_CRITIC, local = r - net * X3_CRITIC, t = local >> 2, kind = local & 3;
-        from = reinterpret_cast<const char *>(x3_tensor(x3_net(S, net), kind, t));
-        to = reinterpret_cast<char *>(x3_tensor(x3_net(T, net), kind, t));
+        from = reinterpret_cast<const char *>(ex_tensor(x3_net(S, net), kind, t));
+        to = reinterpret_cast<char *>(ex_tensor(x3_net(T, net), kind, t));
     } else {
         const int i = r - X3_TENSOR_REGIONS;
         const AdamFused &As = x3_net(S, i >> 1), &At = x3_net(T, i >> 1);
@@ -222,37 +216,7 @@ __global__ __launch_bounds__(X3_THREADS) void k_pop_td3_exploit(const Exploit3Li
         to = reinterpret_cast<char *>((i & 1) ? At.img_t : At.img_p);
     }
     if (!from || !to) return;                      // (images off)
-    const size_t bytes = x3_region_bytes(r), lo = (size_t)c * X3_CHUNK, hi = min(bytes, lo + X3_CHUNK);
-    const int tid = threadIdx.x;
-    const size_t mis = reinterpret_cast<uintptr_t>(to) & 15;
-    if (mis != (reinterpret_cast<uintptr_t>(from) & 15)) {         // no common 16-byte alignment: dwords
-        for (size_t o = lo + 4 * tid; o < hi; o += 4 * X3_THREADS)
-            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
-        return;
-    }
-    // 16-byte accesses over [head, head + body) of the region (head: the dwords before the first 16-byte boundary), dwords around
-    const size_t head = (16 - mis) & 15, body = bytes >= head ? (bytes - head) & ~(size_t)15 : 0;
-    if (c == 0) {
-        const size_t tail0 = head + body;
-        for (size_t o = 4 * tid; o < min(head, bytes); o += 4 * X3_THREADS)
-            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
-        for (size_t o = tail0 + 4 * tid; o < bytes; o += 4 * X3_THREADS)
-            *reinterpret_cast<float *>(to + o) = *reinterpret_cast<const float *>(from + o);
-    }
-    const f32x4 *src4 = reinterpret_cast<const f32x4 *>(from + head);
-    f32x4 *dst4 = reinterpret_cast<f32x4 *>(to + head);
-    const size_t v_lo = lo / 16, v_hi = min(body, hi) / 16;
-    f32x4 x[X3_UNROLL];
-#pragma unroll
-    for (int k = 0; k < X3_UNROLL; ++k) {
-        const size_t i = v_lo + (size_t)k * X3_THREADS + tid;
-        if (i < v_hi) x[k] = src4[i];
-    }
-#pragma unroll
-    for (int k = 0; k < X3_UNROLL; ++k) {
-        const size_t i = v_lo + (size_t)k * X3_THREADS + tid;
-        if (i < v_hi) dst4[i] = x[k];
-    }
+    ex_copy_piece(from, to, x3_region_bytes(r), c);
 }
 
 // what two agents of one population may not share (host only: no HIP call): each list holds one agent's addresses of a kind
@@ -280,11 +244,8 @@ struct tt_pop_td3 {
 extern "C" {
 
 int tt_pop_td3_create(int count, int batch, const tt_td3_agent *agents, tt_pop_td3 **out) {
-    if (!out) return fail(TT_EINVAL, "tt_pop_td3_create: out is NULL");
-    *out = nullptr;
-    if (count < 1 || count > TT_POP_MAX_AGENTS) return fail(TT_EINVAL, "tt_pop_td3_create: count = %d agents, not in [1, %d]", count, TT_POP_MAX_AGENTS);
-    if (batch < 1 || batch > MAXB) return fail(TT_EINVAL, "tt_pop_td3_create: batch = %d rows, not in [1, %d]", batch, MAXB);
-    if (!agents) return fail(TT_EINVAL, "tt_pop_td3_create: agents is NULL");
+    static const char who[] = "tt_pop_td3_create";
+    if (const int rc = check_create(who, count, batch, agents, out)) return rc;
     std::vector<Td3Agent> host(count);
     for (int a = 0; a < count; ++a) {
         const int rc = to_td3_agent(agents[a], a, batch, host[a]);
@@ -299,11 +260,7 @@ int tt_pop_td3_create(int count, int batch, const tt_td3_agent *agents, tt_pop_t
             if (overlap(x.grads, y.grads)) return fail(TT_EINVAL, "tt_pop_td3_create: agents %d and %d share a gradient buffer", a, b);
         }
     Td3Agent *dev = nullptr;
-    if (hipMalloc(&dev, sizeof(Td3Agent) * count) != hipSuccess) return fail(TT_ENOMEM, "tt_pop_td3_create: hipMalloc");
-    if (hipMemcpy(dev, host.data(), sizeof(Td3Agent) * count, hipMemcpyHostToDevice) != hipSuccess) {
-        (void)hipFree(dev);
-        return fail(TT_EHIP, "tt_pop_td3_create: hipMemcpy");
-    }
+    if (const int rc = upload_descriptors(who, host, dev)) return rc;
     *out = new tt_pop_td3{count, batch, dev};
     return TT_OK;
 }
@@ -321,31 +278,15 @@ int tt_pop_td3_learn(tt_pop_td3 *h, int update, int full, tt_stream_t stream) {
 
 int tt_pop_td3_exploit(tt_pop_td3 *h, int pairs, const tt_pop_td3_pair *list, tt_stream_t stream) {
     static const char who[] = "tt_pop_td3_exploit";
-    if (!h) return fail(TT_EINVAL, "%s: handle is NULL", who);
-    if (!list) return fail(TT_EINVAL, "%s: list is NULL", who);
-    const int K = h->K;
-    if (pairs < 1 || pairs > K) return fail(TT_EINVAL, "%s: pairs = %d, not in [1, K = %d]", who, pairs, K);
     Exploit3List L{};
-    L.n = pairs;
-    for (int i = 0; i < pairs; ++i) {
-        const tt_pop_td3_pair &q = list[i];
-        if (q.dst < 0 || q.dst >= K || q.src < 0 || q.src >= K) return fail(TT_EINVAL, "%s: pair %d names an agent outside [0, K = %d)", who, i, K);
-        for (int j = 0; j < pairs; ++j) {
-            if (j == i) continue;
-            if (list[j].dst == q.dst) return fail(TT_EINVAL, "%s: pairs %d and %d have the same dst", who, i, j);
-            if (list[j].src == q.dst) return fail(TT_EINVAL, "%s: the dst of pair %d is the src of pair %d", who, i, j);
-        }
-        const float h6[6] = {q.alpha, q.beta, q.tau, q.gamma, q.target_noise, q.noise_clip};
-        for (const float x : h6)
-            if (!std::isfinite(x)) return fail(TT_EINVAL, "%s: pair %d has a non-finite hyperparameter", who, i);
-        if (!(q.alpha > 0.f && q.alpha <= 1.f) || !(q.beta > 0.f && q.beta <= 1.f))
-            return fail(TT_EINVAL, "%s: pair %d: alpha and beta must lie in (0, 1]", who, i);
-        if (!(q.tau > 0.f && q.tau <= 1.f)) return fail(TT_EINVAL, "%s: pair %d: tau must lie in (0, 1]", who, i);
-        if (!(q.gamma > 0.f && q.gamma < 1.f)) return fail(TT_EINVAL, "%s: pair %d: gamma must lie in (0, 1)", who, i);
-        if (q.target_noise < 0.f || q.noise_clip < 0.f) return fail(TT_EINVAL, "%s: pair %d: target_noise and noise_clip must not be negative", who, i);
-        L.p[i] = q;
-    }
-    hipLaunchKernelGGL(k_pop_td3_exploit, dim3(pairs * X3_CHUNKS), dim3(X3_THREADS), 0, stream, L, h->dev);
+    const int rc = check_pairs(
+        who, h, pairs, list, L, [](const tt_pop_td3_pair &q) { return std::isfinite(q.target_noise) && std::isfinite(q.noise_clip); },
+        [](const tt_pop_td3_pair &q, const int i) {
+            if (q.target_noise < 0.f || q.noise_clip < 0.f) return fail(TT_EINVAL, "%s: pair %d: target_noise and noise_clip must not be negative", who, i);
+            return (int)TT_OK;
+        });
+    if (rc != TT_OK) return rc;
+    hipLaunchKernelGGL(k_pop_td3_exploit, dim3(pairs * X3_CHUNKS), dim3(EX_THREADS), 0, stream, L, h->dev);
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
 }
 

@@ -491,6 +491,14 @@ class FusedLearner:
                            q_out=self.q_t.data_ptr(), step_dev=self.step_dev.data_ptr(), window_dev=L.ptr(window_dev),
                            bias_corr_out=self.bias_corr.data_ptr(), adam_beta1=self.hyp_critic[1], adam_beta2=self.hyp_critic[2])
 
+    def pop_net(self, st, ws, hyp):
+        """One trained network's tt_pop_net from its _NetState, per-row workspace and optimizer hyperparameters: what a
+        population's descriptors (PopulationLearner) and TD3's (td3.TD3Learner) hold per network."""
+        lr, b1, b2, eps, wd = hyp
+        return L.TTPopNet(C.pointer(ws), C.pointer(st.gstruct), st.count, 0, C.cast(st.a_p, C.c_void_p), C.cast(st.a_m, C.c_void_p),
+                          C.cast(st.a_v, C.c_void_p), C.cast(st.a_t, C.c_void_p), lr, b1, b2, eps, wd, self.agent.tau,
+                          C.pointer(st.images) if st.images is not None else None)
+
     def _rows(self, rewards, done_u8, window_dev=None, image=None, n_step=1):
         """learn()'s per-row backward launch (tt_mlp_backward_rows_pair) after the forwards of phase_a."""
         ag, B = self.agent, self.B

@@ -41,7 +41,115 @@ def _refuse_loss_shape(loss_shape, agents=()):
             check_loss_shape(shape, population=True)
 
 
-class PopulationLearner:
+class _PopulationLearnerBase:
+    """What the population learners of DDPG (PopulationLearner) and TD3 (td3.PopulationTD3Learner) share: K agents, each with the
+    state of a fused learner of its own, whose updates are launched together through one handle of the library.  The handle is made
+    at the first eager learn(); every buffer and parameter storage must stay where it is from then on.  A subclass names its C
+    entry points and its hyperparameters, makes the handle (_create), launches (learn(), after _ready()) and fills in exploit()'s
+    three hooks."""
+
+    HYPERS = ("alpha", "beta", "tau", "gamma")         # what a pair of exploit() may set and hyper() reads, in the C order
+    _DESTROY, _HYPER = "tt_pop_learn_destroy", "tt_pop_hyper"
+
+    def __init__(self, agents, batch_size, rings, seeds):
+        self.K, self.B = len(agents), int(batch_size)
+        if not 1 <= self.K <= L.POP_MAX_AGENTS:
+            raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
+        if rings is None or seeds is None or len(rings) != self.K or len(seeds) != self.K:
+            raise ValueError("one ring and one seed per agent")
+        self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
+        self._h = self._key = None
+
+    def _adopt(self, learners):
+        self.lib = L.load()
+        self.learners = list(learners)
+        for ag, fl in zip(self.agents, self.learners):
+            ag.fused_learner = fl          # (checkpoint.py exports the moments through it)
+
+    def __del__(self):
+        if getattr(self, "_h", None) is not None and L._lib is not None:
+            torch.cuda.synchronize()
+            getattr(L._lib, self._DESTROY)(self._h)
+        self._h = None
+
+    def _storage_key(self):
+        return tuple(p.data_ptr() for fl in self.learners for n in fl._nets() for p in n.parameters())
+
+    def _need_handle(self, what):
+        if self._h is None:
+            raise RuntimeError(f"{type(self).__name__}.{what}: no learn() has made the population's descriptors yet")
+
+    def refresh_images(self):
+        for fl in self.learners:
+            FusedLearner.refresh_images(fl)        # (the images alone: TD3Learner's own would make a lone descriptor)
+
+    def _ready(self):
+        """What learn() does before its launches: the handle at the first eager call, and the images of fc2 tensors someone else
+        wrote.  A capture holds launches only."""
+        capturing, name = torch.cuda.is_current_stream_capturing(), type(self).__name__
+        if self._h is None:
+            if capturing:
+                raise RuntimeError(f"{name}: run one eager learn() before capturing it")
+            self._create()
+            self._key = self._storage_key()
+        elif self._key != self._storage_key():
+            raise RuntimeError(f"{name}: a network's parameter storage moved since the descriptors were made")
+        if not capturing:
+            self.refresh_images()
+
+    def tail_gave_up(self):
+        """[agent: 0, or the step whose tail hand-over was abandoned] (host memory only)."""
+        return [fl.tail_gave_up() for fl in self.learners]
+
+    def state_dict(self, a):
+        """Agent a's Adam moments and step count(s), in the format of its learner's state_dict()."""
+        return self.learners[a].state_dict()
+
+    def _hyper_of(self, a):
+        """Agent a's HYPERS as the host holds them."""
+        return {k: getattr(self.agents[a], k) for k in self.HYPERS}
+
+    def exploit(self, pairs):
+        """Population-based training's exploit/explore step, one launch on the current stream: pairs = [(dst, src, {HYPERS})].
+        dst != src: dst's networks, Adam moments and fc2 images become src's; every dst then takes the given hyperparameters (a
+        missing key: src's value).  The host mirrors -- agent.alpha / beta / tau / gamma, the torch optimizers' lr, the learner's
+        hyp_actor / hyp_critic and what the subclass adds -- follow, so a checkpoint sees the new values.  Captured launches stay
+        valid: the descriptors change in place."""
+        self._need_handle("exploit")
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{type(self).__name__}.exploit: not while capturing (it runs between vector steps)")
+        pairs = list(pairs)
+        if not 1 <= len(pairs) <= self.K:
+            raise ValueError(f"exploit: 1 to {self.K} pairs, not {len(pairs)}")
+        self.refresh_images()          # (src's images must hold its weights: they are copied with them)
+        new = []
+        for i, (dst, src, hyp) in enumerate(pairs):
+            dst, src = int(dst), int(src)
+            if not (0 <= dst < self.K and 0 <= src < self.K):
+                raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
+            n = self._pair_n_step(i, dst, src, hyp)
+            of_src = self._hyper_of(src)
+            new.append((dst, src, {k: float(hyp.get(k, of_src[k])) for k in self.HYPERS}, n))
+        self._launch_exploit(new)
+        for dst, _, h, n in new:
+            ag, fl = self.agents[dst], self.learners[dst]
+            ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
+            ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
+            ag.critic.optimizer.param_groups[0]["lr"] = h["beta"]
+            fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
+            fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
+            self._mirror(dst, h, n)
+
+    def hyper(self, a):
+        """Agent a's {HYPERS} as the device descriptors hold them (synchronises)."""
+        self._need_handle("hyper")
+        out = (C.c_float * len(self.HYPERS))()
+        torch.cuda.synchronize()
+        L.check(getattr(self.lib, self._HYPER)(self._h, int(a), C.byref(out)))
+        return dict(zip(self.HYPERS, (float(x) for x in out)))
+
+
+class PopulationLearner(_PopulationLearnerBase):
     """learn() of K agents, each with the state of a FusedLearner of its own (Adam moments, step_dev, bias corrections, tail words,
     fc2 images), launched together.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys (update u of a vector
     step draws with seed + u * _SEED_STRIDE, the lone loop's sampling key).  The device descriptors are made at the first learn():
@@ -51,16 +159,15 @@ class PopulationLearner:
     n-step kernel for good.  Host mirrors: self.n_steps, and each agent's ring.n_step.
     learn_log: None, or the capacity per agent of the learn log (fused_learn.LearnLog; include/ttenv.h: tt_learn_log_*): learn()
     then ends with one more launch that leaves a record of every agent's update whose step count is a multiple of learn_log_every,
-    and drain_learn_log() collects them.  One K-agent handle, made with the descriptors.  Not part of any checkpoint."""
+    and drain_learn_log() collects them.  One K-agent handle, made with the descriptors.  Not part of any checkpoint.
+    exploit() (include/ttenv.h: tt_pop_exploit): a pair's dict may also hold "n_step" (missing: src's): on an n-step population dst
+    then draws with that n and the pair's gamma and discounts with gamma ** n (tt_pop_exploit_nstep); a population without the
+    table refuses an n other than 1."""
 
     def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1,
                  loss_shape=None):
         _refuse_loss_shape(loss_shape, agents)
-        self.K, self.B = len(agents), int(batch_size)
-        if not 1 <= self.K <= L.POP_MAX_AGENTS:
-            raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
-        if rings is None or seeds is None or len(rings) != self.K or len(seeds) != self.K:
-            raise ValueError("one ring and one seed per agent")
+        super().__init__(agents, batch_size, rings, seeds)
         if any(r._side_struct() is not None for r in rings):
             raise ValueError("expert side buffers are not supported in a population")
         self.n_steps = [check_n_step(n) for n in _per_agent(1 if n_steps is None else n_steps, self.K, "n_steps")]
@@ -71,46 +178,24 @@ class PopulationLearner:
                                  f"steps with their n steps intact needs at least {slots_needed(n)} slots")
         self._learn_log_args = check_learn_log(learn_log, learn_log_every) if learn_log is not None else None
         self.learn_log = None
-        self.lib = L.load()
-        self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
         for ring, n in zip(self.rings, self.n_steps):
             ring.n_step = n                # (load_side refuses tuples an n-step draw cannot use)
-        self.learners = [FusedLearner(ag, self.B, fc2_images) for ag in self.agents]
-        for ag, fl in zip(self.agents, self.learners):
-            ag.fused_learner = fl          # (checkpoint.py exports the moments through it)
-        self._h = None
-        self._key = None
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None and L._lib is not None:
-            torch.cuda.synchronize()
-            L._lib.tt_pop_learn_destroy(self._h)
-
-    def _storage_key(self):
-        return tuple(p.data_ptr() for ag in self.agents for n in (ag.actor, ag.critic, ag.target_actor, ag.target_critic)
-                     for p in n.parameters())
+        self._adopt(FusedLearner(ag, self.B, fc2_images) for ag in self.agents)
 
     def _create(self):
         B, keep = self.B, []
         arr = (L.TTPopAgent * self.K)()
         for a, (fl, ring, seed) in enumerate(zip(self.learners, self.rings, self.seeds)):
-            ag = fl.agent
             sample = ring.sample_args(B, seed=seed, seed_stride=_SEED_STRIDE)
             s, act, r, s2, d = ring._batch_bufs(B)[:5]
             jobs, td = fl.fwd_jobs(s, act, s2), fl.td_input(r, d, n_step=self.n_steps[a])
-
-            def net(st, ws, hyp):
-                lr, b1, b2, eps, wd = hyp
-                return L.TTPopNet(C.pointer(ws), C.pointer(st.gstruct), st.count, 0, C.cast(st.a_p, C.c_void_p),
-                                  C.cast(st.a_m, C.c_void_p), C.cast(st.a_v, C.c_void_p), C.cast(st.a_t, C.c_void_p),
-                                  lr, b1, b2, eps, wd, ag.tau, C.pointer(st.images) if st.images is not None else None)
-            arr[a] = L.TTPopAgent(C.pointer(sample), jobs, C.pointer(td), net(fl.critic, fl.ws, fl.hyp_critic),
-                                  net(fl.actor, fl.ws_actor, fl.hyp_actor), fl.q_pi.data_ptr(), fl.dq_da.data_ptr(),
+            arr[a] = L.TTPopAgent(C.pointer(sample), jobs, C.pointer(td), fl.pop_net(fl.critic, fl.ws, fl.hyp_critic),
+                                  fl.pop_net(fl.actor, fl.ws_actor, fl.hyp_actor), fl.q_pi.data_ptr(), fl.dq_da.data_ptr(),
                                   fl.tail_words.data_ptr(), fl.tail_gave_up_host.data_ptr())
             keep += [sample, jobs, td]
         h = C.c_void_p()
         L.check(self.lib.tt_pop_learn_create(self.K, B, arr, C.byref(h)))      # (copies everything: `keep` may go now)
-        self._h, self._key = h, self._storage_key()
+        self._h = h
         if self.nstep_table:
             ns = (L.TTPopNstep * self.K)(*[self._nstep_struct(ag.gamma, n) for ag, n in zip(self.agents, self.n_steps)])
             L.check(self.lib.tt_pop_learn_set_nstep(h, ns))
@@ -121,21 +206,9 @@ class PopulationLearner:
     def _nstep_struct(gamma, n):
         return L.TTPopNstep(int(n), float(gamma), nstep_discount(gamma, n))
 
-    def refresh_images(self):
-        for fl in self.learners:
-            fl.refresh_images()
-
     def learn(self, u=0):
         """Update u of the running vector step for every agent, enqueued on the current stream (capturable once created)."""
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self._h is None:
-            if capturing:
-                raise RuntimeError("PopulationLearner: run one eager learn() before capturing it")
-            self._create()
-        elif self._key != self._storage_key():
-            raise RuntimeError("PopulationLearner: a network's parameter storage moved since the descriptors were made")
-        if not capturing:
-            self.refresh_images()
+        self._ready()
         L.check(self.lib.tt_pop_learn(self._h, int(u), L.stream()))
         if self.learn_log is not None:
             self.learn_log.append()
@@ -149,75 +222,30 @@ class PopulationLearner:
             return [_no_records() for _ in range(self.K)]
         return [self.learn_log.drain(a) for a in range(self.K)]
 
-    def tail_gave_up(self):
-        """[agent: 0, or the learn step whose tail hand-over was abandoned] (host memory only)."""
-        return [fl.tail_gave_up() for fl in self.learners]
+    def _pair_n_step(self, i, dst, src, hyp):
+        n = check_n_step(hyp.get("n_step", self.n_steps[src]))
+        if not self.nstep_table and n != 1:
+            raise ValueError(f"exploit: pair {i} sets n_step = {n}, but this population was built without n-step returns "
+                             "(PopulationLearner(n_steps=...))")
+        if self.rings[dst].slots < slots_needed(n):
+            raise ValueError(f"exploit: pair {i}: n_step = {n} needs a ring of {slots_needed(n)} slots, agent {dst}'s has "
+                             f"{self.rings[dst].slots}")
+        return n
 
-    def state_dict(self, a):
-        """Agent a's Adam moments and step count, in FusedLearner.state_dict()'s format."""
-        return self.learners[a].state_dict()
-
-    def exploit(self, pairs):
-        """Population-based training's exploit/explore step (include/ttenv.h: tt_pop_exploit), one launch on the current stream:
-        pairs = [(dst, src, {"alpha", "beta", "tau", "gamma"})].  dst != src: dst's four networks, Adam moments and fc2 images
-        become src's; every dst then takes the given hyperparameters (a missing key: src's value).  The host mirrors --
-        agent.alpha / beta / tau / gamma, the torch optimizers' lr, FusedLearner.hyp_actor / hyp_critic -- follow, so a checkpoint
-        or a later _create sees the new values.  Captured launches stay valid: the descriptors change in place.
-        A pair's dict may also hold "n_step" (missing: src's): on an n-step population dst then draws with that n and the pair's
-        gamma and discounts with gamma ** n (tt_pop_exploit_nstep); a population without the table refuses an n other than 1."""
-        if self._h is None:
-            raise RuntimeError("PopulationLearner.exploit: no learn() has made the population's descriptors yet")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("PopulationLearner.exploit: not while capturing (it runs between vector steps)")
-        pairs = list(pairs)
-        if not 1 <= len(pairs) <= self.K:
-            raise ValueError(f"exploit: 1 to {self.K} pairs, not {len(pairs)}")
-        self.refresh_images()          # (src's images must hold its weights: they are copied with them)
-        arr = (L.TTPopExploitPair * len(pairs))()
-        ns = (L.TTPopNstep * len(pairs))()
-        new = []
-        for i, (dst, src, hyp) in enumerate(pairs):
-            dst, src = int(dst), int(src)
-            if not (0 <= dst < self.K and 0 <= src < self.K):
-                raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
-            h = {k: float(hyp.get(k, getattr(self.agents[src], k))) for k in ("alpha", "beta", "tau", "gamma")}
-            n = check_n_step(hyp.get("n_step", self.n_steps[src]))
-            if not self.nstep_table and n != 1:
-                raise ValueError(f"exploit: pair {i} sets n_step = {n}, but this population was built without n-step returns "
-                                 "(PopulationLearner(n_steps=...))")
-            if self.rings[dst].slots < slots_needed(n):
-                raise ValueError(f"exploit: pair {i}: n_step = {n} needs a ring of {slots_needed(n)} slots, agent {dst}'s has "
-                                 f"{self.rings[dst].slots}")
-            arr[i] = L.TTPopExploitPair(dst, src, h["alpha"], h["beta"], h["tau"], h["gamma"])
-            ns[i] = self._nstep_struct(h["gamma"], n)
-            new.append((dst, h, n))
-        stream = L.stream()
+    def _launch_exploit(self, new):
+        arr = (L.TTPopExploitPair * len(new))(*[L.TTPopExploitPair(dst, src, *[h[k] for k in self.HYPERS]) for dst, src, h, _ in new])
         if self.nstep_table:
-            L.check(self.lib.tt_pop_exploit_nstep(self._h, len(pairs), arr, ns, stream))
+            ns = (L.TTPopNstep * len(new))(*[self._nstep_struct(h["gamma"], n) for _, _, h, n in new])
+            L.check(self.lib.tt_pop_exploit_nstep(self._h, len(new), arr, ns, L.stream()))
         else:
-            L.check(self.lib.tt_pop_exploit(self._h, len(pairs), arr, stream))
-        for dst, h, n in new:
-            self.n_steps[dst] = self.rings[dst].n_step = n
-            ag, fl = self.agents[dst], self.learners[dst]
-            ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
-            ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
-            ag.critic.optimizer.param_groups[0]["lr"] = h["beta"]
-            fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
-            fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
+            L.check(self.lib.tt_pop_exploit(self._h, len(new), arr, L.stream()))
 
-    def hyper(self, a):
-        """Agent a's {"alpha", "beta", "tau", "gamma"} as the device descriptors hold them (synchronises)."""
-        if self._h is None:
-            raise RuntimeError("PopulationLearner.hyper: no learn() has made the population's descriptors yet")
-        out = (C.c_float * 4)()
-        torch.cuda.synchronize()
-        L.check(self.lib.tt_pop_hyper(self._h, int(a), C.byref(out)))
-        return dict(zip(("alpha", "beta", "tau", "gamma"), (float(x) for x in out)))
+    def _mirror(self, dst, h, n):
+        self.n_steps[dst] = self.rings[dst].n_step = n
 
     def n_step_of(self, a):
         """Agent a's (n_step, gamma, discount) as the device holds them (include/ttenv.h: tt_pop_nstep; synchronises)."""
-        if self._h is None:
-            raise RuntimeError("PopulationLearner.n_step_of: no learn() has made the population's descriptors yet")
+        self._need_handle("n_step_of")
         out = L.TTPopNstep()
         torch.cuda.synchronize()
         L.check(self.lib.tt_pop_nstep(self._h, int(a), C.byref(out)))

@@ -15,6 +15,7 @@ import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner, _NetState
+from ddpg_trucktrailer_amd.population import _PopulationLearnerBase
 
 
 class TD3Config:
@@ -144,10 +145,7 @@ class TD3Learner(FusedLearner):
             arr = lambda ts: (C.c_void_p * st.count)(*[t.data_ptr() for t in ts])
             st.a_p, st.a_t = arr(st.params), arr(st.targets)          # (a parameter storage may have moved)
             st.images = self._images_of(st)
-            lr, b1, b2, eps, wd = hyp
-            nets.append(L.TTPopNet(C.pointer(ws), C.pointer(st.gstruct), st.count, 0, C.cast(st.a_p, C.c_void_p),
-                                   C.cast(st.a_m, C.c_void_p), C.cast(st.a_v, C.c_void_p), C.cast(st.a_t, C.c_void_p),
-                                   lr, b1, b2, eps, wd, ag.tau, C.pointer(st.images) if st.images is not None else None))
+            nets.append(self.pop_net(st, ws, hyp))
         desc = L.TTTd3Agent(C.pointer(sample), jobs, C.pointer(td), nets[0], nets[1], nets[2], self.z_t2.data_ptr(),
                             C.pointer(self.w(ag.target_critic_2)), self.cfg.target_noise, self.cfg.noise_clip, self.noise_seed,
                             self.eps.data_ptr(), self.y2.data_ptr(), self.q2t.data_ptr(), self.step_snap.data_ptr(),
@@ -252,42 +250,29 @@ class TD3Learner(FusedLearner):
 HYPERS6 = ("alpha", "beta", "tau", "gamma", "target_noise", "noise_clip")
 
 
-class PopulationTD3Learner:
+class PopulationTD3Learner(_PopulationLearnerBase):
     """The TD3 updates of K agents launched together (include/ttenv.h: tt_pop_td3_*): each agent has the state of a TD3Learner of
     its own -- buffers, Adam moments, both step counts, tail words, fc2 images, checkpoint format -- and those learners never make
     lone descriptors; the population's one handle is made at the first eager learn(), from then on every buffer and parameter
     storage must stay where it is.  rings / seeds: agent a's TrajectoryRing and the seed of its sampling keys; noise_seeds: the
     seeds of the smoothing noise (None: the sampling seeds, as in a lone loop).  agents[a].td3 holds agent a's target_noise and
-    noise_clip; policy_delay is one value for all, since `full` is an argument of the shared launches."""
+    noise_clip; policy_delay is one value for all, since `full` is an argument of the shared launches.
+    exploit() (include/ttenv.h: tt_pop_td3_exploit) copies six networks, three Adam moment pairs and six fc2 images; a pair's dict
+    may hold the six HYPERS6, and the mirrors include the second critic's optimizer lr, hyp_critic_2 and the learner's TD3Config."""
+
+    HYPERS = HYPERS6
+    _DESTROY, _HYPER = "tt_pop_td3_destroy", "tt_pop_td3_hyper"
 
     def __init__(self, agents, batch_size, rings, seeds, noise_seeds=None, fc2_images=None):
-        self.K, self.B = len(agents), int(batch_size)
-        if not 1 <= self.K <= L.POP_MAX_AGENTS:
-            raise ValueError(f"a population has 1 to {L.POP_MAX_AGENTS} agents, not {self.K}")
-        if rings is None or seeds is None or len(rings) != self.K or len(seeds) != self.K:
-            raise ValueError("one ring and one seed per agent")
+        super().__init__(agents, batch_size, rings, seeds)
         if noise_seeds is not None and len(noise_seeds) != self.K:
             raise ValueError("one noise seed per agent")
         if any(getattr(ag, "td3", None) is None for ag in agents):
             raise ValueError("PopulationTD3Learner needs agents built with Agent(td3=TD3Config(...))")
         self.policy_delay = same_policy_delay([ag.td3 for ag in agents])
-        self.lib = L.load()
-        self.agents, self.rings, self.seeds = list(agents), list(rings), [int(s) for s in seeds]
-        self.learners = [TD3Learner(ag, self.B, ring, seed, fc2_images, None if noise_seeds is None else noise_seeds[a])
-                         for a, (ag, ring, seed) in enumerate(zip(self.agents, self.rings, self.seeds))]
-        for ag, fl in zip(self.agents, self.learners):
-            ag.fused_learner = fl          # (checkpoint.py exports the moments through it)
+        self._adopt(TD3Learner(ag, self.B, ring, seed, fc2_images, None if noise_seeds is None else noise_seeds[a])
+                    for a, (ag, ring, seed) in enumerate(zip(self.agents, self.rings, self.seeds)))
         self.updates = 0                   # learn() calls, for the delay when `full` is left to this learner
-        self._h = self._key = None
-
-    def __del__(self):
-        if getattr(self, "_h", None) is not None and L._lib is not None:
-            torch.cuda.synchronize()
-            L._lib.tt_pop_td3_destroy(self._h)
-        self._h = None
-
-    def _storage_key(self):
-        return tuple(k for fl in self.learners for k in fl._storage_key())
 
     def _create(self):
         arr, keep = (L.TTTd3Agent * self.K)(), []
@@ -297,88 +282,36 @@ class PopulationTD3Learner:
             keep += [desc, objs]
         h = C.c_void_p()
         L.check(self.lib.tt_pop_td3_create(self.K, self.B, arr, C.byref(h)))      # (copies everything: `keep` may go now)
-        self._h, self._key = h, self._storage_key()
-
-    def refresh_images(self):
-        for fl in self.learners:
-            FusedLearner.refresh_images(fl)        # (the images alone: TD3Learner's own would make a lone descriptor)
+        self._h = h
 
     def learn(self, u=0, full=None):
         """Update u of the running vector step for every agent, enqueued on the current stream (capturable once created).  full:
         None = every policy_delay-th learn() by this learner's own count, as TD3Learner counts; else this update is full (True) or
         critic-only (False) for the whole population."""
-        capturing = torch.cuda.is_current_stream_capturing()
-        if self._h is None:
-            if capturing:
-                raise RuntimeError("PopulationTD3Learner: run one eager learn() before capturing it")
-            self.refresh_images()
-            self._create()
-        else:
-            if self._key != self._storage_key():
-                raise RuntimeError("PopulationTD3Learner: a network's parameter storage moved since the descriptors were made")
-            if not capturing:
-                self.refresh_images()
+        self._ready()
         self.updates += 1
         if full is None:
             full = self.updates % self.policy_delay == 0
         L.check(self.lib.tt_pop_td3_learn(self._h, int(u), 1 if full else 0, L.stream()))
 
-    def tail_gave_up(self):
-        """[agent: 0, or the actor step whose tail hand-over was abandoned] (host memory only)."""
-        return [fl.tail_gave_up() for fl in self.learners]
+    def _hyper_of(self, a):
+        cfg = self.learners[a].cfg
+        return dict({k: getattr(self.agents[a], k) for k in HYPERS6[:4]}, target_noise=cfg.target_noise, noise_clip=cfg.noise_clip)
 
-    def state_dict(self, a):
-        """Agent a's Adam moments and step counts, in TD3Learner.state_dict()'s format."""
-        return self.learners[a].state_dict()
+    def _pair_n_step(self, i, dst, src, hyp):
+        if int(hyp.get("n_step", 1)) != 1:
+            raise ValueError(f"exploit: pair {i} sets n_step = {hyp['n_step']}: n-step returns are not supported with td3")
+        return 1
 
-    def _need_handle(self, what):
-        if self._h is None:
-            raise RuntimeError(f"PopulationTD3Learner.{what}: no learn() has made the population's descriptors yet")
+    def _launch_exploit(self, new):
+        arr = (L.TTPopTd3Pair * len(new))(*[L.TTPopTd3Pair(dst, src, *[h[k] for k in HYPERS6]) for dst, src, h, _ in new])
+        L.check(self.lib.tt_pop_td3_exploit(self._h, len(new), arr, L.stream()))
 
-    def exploit(self, pairs):
-        """PBT's exploit/explore step (include/ttenv.h: tt_pop_td3_exploit), one launch on the current stream: pairs = [(dst, src,
-        {"alpha", "beta", "tau", "gamma", "target_noise", "noise_clip"})].  dst != src: dst's six networks, three Adam moment pairs
-        and fc2 images become src's; every dst then takes the given hyperparameters (a missing key: src's value).  The host mirrors
-        -- agent.alpha / beta / tau / gamma, the three torch optimizers' lr, hyp_actor / hyp_critic / hyp_critic_2 and the
-        learner's TD3Config noise values -- follow.  Captured launches stay valid: the descriptors change in place."""
-        self._need_handle("exploit")
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("PopulationTD3Learner.exploit: not while capturing (it runs between vector steps)")
-        pairs = list(pairs)
-        if not 1 <= len(pairs) <= self.K:
-            raise ValueError(f"exploit: 1 to {self.K} pairs, not {len(pairs)}")
-        self.refresh_images()          # (src's images must hold its weights: they are copied with them)
-        arr, new = (L.TTPopTd3Pair * len(pairs))(), []
-        for i, (dst, src, hyp) in enumerate(pairs):
-            dst, src = int(dst), int(src)
-            if not (0 <= dst < self.K and 0 <= src < self.K):
-                raise ValueError(f"exploit: pair {i} ({dst} <- {src}) names an agent outside [0, {self.K})")
-            if int(hyp.get("n_step", 1)) != 1:
-                raise ValueError(f"exploit: pair {i} sets n_step = {hyp['n_step']}: n-step returns are not supported with td3")
-            of_src = {k: getattr(self.agents[src], k) for k in HYPERS6[:4]}
-            of_src["target_noise"], of_src["noise_clip"] = self.learners[src].cfg.target_noise, self.learners[src].cfg.noise_clip
-            h = {k: float(hyp.get(k, of_src[k])) for k in HYPERS6}
-            arr[i] = L.TTPopTd3Pair(dst, src, *[h[k] for k in HYPERS6])
-            new.append((dst, h))
-        L.check(self.lib.tt_pop_td3_exploit(self._h, len(pairs), arr, L.stream()))
-        for dst, h in new:
-            ag, fl = self.agents[dst], self.learners[dst]
-            ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
-            ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
-            ag.critic.optimizer.param_groups[0]["lr"] = ag.critic_2.optimizer.param_groups[0]["lr"] = h["beta"]
-            fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
-            fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
-            fl.hyp_critic_2 = (h["beta"],) + tuple(fl.hyp_critic_2[1:])
-            fl.cfg = ag.td3 = TD3Config(self.policy_delay, h["target_noise"], h["noise_clip"])
-
-    def hyper(self, a):
-        """Agent a's {"alpha", "beta", "tau", "gamma", "target_noise", "noise_clip"} as the device descriptors hold them
-        (synchronises)."""
-        self._need_handle("hyper")
-        out = (C.c_float * 6)()
-        torch.cuda.synchronize()
-        L.check(self.lib.tt_pop_td3_hyper(self._h, int(a), C.byref(out)))
-        return dict(zip(HYPERS6, (float(x) for x in out)))
+    def _mirror(self, dst, h, n):
+        ag, fl = self.agents[dst], self.learners[dst]
+        ag.critic_2.optimizer.param_groups[0]["lr"] = h["beta"]
+        fl.hyp_critic_2 = (h["beta"],) + tuple(fl.hyp_critic_2[1:])
+        fl.cfg = ag.td3 = TD3Config(self.policy_delay, h["target_noise"], h["noise_clip"])
 
 
 def same_policy_delay(cfgs):

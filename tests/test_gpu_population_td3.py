@@ -228,17 +228,54 @@ def test_population_loop_equals_lone_td3_loops_and_its_own_eager_steps(gpu_devic
         env.close()
 
 
-def _own_state(pop, a):
-    """What an exploit must not touch of agent a: both step counts, both bias corrections, the snapshot, tail words, ring, env,
-    OU noise and the noise seed."""
-    lp, fl = pop.loops[a], pop.learner.learners[a]
+def _own_learner_state(fl, ring):
+    """What an exploit must not touch of a learner: both step counts, both bias corrections, the snapshot, tail words, the ring."""
     return [t.clone() for t in (fl.step_dev, fl.actor_step_dev, fl.bias_corr, fl.actor_bias_corr, fl.step_snap, fl.tail_words,
-                                lp.ring.obs, lp.ring.act, lp.ring.rew, lp.ring.done, lp.ring.k_dev, lp.env.state, lp.noise.x)], fl.noise_seed
+                                ring.obs, ring.act, ring.rew, ring.done, ring.k_dev)]
+
+
+def _own_state(pop, a):
+    """What an exploit must not touch of agent a of a loop: _own_learner_state, env, OU noise and the noise seed."""
+    lp, fl = pop.loops[a], pop.learner.learners[a]
+    return _own_learner_state(fl, lp.ring) + [lp.env.state.clone(), lp.noise.x.clone()], fl.noise_seed
 
 
 def _f32(x):
     import numpy as np
     return float(np.float32(x))
+
+
+@pytest.mark.parametrize("images", [True, False], ids=["images", "f32"])
+def test_exploit_copy_is_complete_and_isolated(gpu_device, trained_states, images):
+    """The learner-level twin of tests/test_gpu_pbt.py's test of the same name: K = 2 (a src and a dst), B = 16, delay 2.  After a
+    critic-only and a full eager learn(), exploit([(1, 0, six new values)]): agent 1's learning state -- six networks, three moment
+    pairs, and the six fc2 images when they are on (off: those six regions of the copy return early) -- is agent 0's bit for bit,
+    agent 0's is what it was, both agents' own state (step counts, bias corrections, snapshot, tail words, ring, noise seed) is
+    what it was, and hyper(1) reads the six values back as f32."""
+    import torch
+    dev, K, B = gpu_device, 2, 16
+    pop = _population(dev, trained_states[:K], R.TRAINED_HYPER, [_cfg(2, 0.2, 0.5), _cfg(2, 0.1, 0.05)],
+                      [_batch(B, 700 + a) for a in range(K)], images, [5, 6])
+    pop.learn(0)
+    pop.learn(1)
+    torch.cuda.synchronize()
+    assert all(fl.use_images == images for fl in pop.learners) and pop.tail_gave_up() == [0] * K
+    before = [_learning_state(fl) for fl in pop.learners]
+    own = [_own_learner_state(fl, r) for fl, r in zip(pop.learners, pop.rings)]
+    hyp0 = pop.hyper(0)
+    assert len(before[0]) == (2 * 10 + 4 * 12) + 3 * 2 + (6 if images else 0) and not _equal(before[1], before[0])
+    new = dict(alpha=3e-4, beta=2e-3, tau=2e-3, gamma=0.97, target_noise=0.1, noise_clip=0.3)
+    pop.exploit([(1, 0, new)])
+    torch.cuda.synchronize()
+    after = [_learning_state(fl) for fl in pop.learners]
+    assert _equal(after[1], before[0]), ("dst is not src bit for bit", _first_difference(after[1], before[0]))
+    assert _equal(after[0], before[0]), ("src changed", _first_difference(after[0], before[0]))
+    for a, fl in enumerate(pop.learners):
+        got = _own_learner_state(fl, pop.rings[a])
+        assert _equal(got, own[a]), (a, "step counts / bias corrections / snapshot / tail words / ring moved", _first_difference(got, own[a]))
+        assert int(fl.step_dev.item()) == 1001 and int(fl.actor_step_dev.item()) == 500 and fl.noise_seed == 5 + a
+    assert pop.hyper(1) == {k: _f32(v) for k, v in new.items()} and pop.hyper(0) == hyp0
+    assert pop.tail_gave_up() == [0] * K
 
 
 def test_exploit_copies_six_networks_under_captured_graphs(gpu_device):
