@@ -5,6 +5,8 @@ that, same file names), a training-state pickle (trainv2.py:210-229) and the las
 (trainv2.py:333-351) -- but not the optimizer state, the env or the replay contents, so a resumed run restarts
 Adam cold.  `save_training_checkpoint` writes ONE torch file with all of it; `BestModelTracker` is the
 reference's "save when best by success rate, then by average score" rule (trainv2.py:538-572)."""
+import os
+
 import numpy as np
 import torch
 
@@ -101,6 +103,56 @@ def load_loop_checkpoint(path, loop):
     return ck.get("training_state", {})
 
 
+def pbt_file_state(pbt):
+    """pbt.PBT.state_dict() in a form torch.load(weights_only=True) reads: the RandomState as its name, a uint32 tensor and three
+    plain numbers (get_state()'s tuple holds an ndarray, which that loader refuses); windows and history are lists, tuples, floats,
+    ints and bools already."""
+    sd = pbt.state_dict()
+    kind, keys, pos, has_gauss, gauss = sd["rng"]
+    rng = {"kind": str(kind), "keys": torch.from_numpy(np.array(keys, dtype=np.uint32)), "pos": int(pos),
+           "has_gauss": int(has_gauss), "gauss": float(gauss)}
+    return {"rng": rng, "windows": sd["windows"], "last_round": int(sd["last_round"]), "history": sd["history"]}
+
+
+def load_pbt_file_state(pbt, fs):
+    """pbt_file_state() back into the controller, through PBT.load_state_dict."""
+    r = fs["rng"]
+    pbt.load_state_dict({"rng": (r["kind"], r["keys"].numpy().astype(np.uint32), r["pos"], r["has_gauss"], r["gauss"]),
+                         "windows": [[tuple(e) for e in w] for w in fs["windows"]], "last_round": fs["last_round"],
+                         "history": fs["history"]})
+
+
+def save_population_checkpoint(path, pop, pbt=None, training_state=None):
+    """The whole population (PopulationRollout.state_dict: per agent what a lone loop's checkpoint holds, and the hyperparameters
+    and n that exploit() moved), the PBT controller when one is given, and the caller's training_state, in one file; a population
+    restored from it continues bit for bit (tests/test_gpu_population_checkpoint.py).  Refuses, as the population's state_dict
+    does, a population in which a launch gave up.  The file is written under a temporary name beside `path` and moved over it
+    (os.replace): a run killed during a save keeps its previous checkpoint."""
+    ck = {"format": 1, "population": pop.state_dict(), "training_state": training_state or {}}
+    if pbt is not None:
+        ck["pbt"] = pbt_file_state(pbt)
+    tmp = f"{path}.tmp{os.getpid()}"
+    try:
+        torch.save(ck, tmp)
+        os.replace(tmp, path)
+    finally:
+        if os.path.exists(tmp):
+            os.remove(tmp)
+    return path
+
+
+def load_population_checkpoint(path, pop, pbt=None):
+    """Restores what save_population_checkpoint wrote and returns its training_state.  A controller passed for a file without PBT
+    state is a ValueError (nothing is loaded); a file with PBT state loads without a controller."""
+    ck = torch.load(path, map_location="cpu", weights_only=True)
+    if pbt is not None and "pbt" not in ck:
+        raise ValueError(f"{path} holds no PBT state, but a PBT controller was passed to restore")
+    pop.load_state_dict(ck["population"])
+    if pbt is not None:
+        load_pbt_file_state(pbt, ck["pbt"])
+    return ck.get("training_state", {})
+
+
 class BestModelTracker:
     """trainv2.py:538-572: success_rate over the last 100 episodes; best = higher success rate, or equal success
     rate and higher 100-episode average score, and only after 100 episodes of this run."""
@@ -138,6 +190,20 @@ class BestModelTracker:
             if is_best:
                 best.append(j)
         return best, avg, rate
+
+    def state_dict(self):
+        """Everything update() depends on, as plain numbers and lists (a checkpoint's training_state)."""
+        return {"start_episode": int(self.start_episode), "best_score": float(self.best_score),
+                "best_success_rate": float(self.best_success_rate), "score_history": list(self.score_history),
+                "success_history": list(self.success_history), "step_history": list(self.step_history),
+                "total_steps": int(self.total_steps)}
+
+    def load_state_dict(self, sd):
+        self.start_episode, self.total_steps = int(sd["start_episode"]), int(sd["total_steps"])
+        self.best_score, self.best_success_rate = float(sd["best_score"]), float(sd["best_success_rate"])
+        self.score_history = [float(x) for x in sd["score_history"]]
+        self.success_history = [int(x) for x in sd["success_history"]]
+        self.step_history = [int(x) for x in sd["step_history"]]
 
     def training_state(self, episode_num):
         """The dict trainv2.py:210-229 pickles (same keys)."""

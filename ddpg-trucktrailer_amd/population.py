@@ -20,8 +20,13 @@ target_noise and noise_clip -- and a population update is the shared TD3 launche
 DESIGN.md section 17): update u of a vector step is a full one when (u + 1) % policy_delay == 0, as in a lone TD3 loop, whose bits
 agent a keeps.  exploit() then also copies the second critic and carries the two noise values.  Not with n-step returns or a learn log.
 
-Out of scope: the pipelined order, data-parallel populations, expert side buffers (with any n), whole-population checkpoints
-(an agent's weights save through agents[a].save_models())."""
+PopulationRollout.state_dict() / load_state_dict() (checkpoint.save_population_checkpoint) save and resume
+the whole population bit for bit -- every agent's networks, Adam state, ring, env, OU state and the hyperparameters and n that
+exploit() has moved -- and one agent of the file loads into a lone DDPGRollout.  The load makes the handle again from the restored
+host state, so the device holds the file's seeds, hyperparameters, n-step table and TD3 noise values.
+
+Out of scope: the pipelined order, data-parallel populations, expert side buffers (with any n), checkpoints without the rings'
+contents, the learn log's records in a checkpoint."""
 import ctypes as C
 
 import torch
@@ -132,13 +137,46 @@ class _PopulationLearnerBase:
             new.append((dst, src, {k: float(hyp.get(k, of_src[k])) for k in self.HYPERS}, n))
         self._launch_exploit(new)
         for dst, _, h, n in new:
-            ag, fl = self.agents[dst], self.learners[dst]
-            ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
-            ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
-            ag.critic.optimizer.param_groups[0]["lr"] = h["beta"]
-            fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
-            fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
-            self._mirror(dst, h, n)
+            self._set_mirrors(dst, h, n)
+
+    def _set_mirrors(self, a, h, n):
+        """Agent a's host mirrors of the hyperparameters h ({HYPERS}) and of its n: what exploit() and a checkpoint's load leave
+        on the host, and what _create() reads."""
+        ag, fl = self.agents[a], self.learners[a]
+        ag.alpha, ag.beta, ag.tau, ag.gamma = h["alpha"], h["beta"], h["tau"], h["gamma"]
+        ag.actor.optimizer.param_groups[0]["lr"] = h["alpha"]
+        ag.critic.optimizer.param_groups[0]["lr"] = h["beta"]
+        fl.hyp_actor = (h["alpha"],) + tuple(fl.hyp_actor[1:])
+        fl.hyp_critic = (h["beta"],) + tuple(fl.hyp_critic[1:])
+        self._mirror(a, h, n)
+
+    def _set_seed(self, a, seed):
+        self.seeds[a] = int(seed)
+
+    @property
+    def has_handle(self):
+        return self._h is not None
+
+    def restore(self, seeds, hypers, n_steps):
+        """A checkpoint's per-agent seeds, {HYPERS} and n on the host and on the device (PopulationRollout.load_state_dict, after
+        the learners' own load_state_dict): the mirrors first, then the handle again from them.  _create() copies seeds,
+        hyperparameters, the n-step table and TD3's noise values into the descriptors and launches no update, so destroying the
+        handle and making it anew puts all of a checkpoint there at once; graphs captured over the old handle hold its address and
+        must be dropped by the caller.  A learn log comes back empty, its cursors at the loaded step counts.  Without a handle
+        (no learn() yet) only the host changes: the first eager learn() makes the handle from it.  A TD3 agent's smoothing-noise
+        seed becomes its seed, as TD3Learner.set_seed has it: the file holds no noise seeds, so a PopulationTD3Learner built with
+        noise_seeds= of its own loses them here (PopulationRollout never passes any)."""
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError(f"{type(self).__name__}.restore: not while capturing")
+        for a, (seed, h, n) in enumerate(zip(seeds, hypers, n_steps)):
+            self._set_seed(a, seed)
+            self._set_mirrors(a, {k: float(h[k]) for k in self.HYPERS}, int(n))
+        if self._h is not None:
+            torch.cuda.synchronize()
+            getattr(self.lib, self._DESTROY)(self._h)
+            self._h = None
+            self._create()
+            self._key = self._storage_key()
 
     def hyper(self, a):
         """Agent a's {HYPERS} as the device descriptors hold them (synchronises)."""
@@ -269,6 +307,63 @@ def _per_agent(x, K, name):
             raise ValueError(f"{name}: {len(x)} values for {K} agents")
         return list(x)
     return [x] * K
+
+
+POPULATION_FORMAT = 1          # PopulationRollout.state_dict()["format"]; its agents are DDPGRollout.state_dict()s of format 2
+
+
+def check_population_state(sd, K, lanes, slots, batch_size, policy_delay=None, n_step_max=1, n_step_table=False):
+    """What PopulationRollout.load_state_dict refuses, each a ValueError that names what differs, before anything is written: sd is a
+    PopulationRollout.state_dict(), the other arguments describe the population that would load it (policy_delay: None = DDPG).
+    Returns the agents' n_steps.  A pure function: no GPU."""
+    if sd.get("format") != POPULATION_FORMAT:
+        raise ValueError(f"format: the checkpoint has format {sd.get('format')!r}, this code reads format {POPULATION_FORMAT}")
+    agents = sd["agents"]
+    if int(sd["K"]) != int(K) or len(agents) != int(K):
+        raise ValueError(f"K: the checkpoint holds {int(sd['K'])} agents ({len(agents)} agent states), this population has {K}")
+    if int(sd["n"]) != int(lanes):
+        raise ValueError(f"n_envs_per_agent: the checkpoint was written with {int(sd['n'])} lanes per agent, this population has {lanes}")
+    if int(sd["batch_size"]) != int(batch_size):
+        raise ValueError(f"batch_size: the checkpoint was written with {int(sd['batch_size'])}, this population has {batch_size}")
+    have = sd.get("policy_delay")
+    if (have is None) != (policy_delay is None):
+        raise ValueError("td3: the checkpoint was written with td3, this population has none" if have is not None else
+                         "td3: the checkpoint was written without td3, this population has td3 (no second critics in it)")
+    if have is not None and int(have) != int(policy_delay):
+        raise ValueError(f"policy_delay: the checkpoint was written with {int(have)}, this population has {policy_delay}")
+    ups = int(sd["updates_per_step"])
+    if have is not None and ups % int(have) != 0:
+        raise ValueError(f"updates_per_step: the checkpoint's {ups} is not a multiple of policy_delay = {int(have)} (the delay is "
+                         "counted inside a vector step)")
+    n_steps = []
+    for a, st in enumerate(agents):
+        if st.get("format") != 2:
+            raise ValueError(f"format: agent {a}'s state has format {st.get('format')!r}, this code reads format 2")
+        ring = st["ring"]
+        if int(ring["slots"]) != int(slots):
+            raise ValueError(f"replay_slots: agent {a}'s ring was written with {int(ring['slots'])} slots, this population's has {slots}")
+        if int(ring["n"]) != int(lanes):
+            raise ValueError(f"n_envs_per_agent: agent {a}'s ring was written with {int(ring['n'])} lanes, this population has {lanes}")
+        if "obs" not in ring:
+            raise ValueError(f"ring: agent {a}'s ring was written without its contents: a population cannot resume from it")
+        if int(st["batch_size"]) != int(batch_size):
+            raise ValueError(f"batch_size: agent {a}'s state was written with {int(st['batch_size'])}, this population has {batch_size}")
+        if ("td3" in st) != (have is not None):
+            raise ValueError(f"td3: agent {a}'s state was written {'with' if 'td3' in st else 'without'} td3, the checkpoint "
+                             f"{'with' if have is not None else 'without'}")
+        if "td3" in st and int(st["td3"][0]) != int(have):
+            raise ValueError(f"policy_delay: agent {a}'s state was written with {int(st['td3'][0])}, the checkpoint with {int(have)}")
+        need = ("alpha", "beta", "tau", "gamma") + (("target_noise", "noise_clip") if have is not None else ())
+        if any(k not in st.get("hyper", {}) for k in need):
+            raise ValueError(f"hyper: agent {a}'s state lacks one of {need} (a lone loop's state is no population agent's)")
+        n = int(st.get("n_step", 1))
+        if n > int(n_step_max):
+            raise ValueError(f"n_step: agent {a} was saved with n_step = {n}, above this population's n_step_max = {n_step_max}")
+        if n > 1 and not n_step_table:
+            raise ValueError(f"n_step: agent {a} was saved with n_step = {n}, but this population was built without n-step returns "
+                             "(PopulationRollout(n_step=...))")
+        n_steps.append(check_n_step(n))
+    return n_steps
 
 
 class PopulationRollout:
@@ -404,10 +499,11 @@ class PopulationRollout:
 
     def run(self, k):
         """k population vector steps: eager until every agent has stored max(4, 1 + n_step_max) steps, then graph replays of
-        graph_steps and 1 steps."""
+        graph_steps and 1 steps.  A population that loaded warm rings before its first learn() (load_state_dict) has no handle to
+        capture over yet: its first step is an eager one, the same bits, which makes it."""
         self.learner.refresh_images()
         while k > 0:
-            if self.graph_steps and self.k >= self._warm_steps:
+            if self.graph_steps and self.k >= self._warm_steps and self.learner.has_handle:
                 self._check_epoch()
                 if self.graph1 is None:
                     self.graph1 = self._capture(1)
@@ -460,6 +556,58 @@ class PopulationRollout:
 
     def hyper(self, a):
         return self.learner.hyper(a)
+
+    def n_step_of(self, a):
+        return self.learner.n_step_of(a)
+
+    # -------------------------------------------------------------- checkpoint / resume of the whole population
+    def state_dict(self):
+        """Everything the next population step depends on (checkpoint.save_population_checkpoint writes
+        it).  "agents"[a] is a lone loop's DDPGRollout.state_dict() of format 2, key for key -- so DDPGRollout.load_state_dict
+        takes one agent out of a population -- plus "hyper": agent a's hyperparameters as exploit() left them on the host.  With
+        td3 an agent's fused_adam["updates"] is the population's count of learn() calls, what a lone TD3 learner would hold.
+        Synchronises; a population with a give-up raises (_check_handover) and returns nothing.  The learn log is not in it."""
+        torch.cuda.synchronize(self.device)
+        self._check_handover()
+        lr, agents = self.learner, []
+        for a, lp in enumerate(self.loops):
+            st = {"format": 2, "handover_gave_up": [], "batch_size": self.batch_size, "updates_per_step": self.updates_per_step,
+                  "n_step": int(self.n_steps[a]), **lp.acting_state(), "fused_adam": lr.state_dict(a), "hyper": lr._hyper_of(a)}
+            if self.td3 is not None:
+                st["td3"] = list(lp.agent.td3.as_tuple())
+                st["fused_adam"]["updates"] = int(lr.updates)
+            agents.append(st)
+        return {"format": POPULATION_FORMAT, "K": self.K, "n": self.n, "batch_size": self.batch_size,
+                "updates_per_step": self.updates_per_step, "vector_steps": int(self.vector_steps), "seeds": list(self.seeds),
+                "n_step_table": bool(getattr(lr, "nstep_table", False)), "n_step_max": int(self.n_step_max),
+                "policy_delay": self.policy_delay if self.td3 is not None else None, "agents": agents}
+
+    def load_state_dict(self, sd):
+        """Restore a state_dict() in place, in a lone loop's order per agent -- networks, learner, ring, OU state, env, counters --
+        then the seeds, exploit()'s host mirrors and n, and the device descriptors from them (_PopulationLearnerBase.restore).
+        check_population_state names what is refused, before anything is written; updates_per_step follows the file.  That check
+        sees the shapes and options listed there, not the contents: an error raised later, inside an agent's own load (an env blob
+        of another env variant, a damaged file), leaves the agents before it loaded and the population unusable until a whole
+        load succeeds.  An episode log follows the file (capacity and detail mode), as in the lone loop.  Works on a population
+        that has never stepped and on one with captured graphs (they are dropped); run() goes on either way."""
+        n_steps = check_population_state(sd, self.K, self.n, self.loops[0].ring.slots, self.batch_size,
+                                         self.policy_delay if self.td3 is not None else None, self.n_step_max,
+                                         bool(getattr(self.learner, "nstep_table", False)))
+        torch.cuda.synchronize(self.device)
+        self.invalidate_graphs()           # (they hold the handle's address, and the policy launches their agent's seed)
+        lr, agents = self.learner, sd["agents"]
+        for lp, fl, st in zip(self.loops, lr.learners, agents):
+            lp.load_nets(st["nets"])
+            fl.load_state_dict(st["fused_adam"])       # (moments, step counts; tail words reset)
+            lp.load_acting_state(st)
+            lp.seed, lp.vector_steps = int(st["seed"]), int(st["vector_steps"])
+        self.seeds = [int(st["seed"]) for st in agents]
+        hypers = [dict(st["hyper"]) for st in agents]
+        if self.td3 is not None:
+            lr.updates = int(agents[0]["fused_adam"].get("updates", 0))
+        lr.restore(self.seeds, hypers, n_steps)
+        self.vector_steps = int(sd["vector_steps"])
+        self.updates_per_step = int(sd["updates_per_step"])
 
     @property
     def n_steps(self):

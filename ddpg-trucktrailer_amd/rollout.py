@@ -648,13 +648,9 @@ class DDPGRollout(VectorStepper):
         torch.cuda.synchronize(self.device) if self.device.type == "cuda" else None
         self._check_handover(exact=True)
         ag = self.agent
-        sd = {"format": 2, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
-              "handover_gave_up": [int(x) for x in self.handover_gave_up],
+        sd = {"format": 2, "handover_gave_up": [int(x) for x in self.handover_gave_up],
               "batch_size": int(self.batch_size), "updates_per_step": self.updates_per_step, "n_step": int(self.n_step),
-              "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()}
-                       for n in ("actor", "critic", "target_actor", "target_critic") + (("critic_2", "target_critic_2") if self.td3 else ())},
-              "ring": self.ring.state_dict(), "ou": self.noise.x.detach().cpu().clone(),
-              "env": self.env.state_dict() if hasattr(self.env, "state_dict") else None}
+              **self.acting_state()}         # (seed, vector_steps, nets, ring, ou, env: stepper.py)
         if self.learner is not None:
             sd["fused_adam"] = self.learner.state_dict()
         else:
@@ -687,10 +683,7 @@ class DDPGRollout(VectorStepper):
         mine = self.loss_shape.as_tuple() if self.loss_shape is not None else None
         if have != mine:
             raise ValueError(f"the checkpoint was written with loss_shape = {have}, this loop has loss_shape = {mine}")
-        with torch.no_grad():
-            for n, net_sd in sd["nets"].items():
-                for k, v in getattr(ag, n).state_dict().items():      # in place: captured graphs keep the addresses
-                    v.copy_(net_sd[k].to(v.device))
+        self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])
         elif "optim" in sd:
@@ -702,10 +695,7 @@ class DDPGRollout(VectorStepper):
                 if "td3_noise" in sd:
                     ag.set_td3_noise_state(sd["td3_noise"])
             self.graph = None                                         # optimizer state tensors were replaced
-        self.ring.load_state_dict(sd["ring"])
-        self.noise.x.copy_(sd["ou"].to(self.noise.x.device))
-        if sd.get("env") is not None:
-            self.env.load_state_dict(sd["env"])                       # bumps env.graph_epoch: graphs are re-captured
+        self.load_acting_state(sd)                                    # ring, OU state, env (bumps env.graph_epoch)
         self.k_pipe_dev.fill_(self.ring.k)
         if int(sd["seed"]) != int(self.seed):
             self.invalidate_graphs()                                  # the Philox keys are kernel arguments

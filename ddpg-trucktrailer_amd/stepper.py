@@ -120,3 +120,33 @@ class VectorStepper:
     def drain_episodes(self):
         """The env's episode log since the last drain: records sorted by (end_step, lane), end_step = the vector step it ended in."""
         return self.env.drain_episodes()
+
+    # -------------------------------------------------------------- the stepper's part of a checkpoint
+    def net_names(self):
+        td3 = getattr(self.agent, "td3", None) is not None
+        return ("actor", "critic", "target_actor", "target_critic") + (("critic_2", "target_critic_2") if td3 else ())
+
+    def acting_state(self):
+        """What DDPGRollout.state_dict and PopulationRollout.state_dict hold of a stepper, under the lone loop's keys: seed,
+        vector_steps, nets (four networks, six with TD3), ring, ou and env (with the episode log's state when it is on).  The
+        caller has synchronised."""
+        ag = self.agent
+        return {"seed": int(self.seed), "vector_steps": int(self.vector_steps),
+                "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()} for n in self.net_names()},
+                "ring": self.ring.state_dict(), "ou": self.noise.x.detach().cpu().clone(),
+                "env": self.env.state_dict() if hasattr(self.env, "state_dict") else None}
+
+    def load_nets(self, nets):
+        """The networks of a checkpoint, in place: captured graphs and descriptors keep the addresses."""
+        with torch.no_grad():
+            for n, net_sd in nets.items():
+                for k, v in getattr(self.agent, n).state_dict().items():
+                    v.copy_(net_sd[k].to(v.device))
+
+    def load_acting_state(self, sd):
+        """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are
+        captured again).  Seed and counters stay with the caller, which knows what bakes the seed in."""
+        self.ring.load_state_dict(sd["ring"])
+        self.noise.x.copy_(sd["ou"].to(self.noise.x.device))
+        if sd.get("env") is not None:
+            self.env.load_state_dict(sd["env"])

@@ -307,6 +307,11 @@ class PopulationTD3Learner(_PopulationLearnerBase):
         arr = (L.TTPopTd3Pair * len(new))(*[L.TTPopTd3Pair(dst, src, *[h[k] for k in HYPERS6]) for dst, src, h, _ in new])
         L.check(self.lib.tt_pop_td3_exploit(self._h, len(new), arr, L.stream()))
 
+    def _set_seed(self, a, seed):
+        """A checkpoint's seed: the sampling keys' and, as TD3Learner.set_seed has it, the smoothing noise's."""
+        super()._set_seed(a, seed)
+        self.learners[a].seed, self.learners[a].noise_seed = int(seed), int(seed) & (2 ** 64 - 1)
+
     def _mirror(self, dst, h, n):
         ag, fl = self.agents[dst], self.learners[dst]
         ag.critic_2.optimizer.param_groups[0]["lr"] = h["beta"]

@@ -17,8 +17,15 @@ updates_per_step must be a multiple of DELAY; not with --n-step > 1, --pbt-n-ste
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation (evaluation.Evaluator: no noise, the same M start
 poses for every agent, drawn once from first_seed), one summary line per agent; --pbt-on-eval: the block's PBT round ranks on those
 records instead of on the training episodes (PBT.step(..., evaluation=); with --pbt, whose window becomes M).
+--checkpoint PATH [--save-every BLOCKS]: the whole run in one file (checkpoint.save_population_checkpoint: the population, the PBT
+controller, each agent's BestModelTracker and episode count, the block counter and the vector step), written after every BLOCKS-th
+report block and at the end of the run, each time over the previous file by a rename.  --resume PATH: continue such a run, bit for
+bit, to the vector_steps given: the other positional arguments and the options must be the run's own (a population of another
+shape is refused), --eval-every keeps its phase, and one line says from which vector step the run continues.  With --objectives
+the 100-episode objective averages start empty after a resume (RunningObjectives is not in the file).
 Usage: train_population.py [--objectives] [--n-step N[,N...]] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]]
        [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]] [--eval-every R --eval-lanes M [--pbt-on-eval]]
+       [--checkpoint PATH [--save-every BLOCKS]] [--resume PATH]
        K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
 import pickle
@@ -26,7 +33,7 @@ import sys
 import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-from ddpg_trucktrailer_amd.checkpoint import BestModelTracker  # noqa: E402
+from ddpg_trucktrailer_amd.checkpoint import BestModelTracker, load_population_checkpoint, save_population_checkpoint  # noqa: E402
 from ddpg_trucktrailer_amd.population import PopulationRollout  # noqa: E402
 
 detail = "--objectives" in sys.argv[1:]
@@ -53,6 +60,9 @@ pbt_n_steps = _option("--pbt-n-steps", _ints)
 learn_every = _option("--learn-log", int)
 eval_every = _option("--eval-every", int)
 eval_lanes = _option("--eval-lanes", int, 256)
+checkpoint_path = _option("--checkpoint", str)
+save_every = _option("--save-every", int)
+resume_path = _option("--resume", str)
 pbt_on_eval = "--pbt-on-eval" in sys.argv[1:]
 if pbt_on_eval:
     sys.argv.remove("--pbt-on-eval")
@@ -71,6 +81,8 @@ if pbt_n_steps is not None and pbt_ready is None:
     sys.exit("--pbt-n-steps needs --pbt")
 if pbt_on_eval and (pbt_ready is None or eval_every is None):
     sys.exit("--pbt-on-eval needs --pbt and --eval-every")
+if save_every is not None and (checkpoint_path is None or save_every < 1):
+    sys.exit("--save-every BLOCKS (>= 1) needs --checkpoint")
 K, n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:8])
 seed0 = int(sys.argv[8]) if len(sys.argv) > 8 else 27
 graph_steps = int(sys.argv[9]) if len(sys.argv) > 9 else 20
@@ -123,8 +135,21 @@ if eval_every is not None:
           + (", PBT ranks on it" if pbt_on_eval else ""), flush=True)
 blocks = 0
 episodes = [0] * K
-t0 = time.time()
 s = 0
+
+
+def save_checkpoint():
+    state = {"blocks": blocks, "vector_steps": s, "episodes": list(episodes), "trackers": [tr.state_dict() for tr in trackers]}
+    save_population_checkpoint(checkpoint_path, pop, pbt, state)
+
+
+if resume_path is not None:
+    state = load_population_checkpoint(resume_path, pop, pbt)
+    blocks, s, episodes = int(state["blocks"]), int(state["vector_steps"]), [int(x) for x in state["episodes"]]
+    for tr, sd in zip(trackers, state["trackers"]):
+        tr.load_state_dict(sd)
+    print(f"resumed from {resume_path}: continuing from vector step {s} (block {blocks}), n_step {pop.n_steps}", flush=True)
+t0, s0 = time.time(), s
 while s < total:
     k = min(every, total - s)
     pop.run(k)
@@ -163,7 +188,12 @@ while s < total:
             hyp = "  ".join(f"{k} {d['old'][k]:.4g} -> {d['new'][k]:.4g}" for k in d["new"])
             print(f"PBT step {d['step']}: agent {d['dst']} (score {d['dst_score'][0]:.1f}) <- agent {d['src']} "
                   f"(score {d['src_score'][0]:.1f}): {hyp}", flush=True)
-    print(f"  {time.time() - t0:8.1f} s, {s * n * K / max(1e-9, time.time() - t0):.3e} env-steps/s over the population", flush=True)
+    print(f"  {time.time() - t0:8.1f} s, {(s - s0) * n * K / max(1e-9, time.time() - t0):.3e} env-steps/s over the population", flush=True)
+    if save_every is not None and blocks % save_every == 0 and s < total:
+        save_checkpoint()
+if checkpoint_path is not None:
+    save_checkpoint()
+    print(f"checkpoint -> {checkpoint_path} (vector step {s})", flush=True)
 
 os.makedirs("training_states", exist_ok=True)
 for a, tr in enumerate(trackers):
