@@ -57,44 +57,13 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi(const FwdJobs J) {
         if (threadIdx.x == 0) g_kblk[5][0][0] = m;
     }
 #endif
-    static_assert(TR / NW == 2, "two rows per wave");
     const float *orow = nullptr;
     bool have_act = false;
     float act_r0 = 0.f, act_r1 = 0.f;
     if (J.sampled) {
         ttnet::await_progress(J.R.progress, J.R.k_dev);
-        const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
-        if (J.k_snapshot && blockIdx.x == 0 && tid == 0) *J.k_snapshot = *J.R.k_dev;
-        const bool from_s = q.obs == J.R.s_out;                  // this job reads s (else s')
-        {
-            const ttnet::RingPick p = ttnet::ring_sample_index(J.R, min(row0 + l15, J.n - 1));
-            orow = from_s ? ttnet::ring_pick_s(J.R, p) : ttnet::ring_pick_s2(J.R, p);
-        }
-        if (q.critic && q.action) {
-            act_r0 = ttnet::ring_pick_a(J.R, ttnet::ring_sample_index(J.R, min(row0 + wave * 2, J.n - 1)));
-            act_r1 = ttnet::ring_pick_a(J.R, ttnet::ring_sample_index(J.R, min(row0 + wave * 2 + 1, J.n - 1)));
-            have_act = true;
-        }
-        if (job == J.write_s || job == J.write_s2) {
-            // the batch rows of this workgroup for the later launches: thread i < 16 x 23 copies one feature
-            // (loads here and the stores after the forward -- so that its own loads do not queue behind this copy -- changed
-            // nothing: 18.2 us for the slowest workgroup either way)
-            const int lr = tid / ttnet::IN, c = tid - lr * ttnet::IN, b = row0 + lr;
-            if (lr < TR && b < J.n) {
-                const ttnet::RingPick p = ttnet::ring_sample_index(J.R, b);
-                if (job == J.write_s) {
-                    J.R.s_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s(J.R, p)[c];
-                    if (c == 0) {
-                        J.R.a_out[b] = ttnet::ring_pick_a(J.R, p);
-                        if (J.R.idx_out) { J.R.idx_out[2 * b] = p.side ? -1 : p.t; J.R.idx_out[2 * b + 1] = p.side ? p.j : p.e; }
-                    }
-                }
-                if (job == J.write_s2) {
-                    J.R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s2(J.R, p)[c];
-                    if (c == 0) { J.R.r_out[b] = ttnet::ring_pick_r(J.R, p); J.R.d_out[b] = ttnet::ring_pick_d(J.R, p); }
-                }
-            }
-        }
+        if (J.k_snapshot && blockIdx.x == 0 && threadIdx.x == 0) *J.k_snapshot = *J.R.k_dev;
+        TT_SAMPLED_ROWS(J.R, J.n, row0, q, job, J.write_s, J.write_s2, orow, have_act, act_r0, act_r1);
     }
     if (q.critic)
         fwd_small_body<true>(J.n, q.obs, q.action, q.W, q.out, q.sv, q.dq_da, q.z_state, h1_s, z_s, w1_s, row0, orow, have_act, act_r0, act_r1);
@@ -117,18 +86,7 @@ __global__ __launch_bounds__(64 * NW) void k_bwd_rows_pair(const int n, const fl
     __shared__ __attribute__((aligned(16))) float dx2_s[DXS_FLOATS];
     __shared__ float red[2 * NW * TR];
     __shared__ float rsc_s[TR];
-    kernarg_warm<16 + 2 * ((int)sizeof(Weights) + (int)sizeof(Saved) + (int)sizeof(BwdOut)) + (int)sizeof(TdIn) + 8>();
-    const int nb = (n + TR - 1) / TR;
-    if ((int)blockIdx.x == 2 * nb) {         // the extra workgroup: counters + bias corrections (nothing in this launch reads them)
-        if (threadIdx.x == 0) clock_tick(td);
-        return;
-    }
-    if ((int)blockIdx.x > 2 * nb) {          // the image's workgroups (they read a SNAPSHOT of the step number: see ImageJob)
-        ttnet::split_pack_body(img.W, false, img.ws, img.ws_alt, nullptr, img.cur,
-                               ((int)blockIdx.x - 2 * nb - 1) * (64 * NW) + (int)threadIdx.x);
-        ttnet::publish_image(img.cur, IMAGE_WGS);
-        return;
-    }
+    TT_BWD_ROWS_PAIR_FRONT(nb, n, td, img);
     KBEGIN(1);
     if ((int)blockIdx.x < nb) {
         bwd_rows_body<true>(n, scale_c, q_out, Wc, sv_c, o_c, td, dx2_s, red, rsc_s, blockIdx.x * TR);
@@ -165,23 +123,15 @@ __global__ __launch_bounds__(64 * NW) void k_actor_tail(const int n, const float
     __shared__ __attribute__((aligned(16))) float lds[H1S_FLOATS + TR * DS + H1 * IN];
     const int nb = (n + TR - 1) / TR;
     if ((int)blockIdx.x < nb) {
-        const Saved none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         const long long epoch = *A.step_dev;
         KBEGIN(3);
-        fwd_small_body<true>(n, obs, mu, Wc, q_out, none, dq_da, nullptr, lds, lds + H1S_FLOATS, lds + H1S_FLOATS + TR * DS,
-                             blockIdx.x * TR, nullptr, false, 0.f, 0.f, ts.rows, (unsigned)epoch);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave: its rows' words have been sent
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(ts.hints + blockIdx.x, (int)epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        TT_ACTOR_TAIL_ROWS(n, obs, mu, Wc, q_out, dq_da, lds, ts, blockIdx.x, epoch);
         KEND(3);
         return;
     }
     if (threadIdx.x >= 256) return;
-    static_assert(sizeof(float) * (H1S_FLOATS + TR * DS + H1 * IN) >= sizeof(float) * (4 * 4 * 256 + MAXB + 2048), "the weight kernel's LDS fits");
-    float (&part)[4][4][256] = *reinterpret_cast<float (*)[4][4][256]>(lds);
     const long long epoch = *A.step_dev;
-    bwd_weights_body<true, true>((int)blockIdx.x - nb, n, 0, obs, nullptr, sv, d, G, A, RS, part, lds + 4 * 4 * 256, ts, epoch,
-                                 reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB));
+    TT_ACTOR_TAIL_WEIGHTS((int)blockIdx.x - nb, n, obs, sv, d, G, A, RS, lds, ts, epoch);
 }
 
 // ------------------------------------------------------------------------------------------------------

@@ -6,9 +6,9 @@
 // Small-batch geometry: a workgroup owns 16 rows; its 8 waves split the output COLUMNS (so a 256-row batch is 16
 // workgroups x 8 waves), and LayerNorm statistics are combined across the waves through LDS.
 //
-// Not here: the sampled-row prologue of k_fwd_multi (the workgroup's rows of the replay draw, and the batch rows it leaves for the
-// later launches) is written out again in k_pop_fwd_multi.  As one __forceinline__ function here it changed the instructions of
-// both kernels.
+// Not here but in ttlearn_sites.h (included below), as text: the sampled-row prologue of the first launch, the two halves of the actor
+// tail and the front of the rows-pair launch.  As __forceinline__ functions here they changed the instructions of the kernels they
+// served; that header tells the rule and the check.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -17,6 +17,7 @@
 #include "ttenv.h"
 #include "ttnet_common.h"      // the replay draw (ring_sample_index): k_fwd_multi can make it itself
 #include "ttnet_pack.h"        // the policy image (split_pack_body): k_bwd_rows_pair can carry its pack
+#include "ttlearn_sites.h"    // device text shared by several kernels, as macros
 #include "ttstamps.h"
 
 namespace {

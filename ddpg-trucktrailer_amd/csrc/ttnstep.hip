@@ -2,8 +2,8 @@
 // ones, which stay as they are (csrc/ttnet.hip: k_ring_sample, csrc/ttlearn.hip: k_fwd_multi):
 //
 //   k_ring_sample_nstep   the lone draw into the batch buffers, one wave per row (tt_ring_sample_nstep)
-//   k_fwd_multi_nstep     learn()'s first launch making that draw itself (tt_mlp_forward_multi_sampled_nstep): k_fwd_multi's
-//                         sampled prologue written out again with the n-step pick, then fwd_small_body as there
+//   k_fwd_multi_nstep     learn()'s first launch making that draw itself (tt_mlp_forward_multi_sampled_nstep): the sampled
+//                         prologue with the n-step pick (TT_SAMPLED_ROWS_NSTEP, csrc/ttlearn_sites.h), then fwd_small_body as there
 //
 // A batch row is (s, a) of the base step t0, R = the discounted sum of up to n rewards, s' = the observation m steps later and
 // D = 1 when a done ended the walk (csrc/ttnstep.h: nstep_pick).  Rows without a done all have the discount gamma^n, so the TD
@@ -42,40 +42,9 @@ __global__ __launch_bounds__(64 * NW) void k_fwd_multi_nstep(const FwdJobs J, co
     kernarg_warm<(int)sizeof(FwdJobs) + 8>();
     const int job = blockIdx.x / J.blocks_per_job, row0 = (blockIdx.x - job * J.blocks_per_job) * TR;
     const FwdJob &q = J.j[job];
-    static_assert(TR / NW == 2, "two rows per wave");
     ttnet::await_progress(J.R.progress, J.R.k_dev);
-    const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
-    if (J.k_snapshot && blockIdx.x == 0 && tid == 0) *J.k_snapshot = *J.R.k_dev;
-    const bool from_s = q.obs == J.R.s_out;                  // this job reads s (else s')
-    const float *orow;
-    // (a branch, not a select: only the rows at t0 + m need the walk's done flags)
-    if (from_s) orow = ttnet::nstep_s(J.R, ttnet::nstep_pick(J.R, min(row0 + l15, J.n - 1), n_step, gamma));
-    else orow = ttnet::nstep_s2(J.R, ttnet::nstep_pick(J.R, min(row0 + l15, J.n - 1), n_step, gamma));
-    bool have_act = false;
-    float act_r0 = 0.f, act_r1 = 0.f;
-    if (q.critic && q.action) {
-        act_r0 = ttnet::nstep_a(J.R, ttnet::nstep_pick(J.R, min(row0 + wave * 2, J.n - 1), n_step, gamma));
-        act_r1 = ttnet::nstep_a(J.R, ttnet::nstep_pick(J.R, min(row0 + wave * 2 + 1, J.n - 1), n_step, gamma));
-        have_act = true;
-    }
-    if (job == J.write_s || job == J.write_s2) {
-        // the batch rows of this workgroup for the later launches: thread i < 16 x 23 copies one feature
-        const int lr = tid / ttnet::IN, c = tid - lr * ttnet::IN, b = row0 + lr;
-        if (lr < TR && b < J.n) {
-            const ttnet::NstepPick p = ttnet::nstep_pick(J.R, b, n_step, gamma);
-            if (job == J.write_s) {
-                J.R.s_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s(J.R, p)[c];
-                if (c == 0) {
-                    J.R.a_out[b] = ttnet::nstep_a(J.R, p);
-                    if (J.R.idx_out) { J.R.idx_out[2 * b] = p.t0; J.R.idx_out[2 * b + 1] = p.e; }
-                }
-            }
-            if (job == J.write_s2) {
-                J.R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s2(J.R, p)[c];
-                if (c == 0) { J.R.r_out[b] = p.R; J.R.d_out[b] = (uint8_t)p.D; }
-            }
-        }
-    }
+    if (J.k_snapshot && blockIdx.x == 0 && threadIdx.x == 0) *J.k_snapshot = *J.R.k_dev;
+    TT_SAMPLED_ROWS_NSTEP(J.R, J.n, row0, q, job, J.write_s, J.write_s2, n_step, gamma, orow, have_act, act_r0, act_r1);
     if (q.critic)
         fwd_small_body<true>(J.n, q.obs, q.action, q.W, q.out, q.sv, q.dq_da, q.z_state, h1_s, z_s, w1_s, row0, orow, have_act, act_r0, act_r1);
     else

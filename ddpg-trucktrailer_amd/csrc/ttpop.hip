@@ -44,38 +44,10 @@ __global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi(const int K, const in
     const FwdJob &q = P.F.j[job];
     ttnet::RingSample R = P.F.R;
     R.seed += (unsigned long long)u * R.seed_stride;        // DDPGRollout._sample_key(u)
-    static_assert(TR / NW == 2, "two rows per wave");
-    const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
-    const bool from_s = q.obs == R.s_out;
     const float *orow;
-    {
-        const ttnet::RingPick p = ttnet::ring_sample_index(R, min(row0 + l15, n - 1));
-        orow = from_s ? ttnet::ring_pick_s(R, p) : ttnet::ring_pick_s2(R, p);
-    }
     bool have_act = false;
     float act_r0 = 0.f, act_r1 = 0.f;
-    if (q.critic && q.action) {
-        act_r0 = ttnet::ring_pick_a(R, ttnet::ring_sample_index(R, min(row0 + wave * 2, n - 1)));
-        act_r1 = ttnet::ring_pick_a(R, ttnet::ring_sample_index(R, min(row0 + wave * 2 + 1, n - 1)));
-        have_act = true;
-    }
-    if (job == P.F.write_s || job == P.F.write_s2) {        // the batch rows of this workgroup for the later launches
-        const int lr = tid / ttnet::IN, c = tid - lr * ttnet::IN, b = row0 + lr;
-        if (lr < TR && b < n) {
-            const ttnet::RingPick p = ttnet::ring_sample_index(R, b);
-            if (job == P.F.write_s) {
-                R.s_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s(R, p)[c];
-                if (c == 0) {
-                    R.a_out[b] = ttnet::ring_pick_a(R, p);
-                    if (R.idx_out) { R.idx_out[2 * b] = p.side ? -1 : p.t; R.idx_out[2 * b + 1] = p.side ? p.j : p.e; }
-                }
-            }
-            if (job == P.F.write_s2) {
-                R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::ring_pick_s2(R, p)[c];
-                if (c == 0) { R.r_out[b] = ttnet::ring_pick_r(R, p); R.d_out[b] = ttnet::ring_pick_d(R, p); }
-            }
-        }
-    }
+    TT_SAMPLED_ROWS(R, n, row0, q, job, P.F.write_s, P.F.write_s2, orow, have_act, act_r0, act_r1);
     if (q.critic)
         fwd_small_body<true>(n, q.obs, q.action, q.W, q.out, q.sv, q.dq_da, q.z_state, h1_s, z_s, w1_s, row0, orow, have_act, act_r0, act_r1);
     else
@@ -124,22 +96,15 @@ __global__ __launch_bounds__(64 * NW) void k_pop_actor_tail(const int K, const i
     if ((int)blockIdx.x < rows) {
         const int ag = (int)blockIdx.x / nb, lb = (int)blockIdx.x - ag * nb;
         const PopAgent &P = agent_of(D, ag);
-        const Saved none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         const long long epoch = *P.Aa.step_dev;
-        fwd_small_body<true>(n, P.s, P.mu_out, P.Wc, P.q_pi, none, P.dq_da, nullptr, lds, lds + H1S_FLOATS,
-                             lds + H1S_FLOATS + TR * DS, lb * TR, nullptr, false, 0.f, 0.f, P.ts.rows, (unsigned)epoch);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave: its rows' words have been sent
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(P.ts.hints + lb, (int)epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        TT_ACTOR_TAIL_ROWS(n, P.s, P.mu_out, P.Wc, P.q_pi, P.dq_da, lds, P.ts, lb, epoch);
         return;
     }
     const int ag = ((int)blockIdx.x - rows) / WG_ACTOR_WEIGHTS;
     if (threadIdx.x >= 256 || ag >= K) return;
     const PopAgent &P = agent_of(D, ag);
-    float (&part)[4][4][256] = *reinterpret_cast<float (*)[4][4][256]>(lds);
     const long long epoch = *P.Aa.step_dev;
-    bwd_weights_body<true, true>((int)blockIdx.x - rows - ag * WG_ACTOR_WEIGHTS, n, 0, P.s, nullptr, P.sv_a, P.o_a, P.Ga, P.Aa, P.RSa,
-                                 part, lds + 4 * 4 * 256, P.ts, epoch, reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB));
+    TT_ACTOR_TAIL_WEIGHTS((int)blockIdx.x - rows - ag * WG_ACTOR_WEIGHTS, n, P.s, P.sv_a, P.o_a, P.Ga, P.Aa, P.RSa, lds, P.ts, epoch);
 }
 
 // ---- PBT exploit/explore (tt_pop_exploit): dst's learning state <- src's, then dst's hyperparameters, in one launch ----

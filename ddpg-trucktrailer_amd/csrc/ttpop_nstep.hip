@@ -1,15 +1,15 @@
 // ttpop_nstep.hip -- n-step returns in a population's learn() (MI355X, gfx950): each agent draws n-step tuples with its own n and
 // gamma inside the shared first launch.  Two kernels beside those of csrc/ttpop.hip, which stay as they are:
 //
-//   k_pop_fwd_multi_nstep   k_pop_fwd_multi with the sampled prologue written out again with the n-step pick (csrc/ttnstep.h), the way
-//                           k_fwd_multi_nstep (csrc/ttnstep.hip) restates k_fwd_multi's; fwd_small_body as there
+//   k_pop_fwd_multi_nstep   k_pop_fwd_multi with the sampled prologue of k_fwd_multi_nstep (TT_SAMPLED_ROWS_NSTEP,
+//                           csrc/ttlearn_sites.h; the pick is csrc/ttnstep.h's); fwd_small_body as there
 //   k_pop_set_nstep         the table writes of tt_pop_exploit_nstep, after k_pop_exploit on the same stream
 //
 // A workgroup takes n_step and gamma from its agent's entry of a table in device memory (PopNstep), read through the constant
 // address space as the descriptors are: they are scalars of the workgroup, so nstep_pick's grouped loads stay uniform.  The agent's
 // discount gamma ** n_step is its td.gamma, and the three launches behind this one are the one-step population's (csrc/ttnstep.h has
 // the argument).  In a translation unit of its own, so that no kernel of ttpop.hip or ttnstep.hip gains a neighbour that shares its
-// inlined helpers (the head of ttlearn_bodies.h tells why).
+// inlined helpers (the head of ttlearn_sites.h tells why).
 #include "ttnstep.h"
 #include "ttpop.h"
 
@@ -32,37 +32,7 @@ __global__ __launch_bounds__(64 * NW) void k_pop_fwd_multi_nstep(const int K, co
     const FwdJob &q = P.F.j[job];
     ttnet::RingSample R = P.F.R;
     R.seed += (unsigned long long)u * R.seed_stride;        // DDPGRollout._sample_key(u)
-    static_assert(TR / NW == 2, "two rows per wave");
-    const int tid = threadIdx.x, wave = tid >> 6, l15 = tid & 15;
-    const bool from_s = q.obs == R.s_out;                    // this job reads s (else s')
-    const float *orow;
-    // (a branch, not a select: only the rows at t0 + m need the walk's done flags)
-    if (from_s) orow = ttnet::nstep_s(R, ttnet::nstep_pick(R, min(row0 + l15, n - 1), n_step, gamma));
-    else orow = ttnet::nstep_s2(R, ttnet::nstep_pick(R, min(row0 + l15, n - 1), n_step, gamma));
-    bool have_act = false;
-    float act_r0 = 0.f, act_r1 = 0.f;
-    if (q.critic && q.action) {
-        act_r0 = ttnet::nstep_a(R, ttnet::nstep_pick(R, min(row0 + wave * 2, n - 1), n_step, gamma));
-        act_r1 = ttnet::nstep_a(R, ttnet::nstep_pick(R, min(row0 + wave * 2 + 1, n - 1), n_step, gamma));
-        have_act = true;
-    }
-    if (job == P.F.write_s || job == P.F.write_s2) {        // the batch rows of this workgroup for the later launches
-        const int lr = tid / ttnet::IN, c = tid - lr * ttnet::IN, b = row0 + lr;
-        if (lr < TR && b < n) {
-            const ttnet::NstepPick p = ttnet::nstep_pick(R, b, n_step, gamma);
-            if (job == P.F.write_s) {
-                R.s_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s(R, p)[c];
-                if (c == 0) {
-                    R.a_out[b] = ttnet::nstep_a(R, p);
-                    if (R.idx_out) { R.idx_out[2 * b] = p.t0; R.idx_out[2 * b + 1] = p.e; }
-                }
-            }
-            if (job == P.F.write_s2) {
-                R.s2_out[(size_t)b * ttnet::IN + c] = ttnet::nstep_s2(R, p)[c];
-                if (c == 0) { R.r_out[b] = p.R; R.d_out[b] = (uint8_t)p.D; }
-            }
-        }
-    }
+    TT_SAMPLED_ROWS_NSTEP(R, n, row0, q, job, P.F.write_s, P.F.write_s2, n_step, gamma, orow, have_act, act_r0, act_r1);
     if (q.critic)
         fwd_small_body<true>(n, q.obs, q.action, q.W, q.out, q.sv, q.dq_da, q.z_state, h1_s, z_s, w1_s, row0, orow, have_act, act_r0, act_r1);
     else

@@ -28,18 +28,7 @@ __global__ __launch_bounds__(64 * NW) void k_bwd_rows_pair_shaped(const int n, c
     __shared__ __attribute__((aligned(16))) float dx2_s[DXS_FLOATS];
     __shared__ float red[2 * NW * TR];
     __shared__ float rsc_s[TR];
-    kernarg_warm<16 + 2 * ((int)sizeof(Weights) + (int)sizeof(Saved) + (int)sizeof(BwdOut)) + (int)sizeof(TdIn) + 8>();
-    const int nb = (n + TR - 1) / TR;
-    if ((int)blockIdx.x == 2 * nb) {         // the extra workgroup: counters + bias corrections (nothing in this launch reads them)
-        if (threadIdx.x == 0) clock_tick(td);
-        return;
-    }
-    if ((int)blockIdx.x > 2 * nb) {          // the image's workgroups (they read a SNAPSHOT of the step number: see ImageJob)
-        ttnet::split_pack_body(img.W, false, img.ws, img.ws_alt, nullptr, img.cur,
-                               ((int)blockIdx.x - 2 * nb - 1) * (64 * NW) + (int)threadIdx.x);
-        ttnet::publish_image(img.cur, IMAGE_WGS);
-        return;
-    }
+    TT_BWD_ROWS_PAIR_FRONT(nb, n, td, img);
     KBEGIN(1);
     if ((int)blockIdx.x < nb) {
         bwd_rows_body<true, false, true>(n, scale_c, q_out, Wc, sv_c, o_c, td, dx2_s, red, rsc_s, blockIdx.x * TR, nullptr, huber_delta);
@@ -71,23 +60,15 @@ __global__ __launch_bounds__(64 * NW) void k_actor_tail_shaped(const int n, cons
     __shared__ __attribute__((aligned(16))) float lds[H1S_FLOATS + TR * DS + H1 * IN];
     const int nb = (n + TR - 1) / TR;
     if ((int)blockIdx.x < nb) {
-        const Saved none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
         const long long epoch = *A.step_dev;
         KBEGIN(3);
-        fwd_small_body<true>(n, obs, mu, Wc, q_out, none, dq_da, nullptr, lds, lds + H1S_FLOATS, lds + H1S_FLOATS + TR * DS,
-                             blockIdx.x * TR, nullptr, false, 0.f, 0.f, ts.rows, (unsigned)epoch);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // every wave: its rows' words have been sent
-        __syncthreads();
-        if (threadIdx.x == 0) __hip_atomic_store(ts.hints + blockIdx.x, (int)epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        TT_ACTOR_TAIL_ROWS(n, obs, mu, Wc, q_out, dq_da, lds, ts, blockIdx.x, epoch);
         KEND(3);
         return;
     }
     if (threadIdx.x >= 256) return;
-    static_assert(sizeof(float) * (H1S_FLOATS + TR * DS + H1 * IN) >= sizeof(float) * (4 * 4 * 256 + MAXB + 2048), "the weight kernel's LDS fits");
-    float (&part)[4][4][256] = *reinterpret_cast<float (*)[4][4][256]>(lds);
     const long long epoch = *A.step_dev;
-    bwd_weights_body<true, true, true>((int)blockIdx.x - nb, n, 0, obs, nullptr, sv, d, G, A, RS, part, lds + 4 * 4 * 256, ts, epoch,
-                                       reinterpret_cast<_Float16 *>(lds + 4 * 4 * 256 + MAXB), pre_scale, pre);
+    TT_ACTOR_TAIL_WEIGHTS_SHAPED(true, (int)blockIdx.x - nb, n, obs, sv, d, G, A, RS, lds, ts, epoch, pre_scale, pre);
 }
 
 // what every shaped entry point refuses of a tt_loss_shape: TT_OK, or TT_EINVAL with "<who>: <reason>"

@@ -50,3 +50,18 @@ def test_env_step_of_the_loop_keeps_four_waves_per_simd(ks):
     # k_step<PER_ENV = false, INFO = false, AUTO_RESET, RANDOM_POLICY>: the variants bench.py and the DDPG loop launch
     for n, v in the(ks, "6k_stepILb0ELb0E").items():
         assert kr.waves_per_simd(v["vgpr"]) >= 4 and v["scratch"] == 0, (n, v)
+
+
+def test_text_sections_lists_every_code_object_once_and_is_stable():
+    """One (size, sha256) per code object, in the order of build.SRC: hipcc makes one code object per source that defines a kernel
+    (csrc/ttp2p.hip is host code only and has none), so that is what the library must hold.  The table is what
+    `kernel_resources --text before.so after.so` compares (csrc/ttlearn_sites.h)."""
+    from ddpg_trucktrailer_amd import build
+
+    with_kernels = [p for p in build.SRC if "__global__" in open(p).read()]
+    assert len(build.SRC) - len(with_kernels) <= 1, "more than ttp2p.hip without a kernel: look at this test's premise"
+    ts = kr.text_sections()
+    assert len(ts) == len(with_kernels)
+    for size, digest in ts:
+        assert size > 0 and len(digest) == 64 and int(digest, 16) >= 0
+    assert kr.text_sections() == ts
