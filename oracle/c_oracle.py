@@ -77,6 +77,17 @@ class COracle:
                               _p(L2, C.c_double), _p(obs, C.c_float))
         return obs
 
+    def place_lanes(self, idx, start):
+        """place() for the lanes idx [k] alone, at start [k,3]: a fresh episode there (default goal and trailer length); every
+        other lane keeps its state and its reward carry.  Returns the placed lanes' first observations [k,23]."""
+        idx = np.asarray(idx, np.int64).reshape(-1)
+        start = np.ascontiguousarray(np.broadcast_to(np.asarray(start, np.float64), (len(idx), 3)))
+        obs = np.zeros((len(idx), OBS_DIM), np.float32)
+        for j, i in enumerate(idx):
+            lib().tto_place_batch(C.byref(self.params), C.byref(self.envs[int(i)]), 1, _p(start[j], C.c_double), None, None,
+                                  _p(obs[j], C.c_float))
+        return obs
+
     def set_state(self, i, y):
         y = np.ascontiguousarray(y, np.float64)
         lib().tto_set_state(C.byref(self.envs[i]), _p(y, C.c_double))

@@ -1,0 +1,387 @@
+"""GPU (-m gpu): the vector loop (VectorStepper + DDPGRollout) step by step against a plain host reference (tests/loop_ref.py, itself
+held to its statement by tests/test_loop_ref_cpu.py) -- not against another path of the library.
+
+  streams   reset and auto-reset poses, tt_env_random_actions, tt_ring_sample / the seed-stride form / tt_ring_sample_nstep: the
+            library called directly, every value against the generator's definition (poses within 2 ulp, the rest exact)
+  lock-step DDPGRollout at N = 200 (two ragged policy tiles, four ragged step tiles), B = 33, every launch eager, 16 vector steps
+            (the ring wraps more than twice), first episodes capped at 3 + lane % 11 steps; after every step:
+              a  policy: stored action - noise == the actor in f64 on the weights the step began with (2e-5, test_gpu_fused_net's bound)
+              b  noise: x == ou_next(x before, done of step t - 1, ou_normal(seed, t)) within 1e-5 scale max(1, |N|) + ulp32(x)
+              c  scaled == clamp(stored action, -1, 1) * f32(pi / 4), bit for bit
+              d  env: reward, state, s' and done against the C oracle driven with the device's own scaled actions (1e-5, done exact);
+                 a finished lane's episode number, start pose (reset_pose), and first observation (oracle lane placed there)
+              e  every ring row outside slot t (act, rew, done) and slot t + 1 (obs) keeps its bits
+              f  ring counter, window counter, the learner's step count by the order rule (LoopRef.learns)
+              g  the draw: idx == draw(...) exactly, every drawn step inside window(...), the batch buffers == the host's gather
+              h  learn(): a second loop loaded with the state from before the step and given the host-gathered batches through
+                 learner.learn_batch ends with the same weights, targets, Adam moments and step counts, bit for bit
+            in four configurations: serial; pipelined with two updates (the opening launch makes both draws); pipelined with
+            n_step = 3 (learn()'s first launch draws); serial TD3 with two updates (the TD3 launches draw).  The pipelined ones end
+            with the ring's counter set one step behind the window's by hand (what a captured graph's learn chain may meet): the
+            draw must follow the window counter -- in eager steps the two are equal whenever a draw is made.
+
+Tolerances.  Poses: "2 ulp of f64" is taken at the scale of the box (2 * spacing(max(|lo|, |hi|))): lo + (hi - lo) u as one fma
+differs from the separately rounded form by half an ulp of the product plus half an ulp of the sum, and near x = 0 the product is
+the larger.  Noise: the TD3 noise test's bound for the same formula plus the fma's rounding.  Everything else exact or an existing
+bound of the project.
+
+TD3 (configuration 4): the learner always draws for itself, from its ring, so the second loop is given the first one's ring as it
+stood after the env step (held to the oracle by d and e) and the counter t + 1, and ITS draw of every update -- idx and batch
+buffers -- is checked against the host's; the first loop's buffers show the last update's draw only, which is checked as well.
+
+Measured on MI355X (each figure from one run; worst error / bound over the run):
+  poses (streams test, 400 auto-resets and both resets)  0.5 of the 2 ulp, i.e. one ulp at the box's scale
+  n-step R of the lone draws                              0.13 of nstep_ref's bound
+  lock-step                 policy (a)   noise (b)   env (d)   pose    n-step R
+    serial                  0.0024       0.029       0.37      0.5     -
+    pipelined, 2 updates    0.0055       0.029       0.38      0.5     -
+    pipelined, n_step 3     0.0023       0.029       0.39      0.5     0.11
+    serial TD3, 2 updates   0.0038       0.029       0.34      0.5     -
+  (the noise figure repeats because the four loops share the seed; test_gpu_td3.py::test_noise measured 0.019 for the same formula.)
+  In every configuration 200 episodes ended, at 11 different steps; idx, done, scaled, the untouched ring rows, the counters, the
+  gathered batches and the second loop's learner state were equal bit for bit at every step.  The seven tests take 5 s together."""
+import math
+
+import numpy as np
+import pytest
+
+import loop_ref as M
+
+pytestmark = pytest.mark.gpu
+
+N, B, STEPS = 200, 33, 16
+SEED, ENV_SEED = 31, 17
+LANES = np.arange(N)
+
+
+def _pose_tol():
+    lo, hi = M.reset_box()
+    return 2.0 * np.spacing(np.maximum(np.abs(lo), np.abs(hi)))
+
+
+def _check_poses(env, want, what):
+    got = env.episode()["start"].cpu().numpy()
+    err = np.abs(got - want) / _pose_tol()
+    assert err.max() <= 1.0, (what, err.max())
+    return float(err.max())
+
+
+# ---- the streams alone ------------------------------------------------------------------------------------------------
+def test_reset_and_auto_reset_poses_and_random_actions(gpu_device):
+    """reset(seed) -> episode 0 of every lane; a masked reset with another seed -> the masked lanes' episode 1 under that seed, which
+    also serves every later auto-reset; 12 steps of random_actions with auto_reset, episodes capped short (twice) so that lanes end
+    at staggered steps: after each, every lane's start pose is reset_pose(seed, lane, its episode number), and random_actions is
+    random_action bit for bit."""
+    import torch
+    from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+    env = TruckTrailerVecEnv(N)
+    env.reset(seed=41)
+    episode = np.zeros(N, np.int64)
+    worst = _check_poses(env, M.reset_pose(41, LANES, episode), "reset")
+    mask = LANES % 3 == 0
+    env.reset(seed=43, mask=torch.from_numpy(mask.astype(np.uint8)).cuda())
+    episode[mask] += 1
+    want = np.where(mask[:, None], M.reset_pose(43, LANES, episode), M.reset_pose(41, LANES, episode))
+    worst = max(worst, _check_poses(env, want, "masked reset"))
+    env.set_max_steps(2 + LANES % 5)
+    ended, ended_at = 0, set()
+    for t in range(12):
+        if t == 7:        # a second round of short episodes: lanes reach episode numbers 2 and 3
+            env.set_max_steps(env.episode()["steps"].cpu().numpy() + 1 + LANES % 4)
+        a = env.random_actions(seed=9, step=t)
+        assert np.array_equal(a.cpu().numpy(), M.random_action(9, LANES, t)), t
+        _, _, done, _ = env.step(a, auto_reset=True)
+        d = done.cpu().numpy() != 0
+        episode[d] += 1
+        want[d] = M.reset_pose(43, LANES[d], episode[d])
+        worst = max(worst, _check_poses(env, want, f"auto-reset at step {t}"))
+        ended += int(d.sum())
+        if d.any():
+            ended_at.add(t)
+    assert ended >= 2 * N - N // 4 and len(ended_at) >= 6 and episode.max() >= 3, (ended, ended_at, episode.max())
+    big = 2 ** 40 + 5
+    assert np.array_equal(env.random_actions(seed=2 ** 35 + 1, step=big).cpu().numpy(), M.random_action(2 ** 35 + 1, LANES, big))
+    print(f"RATIOS loop poses: worst |start - reset_pose| / (2 ulp) {worst:.3g} over {ended} auto-resets")
+    env.close()
+
+
+def _filled_ring(dev, slots):
+    import torch
+    from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
+    g = torch.Generator().manual_seed(slots)
+    ring = TrajectoryRing(N, slots, 23, dev)
+    ring.obs.copy_(torch.rand(ring.obs.shape, generator=g) * 2 - 1)
+    ring.act.copy_(torch.rand(ring.act.shape, generator=g) * 2 - 1)
+    ring.rew.copy_(torch.rand(ring.rew.shape, generator=g) * 10 - 5)
+    ring.done.copy_((torch.rand(ring.done.shape, generator=g) < 0.2).to(torch.uint8))
+    return ring, {k: getattr(ring, k).cpu().numpy() for k in ("obs", "act", "rew", "done")}
+
+
+def _same_batch(bufs, want, what):
+    for i, (x, y) in enumerate(zip(bufs, want)):
+        assert np.array_equal(x.cpu().numpy().reshape(np.shape(y)), y), (what, i)
+
+
+@pytest.mark.parametrize("reserve,lag", [(0, 0), (2, 1)])
+def test_ring_draws_are_the_documented_rows(gpu_device, reserve, lag):
+    """n_envs = 200, B = 513, every counter 0 .. 14 given through an explicit k_dev: tt_ring_sample (6 slots), the seed-stride form
+    through pack_and_sample(draws=3) (6 slots) and tt_ring_sample_nstep with n = 3 (8 slots: six have no window for n = 3 under a
+    reserve of 2): idx is draw(...) / draw_nstep(...) exactly, and the batch is the host's gather of those rows."""
+    import torch
+    from ddpg_trucktrailer_amd import fused
+    from ddpg_trucktrailer_amd.agent import Agent
+    dev, rows, gamma = gpu_device, 513, 0.99
+    ring, host = _filled_ring(dev, 6)
+    ring8, host8 = _filled_ring(dev, 8)
+    actor = Agent(1e-4, 1e-3, (23,), 1e-3, 1, batch_size=rows, device=dev, replay=False).actor
+    kd = torch.zeros((), dtype=torch.int64, device=dev)
+    worst = 0.0
+    for k in range(15):
+        kd.fill_(k)
+        seed = 2 ** 40 + 7 * k
+        out = ring.sample_fused(rows, seed=seed, return_index=True, done_as_bool=False, k_dev=kd, reserve=reserve, lag=lag)
+        idx = M.draw(seed, k, rows, N, 6, reserve, lag)
+        assert np.array_equal(out[5].cpu().numpy(), idx), k
+        _same_batch(out[:5], M.gather(host, idx), ("one-step", k))
+        fused.pack_and_sample(actor, 0, ring.sample_args(rows, seed=seed, k_dev=kd, reserve=reserve, lag=lag, draws=3,
+                                                         seed_stride=M.SEED_STRIDE))
+        big = [x.cpu().numpy() for x in ring._batch_bufs(3 * rows)]
+        for u in range(3):
+            idx = M.draw(M.update_seed(seed, u), k, rows, N, 6, reserve, lag)
+            assert np.array_equal(big[5][u * rows:(u + 1) * rows], idx), (k, u)
+            for i, y in enumerate(M.gather(host, idx)):
+                assert np.array_equal(big[i][u * rows:(u + 1) * rows].reshape(np.shape(y)), y), (k, u, i)
+        out = ring8.sample_fused(rows, seed=seed, return_index=True, done_as_bool=False, k_dev=kd, reserve=reserve, lag=lag, n_step=3,
+                                 gamma=gamma)
+        idx = M.draw_nstep(seed, k, rows, N, 8, 3, reserve, lag)
+        assert np.array_equal(out[5].cpu().numpy(), idx), k
+        if len(M.window(k, 8, reserve, lag, 3)):
+            want = M.gather_nstep(host8, idx, 3, gamma)
+            _same_batch((out[0], out[1], out[3], out[4]), (want["s"], want["a"][:, None], want["s2"], want["D"].astype(np.uint8)), ("n-step", k))
+            err = np.abs(out[2].double().cpu().numpy() - want["R"])
+            assert (err <= want["bound"]).all(), k
+            worst = max(worst, float((err / np.maximum(want["bound"], 1e-300)).max()))
+    print(f"RATIOS loop draws reserve {reserve} lag {lag}: idx exact, worst |R - R64| / bound {worst:.3g}")
+
+
+# ---- the loop in lock-step --------------------------------------------------------------------------------------------
+def _configs():
+    return [pytest.param("serial", dict(pipeline=False), 6, id="serial"),
+            pytest.param("pipelined", dict(pipeline=True, updates_per_step=2), 6, id="pipelined-2-updates"),
+            pytest.param("pipelined", dict(pipeline=True, n_step=3), 8, id="pipelined-n-step-3"),
+            pytest.param("serial", dict(pipeline=False, updates_per_step=2, td3=True), 6, id="serial-td3")]
+
+
+def _make_loop(dev, kw, slots):
+    from ddpg_trucktrailer_amd.rollout import DDPGRollout
+    from ddpg_trucktrailer_amd.td3 import TD3Config
+    from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
+    kw = dict(kw)
+    if kw.get("td3"):
+        kw["td3"] = TD3Config(policy_delay=2)
+    env = TruckTrailerVecEnv(N)
+    env.reset(seed=ENV_SEED)
+    env.set_max_steps(3 + LANES % 11)
+    return DDPGRollout(env, batch_size=B, replay_slots=slots, seed=SEED, graph_steps=0, use_graph=False, **kw)
+
+
+def _learn_state(loop):
+    fl = loop.learner
+    out = [p.detach() for net in loop.agent._nets() for p in net.parameters()]
+    out += [fl.actor.m, fl.actor.v, fl.critic.m, fl.critic.v, fl.step_dev]
+    if loop.td3 is not None:
+        out += [fl.critic_2.m, fl.critic_2.v, fl.actor_step_dev]
+    return out
+
+
+def _ring_np(ring):
+    return {k: getattr(ring, k).cpu().numpy() for k in ("obs", "act", "rew", "done")}
+
+
+@pytest.mark.parametrize("order,kw,slots", _configs())
+def test_vector_loop_in_lock_step_with_the_host_model(gpu_device, order, kw, slots):
+    import torch
+    from ddpg_trucktrailer_amd.networks import ActorNetwork
+    from ddpg_trucktrailer_amd.td3 import TD3Learner
+    from oracle import c_oracle
+    dev = gpu_device
+    td3, n_step, updates = bool(kw.get("td3")), int(kw.get("n_step", 1)), int(kw.get("updates_per_step", 1))
+    pipelined = order == "pipelined"
+    loop, twin = _make_loop(dev, kw, slots), _make_loop(dev, kw, slots)
+    assert loop.pipeline is pipelined and loop.graph_steps == 0 and not loop.use_graph and loop.ring_mode
+    assert isinstance(loop.learner, TD3Learner) is td3 and loop.learner.fuse_tail == twin.learner.fuse_tail
+    env, ring, fl = loop.env, loop.ring, loop.learner
+    gamma = float(loop.agent.gamma)
+
+    ora = c_oracle.COracle(N)
+    ref = M.LoopRef(SEED, ENV_SEED, N, slots, B, pipelined, updates, n_step, oracle=ora)
+    obs0 = ora.place(ref.start_poses())
+    for i in LANES:
+        ora.set_max_steps(int(i), 3 + int(i) % 11)
+    worst = dict(a=0.0, b=0.0, d=0.0, pose=0.0, R=0.0)
+    worst["pose"] = _check_poses(env, ref.start_poses(), "reset")
+    start_dev = env.episode()["start"].cpu().numpy()
+    assert np.abs(ring.obs[0].cpu().numpy() - obs0).max() <= 1e-5
+    actor64 = ActorNetwork(1e-4, (23,), 400, 300, 1, name="actor", device=torch.device("cpu")).double()
+    high = np.float32(math.pi / 4)
+    episodes, ended_at, restarted_lanes, both_updates = 0, set(), 0, 0
+
+    for t in range(STEPS):
+        sd = loop.state_dict()                     # (synchronises) weights, moments, counts, ring, noise, env before the step
+        before = {k: sd["ring"][k].numpy() for k in ("obs", "act", "rew", "done")}
+        x_before = sd["ou"].numpy().astype(np.float64)
+        state_before = [x.clone() for x in _learn_state(loop)]
+        assert sd["ring"]["k"] == t
+        loop.step()
+        torch.cuda.synchronize()
+        after = _ring_np(ring)
+        s_t, s_t1 = t % slots, (t + 1) % slots
+        x = loop.noise.x.cpu().numpy()
+        act, scaled = after["act"][s_t], loop.scaled.cpu().numpy()
+
+        # a: the policy read obs[slot t] with the weights the step began with
+        actor64.load_state_dict({k: v.double() for k, v in sd["nets"]["actor"].items()})
+        with torch.no_grad():
+            mu64 = actor64(torch.from_numpy(before["obs"][s_t]).double()).view(-1).numpy()
+        err = np.abs(act.astype(np.float64) - x.astype(np.float64) - mu64) / 2e-5
+        worst["a"] = max(worst["a"], float(err.max()))
+        assert err.max() <= 1.0, (t, "policy", err.max())
+
+        # b: the noise
+        done_prev = before["done"][(t - 1) % slots] != 0 if t > 0 else None
+        x_want, nrm = ref.noise(t, x_before, done_prev)
+        tol = 1e-5 * M.OU_SCALE * np.maximum(1.0, np.abs(nrm)) + np.spacing(np.abs(x_want).astype(np.float32)).astype(np.float64)
+        err = np.abs(x.astype(np.float64) - x_want) / tol
+        worst["b"] = max(worst["b"], float(err.max()))
+        assert err.max() <= 1.0, (t, "noise", err.max(), int(err.argmax()))
+        if done_prev is not None and done_prev.any():
+            assert (np.abs(x.astype(np.float64) - M.OU_SCALE * nrm)[done_prev] <= tol[done_prev]).all(), (t, "noise restart")
+            restarted_lanes += int(done_prev.sum())
+
+        # c: what the env was driven with
+        assert np.array_equal(scaled, np.clip(act, np.float32(-1), np.float32(1)) * high), (t, "scaled")
+
+        # d: the env step against the oracle, on the device's own actions
+        o_obs, o_rew, o_done, _ = ora.step(scaled)
+        done = after["done"][s_t] != 0
+        assert np.array_equal(done, o_done), (t, "done")
+        live = ~done
+        state = env.state.cpu().numpy()
+        errs = [np.abs(after["rew"][s_t].astype(np.float64) - o_rew).max(), np.abs(state[live] - ora.state()[live]).max(),
+                np.abs(after["obs"][s_t1][live] - o_obs[live]).max()]
+        if done.any():
+            lanes = LANES[done]
+            poses, first = ref.restart(lanes)
+            got = env.episode()["start"].cpu().numpy()
+            perr = (np.abs(got[lanes] - poses) / _pose_tol()).max()
+            worst["pose"] = max(worst["pose"], float(perr))
+            assert perr <= 1.0, (t, "auto-reset pose", perr)
+            assert np.array_equal(got[live], start_dev[live]), (t, "a running lane's start pose moved")
+            start_dev = got
+            errs += [np.abs(after["obs"][s_t1][lanes] - first).max(), np.abs(state[lanes] - ora.state()[lanes]).max()]
+            episodes += int(done.sum())
+            ended_at.add(t)
+        worst["d"] = max(worst["d"], float(max(errs)) / 1e-5)
+        assert max(errs) <= 1e-5, (t, "env", errs)
+
+        # e: nothing else moved
+        for name in ("act", "rew", "done", "obs"):
+            keep = np.arange(slots) != (s_t1 if name == "obs" else s_t)
+            assert np.array_equal(after[name][keep], before[name][keep]), (t, "ring rows outside the step's slots", name)
+
+        # f: counters
+        assert int(ring.k_dev.item()) == t + 1 and ring.k == t + 1
+        if pipelined:
+            assert int(loop.k_pipe_dev.item()) == t + 1
+        assert int(fl.step_dev.item()) == ref.updates_after(t), (t, int(fl.step_dev.item()), ref.updates_after(t))
+        if td3:
+            assert int(fl.actor_step_dev.item()) == ref.updates_after(t) // 2
+
+        # g, h: the draw and learn()
+        if not ref.learns(t):
+            for i, (p, q) in enumerate(zip(_learn_state(loop), state_before)):
+                assert torch.equal(p, q), (t, "no learn() in this step, yet something moved", i)
+        else:
+            src = before if pipelined else after           # the ring as it stood when the rule says the draw reads it
+            win = ref.window(t)
+            assert len(win) > 0
+            draws = ref.draws(t)
+            twin.load_state_dict(sd)
+            if td3:
+                for name in ("obs", "act", "rew", "done"):
+                    getattr(twin.ring, name).copy_(getattr(ring, name))
+                twin.ring.k = t + 1
+                twin.ring.k_dev.fill_(t + 1)
+            # what the loop's own batch buffers show after the step: (update, its six buffers)
+            if td3:
+                seen = [(updates - 1, [b.cpu().numpy() for b in ring._batch_bufs(B)])]
+            elif updates > 1:
+                big = [b.cpu().numpy() for b in ring._batch_bufs(B * updates)]
+                seen = [(u, [b[u * B:(u + 1) * B] for b in big]) for u in range(updates)]
+            else:
+                seen = [(0, [b.cpu().numpy() for b in ring._batch_bufs(B)])]
+            batches = {}
+            for u, idx in enumerate(draws):
+                steps = ref.steps_of(t, idx)
+                assert steps.min() >= win[0] and steps.max() <= win[-1], (t, u, "a drawn step outside the window")
+                if n_step > 1:
+                    w = M.gather_nstep(src, idx, n_step, gamma)
+                    batches[u] = [w["s"], w["a"][:, None], None, w["s2"], w["D"].astype(np.uint8)]
+                    batches[u].append(w)
+                else:
+                    batches[u] = list(M.gather(src, idx))
+            for u, bufs in seen:
+                assert np.array_equal(bufs[5], draws[u]), (t, u, "idx")
+                for i in (0, 1, 2, 3, 4):
+                    if n_step > 1 and i == 2:
+                        w = batches[u][5]
+                        err = np.abs(bufs[2].astype(np.float64) - w["R"])
+                        assert (err <= w["bound"]).all(), (t, u, "R")
+                        worst["R"] = max(worst["R"], float((err / np.maximum(w["bound"], 1e-300)).max()))
+                        batches[u][2] = bufs[2].copy()           # (f32 bits of R within the bound: what the second loop is given)
+                    else:
+                        assert np.array_equal(bufs[i].reshape(batches[u][i].shape), batches[u][i]), (t, u, "batch tensor", i)
+            if updates > 1 and len(seen) == updates:
+                both_updates += 1
+            for u in range(updates):
+                if td3:
+                    twin.learner.learn_batch(u=u, full=(u + 1) % 2 == 0)
+                    torch.cuda.synchronize()
+                    bufs = [b.cpu().numpy() for b in twin.ring._batch_bufs(B)]
+                    assert np.array_equal(bufs[5], draws[u]), (t, u, "idx (second loop)")
+                    for i in range(5):
+                        assert np.array_equal(bufs[i].reshape(batches[u][i].shape), batches[u][i]), (t, u, "batch tensor (second loop)", i)
+                else:
+                    s, a, r, s2, d = (torch.from_numpy(np.ascontiguousarray(v)).to(dev) for v in batches[u][:5])
+                    twin.learner.learn_batch(s, a, r, s2, d, n_step=n_step)
+            torch.cuda.synchronize()
+            if td3 and updates > 1:
+                both_updates += 1
+            for i, (p, q) in enumerate(zip(_learn_state(loop), _learn_state(twin))):
+                assert torch.equal(p, q), (t, "learn(): the loop and the second loop on the host's batches differ", i)
+            assert any(not torch.equal(p, q) for p, q in zip(_learn_state(loop)[:4], state_before[:4])), (t, "learn() moved no weight")
+
+    assert episodes >= 20 and len(ended_at) >= 5 and restarted_lanes >= 5, (episodes, ended_at, restarted_lanes)
+    assert ring.k >= 2 * slots
+    if updates > 1:
+        assert both_updates >= 10, both_updates
+    assert fl.tail_gave_up() == 0 and not loop.handover_gave_up
+    if pipelined:
+        # The pipelined draw reads the window counter k_pipe_dev, not the ring's k_dev.  In eager steps both hold t when the draw is
+        # made, so the steps above cannot tell them apart; in a captured graph learn()'s chain runs ahead and the ring's counter may
+        # still lack the env step of t - 1.  That state, made by hand: the rows are still those of the counter t.
+        t = STEPS
+        ring.k_dev.fill_(t - 1)
+        if n_step == 1:
+            loop._open_step(True)              # the opening launch makes the step's draws
+        else:
+            loop._learn_all()                  # learn()'s first launch makes the draw
+        torch.cuda.synchronize()
+        ring.k_dev.fill_(t)
+        idx = ring._batch_bufs(B * (updates if n_step == 1 else 1))[5].cpu().numpy()
+        for u, want in enumerate(ref.draws(t)):
+            assert np.array_equal(idx[u * B:(u + 1) * B], want), (u, "the draw is keyed by the ring's counter, not the window's")
+    print(f"RATIOS loop lock-step {order} {kw}: policy {worst['a']:.3g}, noise {worst['b']:.3g}, env {worst['d']:.3g}, "
+          f"pose {worst['pose']:.3g}, n-step R {worst['R']:.3g}; {episodes} episodes ended at {len(ended_at)} different steps")
+    loop.env.close()
+    twin.env.close()
