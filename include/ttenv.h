@@ -13,6 +13,13 @@
  *    tt_last_error() returns a message owned by the handle (or by the library for a NULL handle);
  *  - every array pointer is a DEVICE pointer owned by the caller (e.g. torch `data_ptr()`),
  *    layouts as stated per argument; N = number of envs of the handle;
+ *  - no entry point reads or writes outside the extents stated per argument.  A pointer needs the natural alignment of its
+ *    element type, and 16 bytes -- what any torch allocation has -- where the kernels use 16-byte accesses: the parameter
+ *    tensors of a tt_mlp_weights (w1, the per-neuron vectors, w2, w3, wa, ba), the [B,400] and [B,300] arrays of tt_mlp_saved
+ *    and tt_mlp_bwd_ws (their [B] arrays rstd1, rstd2 and dpre are accessed as scalars), z_state, bias_corr_out, split_ws and
+ *    fc2_img.  Gradient tensors (a tt_mlp_weights of gradients) and Adam moments may sit at their offsets in ONE flat,
+ *    16-byte-aligned f32 buffer in tt_mlp_weights order (so wa and ba are only 4-byte aligned); observation, action, reward
+ *    and done arrays may be slot views of a ring (4- and 1-byte aligned: the env's observation stores test the address);
  *  - work is enqueued on the caller's stream (`tt_stream_t` is `hipStream_t`; NULL = the
  *    default stream) and is asynchronous; nothing here synchronises or allocates after create;
  *  - one host thread per handle; handles are independent (one process per GPU, one handle per
