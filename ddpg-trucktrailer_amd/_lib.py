@@ -135,6 +135,12 @@ class TTLossShape(C.Structure):
     _fields_ = [("huber_delta", C.c_float), ("pre_scale", C.c_float), ("pre", C.c_void_p)]
 
 
+class TTDemoLoss(C.Structure):
+    """tt_demo_loss (include/ttenv.h): a [n], idx [n][2], q [n] (with q_filter), k = 2 lambda, q_filter; out: dq_eff [n], code [n]."""
+    _fields_ = [("a", C.c_void_p), ("idx", C.c_void_p), ("q", C.c_void_p), ("k", C.c_float), ("q_filter", C.c_int32),
+                ("dq_eff", C.c_void_p), ("code", C.c_void_p)]
+
+
 class TTLearnLogJob(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
                [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
@@ -266,6 +272,12 @@ _SIGNATURES = {
                                            C.POINTER(TTMlpWeights), C.c_float, _I, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
                                            C.c_float, C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, _P, _P,
                                            C.POINTER(TTLossShape), _P]),
+    "tt_mlp_forward_save_demo": (C.c_int, [_I, _I, _P, _P, C.POINTER(TTMlpWeights), _P, C.POINTER(TTMlpSaved), _P,
+                                           C.POINTER(TTDemoLoss), _P]),
+    "tt_mlp_actor_tail_demo": (C.c_int, [_I, _P, _P, C.POINTER(TTMlpWeights), _P, _P, C.POINTER(TTMlpSaved), C.POINTER(TTMlpBwdWs),
+                                         C.POINTER(TTMlpWeights), C.c_float, _I, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
+                                         C.c_float, C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, _P, _P,
+                                         C.POINTER(TTLossShape), C.POINTER(TTDemoLoss), _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

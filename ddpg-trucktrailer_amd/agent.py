@@ -44,11 +44,19 @@ class GradAllReduce:
 class Agent():
     def __init__(self, alpha, beta, input_dims, tau, n_actions, gamma=0.99,
                  max_size=1000000, fc1_dims=400, fc2_dims=300,
-                 batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True, td3=None, loss_shape=None):
+                 batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True, td3=None, loss_shape=None,
+                 demo_loss=None):
         """td3: None = DDPG, line for line; a td3.TD3Config = TD3 (Fujimoto et al., 2018): a second critic `critic_2` with its target
         `target_critic_2`, target-policy smoothing, and the actor and all targets updated on every policy_delay-th update only.
         loss_shape: None = the MSE critic loss and the plain actor loss; a loss_shape.LossShape = the Huber critic loss and / or the
-        actor's pre-activation penalty c mean(pre^2) in learn_batch.  Not with td3."""
+        actor's pre-activation penalty c mean(pre^2) in learn_batch.  Not with td3.
+        demo_loss: None, or a demo_loss.DemoLoss = a behaviour-cloning term on the rows learn_batch is told are demonstrations
+        (demo_rows=), gated by a Q-filter.  Composes with loss_shape.  Not with td3."""
+        if demo_loss is not None:
+            from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
+            check_demo_loss(demo_loss, td3=td3)
+        self.demo_loss = demo_loss
+        self.last_demo_mask = None       # [B] bool: the rows the last learn_batch applied the cloning term to
         if loss_shape is not None:
             from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
             check_loss_shape(loss_shape, td3=td3)
@@ -128,10 +136,14 @@ class Agent():
         states, actions, rewards, states_, done = self.memory.sample_buffer(self.batch_size)
         self.learn_batch(states, actions, rewards, states_, done)
 
-    def learn_batch(self, states, actions, rewards, states_, done, discount=None, eps=None, full=None):
+    def learn_batch(self, states, actions, rewards, states_, done, discount=None, eps=None, full=None, demo_rows=None):
         # discount: what multiplies q' in the target (default gamma); gamma ** n for a batch of n-step tuples (TrajectoryRing.sample)
         # eps, full: TD3 only (see _learn_batch_td3)
+        # demo_rows (with demo_loss): [B] bool, the rows that are demonstrations (None: none is)
         discount = self.gamma if discount is None else discount
+        demo = self.demo_loss
+        if demo_rows is not None and demo is None:
+            raise ValueError("demo_rows without demo_loss (Agent(demo_loss=...))")
         if self.td3 is not None:
             return self._learn_batch_td3(states, actions, rewards, states_, done, discount, eps, full)
         with T.no_grad():
@@ -166,9 +178,22 @@ class Agent():
         # zero_grad (DDPG_agent.py:95,100-104); asking for the actor's gradients only changes nothing the optimizers see.
         if shape is not None and shape.pre_penalty > 0:
             mu, pre = self.actor.forward_pre(states)
-            actor_loss = T.mean(-self.critic.forward(states, mu)) + shape.pre_penalty * T.mean(pre * pre)
+            q_pi = self.critic.forward(states, mu)
+            actor_loss = T.mean(-q_pi) + shape.pre_penalty * T.mean(pre * pre)
         else:
-            actor_loss = T.mean(-self.critic.forward(states, self.actor.forward(states)))
+            mu = self.actor.forward(states)
+            q_pi = self.critic.forward(states, mu)
+            actor_loss = T.mean(-q_pi)
+        if demo is not None and demo_rows is not None:
+            # the cloning term on the demonstration rows [that pass the Q-filter]: q = Q(s, a) of the forward that PRECEDED the
+            # critic step, q_pi = Q(s, mu(s)) through the UPDATED critic -- one Adam step apart (demo_loss.py); strict, NaN = out
+            with T.no_grad():
+                m = demo_rows.view(-1).to(device=mu.device, dtype=T.bool)
+                if demo.q_filter:
+                    m = m & (critic_value.view(-1) > q_pi.view(-1))
+            self.last_demo_mask = m
+            d = mu.view(-1) - actions.view(-1)
+            actor_loss = actor_loss + demo.bc_weight * T.sum(m.to(mu.dtype) * d * d) / mu.shape[0]
         for p, g in zip(self._actor_params, T.autograd.grad(actor_loss, self._actor_params)):
             p.grad = g
         if self.grad_sync_actor is not None:

@@ -1,0 +1,141 @@
+// ttdemo.hip -- the demonstration loss of the lone learn(): a behaviour-cloning term on the batch rows that came from the replay
+// side buffer, gated by a Q-filter, inside the launches learn() makes anyway (MI355X, gfx950; include/ttenv.h: tt_demo_loss;
+// DESIGN.md section 25).
+//
+//   k_fwd_small_demo      k_fwd_small<critic>'s launch of the five-launch chain: Q(s, mu(s)) and dQ/da through the UPDATED critic.
+//                         Lane 0 of a row also forms m[b] = demonstration row [and q[b] > q_pi[b]] and the EFFECTIVE derivative
+//                         dq_eff[b] = m ? fmaf(-k, mu[b] - a[b], dQ/da[b]) : dQ/da[b], k = 2 lambda; dq_da keeps the true one.
+//   k_actor_tail_demo     k_actor_tail's grid: the row half with the same term -- the 8-byte hand-over word carries dq_eff --, the
+//                         weight half word for word what it is (PREPEN = a learner with a LossShape).  No wait, flag or atomic added.
+//
+// The actor's row factor (scale dQ/da)(1 - mu^2), scale = -1/B, is linear in dQ/da, and the cloning term's derivative at the
+// pre-activation is (2 lambda / B) m (mu - a)(1 - mu^2): the whole term is the factor of dq_eff.  The separate weight launch needs no
+// kernel of its own: tt_mlp_backward_weights[_shaped] with row_dq_da = dq_eff.  The body is fwd_small_body<true, .., DEMO>
+// (ttlearn_bodies.h); the instantiations of every other translation unit are the ones they were.  A row with m = 0 keeps the bits
+// of dQ/da, so a batch without demonstration rows leaves the bits of the launches these stand in for.
+#include "tthost.h"
+#include "ttlearn_bodies.h"
+
+#include <cmath>
+
+namespace {
+
+using tthost::fail;
+
+__global__ __launch_bounds__(64 * NW) void k_fwd_small_demo(const int n, const float *__restrict__ obs, const float *__restrict__ action,
+                                                            const float *__restrict__ w1e, const float *__restrict__ b1e,
+                                                            const float *__restrict__ g1e, const float *__restrict__ be1e,
+                                                            const Weights W, float *__restrict__ out, const Saved sv,
+                                                            float *__restrict__ dq_da, const DemoIn demo) {
+    // (n .. be1e: the preloaded prefix, as k_fwd_small's)
+    __shared__ __attribute__((aligned(16))) float h1_s[H1S_FLOATS];
+    __shared__ __attribute__((aligned(16))) float z_s[TR * DS];
+    __shared__ __attribute__((aligned(16))) float w1_s[H1 * IN];
+    KernargWarm<64 + (int)sizeof(Weights) + 8 + (int)sizeof(Saved) + 8 + (int)sizeof(DemoIn)> warm;
+    warm.issue();
+    KBEGIN(3);
+    const EarlyW E{w1e, b1e, g1e, be1e};
+    auto hook = [&]() __attribute__((always_inline)) { warm.wait(); };
+    fwd_small_body<true, decltype(hook), true>(n, obs, action, W, out, sv, dq_da, nullptr, h1_s, z_s, w1_s, blockIdx.x * TR, nullptr, false,
+                                               0.f, 0.f, nullptr, 0u, &E, hook, demo);
+    KEND(3);
+}
+
+// k_actor_tail with the demonstration term in the dQ/da the row workgroups hand on; PREPEN: the learner also has a LossShape
+template <bool PREPEN>
+__global__ __launch_bounds__(64 * NW) void k_actor_tail_demo(const int n, const float *__restrict__ obs, const float *__restrict__ mu,
+                                                             const Weights Wc, float *__restrict__ q_out, float *__restrict__ dq_da,
+                                                             const Saved sv, const BwdOut d, const Grads G, const AdamFused A,
+                                                             const RowScale RS, const TailSync ts, const float pre_scale,
+                                                             const float *__restrict__ pre, const DemoIn demo) {
+    __shared__ __attribute__((aligned(16))) float lds[H1S_FLOATS + TR * DS + H1 * IN];
+    const int nb = (n + TR - 1) / TR;
+    if ((int)blockIdx.x < nb) {
+        const long long epoch = *A.step_dev;
+        KBEGIN(3);
+        TT_ACTOR_TAIL_ROWS_DEMO(true, n, obs, mu, Wc, q_out, dq_da, lds, ts, blockIdx.x, epoch, demo);
+        KEND(3);
+        return;
+    }
+    if (threadIdx.x >= 256) return;
+    const long long epoch = *A.step_dev;
+    TT_ACTOR_TAIL_WEIGHTS_SHAPED(PREPEN, (int)blockIdx.x - nb, n, obs, sv, d, G, A, RS, lds, ts, epoch, pre_scale, pre);
+}
+
+// what both entry points refuse of a tt_demo_loss: TT_OK, or TT_EINVAL with "<who>: <reason>"
+int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, DemoIn &out) {
+    if (!dl) return fail(TT_EINVAL, "%s: demo is NULL", who);
+    if (!std::isfinite(dl->k) || dl->k < 0.f) return fail(TT_EINVAL, "%s: demo->k = %g is not a finite number >= 0", who, (double)dl->k);
+    if (!dl->a || !dl->idx || !dl->dq_eff || !dl->code) return fail(TT_EINVAL, "%s: demo->a, idx, dq_eff or code is NULL", who);
+    if (dl->q_filter && !dl->q) return fail(TT_EINVAL, "%s: demo->q is NULL with q_filter set", who);
+    if (!dq_da) return fail(TT_EINVAL, "%s: dq_da is NULL (the true derivative has a buffer of its own)", who);
+    if (dl->dq_eff == dq_da) return fail(TT_EINVAL, "%s: demo->dq_eff is dq_da", who);
+    out = DemoIn{dl->a, dl->idx, dl->q, dl->k, dl->q_filter ? 1 : 0, dl->dq_eff, dl->code};
+    return TT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tt_mlp_forward_save_demo(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
+                             const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, tt_stream_t stream) {
+    const char *const who = "tt_mlp_forward_save_demo";
+    DemoIn din;
+    if (const int rc = refuse_demo(who, demo, dq_da, din)) return rc;
+    if (!critic) return fail(TT_EINVAL, "%s: the actor has no demonstration form (the term is in the critic's pass on (s, mu(s)))", who);
+    if (n < 0) return fail(TT_EINVAL, "%s: n = %d rows, not >= 0", who, n);
+    if (!obs || !out || !action) return fail(TT_EINVAL, "%s: obs, action or out is NULL", who);
+    if (!ok_shape(w, true)) return fail(TT_EINVAL, "%s: the critic's weights are missing or not 23-400-300", who);
+    Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    if (saved && !to_saved(saved, sv)) return fail(TT_EINVAL, "%s: the saved forward lacks an array", who);
+    if (n == 0) return TT_OK;
+    hipLaunchKernelGGL(k_fwd_small_demo, dim3((n + TR - 1) / TR), dim3(64 * NW), 0, stream, n, obs, action, w->w1, w->b1, w->g1, w->be1,
+                       to_weights(w), out, sv, dq_da, din);
+    return hipGetLastError() == hipSuccess ? TT_OK : fail(TT_EHIP, "%s: the launch failed", who);
+}
+
+int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                           const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale, int count,
+                           float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
+                           const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                           const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
+                           const tt_loss_shape *shape, const tt_demo_loss *demo, tt_stream_t stream) {
+    const char *const who = "tt_mlp_actor_tail_demo";
+    DemoIn din;
+    if (const int rc = refuse_demo(who, demo, dq_da, din)) return rc;
+    if (shape) {
+        if (!std::isfinite(shape->huber_delta) || shape->huber_delta < 0.f)
+            return fail(TT_EINVAL, "%s: shape->huber_delta = %g is not a finite number >= 0", who, (double)shape->huber_delta);
+        if (!std::isfinite(shape->pre_scale) || shape->pre_scale < 0.f)
+            return fail(TT_EINVAL, "%s: shape->pre_scale = %g is not a finite number >= 0", who, (double)shape->pre_scale);
+        if (shape->pre_scale > 0.f && !shape->pre)
+            return fail(TT_EINVAL, "%s: shape->pre is NULL with pre_scale = %g > 0", who, (double)shape->pre_scale);
+    }
+    Saved sv;
+    BwdOut o;
+    AdamFused A;
+    if (n <= 0 || n > MAXB) return fail(TT_EINVAL, "%s: n = %d rows, not in [1, %d]", who, n, MAXB);
+    if (!obs || !mu || !q_out) return fail(TT_EINVAL, "%s: obs, mu or q_out is NULL", who);
+    if (!ok_shape(critic, true)) return fail(TT_EINVAL, "%s: the critic's weights are missing or not 23-400-300", who);
+    if (!to_saved(saved, sv)) return fail(TT_EINVAL, "%s: the saved forward lacks an array", who);
+    if (!to_bwd_out(ws, o)) return fail(TT_EINVAL, "%s: the per-row workspace lacks an array", who);
+    if (!ok_shape(grads, false)) return fail(TT_EINVAL, "%s: grads is missing or not 23-400-300", who);
+    if (!to_adam(false, count, params, exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, A))
+        return fail(TT_EINVAL, "%s: the optimizer step lacks a tensor or the step count, or count = %d is not 10", who, count);
+    if (!tail_words) return fail(TT_EINVAL, "%s: tail_words is NULL", who);
+    const int nb = (n + TR - 1) / TR;
+    if (nb > 64) return fail(TT_EINVAL, "%s: %d row workgroups, more than the 64 one wave polls", who, nb);
+    const RowScale rs{dq_da, mu, row_scale};      // (the tail's factors come from the rows' words; dq_da here is never read)
+    const TailSync ts{tail_words, reinterpret_cast<unsigned long long *>(tail_words + 64), nb, gave_up_host};
+    const dim3 grid(nb + WG_ACTOR_WEIGHTS), block(64 * NW);
+    if (shape)
+        hipLaunchKernelGGL(k_actor_tail_demo<true>, grid, block, 0, stream, n, obs, mu, to_weights(critic), q_out, dq_da, sv, o,
+                           to_grads(grads), A, rs, ts, shape->pre_scale, static_cast<const float *>(shape->pre), din);
+    else
+        hipLaunchKernelGGL(k_actor_tail_demo<false>, grid, block, 0, stream, n, obs, mu, to_weights(critic), q_out, dq_da, sv, o,
+                           to_grads(grads), A, rs, ts, 0.f, static_cast<const float *>(nullptr), din);
+    return hipGetLastError() == hipSuccess ? TT_OK : fail(TT_EHIP, "%s: the launch failed", who);
+}
+
+}  // extern "C"

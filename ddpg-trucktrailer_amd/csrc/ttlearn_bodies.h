@@ -275,7 +275,20 @@ __device__ __forceinline__ void split4(const float4 x, uint2 &ph, uint2 &pm) {
 struct EarlyW {
     const float *__restrict__ w1, *__restrict__ b1, *__restrict__ g1, *__restrict__ be1;
 };
-template <bool CRITIC, class Hook = NoHook>
+// DEMO (csrc/ttdemo.hip): the behaviour-cloning term of the actor loss on demonstration rows, folded into the dQ/da the row's lane 0
+// hands on.  a [n]: the batch's stored actions, idx [n][2]: the draw's index buffer (idx[2 b] < 0: row b came from the side buffer),
+// q [n]: Q(s, a) of learn()'s FIRST launch (the critic before this update; read with q_filter only), k = 2 lambda.
+// Out: dq_eff [n] and code [n] (0 a ring row, 1 a demonstration row the filter left out, 2 a demonstration row applied).
+struct DemoIn {
+    const float *a;
+    const int *idx;
+    const float *q;
+    float k;
+    int q_filter;
+    float *dq_eff;
+    int *code;
+};
+template <bool CRITIC, class Hook = NoHook, bool DEMO = false>
 __device__ __forceinline__ void fwd_small_body(const int n, const float *__restrict__ obs,
                                                const float *__restrict__ action, const Weights &W,
                                                float *__restrict__ out, const Saved &sv, float *__restrict__ dq_da,
@@ -285,7 +298,7 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
                                                const bool act_given = false, const float act_row0 = 0.f,
                                                const float act_row1 = 0.f, unsigned long long *dq_words = nullptr,
                                                const unsigned dq_epoch = 0u, const EarlyW *early = nullptr,
-                                               const Hook &loads_issued = Hook()) {
+                                               const Hook &loads_issued = Hook(), const DemoIn &demo = DemoIn{}) {
     // early (optional): fc1 and the layer-1 vectors through pointers that reached the wave in SGPRs (leading kernel arguments) --
     // the same addresses as W's; loads_issued(): called once this phase's loads are out (the kernel's wait for the rest of its arguments)
     const EarlyW E = early ? *early : EarlyW{W.w1, W.b1, W.g1, W.be1};
@@ -582,6 +595,17 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
         const int row = row0 + wave * (TR / NW) + rr;
         avs[rr] = (CRITIC && !z_state && row < n) ? (act_given ? (rr == 0 ? act_row0 : act_row1) : action[row]) : 0.f;
     }
+    float demo_a[TR / NW], demo_q[TR / NW];                // DEMO: requested here too, long before lane 0 of a row needs them
+    int demo_i[TR / NW];
+    if constexpr (DEMO) {
+#pragma unroll
+        for (int rr = 0; rr < TR / NW; ++rr) {
+            const int row = min(row0 + wave * (TR / NW) + rr, n - 1);
+            demo_a[rr] = demo.a[row];
+            demo_i[rr] = demo.idx[2 * row];
+            demo_q[rr] = demo.q_filter ? demo.q[row] : 0.f;
+        }
+    }
     const float b3 = W.b3[0];
 #pragma unroll
     for (int rr = 0; rr < TR / NW; ++rr) {
@@ -649,7 +673,20 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
         if (lane == 0 && row < n) {
             const float v = dot + b3;
             out[row] = CRITIC ? v : tanhf(v);
-            if (CRITIC && dq_da) {
+            if constexpr (DEMO) {
+                // m = a demonstration row [whose stored action the critic BEFORE this update rated above what the UPDATED critic
+                // gives the policy's: q > q_pi, false for a NaN on either side]; the row's d(loss)/d(pre) is linear in dQ/da, so
+                // the cloning term (2 lambda / B) m (mu - a) (1 - mu^2) is dQ/da - k (mu - a) through the factor as it is
+                const float a_b = demo_a[rr], q_b = demo_q[rr];
+                const bool is_demo = demo_i[rr] < 0, m = is_demo && (!demo.q_filter || q_b > v);
+                const float dq_eff = m ? fmaf(-demo.k, av - a_b, dqa) : dqa;
+                dq_da[row] = dqa;                      // (the true derivative: the learn log's statistics keep their meaning)
+                demo.dq_eff[row] = dq_eff;
+                demo.code[row] = m ? 2 : (is_demo ? 1 : 0);
+                if (dq_words)
+                    __hip_atomic_store(dq_words + row, ((unsigned long long)dq_epoch << 32) | (unsigned long long)__float_as_uint(dq_eff),
+                                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            } else if (CRITIC && dq_da) {
                 dq_da[row] = dqa;
                 // k_actor_tail: read by workgroups of the SAME launch on other XCDs.  Value and learn step leave as ONE 8-byte atomic
                 // store (agent scope: coherent by itself), so a reader that finds the step it waits for has the value of that step

@@ -1,6 +1,6 @@
 // ttlearn_sites.h -- device text that several of learn()'s kernels hold word for word, written ONCE: the sampled-row prologue of the
 // first launch (one-step and n-step), the two halves of the actor tail and the front of the rows-pair launch.  The kernels that use
-// it are in csrc/ttlearn.hip, ttpop.hip, ttnstep.hip, ttpop_nstep.hip, tttd3.hip, ttpop_td3.hip and ttshape.hip.
+// it are in csrc/ttlearn.hip, ttpop.hip, ttnstep.hip, ttpop_nstep.hip, tttd3.hip, ttpop_td3.hip, ttshape.hip and ttdemo.hip.
 //
 // These are function-like MACROS, not functions, on purpose.  As __forceinline__ functions (the job indices by value or by
 // reference alike) the prologue and the tail changed the instructions of the kernels they served: csrc/ttpop.hip came out different
@@ -102,15 +102,20 @@
 // lds: the kernel's one LDS array of H1S_FLOATS + TR * DS + H1 * IN floats; lb: the workgroup's number among its agent's row
 // workgroups; epoch: the learn step (the site loads it).  Hand-over order: every wave's row words have left (vmcnt(0)), the
 // workgroup's barrier, then ONE relaxed agent-scope store of the epoch into the workgroup's hint (TailSync, ttlearn_bodies.h).
-#define TT_ACTOR_TAIL_ROWS(n, obs, mu, Wc, q_out, dq_da, lds, ts, lb, epoch)                                                            \
+// DEMO, demo: the demonstration loss's term in the dQ/da a row hands on (csrc/ttdemo.hip; fwd_small_body's DemoIn); the plain form
+// passes fwd_small_body's defaults.
+#define TT_ACTOR_TAIL_ROWS_DEMO(DEMO, n, obs, mu, Wc, q_out, dq_da, lds, ts, lb, epoch, demo)                                           \
     do {                                                                                                                                \
         const Saved none{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};                                                         \
-        fwd_small_body<true>(n, obs, mu, Wc, q_out, none, dq_da, nullptr, lds, (lds) + H1S_FLOATS, (lds) + H1S_FLOATS + TR * DS,        \
-                             (lb) * TR, nullptr, false, 0.f, 0.f, ts.rows, (unsigned)(epoch));                                          \
+        fwd_small_body<true, NoHook, DEMO>(n, obs, mu, Wc, q_out, none, dq_da, nullptr, lds, (lds) + H1S_FLOATS,                        \
+                                           (lds) + H1S_FLOATS + TR * DS, (lb) * TR, nullptr, false, 0.f, 0.f, ts.rows,                  \
+                                           (unsigned)(epoch), nullptr, NoHook(), demo);                                                 \
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); /* every wave: its rows' words have been sent */                               \
         __syncthreads();                                                                                                                \
         if (threadIdx.x == 0) __hip_atomic_store(ts.hints + (lb), (int)(epoch), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);            \
     } while (0)
+#define TT_ACTOR_TAIL_ROWS(n, obs, mu, Wc, q_out, dq_da, lds, ts, lb, epoch)                                                            \
+    TT_ACTOR_TAIL_ROWS_DEMO(false, n, obs, mu, Wc, q_out, dq_da, lds, ts, lb, epoch, DemoIn{})
 
 // ---- the actor tail, weight half: a weight-gradient workgroup (its first 256 threads) carves the row kernel's LDS ----
 // blk: the workgroup's number among its agent's WG_ACTOR_WEIGHTS.  PREPEN, pre_scale, pre: the loss shape's penalty term

@@ -180,13 +180,16 @@ class LearnLog:
 
 
 class FusedLearner:
-    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None):
+    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None):
         """fc2_images (None = on unless TT_LEARN_F32=1): the 400 x 300 products of learn() on the f16 MFMA from pre-split
         images of the four networks' fc2 (include/ttenv.h: tt_mlp_weights.fc2_img) that the optimizer launches keep current;
         off = every product on the exact-f32 MFMA straight from the weights.
         loss_shape (None = the MSE critic loss and the plain actor loss, every launch the one it was): a loss_shape.LossShape --
         the rows launch, the actor's weight launch and the tail then go through the shaped entry points (include/ttenv.h:
-        tt_loss_shape), the same number of launches.  Not with data-parallel ranks."""
+        tt_loss_shape), the same number of launches.  Not with data-parallel ranks.
+        demo_loss (None = no row of the batch is treated as a demonstration): a demo_loss.DemoLoss -- learn_batch then takes the
+        draw's index buffer (demo_index=) and the actor's step through the demonstration entry points (include/ttenv.h:
+        tt_demo_loss), the same number of launches.  Composes with loss_shape.  Not with data-parallel ranks."""
         import os
         assert fused.supported(agent.actor) and fused.supported(agent.critic)
         self.agent, self.B = agent, int(batch_size)
@@ -229,6 +232,9 @@ class FusedLearner:
         self.loss_shape, self.pre, self._shape = None, None, None
         if loss_shape is not None:
             self.set_loss_shape(loss_shape)
+        self.demo_loss, self.dq_eff, self.code, self._demo_actions = None, None, None, None
+        if demo_loss is not None:
+            self.set_demo_loss(demo_loss)
 
     def set_loss_shape(self, loss_shape):
         """Turn a LossShape on (before anything is captured: the constants travel by value in the launches' arguments).  The learner
@@ -244,6 +250,40 @@ class FusedLearner:
     def _refuse_ranks_with_loss_shape(self):
         if self.loss_shape is not None:
             raise ValueError("loss_shape with data-parallel ranks (or the p2p exchange) is not supported")
+        if self.demo_loss is not None:
+            raise ValueError("demo_loss with data-parallel ranks (or the p2p exchange) is not supported")
+
+    def set_demo_loss(self, demo_loss):
+        """Turn a DemoLoss on (before anything is captured: the constants travel by value in the launches' arguments).  The learner
+        owns dq_eff [B], the derivative the actor's rows are scaled by (dQ/da with the cloning term folded in; dq_da keeps the true
+        one), and code [B] int32: 0 a ring row, 1 a demonstration row the filter left out, 2 a demonstration row applied."""
+        from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
+        check_demo_loss(demo_loss, td3=getattr(self.agent, "td3", None),
+                        data_parallel=self.grad_sync_critic is not None or self.p2p is not None)
+        self.demo_loss = demo_loss
+        self.dq_eff = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
+        self.code = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+
+    def _demo_struct(self, actions, demo_index):
+        """tt_demo_loss of one update: the batch's stored actions, the draw's index buffer, q of the first launch."""
+        dl = self.demo_loss
+        return L.TTDemoLoss(a=actions.data_ptr(), idx=demo_index.data_ptr(), q=self.q.data_ptr(), k=dl.k(), q_filter=int(dl.q_filter),
+                            dq_eff=self.dq_eff.data_ptr(), code=self.code.data_ptr())
+
+    def demo_stats(self):
+        """Of the last update (synchronises): {"demo_rows": rows that came from the side buffer, "applied": those the filter let
+        through, "bc_loss": lambda (1/B) sum over the applied rows of (mu - a)^2, formed on the host in f64 from code, mu and the
+        batch's stored actions}."""
+        if self.demo_loss is None:
+            raise ValueError("demo_loss is off (FusedLearner(demo_loss=...))")
+        if self._demo_actions is None:
+            return {"demo_rows": 0, "applied": 0, "bc_loss": 0.0}
+        torch.cuda.synchronize(self.dev)
+        code = self.code.cpu()
+        on = code == 2
+        d = (self.mu.double().cpu() - self._demo_actions.double().cpu().view(-1))[on]
+        return {"demo_rows": int((code > 0).sum().item()), "applied": int(on.sum().item()),
+                "bc_loss": float(self.demo_loss.bc_weight * (d * d).sum().item() / self.B)}
 
     def _nets(self):
         """The networks this learner keeps weight structs and fc2 images of (a subclass with more networks overrides this)."""
@@ -306,8 +346,12 @@ class FusedLearner:
         if self.use_images and not torch.cuda.is_current_stream_capturing():
             self.refresh_images()          # (a capture holds launches only: its owner looks before it replays)
 
-    def _fwd(self, net, obs, action, out, saved=None, dq_da=None):
+    def _fwd(self, net, obs, action, out, saved=None, dq_da=None, demo=None):
         self._fresh()
+        if demo is not None:       # the critic on (s, mu(s)) with the demonstration term in dq_eff (csrc/ttdemo.hip)
+            L.check(self.lib.tt_mlp_forward_save_demo(self.B, 1, L.ptr(obs), L.ptr(action), C.byref(self.w(net)), L.ptr(out),
+                                                      C.byref(saved) if saved else None, L.ptr(dq_da), C.byref(demo), self._stream()))
+            return
         L.check(self.lib.tt_mlp_forward_save(self.B, 1 if action is not None else 0, L.ptr(obs), L.ptr(action),
                                              C.byref(self.w(net)), L.ptr(out), C.byref(saved) if saved else None,
                                              L.ptr(dq_da), self._stream()))
@@ -536,10 +580,11 @@ class FusedLearner:
                                                  C.byref(st.images) if (adam and st.images is not None) else None,
                                                  L.ptr(self.bias_corr), self._stream()))
 
-    def phase_b(self, states, separate_adam):
+    def phase_b(self, states, separate_adam, demo=None):
         """[critic Adam/soft update when not already applied,] then the actor step through the UPDATED critic
         (DDPG_agent.py:100-104): Q(s, mu(s)) with dQ/da (a critic forward), and the actor's weight gradients from its unit
-        per-row backward scaled by -(1/B) dQ/da (1 - mu^2) per row (+ its Adam unless separate_adam)."""
+        per-row backward scaled by -(1/B) dQ/da (1 - mu^2) per row (+ its Adam unless separate_adam).
+        demo: a tt_demo_loss (_demo_struct) -- the same launches through the demonstration entry points, the rows scaled by dq_eff."""
         ag, B = self.agent, self.B
         if separate_adam:
             self._adam(self.critic, self.hyp_critic, ag.tau)
@@ -547,6 +592,16 @@ class FusedLearner:
             self._fresh()
             st = self.actor
             lr, b1, b2, eps, wd = self.hyp_actor
+            if demo is not None:
+                L.check(self.lib.tt_mlp_actor_tail_demo(B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi),
+                                                        L.ptr(self.dq_da), C.byref(st.saved), C.byref(self.ws_actor), C.byref(st.gstruct),
+                                                        -1.0 / B, st.count, st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1,
+                                                        b2, eps, wd, ag.tau, C.byref(st.images) if st.images is not None else None,
+                                                        L.ptr(self.bias_corr), L.ptr(self.tail_words),
+                                                        C.c_void_p(self.tail_gave_up_host.data_ptr()),
+                                                        C.byref(self._shape) if self.loss_shape is not None else None, C.byref(demo),
+                                                        self._stream()))
+                return
             if self.loss_shape is not None:
                 L.check(self.lib.tt_mlp_actor_tail_shaped(B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi),
                                                           L.ptr(self.dq_da), C.byref(st.saved), C.byref(self.ws_actor), C.byref(st.gstruct),
@@ -561,19 +616,34 @@ class FusedLearner:
                                                C.byref(st.images) if st.images is not None else None, L.ptr(self.bias_corr),
                                                L.ptr(self.tail_words), C.c_void_p(self.tail_gave_up_host.data_ptr()), self._stream()))
             return
-        self._fwd(ag.critic, states, self.mu, self.q_pi, dq_da=self.dq_da)
+        self._fwd(ag.critic, states, self.mu, self.q_pi, dq_da=self.dq_da, demo=demo)
         self._weights(self.actor, self.hyp_actor, ag.tau, states, None, self.ws_actor, adam=not separate_adam,
-                      row=(self.dq_da, self.mu, -1.0 / B))
+                      row=(self.dq_eff if demo is not None else self.dq_da, self.mu, -1.0 / B))
 
     def phase_c(self):
         self._adam(self.actor, self.hyp_actor, self.agent.tau)
 
-    def learn_batch(self, states, actions, rewards, states_, done_u8, window_dev=None, sample=None, image=None, n_step=1):
+    def learn_batch(self, states, actions, rewards, states_, done_u8, window_dev=None, sample=None, image=None, n_step=1,
+                    demo_index=None):
         """states, states_ [B,23] f32; actions [B,1] f32; rewards [B] f32; done_u8 [B] uint8 -- all contiguous.
         window_dev: device int64 advanced by the critic's backward launch (a pipelined loop's sampling window).
         sample: see phase_a (the five tensors are then the draw's batch buffers, filled by learn()'s first launch).
-        n_step: see phase_a (n-step returns; 1 = the one-step learn(), launch for launch)."""
+        n_step: see phase_a (n-step returns; 1 = the one-step learn(), launch for launch).
+        demo_index (with demo_loss; else it must be None): the draw's [B, 2] int32 index buffer of this batch (TrajectoryRing: the
+        sixth of its batch buffers) -- row b is a demonstration row where demo_index[b, 0] < 0."""
         assert states.shape[0] == self.B and done_u8.dtype == torch.uint8
+        demo = None
+        if self.demo_loss is not None:
+            from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
+            if demo_index is None:
+                raise ValueError("demo_loss is set: learn_batch needs demo_index, the draw's [B, 2] int32 index buffer")
+            check_demo_loss(self.demo_loss, n_step=n_step)
+            assert demo_index.dtype == torch.int32 and tuple(demo_index.shape) == (self.B, 2) and demo_index.is_contiguous()
+            assert actions.is_contiguous() and actions.numel() == self.B
+            demo = self._demo_struct(actions, demo_index)
+            self._demo_actions = actions
+        elif demo_index is not None:
+            raise ValueError("demo_index without demo_loss (FusedLearner(demo_loss=...))")
         dp = self.grad_sync_critic is not None
         if dp:
             self._refuse_ranks_with_learn_log()
@@ -582,7 +652,7 @@ class FusedLearner:
         self.phase_a(states, actions, rewards, states_, done_u8, fuse_adam=not dp, window_dev=window_dev, sample=sample, image=image, n_step=n_step)
         if dp:
             self.grad_sync_critic()
-        self.phase_b(states, separate_adam=dp)
+        self.phase_b(states, separate_adam=dp, demo=demo)
         if dp:
             self.grad_sync_actor()
             self.phase_c()
@@ -592,12 +662,14 @@ class FusedLearner:
     # ---- checkpoint ---------------------------------------------------------------------------------------------
     def state_dict(self):
         """Adam moments of both networks (flat, tt_mlp_weights order), the learn-step count and the loss shape when one is set.
-        (The learn log is not in it.)"""
+        and the demonstration loss likewise.  (The learn log is not in it.)"""
         sd = {"step": int(self.step_dev.item()),
               "actor": {"m": self.actor.m.cpu(), "v": self.actor.v.cpu()},
               "critic": {"m": self.critic.m.cpu(), "v": self.critic.v.cpu()}}
         if self.loss_shape is not None:
             sd["loss_shape"] = list(self.loss_shape.as_tuple())
+        if self.demo_loss is not None:
+            sd["demo_loss"] = list(self.demo_loss.as_tuple())
         return sd
 
     def load_state_dict(self, sd):
@@ -605,6 +677,10 @@ class FusedLearner:
         mine = self.loss_shape.as_tuple() if self.loss_shape is not None else None
         if have != mine:
             raise ValueError(f"the checkpoint was written with loss_shape = {have}, this learner has loss_shape = {mine}")
+        have = tuple(sd["demo_loss"]) if sd.get("demo_loss") is not None else None
+        mine = self.demo_loss.as_tuple() if self.demo_loss is not None else None
+        if have != mine:
+            raise ValueError(f"the checkpoint was written with demo_loss = {have}, this learner has demo_loss = {mine}")
         for name in ("actor", "critic"):
             st = getattr(self, name)
             st.m.copy_(sd[name]["m"]); st.v.copy_(sd[name]["v"])

@@ -72,7 +72,7 @@ class DDPGRollout(VectorStepper):
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -102,8 +102,24 @@ class DDPGRollout(VectorStepper):
         (pipeline=None resolves to False); td3.check_td3 names what is refused.
         loss_shape: None, or a loss_shape.LossShape: a Huber critic loss and / or a pre-activation penalty on the
         actor, inside the launches learn() makes anyway -- in the serial and the pipelined order, with n_step, learn_log and graphs.
-        loss_shape.check_loss_shape names what is refused (td3, data-parallel ranks, the p2p exchange, TT_FORCE_DP)."""
+        loss_shape.check_loss_shape names what is refused (td3, data-parallel ranks, the p2p exchange, TT_FORCE_DP).
+        demo_loss: None, or a demo_loss.DemoLoss: a behaviour-cloning term, gated by a Q-filter, on the batch
+        rows that came from the ring's side buffer (TrajectoryRing.load_side, expert.load_into_ring) -- every draw form hands the
+        draw's index buffer on to learn(); the same launches, in both orders, with loss_shape, learn_log and graphs.  A ring with no
+        side tuples is allowed (no row is a demonstration).  demo_loss.check_demo_loss names what is refused (td3, n_step > 1,
+        data-parallel ranks, the p2p exchange, TT_FORCE_DP)."""
         self.n_step = check_n_step(n_step)
+        self.demo_loss = None
+        if demo_loss is not None:
+            from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
+            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
+            self.demo_loss = check_demo_loss(demo_loss, td3=td3, data_parallel=ranks or dp_exchange == "p2p",
+                                             force_dp=os.environ.get("TT_FORCE_DP") == "1", n_step=self.n_step)
+            if agent is not None and getattr(agent, "demo_loss", None) != self.demo_loss:
+                raise ValueError(f"demo_loss: the agent passed in was built with demo_loss = {getattr(agent, 'demo_loss', None)!r}, "
+                                 f"the loop with {self.demo_loss!r}")
+        elif agent is not None and getattr(agent, "demo_loss", None) is not None:
+            raise ValueError("demo_loss: the agent passed in was built with a demo_loss, the loop without")
         self.loss_shape = None
         if loss_shape is not None:
             from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
@@ -142,6 +158,7 @@ class DDPGRollout(VectorStepper):
                          td3=self.td3)
         self.batch_size = batch_size
         self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
+        self.agent.demo_loss = self.demo_loss
         self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
         self.dp_exchange = dp_exchange or os.environ.get("TT_DP_EXCHANGE", "collective")
         assert self.dp_exchange in ("collective", "p2p"), self.dp_exchange
@@ -163,7 +180,7 @@ class DDPGRollout(VectorStepper):
                 from ddpg_trucktrailer_amd.td3 import TD3Learner
                 self.learner = TD3Learner(self.agent, batch_size, self.ring, self.seed)
             elif self.td3 is None:
-                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape)
+                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape, demo_loss=self.demo_loss)
             self.agent.fused_learner = self.learner
             if self.dp and self.dp_exchange == "p2p":
                 self.learner.enable_p2p()
@@ -244,6 +261,10 @@ class DDPGRollout(VectorStepper):
             return self.ring.sample_fused(self.batch_size, seed=key, done_as_bool=self.learner is None, **ns)
         return self.ring.sample(self.batch_size, **ns)
 
+    def _demo_rows(self, index):
+        """The torch path's demo_rows of a draw whose index the ring just left ([B, 2]: a side row has index[b, 0] < 0)."""
+        return {} if self.demo_loss is None else dict(demo_rows=index[:, 0] < 0)
+
     def _sample_key(self, u):
         return (self.seed + u * _SEED_STRIDE) & (2 ** 64 - 1)
 
@@ -260,9 +281,10 @@ class DDPGRollout(VectorStepper):
             # the TD3 launches make the draw of update u themselves; the delay is counted inside the vector step
             self.learner.learn_batch(u=u, full=(u + 1) % self.td3.policy_delay == 0)
             return
+        index = None           # (demo_loss) the draw's index buffer: every draw form below writes it with the batch
         if presampled:         # the step's opening launch already drew this batch into the ring's buffers
             B, draws = self.batch_size, self._draws_per_opening()
-            s, a, r, s2, d = (x[u * B:(u + 1) * B] for x in self.ring._batch_bufs(B * draws)[:5])
+            s, a, r, s2, d, index = (x[u * B:(u + 1) * B] for x in self.ring._batch_bufs(B * draws))
         elif self.learner is not None and self.device.type == "cuda":
             # the fused learner's first launch makes the draw itself (tt_mlp_forward_multi_sampled): the same draw as
             # _sample(u), one launch less per update
@@ -271,18 +293,23 @@ class DDPGRollout(VectorStepper):
                                                reserve=_PIPE_RESERVE, lag=_PIPE_LAG, wait_for_steps=wait_for_steps)
             else:
                 sample = self.ring.sample_args(self.batch_size, seed=self._sample_key(u))
-            s, a, r, s2, d = self.ring._batch_bufs(self.batch_size)[:5]
+            s, a, r, s2, d, index = self.ring._batch_bufs(self.batch_size)
+        elif self.demo_loss is not None and self.device.type != "cuda":
+            s, a, r, s2, d, index = self.ring.sample(self.batch_size, return_index=True)
         else:
             s, a, r, s2, d = self._sample(u)
+            if self.demo_loss is not None:
+                index = self.ring._bufs[5]                  # (sample_fused's)
         if self.learner is not None:
             # (pipelined order) the last update of a vector step moves the sampling window on
             last = self.pipeline and u == self.updates_per_step - 1
             self.learner.learn_batch(s, a, r, s2, d, window_dev=self.k_pipe_dev if last else None, sample=sample,
-                                     image=self._image_job() if with_image else None, n_step=self.n_step)   # raw uint8 done flags
+                                     image=self._image_job() if with_image else None, n_step=self.n_step,   # raw uint8 done flags
+                                     demo_index=index if self.demo_loss is not None else None)
         elif self.n_step > 1:
             self.agent.learn_batch(s, a, r, s2, d, discount=float(self.agent.gamma) ** self.n_step)
         else:
-            self.agent.learn_batch(s, a, r, s2, d)
+            self.agent.learn_batch(s, a, r, s2, d, **self._demo_rows(index))
 
     def _draws_per_opening(self):
         """Batches the opening launch of a pipelined step draws: all of the step's updates' (tt_sample_args.draws) -- each the
@@ -663,7 +690,15 @@ class DDPGRollout(VectorStepper):
             sd["td3"] = list(self.td3.as_tuple())
         if self.loss_shape is not None:
             sd["loss_shape"] = list(self.loss_shape.as_tuple())
+        if self.demo_loss is not None:
+            sd["demo_loss"] = list(self.demo_loss.as_tuple())
         return sd
+
+    def demo_stats(self):
+        """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}.  Synchronises."""
+        if self.learner is None or self.demo_loss is None:
+            raise ValueError("demo_loss is off or the learner is the torch path (DDPGRollout(demo_loss=...))")
+        return self.learner.demo_stats()
 
     def drain_learn_log(self):
         """The learn log's records since the last drain: a dict of numpy columns and "dropped" (FusedLearner.drain_learn_log)."""
@@ -683,6 +718,10 @@ class DDPGRollout(VectorStepper):
         mine = self.loss_shape.as_tuple() if self.loss_shape is not None else None
         if have != mine:
             raise ValueError(f"the checkpoint was written with loss_shape = {have}, this loop has loss_shape = {mine}")
+        have = tuple(sd["demo_loss"]) if sd.get("demo_loss") is not None else None
+        mine = self.demo_loss.as_tuple() if self.demo_loss is not None else None
+        if have != mine:
+            raise ValueError(f"the checkpoint was written with demo_loss = {have}, this loop has demo_loss = {mine}")
         self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])

@@ -918,6 +918,47 @@ int tt_mlp_actor_tail_shaped(int n, const float *obs, const float *mu, const tt_
                              const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
                              const tt_loss_shape *shape, tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Demonstration loss of the lone learn() (csrc/ttdemo.hip): a behaviour-cloning term on the batch rows that came from the replay
+ * side buffer, gated by a Q-filter (Nair et al. 2018), inside the launches learn() makes anyway.  For a batch of B rows the actor
+ * loss is
+ *     -mean_b Q(s_b, mu(s_b)) + lambda (1/B) sum_b m_b (mu_b - a_b)^2
+ * a_b = the row's stored action; demo_b = idx[2 b] < 0, the mark the replay draw leaves for a side-buffer row (tt_sample_args.idx_out);
+ * m_b = demo_b, and with q_filter also q_b > q_pi_b (strict; a NaN on either side leaves m_b = 0).
+ * THE TWO SIDES OF THE FILTER ARE ONE CRITIC ADAM STEP APART:
+ *   q_b    = Q(s_b, a_b) as learn()'s FIRST launch computed it, with the critic BEFORE this update -- the q the TD error uses;
+ *   q_pi_b = Q(s_b, mu(s_b)) through the UPDATED critic -- the q_out of these launches, the number the actor loss is built from.
+ * Both numbers exist anyway; a second critic forward on (s, a) would lengthen the launch the learn chain waits on longest.
+ * The actor's row factor row_scale dQ/da (1 - mu^2), row_scale = -1/B, is linear in dQ/da, so the whole term is an EFFECTIVE
+ *     dq_eff[b] = m_b ? fmaf(-k, mu_b - a_b, dQ/da_b) : dQ/da_b            k = (float)(2 lambda), formed in f64 by the caller
+ * (a row with m_b = 0 keeps the bits of dQ/da_b).  Lane 0 of a row of the critic's pass on (s, mu(s)) writes the TRUE derivative to
+ * dq_da[b], dq_eff[b], and code[b] = 0 (a ring row), 1 (a demonstration row the filter left out) or 2 (a demonstration row applied).
+ *   tt_mlp_forward_save_demo   tt_mlp_forward_save(critic on (s, mu(s)), dq_da) of the five-launch chain; the actor's weight launch
+ *                              that follows is tt_mlp_backward_weights[_shaped] with row_dq_da = demo->dq_eff.
+ *   tt_mlp_actor_tail_demo     tt_mlp_actor_tail_shaped: the same grid, dispatch order and hand-over (the 8-byte word of a row carries
+ *                              dq_eff; no wait, flag or atomic added).  shape may be NULL: then tt_mlp_actor_tail.
+ * With no demonstration row in the batch both leave the bits of the entry points they stand in for.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL demo; k negative or not finite; a, idx, dq_eff or
+ * code NULL; q NULL with q_filter; dq_eff equal to dq_da; no dq_da; critic = 0 in tt_mlp_forward_save_demo; and whatever the entry
+ * point it stands in for refuses. */
+typedef struct tt_demo_loss {
+    const float *a;       /* [n] the batch's stored actions */
+    const int32_t *idx;   /* [n][2] the draw's index buffer: idx[2 b] < 0 = a side-buffer row */
+    const float *q;       /* [n] Q(s, a) with the critic before this update; read with q_filter only */
+    float k;              /* 2 lambda, >= 0 */
+    int32_t q_filter;     /* 0 = every demonstration row is applied */
+    float *dq_eff;        /* [n] out */
+    int32_t *code;        /* [n] out: 0, 1 or 2 */
+} tt_demo_loss;
+int tt_mlp_forward_save_demo(int n, int critic /* must be 1 */, const float *obs, const float *action, const tt_mlp_weights *w,
+                             float *out, const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, tt_stream_t stream);
+int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                           const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale, int count,
+                           float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
+                           const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                           const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
+                           const tt_loss_shape *shape /* may be NULL */, const tt_demo_loss *demo, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -14,11 +14,15 @@ lone DELAY is written --td3=DELAY.  updates_per_step must be a multiple of DELAY
 --huber D / --pre-penalty C: the loss shape (DDPGRollout(loss_shape=LossShape(D, C))): a Huber critic loss
 with delta D (torch's definition: half the MSE gradient inside the zone) and / or the penalty C mean(pre^2) on the actor head's
 pre-activation.  Not with --td3.
+--demos FILE.npz --bc-weight L [--no-q-filter]: the demonstration loss (DDPGRollout(demo_loss=DemoLoss(L, q_filter)); DESIGN.md section
+25): FILE holds obs, act, rew, obs2, done (expert.save_transitions_npz) and goes into the ring's side buffer; the batch rows drawn
+from it get the behaviour-cloning term L (mu - a)^2, by default only where Q(s, a) > Q(s, mu(s)).  Each line adds the demonstration
+rows of the block's last update, how many the filter let through and the term's value.  Not with --td3 or --n-step > 1.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
 Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
-       [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+       [--demos FILE.npz --bc-weight L [--no-q-filter]] [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -49,6 +53,24 @@ if "--pre-penalty" in sys.argv[1:]:
     at = sys.argv.index("--pre-penalty")
     pre_penalty = float(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+demos, bc_weight, q_filter = None, None, True
+if "--demos" in sys.argv[1:]:
+    at = sys.argv.index("--demos")
+    demos = sys.argv[at + 1]
+    del sys.argv[at:at + 2]
+if "--bc-weight" in sys.argv[1:]:
+    at = sys.argv.index("--bc-weight")
+    bc_weight = float(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
+if "--no-q-filter" in sys.argv[1:]:
+    sys.argv.remove("--no-q-filter")
+    q_filter = False
+if (demos is None) != (bc_weight is None):
+    sys.exit("--demos FILE.npz and --bc-weight L go together")
+demo_loss = None
+if demos is not None:
+    from ddpg_trucktrailer_amd.demo_loss import DemoLoss
+    demo_loss = DemoLoss(bc_weight, q_filter)
 eval_every, eval_lanes = None, 256
 if "--eval-every" in sys.argv[1:]:
     at = sys.argv.index("--eval-every")
@@ -83,10 +105,15 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape)
+                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss)
+if demos is not None:
+    from ddpg_trucktrailer_amd.expert import load_transitions_npz
+    d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
+    loop.ring.load_side(d_obs, d_act[:, 0], d_rew, d_obs2, d_done)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else "") +
-      (f", {loss_shape}" if loss_shape is not None else ""), flush=True)
+      (f", {loss_shape}" if loss_shape is not None else "") +
+      (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else ""), flush=True)
 
 
 def learn_line(rec):
@@ -97,6 +124,10 @@ def learn_line(rec):
     return (f"  update {int(rec['step'][-1])}: critic loss {rec['critic_loss'][-1]:.4g}  actor loss {rec['actor_loss'][-1]:.4g}  "
             f"Q mean {rec['q_mean'][-1]:.4g}  |TD| mean {rec['td_abs_mean'][-1]:.4g}  |grad| critic {rec['grad_norm_critic'][-1]:.4g} "
             f"actor {rec['grad_norm_actor'][-1]:.4g}  non-finite {bad}" + (f"  ({rec['dropped']} records overwritten)" if rec["dropped"] else ""))
+
+
+def demo_line(st):
+    return f"  demonstrations {st['demo_rows']} rows, {st['applied']} applied, bc loss {st['bc_loss']:.4g}"
 
 
 tracker = BestModelTracker()
@@ -125,7 +156,8 @@ while s < total:
           f"mean length {r['len'].double().sum().item() / e:6.1f}  mean return {r['ret'].sum().item() / e:9.1f}  "
           f"successes {int(r['success'].sum().item()):6d} ({100 * r['success'].double().sum().item() / e:4.1f} %)  "
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
-          f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}  "
+          f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}"
+          f"{demo_line(loop.demo_stats()) if demo_loss is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
     if evaluator is not None and blocks % eval_every == 0:
