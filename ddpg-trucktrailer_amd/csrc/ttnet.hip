@@ -101,6 +101,9 @@ __global__ __launch_bounds__(256, 1) void k_mlp_forward_v2(const int n, const fl
             for (int ks = 0; ks < INP / 4; ++ks) acc1[t] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[ks], b[ks], acc1[t], 0, 0, 0);
         }
     }
+    // per row: -0 while both LayerNorms' 1/sigma (critic: and the action) are finite, NaN otherwise; added to the head value below,
+    // because fmaxf(NaN, 0) = 0 would turn a row of NaN pre-activations into zeros and a finite output (csrc/ttnet_split.hip, `poison`)
+    float poison[4];
     {
         float s[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -117,7 +120,7 @@ __global__ __launch_bounds__(256, 1) void k_mlp_forward_v2(const int n, const fl
 #pragma unroll
             for (int r = 0; r < 4; ++r) { const float d = acc1[t][r] - mean[r]; ss[r] = fmaf(d, d, ss[r]); }
 #pragma unroll
-        for (int r = 0; r < 4; ++r) rstd[r] = rsqrtf(row_sum16(ss[r]) * (1.f / H1) + 1e-5f);
+        for (int r = 0; r < 4; ++r) { rstd[r] = rsqrtf(row_sum16(ss[r]) * (1.f / H1) + 1e-5f); poison[r] = rstd[r] * -0.f; }
 #pragma unroll
         for (int t = 0; t < NT1; ++t) {
             const int col = t * 16 + l15;
@@ -223,7 +226,9 @@ __global__ __launch_bounds__(256, 1) void k_mlp_forward_v2(const int n, const fl
     const float b3 = W.b3[0];
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-        const float v = row_sum16(dot[r]) + b3;
+        float p = rstd[r] * poison[r];
+        if (CRITIC) p = fmaf(fabsf(av[r]), -0.f, p);
+        const float v = row_sum16(dot[r]) + b3 + p;
         const int row = wrow0 + l4 * 4 + r;
         if (l15 == 0 && row < n) finish_row<CRITIC>(row, v, out, act);
     }

@@ -50,11 +50,14 @@ __device__ __forceinline__ const float *resolve_obs(const ActArgs &act, const fl
 
 using ttrng::philox4x32;
 
+// clip(a, -1, 1) as torch.clamp does it: a NaN stays a NaN (fminf(fmaxf(NaN, -1), 1) is -1: full lock).  One select per row.
+__device__ __forceinline__ float clip_unit(const float a) { return a != a ? a : fminf(fmaxf(a, -1.f), 1.f); }
+
 // The tail of one row once the head's pre-activation v is known.  Critic: out[row] = v.  Actor: mu = tanh(v)
 // (networks.py:145) and, when act.ou is set, DDPG_agent.choose_action + trainv2.py:516: OU noise (noise.py:13-17:
 // x <- x + theta*(0 - x)*dt + sigma*sqrt(dt)*N(0,1), restarted at 0 for an env whose episode just ended,
 // trainv2.py:492; N(0,1) from Philox + Box-Muller), stored action mu + x (unclipped, trainv2.py:525), env action
-// clip(a,-1,1)*high.
+// clip(a,-1,1)*high (clip_unit: NaN stays NaN).
 template <bool CRITIC>
 __device__ __forceinline__ void finish_row(const int row, const float v, float *__restrict__ out, const ActArgs &act) {
     if (CRITIC) {
@@ -84,7 +87,7 @@ __device__ __forceinline__ void finish_row(const int row, const float v, float *
         act.ou[row] = x;
         const float a = mu + x;
         act_raw[row] = a;
-        act.act_scaled[row] = fminf(fmaxf(a, -1.f), 1.f) * act.high;
+        act.act_scaled[row] = clip_unit(a) * act.high;
     }
 }
 
@@ -109,7 +112,7 @@ __device__ __forceinline__ void finish_row_noise(const int row, const float v, f
     act.ou[row] = x_new;
     const float a = mu + x_new;
     act_raw[row] = a;
-    act.act_scaled[row] = fminf(fmaxf(a, -1.f), 1.f) * act.high;
+    act.act_scaled[row] = clip_unit(a) * act.high;
 }
 
 

@@ -11,8 +11,11 @@
 // to within ~3 of its own rounding errors, at 3/16 of the f32 MFMA's cycles (the round-1 kernel used three bf16 pieces
 // and six MFMAs per product block).  f16 has 5 exponent bits, so both operands are scaled by powers of two (exact) to
 // keep their `m` pieces normal: activations by 2^4, weights by 2^6; the accumulator is scaled back by 2^-10 (exact)
-// where the bias is added.  Ranges: |activation| < 4094, |weight| < 1023 -- beyond them a piece becomes inf and the row's
-// output NaN (loud, not silently wrong); pieces below the normal range carry an absolute error <= 2^-25 / scale.
+// where the bias is added.  Ranges: |activation| < 4094, |weight| < 1023 (a piece becomes inf from 16 |x| >= 65520 and
+// 64 |w| >= 65520: 4095 and 1023.75) -- beyond them a piece becomes inf and the row's output NaN (loud, not silently wrong:
+// the `poison` term of the epilogue; a weight beyond the range does that to EVERY row); a NaN or inf observation or action
+// likewise gives a NaN row, as in the torch modules, and leaves every other row's bits alone (tests/test_gpu_policy_edges.py).
+// Pieces below the normal range carry an absolute error <= 2^-25 / scale.
 //
 // Orientation: everything is computed TRANSPOSED (neurons on the MFMA's M axis, envs on N), with
 // v_mfma_f32_32x32x16_f16.  Its 32x32 result has the env on the lane (lane & 31) and 16 neurons in the lane's
@@ -613,7 +616,13 @@ __global__ __launch_bounds__(256, 1) void k_mlp_split(const int n, const int til
             }
         }
         const float dot = dotp[0] + dotp[1];
-        const float v = dot + __shfl_xor(dot, 32) + lds4(pv1 - 4 * h + VEC_FLOATS).x;
+        // A row with a NaN or inf pre-activation in either layer has a NaN 1/sigma there, but fmaxf(NaN, 0) = 0 would hand on zeros
+        // and the row would end as the finite tanh(b3) / b3.  The row's two 1/sigma (critic: and its action) go into the head value
+        // through a term that is exactly -0 for finite inputs (v + -0 = v for every v, -0 included) and NaN otherwise: one
+        // multiply-add per ROW, and the torch modules' result (F.relu propagates NaN).
+        float poison = rstdp[0] * (rstd2 * -0.f);
+        if (CRITIC) poison = fmaf(fabsf(av), -0.f, poison);
+        const float v = dot + __shfl_xor(dot, 32) + lds4(pv1 - 4 * h + VEC_FLOATS).x + poison;
         if (h == 0 && row < n) {
             if (with_noise) finish_row_noise(row, v, out, act, ou_next, araw);
             else finish_row<CRITIC>(row, v, out, act);

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """GPU: the split-f16 forward (csrc/ttnet_split.hip) against the exact-f32 kernel, torch and torch-in-f64, its time, and
-the corner cases of the two-piece f16 split (tiny weights/activations whose `m` piece is subnormal, large ones near the
-stated range)."""
+one corner case of the two-piece f16 split: tiny weights whose `m` piece is subnormal (x1e-3), beside trained sizes (x20).
+Operands near the stated range (|activation| < 4094, |weight| < 1023) are not exercised here: tests/test_gpu_policy_edges.py
+does that."""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
