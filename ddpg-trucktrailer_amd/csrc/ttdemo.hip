@@ -11,16 +11,11 @@
 // The actor's row factor (scale dQ/da)(1 - mu^2), scale = -1/B, is linear in dQ/da, and the cloning term's derivative at the
 // pre-activation is (2 lambda / B) m (mu - a)(1 - mu^2): the whole term is the factor of dq_eff.  The separate weight launch needs no
 // kernel of its own: tt_mlp_backward_weights[_shaped] with row_dq_da = dq_eff.  The body is fwd_small_body<true, .., DEMO>
-// (ttlearn_bodies.h); the instantiations of every other translation unit are the ones they were.  A row with m = 0 keeps the bits
-// of dQ/da, so a batch without demonstration rows leaves the bits of the launches these stand in for.
-#include "tthost.h"
-#include "ttlearn_bodies.h"
-
-#include <cmath>
+// (ttlearn_bodies.h), the tail's checks and conversion those of every tail (ttlearn_host.h); other units' instantiations are unchanged.
+// A row with m = 0 keeps the bits of dQ/da, so a batch without demonstration rows leaves the bits of the launches these stand in for.
+#include "ttlearn_host.h"
 
 namespace {
-
-using tthost::fail;
 
 __global__ __launch_bounds__(64 * NW) void k_fwd_small_demo(const int n, const float *__restrict__ obs, const float *__restrict__ action,
                                                             const float *__restrict__ w1e, const float *__restrict__ b1e,
@@ -92,7 +87,7 @@ int tt_mlp_forward_save_demo(int n, int critic, const float *obs, const float *a
     if (n == 0) return TT_OK;
     hipLaunchKernelGGL(k_fwd_small_demo, dim3((n + TR - 1) / TR), dim3(64 * NW), 0, stream, n, obs, action, w->w1, w->b1, w->g1, w->be1,
                        to_weights(w), out, sv, dq_da, din);
-    return hipGetLastError() == hipSuccess ? TT_OK : fail(TT_EHIP, "%s: the launch failed", who);
+    return launched(who);
 }
 
 int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
@@ -104,38 +99,16 @@ int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_ml
     const char *const who = "tt_mlp_actor_tail_demo";
     DemoIn din;
     if (const int rc = refuse_demo(who, demo, dq_da, din)) return rc;
-    if (shape) {
-        if (!std::isfinite(shape->huber_delta) || shape->huber_delta < 0.f)
-            return fail(TT_EINVAL, "%s: shape->huber_delta = %g is not a finite number >= 0", who, (double)shape->huber_delta);
-        if (!std::isfinite(shape->pre_scale) || shape->pre_scale < 0.f)
-            return fail(TT_EINVAL, "%s: shape->pre_scale = %g is not a finite number >= 0", who, (double)shape->pre_scale);
-        if (shape->pre_scale > 0.f && !shape->pre)
-            return fail(TT_EINVAL, "%s: shape->pre is NULL with pre_scale = %g > 0", who, (double)shape->pre_scale);
-    }
-    Saved sv;
-    BwdOut o;
-    AdamFused A;
-    if (n <= 0 || n > MAXB) return fail(TT_EINVAL, "%s: n = %d rows, not in [1, %d]", who, n, MAXB);
-    if (!obs || !mu || !q_out) return fail(TT_EINVAL, "%s: obs, mu or q_out is NULL", who);
-    if (!ok_shape(critic, true)) return fail(TT_EINVAL, "%s: the critic's weights are missing or not 23-400-300", who);
-    if (!to_saved(saved, sv)) return fail(TT_EINVAL, "%s: the saved forward lacks an array", who);
-    if (!to_bwd_out(ws, o)) return fail(TT_EINVAL, "%s: the per-row workspace lacks an array", who);
-    if (!ok_shape(grads, false)) return fail(TT_EINVAL, "%s: grads is missing or not 23-400-300", who);
-    if (!to_adam(false, count, params, exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, A))
-        return fail(TT_EINVAL, "%s: the optimizer step lacks a tensor or the step count, or count = %d is not 10", who, count);
-    if (!tail_words) return fail(TT_EINVAL, "%s: tail_words is NULL", who);
-    const int nb = (n + TR - 1) / TR;
-    if (nb > 64) return fail(TT_EINVAL, "%s: %d row workgroups, more than the 64 one wave polls", who, nb);
-    const RowScale rs{dq_da, mu, row_scale};      // (the tail's factors come from the rows' words; dq_da here is never read)
-    const TailSync ts{tail_words, reinterpret_cast<unsigned long long *>(tail_words + 64), nb, gave_up_host};
-    const dim3 grid(nb + WG_ACTOR_WEIGHTS), block(64 * NW);
     if (shape)
-        hipLaunchKernelGGL(k_actor_tail_demo<true>, grid, block, 0, stream, n, obs, mu, to_weights(critic), q_out, dq_da, sv, o,
-                           to_grads(grads), A, rs, ts, shape->pre_scale, static_cast<const float *>(shape->pre), din);
-    else
-        hipLaunchKernelGGL(k_actor_tail_demo<false>, grid, block, 0, stream, n, obs, mu, to_weights(critic), q_out, dq_da, sv, o,
-                           to_grads(grads), A, rs, ts, 0.f, static_cast<const float *>(nullptr), din);
-    return hipGetLastError() == hipSuccess ? TT_OK : fail(TT_EHIP, "%s: the launch failed", who);
+        if (const int rc = refuse_shape(who, shape)) return rc;
+    Tail T;
+    if (const int rc = to_actor_tail(who, n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params, exp_avg, exp_avg_sq,
+                                     targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words, gave_up_host, T))
+        return rc;
+    hipLaunchKernelGGL(shape ? k_actor_tail_demo<true> : k_actor_tail_demo<false>, T.grid, dim3(64 * NW), 0, stream, n, obs, mu, T.Wc, q_out,
+                       dq_da, T.sv, T.o, T.G, T.A, T.rs, T.ts, shape ? shape->pre_scale : 0.f,
+                       shape ? static_cast<const float *>(shape->pre) : nullptr, din);
+    return launched(who);
 }
 
 }  // extern "C"

@@ -12,9 +12,9 @@
 //                         update + the soft target update on each element just finished
 //   k_adam_soft           Adam + soft update as a launch of its own (data-parallel ranks: after the all-reduce)
 //
-// The structs, device bodies and host conversions are in ttlearn_bodies.h, which the population's launches (csrc/ttpop.hip) share
-// as well; this file holds the lone kernels and the C entry points.
-#include "ttlearn_bodies.h"
+// The structs, device bodies and host conversions are in ttlearn_bodies.h, which the population's launches (csrc/ttpop.hip) share as
+// well, the checked conversions of the launches with option forms in ttlearn_host.h; this file holds the lone kernels and entry points.
+#include "ttlearn_host.h"
 #include "ttp2p.h"             // the peer-to-peer gradient exchange of data-parallel ranks: k_adam_soft_p2p reads it
 
 namespace {
@@ -306,13 +306,8 @@ int tt_mlp_forward_save(int n, int critic, const float *obs, const float *action
     if (n == 0) return TT_OK;
     Saved sv{nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
     if (saved && !to_saved(saved, sv)) return TT_EINVAL;
-    const dim3 grid((n + TR - 1) / TR), block(64 * NW);
-    if (critic)
-        hipLaunchKernelGGL(k_fwd_small<true>, grid, block, 0, stream, n, obs, action, w->w1, w->b1, w->g1, w->be1, to_weights(w), out, sv, dq_da,
-                           static_cast<float *>(nullptr));
-    else
-        hipLaunchKernelGGL(k_fwd_small<false>, grid, block, 0, stream, n, obs, action, w->w1, w->b1, w->g1, w->be1, to_weights(w), out, sv,
-                           static_cast<float *>(nullptr), static_cast<float *>(nullptr));
+    hipLaunchKernelGGL(critic ? k_fwd_small<true> : k_fwd_small<false>, dim3((n + TR - 1) / TR), dim3(64 * NW), 0, stream, n, obs, action, w->w1,
+                       w->b1, w->g1, w->be1, to_weights(w), out, sv, critic ? dq_da : nullptr, static_cast<float *>(nullptr));
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
 }
 
@@ -353,28 +348,12 @@ int tt_mlp_backward_rows_pair(int n, float scale_critic, const float *q_out, con
                               const tt_mlp_saved *saved_critic, const tt_mlp_bwd_ws *ws_critic, const tt_td_input *tdi,
                               const float *mu_out, const tt_mlp_weights *actor, const tt_mlp_saved *saved_actor,
                               const tt_mlp_bwd_ws *ws_actor, const tt_image_job *image, tt_stream_t stream) {
-    ImageJob ij{};
-    if (image) {
-        const tt_mlp_weights *w = image->actor;
-        const tt_ring_cursor *c = image->cursor;
-        if (!ok_shape(w, false) || !w->split_ws || !c || !c->cursor || !c->k_dev || c->slots <= 0 || (tdi && (c->k_dev == tdi->step_dev ||
-                                                                                                         c->k_dev == tdi->window_dev)))
-            return TT_EINVAL;      // (the cursor's step number must be a word this launch does not advance)
-        ij.W = ttnet::to_weights(w);
-        ij.ws = reinterpret_cast<unsigned char *>(w->split_ws);
-        ij.ws_alt = reinterpret_cast<unsigned char *>(w->split_ws_alt);
-        ij.cur = ttnet::RingCursor{reinterpret_cast<const long long *>(c->k_dev), c->slots, c->cursor};
-        ij.on = 1;
-    }
-    Saved sc, sa;
-    BwdOut oc, oa;
-    TdIn td;
-    if (n <= 0 || !q_out || !mu_out || !ok_shape(critic, true) || !ok_shape(actor, false) || !to_saved(saved_critic, sc) ||
-        !to_saved(saved_actor, sa) || !to_bwd_out(ws_critic, oc) || !to_bwd_out(ws_actor, oa) || oc.dx2 == oa.dx2 || !to_td(tdi, td))
-        return TT_EINVAL;
-    hipLaunchKernelGGL(k_bwd_rows_pair, dim3(2 * ((n + TR - 1) / TR) + 1 + (ij.on ? IMAGE_WGS : 0)), dim3(64 * NW), 0, stream, n,
-                       scale_critic, q_out, to_weights(critic), sc, oc, td, mu_out, to_weights(actor), sa, oa, ij);
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+    const char *const who = "tt_mlp_backward_rows_pair";
+    RowsPair R;
+    if (const int rc = to_rows_pair(who, n, q_out, critic, saved_critic, ws_critic, tdi, mu_out, actor, saved_actor, ws_actor, image, R)) return rc;
+    hipLaunchKernelGGL(k_bwd_rows_pair, R.grid, dim3(64 * NW), 0, stream, n, scale_critic, q_out, R.Wc, R.sc, R.oc, R.td, mu_out, R.Wa, R.sa,
+                       R.oa, R.img);
+    return launched(who);
 }
 
 int tt_mlp_backward_weights(int n, int critic, const float *obs, const float *action, const tt_mlp_saved *saved,
@@ -383,24 +362,15 @@ int tt_mlp_backward_weights(int n, int critic, const float *obs, const float *ac
                             float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
                             float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
                             tt_stream_t stream) {
-    Saved sv;
-    BwdOut o;
-    if (n <= 0 || !obs || (critic && !action) || !to_saved(saved, sv) || !to_bwd_out(ws, o) || !ok_shape(grads, critic != 0) ||
-        ((row_dq_da == nullptr) != (row_mu == nullptr)))
-        return TT_EINVAL;
-    AdamFused A{};      // count = 0: gradients only; else Adam + soft update applied in the same launch (one rank)
-    if (count && !to_adam(critic != 0, count, params, exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau,
-                          images, bias_corr, A))
-        return TT_EINVAL;
-    const RowScale rs{row_dq_da, row_mu, row_scale};
-    const dim3 grid(critic ? WG_CRITIC_WEIGHTS : WG_ACTOR_WEIGHTS);
-    if (row_dq_da) {
-        if (n > MAXB) return TT_EINVAL;
-        hipLaunchKernelGGL(k_bwd_weights<true>, grid, dim3(256), 0, stream, n, critic, obs, action, sv, o, to_grads(grads), A, rs);
-    } else {
-        hipLaunchKernelGGL(k_bwd_weights<false>, grid, dim3(256), 0, stream, n, critic, obs, action, sv, o, to_grads(grads), A, rs);
-    }
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+    const char *const who = "tt_mlp_backward_weights";
+    if (critic && !action) return fail(TT_EINVAL, "%s: action is NULL for the critic", who);
+    WeightsLaunch L;      // (count = 0: gradients only; else Adam + soft update applied in the same launch, one rank)
+    if (const int rc = to_weights_launch(who, false, n, critic, obs, saved, ws, grads, row_dq_da, row_mu, row_scale, count, params, exp_avg,
+                                         exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, L))
+        return rc;
+    hipLaunchKernelGGL(row_dq_da ? k_bwd_weights<true> : k_bwd_weights<false>, dim3(critic ? WG_CRITIC_WEIGHTS : WG_ACTOR_WEIGHTS), dim3(256), 0,
+                       stream, n, critic, obs, action, L.sv, L.o, L.G, L.A, L.rs);
+    return launched(who);
 }
 
 int tt_mlp_actor_tail(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
@@ -409,21 +379,13 @@ int tt_mlp_actor_tail(int n, const float *obs, const float *mu, const tt_mlp_wei
                       const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                       const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
                       tt_stream_t stream) {
-    Saved sv;
-    BwdOut o;
-    AdamFused A;
-    if (n <= 0 || n > MAXB || !obs || !mu || !q_out || !dq_da || !ok_shape(critic, true) || !to_saved(saved, sv) || !to_bwd_out(ws, o) ||
-        !ok_shape(grads, false) || !to_adam(false, count, params, exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps,
-                                            weight_decay, tau, images, bias_corr, A) || !tail_words)
-        return TT_EINVAL;
-    const int nb = (n + TR - 1) / TR;
-    if (nb > 64) return TT_EINVAL;                         // (one wave polls the producers' words)
-    const RowScale rs{dq_da, mu, row_scale};
-    // tail_words: [0, 64) the row workgroups' hints, [64, 64 + 2 n) the rows' 8-byte words
-    const TailSync ts{tail_words, reinterpret_cast<unsigned long long *>(tail_words + 64), nb, gave_up_host};
-    hipLaunchKernelGGL(k_actor_tail, dim3(nb + WG_ACTOR_WEIGHTS), dim3(64 * NW), 0, stream, n, obs, mu, to_weights(critic), q_out,
-                       dq_da, sv, o, to_grads(grads), A, rs, ts);
-    return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
+    const char *const who = "tt_mlp_actor_tail";
+    Tail T;
+    if (const int rc = to_actor_tail(who, n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params, exp_avg, exp_avg_sq,
+                                     targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words, gave_up_host, T))
+        return rc;
+    hipLaunchKernelGGL(k_actor_tail, T.grid, dim3(64 * NW), 0, stream, n, obs, mu, T.Wc, q_out, dq_da, T.sv, T.o, T.G, T.A, T.rs, T.ts);
+    return launched(who);
 }
 
 // The table of both optimizer launches: the tensors, the fc2 images and each tensor's first workgroup at `per_block` elements per

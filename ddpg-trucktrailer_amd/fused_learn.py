@@ -78,6 +78,11 @@ class _NetState:
         self.a_t = arr(self.targets) if self.targets is not None else None
         self.a_n = (C.c_int32 * cnt)(*[p.numel() for p in self.params])
         self.count = cnt
+        self.images = None              # a tt_fc2_images of net and target, set by the learner when it keeps fc2 images
+
+    def images_ref(self, on=True):
+        """The tt_fc2_images argument of an optimizer step: a reference, or None without images (or with `on` false)."""
+        return C.byref(self.images) if (on and self.images is not None) else None
 
     def bind_flat_grad(self, flat):
         """The flat gradient buffer (tt_mlp_weights order) the backward launches write and the optimizer launch / the gradient
@@ -360,13 +365,11 @@ class FusedLearner:
         lr, b1, b2, eps, wd = hyp
         if self.p2p is not None:       # the mean of the ranks' gradients is formed INSIDE this launch (include/ttenv.h: tt_p2p_*)
             L.check_p2p(self.lib.tt_adam_soft_update_p2p(self.p2p, 0 if st.critic else 1, st.count, st.a_p, st.a_m, st.a_v, st.a_t, st.a_n,
-                                                         L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau,
-                                                         C.byref(st.images) if st.images is not None else None,
+                                                         L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau, st.images_ref(),
                                                          L.ptr(self.bias_corr), self._stream()), self.p2p)
             return
         L.check(self.lib.tt_adam_soft_update(st.count, st.a_p, st.a_g, st.a_m, st.a_v, st.a_t, st.a_n, L.ptr(self.step_dev),
-                                             lr, b1, b2, eps, wd, tau, C.byref(st.images) if st.images is not None else None,
-                                             L.ptr(self.bias_corr), self._stream()))
+                                             lr, b1, b2, eps, wd, tau, st.images_ref(), L.ptr(self.bias_corr), self._stream()))
 
     def enable_data_parallel(self, group=None):
         """Mean of the flat gradient buffers over the ranks at the reference's two optimizer sites (RCCL: one AVG
@@ -552,33 +555,26 @@ class FusedLearner:
         # ... and, on other workgroups of the same launch, the ACTOR's per-row backward for a unit gradient: it is linear in
         # the row's d(loss)/d(pre-tanh), which needs the updated critic and is applied in phase_b (include/ttenv.h)
         job = C.byref(L.TTImageJob(C.pointer(image[0]), C.pointer(image[1]))) if image is not None else None
-        if self.loss_shape is not None:       # the same grid with the Huber clamp and the actor's pre-activations (csrc/ttshape.hip)
-            L.check(self.lib.tt_mlp_backward_rows_pair_shaped(B, self.loss_shape.critic_scale(B), L.ptr(self.q), C.byref(self.w(ag.critic)),
-                                                              C.byref(self.critic.saved), C.byref(self.ws), C.byref(td), L.ptr(self.mu),
-                                                              C.byref(self.w(ag.actor)), C.byref(self.actor.saved),
-                                                              C.byref(self.ws_actor), job, C.byref(self._shape), self._stream()))
-            return
-        L.check(self.lib.tt_mlp_backward_rows_pair(B, 2.0 / B, L.ptr(self.q), C.byref(self.w(ag.critic)),
-                                                   C.byref(self.critic.saved), C.byref(self.ws), C.byref(td), L.ptr(self.mu),
-                                                   C.byref(self.w(ag.actor)), C.byref(self.actor.saved),
-                                                   C.byref(self.ws_actor), job, self._stream()))
+        shape = self.loss_shape       # with one: the same grid with the Huber clamp and the actor's pre-activations (csrc/ttshape.hip)
+        args = [B, 2.0 / B if shape is None else shape.critic_scale(B), L.ptr(self.q), C.byref(self.w(ag.critic)), C.byref(self.critic.saved),
+                C.byref(self.ws), C.byref(td), L.ptr(self.mu), C.byref(self.w(ag.actor)), C.byref(self.actor.saved), C.byref(self.ws_actor), job]
+        if shape is None:
+            L.check(self.lib.tt_mlp_backward_rows_pair(*args, self._stream()))
+        else:
+            L.check(self.lib.tt_mlp_backward_rows_pair_shaped(*args, C.byref(self._shape), self._stream()))
 
     def _weights(self, st, hyp, tau, obs, action, ws, adam, row=None):
         """The weight-gradient launch (tt_mlp_backward_weights), with Adam + soft update in it when `adam`."""
         lr, b1, b2, eps, wd = hyp
         dq, mu, sc = row if row is not None else (None, None, 1.0)
-        if self.loss_shape is not None and not st.critic and row is not None:      # the actor's rows also carry the penalty's term
-            L.check(self.lib.tt_mlp_backward_weights_shaped(self.B, 0, L.ptr(obs), None, C.byref(st.saved), C.byref(ws),
-                                                            C.byref(st.gstruct), L.ptr(dq), L.ptr(mu), float(sc), st.count if adam else 0,
-                                                            st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau,
-                                                            C.byref(st.images) if (adam and st.images is not None) else None,
-                                                            L.ptr(self.bias_corr), C.byref(self._shape), self._stream()))
-            return
-        L.check(self.lib.tt_mlp_backward_weights(self.B, 1 if st.critic else 0, L.ptr(obs), L.ptr(action), C.byref(st.saved), C.byref(ws),
-                                                 C.byref(st.gstruct), L.ptr(dq), L.ptr(mu), float(sc), st.count if adam else 0,
-                                                 st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau,
-                                                 C.byref(st.images) if (adam and st.images is not None) else None,
-                                                 L.ptr(self.bias_corr), self._stream()))
+        shaped = self.loss_shape is not None and not st.critic and row is not None      # the actor's rows also carry the penalty's term
+        args = [self.B, 1 if st.critic else 0, L.ptr(obs), L.ptr(action), C.byref(st.saved), C.byref(ws), C.byref(st.gstruct),
+                L.ptr(dq), L.ptr(mu), float(sc), st.count if adam else 0, st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev),
+                lr, b1, b2, eps, wd, tau, st.images_ref(adam), L.ptr(self.bias_corr)]      # (the shaped form ignores the action)
+        if shaped:
+            L.check(self.lib.tt_mlp_backward_weights_shaped(*args, C.byref(self._shape), self._stream()))
+        else:
+            L.check(self.lib.tt_mlp_backward_weights(*args, self._stream()))
 
     def phase_b(self, states, separate_adam, demo=None):
         """[critic Adam/soft update when not already applied,] then the actor step through the UPDATED critic
@@ -592,29 +588,17 @@ class FusedLearner:
             self._fresh()
             st = self.actor
             lr, b1, b2, eps, wd = self.hyp_actor
-            if demo is not None:
-                L.check(self.lib.tt_mlp_actor_tail_demo(B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi),
-                                                        L.ptr(self.dq_da), C.byref(st.saved), C.byref(self.ws_actor), C.byref(st.gstruct),
-                                                        -1.0 / B, st.count, st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1,
-                                                        b2, eps, wd, ag.tau, C.byref(st.images) if st.images is not None else None,
-                                                        L.ptr(self.bias_corr), L.ptr(self.tail_words),
-                                                        C.c_void_p(self.tail_gave_up_host.data_ptr()),
-                                                        C.byref(self._shape) if self.loss_shape is not None else None, C.byref(demo),
-                                                        self._stream()))
-                return
-            if self.loss_shape is not None:
-                L.check(self.lib.tt_mlp_actor_tail_shaped(B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi),
-                                                          L.ptr(self.dq_da), C.byref(st.saved), C.byref(self.ws_actor), C.byref(st.gstruct),
-                                                          -1.0 / B, st.count, st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1,
-                                                          b2, eps, wd, ag.tau, C.byref(st.images) if st.images is not None else None,
-                                                          L.ptr(self.bias_corr), L.ptr(self.tail_words),
-                                                          C.c_void_p(self.tail_gave_up_host.data_ptr()), C.byref(self._shape), self._stream()))
-                return
-            L.check(self.lib.tt_mlp_actor_tail(B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi), L.ptr(self.dq_da),
-                                               C.byref(st.saved), C.byref(self.ws_actor), C.byref(st.gstruct), -1.0 / B, st.count,
-                                               st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev), lr, b1, b2, eps, wd, ag.tau,
-                                               C.byref(st.images) if st.images is not None else None, L.ptr(self.bias_corr),
-                                               L.ptr(self.tail_words), C.c_void_p(self.tail_gave_up_host.data_ptr()), self._stream()))
+            args = [B, L.ptr(states), L.ptr(self.mu), C.byref(self.w(ag.critic)), L.ptr(self.q_pi), L.ptr(self.dq_da), C.byref(st.saved),
+                    C.byref(self.ws_actor), C.byref(st.gstruct), -1.0 / B, st.count, st.a_p, st.a_m, st.a_v, st.a_t, L.ptr(self.step_dev),
+                    lr, b1, b2, eps, wd, ag.tau, st.images_ref(), L.ptr(self.bias_corr), L.ptr(self.tail_words),
+                    C.c_void_p(self.tail_gave_up_host.data_ptr())]
+            shape = C.byref(self._shape) if self.loss_shape is not None else None
+            if demo is not None:              # (the demonstration form takes the shape as well, NULL without one)
+                L.check(self.lib.tt_mlp_actor_tail_demo(*args, shape, C.byref(demo), self._stream()))
+            elif shape is not None:
+                L.check(self.lib.tt_mlp_actor_tail_shaped(*args, shape, self._stream()))
+            else:
+                L.check(self.lib.tt_mlp_actor_tail(*args, self._stream()))
             return
         self._fwd(ag.critic, states, self.mu, self.q_pi, dq_da=self.dq_da, demo=demo)
         self._weights(self.actor, self.hyp_actor, ag.tau, states, None, self.ws_actor, adam=not separate_adam,

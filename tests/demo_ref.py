@@ -1,13 +1,13 @@
-"""tests/shape_ref.py's f64 learn() step with a demonstration loss (ddpg_trucktrailer_amd/demo_loss.py): a behaviour-cloning term
-lambda (1/B) sum_b m_b (mu_b - a_b)^2 on the demonstration rows of the batch, m_b gated by the Q-filter q_b > q_pi_b.  What
+"""The cases of tests/learn_ref.py's f64 learn() step with a demonstration loss (ddpg_trucktrailer_amd/demo_loss.py): a behaviour-cloning
+term lambda (1/B) sum_b m_b (mu_b - a_b)^2 on the demonstration rows of the batch, m_b gated by the Q-filter q_b > q_pi_b; lam, the
+filter and the rows' mask are arguments of learn_ref.ref_step, the applied mask one of learn_ref.actor_half.  What
 tests/test_demo_loss_cpu.py (CPU) and tests/test_gpu_demo_loss.py (GPU) share.  States and batches are learn_ref.case's, unchanged:
 the option moves no pre-ReLU value of critic(s, a) or actor(s), so a batch that learn_ref.make_batch found clean stays clean.
 
     demo_mask(B)        THE RULE that names the demonstration rows of a batch: rows b with b % 3 == 0 (row 0 alone at B = 1)
     filter_of           the f64 filter of a step: q (the critic BEFORE the update) > q_pi (the UPDATED critic), the margin below
                         which a row is undecided, and the rows on each side
-    actor_half          shape_ref.actor_half plus the cloning term for a given applied mask; also returns bc_part
-    ref_step            shape_ref.ref_step with (lam, q_filter, demo_mask); also returns m (applied), code, dq_eff, bc_loss
+    ref_step            learn_ref.ref_step on the rows of demo_mask; also returns code
     zero_action_case    a state and batch (action_value weights zero, stored actions zero) with dQ/da exactly 0 on every row
 
 The two sides of the filter are one critic Adam step apart, by definition (demo_loss.py): q is the first forward's, q_pi the third's.
@@ -18,7 +18,6 @@ learn_ref.MAX_DISCARD of the demonstration rows, and at B >= 33 each side of the
 import functools
 
 import torch
-import torch.nn.functional as F
 
 import learn_ref as R
 import shape_ref as S
@@ -68,77 +67,15 @@ def check_inputs(q, q_pi, mask):
     return above, n - above, und, n
 
 
-def actor_half(critic, actor, s, a, dq_da=None, c=0.0, lam=0.0, applied=None):
-    """shape_ref.actor_half for the loss -mean Q(s, mu(s)) + c mean(pre^2) + lam (1/B) sum_b m_b (mu_b - a_b)^2 with the APPLIED mask
-    m given (None: no row): the gradient of sum_b c_b mu_b + (c / B) sum_b pre_b^2 + (lam / B) sum_b m_b (mu_b - a_b)^2, c_b = -(1/B)
-    dQ/da[b].  Returns shape_ref.actor_half's dict plus bc_part and dq_eff = dQ/da - 2 lam m (mu - a) (of the dq_da used)."""
-    B = s.shape[0]
-    z1 = actor.bn1(actor.fc1(s))
-    z2 = actor.bn2(actor.fc2(F.relu(z1)))
-    pre = actor.mu(F.relu(z2))
-    mu = torch.tanh(pre)
-    at_mu = mu.detach().clone().requires_grad_(True)
-    q_pi, *z_pi = R.forward_z(critic, s, at_mu)
-    own = torch.autograd.grad(q_pi.sum(), at_mu)[0].view(-1)
-    used = own if dq_da is None else dq_da.to(mu).view(-1)
-    cb = -used / B
-    m = torch.zeros(B, dtype=mu.dtype, device=mu.device) if applied is None else applied.to(mu).view(-1)
-    d = mu.view(-1) - a.to(mu).view(-1)
-    bc = lam * (m * d * d).sum() / B
-    loss = (cb.view(-1, 1) * mu).sum() + c * (pre * pre).mean() + bc
-    g = torch.autograd.grad(loss, list(actor.parameters()))
-    names = [k for k, _ in actor.named_parameters()]
-    return dict(mu=mu.detach().view(-1), pre=pre.detach().view(-1), q_pi=q_pi.detach().view(-1), dq_da=own,
-                z_actor=(z1.detach(), z2.detach()), z_pi=tuple(t.detach() for t in z_pi),
-                grads=dict(zip(names, (x.clone() for x in g))), q_part=float(-q_pi.mean().item()),
-                pen_part=float(c * (pre * pre).mean().item()), bc_part=float(bc.item()),
-                dq_eff=(used - 2.0 * lam * m * d).detach())
-
-
 def codes(mask, applied):
     """code [B] int: 0 a ring row, 1 a demonstration row left out, 2 a demonstration row applied."""
     return mask.to(torch.int32) + (mask & applied).to(torch.int32)
 
 
 def ref_step(state, batch, hyper, delta=None, c=0.0, lam=0.0, q_filter=True, mask=None):
-    """shape_ref.ref_step with the demonstration loss: `mask` [B] bool names the demonstration rows (None: demo_mask(B)), the filter
-    compares q of the critic BEFORE its step with q_pi through the UPDATED critic.  Returns its dict plus m (the applied rows),
-    code, dq_eff, bc_loss and demo (the mask)."""
-    s, a, r, s2, done = (t.detach().cpu() for t in batch)
-    s, a, r, s2, done = s.double(), a.double().view(-1, 1), r.double().view(-1), s2.double(), done.bool().view(-1)
-    mask = demo_mask(s.shape[0]) if mask is None else mask.cpu().bool().view(-1)
-    agent = R.load_agent(state, hyper, torch.device("cpu"), torch.float64)
-    with torch.no_grad():
-        q_next = agent.target_critic(s2, agent.target_actor(s2)).view(-1)
-        y = r + hyper["gamma"] * q_next.masked_fill(done, 0.0)
-    grads, z = {}, {}
-    q, *z["critic"] = R.forward_z(agent.critic, s, a)
-    names = [k for k, _ in agent.critic.named_parameters()]
-    critic_loss = F.mse_loss(y.view(-1, 1), q) if delta is None else F.huber_loss(q, y.view(-1, 1), delta=delta)
-    g = torch.autograd.grad(critic_loss, list(agent.critic.parameters()))
-    for p, gp in zip(agent.critic.parameters(), g):
-        p.grad = gp
-    grads["critic"] = dict(zip(names, (x.clone() for x in g)))
-    agent.critic.optimizer.step()
-    q = q.detach().view(-1)
-    with torch.no_grad():
-        q_pi = agent.critic(s, agent.actor(s)).view(-1)              # through the UPDATED critic
-    applied = mask & (q > q_pi) if q_filter else mask.clone()
-    half = actor_half(agent.critic, agent.actor, s, a, c=c, lam=lam, applied=applied)
-    for k, p in agent.actor.named_parameters():
-        p.grad = half["grads"][k]
-    grads["actor"] = half["grads"]
-    agent.actor.optimizer.step()
-    agent.update_network_parameters()
-    z = dict(critic=tuple(t.detach() for t in z["critic"]), actor=half["z_actor"], critic_pi=half["z_pi"])
-    margin = torch.stack([t.abs().min(1).values for k in ("critic", "actor") for t in z[k]]).min(0).values
-    return dict(y=y, q=q, q_pi=half["q_pi"], dq_da=half["dq_da"], mu=half["mu"], pre=half["pre"], grads=grads,
-                nets={n: {k: v.detach().clone() for k, v in getattr(agent, n).state_dict().items()} for n in R.NETS},
-                m={n: R._moments(getattr(agent, n), "exp_avg") for n in ("actor", "critic")},
-                v={n: R._moments(getattr(agent, n), "exp_avg_sq") for n in ("actor", "critic")},
-                step=int(state["step"]) + 1, z=z, margin=margin, critic_loss=float(critic_loss.item()),
-                actor_loss=half["q_part"] + half["pen_part"] + half["bc_part"], demo=mask, applied=applied, code=codes(mask, applied),
-                dq_eff=half["dq_eff"], bc_loss=half["bc_part"])
+    """learn_ref.ref_step with demo_mask(B) for the demonstration rows where `mask` is None; also returns code."""
+    out = R.ref_step(state, batch, hyper, delta, c, lam, q_filter, demo_mask(len(batch[0])) if mask is None else mask)
+    return dict(out, code=codes(out["demo"], out["applied"]))
 
 
 def demo_case(case, lam, q_filter, huber=False, c=0.0):

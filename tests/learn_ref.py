@@ -1,5 +1,6 @@
 """What tests/test_learn_ref.py (CPU) and tests/test_gpu_learn_shapes.py (GPU) share: learn() restated in f64 with the project's own
-modules, autograd and torch.optim.Adam (ref_step, actor_half), the optimizer formula of adam_finish (csrc/ttlearn_bodies.h) in f64
+modules, autograd and torch.optim.Adam (ref_step, actor_half: the loss shape and the demonstration loss are arguments of the one
+step; tests/shape_ref.py and tests/demo_ref.py hold what is those options' own), the optimizer formula of adam_finish (csrc/ttlearn_bodies.h) in f64
 (adam64), and a builder of states and batches whose ReLU units stay clear of zero (make_state, make_batch).
 
 A unit whose pre-ReLU value lies within rounding of zero can fall on the other side in f32 than in f64, and its row's whole
@@ -101,20 +102,35 @@ def _moments(net, key):
     return {k: net.optimizer.state[p][key].detach().clone() for k, p in net.named_parameters()}
 
 
-def actor_half(critic, actor, s, dq_da=None):
+def actor_half(critic, actor, s, a=None, dq_da=None, c=0.0, lam=0.0, applied=None):
     """The actor half of learn() in f64 on modules: mu(s); Q(s, mu(s)) and dQ/da at a = mu(s) through `critic` (the updated one);
     the actor's gradients of mean(-Q(s, mu(s))), formed as the gradient of sum_b c_b mu_b with c_b = -(1/B) dQ/da[b] (the chain
     rule through the critic written out: what tt_mlp_backward_weights' row factor is).  dq_da: per-row values to use for c_b in
-    place of this function's own.  Returns dict(mu, q_pi, dq_da, z_actor, z_pi, grads {name: tensor})."""
-    mu, *z_actor = forward_z(actor, s)
+    place of this function's own.  With a loss shape (c) and a demonstration loss (lam, the stored actions `a` and the APPLIED mask;
+    None: no row) the loss is -mean Q(s, mu(s)) + c mean(pre^2) + lam (1/B) sum_b m_b (mu_b - a_b)^2, pre the value in front of tanh.
+    Returns dict(mu, pre, q_pi, dq_da, z_actor, z_pi, grads {name: tensor}, q_part = -mean q_pi, pen_part, bc_part -- the three
+    parts of the loss --, dq_eff = dQ/da - 2 lam m (mu - a) of the dq_da used)."""
+    B = s.shape[0]
+    z1 = actor.bn1(actor.fc1(s))
+    z2 = actor.bn2(actor.fc2(F.relu(z1)))
+    pre = actor.mu(F.relu(z2))
+    mu = torch.tanh(pre)
     at_mu = mu.detach().clone().requires_grad_(True)
     q_pi, *z_pi = forward_z(critic, s, at_mu)
     own = torch.autograd.grad(q_pi.sum(), at_mu)[0].view(-1)
-    c = -(own if dq_da is None else dq_da.to(mu).view(-1)) / s.shape[0]
-    g = torch.autograd.grad((c.view(-1, 1) * mu).sum(), list(actor.parameters()))
+    used = own if dq_da is None else dq_da.to(mu).view(-1)
+    cb = -used / B
+    m = torch.zeros(B, dtype=mu.dtype, device=mu.device) if applied is None else applied.to(mu).view(-1)
+    d = mu.view(-1) - (0.0 if a is None else a.to(mu).view(-1))
+    bc = lam * (m * d * d).sum() / B
+    loss = (cb.view(-1, 1) * mu).sum() + c * (pre * pre).mean() + bc
+    g = torch.autograd.grad(loss, list(actor.parameters()))
     names = [k for k, _ in actor.named_parameters()]
-    return dict(mu=mu.detach().view(-1), q_pi=q_pi.detach().view(-1), dq_da=own, z_actor=tuple(t.detach() for t in z_actor),
-                z_pi=tuple(t.detach() for t in z_pi), grads=dict(zip(names, (x.clone() for x in g))))
+    return dict(mu=mu.detach().view(-1), pre=pre.detach().view(-1), q_pi=q_pi.detach().view(-1), dq_da=own,
+                z_actor=(z1.detach(), z2.detach()), z_pi=tuple(t.detach() for t in z_pi),
+                grads=dict(zip(names, (x.clone() for x in g))), q_part=float(-q_pi.mean().item()),
+                pen_part=float(c * (pre * pre).mean().item()), bc_part=float(bc.item()),
+                dq_eff=(used - 2.0 * lam * m * d).detach())
 
 
 def near_units(z2_pi, margin=MARGIN):
@@ -135,14 +151,18 @@ def dq_da_choices(critic, z2_pi, dq_da, margin=MARGIN):
     return out
 
 
-def ref_step(state, batch, hyper):
+def ref_step(state, batch, hyper, delta=None, c=0.0, lam=0.0, q_filter=True, mask=None):
     """One learn() in f64 (DDPG_agent.py:72-106 as agent.py's learn_batch orders it).  batch = (s, a, r, s2, done), done bool or
-    uint8.  Returns a dict: y, q, mu, q_pi (Q(s, mu(s)) through the updated critic), dq_da (its derivative at a = mu(s)), grads
-    {critic, actor: {name: tensor}} as the optimizers saw them, nets / m / v / step after the step, z {critic, actor, critic_pi:
-    (z1, z2)} in front of the ReLUs of the three forwards that carry a gradient, and margin = per row the smallest |z| of the two
-    forwards that depend on the row alone (critic, actor)."""
+    uint8.  The options: the critic loss huber_loss(q, y, delta) (delta None: mse_loss), the actor's pre-activation penalty c
+    mean(pre^2), and the demonstration loss lam on the rows `mask` [B] bool names (None: no row), gated by the filter q > q_pi -- q of
+    the critic BEFORE its step, q_pi through the UPDATED one -- when q_filter.  Returns a dict: y, q, mu, pre, q_pi (Q(s, mu(s))
+    through the updated critic), dq_da (its derivative at a = mu(s)), grads {critic, actor: {name: tensor}} as the optimizers saw
+    them, nets / m / v / step after the step, z {critic, actor, critic_pi: (z1, z2)} in front of the ReLUs of the three forwards
+    that carry a gradient, margin = per row the smallest |z| of the two forwards that depend on the row alone (critic, actor),
+    critic_loss, actor_loss, and of the demonstration loss demo (the mask), applied, dq_eff, bc_loss."""
     s, a, r, s2, done = (t.detach().cpu() for t in batch)
     s, a, r, s2, done = s.double(), a.double().view(-1, 1), r.double().view(-1), s2.double(), done.bool().view(-1)
+    mask = torch.zeros(s.shape[0], dtype=torch.bool) if mask is None else mask.cpu().bool().view(-1)
     agent = load_agent(state, hyper, torch.device("cpu"), torch.float64)
     with torch.no_grad():
         q_next = agent.target_critic(s2, agent.target_actor(s2)).view(-1)
@@ -150,12 +170,17 @@ def ref_step(state, batch, hyper):
     grads, z = {}, {}
     q, *z["critic"] = forward_z(agent.critic, s, a)
     names = [k for k, _ in agent.critic.named_parameters()]
-    g = torch.autograd.grad(F.mse_loss(y.view(-1, 1), q), list(agent.critic.parameters()))
+    critic_loss = F.mse_loss(y.view(-1, 1), q) if delta is None else F.huber_loss(q, y.view(-1, 1), delta=delta)
+    g = torch.autograd.grad(critic_loss, list(agent.critic.parameters()))
     for p, gp in zip(agent.critic.parameters(), g):
         p.grad = gp
     grads["critic"] = dict(zip(names, (x.clone() for x in g)))
     agent.critic.optimizer.step()
-    half = actor_half(agent.critic, agent.actor, s)          # the actor step, through the UPDATED critic
+    q = q.detach().view(-1)
+    with torch.no_grad():
+        q_pi = agent.critic(s, agent.actor(s)).view(-1)              # through the UPDATED critic
+    applied = mask & (q > q_pi) if q_filter else mask.clone()
+    half = actor_half(agent.critic, agent.actor, s, a, c=c, lam=lam, applied=applied)      # the actor step, through the UPDATED critic
     for k, p in agent.actor.named_parameters():
         p.grad = half["grads"][k]
     grads["actor"] = half["grads"]
@@ -163,11 +188,13 @@ def ref_step(state, batch, hyper):
     agent.update_network_parameters()
     z = dict(critic=tuple(t.detach() for t in z["critic"]), actor=half["z_actor"], critic_pi=half["z_pi"])
     margin = torch.stack([t.abs().min(1).values for k in ("critic", "actor") for t in z[k]]).min(0).values
-    return dict(y=y, q=q.detach().view(-1), q_pi=half["q_pi"], dq_da=half["dq_da"], mu=half["mu"], grads=grads,
+    return dict(y=y, q=q, q_pi=half["q_pi"], dq_da=half["dq_da"], mu=half["mu"], pre=half["pre"], grads=grads,
                 nets={n: {k: v.detach().clone() for k, v in getattr(agent, n).state_dict().items()} for n in NETS},
                 m={n: _moments(getattr(agent, n), "exp_avg") for n in ("actor", "critic")},
                 v={n: _moments(getattr(agent, n), "exp_avg_sq") for n in ("actor", "critic")},
-                step=int(state["step"]) + 1, z=z, margin=margin)
+                step=int(state["step"]) + 1, z=z, margin=margin, critic_loss=float(critic_loss.item()),
+                actor_loss=half["q_part"] + half["pen_part"] + half["bc_part"], demo=mask, applied=applied, dq_eff=half["dq_eff"],
+                bc_loss=half["bc_part"])
 
 
 def soft64(tgt, p, tau):

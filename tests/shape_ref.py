@@ -1,14 +1,12 @@
-"""tests/learn_ref.py's f64 learn() step with a loss shape (ddpg_trucktrailer_amd/loss_shape.py): a Huber critic loss with delta and
-the actor's pre-activation penalty c mean(pre^2).  What tests/test_loss_shape_cpu.py (CPU) and tests/test_gpu_loss_shape.py (GPU)
-share.  States, batches and their MAX_DISCARD cap are learn_ref's, unchanged: neither option moves a pre-ReLU value of critic(s, a)
+"""The cases of tests/learn_ref.py's f64 learn() step with a loss shape (ddpg_trucktrailer_amd/loss_shape.py): a Huber critic loss
+with delta and the actor's pre-activation penalty c mean(pre^2), both arguments of learn_ref.ref_step and learn_ref.actor_half.  What
+tests/test_loss_shape_cpu.py (CPU) and tests/test_gpu_loss_shape.py (GPU) share.  States, batches and their MAX_DISCARD cap are learn_ref's, unchanged: neither option moves a pre-ReLU value of critic(s, a)
 or actor(s), so a batch that learn_ref.make_batch found clean stays clean.
 
     delta_of(ref)       the delta of a case: the median of |q - y| of the f64 reference on the batch
-    actor_half          learn_ref.actor_half plus c mean(pre^2) in the actor's loss; also returns pre and both parts of the loss
-    ref_step            learn_ref.ref_step with delta and c; also returns pre, critic_loss and actor_loss
+    shaped(case, ..)    a learn_ref case with a shape, and learn_ref.ref_step's result on it
     saturated_state     a state whose actor head is scaled and biased so that mu is exactly +-1.0f on some rows of a batch"""
 import torch
-import torch.nn.functional as F
 
 import learn_ref as R
 
@@ -34,66 +32,12 @@ def sides(ref, delta):
     return int((e < delta).sum().item()), int((e > delta).sum().item())
 
 
-def actor_half(critic, actor, s, dq_da=None, c=0.0):
-    """learn_ref.actor_half for the loss -mean Q(s, mu(s)) + c mean(pre^2): the gradient of sum_b c_b mu_b + (c / B) sum_b pre_b^2
-    with c_b = -(1/B) dQ/da[b].  Returns learn_ref.actor_half's dict plus pre [B], q_part = -mean q_pi and pen_part = c mean(pre^2)."""
-    z1 = actor.bn1(actor.fc1(s))
-    z2 = actor.bn2(actor.fc2(F.relu(z1)))
-    pre = actor.mu(F.relu(z2))
-    mu = torch.tanh(pre)
-    at_mu = mu.detach().clone().requires_grad_(True)
-    q_pi, *z_pi = R.forward_z(critic, s, at_mu)
-    own = torch.autograd.grad(q_pi.sum(), at_mu)[0].view(-1)
-    cb = -(own if dq_da is None else dq_da.to(mu).view(-1)) / s.shape[0]
-    loss = (cb.view(-1, 1) * mu).sum() + c * (pre * pre).mean()
-    g = torch.autograd.grad(loss, list(actor.parameters()))
-    names = [k for k, _ in actor.named_parameters()]
-    return dict(mu=mu.detach().view(-1), pre=pre.detach().view(-1), q_pi=q_pi.detach().view(-1), dq_da=own,
-                z_actor=(z1.detach(), z2.detach()), z_pi=tuple(t.detach() for t in z_pi),
-                grads=dict(zip(names, (x.clone() for x in g))), q_part=float(-q_pi.mean().item()),
-                pen_part=float(c * (pre * pre).mean().item()))
-
-
-def ref_step(state, batch, hyper, delta=None, c=0.0):
-    """learn_ref.ref_step with the critic loss huber_loss(q, y, delta) (delta None: mse_loss) and the actor loss -mean Q + c
-    mean(pre^2).  Returns its dict plus pre, critic_loss, actor_loss."""
-    s, a, r, s2, done = (t.detach().cpu() for t in batch)
-    s, a, r, s2, done = s.double(), a.double().view(-1, 1), r.double().view(-1), s2.double(), done.bool().view(-1)
-    agent = R.load_agent(state, hyper, torch.device("cpu"), torch.float64)
-    with torch.no_grad():
-        q_next = agent.target_critic(s2, agent.target_actor(s2)).view(-1)
-        y = r + hyper["gamma"] * q_next.masked_fill(done, 0.0)
-    grads, z = {}, {}
-    q, *z["critic"] = R.forward_z(agent.critic, s, a)
-    names = [k for k, _ in agent.critic.named_parameters()]
-    critic_loss = F.mse_loss(y.view(-1, 1), q) if delta is None else F.huber_loss(q, y.view(-1, 1), delta=delta)
-    g = torch.autograd.grad(critic_loss, list(agent.critic.parameters()))
-    for p, gp in zip(agent.critic.parameters(), g):
-        p.grad = gp
-    grads["critic"] = dict(zip(names, (x.clone() for x in g)))
-    agent.critic.optimizer.step()
-    half = actor_half(agent.critic, agent.actor, s, c=c)     # the actor step, through the UPDATED critic
-    for k, p in agent.actor.named_parameters():
-        p.grad = half["grads"][k]
-    grads["actor"] = half["grads"]
-    agent.actor.optimizer.step()
-    agent.update_network_parameters()
-    z = dict(critic=tuple(t.detach() for t in z["critic"]), actor=half["z_actor"], critic_pi=half["z_pi"])
-    margin = torch.stack([t.abs().min(1).values for k in ("critic", "actor") for t in z[k]]).min(0).values
-    return dict(y=y, q=q.detach().view(-1), q_pi=half["q_pi"], dq_da=half["dq_da"], mu=half["mu"], pre=half["pre"], grads=grads,
-                nets={n: {k: v.detach().clone() for k, v in getattr(agent, n).state_dict().items()} for n in R.NETS},
-                m={n: R._moments(getattr(agent, n), "exp_avg") for n in ("actor", "critic")},
-                v={n: R._moments(getattr(agent, n), "exp_avg_sq") for n in ("actor", "critic")},
-                step=int(state["step"]) + 1, z=z, margin=margin, critic_loss=float(critic_loss.item()),
-                actor_loss=half["q_part"] + half["pen_part"])
-
-
 def shaped(case, huber, c):
-    """(state, hyper, batch, delta or None, shape_ref.ref_step's result) of a learn_ref case tuple with a shape; the batch is
+    """(state, hyper, batch, delta or None, learn_ref.ref_step's result) of a learn_ref case tuple with a shape; the batch is
     learn_ref.case's own (do not write to it)."""
     state, hyper, batch, ref, _ = R.case(*case)
     delta = delta_of(ref) if huber else None
-    return state, hyper, batch, delta, ref_step(state, batch, hyper, delta=delta, c=c)
+    return state, hyper, batch, delta, R.ref_step(state, batch, hyper, delta=delta, c=c)
 
 
 def saturated_state(state, batch, gain=13.0, bias=-18.5):

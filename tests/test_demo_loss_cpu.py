@@ -9,6 +9,7 @@ import pytest
 import torch
 
 import demo_ref as D
+import fake_args as F
 import learn_ref as R
 import shape_ref as S
 
@@ -63,7 +64,7 @@ def test_demo_ref_without_the_term_is_shape_refs_step_exactly():
     state, hyper, batch, ref, _ = R.case(*_CASE)
     delta = S.delta_of(ref)
     for lam, mask in ((0.0, None), (0.5, torch.zeros(_CASE[0], dtype=torch.bool))):
-        out, want = D.ref_step(state, batch, hyper, delta=delta, c=0.01, lam=lam, mask=mask), S.ref_step(state, batch, hyper, delta=delta, c=0.01)
+        out, want = D.ref_step(state, batch, hyper, delta=delta, c=0.01, lam=lam, mask=mask), R.ref_step(state, batch, hyper, delta=delta, c=0.01)
         for k in ("y", "q", "q_pi", "dq_da", "mu", "pre"):
             assert torch.equal(out[k], want[k]), k
         for name in R.NETS:
@@ -232,42 +233,10 @@ def lib():
     return L
 
 
-class _Fake:
-    """Plausible arguments of the two demonstration entry points over made-up device addresses: the library checks them on the host,
-    and with one bad argument nothing reaches the GPU."""
-
-    def __init__(self, L, B):
-        addr = iter(range(0x10000, 0x10000 + 0x1000 * 300, 0x1000))
-        nxt = self.nxt = lambda: next(addr)
-        self.B = B
-        self.critic, self.grads = (L.TTMlpWeights(*[nxt() for _ in range(12)], 23, 400, 300) for _ in range(2))
-        self.saved_a = L.TTMlpSaved(*[nxt() for _ in range(6)])
-        self.ws_a = L.TTMlpBwdWs(*[nxt() for _ in range(5)])
-        self.mu, self.obs, self.q_pi, self.dq_da, self.step, self.bias_corr, self.tail = (nxt() for _ in range(7))
-        self.tables = [(C.c_void_p * 10)(*[nxt() for _ in range(10)]) for _ in range(4)]
-        self.shape = L.TTLossShape(1.5, 0.01, nxt())
-        self.demo = L.TTDemoLoss(a=nxt(), idx=nxt(), q=nxt(), k=0.2, q_filter=1, dq_eff=nxt(), code=nxt())
-        self.count = 10
-        self.critic_flag = 1
-        self.with_shape = True
-
-    def fwd(self, L, demo=True):
-        return L.load().tt_mlp_forward_save_demo(self.B, self.critic_flag, self.obs, self.mu, C.byref(self.critic), self.q_pi, None,
-                                                 self.dq_da, C.byref(self.demo) if demo else None, None)
-
-    def tail_(self, L, demo=True):
-        p, m, v, t = self.tables
-        return L.load().tt_mlp_actor_tail_demo(
-            self.B, self.obs, self.mu, C.byref(self.critic), self.q_pi, self.dq_da, C.byref(self.saved_a), C.byref(self.ws_a),
-            C.byref(self.grads), -1.0 / max(1, self.B), self.count, p, m, v, t, self.step, 1e-4, 0.9, 0.999, 1e-8, 0.0, 1e-3, None,
-            self.bias_corr, self.tail, None, C.byref(self.shape) if self.with_shape else None, C.byref(self.demo) if demo else None, None)
-
-
 _ENTRY = dict(fwd="tt_mlp_forward_save_demo", tail_="tt_mlp_actor_tail_demo")
 
 
-def _set(obj, field, value):
-    return lambda f: setattr(getattr(f, obj), field, value)
+_set = F.set_field
 
 
 _COMMON = [("demo is NULL", None, False),
@@ -277,7 +246,7 @@ _COMMON = [("demo is NULL", None, False),
            ("NULL", _set("demo", "code", None), True), ("demo->q is NULL", _set("demo", "q", None), True),
            ("dq_eff is dq_da", lambda f: setattr(f.demo, "dq_eff", f.dq_da), True),
            ("dq_da is NULL", lambda f: setattr(f, "dq_da", None), True)]
-_FWD = [("actor", lambda f: setattr(f, "critic_flag", 0), True), ("n = -1", lambda f: setattr(f, "B", -1), True),
+_FWD = [("actor", lambda f: setattr(f, "fwd_critic", 0), True), ("n = -1", lambda f: setattr(f, "B", -1), True),
         ("obs", lambda f: setattr(f, "obs", None), True), ("action", lambda f: setattr(f, "mu", None), True),
         ("out", lambda f: setattr(f, "q_pi", None), True), ("weights", _set("critic", "wa", None), True),
         ("weights", _set("critic", "fc2_dims", 301), True)]
@@ -298,11 +267,11 @@ _REFUSALS = [(e, *r) for e, rs in (("fwd", _COMMON + _FWD), ("tail_", _COMMON + 
 def test_demo_entry_points_check_their_arguments_before_any_hip_call(lib, entry, word, spoil, with_demo):
     """TT_EINVAL and a message that starts with the entry point's name and names the argument, for one spoiled argument at a time."""
     L = lib
-    f = _Fake(L, 256)
+    f = F.Fake(L, 256, "demo")
     if spoil is not None:
         spoil(f)
-    rc = getattr(f, entry)(L, demo=with_demo)
-    msg = L.load().tt_last_error(None).decode()
+    f.with_demo = with_demo
+    rc, msg = getattr(f, entry)(), f.last_error()
     assert rc == L.TT_EINVAL, (rc, msg)
     assert msg.startswith(_ENTRY[entry] + ":") and word in msg, msg
 
@@ -311,11 +280,10 @@ def test_q_may_be_null_without_the_filter_and_the_shape_may_be_null(lib):
     """q NULL is refused only with q_filter; a NULL shape is allowed in the tail (the refusal then met is the next spoiled argument's)."""
     L = lib
     for entry in ("fwd", "tail_"):
-        f = _Fake(L, 256)
+        f = F.Fake(L, 256, "demo")
         f.demo.q, f.demo.q_filter, f.with_shape = None, 0, False
         f.obs = None
-        rc = getattr(f, entry)(L)
-        msg = L.load().tt_last_error(None).decode()
+        rc, msg = getattr(f, entry)(), f.last_error()
         assert rc == L.TT_EINVAL and msg.startswith(_ENTRY[entry] + ":") and "obs" in msg and "demo->q" not in msg, msg
 
 

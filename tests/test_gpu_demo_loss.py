@@ -38,39 +38,19 @@ import math
 import pytest
 
 import demo_ref as D
+import learn_checks as K
 import learn_ref as R
 import shape_ref as S
-from test_gpu_learn_shapes import _ACTOR_NAMES, _CRITIC_NAMES, _scratch_image, _ulp32
-from test_gpu_loss_shape import _flat, _results, _same
 
 pytestmark = pytest.mark.gpu
 
-
-def _id(case):
-    return "B{}-x{:g}".format(case[0], case[1])
+_id = K.case_id
+_learner, _results, _same, _flat, _shape = K.learner, K.results, K.same, K.flat, K.loss_shape
 
 
 def _demo(lam, q_filter=True):
     from ddpg_trucktrailer_amd.demo_loss import DemoLoss
     return DemoLoss(lam, q_filter)
-
-
-def _shape(delta, c):
-    from ddpg_trucktrailer_amd.loss_shape import LossShape
-    return LossShape(delta, c)
-
-
-def _learner(dev, state, hyper, batch, step, images=True, shape=None, tail=False, demo=None):
-    """(agent, FusedLearner, batch on the device) holding `state`: f32 nets, Adam moments and step count."""
-    import torch
-    from ddpg_trucktrailer_amd.fused_learn import FusedLearner
-    agent = R.load_agent(state, hyper, dev, torch.float32)
-    fl = FusedLearner(agent, batch[0].shape[0], fc2_images=images, loss_shape=shape, demo_loss=demo)
-    fl.import_from_optimizers()
-    fl.refresh_images()
-    fl.fuse_tail = tail
-    assert fl.use_images == images and int(fl.step_dev.item()) == step
-    return agent, fl, [t.to(dev).contiguous() for t in batch]
 
 
 def _ring_index(B, dev):
@@ -119,130 +99,6 @@ def _case(case, lam, q_filter, huber, c):
     return D.demo_case(case, lam, q_filter, huber, c)
 
 
-def _against_f64(dev, state, hyper, batch, ref, lam, q_filter, delta, c, images, tag, frozen=()):
-    """test_gpu_learn_shapes.test_one_learn_step_against_f64's checks, bounds unchanged, for a learner with DemoLoss(lam, q_filter) [and
-    LossShape(delta, c)] against demo_ref; plus code (the reference's except on undecided rows, where either is accepted and the
-    reference gradient is formed with the learner's choice) and dq_eff within 2e-5 max(1, max |ref|).  frozen: names of critic tensors
-    the step cannot move.  Returns (worst ratios, the learner, the f64 actor half, dq64)."""
-    import torch
-    B, step0 = batch[0].shape[0], state["step"]
-    shape = _shape(delta, c) if (delta is not None or c) else None
-    h32 = R.f32_hyper(hyper)
-    mask = ref["demo"]
-    idx = D.demo_index(B, dev)
-    assert torch.equal(idx[:, 0].cpu() < 0, mask)
-    agent, fl, (s, a, r, s2, d8) = _learner(dev, state, hyper, batch, step0, images, shape, demo=_demo(lam, q_filter))
-    twin = R.load_agent(state, hyper, dev, torch.float32)
-    twin.loss_shape = shape
-    before = {st: dict(p=[x.detach().clone() for x in st.params], t=[x.detach().clone() for x in st.targets],
-                       m=[x.clone() for x in st.ms], v=[x.clone() for x in st.vs]) for st in (fl.critic, fl.actor)}
-    fl.learn_batch(s, a, r, s2, d8, demo_index=idx)
-    torch.cuda.synchronize()
-    worst = {}
-
-    def check(name, err, tol):
-        ratio = (err / tol).max().item() if torch.is_tensor(err) else err / tol
-        worst[name] = max(worst.get(name, 0.0), ratio)
-        assert ratio <= 1.0, (tag, name, B, ratio)
-
-    # ---- no unit changes side
-    for st, key in ((fl.critic, "critic"), (fl.actor, "actor")):
-        sd = {k: v.to(dev).double() for k, v in state["nets"][key].items()}
-        z1 = st.saved_t["xh1"].double() * sd["bn1.weight"] + sd["bn1.bias"]
-        z2 = st.saved_t["xh2"].double() * sd["bn2.weight"] + sd["bn2.bias"]
-        if st.critic:
-            z2 = z2 + a.double().view(-1, 1) * sd["action_value.weight"].view(1, -1) + sd["action_value.bias"]
-        for got, want in zip((z1, z2), ref["z"][key]):
-            check("pre-relu", (got.cpu() - want).abs().max().item(), R.MARGIN / 3)
-    # ---- outputs
-    done = d8.bool()
-    assert torch.equal(fl.y[done], r[done])
-    for name in ("y", "q"):
-        check(name, (getattr(fl, name).double().cpu() - ref[name]).abs().max().item(), 2e-5 * max(1.0, ref[name].abs().max().item()))
-    nets = dict(state["nets"], critic={k: v.detach().cpu() for k, v in agent.critic.state_dict().items()})
-    a64 = R.load_agent(dict(state, nets=nets), hyper, torch.device("cpu"), torch.float64)
-    s64, act64 = s.double().cpu(), a.double().cpu()
-    half = D.actor_half(a64.critic, a64.actor, s64, act64, c=c)
-    check("q_pi", (fl.q_pi.double().cpu() - half["q_pi"]).abs().max().item(), 2e-5 * max(1.0, half["q_pi"].abs().max().item()))
-    got_dq, dq64 = fl.dq_da.double().cpu(), half["dq_da"].clone()
-    choices = R.dq_da_choices(a64.critic, half["z_pi"][1], half["dq_da"])
-    for b, values in choices.items():
-        dq64[b] = min(values, key=lambda x: abs(x - got_dq[b].item()))
-    check("dq_da", (got_dq - dq64).abs().max().item(), 2e-5 * max(1.0, dq64.abs().max().item()))     # (dq_da stays the TRUE derivative)
-    if shape is not None:
-        check("pre", (fl.pre.double().cpu() - half["pre"]).abs().max().item(), 2e-5 * max(1.0, half["pre"].abs().max().item()))
-    # ---- the filter: q of the critic before its step against q_pi through the critic the learner left
-    filt = D.filter_of(ref["q"], half["q_pi"], mask)
-    want_code = D.codes(mask, filt["above"] if q_filter else mask)
-    code = fl.code.cpu()
-    und = filt["undecided"] if q_filter else torch.zeros_like(mask)
-    assert int(und.sum()) <= D.MAX_UNDECIDED * int(mask.sum()) or B < 33, (tag, int(und.sum()))
-    assert torch.equal(code[~und], want_code[~und]), (tag, "code")
-    assert bool(((code[und] == 1) | (code[und] == 2)).all())
-    applied = code == 2
-    # ---- gradients at both optimizer sites, the actor's with the rows the learner applied
-    half_dq = D.actor_half(a64.critic, a64.actor, s64, act64, dq_da=dq64, c=c, lam=lam, applied=applied)
-    check("dq_eff", (fl.dq_eff.double().cpu() - half_dq["dq_eff"]).abs().max().item(), 2e-5 * max(1.0, half_dq["dq_eff"].abs().max().item()))
-    assert torch.equal(fl.dq_eff[~applied.to(dev)], fl.dq_da[~applied.to(dev)])          # (a row without the term keeps dQ/da's bits)
-    g64 = dict(critic=ref["grads"]["critic"], actor=half_dq["grads"])
-    g32 = dict(actor=D.actor_half(twin.critic, twin.actor, s, a, dq_da=dq64.to(dev), c=c, lam=lam, applied=applied.to(dev))["grads"])
-    seen, orig = {}, twin.critic.optimizer.step
-
-    def step(*args, **kw):
-        seen.update({k: p.grad.clone() for k, p in twin.critic.named_parameters()})
-        return orig(*args, **kw)
-    twin.critic.optimizer.step = step
-    twin.learn_batch(s, a, r, s2, done)
-    g32["critic"] = seen
-    for st, key, names in ((fl.critic, "critic", _CRITIC_NAMES), (fl.actor, "actor", _ACTOR_NAMES)):
-        assert len(st.grads) == len(names) == len(g64[key])
-        for name, g in zip(names, st.grads):
-            want = g64[key][name]
-            e32 = (g32[key][name].double().cpu() - want).abs().max().item()
-            tol = max(3e-5 * want.abs().max().item() + 1e-7, 3 * e32)
-            check("grad " + key, (g.double().cpu() - want).abs().max().item(), tol)
-            worst["e32 share " + key] = max(worst.get("e32 share " + key, 0.0), 3 * e32 / (3e-5 * want.abs().max().item() + 1e-7))
-    # ---- optimizer arithmetic at the kernel's own gradient
-    t = step0 + 1
-    assert int(fl.step_dev.item()) == t
-    for st, key, names in ((fl.critic, "critic", _CRITIC_NAMES), (fl.actor, "actor", _ACTOR_NAMES)):
-        h = R.net_hyper(h32, key)
-        b1 = h["betas"][0]
-        for i in range(len(st.params)):
-            p0, m0, v0, t0 = (before[st][k][i].double().reshape(-1) for k in ("p", "m", "v", "t"))
-            g = st.grads[i].double().reshape(-1)
-            p64, m64, v64, _, g2 = R.adam64(p0, m0, v0, t0, g, t, h)
-            p, m, v, tg = (x.detach().double().reshape(-1) for x in (st.params[i], st.ms[i], st.vs[i], st.targets[i]))
-            terms = (b1 * m0).abs() + ((1 - b1) * g2).abs()
-            check("adam m " + key, (m - m64).abs(), (4 * 2.0 ** -24 * terms).clamp_min(2.0 ** -149))
-            check("adam v " + key, (v - v64).abs(), 6 * 2.0 ** -24 * v64 + 2.0 ** -149)
-            kappa = terms / m64.abs().clamp_min(1e-300)
-            rel = ((18 + 6 * kappa) * 2.0 ** -24).clamp_min(2.0 ** -19)
-            check("adam p " + key, (p - p64).abs(), _ulp32(p64) + rel * (p64 - p0).abs())
-            tg64 = R.soft64(t0, p, h["tau"])
-            check("target " + key, (tg - tg64).abs(), 2 * _ulp32(tg64))
-            if not (key == "critic" and names[i] in frozen):
-                assert not torch.equal(p, p0), (key, i)                                          # the step moved the tensor
-    # ---- images
-    if images:
-        fwd = 2 * 20 * 13 * 512
-        assert fl.images_current()
-        for net in (agent.actor, agent.critic, agent.target_actor, agent.target_critic):
-            kept, fresh = fl._img[id(net)], _scratch_image(fl, net, dev)
-            if net in (agent.target_actor, agent.target_critic):
-                assert torch.equal(kept.view(torch.float16)[:fwd], fresh.view(torch.float16)[:fwd]), "target image differs"
-            else:
-                assert torch.equal(kept, fresh), "maintained image differs from one made from scratch"
-    # ---- demo_stats of this update
-    st = fl.demo_stats()
-    assert st["demo_rows"] == int(mask.sum()) and st["applied"] == int(applied.sum())
-    assert abs(st["bc_loss"] - half_dq["bc_part"]) <= 1e-5 * max(1e-3, abs(half_dq["bc_part"]))
-    print(f"RATIOS {tag} {'images' if images else 'f32'}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()) +
-          f", rows near a boundary in Q(s, mu(s)) {len(choices)}, demonstration rows {int(mask.sum())}, applied {int(applied.sum())}, "
-          f"undecided {int(und.sum())}")
-    return worst, fl, half_dq, dq64
-
-
 _F64 = [(case, lam, qf, False, 0.0, True) for case in D.F64_CASES for lam, qf in D.DEMOS] + \
        [(D.OFF_CASES[1], 0.1, True, True, 0.01, True), (D.F64_CASES[2], 10.0, True, False, 0.0, False)]
 
@@ -258,7 +114,7 @@ def test_one_demo_learn_step_against_f64(gpu_device, case, lam, q_filter, huber,
     except on undecided rows; dq_da stays the true derivative; dq_eff within 2e-5 max(1, max |ref|)."""
     state, hyper, batch, delta, ref = _case(case, lam, q_filter, huber, c)
     tag = f"B{case[0]} x{case[1]:g} lam={lam:g} {'filter' if q_filter else 'all'}{' huber c=%g' % c if huber else ''}"
-    _, fl, _, _ = _against_f64(gpu_device, state, hyper, batch, ref, lam, q_filter, delta, c, images, tag)
+    _, fl, _, _ = K.against_f64(gpu_device, state, hyper, batch, ref, delta=delta, c=c, demo=_demo(lam, q_filter), images=images, tag=tag)
     if case[0] >= 33:
         assert int((fl.code == 2).sum().item()) >= 1 and (not q_filter or int((fl.code == 1).sum().item()) >= 1)
 
@@ -283,8 +139,8 @@ def test_a_critic_without_dq_da_learns_the_actor_only_from_demonstrations(gpu_de
     assert bool((plain.dq_da == 0).all()) and bool((plain.actor.flat_grad == 0).all())
     assert not bool((plain.critic.flat_grad == 0).all())
     ref = D.ref_step(state, batch, hyper, lam=lam)
-    _, fl, half_dq, _ = _against_f64(dev, state, hyper, batch, ref, lam, True, None, 0.0, True, "zero dQ/da lam=0.1",
-                                     frozen=("action_value.weight",))
+    _, fl, half_dq, _ = K.against_f64(dev, state, hyper, batch, ref, demo=_demo(lam), images=True, tag="zero dQ/da lam=0.1",
+                                      frozen=("action_value.weight",))
     assert bool((fl.dq_da == 0).all()) and torch.equal(fl.mu, plain.mu)
     code = fl.code.clone()
     n0, n1, n2 = (int((code == k).sum().item()) for k in (0, 1, 2))

@@ -16,7 +16,8 @@ import numpy as np
 import pytest
 
 import learn_ref as R
-from test_gpu_learn_shapes import _learner, _ring_with_batch
+from learn_checks import ring_with_batch as _ring_with_batch
+from test_gpu_learn_shapes import _learner
 
 pytestmark = pytest.mark.gpu
 

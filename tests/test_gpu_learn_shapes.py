@@ -34,52 +34,22 @@ weight gradient rounded differently per launch path from 257 rows on (csrc/ttlea
 of dW2 cut to one iteration the f64 test fails at B = 1000 and 1024 (critic gradient 18000 to 26000 times its bound) and passes
 at B <= 257.
 """
-import ctypes as C
 import math
 
 import pytest
 
+import learn_checks as K
 import learn_ref as R
 
 pytestmark = pytest.mark.gpu
 
-_CRITIC_NAMES = ["fc1.weight", "fc1.bias", "bn1.weight", "bn1.bias", "fc2.weight", "fc2.bias", "bn2.weight", "bn2.bias", "q.weight",
-                 "q.bias", "action_value.weight", "action_value.bias"]
-_ACTOR_NAMES = _CRITIC_NAMES[:8] + ["mu.weight", "mu.bias"]          # the order of FusedLearner's gradient views (tt_mlp_weights)
-
-
-def _id(case):
-    return "B{}-x{:g}".format(case[0], case[1])
+_id = K.case_id
 
 
 def _learner(dev, case, images):
     """(agent, FusedLearner, batch on the device) holding the case's state: f32 nets, Adam moments and step count."""
-    import torch
-    from ddpg_trucktrailer_amd.fused_learn import FusedLearner
     state, hyper, batch, _, _ = R.case(*case)
-    agent = R.load_agent(state, hyper, dev, torch.float32)
-    fl = FusedLearner(agent, case[0], fc2_images=images)
-    fl.import_from_optimizers()
-    fl.refresh_images()
-    assert fl.use_images == images and int(fl.step_dev.item()) == case[3]
-    return agent, fl, [t.to(dev).contiguous() for t in batch]
-
-
-def _ulp32(x64):
-    import torch
-    x = x64.float().abs()
-    return (torch.nextafter(x, torch.full_like(x, float("inf"))) - x).double()
-
-
-def _scratch_image(fl, net, dev):
-    import torch
-    from ddpg_trucktrailer_amd import _lib as L
-    w = L.TTMlpWeights()
-    C.memmove(C.byref(w), C.byref(fl.w(net)), C.sizeof(w))
-    img = torch.zeros(int(fl.lib.tt_mlp_fc2_image_bytes()), dtype=torch.uint8, device=dev)
-    w.fc2_img = img.data_ptr()
-    L.check(fl.lib.tt_mlp_fc2_image_pack(C.byref(w), C.c_void_p(torch.cuda.current_stream().cuda_stream)))
-    return img
+    return K.learner(dev, state, hyper, batch, case[3], images)
 
 
 @pytest.mark.parametrize("images", [True, False], ids=["images", "f32"])
@@ -109,127 +79,8 @@ def test_one_learn_step_against_f64(gpu_device, case, images):
     it is for kappa <= 2.3 (always, from zero moments); the last subtraction rounds p once more.
     Step count + 1; with images, each of the four fc2 images equals one packed from scratch, bit for bit (a target's over its forward
     planes only)."""
-    import torch
-    dev = gpu_device
-    B, step0 = case[0], case[3]
-    state, hyper, _, ref, _ = R.case(*case)
-    h32 = R.f32_hyper(hyper)
-    agent, fl, (s, a, r, s2, d8) = _learner(dev, case, images)
-    twin = R.load_agent(state, hyper, dev, torch.float32)
-    before = {st: dict(p=[x.detach().clone() for x in st.params], t=[x.detach().clone() for x in st.targets],
-                       m=[x.clone() for x in st.ms], v=[x.clone() for x in st.vs]) for st in (fl.critic, fl.actor)}
-    fl.learn_batch(s, a, r, s2, d8)
-    torch.cuda.synchronize()
-    worst = {}
-
-    def check(name, err, tol):
-        ratio = (err / tol).max().item() if torch.is_tensor(err) else err / tol
-        worst[name] = max(worst.get(name, 0.0), ratio)
-        assert ratio <= 1.0, (name, B, ratio)
-
-    # ---- no unit changes side
-    for st, key in ((fl.critic, "critic"), (fl.actor, "actor")):
-        sd = {k: v.to(dev).double() for k, v in state["nets"][key].items()}
-        z1 = st.saved_t["xh1"].double() * sd["bn1.weight"] + sd["bn1.bias"]
-        z2 = st.saved_t["xh2"].double() * sd["bn2.weight"] + sd["bn2.bias"]
-        if st.critic:
-            z2 = z2 + a.double().view(-1, 1) * sd["action_value.weight"].view(1, -1) + sd["action_value.bias"]
-        for got, want in zip((z1, z2), ref["z"][key]):
-            check("pre-relu", (got.cpu() - want).abs().max().item(), R.MARGIN / 3)
-    # ---- outputs
-    done = d8.bool()
-    assert torch.equal(fl.y[done], r[done])
-    for name in ("y", "q"):
-        check(name, (getattr(fl, name).double().cpu() - ref[name]).abs().max().item(), 2e-5 * max(1.0, ref[name].abs().max().item()))
-    # the third forward, in f64 on the critic this learn() left
-    nets = dict(state["nets"], critic={k: v.detach().cpu() for k, v in agent.critic.state_dict().items()})
-    a64 = R.load_agent(dict(state, nets=nets), hyper, torch.device("cpu"), torch.float64)
-    s64 = s.double().cpu()
-    half = R.actor_half(a64.critic, a64.actor, s64)
-    check("q_pi", (fl.q_pi.double().cpu() - half["q_pi"]).abs().max().item(), 2e-5 * max(1.0, half["q_pi"].abs().max().item()))
-    got_dq, dq64 = fl.dq_da.double().cpu(), half["dq_da"].clone()
-    choices = R.dq_da_choices(a64.critic, half["z_pi"][1], half["dq_da"])
-    for b, values in choices.items():
-        dq64[b] = min(values, key=lambda x: abs(x - got_dq[b].item()))
-    other_side = sum(1 for b in choices if dq64[b] != half["dq_da"][b])
-    check("dq_da", (got_dq - dq64).abs().max().item(), 2e-5 * max(1.0, dq64.abs().max().item()))
-    # ---- gradients at both optimizer sites
-    g64 = dict(critic=ref["grads"]["critic"], actor=R.actor_half(a64.critic, a64.actor, s64, dq_da=dq64)["grads"])
-    g32 = dict(actor=R.actor_half(twin.critic, twin.actor, s, dq_da=dq64.to(dev))["grads"])
-    seen, orig = {}, twin.critic.optimizer.step
-
-    def step(*args, **kw):
-        seen.update({k: p.grad.clone() for k, p in twin.critic.named_parameters()})
-        return orig(*args, **kw)
-    twin.critic.optimizer.step = step
-    twin.learn_batch(s, a, r, s2, done)
-    g32["critic"] = seen
-    for st, key, names in ((fl.critic, "critic", _CRITIC_NAMES), (fl.actor, "actor", _ACTOR_NAMES)):
-        assert len(st.grads) == len(names) == len(g64[key])
-        for name, g in zip(names, st.grads):
-            want = g64[key][name]
-            e32 = (g32[key][name].double().cpu() - want).abs().max().item()
-            tol = max(3e-5 * want.abs().max().item() + 1e-7, 3 * e32)
-            check("grad " + key, (g.double().cpu() - want).abs().max().item(), tol)
-            worst["e32 share " + key] = max(worst.get("e32 share " + key, 0.0), 3 * e32 / (3e-5 * want.abs().max().item() + 1e-7))
-    # ---- optimizer arithmetic at the kernel's own gradient
-    t = step0 + 1
-    assert int(fl.step_dev.item()) == t
-    for st, key in ((fl.critic, "critic"), (fl.actor, "actor")):
-        h = R.net_hyper(h32, key)
-        b1 = h["betas"][0]
-        for i in range(len(st.params)):
-            p0, m0, v0, t0 = (before[st][k][i].double().reshape(-1) for k in ("p", "m", "v", "t"))
-            g = st.grads[i].double().reshape(-1)
-            p64, m64, v64, _, g2 = R.adam64(p0, m0, v0, t0, g, t, h)
-            p, m, v, tg = (x.detach().double().reshape(-1) for x in (st.params[i], st.ms[i], st.vs[i], st.targets[i]))
-            terms = (b1 * m0).abs() + ((1 - b1) * g2).abs()
-            check("adam m " + key, (m - m64).abs(), (4 * 2.0 ** -24 * terms).clamp_min(2.0 ** -149))
-            check("adam v " + key, (v - v64).abs(), 6 * 2.0 ** -24 * v64 + 2.0 ** -149)
-            kappa = terms / m64.abs().clamp_min(1e-300)
-            rel = ((18 + 6 * kappa) * 2.0 ** -24).clamp_min(2.0 ** -19)
-            check("adam p " + key, (p - p64).abs(), _ulp32(p64) + rel * (p64 - p0).abs())
-            flat = ((p - p64).abs() / (_ulp32(p64) + 2.0 ** -19 * (p64 - p0).abs())).max().item()       # (a figure, not a check)
-            worst["p at 2^-19 without kappa " + key] = max(worst.get("p at 2^-19 without kappa " + key, 0.0), flat)
-            worst["kappa " + key] = max(worst.get("kappa " + key, 0.0), kappa[terms > 0].max().item() if (terms > 0).any() else 0.0)
-            tg64 = R.soft64(t0, p, h["tau"])
-            check("target " + key, (tg - tg64).abs(), 2 * _ulp32(tg64))
-            assert not torch.equal(p, p0), (key, i)                                              # the step moved the tensor
-    # ---- images
-    if images:
-        fwd = 2 * 20 * 13 * 512                              # halves of the two forward planes (test_fc2_images_follow_the_weights)
-        assert fl.images_current()
-        for net in (agent.actor, agent.critic, agent.target_actor, agent.target_critic):
-            kept, fresh = fl._img[id(net)], _scratch_image(fl, net, dev)
-            if net in (agent.target_actor, agent.target_critic):
-                assert torch.equal(kept.view(torch.float16)[:fwd], fresh.view(torch.float16)[:fwd]), "target image differs"
-            else:
-                assert torch.equal(kept, fresh), "maintained image differs from one made from scratch"
-    print(f"RATIOS {_id(case)} {'images' if images else 'f32'}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()) +
-          f", rows near a boundary in Q(s, mu(s)) {len(choices)} (other side: {other_side})")
-
-
-def _ring_with_batch(dev, B, batch):
-    """A ring of one stored step whose draw with `seed` IS the batch, in order (as tests/test_gpu_population.py lays out F5's): with
-    2^20 envs the first seed of a short list whose B rows pick distinct envs."""
-    import torch
-    from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
-    s, a, r, s2, d8 = batch
-    ring = TrajectoryRing(1 << 20, 3, 23, dev)
-    ring.k = 1
-    ring.k_dev.fill_(1)
-    for seed in range(4242, 4242 + 32):
-        idx = ring.sample_fused(B, seed=seed, return_index=True)[-1]
-        env = idx[:, 1].long()
-        if env.unique().numel() == B:
-            break
-    assert idx[:, 0].eq(0).all() and env.unique().numel() == B
-    ring.obs[0, env] = s
-    ring.obs[1, env] = s2
-    ring.act[0, env] = a.view(-1)
-    ring.rew[0, env] = r
-    ring.done[0, env] = d8
-    return ring, seed
+    state, hyper, batch, ref, _ = R.case(*case)
+    K.against_f64(gpu_device, state, hyper, batch, ref, images=images, tag=_id(case))
 
 
 def _results(fl):
@@ -269,7 +120,7 @@ def test_learn_paths_agree_bitwise_at_every_batch(gpu_device, case):
             assert rows[:, 1].eq(step0 + 2).all() and torch.equal(rows[:, 0].contiguous().view(torch.float32), fl.dq_da.cpu())
             assert fl.tail_words[64 + 2 * B:].eq(-1).all()
         runs[how] = _results(fl)
-    rings = [_ring_with_batch(dev, B, batch) for _ in range(2)]
+    rings = [K.ring_with_batch(dev, B, batch) for _ in range(2)]
     agents = [R.load_agent(state, hyper, dev, torch.float32) for _ in range(2)]
     pop = PopulationLearner(agents, B, fc2_images=True, rings=[ring for ring, _ in rings], seeds=[seed for _, seed in rings])
     for fl in pop.learners:

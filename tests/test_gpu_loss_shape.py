@@ -40,47 +40,15 @@ import math
 
 import pytest
 
+import learn_checks as K
 import learn_ref as R
 import shape_ref as S
-from test_gpu_learn_shapes import _ACTOR_NAMES, _CRITIC_NAMES, _ring_with_batch, _scratch_image, _ulp32
 
 pytestmark = pytest.mark.gpu
 
-
-def _id(case):
-    return "B{}-x{:g}".format(case[0], case[1])
-
-
-def _shape(delta, c):
-    from ddpg_trucktrailer_amd.loss_shape import LossShape
-    return LossShape(delta, c)
-
-
-def _learner(dev, state, hyper, batch, step, images=True, shape=None, tail=False):
-    """(agent, FusedLearner, batch on the device) holding `state`: f32 nets, Adam moments and step count."""
-    import torch
-    from ddpg_trucktrailer_amd.fused_learn import FusedLearner
-    agent = R.load_agent(state, hyper, dev, torch.float32)
-    fl = FusedLearner(agent, batch[0].shape[0], fc2_images=images, loss_shape=shape)
-    fl.import_from_optimizers()
-    fl.refresh_images()
-    fl.fuse_tail = tail
-    assert fl.use_images == images and int(fl.step_dev.item()) == step
-    return agent, fl, [t.to(dev).contiguous() for t in batch]
-
-
-def _results(fl):
-    ag = fl.agent
-    out = [p.detach().clone() for n in (ag.actor, ag.critic, ag.target_actor, ag.target_critic) for p in n.parameters()]
-    return out + [t.clone() for t in (fl.actor.m, fl.actor.v, fl.critic.m, fl.critic.v, fl.actor.flat_grad, fl.critic.flat_grad,
-                                      fl.y, fl.q, fl.q_pi, fl.dq_da, fl.step_dev)]
-
-
-def _same(a, b, what):
-    import torch
-    assert len(a) == len(b)
-    for i, (x, y) in enumerate(zip(a, b)):
-        assert torch.equal(x, y), (what, i)
+_id = K.case_id
+_ACTOR_NAMES, _learner, _results, _same, _flat, _ring_with_batch = K.ACTOR_NAMES, K.learner, K.results, K.same, K.flat, K.ring_with_batch
+_shape = K.loss_shape
 
 
 # ---- off equals today ---------------------------------------------------------------------------------------------------
@@ -114,108 +82,6 @@ def _shaped(case, huber, c):
     return S.shaped(case, huber, c)
 
 
-def _against_f64(dev, state, hyper, batch, ref, delta, c, images, tag):
-    """test_gpu_learn_shapes.test_one_learn_step_against_f64's checks, bounds unchanged, for a learner with LossShape(delta, c) against
-    shape_ref; plus pre within 2e-5 max(1, max |pre64|).  Returns (worst ratios, the learner, the f64 actor half, dq64)."""
-    import torch
-    B, step0 = batch[0].shape[0], state["step"]
-    shape = _shape(delta, c)
-    h32 = R.f32_hyper(hyper)
-    agent, fl, (s, a, r, s2, d8) = _learner(dev, state, hyper, batch, step0, images, shape)
-    twin = R.load_agent(state, hyper, dev, torch.float32)
-    twin.loss_shape = shape
-    before = {st: dict(p=[x.detach().clone() for x in st.params], t=[x.detach().clone() for x in st.targets],
-                       m=[x.clone() for x in st.ms], v=[x.clone() for x in st.vs]) for st in (fl.critic, fl.actor)}
-    fl.learn_batch(s, a, r, s2, d8)
-    torch.cuda.synchronize()
-    worst = {}
-
-    def check(name, err, tol):
-        ratio = (err / tol).max().item() if torch.is_tensor(err) else err / tol
-        worst[name] = max(worst.get(name, 0.0), ratio)
-        assert ratio <= 1.0, (tag, name, B, ratio)
-
-    # ---- no unit changes side
-    for st, key in ((fl.critic, "critic"), (fl.actor, "actor")):
-        sd = {k: v.to(dev).double() for k, v in state["nets"][key].items()}
-        z1 = st.saved_t["xh1"].double() * sd["bn1.weight"] + sd["bn1.bias"]
-        z2 = st.saved_t["xh2"].double() * sd["bn2.weight"] + sd["bn2.bias"]
-        if st.critic:
-            z2 = z2 + a.double().view(-1, 1) * sd["action_value.weight"].view(1, -1) + sd["action_value.bias"]
-        for got, want in zip((z1, z2), ref["z"][key]):
-            check("pre-relu", (got.cpu() - want).abs().max().item(), R.MARGIN / 3)
-    # ---- outputs
-    done = d8.bool()
-    assert torch.equal(fl.y[done], r[done])
-    for name in ("y", "q"):
-        check(name, (getattr(fl, name).double().cpu() - ref[name]).abs().max().item(), 2e-5 * max(1.0, ref[name].abs().max().item()))
-    nets = dict(state["nets"], critic={k: v.detach().cpu() for k, v in agent.critic.state_dict().items()})
-    a64 = R.load_agent(dict(state, nets=nets), hyper, torch.device("cpu"), torch.float64)
-    s64 = s.double().cpu()
-    half = S.actor_half(a64.critic, a64.actor, s64, c=c)
-    check("q_pi", (fl.q_pi.double().cpu() - half["q_pi"]).abs().max().item(), 2e-5 * max(1.0, half["q_pi"].abs().max().item()))
-    got_dq, dq64 = fl.dq_da.double().cpu(), half["dq_da"].clone()
-    choices = R.dq_da_choices(a64.critic, half["z_pi"][1], half["dq_da"])
-    for b, values in choices.items():
-        dq64[b] = min(values, key=lambda x: abs(x - got_dq[b].item()))
-    check("dq_da", (got_dq - dq64).abs().max().item(), 2e-5 * max(1.0, dq64.abs().max().item()))
-    # the head's pre-activation as the rows launch recomputed it: a head output of the same dot product
-    check("pre", (fl.pre.double().cpu() - half["pre"]).abs().max().item(), 2e-5 * max(1.0, half["pre"].abs().max().item()))
-    # ---- gradients at both optimizer sites
-    half_dq = S.actor_half(a64.critic, a64.actor, s64, dq_da=dq64, c=c)
-    g64 = dict(critic=ref["grads"]["critic"], actor=half_dq["grads"])
-    g32 = dict(actor=S.actor_half(twin.critic, twin.actor, s, dq_da=dq64.to(dev), c=c)["grads"])
-    seen, orig = {}, twin.critic.optimizer.step
-
-    def step(*args, **kw):
-        seen.update({k: p.grad.clone() for k, p in twin.critic.named_parameters()})
-        return orig(*args, **kw)
-    twin.critic.optimizer.step = step
-    twin.learn_batch(s, a, r, s2, done)
-    g32["critic"] = seen
-    for st, key, names in ((fl.critic, "critic", _CRITIC_NAMES), (fl.actor, "actor", _ACTOR_NAMES)):
-        assert len(st.grads) == len(names) == len(g64[key])
-        for name, g in zip(names, st.grads):
-            want = g64[key][name]
-            e32 = (g32[key][name].double().cpu() - want).abs().max().item()
-            tol = max(3e-5 * want.abs().max().item() + 1e-7, 3 * e32)
-            check("grad " + key, (g.double().cpu() - want).abs().max().item(), tol)
-            worst["e32 share " + key] = max(worst.get("e32 share " + key, 0.0), 3 * e32 / (3e-5 * want.abs().max().item() + 1e-7))
-    # ---- optimizer arithmetic at the kernel's own gradient
-    t = step0 + 1
-    assert int(fl.step_dev.item()) == t
-    for st, key in ((fl.critic, "critic"), (fl.actor, "actor")):
-        h = R.net_hyper(h32, key)
-        b1 = h["betas"][0]
-        for i in range(len(st.params)):
-            p0, m0, v0, t0 = (before[st][k][i].double().reshape(-1) for k in ("p", "m", "v", "t"))
-            g = st.grads[i].double().reshape(-1)
-            p64, m64, v64, _, g2 = R.adam64(p0, m0, v0, t0, g, t, h)
-            p, m, v, tg = (x.detach().double().reshape(-1) for x in (st.params[i], st.ms[i], st.vs[i], st.targets[i]))
-            terms = (b1 * m0).abs() + ((1 - b1) * g2).abs()
-            check("adam m " + key, (m - m64).abs(), (4 * 2.0 ** -24 * terms).clamp_min(2.0 ** -149))
-            check("adam v " + key, (v - v64).abs(), 6 * 2.0 ** -24 * v64 + 2.0 ** -149)
-            kappa = terms / m64.abs().clamp_min(1e-300)
-            rel = ((18 + 6 * kappa) * 2.0 ** -24).clamp_min(2.0 ** -19)
-            check("adam p " + key, (p - p64).abs(), _ulp32(p64) + rel * (p64 - p0).abs())
-            tg64 = R.soft64(t0, p, h["tau"])
-            check("target " + key, (tg - tg64).abs(), 2 * _ulp32(tg64))
-            assert not torch.equal(p, p0), (key, i)                                              # the step moved the tensor
-    # ---- images
-    if images:
-        fwd = 2 * 20 * 13 * 512
-        assert fl.images_current()
-        for net in (agent.actor, agent.critic, agent.target_actor, agent.target_critic):
-            kept, fresh = fl._img[id(net)], _scratch_image(fl, net, dev)
-            if net in (agent.target_actor, agent.target_critic):
-                assert torch.equal(kept.view(torch.float16)[:fwd], fresh.view(torch.float16)[:fwd]), "target image differs"
-            else:
-                assert torch.equal(kept, fresh), "maintained image differs from one made from scratch"
-    print(f"RATIOS {tag} {'images' if images else 'f32'}: " + ", ".join(f"{k} {v:.3g}" for k, v in worst.items()) +
-          f", rows near a boundary in Q(s, mu(s)) {len(choices)}")
-    return worst, fl, half_dq, dq64
-
-
 _F64 = [(case, huber, c, True) for case in S.F64_CASES for huber, c in S.SHAPES] + [(case, True, 1.0, False) for case in S.F64_CASES]
 
 
@@ -226,7 +92,7 @@ def test_one_shaped_learn_step_against_f64(gpu_device, case, huber, c, images):
     reference: half the rows on each side of the clamp), c on (0.01, and 1.0, where the penalty dominates the actor's gradient), both
     together.  Every check of test_one_learn_step_against_f64 with its bounds, and pre within 2e-5 max(1, max |pre64|)."""
     state, hyper, batch, delta, ref = _shaped(case, huber, c)
-    _against_f64(gpu_device, state, hyper, batch, ref, delta, c, images, f"B{case[0]} {'huber ' if huber else 'mse '}c={c:g}")
+    K.against_f64(gpu_device, state, hyper, batch, ref, delta=delta, c=c, images=images, tag=f"B{case[0]} {'huber ' if huber else 'mse '}c={c:g}")
 
 
 # ---- a saturated row ------------------------------------------------------------------------------------------------------
@@ -264,8 +130,8 @@ def test_a_saturated_row_learns_only_with_the_penalty(gpu_device):
     torch.cuda.synchronize()
     assert not torch.equal(plain.actor.flat_grad, g_plain)
     # with the penalty: the whole f64 check on the same state
-    ref = S.ref_step(state, batch, hyper, delta=None, c=c)
-    _, fl, half_dq, _ = _against_f64(dev, state, hyper, batch, ref, None, c, True, "saturated c=0.01")
+    ref = R.ref_step(state, batch, hyper, delta=None, c=c)
+    _, fl, half_dq, _ = K.against_f64(dev, state, hyper, batch, ref, c=c, images=True, tag="saturated c=0.01")
     assert torch.equal(fl.mu, plain.mu)
     far = 0
     off = 0
@@ -368,11 +234,6 @@ def test_shaped_learn_with_an_n_step_draw(gpu_device):
 
 
 # ---- the loop ---------------------------------------------------------------------------------------------------------------
-def _flat(loop):
-    import torch
-    return torch.cat([p.detach().reshape(-1) for net in loop.agent._nets() for p in net.parameters()])
-
-
 def _loop(seed=6, graph_steps=4, pipeline=False, shape="default", **kw):
     from ddpg_trucktrailer_amd.rollout import DDPGRollout
     from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv

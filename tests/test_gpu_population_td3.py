@@ -96,7 +96,7 @@ def _population(dev, states, hyper, cfgs, batches, images, noise_seeds):
     """A PopulationTD3Learner whose agent a holds states[a] and draws batches[a] (tests/test_gpu_td3.py's _td3_learner, per agent)."""
     import torch
     from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner
-    from test_gpu_learn_shapes import _ring_with_batch
+    from learn_checks import ring_with_batch as _ring_with_batch
     agents, rings, seeds = [], [], []
     for state, cfg, batch in zip(states, cfgs, batches):
         ring, seed = _ring_with_batch(dev, batch[0].shape[0], [t.to(dev).contiguous() for t in batch])

@@ -24,7 +24,7 @@ def _td3_learner(dev, state, hyper, cfg, batch, images, noise_seed=None):
     """(agent, TD3Learner, ring, batch on the device): f32 nets, moments and both step counts of `state`; the ring's draw IS the batch."""
     import torch
     from ddpg_trucktrailer_amd.td3 import TD3Learner
-    from test_gpu_learn_shapes import _ring_with_batch
+    from learn_checks import ring_with_batch as _ring_with_batch
     B = batch[0].shape[0]
     on_dev = [t.to(dev).contiguous() for t in batch]
     ring, seed = _ring_with_batch(dev, B, on_dev)
@@ -138,7 +138,7 @@ def test_one_full_update_against_f64(gpu_device, case, images):
         B250  0.014|0.010    0.015|0.019  0.006|0.009  0.43|0.43  0.64|0.61  0.50|0.50  0.42|0.42     6
         B257  0.012|0.013    0.013|0.012  0.005|0.009  0.43|0.43  0.62|0.63  0.50|0.50  0.42|0.42     1"""
     import torch
-    from test_gpu_learn_shapes import _CRITIC_NAMES, _ACTOR_NAMES, _scratch_image
+    from learn_checks import ACTOR_NAMES as _ACTOR_NAMES, CRITIC_NAMES as _CRITIC_NAMES, scratch_image as _scratch_image
     dev = gpu_device
     B = case[0]
     state, hyper, batch, _ = T.case(*case)

@@ -7,6 +7,7 @@ import hashlib
 import pytest
 import torch
 
+import fake_args as F
 import learn_ref as R
 import shape_ref as S
 
@@ -36,7 +37,7 @@ def test_the_saturated_state_saturates_some_rows_on_both_sides_and_keeps_the_bat
     """shape_ref.saturated_state on the B = 33 case, in f64: at least two rows beyond +9.3 and two beyond -9.3 (tanh is exactly +-1.0f
     in f32 from 9.02 on), at least two within 8.7, none between; every pre-ReLU value of actor(s) and critic(s, a) is the case's own."""
     state, hyper, batch, ref, _ = R.case(*_CASE)
-    out = S.ref_step(S.saturated_state(state, batch), batch, hyper, c=0.01)
+    out = R.ref_step(S.saturated_state(state, batch), batch, hyper, c=0.01)
     pre = out["pre"]
     counts = (int((pre > 9.3).sum()), int((pre < -9.3).sum()), int((pre.abs() < 8.7).sum()))
     print("rows beyond +9.3, beyond -9.3, within 8.7:", counts)
@@ -49,7 +50,7 @@ def test_the_saturated_state_saturates_some_rows_on_both_sides_and_keeps_the_bat
 
 def test_shape_ref_without_a_shape_is_learn_refs_step_exactly():
     state, hyper, batch, ref, _ = R.case(*_CASE)
-    out = S.ref_step(state, batch, hyper)
+    out = R.ref_step(state, batch, hyper)
     for k in ("y", "q", "q_pi", "dq_da", "mu"):
         assert torch.equal(out[k], ref[k]), k
     for name in R.NETS:
@@ -64,13 +65,13 @@ def test_shape_ref_gradients_are_the_stated_ones():
     state, hyper, batch, ref, _ = R.case(*_CASE)
     B = _CASE[0]
     delta = S.delta_of(ref)
-    out = S.ref_step(state, batch, hyper, delta=delta, c=0.5)
+    out = R.ref_step(state, batch, hyper, delta=delta, c=0.5)
     e = ref["q"] - ref["y"]
     want = e.clamp(-delta, delta).sum() / B
     assert abs(out["grads"]["critic"]["q.bias"].item() - want.item()) <= 1e-12 * max(1.0, abs(want.item()))
     inside = e.abs() < delta
     assert torch.allclose(e.clamp(-delta, delta)[inside] / B, 0.5 * (2.0 / B) * e[inside], rtol=1e-15, atol=0)
-    plain = S.ref_step(state, batch, hyper, delta=delta, c=0.0)
+    plain = R.ref_step(state, batch, hyper, delta=delta, c=0.0)
     extra = out["grads"]["actor"]["mu.bias"] - plain["grads"]["actor"]["mu.bias"]
     pen = (2 * 0.5 * out["pre"] / B).sum()
     assert abs(extra.item() - pen.item()) <= 1e-12 * max(1.0, abs(pen.item()))
@@ -220,52 +221,10 @@ def lib():
     return L
 
 
-class _Fake:
-    """Plausible arguments of the three shaped entry points over made-up device addresses: the library checks them on the host, and
-    with one bad argument nothing reaches the GPU."""
-
-    def __init__(self, L, B):
-        addr = iter(range(0x10000, 0x10000 + 0x1000 * 300, 0x1000))
-        nxt = self.nxt = lambda: next(addr)
-        self.B = B
-        self.actor, self.critic, self.target_critic, self.grads = (L.TTMlpWeights(*[nxt() for _ in range(12)], 23, 400, 300) for _ in range(4))
-        self.saved_c, self.saved_a = (L.TTMlpSaved(*[nxt() for _ in range(6)]) for _ in range(2))
-        self.ws_c, self.ws_a = (L.TTMlpBwdWs(*[nxt() for _ in range(5)]) for _ in range(2))
-        self.td = L.TTTdInput(z_state=nxt(), mu_target=nxt(), target_critic=C.pointer(self.target_critic), reward=nxt(), done=nxt(),
-                              gamma=0.99, y_out=nxt(), q_out=nxt(), step_dev=nxt(), window_dev=None, bias_corr_out=nxt(),
-                              adam_beta1=0.9, adam_beta2=0.999)
-        self.q, self.mu, self.obs, self.q_pi, self.dq_da, self.step, self.bias_corr, self.tail = (nxt() for _ in range(8))
-        self.tables = [(C.c_void_p * 10)(*[nxt() for _ in range(10)]) for _ in range(4)]
-        self.shape = L.TTLossShape(1.5, 0.01, nxt())
-        self.count = 10
-        self.critic_flag = 0
-        self.scale = 1.0 / B
-
-    def rows(self, L, shape=True):
-        return L.load().tt_mlp_backward_rows_pair_shaped(
-            self.B, self.scale, self.q, C.byref(self.critic), C.byref(self.saved_c), C.byref(self.ws_c), C.byref(self.td), self.mu,
-            C.byref(self.actor), C.byref(self.saved_a), C.byref(self.ws_a), None, C.byref(self.shape) if shape else None, None)
-
-    def weights(self, L, shape=True):
-        p, m, v, t = self.tables
-        return L.load().tt_mlp_backward_weights_shaped(
-            self.B, self.critic_flag, self.obs, None, C.byref(self.saved_a), C.byref(self.ws_a), C.byref(self.grads), self.dq_da, self.mu,
-            -self.scale, self.count, p, m, v, t, self.step, 1e-4, 0.9, 0.999, 1e-8, 0.0, 1e-3, None, self.bias_corr,
-            C.byref(self.shape) if shape else None, None)
-
-    def tail_(self, L, shape=True):
-        p, m, v, t = self.tables
-        return L.load().tt_mlp_actor_tail_shaped(
-            self.B, self.obs, self.mu, C.byref(self.critic), self.q_pi, self.dq_da, C.byref(self.saved_a), C.byref(self.ws_a),
-            C.byref(self.grads), -self.scale, self.count, p, m, v, t, self.step, 1e-4, 0.9, 0.999, 1e-8, 0.0, 1e-3, None, self.bias_corr,
-            self.tail, None, C.byref(self.shape) if shape else None, None)
-
-
 _ENTRY = dict(rows="tt_mlp_backward_rows_pair_shaped", weights="tt_mlp_backward_weights_shaped", tail_="tt_mlp_actor_tail_shaped")
 
 
-def _set(obj, field, value):
-    return lambda f: setattr(getattr(f, obj), field, value)
+_set = F.set_field
 
 
 _COMMON = [("shape is NULL", None, False),
@@ -274,28 +233,7 @@ _COMMON = [("shape is NULL", None, False),
            ("pre_scale", _set("shape", "pre_scale", -0.5), True), ("pre_scale", _set("shape", "pre_scale", float("nan")), True),
            ("pre_scale", _set("shape", "pre_scale", float("inf")), True),
            ("pre is NULL", _set("shape", "pre", None), True)]
-_ROWS = [("n = 0", lambda f: setattr(f, "B", 0), True), ("q_out", lambda f: setattr(f, "q", None), True),
-         ("mu_out", lambda f: setattr(f, "mu", None), True), ("weights", _set("critic", "wa", None), True),
-         ("weights", _set("actor", "w3", None), True), ("weights", _set("actor", "fc1_dims", 401), True),
-         ("saved", _set("saved_c", "h2", None), True), ("saved", _set("saved_a", "rstd2", None), True),
-         ("workspace", _set("ws_c", "dz", None), True), ("workspace", _set("ws_a", "dx1", None), True),
-         ("same workspace", lambda f: setattr(f.ws_a, "dx2", f.ws_c.dx2), True),
-         ("TD input", _set("td", "y_out", None), True), ("TD input", _set("td", "reward", None), True),
-         ("TD input", _set("target_critic", "ba", None), True)]
-_WEIGHTS = [("critic", lambda f: setattr(f, "critic_flag", 1), True), ("row_dq_da", lambda f: setattr(f, "dq_da", None), True),
-            ("row_mu", lambda f: setattr(f, "mu", None), True), ("n = 0", lambda f: setattr(f, "B", 0), True),
-            ("n = 1025", lambda f: setattr(f, "B", 1025), True), ("obs", lambda f: setattr(f, "obs", None), True),
-            ("saved", _set("saved_a", "xh1", None), True), ("workspace", _set("ws_a", "dpre", None), True),
-            ("grads", _set("grads", "b3", None), True), ("count = 12", lambda f: setattr(f, "count", 12), True),
-            ("count = 5", lambda f: setattr(f, "count", 5), True), ("optimizer step", lambda f: f.tables[1].__setitem__(3, None), True),
-            ("optimizer step", lambda f: setattr(f, "step", None), True)]
-_TAIL = [("n = 0", lambda f: setattr(f, "B", 0), True), ("n = 1025", lambda f: setattr(f, "B", 1025), True),
-         ("obs", lambda f: setattr(f, "obs", None), True), ("mu", lambda f: setattr(f, "mu", None), True),
-         ("q_out", lambda f: setattr(f, "q_pi", None), True), ("dq_da", lambda f: setattr(f, "dq_da", None), True),
-         ("critic", _set("critic", "wa", None), True), ("saved", _set("saved_a", "h1", None), True),
-         ("workspace", _set("ws_a", "dy1", None), True), ("grads", _set("grads", "w1", None), True),
-         ("count = 0", lambda f: setattr(f, "count", 0), True), ("optimizer step", lambda f: f.tables[0].__setitem__(9, None), True),
-         ("tail_words", lambda f: setattr(f, "tail", None), True)]
+_ROWS, _WEIGHTS, _TAIL = ([(w, spoil, True) for w, spoil in rs] for rs in (F.ROWS, F.WEIGHTS, F.TAIL))
 _REFUSALS = [(e, *r) for e, rs in (("rows", _COMMON + _ROWS), ("weights", _COMMON + _WEIGHTS), ("tail_", _COMMON + _TAIL)) for r in rs]
 
 
@@ -304,11 +242,11 @@ _REFUSALS = [(e, *r) for e, rs in (("rows", _COMMON + _ROWS), ("weights", _COMMO
 def test_shaped_entry_points_check_their_arguments_before_any_hip_call(lib, entry, word, spoil, with_shape):
     """TT_EINVAL and a message that starts with the entry point's name and names the argument, for one spoiled argument at a time."""
     L = lib
-    f = _Fake(L, 256)
+    f = F.Fake(L, 256, "shaped")
     if spoil is not None:
         spoil(f)
-    rc = getattr(f, entry)(L, shape=with_shape)
-    msg = L.load().tt_last_error(None).decode()
+    f.with_shape = with_shape
+    rc, msg = getattr(f, entry)(), f.last_error()
     assert rc == L.TT_EINVAL, (rc, msg)
     assert msg.startswith(_ENTRY[entry] + ":") and word in msg, msg
 
