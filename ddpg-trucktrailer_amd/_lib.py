@@ -141,6 +141,12 @@ class TTDemoLoss(C.Structure):
                 ("dq_eff", C.c_void_p), ("code", C.c_void_p)]
 
 
+class TTMpcArgs(C.Structure):
+    """tt_mpc_args (include/ttenv.h: tt_env_mpc_plan)."""
+    _fields_ = [("horizon", C.c_int32), ("samples", C.c_int32)] + \
+               [(n, C.c_float) for n in ("sigma", "rho", "lambda_", "gamma", "k_lat", "k_yaw", "action_scale")] + [("seed", C.c_uint64)]
+
+
 class TTLearnLogJob(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
                [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
@@ -154,6 +160,8 @@ LEARN_LOG_MAX_CAPACITY = 1 << 22        # TT_LEARN_LOG_MAX_CAPACITY
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 NSTEP_MAX = 16          # TT_NSTEP_MAX
 TD3_NOISE_TAG = 0x7D3E  # the Philox domain of TD3's target-smoothing noise (csrc/tttd3.h)
+MPC_NOISE_TAG = 0x4D50  # the Philox domain of the MPC expert's exploration noise (csrc/ttenv.hip)
+MPC_MAX_HORIZON, MPC_MAX_SAMPLES = 64, 1024     # TT_MPC_MAX_HORIZON, TT_MPC_MAX_SAMPLES
 
 
 class TTError(RuntimeError):
@@ -196,6 +204,7 @@ _SIGNATURES = {
     "tt_env_step_hold": (C.c_int, [_P, _P, C.c_float, _P, _P]),
     "tt_env_hold_read": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P]),
     "tt_env_rollout_random": (C.c_int, [_P, _I, _U64, _P, _P, _P, _P]),
+    "tt_env_mpc_plan": (C.c_int, [_P, C.POINTER(TTMpcArgs), _P, _P, _P, _P, _P]),
     "tt_env_profile": (C.c_int, [_P, _I]),
     "tt_env_profile_read": (C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int64)]),
     "tt_mlp_split_ws_bytes": (C.c_uint64, []),

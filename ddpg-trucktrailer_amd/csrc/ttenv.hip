@@ -1056,6 +1056,135 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(const KParams P, const int n,
 }
 
 // ------------------------------------------------------------------------------------------
+// Sampling MPC (MPPI; include/ttenv.h: tt_env_mpc_plan has the definition of a decision).
+// ONE WORKGROUP PLANS FOR ONE LANE: thread `tid` rolls samples tid, tid + BLOCK, ... through step_env on a copy of the lane's env
+// in registers; the env in memory is only read.  The weighted mean needs every u[s, t] again once the largest return is known:
+// the noise is counter-based, so the second pass REGENERATES a sample's sequence (S * H Philox blocks, a log and a sincos each:
+// a few per cent of the S * H env steps of the first pass) instead of keeping S * H values (256 KB at the limits).  `chunk`
+// samples at a time go through an LDS tile [chunk][H | 1] (odd stride: conflict-free both ways), and thread t < H adds column t
+// of the tile in sample order.
+//
+// step_env's three wave votes with a wave that holds different SAMPLES of one lane, some of which have left the horizon loop:
+// a vote counts the active lanes only, and each of them only widens what the wave computes -- the quotient by a real division
+// gives every lane the value its own test would (the two quotients truncate differently only where the lane itself votes), and
+// the staged bonuses and the backward penalty are recomputed under each lane's own comparison inside the voted branch.
+constexpr uint32_t MPC_NOISE_TAG = 0x4D50u;     // Philox domain of the MPC's exploration noise
+constexpr int MPC_TILE_FLOATS = 12288;          // the second pass's LDS tile: 48 KB
+
+struct MpcK {
+    int H, S, chunk;
+    float action_scale;
+    double sigma, rho, sigma_c;     // sigma_c = sqrt(1 - rho^2) sigma
+    double lambda, gamma, k_lat, k_yaw;
+    uint64_t seed;
+};
+
+// z[s, t]: the recipe of the TD3 smoothing noise (csrc/tttd3.h) with log, sqrt and cos in f64; products only, so that both passes
+// get the same bits however they are contracted
+__device__ __forceinline__ double mpc_normal(const MpcK &m, uint32_t lane, uint32_t episode, uint32_t steps, int s, int t) {
+    uint32_t r[4];
+    philox4x32(lane, episode, steps | ((uint32_t)t << 12) | ((uint32_t)s << 18), MPC_NOISE_TAG, (uint32_t)m.seed,
+               (uint32_t)(m.seed >> 32), r);
+    const float u1 = ((float)(r[0] >> 8) + 0.5f) * (1.f / 16777216.f);
+    const float u2 = ((float)(r[1] >> 8) + 0.5f) * (1.f / 16777216.f);
+    double sn, cs;
+    tt_sincos(kTable, (double)(6.28318530717958647692f * u2), sn, cs);
+    return sqrt(-2.0 * log((double)u1)) * cs;
+}
+
+// u[s, t] from the AR(1) state `eps` (advanced here) and the plan's entry
+__device__ __forceinline__ float mpc_sample(const MpcK &m, uint32_t lane, uint32_t episode, uint32_t steps, int s, int t, float plan_t,
+                                            double &eps) {
+    if (s > 0) {
+        const double z = mpc_normal(m, lane, episode, steps, s, t);
+        eps = t == 0 ? m.sigma * z : fma(m.rho, eps, m.sigma_c * z);
+    }
+    return (float)fmin(fmax((double)plan_t + eps, -1.0), 1.0);
+}
+
+template <bool PER_ENV>
+__global__ __launch_bounds__(BLOCK) void k_mpc_plan(const KParams P, const int n, const Bufs b, const MpcK m, float *plan,
+                                                    float *mu_out, const uint8_t *live, double *returns_out) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char mpc_lds[];
+    const int i = blockIdx.x, tid = threadIdx.x;
+    if (i >= n || (live && !live[i])) return;       // uniform: a skipped lane keeps every output's bits
+    const int H = m.H, S = m.S, HP = H | 1;
+    double *G = reinterpret_cast<double *>(mpc_lds);            // [S] returns, then weights
+    double *red = G + S;                                        // [BLOCK]
+    float *pl = reinterpret_cast<float *>(red + BLOCK);         // [H] the plan as read
+    float *tile = pl + ((H + 3) & ~3);                          // [chunk][HP]
+    const KTable &T = kTable;
+
+    const uint32_t pk0 = reinterpret_cast<const uint2 *>(hot_ptr(b.hot, i) + H_MISC * TILE)->y;
+    const uint32_t steps0 = pk_steps(pk0), ep = b.episodes[i];
+    if (tid < H) pl[tid] = steps0 == 0u ? 0.f : plan[(size_t)i * H + tid];
+    __syncthreads();
+
+    // ---- pass 1: the returns
+    double gmax = -INFINITY;
+    for (int s = tid; s < S; s += BLOCK) {
+        Env e;
+        load_env<PER_ENV>(P, b, i, e);
+        double Gs = 0.0, disc = 1.0, eps = 0.0;
+        bool open = true;
+        float of[OBS];
+        for (int t = 0; t < H; ++t) {
+            const float u = mpc_sample(m, (uint32_t)i, ep, steps0, s, t, pl[t], eps);
+            const float a = u * m.action_scale;
+            StepOut o;
+            step_env(P, e, a, of, o);
+            Gs += disc * o.total;
+            disc *= m.gamma;
+            if (o.done) { open = false; break; }     // the sample's env stops here: pk's packed fields are not stepped past done
+        }
+        if (open) {
+            const double lat = -(e.x2 - e.g.gx) * e.g.sg + (e.y2 - e.g.gy) * e.g.cg;
+            const double dyaw = tt_wrap_pi(T, e.gyaw - e.psi2);
+            Gs += disc * -(m.k_lat * (lat * lat) + m.k_yaw * (dyaw * dyaw));
+        }
+        G[s] = Gs;
+        if (returns_out) returns_out[(size_t)i * S + s] = Gs;
+        if (isfinite(Gs)) gmax = fmax(gmax, Gs);
+    }
+    red[tid] = gmax;
+    __syncthreads();
+    for (int d = BLOCK >> 1; d > 0; d >>= 1) {
+        if (tid < d) red[tid] = fmax(red[tid], red[tid + d]);
+        __syncthreads();
+    }
+    gmax = red[0];
+    for (int s = tid; s < S; s += BLOCK) {
+        const double g = G[s];
+        G[s] = isfinite(g) ? tt_exp_neg(T, (g - gmax) / m.lambda) : 0.0;
+    }
+
+    // ---- pass 2: the weighted mean, in sample order
+    double num = 0.0, den = 0.0;
+    for (int s0 = 0; s0 < S; s0 += m.chunk) {
+        const int ns = min(m.chunk, S - s0);
+        __syncthreads();        // the weights are written (first round); the tile's readers are done (later rounds)
+        if (tid < ns) {
+            double eps = 0.0;
+            for (int t = 0; t < H; ++t) tile[tid * HP + t] = mpc_sample(m, (uint32_t)i, ep, steps0, s0 + tid, t, pl[t], eps);
+        }
+        __syncthreads();
+        if (tid < H)
+            for (int q = 0; q < ns; ++q) {
+                const double w = G[s0 + q];
+                num = fma(w, (double)tile[q * HP + tid], num);
+                den += w;
+            }
+    }
+    if (tid < H) {
+        const float un = den > 0.0 ? (float)(num / den) : pl[tid];     // no finite sample: the plan shifts unchanged
+        float *row = plan + (size_t)i * H;
+        if (tid == 0) mu_out[i] = un;
+        else row[tid - 1] = un;
+        if (tid == H - 1) row[tid] = un;
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // reset / pose / state kernels (not hot)
 __global__ __launch_bounds__(BLOCK) void k_reset(const KParams P, const int n, const Bufs b, const uint8_t *mask,
                                                  float *obs, const uint64_t seed) {
@@ -2078,6 +2207,45 @@ int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float 
     by_per_env(env, [&](auto per_env) {
         hipLaunchKernelGGL(k_rollout<decltype(per_env)::value>, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b,
                            k_steps, obs_out, reward_sum, episodes_done, env->seed, policy_seed);
+    });
+    TT_HIP(env, hipGetLastError());
+    return TT_OK;
+}
+
+int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan, float *mu_out, const uint8_t *live, double *returns_out,
+                    tt_stream_t stream) {
+    static_assert(TT_MPC_MAX_HORIZON <= BLOCK && TT_MPC_MAX_HORIZON <= 64 && TT_MPC_MAX_SAMPLES <= 1024,
+                  "k_mpc_plan: a thread per plan entry; 6 bits of t and 10 bits of s in the noise counter");
+    TT_HANDLE(env);
+    // (before the handle is read: these hold for any handle)
+    if (!args || !plan || !mu_out) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: args, plan and mu_out are required");
+    const tt_mpc_args &a = *args;
+    if (a.horizon < 1 || a.horizon > TT_MPC_MAX_HORIZON)
+        return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: horizon %d outside [1, %d]", a.horizon, TT_MPC_MAX_HORIZON);
+    if (a.samples < 1 || a.samples > TT_MPC_MAX_SAMPLES)
+        return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: samples %d outside [1, %d]", a.samples, TT_MPC_MAX_SAMPLES);
+    if (!std::isfinite(a.sigma) || a.sigma < 0.f) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: sigma is negative or not finite");
+    if (!std::isfinite(a.k_lat) || a.k_lat < 0.f) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: k_lat is negative or not finite");
+    if (!std::isfinite(a.k_yaw) || a.k_yaw < 0.f) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: k_yaw is negative or not finite");
+    if (!(a.rho >= 0.f && a.rho < 1.f)) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: rho is outside [0, 1)");
+    if (!std::isfinite(a.lambda) || !(a.lambda > 0.f)) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: lambda is not finite or <= 0");
+    if (!(a.gamma > 0.f && a.gamma <= 1.f)) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: gamma is outside (0, 1]");
+    if (!std::isfinite(a.action_scale) || !(a.action_scale > 0.f))
+        return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: action_scale is not finite or <= 0");
+    MpcK m{};
+    m.H = a.horizon; m.S = a.samples;
+    const int hp = m.H | 1;
+    m.chunk = MPC_TILE_FLOATS / hp < BLOCK ? MPC_TILE_FLOATS / hp : BLOCK;
+    m.action_scale = a.action_scale;
+    m.sigma = (double)a.sigma; m.rho = (double)a.rho;
+    m.sigma_c = std::sqrt(1.0 - m.rho * m.rho) * m.sigma;
+    m.lambda = (double)a.lambda; m.gamma = (double)a.gamma; m.k_lat = (double)a.k_lat; m.k_yaw = (double)a.k_yaw;
+    m.seed = a.seed;
+    const size_t lds = sizeof(double) * ((size_t)m.S + BLOCK) + sizeof(float) * ((size_t)((m.H + 3) & ~3) + (size_t)m.chunk * hp);
+    TT_HIP(env, hipSetDevice(env->device));
+    by_per_env(env, [&](auto per_env) {
+        hipLaunchKernelGGL(k_mpc_plan<decltype(per_env)::value>, dim3(env->n), dim3(BLOCK), lds, stream, env->kp, env->n, env->b, m,
+                           plan, mu_out, live, returns_out);
     });
     TT_HIP(env, hipGetLastError());
     return TT_OK;

@@ -238,6 +238,21 @@ class TruckTrailerVecEnv:
                                                    L.ptr(reward_sum), L.ptr(episodes_done), self._stream()))
         return obs
 
+    # ------------------------------------------------------------------ sampling MPC expert
+    def mpc_plan(self, cfg, plan, mu_out, live=None, returns_out=None, seed=0):
+        """One MPC decision for every lane (include/ttenv.h: tt_env_mpc_plan; mpc.MPCConfig): reads the envs, rolls cfg.samples
+        perturbed copies of plan [N, H] f32 through the env step, writes the first action of the weighted mean to mu_out [N] f32
+        (normalised units: step with mu_out * max_steer) and the shifted mean back into plan.  live [N] u8: lanes with 0 are skipped;
+        returns_out [N, S] f64 receives every sample's return.  The envs do not change.  Capturable.  Returns mu_out."""
+        from ddpg_trucktrailer_amd.mpc import check_mpc
+        check_mpc(cfg, action_scale=self.max_steer, n_envs=self.n_envs, device=self.device, plan=plan, mu_out=mu_out, live=live,
+                  returns_out=returns_out)
+        args = L.TTMpcArgs(cfg.horizon, cfg.samples, cfg.sigma, cfg.rho, cfg.temperature, cfg.gamma, cfg.k_lat, cfg.k_yaw,
+                           self.max_steer, int(seed) & (2 ** 64 - 1))
+        self._check(self.lib.tt_env_mpc_plan(self._h, C.byref(args), L.ptr(plan), L.ptr(mu_out), L.ptr(live), L.ptr(returns_out),
+                                             self._stream()))
+        return mu_out
+
     # ------------------------------------------------------------------ held lanes (greedy evaluation)
     def enable_hold(self):
         """Allocate the handle's evaluation block (include/ttenv.h: tt_env_set_hold) and the tensors hold_records() fills.

@@ -305,6 +305,46 @@ int tt_env_hold_read(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uin
 int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float *obs_out, float *reward_sum,
                           int32_t *episodes_done, tt_stream_t stream);
 
+/* Sampling MPC expert (MPPI, Williams et al. 2017; the reference's demonstrations come from a CasADi / IPOPT
+ * NMPC, DDPG/exp_gen.py, npc_solver.py).  One launch makes ONE DECISION for every lane: it rolls S perturbed steering sequences
+ * H steps forward from the lane's state through the step kernel's own env step, weights them by their return and writes the
+ * first action of the weighted mean.  The env is only read: no state, counter, episode number, cold attribute, ring, step
+ * counter or episode log changes.  For lane i, with H = horizon, S = samples, every f32 field of tt_mpc_args taken to f64:
+ *   plan     plan[i, 0..H-1] f32, normalised units in [-1, 1].  When the lane's step-in-episode is 0 the plan READ is all zeros
+ *            (after a reset or tt_env_set_pose no host call is needed, and a captured graph stays valid).
+ *   noise    z[s, t] = sqrt(-2 ln u1) cos(2 pi u2), u = ((r >> 8) + 0.5) 2^-24 in f32 from the first two words r of
+ *            Philox4x32-10 with counter (lane i, episode number, step-in-episode | t << 12 | s << 18, the domain tag 0x4D50) and
+ *            key (seed low, seed high); the angle is the f32 product 2 pi u2; log, sqrt and cos in f64 (the recipe of
+ *            tt_td3_agent's noise).  No other stream of the library uses the tag (0x7452 reset poses, 0xAC71 random actions,
+ *            0x0A5E OU noise, 0x5A3D replay draws, 0x7D3E TD3 smoothing).
+ *            eps[s, 0] = sigma z[s, 0];  eps[s, t] = rho eps[s, t-1] + sqrt(1 - rho^2) sigma z[s, t]  (f64; the factor
+ *            sqrt(1 - rho^2) sigma is formed once).  Sample 0 is the noise-free nominal: eps[0, .] = 0.
+ *   sample   u[s, t] = (float) clip(plan_t + eps[s, t], -1, 1); the steering is u * action_scale, ONE f32 multiply (the product
+ *            tt_env_step_hold forms); the step clips it as always.
+ *   return   G_s = sum_{t < T_s} gamma^t total_t in f64, in step order (gamma^t by repeated multiplication), total_t the
+ *            TT_I_TOTAL of the step; T_s = the step at which done first holds, inclusive, or H.  A sample that did not terminate
+ *            adds gamma^H (-(k_lat lat^2 + k_yaw dyaw^2)), lat = -(x2 - gx) sin(gyaw) + (y2 - gy) cos(gyaw) the trailer's offset
+ *            from the goal axis, dyaw = wrap(gyaw - psi2).
+ *   update   w_s = exp((G_s - max_s G) / lambda) in f64 (the exponent is clamped at -100), 0 for a return that is not finite (the
+ *            maximum is over the finite ones);  U'_t = sum_s w_s u[s, t] / sum_s w_s, both sums in f64 IN SAMPLE ORDER, stored as
+ *            f32: the same inputs give the same bits whatever the launch.  mu_out[i] = U'_0, and the plan is stored shifted:
+ *            (U'_1, ..., U'_{H-1}, U'_{H-1}).  With no finite sample mu_out[i] = plan_0 and the plan read shifts unchanged.
+ *   live     device u8 [N] or NULL; a lane with live[i] == 0 is skipped: its plan row, mu_out[i] and returns_out row keep their bits.
+ *   returns_out   f64 [N, S] or NULL: every G_s.
+ * Capturable into a hipGraph: no allocation, no host read; the noise keys are read from the device.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL handle, args, plan or mu_out; horizon outside
+ * [1, TT_MPC_MAX_HORIZON]; samples outside [1, TT_MPC_MAX_SAMPLES]; sigma, k_lat or k_yaw negative or not finite; rho outside
+ * [0, 1); lambda not finite or <= 0; gamma outside (0, 1]; action_scale not finite or <= 0. */
+#define TT_MPC_MAX_HORIZON 64
+#define TT_MPC_MAX_SAMPLES 1024
+typedef struct tt_mpc_args {
+    int32_t horizon, samples;
+    float sigma, rho, lambda, gamma, k_lat, k_yaw, action_scale;
+    uint64_t seed;
+} tt_mpc_args;
+int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan /* [N, H] in / out */, float *mu_out /* [N] */,
+                    const uint8_t *live, double *returns_out, tt_stream_t stream);
+
 /* Measurement hook (no reference counterpart): time each of the next `max_launches` step-kernel dispatches
  * with a HIP event pair bound to the dispatch itself (hipExtLaunchKernelGGL), on the stream they are launched
  * on; max_launches = 0 switches it off.  tt_env_profile_read waits for the recorded launches, adds them to the
