@@ -287,6 +287,14 @@ _SIGNATURES = {
                                          C.POINTER(TTMlpWeights), C.c_float, _I, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float,
                                          C.c_float, C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, _P, _P,
                                          C.POINTER(TTLossShape), C.POINTER(TTDemoLoss), _P]),
+    "tt_env_mpc_act_ring": (C.c_int, [_P, C.POINTER(TTMpcArgs), _P, C.c_int32, C.POINTER(TTRingView), C.c_float, _P, _P]),
+    "tt_mlp_forward_save_demo_lanes": (C.c_int, [_I, _I, _P, _P, C.POINTER(TTMlpWeights), _P, C.POINTER(TTMlpSaved), _P,
+                                                 C.POINTER(TTDemoLoss), C.c_int32, _P]),
+    "tt_mlp_actor_tail_demo_lanes": (C.c_int, [_I, _P, _P, C.POINTER(TTMlpWeights), _P, _P, C.POINTER(TTMlpSaved),
+                                               C.POINTER(TTMlpBwdWs), C.POINTER(TTMlpWeights), C.c_float, _I, _P, _P, _P, _P, _P,
+                                               C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                               C.POINTER(TTFc2Images), _P, _P, _P, C.POINTER(TTLossShape), C.POINTER(TTDemoLoss),
+                                               C.c_int32, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -13,6 +13,8 @@
 // kernel of its own: tt_mlp_backward_weights[_shaped] with row_dq_da = dq_eff.  The body is fwd_small_body<true, .., DEMO>
 // (ttlearn_bodies.h), the tail's checks and conversion those of every tail (ttlearn_host.h); other units' instantiations are unchanged.
 // A row with m = 0 keeps the bits of dQ/da, so a batch without demonstration rows leaves the bits of the launches these stand in for.
+// The _lanes entry points take expert_lanes by value -- tt_demo_loss keeps its layout -- and make a ring row of
+// a lane < expert_lanes a demonstration row as well; the entry points without the count are those with 0, the same launches.
 #include "ttlearn_host.h"
 
 namespace {
@@ -58,14 +60,15 @@ __global__ __launch_bounds__(64 * NW) void k_actor_tail_demo(const int n, const 
 }
 
 // what both entry points refuse of a tt_demo_loss: TT_OK, or TT_EINVAL with "<who>: <reason>"
-int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, DemoIn &out) {
+int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, const int32_t expert_lanes, DemoIn &out) {
     if (!dl) return fail(TT_EINVAL, "%s: demo is NULL", who);
+    if (expert_lanes < 0) return fail(TT_EINVAL, "%s: expert_lanes = %d is negative", who, (int)expert_lanes);
     if (!std::isfinite(dl->k) || dl->k < 0.f) return fail(TT_EINVAL, "%s: demo->k = %g is not a finite number >= 0", who, (double)dl->k);
     if (!dl->a || !dl->idx || !dl->dq_eff || !dl->code) return fail(TT_EINVAL, "%s: demo->a, idx, dq_eff or code is NULL", who);
     if (dl->q_filter && !dl->q) return fail(TT_EINVAL, "%s: demo->q is NULL with q_filter set", who);
     if (!dq_da) return fail(TT_EINVAL, "%s: dq_da is NULL (the true derivative has a buffer of its own)", who);
     if (dl->dq_eff == dq_da) return fail(TT_EINVAL, "%s: demo->dq_eff is dq_da", who);
-    out = DemoIn{dl->a, dl->idx, dl->q, dl->k, dl->q_filter ? 1 : 0, dl->dq_eff, dl->code};
+    out = DemoIn{dl->a, dl->idx, dl->q, dl->k, dl->q_filter ? 1 : 0, dl->dq_eff, dl->code, (int)expert_lanes};
     return TT_OK;
 }
 
@@ -73,11 +76,11 @@ int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, Dem
 
 extern "C" {
 
-int tt_mlp_forward_save_demo(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
-                             const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, tt_stream_t stream) {
-    const char *const who = "tt_mlp_forward_save_demo";
+// both forms of the forward: `who` names the entry point in every refusal
+static int forward_save_demo(const char *who, int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
+                             const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes, tt_stream_t stream) {
     DemoIn din;
-    if (const int rc = refuse_demo(who, demo, dq_da, din)) return rc;
+    if (const int rc = refuse_demo(who, demo, dq_da, expert_lanes, din)) return rc;
     if (!critic) return fail(TT_EINVAL, "%s: the actor has no demonstration form (the term is in the critic's pass on (s, mu(s)))", who);
     if (n < 0) return fail(TT_EINVAL, "%s: n = %d rows, not >= 0", who, n);
     if (!obs || !out || !action) return fail(TT_EINVAL, "%s: obs, action or out is NULL", who);
@@ -90,15 +93,25 @@ int tt_mlp_forward_save_demo(int n, int critic, const float *obs, const float *a
     return launched(who);
 }
 
-int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
-                           const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale, int count,
-                           float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
+int tt_mlp_forward_save_demo(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
+                             const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, tt_stream_t stream) {
+    return forward_save_demo("tt_mlp_forward_save_demo", n, critic, obs, action, w, out, saved, dq_da, demo, 0, stream);
+}
+
+int tt_mlp_forward_save_demo_lanes(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
+                                   const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes,
+                                   tt_stream_t stream) {
+    return forward_save_demo("tt_mlp_forward_save_demo_lanes", n, critic, obs, action, w, out, saved, dq_da, demo, expert_lanes, stream);
+}
+
+static int actor_tail_demo(const char *who, int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out,
+                           float *dq_da, const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale,
+                           int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
                            const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                            const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
-                           const tt_loss_shape *shape, const tt_demo_loss *demo, tt_stream_t stream) {
-    const char *const who = "tt_mlp_actor_tail_demo";
+                           const tt_loss_shape *shape, const tt_demo_loss *demo, int32_t expert_lanes, tt_stream_t stream) {
     DemoIn din;
-    if (const int rc = refuse_demo(who, demo, dq_da, din)) return rc;
+    if (const int rc = refuse_demo(who, demo, dq_da, expert_lanes, din)) return rc;
     if (shape)
         if (const int rc = refuse_shape(who, shape)) return rc;
     Tail T;
@@ -109,6 +122,29 @@ int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_ml
                        dq_da, T.sv, T.o, T.G, T.A, T.rs, T.ts, shape ? shape->pre_scale : 0.f,
                        shape ? static_cast<const float *>(shape->pre) : nullptr, din);
     return launched(who);
+}
+
+int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                           const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale, int count,
+                           float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
+                           const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                           const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
+                           const tt_loss_shape *shape, const tt_demo_loss *demo, tt_stream_t stream) {
+    return actor_tail_demo("tt_mlp_actor_tail_demo", n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params, exp_avg,
+                           exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words,
+                           gave_up_host, shape, demo, 0, stream);
+}
+
+int tt_mlp_actor_tail_demo_lanes(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                                 const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale,
+                                 int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq,
+                                 float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
+                                 int32_t *tail_words, int32_t *gave_up_host, const tt_loss_shape *shape, const tt_demo_loss *demo,
+                                 int32_t expert_lanes, tt_stream_t stream) {
+    return actor_tail_demo("tt_mlp_actor_tail_demo_lanes", n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params,
+                           exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words,
+                           gave_up_host, shape, demo, expert_lanes, stream);
 }
 
 }  // extern "C"

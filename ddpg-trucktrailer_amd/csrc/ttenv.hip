@@ -1102,9 +1102,22 @@ __device__ __forceinline__ float mpc_sample(const MpcK &m, uint32_t lane, uint32
     return (float)fmin(fmax((double)plan_t + eps, -1.0), 1.0);
 }
 
-template <bool PER_ENV>
-__global__ __launch_bounds__(BLOCK) void k_mpc_plan(const KParams P, const int n, const Bufs b, const MpcK m, float *plan,
-                                                    float *mu_out, const uint8_t *live, double *returns_out) {
+// Where a decision of an EXPERT LANE goes (tt_env_mpc_act_ring): the running step's action row of a trajectory ring, found through
+// the cursor as k_step finds its rows, and the loop's scaled-action buffer -- the two values the policy launch wrote for the lane.
+struct MpcRing {
+    const int *cursor;      // [0]: the running step's slot t (left by tt_actor_act_ring)
+    float *act;             // the ring's action rows [slots, n_envs]
+    float *act_scaled;      // [n_envs]
+    int n_envs, slots;
+    float high;
+};
+struct MpcNoRing {};
+
+// One planner, two launches: k_mpc_plan (RING = MpcNoRing: mu_out, live, returns_out) and k_mpc_act_ring (RING = MpcRing: workgroup
+// i < n plans for lane i of the first n lanes, and U'_0 goes to the ring).  Everything before the last store is the same text.
+template <bool PER_ENV, class RING>
+__device__ __forceinline__ void mpc_plan_body(const KParams P, const int n, const Bufs b, const MpcK m, float *plan, float *mu_out,
+                                              const uint8_t *live, double *returns_out, const RING ring) {
     extern __shared__ __attribute__((aligned(16))) unsigned char mpc_lds[];
     const int i = blockIdx.x, tid = threadIdx.x;
     if (i >= n || (live && !live[i])) return;       // uniform: a skipped lane keeps every output's bits
@@ -1178,10 +1191,34 @@ __global__ __launch_bounds__(BLOCK) void k_mpc_plan(const KParams P, const int n
     if (tid < H) {
         const float un = den > 0.0 ? (float)(num / den) : pl[tid];     // no finite sample: the plan shifts unchanged
         float *row = plan + (size_t)i * H;
-        if (tid == 0) mu_out[i] = un;
-        else row[tid - 1] = un;
+        if (tid == 0) {
+            if constexpr (std::is_same<RING, MpcRing>::value) {
+                // ring.act[t][i] = U'_0 (the normalised action: what collect_demonstrations stores) and the env step's input, one
+                // f32 product; a cursor outside the ring (never written by a pack launch) stores nothing
+                const int t = ring.cursor[0];
+                if ((unsigned)t < (unsigned)ring.slots) ring.act[(size_t)t * ring.n_envs + i] = un;
+                ring.act_scaled[i] = un * ring.high;
+            } else {
+                mu_out[i] = un;
+            }
+        } else {
+            row[tid - 1] = un;
+        }
         if (tid == H - 1) row[tid] = un;
     }
+}
+
+template <bool PER_ENV>
+__global__ __launch_bounds__(BLOCK) void k_mpc_plan(const KParams P, const int n, const Bufs b, const MpcK m, float *plan,
+                                                    float *mu_out, const uint8_t *live, double *returns_out) {
+    mpc_plan_body<PER_ENV>(P, n, b, m, plan, mu_out, live, returns_out, MpcNoRing{});
+}
+
+// lanes [0, lanes) of the env: grid = lanes; plan is [lanes, H]
+template <bool PER_ENV>
+__global__ __launch_bounds__(BLOCK) void k_mpc_act_ring(const KParams P, const int lanes, const Bufs b, const MpcK m, float *plan,
+                                                        const MpcRing ring) {
+    mpc_plan_body<PER_ENV>(P, lanes, b, m, plan, nullptr, nullptr, nullptr, ring);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -2212,27 +2249,24 @@ int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float 
     return TT_OK;
 }
 
-int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan, float *mu_out, const uint8_t *live, double *returns_out,
-                    tt_stream_t stream) {
+// what both planning entry points refuse of a tt_mpc_args (TT_EINVAL with "<who>: <reason>", no handle read, no HIP call), and the
+// kernel's constants and dynamic LDS bytes of one that passes
+static int mpc_constants(const char *who, const tt_mpc_args &a, MpcK &m, size_t &lds) {
     static_assert(TT_MPC_MAX_HORIZON <= BLOCK && TT_MPC_MAX_HORIZON <= 64 && TT_MPC_MAX_SAMPLES <= 1024,
                   "k_mpc_plan: a thread per plan entry; 6 bits of t and 10 bits of s in the noise counter");
-    TT_HANDLE(env);
-    // (before the handle is read: these hold for any handle)
-    if (!args || !plan || !mu_out) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: args, plan and mu_out are required");
-    const tt_mpc_args &a = *args;
     if (a.horizon < 1 || a.horizon > TT_MPC_MAX_HORIZON)
-        return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: horizon %d outside [1, %d]", a.horizon, TT_MPC_MAX_HORIZON);
+        return tthost::fail(TT_EINVAL, "%s: horizon %d outside [1, %d]", who, a.horizon, TT_MPC_MAX_HORIZON);
     if (a.samples < 1 || a.samples > TT_MPC_MAX_SAMPLES)
-        return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: samples %d outside [1, %d]", a.samples, TT_MPC_MAX_SAMPLES);
-    if (!std::isfinite(a.sigma) || a.sigma < 0.f) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: sigma is negative or not finite");
-    if (!std::isfinite(a.k_lat) || a.k_lat < 0.f) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: k_lat is negative or not finite");
-    if (!std::isfinite(a.k_yaw) || a.k_yaw < 0.f) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: k_yaw is negative or not finite");
-    if (!(a.rho >= 0.f && a.rho < 1.f)) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: rho is outside [0, 1)");
-    if (!std::isfinite(a.lambda) || !(a.lambda > 0.f)) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: lambda is not finite or <= 0");
-    if (!(a.gamma > 0.f && a.gamma <= 1.f)) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: gamma is outside (0, 1]");
+        return tthost::fail(TT_EINVAL, "%s: samples %d outside [1, %d]", who, a.samples, TT_MPC_MAX_SAMPLES);
+    if (!std::isfinite(a.sigma) || a.sigma < 0.f) return tthost::fail(TT_EINVAL, "%s: sigma is negative or not finite", who);
+    if (!std::isfinite(a.k_lat) || a.k_lat < 0.f) return tthost::fail(TT_EINVAL, "%s: k_lat is negative or not finite", who);
+    if (!std::isfinite(a.k_yaw) || a.k_yaw < 0.f) return tthost::fail(TT_EINVAL, "%s: k_yaw is negative or not finite", who);
+    if (!(a.rho >= 0.f && a.rho < 1.f)) return tthost::fail(TT_EINVAL, "%s: rho is outside [0, 1)", who);
+    if (!std::isfinite(a.lambda) || !(a.lambda > 0.f)) return tthost::fail(TT_EINVAL, "%s: lambda is not finite or <= 0", who);
+    if (!(a.gamma > 0.f && a.gamma <= 1.f)) return tthost::fail(TT_EINVAL, "%s: gamma is outside (0, 1]", who);
     if (!std::isfinite(a.action_scale) || !(a.action_scale > 0.f))
-        return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: action_scale is not finite or <= 0");
-    MpcK m{};
+        return tthost::fail(TT_EINVAL, "%s: action_scale is not finite or <= 0", who);
+    m = MpcK{};
     m.H = a.horizon; m.S = a.samples;
     const int hp = m.H | 1;
     m.chunk = MPC_TILE_FLOATS / hp < BLOCK ? MPC_TILE_FLOATS / hp : BLOCK;
@@ -2241,11 +2275,47 @@ int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan, float *mu
     m.sigma_c = std::sqrt(1.0 - m.rho * m.rho) * m.sigma;
     m.lambda = (double)a.lambda; m.gamma = (double)a.gamma; m.k_lat = (double)a.k_lat; m.k_yaw = (double)a.k_yaw;
     m.seed = a.seed;
-    const size_t lds = sizeof(double) * ((size_t)m.S + BLOCK) + sizeof(float) * ((size_t)((m.H + 3) & ~3) + (size_t)m.chunk * hp);
+    lds = sizeof(double) * ((size_t)m.S + BLOCK) + sizeof(float) * ((size_t)((m.H + 3) & ~3) + (size_t)m.chunk * hp);
+    return TT_OK;
+}
+
+int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan, float *mu_out, const uint8_t *live, double *returns_out,
+                    tt_stream_t stream) {
+    TT_HANDLE(env);
+    // (before the handle is read: these hold for any handle)
+    if (!args || !plan || !mu_out) return tthost::fail(TT_EINVAL, "tt_env_mpc_plan: args, plan and mu_out are required");
+    MpcK m;
+    size_t lds;
+    if (const int rc = mpc_constants("tt_env_mpc_plan", *args, m, lds)) return rc;
     TT_HIP(env, hipSetDevice(env->device));
     by_per_env(env, [&](auto per_env) {
         hipLaunchKernelGGL(k_mpc_plan<decltype(per_env)::value>, dim3(env->n), dim3(BLOCK), lds, stream, env->kp, env->n, env->b, m,
                            plan, mu_out, live, returns_out);
+    });
+    TT_HIP(env, hipGetLastError());
+    return TT_OK;
+}
+
+int tt_env_mpc_act_ring(tt_env *env, const tt_mpc_args *args, float *plan, int32_t lanes, const tt_ring_view *ring, float high,
+                        float *act_scaled, tt_stream_t stream) {
+    const char *const who = "tt_env_mpc_act_ring";
+    TT_HANDLE(env);
+    // (before the handle is read: these hold for any handle)
+    if (!args || !plan || !ring || !act_scaled) return tthost::fail(TT_EINVAL, "%s: args, plan, ring and act_scaled are required", who);
+    if (!ring->cursor || !ring->act) return tthost::fail(TT_EINVAL, "%s: ring->cursor and ring->act are required", who);
+    if (ring->slots < 1) return tthost::fail(TT_EINVAL, "%s: a ring of %d slots", who, ring->slots);
+    if (lanes < 1 || lanes > ring->n_envs)
+        return tthost::fail(TT_EINVAL, "%s: lanes %d outside [1, n_envs = %d]", who, lanes, ring->n_envs);
+    if (!std::isfinite(high) || !(high > 0.f)) return tthost::fail(TT_EINVAL, "%s: high is not finite or <= 0", who);
+    MpcK m;
+    size_t lds;
+    if (const int rc = mpc_constants(who, *args, m, lds)) return rc;
+    if (ring->n_envs != env->n) return tthost::fail(TT_EINVAL, "%s: the ring view has %d envs, this handle %d", who, ring->n_envs, env->n);
+    const MpcRing r{ring->cursor, ring->act, act_scaled, ring->n_envs, ring->slots, high};
+    TT_HIP(env, hipSetDevice(env->device));
+    by_per_env(env, [&](auto per_env) {
+        hipLaunchKernelGGL(k_mpc_act_ring<decltype(per_env)::value>, dim3(lanes), dim3(BLOCK), lds, stream, env->kp, (int)lanes, env->b, m,
+                           plan, r);
     });
     TT_HIP(env, hipGetLastError());
     return TT_OK;

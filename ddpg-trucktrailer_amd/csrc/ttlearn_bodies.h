@@ -276,7 +276,8 @@ struct EarlyW {
     const float *__restrict__ w1, *__restrict__ b1, *__restrict__ g1, *__restrict__ be1;
 };
 // DEMO (csrc/ttdemo.hip): the behaviour-cloning term of the actor loss on demonstration rows, folded into the dQ/da the row's lane 0
-// hands on.  a [n]: the batch's stored actions, idx [n][2]: the draw's index buffer (idx[2 b] < 0: row b came from the side buffer),
+// hands on.  a [n]: the batch's stored actions, idx [n][2]: the draw's index buffer (idx[2 b] < 0: row b came from the side buffer;
+// else (slot, lane) of a ring row, a demonstration row too where lane < lanes: the loop's expert lanes),
 // q [n]: Q(s, a) of learn()'s FIRST launch (the critic before this update; read with q_filter only), k = 2 lambda.
 // Out: dq_eff [n] and code [n] (0 a ring row, 1 a demonstration row the filter left out, 2 a demonstration row applied).
 struct DemoIn {
@@ -287,6 +288,7 @@ struct DemoIn {
     int q_filter;
     float *dq_eff;
     int *code;
+    int lanes;      // expert lanes of the loop's env: a ring row (idx[2 b] >= 0) of lane idx[2 b + 1] < lanes is a demonstration row too
 };
 template <bool CRITIC, class Hook = NoHook, bool DEMO = false>
 __device__ __forceinline__ void fwd_small_body(const int n, const float *__restrict__ obs,
@@ -602,7 +604,8 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
         for (int rr = 0; rr < TR / NW; ++rr) {
             const int row = min(row0 + wave * (TR / NW) + rr, n - 1);
             demo_a[rr] = demo.a[row];
-            demo_i[rr] = demo.idx[2 * row];
+            // a side row, or a ring row of an expert lane (lanes = 0: idx[2 row + 1] >= 0 always, the side-row test alone)
+            demo_i[rr] = (demo.idx[2 * row] < 0 || demo.idx[2 * row + 1] < demo.lanes) ? -1 : 0;
             demo_q[rr] = demo.q_filter ? demo.q[row] : 0.f;
         }
     }

@@ -185,7 +185,7 @@ class LearnLog:
 
 
 class FusedLearner:
-    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None):
+    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None, expert_lanes=None):
         """fc2_images (None = on unless TT_LEARN_F32=1): the 400 x 300 products of learn() on the f16 MFMA from pre-split
         images of the four networks' fc2 (include/ttenv.h: tt_mlp_weights.fc2_img) that the optimizer launches keep current;
         off = every product on the exact-f32 MFMA straight from the weights.
@@ -194,8 +194,15 @@ class FusedLearner:
         tt_loss_shape), the same number of launches.  Not with data-parallel ranks.
         demo_loss (None = no row of the batch is treated as a demonstration): a demo_loss.DemoLoss -- learn_batch then takes the
         draw's index buffer (demo_index=) and the actor's step through the demonstration entry points (include/ttenv.h:
-        tt_demo_loss), the same number of launches.  Composes with loss_shape.  Not with data-parallel ranks."""
+        tt_demo_loss), the same number of launches.  Composes with loss_shape.  Not with data-parallel ranks.
+        expert_lanes (with demo_loss; None = the entry points above): a whole number >= 0 -- the ring rows of lanes < expert_lanes
+        are demonstration rows as well (the loop's mpc.ExpertLanes) and the actor's step goes through the
+        _lanes entry points, which with 0 leave the bits of the entry points above."""
         import os
+        if expert_lanes is not None and not (isinstance(expert_lanes, int) and not isinstance(expert_lanes, bool) and expert_lanes >= 0):
+            raise ValueError(f"expert_lanes = {expert_lanes!r} is not None or a whole number >= 0")
+        if expert_lanes is not None and demo_loss is None:
+            raise ValueError(f"expert_lanes = {expert_lanes} without demo_loss: the learner has nothing to do with the lanes")
         assert fused.supported(agent.actor) and fused.supported(agent.critic)
         self.agent, self.B = agent, int(batch_size)
         dev = self.dev = agent.actor.fc1.weight.device
@@ -238,6 +245,7 @@ class FusedLearner:
         if loss_shape is not None:
             self.set_loss_shape(loss_shape)
         self.demo_loss, self.dq_eff, self.code, self._demo_actions = None, None, None, None
+        self.expert_lanes = expert_lanes
         if demo_loss is not None:
             self.set_demo_loss(demo_loss)
 
@@ -276,7 +284,8 @@ class FusedLearner:
                             dq_eff=self.dq_eff.data_ptr(), code=self.code.data_ptr())
 
     def demo_stats(self):
-        """Of the last update (synchronises): {"demo_rows": rows that came from the side buffer, "applied": those the filter let
+        """Of the last update (synchronises): {"demo_rows": rows that came from the side buffer or, with expert_lanes, from an
+        expert lane of the ring, "applied": those the filter let
         through, "bc_loss": lambda (1/B) sum over the applied rows of (mu - a)^2, formed on the host in f64 from code, mu and the
         batch's stored actions}."""
         if self.demo_loss is None:
@@ -354,8 +363,12 @@ class FusedLearner:
     def _fwd(self, net, obs, action, out, saved=None, dq_da=None, demo=None):
         self._fresh()
         if demo is not None:       # the critic on (s, mu(s)) with the demonstration term in dq_eff (csrc/ttdemo.hip)
-            L.check(self.lib.tt_mlp_forward_save_demo(self.B, 1, L.ptr(obs), L.ptr(action), C.byref(self.w(net)), L.ptr(out),
-                                                      C.byref(saved) if saved else None, L.ptr(dq_da), C.byref(demo), self._stream()))
+            args = (self.B, 1, L.ptr(obs), L.ptr(action), C.byref(self.w(net)), L.ptr(out), C.byref(saved) if saved else None,
+                    L.ptr(dq_da), C.byref(demo))
+            if self.expert_lanes is not None:
+                L.check(self.lib.tt_mlp_forward_save_demo_lanes(*args, self.expert_lanes, self._stream()))
+            else:
+                L.check(self.lib.tt_mlp_forward_save_demo(*args, self._stream()))
             return
         L.check(self.lib.tt_mlp_forward_save(self.B, 1 if action is not None else 0, L.ptr(obs), L.ptr(action),
                                              C.byref(self.w(net)), L.ptr(out), C.byref(saved) if saved else None,
@@ -593,7 +606,9 @@ class FusedLearner:
                     lr, b1, b2, eps, wd, ag.tau, st.images_ref(), L.ptr(self.bias_corr), L.ptr(self.tail_words),
                     C.c_void_p(self.tail_gave_up_host.data_ptr())]
             shape = C.byref(self._shape) if self.loss_shape is not None else None
-            if demo is not None:              # (the demonstration form takes the shape as well, NULL without one)
+            if demo is not None and self.expert_lanes is not None:
+                L.check(self.lib.tt_mlp_actor_tail_demo_lanes(*args, shape, C.byref(demo), self.expert_lanes, self._stream()))
+            elif demo is not None:            # (the demonstration form takes the shape as well, NULL without one)
                 L.check(self.lib.tt_mlp_actor_tail_demo(*args, shape, C.byref(demo), self._stream()))
             elif shape is not None:
                 L.check(self.lib.tt_mlp_actor_tail_shaped(*args, shape, self._stream()))
@@ -614,7 +629,8 @@ class FusedLearner:
         sample: see phase_a (the five tensors are then the draw's batch buffers, filled by learn()'s first launch).
         n_step: see phase_a (n-step returns; 1 = the one-step learn(), launch for launch).
         demo_index (with demo_loss; else it must be None): the draw's [B, 2] int32 index buffer of this batch (TrajectoryRing: the
-        sixth of its batch buffers) -- row b is a demonstration row where demo_index[b, 0] < 0."""
+        sixth of its batch buffers) -- row b is a demonstration row where demo_index[b, 0] < 0, or, with expert_lanes, where
+        demo_index[b, 1] < expert_lanes."""
         assert states.shape[0] == self.B and done_u8.dtype == torch.uint8
         demo = None
         if self.demo_loss is not None:

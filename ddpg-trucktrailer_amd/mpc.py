@@ -6,6 +6,8 @@ weights them by their return and executes the first action of the weighted mean.
     MPCConfig                 horizon H, samples S, noise (sigma, rho), temperature lambda, gamma, terminal cost (k_lat, k_yaw)
     check_mpc                 everything a planning call refuses, as one pure function
     MPCExpert                 a TruckTrailerVecEnv's planner: owns the plan buffer, act() -> mu [N] in normalised units
+    ExpertLanes               lanes [0, M) of a vector loop's env driven by the expert inside the captured step
+    check_expert_lanes        everything a loop refuses with expert lanes, as one pure function; expert_mask: the host's mask rule
     collect_demonstrations    places lanes, runs plan -> step until every lane is done, returns the five arrays of
                               expert.transitions_to_arrays (what expert.save_transitions_npz and TrajectoryRing.load_side take)
 
@@ -119,6 +121,67 @@ class MPCExpert:
 
     def act(self, live=None, returns_out=None):
         return self.env.mpc_plan(self.cfg, self.plan, self.mu, live=live, returns_out=returns_out, seed=self.seed)
+
+
+class ExpertLanes:
+    """Expert lanes of a vector loop (include/ttenv.h: tt_env_mpc_act_ring): lanes [0, lanes) of the loop's env
+    are driven by the MPC expert in every vector step -- one decision per lane between the policy launch and the env step, inside
+    the captured step -- and their transitions land in the ring like any other lane's.  lanes: a whole number >= 1 (at most the
+    env's lanes: the loop checks); mpc: an MPCConfig; seed: a whole number in [0, 2^64), the key of the planner's noise."""
+
+    def __init__(self, lanes, mpc=None, seed=0):
+        self.lanes, self.mpc, self.seed = lanes, MPCConfig() if mpc is None else mpc, seed
+        check_expert_lanes(self)
+        self.lanes, self.seed = int(lanes), int(seed)
+
+    def __repr__(self):
+        return f"ExpertLanes(lanes={self.lanes}, mpc={self.mpc!r}, seed={self.seed})"
+
+    def __eq__(self, other):
+        return isinstance(other, ExpertLanes) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def as_tuple(self):
+        return (self.lanes, self.mpc.as_tuple(), self.seed)
+
+    @classmethod
+    def from_tuple(cls, t):
+        return cls(int(t[0]), MPCConfig.from_tuple(tuple(t[1])), int(t[2]))
+
+
+def expert_mask(index, lanes):
+    """The demonstration rows of a batch under expert lanes, from the draw's [B, 2] index buffer (a side row is (-1, j), a ring row
+    (slot, lane)): a side row, or a ring row of a lane < lanes.  What the kernels test (csrc/ttlearn_bodies.h: DemoIn.lanes)."""
+    return (index[:, 0] < 0) | (index[:, 1] < int(lanes))
+
+
+def check_expert_lanes(expert, n_envs=None, ring_mode=None, population=False, data_parallel=False, force_dp=False):
+    """What is refused with expert lanes, each a ValueError that names expert: a malformed ExpertLanes; with n_envs, more lanes than
+    the env has; a stepper that is not in ring mode (a CPU device or a torch actor: the launch addresses the ring through its device
+    cursor); a population; data-parallel ranks, the p2p exchange or the TT_FORCE_DP launch structure (not testable on one GPU)."""
+    if not isinstance(expert, ExpertLanes):
+        raise ValueError(f"expert = {expert!r} is not an ExpertLanes")
+    if not isinstance(expert.mpc, MPCConfig):
+        raise ValueError(f"expert: mpc = {expert.mpc!r} is not an MPCConfig")
+    check_mpc(expert.mpc)
+    if not (_whole(expert.lanes) and expert.lanes >= 1):
+        raise ValueError(f"expert: lanes = {expert.lanes!r} is not a whole number >= 1")
+    if not (_whole(expert.seed) and 0 <= expert.seed < 2 ** 64):
+        raise ValueError(f"expert: seed = {expert.seed!r} is not a whole number in [0, 2^64)")
+    if n_envs is not None and expert.lanes > int(n_envs):
+        raise ValueError(f"expert: lanes = {expert.lanes} is outside [1, {int(n_envs)}], the env's lanes")
+    if ring_mode is not None and not ring_mode:
+        raise ValueError("expert lanes need a stepper in ring mode (the reference-shaped actor on a GPU): the expert's launch finds "
+                         "the step's ring row through the device cursor")
+    if population:
+        raise ValueError("expert lanes in a population are not supported (PopulationRollout / PopulationLearner)")
+    if data_parallel:
+        raise ValueError("expert lanes with data-parallel ranks (or the p2p exchange) are not supported")
+    if force_dp:
+        raise ValueError("expert lanes with the data-parallel launch structure (TT_FORCE_DP) are not supported")
+    return expert
 
 
 def exp_gen_poses(lanes, seed=0):

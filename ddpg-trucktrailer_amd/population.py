@@ -54,6 +54,13 @@ def _refuse_demo_loss(demo_loss, agents=()):
             check_demo_loss(demo, population=True)
 
 
+def _refuse_expert(expert):
+    """A population has no expert lanes (mpc.check_expert_lanes)."""
+    if expert is not None:
+        from ddpg_trucktrailer_amd.mpc import check_expert_lanes
+        check_expert_lanes(expert, population=True)
+
+
 class _PopulationLearnerBase:
     """What the population learners of DDPG (PopulationLearner) and TD3 (td3.PopulationTD3Learner) share: K agents, each with the
     state of a fused learner of its own, whose updates are launched together through one handle of the library.  The handle is made
@@ -211,9 +218,10 @@ class PopulationLearner(_PopulationLearnerBase):
     table refuses an n other than 1."""
 
     def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1,
-                 loss_shape=None, demo_loss=None):
+                 loss_shape=None, demo_loss=None, expert=None):
         _refuse_loss_shape(loss_shape, agents)
         _refuse_demo_loss(demo_loss, agents)
+        _refuse_expert(expert)
         super().__init__(agents, batch_size, rings, seeds)
         if any(r._side_struct() is not None for r in rings):
             raise ValueError("expert side buffers are not supported in a population")
@@ -389,10 +397,11 @@ class PopulationRollout:
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
         _refuse_loss_shape(loss_shape)
         _refuse_demo_loss(demo_loss)
+        _refuse_expert(expert)
         if td3 is not None:            # (before anything else: each refusal names its option)
             from ddpg_trucktrailer_amd.td3 import check_population_td3
             td3 = check_population_td3(td3, len(seeds), updates_per_step, _listed(n_step), 1 if n_step_max is None else n_step_max,

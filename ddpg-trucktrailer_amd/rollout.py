@@ -72,7 +72,7 @@ class DDPGRollout(VectorStepper):
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -107,7 +107,18 @@ class DDPGRollout(VectorStepper):
         rows that came from the ring's side buffer (TrajectoryRing.load_side, expert.load_into_ring) -- every draw form hands the
         draw's index buffer on to learn(); the same launches, in both orders, with loss_shape, learn_log and graphs.  A ring with no
         side tuples is allowed (no row is a demonstration).  demo_loss.check_demo_loss names what is refused (td3, n_step > 1,
-        data-parallel ranks, the p2p exchange, TT_FORCE_DP)."""
+        data-parallel ranks, the p2p exchange, TT_FORCE_DP).
+        expert: None, or an mpc.ExpertLanes: lanes [0, expert.lanes) of the env are driven by the sampling MPC
+        expert, one launch per vector step between the policy launch and the env step, in every order and draw form and inside the
+        captured steps; their transitions land in the ring like any other lane's.  With demo_loss the ring rows of those lanes are
+        demonstration rows as well (a ring with no side tuples is the intended use); without it the expert only acts, which composes
+        with n_step, td3, loss_shape, the learn log and the episode log.  mpc.check_expert_lanes names what is refused (a stepper
+        that is not in ring mode, data-parallel ranks, the p2p exchange, TT_FORCE_DP, more lanes than the env has)."""
+        if expert is not None:
+            from ddpg_trucktrailer_amd.mpc import check_expert_lanes
+            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
+            check_expert_lanes(expert, n_envs=env.n_envs, data_parallel=ranks or dp_exchange == "p2p",
+                               force_dp=os.environ.get("TT_FORCE_DP") == "1")
         self.n_step = check_n_step(n_step)
         self.demo_loss = None
         if demo_loss is not None:
@@ -155,7 +166,7 @@ class DDPGRollout(VectorStepper):
         super().__init__(env, batch_size=batch_size, replay_slots=replay_slots, seed=seed, alpha=alpha, beta=beta, tau=tau, gamma=gamma,
                          fc1_dims=fc1_dims, fc2_dims=fc2_dims, agent=agent, capturable=use_graph, policy_workgroups=policy_workgroups,
                          policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail,
-                         td3=self.td3)
+                         td3=self.td3, expert=expert)
         self.batch_size = batch_size
         self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
         self.agent.demo_loss = self.demo_loss
@@ -180,7 +191,8 @@ class DDPGRollout(VectorStepper):
                 from ddpg_trucktrailer_amd.td3 import TD3Learner
                 self.learner = TD3Learner(self.agent, batch_size, self.ring, self.seed)
             elif self.td3 is None:
-                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape, demo_loss=self.demo_loss)
+                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape, demo_loss=self.demo_loss,
+                                            expert_lanes=self.expert.lanes if self.expert is not None and self.demo_loss is not None else None)
             self.agent.fused_learner = self.learner
             if self.dp and self.dp_exchange == "p2p":
                 self.learner.enable_p2p()
@@ -262,8 +274,12 @@ class DDPGRollout(VectorStepper):
         return self.ring.sample(self.batch_size, **ns)
 
     def _demo_rows(self, index):
-        """The torch path's demo_rows of a draw whose index the ring just left ([B, 2]: a side row has index[b, 0] < 0)."""
-        return {} if self.demo_loss is None else dict(demo_rows=index[:, 0] < 0)
+        """The torch path's demo_rows of a draw whose index the ring just left ([B, 2]: a side row has index[b, 0] < 0; under
+        expert lanes a ring row of a lane < expert.lanes is one too: mpc.expert_mask)."""
+        if self.demo_loss is None:
+            return {}
+        from ddpg_trucktrailer_amd.mpc import expert_mask
+        return dict(demo_rows=expert_mask(index, self.expert.lanes if self.expert is not None else 0))
 
     def _sample_key(self, u):
         return (self.seed + u * _SEED_STRIDE) & (2 ** 64 - 1)
@@ -695,7 +711,8 @@ class DDPGRollout(VectorStepper):
         return sd
 
     def demo_stats(self):
-        """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}.  Synchronises."""
+        """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}; with expert lanes the ring rows of those
+        lanes count as demonstration rows, as in the kernels.  Synchronises."""
         if self.learner is None or self.demo_loss is None:
             raise ValueError("demo_loss is off or the learner is the torch path (DDPGRollout(demo_loss=...))")
         return self.learner.demo_stats()
@@ -722,6 +739,7 @@ class DDPGRollout(VectorStepper):
         mine = self.demo_loss.as_tuple() if self.demo_loss is not None else None
         if have != mine:
             raise ValueError(f"the checkpoint was written with demo_loss = {have}, this loop has demo_loss = {mine}")
+        self.check_expert_state(sd)                                   # (before anything is written)
         self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])

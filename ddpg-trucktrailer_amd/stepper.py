@@ -16,12 +16,15 @@ from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 class VectorStepper:
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
-                 episode_log_detail=False, td3=None):
+                 episode_log_detail=False, td3=None, expert=None):
         """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold);
         td3: its TD3Config (Agent(td3=)), whose torch path draws its smoothing noise from a generator seeded with `seed`.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
         before any step or capture: the env step kernel logs every episode that ends in the loop, end_step = the loop's vector
-        step, and drain_episodes() collects the records.  episode_log_detail: the detailed log (episode_metrics.py)."""
+        step, and drain_episodes() collects the records.  episode_log_detail: the detailed log (episode_metrics.py).
+        expert: None, or an mpc.ExpertLanes: lanes [0, expert.lanes) are driven by the MPC expert -- one launch
+        between the policy launch and the env step writes their decisions over the policy's (ring mode only); the stepper owns
+        their plan [lanes, H]."""
         self.env, self.n, self.device, self.seed = env, env.n_envs, env.device, seed
         if episode_log:
             env.enable_episode_log(int(episode_log), detail=episode_log_detail)
@@ -56,6 +59,13 @@ class VectorStepper:
         # graph serves every ring position: a single-step graph and a graph of `graph_steps` steps are all there is
         self.ring_mode = self.fused_act and self.device.type == "cuda" and self.ring._env_counts
         self._view = self.ring.view() if self.ring_mode else None
+        self.expert, self.expert_plan = None, None
+        if expert is not None:
+            from ddpg_trucktrailer_amd.mpc import check_expert_lanes, check_mpc
+            self.expert = check_expert_lanes(expert, n_envs=self.n, ring_mode=self.ring_mode)
+            check_mpc(expert.mpc, action_scale=env.max_steer)
+            with torch.cuda.device(self.device):
+                self.expert_plan = torch.zeros((expert.lanes, expert.mpc.horizon), dtype=torch.float32, device=self.device)
 
     def _image(self):
         """The packed actor under two_images: the image packed at the start of the step, never the live weights learn() updates."""
@@ -97,6 +107,9 @@ class VectorStepper:
         device (after open_step).  Otherwise (CPU, torch actor) k selects them."""
         if self.ring_mode:
             self.policy_launch()
+            if self.expert is not None:       # the expert lanes' decisions over the policy's, in ring.act[t] and self.scaled
+                self.env.mpc_act_ring(self.expert.mpc, self.expert_plan, self.expert.lanes, self._view, self.high, self.scaled,
+                                      seed=self.expert.seed)
             self.env.step_ring(self.scaled, self._view, auto_reset=True)
             return
         ring = self.ring
@@ -113,9 +126,11 @@ class VectorStepper:
 
     def graph_key(self):
         """What captured launches of this stepper bake in: env.graph_epoch (reset seed, per-env-goal mode, pose pool), the ring's
-        side-buffer count, and the actor's parameter storages (the policy's packed-image struct is keyed on them, fused.py)."""
+        side-buffer count, the actor's parameter storages (the policy's packed-image struct is keyed on them, fused.py) and the
+        expert lanes' configuration (its numbers are kernel arguments)."""
         return (getattr(self.env, "graph_epoch", 0), self.ring.side_epoch,
-                fused.packed_key_of(self.agent.actor) if self.fused_act else None)
+                fused.packed_key_of(self.agent.actor) if self.fused_act else None,
+                self.expert.as_tuple() if self.expert is not None else None)
 
     def drain_episodes(self):
         """The env's episode log since the last drain: records sorted by (end_step, lane), end_step = the vector step it ended in."""
@@ -131,7 +146,8 @@ class VectorStepper:
         vector_steps, nets (four networks, six with TD3), ring, ou and env (with the episode log's state when it is on).  The
         caller has synchronised."""
         ag = self.agent
-        return {"seed": int(self.seed), "vector_steps": int(self.vector_steps),
+        ex = {} if self.expert is None else {"expert": list(self.expert.as_tuple()), "expert_plan": self.expert_plan.detach().cpu().clone()}
+        return {**ex, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
                 "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()} for n in self.net_names()},
                 "ring": self.ring.state_dict(), "ou": self.noise.x.detach().cpu().clone(),
                 "env": self.env.state_dict() if hasattr(self.env, "state_dict") else None}
@@ -143,9 +159,21 @@ class VectorStepper:
                 for k, v in getattr(self.agent, n).state_dict().items():
                     v.copy_(net_sd[k].to(v.device))
 
+    def check_expert_state(self, sd):
+        """ValueError when acting_state() `sd` was written with other expert lanes than this stepper's (or with none)."""
+        have = sd.get("expert")
+        have = (int(have[0]), tuple(have[1]), int(have[2])) if have is not None else None
+        mine = self.expert.as_tuple() if self.expert is not None else None
+        if have != mine:
+            raise ValueError(f"the checkpoint was written with expert = {have}, this loop has expert = {mine}")
+
     def load_acting_state(self, sd):
         """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are
-        captured again).  Seed and counters stay with the caller, which knows what bakes the seed in."""
+        captured again).  Seed and counters stay with the caller, which knows what bakes the seed in.  A checkpoint written with
+        other expert lanes (or none) is refused: the plan and the lanes' ring rows would not be this loop's."""
+        self.check_expert_state(sd)
+        if self.expert is not None:
+            self.expert_plan.copy_(sd["expert_plan"].to(self.expert_plan.device))
         self.ring.load_state_dict(sd["ring"])
         self.noise.x.copy_(sd["ou"].to(self.noise.x.device))
         if sd.get("env") is not None:

@@ -253,6 +253,23 @@ class TruckTrailerVecEnv:
                                              self._stream()))
         return mu_out
 
+    def mpc_act_ring(self, cfg, plan, lanes, ring_view, high, act_scaled, seed=0):
+        """One MPC decision for each of lanes [0, lanes), written over what the step's policy launch left for them
+        (include/ttenv.h: tt_env_mpc_act_ring): the normalised action into the running step's action row of the ring, times `high`
+        into act_scaled [N] f32.  plan [lanes, H] f32 is the lanes' plan, shifted as mpc_plan shifts it.  Between
+        fused.actor_act_ring and step_ring, on their stream.  Capturable."""
+        from ddpg_trucktrailer_amd.mpc import check_mpc, _check_array
+        lanes = int(lanes)
+        if not 1 <= lanes <= self.n_envs:
+            raise ValueError(f"mpc: lanes = {lanes} is outside [1, {self.n_envs}]")
+        check_mpc(cfg, action_scale=self.max_steer)
+        _check_array("plan", plan, (lanes, cfg.horizon), "float32", self.device)
+        _check_array("act_scaled", act_scaled, (self.n_envs,), "float32", self.device)
+        args = L.TTMpcArgs(cfg.horizon, cfg.samples, cfg.sigma, cfg.rho, cfg.temperature, cfg.gamma, cfg.k_lat, cfg.k_yaw,
+                           self.max_steer, int(seed) & (2 ** 64 - 1))
+        self._check(self.lib.tt_env_mpc_act_ring(self._h, C.byref(args), L.ptr(plan), lanes, C.byref(ring_view), float(high),
+                                                 L.ptr(act_scaled), self._stream()))
+
     # ------------------------------------------------------------------ held lanes (greedy evaluation)
     def enable_hold(self):
         """Allocate the handle's evaluation block (include/ttenv.h: tt_env_set_hold) and the tensors hold_records() fills.

@@ -345,6 +345,20 @@ typedef struct tt_mpc_args {
 int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan /* [N, H] in / out */, float *mu_out /* [N] */,
                     const uint8_t *live, double *returns_out, tt_stream_t stream);
 
+/* Expert lanes of a rollout loop: lanes [0, lanes) of the env make ONE tt_env_mpc_plan DECISION each -- the
+ * same noise keys, the plan read as zeros at step-in-episode 0, the same f64 sample-ordered update and shifted plan; plan is
+ * [lanes, H] -- and the decision replaces what the step's policy launch wrote for the lane:
+ *     ring->act[t][i] = U'_0              (the normalised action, what a demonstration file stores)
+ *     act_scaled[i]   = U'_0 * high       (ONE f32 product: the env step's input)
+ * with t = ring->cursor[0], the running step's slot as tt_actor_act_ring left it for tt_env_step_ring: launch it between the two,
+ * on their stream.  Lanes >= `lanes` keep every bit in ring->act and act_scaled; the env is only read; no other ring row, no
+ * counter and no noise state changes.  Capturable into a hipGraph: no allocation, no host read.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL handle, args, plan, ring, ring->cursor,
+ * ring->act or act_scaled; ring->slots < 1; lanes outside [1, ring->n_envs]; high not finite or <= 0; everything tt_env_mpc_plan
+ * refuses of args; a ring view of another number of envs than the handle's. */
+int tt_env_mpc_act_ring(tt_env *env, const tt_mpc_args *args, float *plan /* [lanes, H] in / out */, int32_t lanes,
+                        const tt_ring_view *ring, float high, float *act_scaled /* [N] */, tt_stream_t stream);
+
 /* Measurement hook (no reference counterpart): time each of the next `max_launches` step-kernel dispatches
  * with a HIP event pair bound to the dispatch itself (hipExtLaunchKernelGGL), on the stream they are launched
  * on; max_launches = 0 switches it off.  tt_env_profile_read waits for the recorded launches, adds them to the
@@ -998,6 +1012,22 @@ int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_ml
                            const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                            const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
                            const tt_loss_shape *shape /* may be NULL */, const tt_demo_loss *demo, tt_stream_t stream);
+/* Ring rows of EXPERT LANES as demonstration rows (tt_env_mpc_act_ring): with expert_lanes = M >= 0
+ *     demo_b = idx[2 b] < 0  or  idx[2 b + 1] < M
+ * -- a ring row's idx pair is (slot, lane), and lanes [0, M) of the loop's env are driven by the expert.  q, q_pi, the strict
+ * comparison, dq_eff and the code values are unchanged (code 1 / 2 for a ring row of an expert lane as well).  The count travels
+ * by value so that tt_demo_loss keeps its layout; the entry points above are these with expert_lanes = 0, bit for bit.
+ * TT_EINVAL in the entry point's own name, before any HIP call: expert_lanes < 0, and everything the entry point above refuses. */
+int tt_mlp_forward_save_demo_lanes(int n, int critic /* must be 1 */, const float *obs, const float *action, const tt_mlp_weights *w,
+                                   float *out, const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes,
+                                   tt_stream_t stream);
+int tt_mlp_actor_tail_demo_lanes(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                                 const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale,
+                                 int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq,
+                                 float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
+                                 float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
+                                 int32_t *tail_words, int32_t *gave_up_host, const tt_loss_shape *shape /* may be NULL */,
+                                 const tt_demo_loss *demo, int32_t expert_lanes, tt_stream_t stream);
 
 #ifdef __cplusplus
 }

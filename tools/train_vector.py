@@ -18,11 +18,17 @@ pre-activation.  Not with --td3.
 25): FILE holds obs, act, rew, obs2, done (expert.save_transitions_npz) and goes into the ring's side buffer; the batch rows drawn
 from it get the behaviour-cloning term L (mu - a)^2, by default only where Q(s, a) > Q(s, mu(s)).  Each line adds the demonstration
 rows of the block's last update, how many the filter let through and the term's value.  Not with --td3 or --n-step > 1.
+--expert-lanes M [--expert-horizon H] [--expert-samples S] [--expert-seed K]: expert lanes (DDPGRollout(expert=ExpertLanes(M,
+MPCConfig(horizon=H, samples=S), seed=K)); defaults H = 64, S = 256, K = the loop's seed): lanes [0, M) of the env
+are driven by the sampling MPC expert inside the captured step.  With --bc-weight L (no --demos needed) the ring rows of those lanes
+are demonstration rows.  Each line then splits the block's finished episodes and successes into lanes < M (the expert's) and lanes >= M
+(the policy's), from the episode log's lane field, so that the expert's successes are not read as the policy's.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
 Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
-       [--demos FILE.npz --bc-weight L [--no-q-filter]] [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+       [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M [--expert-horizon H] [--expert-samples S] [--expert-seed K]]
+       [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -65,10 +71,20 @@ if "--bc-weight" in sys.argv[1:]:
 if "--no-q-filter" in sys.argv[1:]:
     sys.argv.remove("--no-q-filter")
     q_filter = False
-if (demos is None) != (bc_weight is None):
-    sys.exit("--demos FILE.npz and --bc-weight L go together")
+expert_opt = {}
+for flag in ("--expert-lanes", "--expert-horizon", "--expert-samples", "--expert-seed"):
+    if flag in sys.argv[1:]:
+        at = sys.argv.index(flag)
+        expert_opt[flag[9:]] = int(sys.argv[at + 1])
+        del sys.argv[at:at + 2]
+if expert_opt and "lanes" not in expert_opt:
+    sys.exit("--expert-horizon / --expert-samples / --expert-seed need --expert-lanes M")
+if demos is not None and bc_weight is None:
+    sys.exit("--demos FILE.npz needs --bc-weight L")
+if bc_weight is not None and demos is None and not expert_opt:
+    sys.exit("--bc-weight L needs demonstrations: --demos FILE.npz or --expert-lanes M")
 demo_loss = None
-if demos is not None:
+if bc_weight is not None:
     from ddpg_trucktrailer_amd.demo_loss import DemoLoss
     demo_loss = DemoLoss(bc_weight, q_filter)
 eval_every, eval_lanes = None, 256
@@ -97,6 +113,12 @@ for at, arg in enumerate(sys.argv):
         break
 n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:7])
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 27
+expert = None
+if expert_opt:
+    from ddpg_trucktrailer_amd.mpc import ExpertLanes, MPCConfig
+    # horizon 64: what the planner's record supports from the env's own reset poses
+    expert = ExpertLanes(expert_opt["lanes"], MPCConfig(horizon=expert_opt.get("horizon", 64), samples=expert_opt.get("samples", 256)),
+                         seed=expert_opt.get("seed", seed))
 graph_steps = int(sys.argv[8]) if len(sys.argv) > 8 else (20 if slots <= 1024 else 0)      # (as before: no graphs past 1024 slots)
 env = TruckTrailerVecEnv(n)
 env.reset(seed=seed)
@@ -105,7 +127,7 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss)
+                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert)
 if demos is not None:
     from ddpg_trucktrailer_amd.expert import load_transitions_npz
     d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
@@ -113,7 +135,8 @@ if demos is not None:
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else "") +
       (f", {loss_shape}" if loss_shape is not None else "") +
-      (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else ""), flush=True)
+      (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else "") +
+      (f", {expert}" if expert is not None else ""), flush=True)
 
 
 def learn_line(rec):
@@ -128,6 +151,14 @@ def learn_line(rec):
 
 def demo_line(st):
     return f"  demonstrations {st['demo_rows']} rows, {st['applied']} applied, bc loss {st['bc_loss']:.4g}"
+
+
+def lanes_line(r, m_lanes):
+    """The block's finished episodes and successes by lane group: the expert's lanes [0, M) and the policy's."""
+    ex = r["lane"] < m_lanes
+    ok = r["success"]
+    return (f"  expert lanes: episodes {int(ex.sum().item())} successes {int((ok & ex).sum().item())}"
+            f"  policy lanes: episodes {int((~ex).sum().item())} successes {int((ok & ~ex).sum().item())}")
 
 
 tracker = BestModelTracker()
@@ -157,7 +188,8 @@ while s < total:
           f"successes {int(r['success'].sum().item()):6d} ({100 * r['success'].double().sum().item() / e:4.1f} %)  "
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
           f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}"
-          f"{demo_line(loop.demo_stats()) if demo_loss is not None else ''}  "
+          f"{demo_line(loop.demo_stats()) if demo_loss is not None else ''}"
+          f"{lanes_line(r, expert.lanes) if expert is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
     if evaluator is not None and blocks % eval_every == 0:
