@@ -141,6 +141,11 @@ class TTDemoLoss(C.Structure):
                 ("dq_eff", C.c_void_p), ("code", C.c_void_p)]
 
 
+class TTDemoLabels(C.Structure):
+    """tt_demo_labels (include/ttenv.h): the ring's label array [slots, n_envs] f32 and the labelled lanes [first, first + count)."""
+    _fields_ = [("label", C.c_void_p), ("n_envs", C.c_int32), ("slots", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
+
+
 class TTMpcArgs(C.Structure):
     """tt_mpc_args (include/ttenv.h: tt_env_mpc_plan)."""
     _fields_ = [("horizon", C.c_int32), ("samples", C.c_int32)] + \
@@ -295,6 +300,15 @@ _SIGNATURES = {
                                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                                C.POINTER(TTFc2Images), _P, _P, _P, C.POINTER(TTLossShape), C.POINTER(TTDemoLoss),
                                                C.c_int32, _P]),
+    "tt_env_mpc_label_ring": (C.c_int, [_P, C.POINTER(TTMpcArgs), _P, C.c_int32, C.c_int32, C.POINTER(TTRingView), _P, C.c_float, _P,
+                                        _P]),
+    "tt_mlp_forward_save_demo_labels": (C.c_int, [_I, _I, _P, _P, C.POINTER(TTMlpWeights), _P, C.POINTER(TTMlpSaved), _P,
+                                                  C.POINTER(TTDemoLoss), C.c_int32, C.POINTER(TTDemoLabels), _P]),
+    "tt_mlp_actor_tail_demo_labels": (C.c_int, [_I, _P, _P, C.POINTER(TTMlpWeights), _P, _P, C.POINTER(TTMlpSaved),
+                                                C.POINTER(TTMlpBwdWs), C.POINTER(TTMlpWeights), C.c_float, _I, _P, _P, _P, _P, _P,
+                                                C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                                C.POINTER(TTFc2Images), _P, _P, _P, C.POINTER(TTLossShape), C.POINTER(TTDemoLoss),
+                                                C.c_int32, C.POINTER(TTDemoLabels), _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

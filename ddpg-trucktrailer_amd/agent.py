@@ -136,14 +136,23 @@ class Agent():
         states, actions, rewards, states_, done = self.memory.sample_buffer(self.batch_size)
         self.learn_batch(states, actions, rewards, states_, done)
 
-    def learn_batch(self, states, actions, rewards, states_, done, discount=None, eps=None, full=None, demo_rows=None):
+    def learn_batch(self, states, actions, rewards, states_, done, discount=None, eps=None, full=None, demo_rows=None,
+                    label_rows=None, labels=None):
         # discount: what multiplies q' in the target (default gamma); gamma ** n for a batch of n-step tuples (TrajectoryRing.sample)
         # eps, full: TD3 only (see _learn_batch_td3)
         # demo_rows (with demo_loss): [B] bool, the rows that are demonstrations (None: none is)
+        # label_rows, labels (with demo_loss; together): [B] bool and [B] f32 -- on a labelled row the cloning target is the label
+        # (the expert's decision on the row's state) and the Q-filter is skipped; it wins over demo_rows
         discount = self.gamma if discount is None else discount
         demo = self.demo_loss
         if demo_rows is not None and demo is None:
             raise ValueError("demo_rows without demo_loss (Agent(demo_loss=...))")
+        if (label_rows is None) != (labels is None):
+            raise ValueError("label_rows and labels go together ([B] bool and [B] f32)")
+        if label_rows is not None and demo is None:
+            raise ValueError("label_rows without demo_loss (Agent(demo_loss=...))")
+        if label_rows is not None and self.td3 is not None:
+            raise ValueError("label_rows with td3 is not supported")
         if self.td3 is not None:
             return self._learn_batch_td3(states, actions, rewards, states_, done, discount, eps, full)
         with T.no_grad():
@@ -184,15 +193,21 @@ class Agent():
             mu = self.actor.forward(states)
             q_pi = self.critic.forward(states, mu)
             actor_loss = T.mean(-q_pi)
-        if demo is not None and demo_rows is not None:
+        if demo is not None and (demo_rows is not None or label_rows is not None):
             # the cloning term on the demonstration rows [that pass the Q-filter]: q = Q(s, a) of the forward that PRECEDED the
             # critic step, q_pi = Q(s, mu(s)) through the UPDATED critic -- one Adam step apart (demo_loss.py); strict, NaN = out
             with T.no_grad():
-                m = demo_rows.view(-1).to(device=mu.device, dtype=T.bool)
+                m = (demo_rows.view(-1).to(device=mu.device, dtype=T.bool) if demo_rows is not None
+                     else T.zeros(mu.shape[0], dtype=T.bool, device=mu.device))
                 if demo.q_filter:
                     m = m & (critic_value.view(-1) > q_pi.view(-1))
+                target_a = actions.view(-1)
+                if label_rows is not None:
+                    lab = label_rows.view(-1).to(device=mu.device, dtype=T.bool)
+                    m = m | lab
+                    target_a = T.where(lab, labels.view(-1).to(device=mu.device, dtype=mu.dtype), target_a)
             self.last_demo_mask = m
-            d = mu.view(-1) - actions.view(-1)
+            d = mu.view(-1) - target_a
             actor_loss = actor_loss + demo.bc_weight * T.sum(m.to(mu.dtype) * d * d) / mu.shape[0]
         for p, g in zip(self._actor_params, T.autograd.grad(actor_loss, self._actor_params)):
             p.grad = g

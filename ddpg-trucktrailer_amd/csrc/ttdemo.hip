@@ -15,6 +15,9 @@
 // A row with m = 0 keeps the bits of dQ/da, so a batch without demonstration rows leaves the bits of the launches these stand in for.
 // The _lanes entry points take expert_lanes by value -- tt_demo_loss keeps its layout -- and make a ring row of
 // a lane < expert_lanes a demonstration row as well; the entry points without the count are those with 0, the same launches.
+// The _labels entry points take a tt_demo_labels as well: a ring row of a labelled lane clones the ring's label
+// (the expert's decision on the state the policy acted in) in place of the stored action, unfiltered, code 3; with NULL they are the
+// _lanes entry points, the same launches.  The label's fields travel in DemoIn (no further kernel).
 #include "ttlearn_host.h"
 
 namespace {
@@ -60,7 +63,8 @@ __global__ __launch_bounds__(64 * NW) void k_actor_tail_demo(const int n, const 
 }
 
 // what both entry points refuse of a tt_demo_loss: TT_OK, or TT_EINVAL with "<who>: <reason>"
-int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, const int32_t expert_lanes, DemoIn &out) {
+int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, const int32_t expert_lanes, const tt_demo_labels *lb,
+                DemoIn &out) {
     if (!dl) return fail(TT_EINVAL, "%s: demo is NULL", who);
     if (expert_lanes < 0) return fail(TT_EINVAL, "%s: expert_lanes = %d is negative", who, (int)expert_lanes);
     if (!std::isfinite(dl->k) || dl->k < 0.f) return fail(TT_EINVAL, "%s: demo->k = %g is not a finite number >= 0", who, (double)dl->k);
@@ -68,7 +72,20 @@ int refuse_demo(const char *who, const tt_demo_loss *dl, const float *dq_da, con
     if (dl->q_filter && !dl->q) return fail(TT_EINVAL, "%s: demo->q is NULL with q_filter set", who);
     if (!dq_da) return fail(TT_EINVAL, "%s: dq_da is NULL (the true derivative has a buffer of its own)", who);
     if (dl->dq_eff == dq_da) return fail(TT_EINVAL, "%s: demo->dq_eff is dq_da", who);
-    out = DemoIn{dl->a, dl->idx, dl->q, dl->k, dl->q_filter ? 1 : 0, dl->dq_eff, dl->code, (int)expert_lanes};
+    out = DemoIn{dl->a, dl->idx, dl->q, dl->k, dl->q_filter ? 1 : 0, dl->dq_eff, dl->code, (int)expert_lanes, 0, nullptr, 0, 0, 0};
+    if (lb) {
+        if (!lb->label) return fail(TT_EINVAL, "%s: labels->label is NULL", who);
+        if (lb->n_envs < 1 || lb->slots < 1)
+            return fail(TT_EINVAL, "%s: labels of %d envs and %d slots, not >= 1 each", who, (int)lb->n_envs, (int)lb->slots);
+        if (lb->first < 0) return fail(TT_EINVAL, "%s: labels->first = %d is negative", who, (int)lb->first);
+        if (lb->count < 1) return fail(TT_EINVAL, "%s: labels->count = %d, not >= 1", who, (int)lb->count);
+        if ((int64_t)lb->first + (int64_t)lb->count > (int64_t)lb->n_envs)
+            return fail(TT_EINVAL, "%s: labelled lanes [%d, %d + %d) leave the %d envs", who, (int)lb->first, (int)lb->first, (int)lb->count,
+                        (int)lb->n_envs);
+        if (lb->first < expert_lanes)
+            return fail(TT_EINVAL, "%s: labels->first = %d overlaps the %d expert lanes", who, (int)lb->first, (int)expert_lanes);
+        out.label_first = lb->first; out.label = lb->label; out.label_n = lb->n_envs; out.label_slots = lb->slots; out.label_count = lb->count;
+    }
     return TT_OK;
 }
 
@@ -78,9 +95,10 @@ extern "C" {
 
 // both forms of the forward: `who` names the entry point in every refusal
 static int forward_save_demo(const char *who, int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
-                             const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes, tt_stream_t stream) {
+                             const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes,
+                             const tt_demo_labels *labels, tt_stream_t stream) {
     DemoIn din;
-    if (const int rc = refuse_demo(who, demo, dq_da, expert_lanes, din)) return rc;
+    if (const int rc = refuse_demo(who, demo, dq_da, expert_lanes, labels, din)) return rc;
     if (!critic) return fail(TT_EINVAL, "%s: the actor has no demonstration form (the term is in the critic's pass on (s, mu(s)))", who);
     if (n < 0) return fail(TT_EINVAL, "%s: n = %d rows, not >= 0", who, n);
     if (!obs || !out || !action) return fail(TT_EINVAL, "%s: obs, action or out is NULL", who);
@@ -95,13 +113,21 @@ static int forward_save_demo(const char *who, int n, int critic, const float *ob
 
 int tt_mlp_forward_save_demo(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
                              const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, tt_stream_t stream) {
-    return forward_save_demo("tt_mlp_forward_save_demo", n, critic, obs, action, w, out, saved, dq_da, demo, 0, stream);
+    return forward_save_demo("tt_mlp_forward_save_demo", n, critic, obs, action, w, out, saved, dq_da, demo, 0, nullptr, stream);
 }
 
 int tt_mlp_forward_save_demo_lanes(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
                                    const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes,
                                    tt_stream_t stream) {
-    return forward_save_demo("tt_mlp_forward_save_demo_lanes", n, critic, obs, action, w, out, saved, dq_da, demo, expert_lanes, stream);
+    return forward_save_demo("tt_mlp_forward_save_demo_lanes", n, critic, obs, action, w, out, saved, dq_da, demo, expert_lanes, nullptr,
+                             stream);
+}
+
+int tt_mlp_forward_save_demo_labels(int n, int critic, const float *obs, const float *action, const tt_mlp_weights *w, float *out,
+                                    const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes,
+                                    const tt_demo_labels *labels, tt_stream_t stream) {
+    return forward_save_demo("tt_mlp_forward_save_demo_labels", n, critic, obs, action, w, out, saved, dq_da, demo, expert_lanes, labels,
+                             stream);
 }
 
 static int actor_tail_demo(const char *who, int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out,
@@ -109,9 +135,10 @@ static int actor_tail_demo(const char *who, int n, const float *obs, const float
                            int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq, float *const *targets,
                            const int64_t *step_dev, float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
                            const tt_fc2_images *images, const float *bias_corr, int32_t *tail_words, int32_t *gave_up_host,
-                           const tt_loss_shape *shape, const tt_demo_loss *demo, int32_t expert_lanes, tt_stream_t stream) {
+                           const tt_loss_shape *shape, const tt_demo_loss *demo, int32_t expert_lanes, const tt_demo_labels *labels,
+                           tt_stream_t stream) {
     DemoIn din;
-    if (const int rc = refuse_demo(who, demo, dq_da, expert_lanes, din)) return rc;
+    if (const int rc = refuse_demo(who, demo, dq_da, expert_lanes, labels, din)) return rc;
     if (shape)
         if (const int rc = refuse_shape(who, shape)) return rc;
     Tail T;
@@ -132,7 +159,7 @@ int tt_mlp_actor_tail_demo(int n, const float *obs, const float *mu, const tt_ml
                            const tt_loss_shape *shape, const tt_demo_loss *demo, tt_stream_t stream) {
     return actor_tail_demo("tt_mlp_actor_tail_demo", n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params, exp_avg,
                            exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words,
-                           gave_up_host, shape, demo, 0, stream);
+                           gave_up_host, shape, demo, 0, nullptr, stream);
 }
 
 int tt_mlp_actor_tail_demo_lanes(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
@@ -144,7 +171,19 @@ int tt_mlp_actor_tail_demo_lanes(int n, const float *obs, const float *mu, const
                                  int32_t expert_lanes, tt_stream_t stream) {
     return actor_tail_demo("tt_mlp_actor_tail_demo_lanes", n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params,
                            exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words,
-                           gave_up_host, shape, demo, expert_lanes, stream);
+                           gave_up_host, shape, demo, expert_lanes, nullptr, stream);
+}
+
+int tt_mlp_actor_tail_demo_labels(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                                  const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale,
+                                  int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq,
+                                  float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
+                                  int32_t *tail_words, int32_t *gave_up_host, const tt_loss_shape *shape, const tt_demo_loss *demo,
+                                  int32_t expert_lanes, const tt_demo_labels *labels, tt_stream_t stream) {
+    return actor_tail_demo("tt_mlp_actor_tail_demo_labels", n, obs, mu, critic, q_out, dq_da, saved, ws, grads, row_scale, count, params,
+                           exp_avg, exp_avg_sq, targets, step_dev, lr, beta1, beta2, eps, weight_decay, tau, images, bias_corr, tail_words,
+                           gave_up_host, shape, demo, expert_lanes, labels, stream);
 }
 
 }  // extern "C"

@@ -1112,9 +1112,21 @@ struct MpcRing {
     float high;
 };
 struct MpcNoRing {};
+// Expert lanes [0, expert) as MpcRing, and LABELLED LANES [expert, n) behind them (tt_env_mpc_label_ring): the decision of a
+// labelled lane goes to the ring's label row of the running step and nowhere else -- the lane executes what the policy wrote.
+struct MpcLabel {
+    const int *cursor;      // [0]: the running step's slot t (left by tt_actor_act_ring)
+    float *act;             // the ring's action rows [slots, n_envs] (expert lanes only; unused with expert = 0)
+    float *act_scaled;      // [n_envs] (expert lanes only)
+    float *label;           // the ring's label rows [slots, n_envs]
+    int n_envs, slots;
+    float high;
+    int expert;             // M: workgroup i < M stores as MpcRing, i >= M stores label[t][i]
+};
 
-// One planner, two launches: k_mpc_plan (RING = MpcNoRing: mu_out, live, returns_out) and k_mpc_act_ring (RING = MpcRing: workgroup
-// i < n plans for lane i of the first n lanes, and U'_0 goes to the ring).  Everything before the last store is the same text.
+// One planner, three launches: k_mpc_plan (RING = MpcNoRing: mu_out, live, returns_out), k_mpc_act_ring (RING = MpcRing: workgroup
+// i < n plans for lane i of the first n lanes, and U'_0 goes to the ring) and k_mpc_label_ring (RING = MpcLabel: the same for lanes
+// < ring.expert, U'_0 to the label row for the others).  Everything before the last store is the same text.
 template <bool PER_ENV, class RING>
 __device__ __forceinline__ void mpc_plan_body(const KParams P, const int n, const Bufs b, const MpcK m, float *plan, float *mu_out,
                                               const uint8_t *live, double *returns_out, const RING ring) {
@@ -1198,6 +1210,16 @@ __device__ __forceinline__ void mpc_plan_body(const KParams P, const int n, cons
                 const int t = ring.cursor[0];
                 if ((unsigned)t < (unsigned)ring.slots) ring.act[(size_t)t * ring.n_envs + i] = un;
                 ring.act_scaled[i] = un * ring.high;
+            } else if constexpr (std::is_same<RING, MpcLabel>::value) {
+                // an expert lane: MpcRing's two stores; a labelled lane: label[t][i] = U'_0 alone (ring.act[t][i] and act_scaled[i]
+                // keep the policy's bits).  i is the workgroup's lane: the branch is uniform
+                const int t = ring.cursor[0];
+                if (i < ring.expert) {
+                    if ((unsigned)t < (unsigned)ring.slots) ring.act[(size_t)t * ring.n_envs + i] = un;
+                    ring.act_scaled[i] = un * ring.high;
+                } else if ((unsigned)t < (unsigned)ring.slots) {
+                    ring.label[(size_t)t * ring.n_envs + i] = un;
+                }
             } else {
                 mu_out[i] = un;
             }
@@ -1218,6 +1240,13 @@ __global__ __launch_bounds__(BLOCK) void k_mpc_plan(const KParams P, const int n
 template <bool PER_ENV>
 __global__ __launch_bounds__(BLOCK) void k_mpc_act_ring(const KParams P, const int lanes, const Bufs b, const MpcK m, float *plan,
                                                         const MpcRing ring) {
+    mpc_plan_body<PER_ENV>(P, lanes, b, m, plan, nullptr, nullptr, nullptr, ring);
+}
+
+// lanes [0, lanes) of the env, lanes = expert + labelled: grid = lanes; plan is [lanes, H]
+template <bool PER_ENV>
+__global__ __launch_bounds__(BLOCK) void k_mpc_label_ring(const KParams P, const int lanes, const Bufs b, const MpcK m, float *plan,
+                                                          const MpcLabel ring) {
     mpc_plan_body<PER_ENV>(P, lanes, b, m, plan, nullptr, nullptr, nullptr, ring);
 }
 
@@ -2315,6 +2344,37 @@ int tt_env_mpc_act_ring(tt_env *env, const tt_mpc_args *args, float *plan, int32
     TT_HIP(env, hipSetDevice(env->device));
     by_per_env(env, [&](auto per_env) {
         hipLaunchKernelGGL(k_mpc_act_ring<decltype(per_env)::value>, dim3(lanes), dim3(BLOCK), lds, stream, env->kp, (int)lanes, env->b, m,
+                           plan, r);
+    });
+    TT_HIP(env, hipGetLastError());
+    return TT_OK;
+}
+
+int tt_env_mpc_label_ring(tt_env *env, const tt_mpc_args *args, float *plan, int32_t expert_lanes, int32_t label_lanes,
+                          const tt_ring_view *ring, float *label, float high, float *act_scaled, tt_stream_t stream) {
+    const char *const who = "tt_env_mpc_label_ring";
+    TT_HANDLE(env);
+    // (before the handle is read: these hold for any handle)
+    if (!args || !plan || !ring || !label) return tthost::fail(TT_EINVAL, "%s: args, plan, ring and label are required", who);
+    if (expert_lanes < 0) return tthost::fail(TT_EINVAL, "%s: expert_lanes = %d is negative", who, (int)expert_lanes);
+    if (label_lanes < 1) return tthost::fail(TT_EINVAL, "%s: label_lanes = %d, not >= 1", who, (int)label_lanes);
+    if (!ring->cursor) return tthost::fail(TT_EINVAL, "%s: ring->cursor is required", who);
+    if (expert_lanes > 0 && (!ring->act || !act_scaled))
+        return tthost::fail(TT_EINVAL, "%s: ring->act and act_scaled are required with expert_lanes > 0", who);
+    if (ring->slots < 1) return tthost::fail(TT_EINVAL, "%s: a ring of %d slots", who, ring->slots);
+    if ((int64_t)expert_lanes + (int64_t)label_lanes > (int64_t)ring->n_envs)
+        return tthost::fail(TT_EINVAL, "%s: expert_lanes + label_lanes = %d + %d is more than n_envs = %d", who, (int)expert_lanes,
+                            (int)label_lanes, ring->n_envs);
+    if (!std::isfinite(high) || !(high > 0.f)) return tthost::fail(TT_EINVAL, "%s: high is not finite or <= 0", who);
+    MpcK m;
+    size_t lds;
+    if (const int rc = mpc_constants(who, *args, m, lds)) return rc;
+    if (ring->n_envs != env->n) return tthost::fail(TT_EINVAL, "%s: the ring view has %d envs, this handle %d", who, ring->n_envs, env->n);
+    const int lanes = (int)(expert_lanes + label_lanes);
+    const MpcLabel r{ring->cursor, ring->act, act_scaled, label, ring->n_envs, ring->slots, high, (int)expert_lanes};
+    TT_HIP(env, hipSetDevice(env->device));
+    by_per_env(env, [&](auto per_env) {
+        hipLaunchKernelGGL(k_mpc_label_ring<decltype(per_env)::value>, dim3(lanes), dim3(BLOCK), lds, stream, env->kp, lanes, env->b, m,
                            plan, r);
     });
     TT_HIP(env, hipGetLastError());

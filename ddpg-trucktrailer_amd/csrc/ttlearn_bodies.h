@@ -280,6 +280,9 @@ struct EarlyW {
 // else (slot, lane) of a ring row, a demonstration row too where lane < lanes: the loop's expert lanes),
 // q [n]: Q(s, a) of learn()'s FIRST launch (the critic before this update; read with q_filter only), k = 2 lambda.
 // Out: dq_eff [n] and code [n] (0 a ring row, 1 a demonstration row the filter left out, 2 a demonstration row applied).
+// LABELS: a ring row (slot, lane) with label_first <= lane < label_first + label_count is a LABELLED row -- its
+// target is label[slot * label_n + lane], the expert's decision on the state the policy acted in, the filter does not apply (q rates
+// the STORED action) and its code is 3.  label_count = 0 (label unread): no row is labelled, the bits of the form without labels.
 struct DemoIn {
     const float *a;
     const int *idx;
@@ -289,6 +292,9 @@ struct DemoIn {
     float *dq_eff;
     int *code;
     int lanes;      // expert lanes of the loop's env: a ring row (idx[2 b] >= 0) of lane idx[2 b + 1] < lanes is a demonstration row too
+    int label_first;            // labelled lanes [label_first, label_first + label_count), label_first >= lanes
+    const float *label;         // [label_slots, label_n]: the ring's label array
+    int label_n, label_slots, label_count;
 };
 template <bool CRITIC, class Hook = NoHook, bool DEMO = false>
 __device__ __forceinline__ void fwd_small_body(const int n, const float *__restrict__ obs,
@@ -603,9 +609,12 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
 #pragma unroll
         for (int rr = 0; rr < TR / NW; ++rr) {
             const int row = min(row0 + wave * (TR / NW) + rr, n - 1);
-            demo_a[rr] = demo.a[row];
-            // a side row, or a ring row of an expert lane (lanes = 0: idx[2 row + 1] >= 0 always, the side-row test alone)
-            demo_i[rr] = (demo.idx[2 * row] < 0 || demo.idx[2 * row + 1] < demo.lanes) ? -1 : 0;
+            const int slot = demo.idx[2 * row], ln = demo.idx[2 * row + 1];
+            // a labelled row (a slot past the array is never read): the label is the target, and its load hangs on idx's
+            const bool lab = (unsigned)slot < (unsigned)demo.label_slots && (unsigned)(ln - demo.label_first) < (unsigned)demo.label_count;
+            demo_a[rr] = lab ? demo.label[(size_t)slot * demo.label_n + ln] : demo.a[row];
+            // else a side row, or a ring row of an expert lane (lanes = 0: idx[2 row + 1] >= 0 always, the side-row test alone)
+            demo_i[rr] = lab ? 1 : ((slot < 0 || ln < demo.lanes) ? -1 : 0);
             demo_q[rr] = demo.q_filter ? demo.q[row] : 0.f;
         }
     }
@@ -681,11 +690,12 @@ __device__ __forceinline__ void fwd_small_body(const int n, const float *__restr
                 // gives the policy's: q > q_pi, false for a NaN on either side]; the row's d(loss)/d(pre) is linear in dQ/da, so
                 // the cloning term (2 lambda / B) m (mu - a) (1 - mu^2) is dQ/da - k (mu - a) through the factor as it is
                 const float a_b = demo_a[rr], q_b = demo_q[rr];
-                const bool is_demo = demo_i[rr] < 0, m = is_demo && (!demo.q_filter || q_b > v);
+                const bool is_lab = demo_i[rr] > 0;    // a labelled row: never filtered (no launch computes Q(s, a*))
+                const bool is_demo = demo_i[rr] < 0, m = is_lab || (is_demo && (!demo.q_filter || q_b > v));
                 const float dq_eff = m ? fmaf(-demo.k, av - a_b, dqa) : dqa;
                 dq_da[row] = dqa;                      // (the true derivative: the learn log's statistics keep their meaning)
                 demo.dq_eff[row] = dq_eff;
-                demo.code[row] = m ? 2 : (is_demo ? 1 : 0);
+                demo.code[row] = is_lab ? 3 : (m ? 2 : (is_demo ? 1 : 0));
                 if (dq_words)
                     __hip_atomic_store(dq_words + row, ((unsigned long long)dq_epoch << 32) | (unsigned long long)__float_as_uint(dq_eff),
                                        __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);

@@ -185,7 +185,7 @@ class LearnLog:
 
 
 class FusedLearner:
-    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None, expert_lanes=None):
+    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None, expert_lanes=None, labels=None):
         """fc2_images (None = on unless TT_LEARN_F32=1): the 400 x 300 products of learn() on the f16 MFMA from pre-split
         images of the four networks' fc2 (include/ttenv.h: tt_mlp_weights.fc2_img) that the optimizer launches keep current;
         off = every product on the exact-f32 MFMA straight from the weights.
@@ -197,12 +197,28 @@ class FusedLearner:
         tt_demo_loss), the same number of launches.  Composes with loss_shape.  Not with data-parallel ranks.
         expert_lanes (with demo_loss; None = the entry points above): a whole number >= 0 -- the ring rows of lanes < expert_lanes
         are demonstration rows as well (the loop's mpc.ExpertLanes) and the actor's step goes through the
-        _lanes entry points, which with 0 leave the bits of the entry points above."""
+        _lanes entry points, which with 0 leave the bits of the entry points above.
+        labels (with demo_loss; None = the entry points above): (first, count) -- the ring rows of lanes [first, first + count) are
+        LABELLED rows (the loop's mpc.ExpertLabels): their cloning target is the ring's label array, handed
+        over as a third entry or with set_label_array() before the first update, the filter does not apply to them and the actor's step goes through
+        the _labels entry points.  first >= expert_lanes (None counts as 0)."""
         import os
         if expert_lanes is not None and not (isinstance(expert_lanes, int) and not isinstance(expert_lanes, bool) and expert_lanes >= 0):
             raise ValueError(f"expert_lanes = {expert_lanes!r} is not None or a whole number >= 0")
         if expert_lanes is not None and demo_loss is None:
             raise ValueError(f"expert_lanes = {expert_lanes} without demo_loss: the learner has nothing to do with the lanes")
+        label_array = None
+        if isinstance(labels, (tuple, list)) and len(labels) == 3:      # (first, count, the ring's label array)
+            labels, label_array = tuple(labels[:2]), labels[2]
+        if labels is not None:
+            ok = isinstance(labels, (tuple, list)) and len(labels) == 2 and all(isinstance(v, int) and not isinstance(v, bool) for v in labels)
+            if not ok or labels[0] < 0 or labels[1] < 1:
+                raise ValueError(f"labels = {labels!r} is not None or (first >= 0, count >= 1) in whole numbers")
+            if demo_loss is None:
+                raise ValueError(f"labels = {tuple(labels)} without demo_loss: the learner has nothing to do with the labels")
+            if labels[0] < (expert_lanes or 0):
+                raise ValueError(f"labels = {tuple(labels)}: first = {labels[0]} overlaps the {expert_lanes} expert lanes")
+            labels = (int(labels[0]), int(labels[1]))
         assert fused.supported(agent.actor) and fused.supported(agent.critic)
         self.agent, self.B = agent, int(batch_size)
         dev = self.dev = agent.actor.fc1.weight.device
@@ -246,6 +262,9 @@ class FusedLearner:
             self.set_loss_shape(loss_shape)
         self.demo_loss, self.dq_eff, self.code, self._demo_actions = None, None, None, None
         self.expert_lanes = expert_lanes
+        self.labels, self.label_array, self._labels_struct, self._demo_index = labels, None, None, None
+        if label_array is not None:
+            self.set_label_array(label_array)
         if demo_loss is not None:
             self.set_demo_loss(demo_loss)
 
@@ -283,21 +302,47 @@ class FusedLearner:
         return L.TTDemoLoss(a=actions.data_ptr(), idx=demo_index.data_ptr(), q=self.q.data_ptr(), k=dl.k(), q_filter=int(dl.q_filter),
                             dq_eff=self.dq_eff.data_ptr(), code=self.code.data_ptr())
 
+    def set_label_array(self, label):
+        """The ring's label array [slots, N] f32 (TrajectoryRing.enable_labels) that labelled rows take their target from; before
+        anything is captured (its address is a launch argument)."""
+        if self.labels is None:
+            raise ValueError("labels is off (FusedLearner(labels=(first, count)))")
+        first, count = self.labels
+        ok = torch.is_tensor(label) and label.dtype == torch.float32 and label.dim() == 2 and label.is_contiguous() and label.device == self.dev
+        if not ok:
+            raise ValueError("labels: the label array is not a contiguous [slots, N] f32 tensor on the learner's device")
+        if first + count > label.shape[1]:
+            raise ValueError(f"labels: lanes [{first}, {first + count}) leave the label array's {label.shape[1]} lanes")
+        self.label_array = label
+        self._labels_struct = L.TTDemoLabels(label=label.data_ptr(), n_envs=int(label.shape[1]), slots=int(label.shape[0]),
+                                             first=first, count=count)
+
     def demo_stats(self):
         """Of the last update (synchronises): {"demo_rows": rows that came from the side buffer or, with expert_lanes, from an
         expert lane of the ring, "applied": those the filter let
         through, "bc_loss": lambda (1/B) sum over the applied rows of (mu - a)^2, formed on the host in f64 from code, mu and the
-        batch's stored actions}."""
+        batch's stored actions}.  With labels also "labelled": the labelled rows (code 3) -- they count as applied (not as
+        demo_rows) and enter bc_loss with their label as a."""
         if self.demo_loss is None:
             raise ValueError("demo_loss is off (FusedLearner(demo_loss=...))")
+        lab = {} if self.labels is None else {"labelled": 0}
         if self._demo_actions is None:
-            return {"demo_rows": 0, "applied": 0, "bc_loss": 0.0}
-        torch.cuda.synchronize(self.dev)
+            return {"demo_rows": 0, "applied": 0, "bc_loss": 0.0, **lab}
+        if self.dev.type == "cuda":
+            torch.cuda.synchronize(self.dev)
         code = self.code.cpu()
-        on = code == 2
-        d = (self.mu.double().cpu() - self._demo_actions.double().cpu().view(-1))[on]
-        return {"demo_rows": int((code > 0).sum().item()), "applied": int(on.sum().item()),
-                "bc_loss": float(self.demo_loss.bc_weight * (d * d).sum().item() / self.B)}
+        a = self._demo_actions.double().cpu().view(-1)
+        if self.labels is not None:
+            from ddpg_trucktrailer_amd.mpc import gather_labels
+            three = code == 3
+            # (the labelled rows alone are gathered: a side row's second index counts side tuples and may be >= N)
+            _, values = gather_labels(self.label_array.cpu(), self._demo_index.cpu(), *self.labels)
+            a = torch.where(three, values.double(), a)
+            lab = {"labelled": int(three.sum().item())}
+        on = code >= 2
+        d = (self.mu.double().cpu() - a)[on]
+        return {"demo_rows": int(((code == 1) | (code == 2)).sum().item()), "applied": int(on.sum().item()),
+                "bc_loss": float(self.demo_loss.bc_weight * (d * d).sum().item() / self.B), **lab}
 
     def _nets(self):
         """The networks this learner keeps weight structs and fc2 images of (a subclass with more networks overrides this)."""
@@ -360,12 +405,19 @@ class FusedLearner:
         if self.use_images and not torch.cuda.is_current_stream_capturing():
             self.refresh_images()          # (a capture holds launches only: its owner looks before it replays)
 
+    def _labels_ref(self):
+        if self._labels_struct is None:
+            raise ValueError("labels is set: the learner needs the ring's label array first (set_label_array)")
+        return C.byref(self._labels_struct)
+
     def _fwd(self, net, obs, action, out, saved=None, dq_da=None, demo=None):
         self._fresh()
         if demo is not None:       # the critic on (s, mu(s)) with the demonstration term in dq_eff (csrc/ttdemo.hip)
             args = (self.B, 1, L.ptr(obs), L.ptr(action), C.byref(self.w(net)), L.ptr(out), C.byref(saved) if saved else None,
                     L.ptr(dq_da), C.byref(demo))
-            if self.expert_lanes is not None:
+            if self.labels is not None:
+                L.check(self.lib.tt_mlp_forward_save_demo_labels(*args, self.expert_lanes or 0, self._labels_ref(), self._stream()))
+            elif self.expert_lanes is not None:
                 L.check(self.lib.tt_mlp_forward_save_demo_lanes(*args, self.expert_lanes, self._stream()))
             else:
                 L.check(self.lib.tt_mlp_forward_save_demo(*args, self._stream()))
@@ -606,7 +658,10 @@ class FusedLearner:
                     lr, b1, b2, eps, wd, ag.tau, st.images_ref(), L.ptr(self.bias_corr), L.ptr(self.tail_words),
                     C.c_void_p(self.tail_gave_up_host.data_ptr())]
             shape = C.byref(self._shape) if self.loss_shape is not None else None
-            if demo is not None and self.expert_lanes is not None:
+            if demo is not None and self.labels is not None:
+                L.check(self.lib.tt_mlp_actor_tail_demo_labels(*args, shape, C.byref(demo), self.expert_lanes or 0, self._labels_ref(),
+                                                               self._stream()))
+            elif demo is not None and self.expert_lanes is not None:
                 L.check(self.lib.tt_mlp_actor_tail_demo_lanes(*args, shape, C.byref(demo), self.expert_lanes, self._stream()))
             elif demo is not None:            # (the demonstration form takes the shape as well, NULL without one)
                 L.check(self.lib.tt_mlp_actor_tail_demo(*args, shape, C.byref(demo), self._stream()))
@@ -630,7 +685,7 @@ class FusedLearner:
         n_step: see phase_a (n-step returns; 1 = the one-step learn(), launch for launch).
         demo_index (with demo_loss; else it must be None): the draw's [B, 2] int32 index buffer of this batch (TrajectoryRing: the
         sixth of its batch buffers) -- row b is a demonstration row where demo_index[b, 0] < 0, or, with expert_lanes, where
-        demo_index[b, 1] < expert_lanes."""
+        demo_index[b, 1] < expert_lanes; with labels, a ring row of a labelled lane is a labelled row."""
         assert states.shape[0] == self.B and done_u8.dtype == torch.uint8
         demo = None
         if self.demo_loss is not None:
@@ -641,7 +696,7 @@ class FusedLearner:
             assert demo_index.dtype == torch.int32 and tuple(demo_index.shape) == (self.B, 2) and demo_index.is_contiguous()
             assert actions.is_contiguous() and actions.numel() == self.B
             demo = self._demo_struct(actions, demo_index)
-            self._demo_actions = actions
+            self._demo_actions, self._demo_index = actions, demo_index
         elif demo_index is not None:
             raise ValueError("demo_index without demo_loss (FusedLearner(demo_loss=...))")
         dp = self.grad_sync_critic is not None

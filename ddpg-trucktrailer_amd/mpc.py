@@ -8,6 +8,9 @@ weights them by their return and executes the first action of the weighted mean.
     MPCExpert                 a TruckTrailerVecEnv's planner: owns the plan buffer, act() -> mu [N] in normalised units
     ExpertLanes               lanes [0, M) of a vector loop's env driven by the expert inside the captured step
     check_expert_lanes        everything a loop refuses with expert lanes, as one pure function; expert_mask: the host's mask rule
+    ExpertLabels              lanes [M, M + L) of a vector loop's env labelled by the expert while the policy acts
+    check_expert_labels       everything a loop refuses with expert labels, as one pure function; label_mask: the host's mask rule;
+                              gather_labels: the labels of a batch's labelled rows from the ring's array
     collect_demonstrations    places lanes, runs plan -> step until every lane is done, returns the five arrays of
                               expert.transitions_to_arrays (what expert.save_transitions_npz and TrajectoryRing.load_side take)
 
@@ -182,6 +185,97 @@ def check_expert_lanes(expert, n_envs=None, ring_mode=None, population=False, da
     if force_dp:
         raise ValueError("expert lanes with the data-parallel launch structure (TT_FORCE_DP) are not supported")
     return expert
+
+
+class ExpertLabels:
+    """Expert labels of a vector loop (include/ttenv.h: tt_env_mpc_label_ring): the `lanes` lanes behind the
+    loop's expert lanes, [M, M + lanes) with M = 0 without ExpertLanes, are driven by the POLICY as every lane is, and in every vector
+    step the MPC expert makes one decision on each of them that goes to the ring's label array -- the learner's demonstration term
+    clones the label on their ring rows (DAgger: the expert labels the states the policy reaches).  lanes: a whole number >= 1
+    (M + lanes at most the env's lanes: the loop checks); mpc: an MPCConfig; seed: a whole number in [0, 2^64), the key of the
+    planner's noise.  With ExpertLanes in the same loop mpc and seed must be the expert's: one launch plans for both."""
+
+    def __init__(self, lanes, mpc=None, seed=0):
+        self.lanes, self.mpc, self.seed = lanes, MPCConfig() if mpc is None else mpc, seed
+        check_expert_labels(self)
+        self.lanes, self.seed = int(lanes), int(seed)
+
+    def __repr__(self):
+        return f"ExpertLabels(lanes={self.lanes}, mpc={self.mpc!r}, seed={self.seed})"
+
+    def __eq__(self, other):
+        return isinstance(other, ExpertLabels) and self.as_tuple() == other.as_tuple()
+
+    def __hash__(self):
+        return hash(self.as_tuple())
+
+    def as_tuple(self):
+        return (self.lanes, self.mpc.as_tuple(), self.seed)
+
+    @classmethod
+    def from_tuple(cls, t):
+        return cls(int(t[0]), MPCConfig.from_tuple(tuple(t[1])), int(t[2]))
+
+
+def label_mask(index, first, count):
+    """The labelled rows of a batch, from the draw's [B, 2] index buffer (a side row is (-1, j), a ring row (slot, lane)): a ring row
+    of a lane in [first, first + count).  What the kernels test (csrc/ttlearn_bodies.h: DemoIn.label_first, label_count)."""
+    return (index[:, 0] >= 0) & (index[:, 1] >= int(first)) & (index[:, 1] < int(first) + int(count))
+
+
+def gather_labels(label, index, first, count):
+    """([B] bool, [B] f32): label_mask(index, first, count) and, on those rows, label[slot, lane] of the ring's label array [slots, N];
+    0 on every other row.  Only labelled rows are gathered: a side row's second index counts side tuples and may be >= N, and a
+    labelled row whose slot lies past the array (never left by a draw) is not labelled, as in the kernels."""
+    import torch
+    mask = label_mask(index, first, count) & (index[:, 0] < label.shape[0])
+    out = torch.zeros(index.shape[0], dtype=label.dtype, device=label.device)
+    rows = mask.to(label.device)
+    idx = index.to(label.device).long()[rows]
+    out[rows] = label[idx[:, 0], idx[:, 1]]
+    return mask, out
+
+
+_UNSET = object()
+
+
+def check_expert_labels(labels, expert=None, n_envs=None, ring_mode=None, population=False, data_parallel=False, force_dp=False,
+                        demo_loss=_UNSET):
+    """What is refused with expert labels, each a ValueError that names labels: a malformed ExpertLabels; with n_envs, more expert
+    and labelled lanes together than the env has; with expert (the loop's ExpertLanes), another mpc or seed than the expert's; a
+    stepper that is not in ring mode; a population; data-parallel ranks, the p2p exchange or the TT_FORCE_DP launch structure; with
+    demo_loss passed, None (labels without a learner that reads them do nothing)."""
+    if not isinstance(labels, ExpertLabels):
+        raise ValueError(f"labels = {labels!r} is not an ExpertLabels")
+    if not isinstance(labels.mpc, MPCConfig):
+        raise ValueError(f"labels: mpc = {labels.mpc!r} is not an MPCConfig")
+    check_mpc(labels.mpc)
+    if not (_whole(labels.lanes) and labels.lanes >= 1):
+        raise ValueError(f"labels: lanes = {labels.lanes!r} is not a whole number >= 1")
+    if not (_whole(labels.seed) and 0 <= labels.seed < 2 ** 64):
+        raise ValueError(f"labels: seed = {labels.seed!r} is not a whole number in [0, 2^64)")
+    m = 0
+    if expert is not None:
+        check_expert_lanes(expert)
+        m = expert.lanes
+        if labels.mpc.as_tuple() != expert.mpc.as_tuple():
+            raise ValueError(f"labels: mpc = {labels.mpc!r} is not the expert lanes' {expert.mpc!r} (one launch plans for both)")
+        if labels.seed != expert.seed:
+            raise ValueError(f"labels: seed = {labels.seed} is not the expert lanes' {expert.seed} (one launch plans for both)")
+    if n_envs is not None and m + labels.lanes > int(n_envs):
+        raise ValueError(f"labels: {m} expert lanes + {labels.lanes} labelled lanes are more than the env's {int(n_envs)} lanes")
+    if ring_mode is not None and not ring_mode:
+        raise ValueError("expert labels need a stepper in ring mode (the reference-shaped actor on a GPU): the planner's launch finds "
+                         "the step's label row through the device cursor")
+    if population:
+        raise ValueError("expert labels in a population are not supported (PopulationRollout / PopulationLearner)")
+    if data_parallel:
+        raise ValueError("expert labels with data-parallel ranks (or the p2p exchange) are not supported")
+    if force_dp:
+        raise ValueError("expert labels with the data-parallel launch structure (TT_FORCE_DP) are not supported")
+    if demo_loss is None:
+        raise ValueError("expert labels without demo_loss: no learner would read the labels (DDPGRollout(demo_loss=DemoLoss(...)))")
+    return labels
 
 
 def exp_gen_poses(lanes, seed=0):

@@ -89,6 +89,7 @@ class TrajectoryRing:
         self.k = 0                                                          # vector steps completed (host)
         self.k_dev = torch.zeros((), dtype=torch.int64, device=device)      # same, on the device (graph-safe)
         self._env_counts = False                                            # True: the env's step kernel advances k_dev
+        self.label = None            # enable_labels(): [slots, n_envs] f32, the expert's decision on the state of (t, n)
         # stand-alone transitions (expert tuples, trainv2.py:457-466) that take part in every uniform draw.  Fixed
         # capacity and fixed addresses (a captured sampling launch keeps pointing at them); only `count` moves, and a
         # launch bakes it by value: holders of captured graphs re-capture when side_epoch moves
@@ -120,6 +121,15 @@ class TrajectoryRing:
         then on every env.step()/step_random() of that env counts as one stored vector step."""
         env.set_step_counter(self.k_dev)
         self._env_counts = True
+
+    def enable_labels(self):
+        """Allocate the label array [slots, n_envs] f32, zeroed: label[t][n] is the MPC expert's decision on
+        the state obs[t][n] the policy acted in, written for the loop's labelled lanes (include/ttenv.h: tt_env_mpc_label_ring);
+        lanes that are not labelled keep zeros.  Checkpoints carry the array only once it is enabled.  Before anything is
+        captured: its address is a launch argument."""
+        if self.label is None:
+            self.label = torch.zeros((self.slots, self.n), dtype=torch.float32, device=self.device)
+        return self.label
 
     @property
     def capacity(self):
@@ -178,6 +188,8 @@ class TrajectoryRing:
         sd = {"k": int(self.k), "slots": int(self.slots), "n": int(self.n), "side_count": int(self.side_count)}
         if with_replay:
             sd.update(obs=self.obs.cpu(), act=self.act.cpu(), rew=self.rew.cpu(), done=self.done.cpu())
+            if self.label is not None:
+                sd["label"] = self.label.cpu()
             if self.side is not None:
                 sd["side"] = {k: v.cpu() for k, v in self.side.items()}
         return sd
@@ -185,7 +197,12 @@ class TrajectoryRing:
     def load_state_dict(self, sd):
         assert (int(sd["slots"]), int(sd["n"])) == (self.slots, self.n), "replay ring geometry differs"
         if "obs" in sd:
+            if (self.label is not None) != ("label" in sd):
+                raise ValueError("the ring's label array is " + ("enabled" if self.label is not None else "off") +
+                                 " and the checkpoint's ring has " + ("one" if "label" in sd else "none"))
             self.obs.copy_(sd["obs"]); self.act.copy_(sd["act"]); self.rew.copy_(sd["rew"]); self.done.copy_(sd["done"])
+            if self.label is not None:
+                self.label.copy_(sd["label"])
             if "side" in sd:
                 cap = sd["side"]["act"].shape[0]
                 if self.side is None or self.side["act"].shape[0] != cap:

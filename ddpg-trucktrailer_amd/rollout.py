@@ -72,7 +72,7 @@ class DDPGRollout(VectorStepper):
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, labels=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -113,7 +113,16 @@ class DDPGRollout(VectorStepper):
         captured steps; their transitions land in the ring like any other lane's.  With demo_loss the ring rows of those lanes are
         demonstration rows as well (a ring with no side tuples is the intended use); without it the expert only acts, which composes
         with n_step, td3, loss_shape, the learn log and the episode log.  mpc.check_expert_lanes names what is refused (a stepper
-        that is not in ring mode, data-parallel ranks, the p2p exchange, TT_FORCE_DP, more lanes than the env has)."""
+        that is not in ring mode, data-parallel ranks, the p2p exchange, TT_FORCE_DP, more lanes than the env has).
+        labels: None, or an mpc.ExpertLabels (needs demo_loss): the lanes behind the expert's, [M, M + L), are
+        driven by the policy as every lane is -- their trajectories do not change by a bit -- and the expert's decision on each
+        of their states goes to the ring's label array, in the expert lanes' launch.  The demonstration term clones the label on
+        the ring rows of those lanes (code 3 in demo_stats: "labelled"), unfiltered.  mpc.check_expert_labels names what is refused."""
+        if labels is not None:
+            from ddpg_trucktrailer_amd.mpc import check_expert_labels
+            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
+            check_expert_labels(labels, expert=expert, n_envs=env.n_envs, data_parallel=ranks or dp_exchange == "p2p",
+                                force_dp=os.environ.get("TT_FORCE_DP") == "1", demo_loss=demo_loss)
         if expert is not None:
             from ddpg_trucktrailer_amd.mpc import check_expert_lanes
             ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
@@ -166,7 +175,7 @@ class DDPGRollout(VectorStepper):
         super().__init__(env, batch_size=batch_size, replay_slots=replay_slots, seed=seed, alpha=alpha, beta=beta, tau=tau, gamma=gamma,
                          fc1_dims=fc1_dims, fc2_dims=fc2_dims, agent=agent, capturable=use_graph, policy_workgroups=policy_workgroups,
                          policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail,
-                         td3=self.td3, expert=expert)
+                         td3=self.td3, expert=expert, labels=labels)
         self.batch_size = batch_size
         self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
         self.agent.demo_loss = self.demo_loss
@@ -192,7 +201,8 @@ class DDPGRollout(VectorStepper):
                 self.learner = TD3Learner(self.agent, batch_size, self.ring, self.seed)
             elif self.td3 is None:
                 self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape, demo_loss=self.demo_loss,
-                                            expert_lanes=self.expert.lanes if self.expert is not None and self.demo_loss is not None else None)
+                                            expert_lanes=self.expert.lanes if self.expert is not None and self.demo_loss is not None else None,
+                                            labels=(self.label_first, self.labels.lanes, self.ring.label) if self.labels is not None else None)
             self.agent.fused_learner = self.learner
             if self.dp and self.dp_exchange == "p2p":
                 self.learner.enable_p2p()
@@ -278,8 +288,12 @@ class DDPGRollout(VectorStepper):
         expert lanes a ring row of a lane < expert.lanes is one too: mpc.expert_mask)."""
         if self.demo_loss is None:
             return {}
-        from ddpg_trucktrailer_amd.mpc import expert_mask
-        return dict(demo_rows=expert_mask(index, self.expert.lanes if self.expert is not None else 0))
+        from ddpg_trucktrailer_amd.mpc import expert_mask, gather_labels
+        rows = dict(demo_rows=expert_mask(index, self.expert.lanes if self.expert is not None else 0))
+        if getattr(self, "labels", None) is not None:           # the label of a labelled row, from the ring's array at the row's (slot, lane)
+            lab, values = gather_labels(self.ring.label, index, self.label_first, self.labels.lanes)      # (labelled rows only)
+            rows.update(label_rows=lab, labels=values)
+        return rows
 
     def _sample_key(self, u):
         return (self.seed + u * _SEED_STRIDE) & (2 ** 64 - 1)
@@ -712,7 +726,8 @@ class DDPGRollout(VectorStepper):
 
     def demo_stats(self):
         """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}; with expert lanes the ring rows of those
-        lanes count as demonstration rows, as in the kernels.  Synchronises."""
+        lanes count as demonstration rows, as in the kernels; with labels also "labelled", the rows of labelled lanes (code 3), which
+        count as applied and enter bc_loss with their label.  Synchronises."""
         if self.learner is None or self.demo_loss is None:
             raise ValueError("demo_loss is off or the learner is the torch path (DDPGRollout(demo_loss=...))")
         return self.learner.demo_stats()

@@ -16,7 +16,7 @@ from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 class VectorStepper:
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
-                 episode_log_detail=False, td3=None, expert=None):
+                 episode_log_detail=False, td3=None, expert=None, labels=None):
         """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold);
         td3: its TD3Config (Agent(td3=)), whose torch path draws its smoothing noise from a generator seeded with `seed`.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
@@ -24,7 +24,10 @@ class VectorStepper:
         step, and drain_episodes() collects the records.  episode_log_detail: the detailed log (episode_metrics.py).
         expert: None, or an mpc.ExpertLanes: lanes [0, expert.lanes) are driven by the MPC expert -- one launch
         between the policy launch and the env step writes their decisions over the policy's (ring mode only); the stepper owns
-        their plan [lanes, H]."""
+        their plan [lanes, H].
+        labels: None, or an mpc.ExpertLabels: the lanes behind the expert's, [M, M + labels.lanes), act on the
+        policy's values as every lane does, and the expert's decision on each of them goes to the ring's label array (enabled
+        here) -- ONE launch, in the expert lanes' place, plans for both kinds of lane, and the stepper owns the plan [M + L, H]."""
         self.env, self.n, self.device, self.seed = env, env.n_envs, env.device, seed
         if episode_log:
             env.enable_episode_log(int(episode_log), detail=episode_log_detail)
@@ -66,6 +69,16 @@ class VectorStepper:
             check_mpc(expert.mpc, action_scale=env.max_steer)
             with torch.cuda.device(self.device):
                 self.expert_plan = torch.zeros((expert.lanes, expert.mpc.horizon), dtype=torch.float32, device=self.device)
+        self.labels = None
+        if labels is not None:
+            from ddpg_trucktrailer_amd.mpc import check_expert_labels, check_mpc
+            self.labels = check_expert_labels(labels, expert=self.expert, n_envs=self.n, ring_mode=self.ring_mode)
+            check_mpc(labels.mpc, action_scale=env.max_steer)
+            self.label_first = self.expert.lanes if self.expert is not None else 0
+            self.ring.enable_labels()
+            with torch.cuda.device(self.device):       # one plan for the launch's lanes: rows [0, M) the expert lanes'
+                self.expert_plan = torch.zeros((self.label_first + labels.lanes, labels.mpc.horizon), dtype=torch.float32,
+                                               device=self.device)
 
     def _image(self):
         """The packed actor under two_images: the image packed at the start of the step, never the live weights learn() updates."""
@@ -107,7 +120,10 @@ class VectorStepper:
         device (after open_step).  Otherwise (CPU, torch actor) k selects them."""
         if self.ring_mode:
             self.policy_launch()
-            if self.expert is not None:       # the expert lanes' decisions over the policy's, in ring.act[t] and self.scaled
+            if self.labels is not None:       # the labelled lanes' decisions into ring.label[t]; the expert lanes' as below
+                self.env.mpc_label_ring(self.labels.mpc, self.expert_plan, self.label_first, self.labels.lanes, self._view,
+                                        self.ring.label, self.high, self.scaled, seed=self.labels.seed)
+            elif self.expert is not None:     # the expert lanes' decisions over the policy's, in ring.act[t] and self.scaled
                 self.env.mpc_act_ring(self.expert.mpc, self.expert_plan, self.expert.lanes, self._view, self.high, self.scaled,
                                       seed=self.expert.seed)
             self.env.step_ring(self.scaled, self._view, auto_reset=True)
@@ -127,10 +143,11 @@ class VectorStepper:
     def graph_key(self):
         """What captured launches of this stepper bake in: env.graph_epoch (reset seed, per-env-goal mode, pose pool), the ring's
         side-buffer count, the actor's parameter storages (the policy's packed-image struct is keyed on them, fused.py) and the
-        expert lanes' configuration (its numbers are kernel arguments)."""
+        expert lanes' and the expert labels' configurations (their numbers are kernel arguments)."""
         return (getattr(self.env, "graph_epoch", 0), self.ring.side_epoch,
                 fused.packed_key_of(self.agent.actor) if self.fused_act else None,
-                self.expert.as_tuple() if self.expert is not None else None)
+                self.expert.as_tuple() if self.expert is not None else None) + \
+               ((self.labels.as_tuple(),) if self.labels is not None else ())
 
     def drain_episodes(self):
         """The env's episode log since the last drain: records sorted by (end_step, lane), end_step = the vector step it ended in."""
@@ -147,6 +164,9 @@ class VectorStepper:
         caller has synchronised."""
         ag = self.agent
         ex = {} if self.expert is None else {"expert": list(self.expert.as_tuple()), "expert_plan": self.expert_plan.detach().cpu().clone()}
+        if self.labels is not None:           # (expert_plan is then the launch's whole plan [M + L, H])
+            ex["labels"] = list(self.labels.as_tuple())
+            ex["expert_plan"] = self.expert_plan.detach().cpu().clone()
         return {**ex, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
                 "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()} for n in self.net_names()},
                 "ring": self.ring.state_dict(), "ou": self.noise.x.detach().cpu().clone(),
@@ -166,13 +186,19 @@ class VectorStepper:
         mine = self.expert.as_tuple() if self.expert is not None else None
         if have != mine:
             raise ValueError(f"the checkpoint was written with expert = {have}, this loop has expert = {mine}")
+        have = sd.get("labels")
+        have = (int(have[0]), tuple(have[1]), int(have[2])) if have is not None else None
+        mine = self.labels.as_tuple() if self.labels is not None else None
+        if have != mine:
+            raise ValueError(f"the checkpoint was written with labels = {have}, this loop has labels = {mine}")
 
     def load_acting_state(self, sd):
         """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are
         captured again).  Seed and counters stay with the caller, which knows what bakes the seed in.  A checkpoint written with
-        other expert lanes (or none) is refused: the plan and the lanes' ring rows would not be this loop's."""
+        other expert lanes or expert labels (or none) is refused before anything is written: the plan, the lanes' ring rows and the
+        label array would not be this loop's."""
         self.check_expert_state(sd)
-        if self.expert is not None:
+        if self.expert_plan is not None:
             self.expert_plan.copy_(sd["expert_plan"].to(self.expert_plan.device))
         self.ring.load_state_dict(sd["ring"])
         self.noise.x.copy_(sd["ou"].to(self.noise.x.device))

@@ -270,6 +270,25 @@ class TruckTrailerVecEnv:
         self._check(self.lib.tt_env_mpc_act_ring(self._h, C.byref(args), L.ptr(plan), lanes, C.byref(ring_view), float(high),
                                                  L.ptr(act_scaled), self._stream()))
 
+    def mpc_label_ring(self, cfg, plan, expert_lanes, label_lanes, ring_view, label, high, act_scaled, seed=0):
+        """One MPC decision for each of lanes [0, expert_lanes + label_lanes) (include/ttenv.h: tt_env_mpc_label_ring): lanes
+        < expert_lanes as mpc_act_ring, bit for bit; a LABELLED lane's decision goes to label [slots, N] f32 at the running step's
+        slot and nowhere else -- the ring's action row, act_scaled and the env keep what the policy launch left.  plan
+        [expert_lanes + label_lanes, H] f32.  In mpc_act_ring's place: between fused.actor_act_ring and step_ring, on their stream.
+        Capturable."""
+        from ddpg_trucktrailer_amd.mpc import check_mpc, _check_array
+        m, l = int(expert_lanes), int(label_lanes)
+        if m < 0 or l < 1 or m + l > self.n_envs:
+            raise ValueError(f"mpc: expert_lanes = {m}, label_lanes = {l}: not M >= 0, L >= 1, M + L <= {self.n_envs}")
+        check_mpc(cfg, action_scale=self.max_steer)
+        _check_array("plan", plan, (m + l, cfg.horizon), "float32", self.device)
+        _check_array("label", label, (int(ring_view.slots), self.n_envs), "float32", self.device)
+        _check_array("act_scaled", act_scaled, (self.n_envs,), "float32", self.device)
+        args = L.TTMpcArgs(cfg.horizon, cfg.samples, cfg.sigma, cfg.rho, cfg.temperature, cfg.gamma, cfg.k_lat, cfg.k_yaw,
+                           self.max_steer, int(seed) & (2 ** 64 - 1))
+        self._check(self.lib.tt_env_mpc_label_ring(self._h, C.byref(args), L.ptr(plan), m, l, C.byref(ring_view), L.ptr(label),
+                                                   float(high), L.ptr(act_scaled), self._stream()))
+
     # ------------------------------------------------------------------ held lanes (greedy evaluation)
     def enable_hold(self):
         """Allocate the handle's evaluation block (include/ttenv.h: tt_env_set_hold) and the tensors hold_records() fills.

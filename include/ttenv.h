@@ -359,6 +359,26 @@ int tt_env_mpc_plan(tt_env *env, const tt_mpc_args *args, float *plan /* [N, H] 
 int tt_env_mpc_act_ring(tt_env *env, const tt_mpc_args *args, float *plan /* [lanes, H] in / out */, int32_t lanes,
                         const tt_ring_view *ring, float high, float *act_scaled /* [N] */, tt_stream_t stream);
 
+/* Expert labels of a rollout loop: with expert_lanes = M >= 0 and label_lanes = L >= 1, M + L <= n_envs, lanes
+ * [M, M + L) are LABELLED LANES.  Each of them makes ONE tt_env_mpc_plan DECISION per launch, exactly as defined above -- the same
+ * noise keys, the plan read as zeros at step-in-episode 0, the f64 sample-ordered update, the plan stored shifted -- and the
+ * decision goes to the ring's label array and nowhere else:
+ *     label[t][i] = U'_0                  t = ring->cursor[0], label is f32 [slots, n_envs], i in [M, M + L)
+ * Nothing of the decision's definition changes because the lane then executes the POLICY's action and not U'_0: the shifted plan is
+ * only the next decision's warm start, not a record of what the lane did.  ring->act[t][i], act_scaled[i], the policy's noise state
+ * and the env of a labelled lane keep every bit.  In the same launch lanes [0, M) do what tt_env_mpc_act_ring does, bit for bit, and
+ * store no label (their stored action is their label).  plan is [M + L, H], row i the plan of lane i.  A cursor outside [0, slots)
+ * stores no label (and no ring->act value, as above).  Launch it where tt_env_mpc_act_ring goes, in its place: between
+ * tt_actor_act_ring and tt_env_step_ring, on their stream.  tt_ring_view keeps its layout: the label array is an argument.
+ * Capturable into a hipGraph: no allocation, no host read.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL handle, args, plan, ring, ring->cursor or label;
+ * expert_lanes < 0; label_lanes < 1; with expert_lanes > 0 a NULL ring->act or act_scaled (unused, and may be NULL, with 0);
+ * ring->slots < 1; expert_lanes + label_lanes > ring->n_envs; high not finite or <= 0; everything tt_env_mpc_plan refuses of args; a
+ * ring view of another number of envs than the handle's. */
+int tt_env_mpc_label_ring(tt_env *env, const tt_mpc_args *args, float *plan /* [M + L, H] in / out */, int32_t expert_lanes /* M >= 0 */,
+                          int32_t label_lanes /* L >= 1 */, const tt_ring_view *ring, float *label /* [slots, N] */, float high,
+                          float *act_scaled /* [N]; may be NULL when M == 0 */, tt_stream_t stream);
+
 /* Measurement hook (no reference counterpart): time each of the next `max_launches` step-kernel dispatches
  * with a HIP event pair bound to the dispatch itself (hipExtLaunchKernelGGL), on the stream they are launched
  * on; max_launches = 0 switches it off.  tt_env_profile_read waits for the recorded launches, adds them to the
@@ -1028,6 +1048,34 @@ int tt_mlp_actor_tail_demo_lanes(int n, const float *obs, const float *mu, const
                                  float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
                                  int32_t *tail_words, int32_t *gave_up_host, const tt_loss_shape *shape /* may be NULL */,
                                  const tt_demo_loss *demo, int32_t expert_lanes, tt_stream_t stream);
+/* EXPERT LABELS in the demonstration term (tt_env_mpc_label_ring).  A ring row of batch row b, idx[2 b] >= 0,
+ * with first <= idx[2 b + 1] < first + count is a LABELLED ROW:
+ *     a*_b   = label[idx[2 b] * n_envs + idx[2 b + 1]]      the expert's decision on the state the policy acted in
+ *     m_b    = 1                                            never filtered, whatever q_filter says: q rates the STORED action, and
+ *                                                           no launch computes Q(s, a*)
+ *     dq_eff = fmaf(-k, mu_b - a*_b, dQ/da_b)
+ *     code   = 3
+ * (idx[2 b] is taken to be < slots, as the draw leaves it; a row with a slot past the array is not labelled.)  Every other row is
+ * as in the _lanes form: a side row or a ring row of a lane < expert_lanes has the target demo->a[b], the filter, code 1 or 2; any
+ * other ring row code 0 and the bits of dQ/da.  labels == NULL is the _lanes form, the same launches and bits.
+ * TT_EINVAL in the entry point's own name, before any HIP call: everything the _lanes form refuses; with labels, label NULL,
+ * n_envs < 1, slots < 1, first < 0, count < 1, first + count > n_envs, first < expert_lanes (an overlap). */
+typedef struct tt_demo_labels {
+    const float *label;            /* [slots, n_envs] the ring's label array */
+    int32_t n_envs, slots;
+    int32_t first, count;          /* labelled lanes [first, first + count) */
+} tt_demo_labels;
+int tt_mlp_forward_save_demo_labels(int n, int critic /* must be 1 */, const float *obs, const float *action, const tt_mlp_weights *w,
+                                    float *out, const tt_mlp_saved *saved, float *dq_da, const tt_demo_loss *demo, int32_t expert_lanes,
+                                    const tt_demo_labels *labels /* may be NULL */, tt_stream_t stream);
+int tt_mlp_actor_tail_demo_labels(int n, const float *obs, const float *mu, const tt_mlp_weights *critic, float *q_out, float *dq_da,
+                                  const tt_mlp_saved *saved, const tt_mlp_bwd_ws *ws, const tt_mlp_weights *grads, float row_scale,
+                                  int count, float *const *params, float *const *exp_avg, float *const *exp_avg_sq,
+                                  float *const *targets, const int64_t *step_dev, float lr, float beta1, float beta2, float eps,
+                                  float weight_decay, float tau, const tt_fc2_images *images, const float *bias_corr,
+                                  int32_t *tail_words, int32_t *gave_up_host, const tt_loss_shape *shape /* may be NULL */,
+                                  const tt_demo_loss *demo, int32_t expert_lanes, const tt_demo_labels *labels /* may be NULL */,
+                                  tt_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -23,11 +23,17 @@ MPCConfig(horizon=H, samples=S), seed=K)); defaults H = 64
 are driven by the sampling MPC expert inside the captured step.  With --bc-weight L (no --demos needed) the ring rows of those lanes
 are demonstration rows.  Each line then splits the block's finished episodes and successes into lanes < M (the expert's) and lanes >= M
 (the policy's), from the episode log's lane field, so that the expert's successes are not read as the policy's.
+--label-lanes L: expert labels (DDPGRollout(labels=ExpertLabels(L, ...)); needs --bc-weight): the L lanes behind the
+expert's are driven by the POLICY, and the expert's decision on each of their states goes to the ring's label array -- the cloning term
+follows the label on their ring rows, unfiltered.  Takes the expert's --expert-horizon, --expert-samples and --expert-seed (with
+--expert-lanes both use the same: one launch plans for both).  Each line then shows demonstration / labelled / applied rows of the block's
+last update, and the successes split into the policy's lanes and the others.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
 Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
-       [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M [--expert-horizon H] [--expert-samples S] [--expert-seed K]]
+       [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M] [--label-lanes L] [--expert-horizon H] [--expert-samples S]
+       [--expert-seed K]
        [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -72,17 +78,24 @@ if "--no-q-filter" in sys.argv[1:]:
     sys.argv.remove("--no-q-filter")
     q_filter = False
 expert_opt = {}
+label_lanes = None
+if "--label-lanes" in sys.argv[1:]:
+    at = sys.argv.index("--label-lanes")
+    label_lanes = int(sys.argv[at + 1])
+    del sys.argv[at:at + 2]
 for flag in ("--expert-lanes", "--expert-horizon", "--expert-samples", "--expert-seed"):
     if flag in sys.argv[1:]:
         at = sys.argv.index(flag)
         expert_opt[flag[9:]] = int(sys.argv[at + 1])
         del sys.argv[at:at + 2]
-if expert_opt and "lanes" not in expert_opt:
-    sys.exit("--expert-horizon / --expert-samples / --expert-seed need --expert-lanes M")
+if expert_opt and "lanes" not in expert_opt and label_lanes is None:
+    sys.exit("--expert-horizon / --expert-samples / --expert-seed need --expert-lanes M or --label-lanes L")
+if label_lanes is not None and bc_weight is None:
+    sys.exit("--label-lanes L needs --bc-weight L: labels without a learner that reads them do nothing")
 if demos is not None and bc_weight is None:
     sys.exit("--demos FILE.npz needs --bc-weight L")
-if bc_weight is not None and demos is None and not expert_opt:
-    sys.exit("--bc-weight L needs demonstrations: --demos FILE.npz or --expert-lanes M")
+if bc_weight is not None and demos is None and not expert_opt and label_lanes is None:
+    sys.exit("--bc-weight L needs demonstrations: --demos FILE.npz, --expert-lanes M or --label-lanes L")
 demo_loss = None
 if bc_weight is not None:
     from ddpg_trucktrailer_amd.demo_loss import DemoLoss
@@ -113,12 +126,15 @@ for at, arg in enumerate(sys.argv):
         break
 n, slots, upd, batch, total, every = (int(x) for x in sys.argv[1:7])
 seed = int(sys.argv[7]) if len(sys.argv) > 7 else 27
-expert = None
-if expert_opt:
-    from ddpg_trucktrailer_amd.mpc import ExpertLanes, MPCConfig
+expert, labels = None, None
+if expert_opt or label_lanes is not None:
+    from ddpg_trucktrailer_amd.mpc import ExpertLabels, ExpertLanes, MPCConfig
     # horizon 64: what the planner's record supports from the env's own reset poses
-    expert = ExpertLanes(expert_opt["lanes"], MPCConfig(horizon=expert_opt.get("horizon", 64), samples=expert_opt.get("samples", 256)),
-                         seed=expert_opt.get("seed", seed))
+    mpc_cfg = MPCConfig(horizon=expert_opt.get("horizon", 64), samples=expert_opt.get("samples", 256))
+    if "lanes" in expert_opt:
+        expert = ExpertLanes(expert_opt["lanes"], mpc_cfg, seed=expert_opt.get("seed", seed))
+    if label_lanes is not None:
+        labels = ExpertLabels(label_lanes, mpc_cfg, seed=expert_opt.get("seed", seed))
 graph_steps = int(sys.argv[8]) if len(sys.argv) > 8 else (20 if slots <= 1024 else 0)      # (as before: no graphs past 1024 slots)
 env = TruckTrailerVecEnv(n)
 env.reset(seed=seed)
@@ -127,7 +143,7 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert)
+                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert, labels=labels)
 if demos is not None:
     from ddpg_trucktrailer_amd.expert import load_transitions_npz
     d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
@@ -136,7 +152,7 @@ print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn()
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else "") +
       (f", {loss_shape}" if loss_shape is not None else "") +
       (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else "") +
-      (f", {expert}" if expert is not None else ""), flush=True)
+      (f", {expert}" if expert is not None else "") + (f", {labels}" if labels is not None else ""), flush=True)
 
 
 def learn_line(rec):
@@ -150,15 +166,23 @@ def learn_line(rec):
 
 
 def demo_line(st):
-    return f"  demonstrations {st['demo_rows']} rows, {st['applied']} applied, bc loss {st['bc_loss']:.4g}"
+    lab = f", {st['labelled']} labelled" if "labelled" in st else ""
+    return f"  demonstrations {st['demo_rows']} rows{lab}, {st['applied']} applied, bc loss {st['bc_loss']:.4g}"
 
 
-def lanes_line(r, m_lanes):
-    """The block's finished episodes and successes by lane group: the expert's lanes [0, M) and the policy's."""
+def lanes_line(r, m_lanes, l_lanes=0):
+    """The block's finished episodes and successes by lane group: the expert's lanes [0, M) and the policy's.  With labels the groups
+    carry their lane ranges, the expert's group is left out when there is none, and the policy's lanes [M, M + L) that the expert
+    labels are shown on their own as well."""
     ex = r["lane"] < m_lanes
     ok = r["success"]
-    return (f"  expert lanes: episodes {int(ex.sum().item())} successes {int((ok & ex).sum().item())}"
-            f"  policy lanes: episodes {int((~ex).sum().item())} successes {int((ok & ~ex).sum().item())}")
+    if not l_lanes:
+        return (f"  expert lanes: episodes {int(ex.sum().item())} successes {int((ok & ex).sum().item())}"
+                f"  policy lanes: episodes {int((~ex).sum().item())} successes {int((ok & ~ex).sum().item())}")
+    lab = ~ex & (r["lane"] < m_lanes + l_lanes)
+    out = f"  expert lanes [0, {m_lanes}): episodes {int(ex.sum().item())} successes {int((ok & ex).sum().item())}" if m_lanes else ""
+    return (out + f"  policy lanes [{m_lanes}, {n}): episodes {int((~ex).sum().item())} successes {int((ok & ~ex).sum().item())}"
+            f"  of them labelled lanes [{m_lanes}, {m_lanes + l_lanes}): episodes {int(lab.sum().item())} successes {int((ok & lab).sum().item())}")
 
 
 tracker = BestModelTracker()
@@ -189,7 +213,7 @@ while s < total:
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
           f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}"
           f"{demo_line(loop.demo_stats()) if demo_loss is not None else ''}"
-          f"{lanes_line(r, expert.lanes) if expert is not None else ''}  "
+          f"{lanes_line(r, expert.lanes if expert is not None else 0, labels.lanes if labels is not None else 0) if expert is not None or labels is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
     if evaluator is not None and blocks % eval_every == 0:
