@@ -186,7 +186,8 @@ __device__ __forceinline__ void tt_sincos(const KTable &T, double x, double &s, 
     ps = fma(ps, u, T.f[7]);
     ps = fma(ps, u, T.f[5]);
     ps = fma(ps, u, T.f[3]);
-    const double sr = fma(r * u, ps, r);
+    // sin(-0.0) is -0.0 (np.sin; the f32 observation keeps the sign); k = -0 makes the reduction's first fma return +0
+    const double sr = x == 0.0 ? x : fma(r * u, ps, r);
     double pc = T.f[16];
     pc = fma(pc, u, T.f[14]);
     pc = fma(pc, u, T.f[12]);
