@@ -17,35 +17,19 @@ section 25).
 
 The torch form is Agent(demo_loss=).learn_batch(..., demo_rows=) (agent.py): the CPU path, and the twin the kernels are tested
 against."""
-import math
+from ddpg_trucktrailer_amd.options import Option, finite_number, refuse
 
 
-class DemoLoss:
+class DemoLoss(Option):
     """bc_weight: a finite number > 0.  q_filter: apply the term only where the critic rates the stored action above the policy's."""
+    FIELDS = ("bc_weight", "q_filter")
 
     def __init__(self, bc_weight, q_filter=True):
-        if not (isinstance(bc_weight, (int, float)) and not isinstance(bc_weight, bool) and math.isfinite(bc_weight) and bc_weight > 0):
-            raise ValueError(f"demo_loss: bc_weight = {bc_weight!r} is not a finite number > 0")
+        finite_number("demo_loss: bc_weight", bc_weight, "> 0")
         if not isinstance(q_filter, (bool, int)) or q_filter not in (0, 1):
             raise ValueError(f"demo_loss: q_filter = {q_filter!r} is not a bool")
         self.bc_weight = float(bc_weight)
         self.q_filter = bool(q_filter)
-
-    def __repr__(self):
-        return f"DemoLoss(bc_weight={self.bc_weight}, q_filter={self.q_filter})"
-
-    def __eq__(self, other):
-        return isinstance(other, DemoLoss) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def as_tuple(self):
-        return (self.bc_weight, self.q_filter)
-
-    @classmethod
-    def from_tuple(cls, t):
-        return cls(t[0], bool(t[1]))
 
     def k(self):
         """k = 2 lambda of tt_demo_loss, formed in f64 (the struct member rounds it to f32)."""
@@ -56,17 +40,5 @@ def check_demo_loss(demo, td3=None, population=False, data_parallel=False, force
     """What is refused with a demonstration loss, each a ValueError that names demo_loss.  Those paths have kernels of their own
     (TD3, populations), cannot be tested on one GPU (data-parallel ranks, the p2p exchange, the TT_FORCE_DP launch structure) or
     cannot hold demonstration rows at all (n_step > 1: the ring refuses side tuples there)."""
-    if not isinstance(demo, DemoLoss):
-        raise ValueError(f"demo_loss = {demo!r} is not a DemoLoss")
-    if td3 is not None:
-        raise ValueError("demo_loss with td3 is not supported (the TD3 launches have no demonstration form)")
-    if population:
-        raise ValueError("demo_loss in a population is not supported (the population's launches have no demonstration form)")
-    if data_parallel:
-        raise ValueError("demo_loss with data-parallel ranks (or the p2p exchange) is not supported")
-    if force_dp:
-        raise ValueError("demo_loss with the data-parallel launch structure (TT_FORCE_DP) is not supported")
-    if int(n_step) > 1:
-        raise ValueError(f"demo_loss with n_step = {int(n_step)} is not supported: side tuples are single steps, and the ring refuses "
-                         "them in an n-step draw")
-    return demo
+    DemoLoss.expect("demo_loss", demo)
+    return refuse("demo_loss", demo, td3=td3, population=population, data_parallel=data_parallel, force_dp=force_dp, n_step=n_step)

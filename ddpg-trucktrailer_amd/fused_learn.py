@@ -12,6 +12,7 @@ import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd import fused
+from ddpg_trucktrailer_amd.options import compare_options, refuse, write_options
 from ddpg_trucktrailer_amd.replay_buffer import check_n_step
 
 _p = L.ptr        # (the name this module's callers import)
@@ -280,10 +281,9 @@ class FusedLearner:
                                     pre=self.pre.data_ptr())
 
     def _refuse_ranks_with_loss_shape(self):
-        if self.loss_shape is not None:
-            raise ValueError("loss_shape with data-parallel ranks (or the p2p exchange) is not supported")
-        if self.demo_loss is not None:
-            raise ValueError("demo_loss with data-parallel ranks (or the p2p exchange) is not supported")
+        for name in ("loss_shape", "demo_loss"):
+            if getattr(self, name) is not None:
+                refuse(name, data_parallel=True)
 
     def set_demo_loss(self, demo_loss):
         """Turn a DemoLoss on (before anything is captured: the constants travel by value in the launches' arguments).  The learner
@@ -721,21 +721,11 @@ class FusedLearner:
         sd = {"step": int(self.step_dev.item()),
               "actor": {"m": self.actor.m.cpu(), "v": self.actor.v.cpu()},
               "critic": {"m": self.critic.m.cpu(), "v": self.critic.v.cpu()}}
-        if self.loss_shape is not None:
-            sd["loss_shape"] = list(self.loss_shape.as_tuple())
-        if self.demo_loss is not None:
-            sd["demo_loss"] = list(self.demo_loss.as_tuple())
+        write_options(sd, loss_shape=self.loss_shape, demo_loss=self.demo_loss)
         return sd
 
     def load_state_dict(self, sd):
-        have = tuple(sd["loss_shape"]) if sd.get("loss_shape") is not None else None
-        mine = self.loss_shape.as_tuple() if self.loss_shape is not None else None
-        if have != mine:
-            raise ValueError(f"the checkpoint was written with loss_shape = {have}, this learner has loss_shape = {mine}")
-        have = tuple(sd["demo_loss"]) if sd.get("demo_loss") is not None else None
-        mine = self.demo_loss.as_tuple() if self.demo_loss is not None else None
-        if have != mine:
-            raise ValueError(f"the checkpoint was written with demo_loss = {have}, this learner has demo_loss = {mine}")
+        compare_options(sd, "learner", loss_shape=self.loss_shape, demo_loss=self.demo_loss)
         for name in ("actor", "critic"):
             st = getattr(self, name)
             st.m.copy_(sd[name]["m"]); st.v.copy_(sd[name]["v"])

@@ -12,37 +12,18 @@ csrc/ttshape.hip).
              policy_pre_activation_weight).  Its gradient 2 c pre / B does not vanish where tanh saturates.
 
 The torch form is Agent(loss_shape=).learn_batch (agent.py): the CPU path, and the twin the kernels are tested against."""
-import math
+from ddpg_trucktrailer_amd.options import Option, finite_number, refuse
 
 
-class LossShape:
+class LossShape(Option):
     """huber_delta: None, or a finite number > 0.  pre_penalty: a finite number >= 0.  LossShape() changes nothing."""
+    FIELDS = ("huber_delta", "pre_penalty")
 
     def __init__(self, huber_delta=None, pre_penalty=0.0):
-        if huber_delta is not None and not (isinstance(huber_delta, (int, float)) and not isinstance(huber_delta, bool) and
-                                            math.isfinite(huber_delta) and huber_delta > 0):
-            raise ValueError(f"huber_delta = {huber_delta!r} is not None or a finite number > 0")
-        if not (isinstance(pre_penalty, (int, float)) and not isinstance(pre_penalty, bool) and math.isfinite(pre_penalty) and
-                pre_penalty >= 0):
-            raise ValueError(f"pre_penalty = {pre_penalty!r} is not a finite number >= 0")
+        finite_number("huber_delta", huber_delta, "> 0", or_none=True)
+        finite_number("pre_penalty", pre_penalty, ">= 0")
         self.huber_delta = None if huber_delta is None else float(huber_delta)
         self.pre_penalty = float(pre_penalty)
-
-    def __repr__(self):
-        return f"LossShape(huber_delta={self.huber_delta}, pre_penalty={self.pre_penalty})"
-
-    def __eq__(self, other):
-        return isinstance(other, LossShape) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def as_tuple(self):
-        return (self.huber_delta, self.pre_penalty)
-
-    @classmethod
-    def from_tuple(cls, t):
-        return cls(t[0], t[1])
 
     # what the launches take (include/ttenv.h: tt_loss_shape and the caller's scale_critic), for a batch of B rows
     def critic_scale(self, batch):
@@ -60,14 +41,5 @@ class LossShape:
 def check_loss_shape(shape, td3=None, population=False, data_parallel=False, force_dp=False):
     """What is refused with a loss shape, each a ValueError that names loss_shape.  Those paths have kernels of their own (TD3,
     populations) or cannot be tested on one GPU (data-parallel ranks, the p2p exchange, the TT_FORCE_DP launch structure)."""
-    if not isinstance(shape, LossShape):
-        raise ValueError(f"loss_shape = {shape!r} is not a LossShape")
-    if td3 is not None:
-        raise ValueError("loss_shape with td3 is not supported (the TD3 launches have no shaped form)")
-    if population:
-        raise ValueError("loss_shape in a population is not supported (the population's launches have no shaped form)")
-    if data_parallel:
-        raise ValueError("loss_shape with data-parallel ranks (or the p2p exchange) is not supported")
-    if force_dp:
-        raise ValueError("loss_shape with the data-parallel launch structure (TT_FORCE_DP) is not supported")
-    return shape
+    LossShape.expect("loss_shape", shape)
+    return refuse("loss_shape", shape, td3=td3, population=population, data_parallel=data_parallel, force_dp=force_dp)

@@ -17,29 +17,21 @@ weights them by their return and executes the first action of the weighted mean.
 The objective is the env's reward plus, for a rollout that did not terminate inside the horizon, a terminal cost on the trailer's
 lateral offset from the goal axis and its yaw error: the reward alone has no term that looks ahead to the final alignment, and
 plans that maximise it reach the goal line outside the 0.5 m / 15 degree box.  The exploration noise is AR(1) in time."""
-import math
 import time
 
 from ddpg_trucktrailer_amd import _lib as L
+from ddpg_trucktrailer_amd.options import UNSET, Option, finite_number, is_number, refuse, refuse_value, whole_number
 
 FLAG_NAMES = ("jackknife", "out_of_map", "max_steps", "goal_reached", "goal_passed", "excessive_back", "success")      # TT_F_* bits 0..6
 EXP_GEN_START = (0.0, 10.0)                       # DDPG/exp_gen.py:31
 EXP_GEN_YAW_DEG = (45.0, 120.0)                   # DDPG/exp_gen.py:32
 
 
-def _number(x):
-    return isinstance(x, (int, float)) and not isinstance(x, bool)
-
-
-def _whole(x):
-    return isinstance(x, int) and not isinstance(x, bool)
-
-
-class MPCConfig:
+class MPCConfig(Option):
     """horizon in [1, 64], samples in [1, 1024] (sample 0 is the noise-free nominal), sigma >= 0 and rho in [0, 1) of the AR(1)
     noise in normalised action units, temperature lambda > 0 of the softmax over returns, gamma in (0, 1], k_lat >= 0 [1/m^2] and
     k_yaw >= 0 [1/rad^2] of the terminal cost.  The C struct holds the numbers as f32; the kernel computes with those in f64."""
-    FIELDS = ("horizon", "samples", "sigma", "rho", "temperature", "gamma", "k_lat", "k_yaw")
+    FIELDS, A = ("horizon", "samples", "sigma", "rho", "temperature", "gamma", "k_lat", "k_yaw"), "an"
 
     def __init__(self, horizon=40, samples=256, sigma=0.3, rho=0.8, temperature=10.0, gamma=1.0, k_lat=20.0, k_yaw=300.0):
         self.horizon, self.samples = horizon, samples
@@ -48,22 +40,6 @@ class MPCConfig:
         self.horizon, self.samples = int(horizon), int(samples)
         for name in self.FIELDS[2:]:
             setattr(self, name, float(getattr(self, name)))
-
-    def __repr__(self):
-        return "MPCConfig(" + ", ".join(f"{n}={getattr(self, n)}" for n in self.FIELDS) + ")"
-
-    def __eq__(self, other):
-        return isinstance(other, MPCConfig) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def as_tuple(self):
-        return tuple(getattr(self, n) for n in self.FIELDS)
-
-    @classmethod
-    def from_tuple(cls, t):
-        return cls(*t)
 
 
 def _check_array(name, t, shape, dtype, device):
@@ -76,24 +52,18 @@ def _check_array(name, t, shape, dtype, device):
 def check_mpc(cfg, action_scale=None, n_envs=None, device=None, plan=None, mu_out=None, live=None, returns_out=None):
     """What a planning call refuses, each a ValueError that names mpc and the field: the limits of include/ttenv.h
     (tt_env_mpc_plan) on the config and the action scale and, with n_envs, the buffers' dtype, shape, layout and device."""
-    if not isinstance(cfg, MPCConfig):
-        raise ValueError(f"mpc: cfg = {cfg!r} is not an MPCConfig")
-    if not (_whole(cfg.horizon) and 1 <= cfg.horizon <= L.MPC_MAX_HORIZON):
-        raise ValueError(f"mpc: horizon = {cfg.horizon!r} is not a whole number in [1, {L.MPC_MAX_HORIZON}]")
-    if not (_whole(cfg.samples) and 1 <= cfg.samples <= L.MPC_MAX_SAMPLES):
-        raise ValueError(f"mpc: samples = {cfg.samples!r} is not a whole number in [1, {L.MPC_MAX_SAMPLES}]")
+    MPCConfig.expect("mpc: cfg", cfg)
+    whole_number("mpc: horizon", cfg.horizon, 1, L.MPC_MAX_HORIZON)
+    whole_number("mpc: samples", cfg.samples, 1, L.MPC_MAX_SAMPLES)
     for name in ("sigma", "k_lat", "k_yaw"):
-        v = getattr(cfg, name)
-        if not (_number(v) and math.isfinite(v) and v >= 0):
-            raise ValueError(f"mpc: {name} = {v!r} is not a finite number >= 0")
-    if not (_number(cfg.rho) and 0 <= cfg.rho < 1):
-        raise ValueError(f"mpc: rho = {cfg.rho!r} is not a number in [0, 1)")
-    if not (_number(cfg.temperature) and math.isfinite(cfg.temperature) and cfg.temperature > 0):
-        raise ValueError(f"mpc: temperature = {cfg.temperature!r} is not a finite number > 0")
-    if not (_number(cfg.gamma) and 0 < cfg.gamma <= 1):
-        raise ValueError(f"mpc: gamma = {cfg.gamma!r} is not a number in (0, 1]")
-    if action_scale is not None and not (_number(action_scale) and math.isfinite(action_scale) and action_scale > 0):
-        raise ValueError(f"mpc: action_scale = {action_scale!r} is not a finite number > 0")
+        finite_number(f"mpc: {name}", getattr(cfg, name), ">= 0")
+    if not (is_number(cfg.rho) and 0 <= cfg.rho < 1):
+        refuse_value("mpc: rho", cfg.rho, "a number in [0, 1)")
+    finite_number("mpc: temperature", cfg.temperature, "> 0")
+    if not (is_number(cfg.gamma) and 0 < cfg.gamma <= 1):
+        refuse_value("mpc: gamma", cfg.gamma, "a number in (0, 1]")
+    if action_scale is not None:
+        finite_number("mpc: action_scale", action_scale, "> 0")
     if n_envs is None:
         return cfg
     n = int(n_envs)
@@ -126,32 +96,31 @@ class MPCExpert:
         return self.env.mpc_plan(self.cfg, self.plan, self.mu, live=live, returns_out=returns_out, seed=self.seed)
 
 
-class ExpertLanes:
+class _Lanes(Option):
+    """What ExpertLanes and ExpertLabels share: lanes, an MPCConfig and the seed of the planner's noise, checked by the class's own
+    check function under the option's name."""
+    FIELDS, NESTED, A = ("lanes", "mpc", "seed"), {"mpc": MPCConfig}, "an"
+
+    def __init__(self, lanes, mpc=None, seed=0):
+        self.lanes, self.mpc, self.seed = lanes, MPCConfig() if mpc is None else mpc, seed
+        self._well_formed(self.NAME)
+        self.lanes, self.seed = int(lanes), int(seed)
+
+    def _well_formed(self, name):
+        """The value itself, as the constructor and every later check see it (a field may have been set since)."""
+        if not isinstance(self.mpc, MPCConfig):
+            refuse_value(f"{name}: mpc", self.mpc, "an MPCConfig")
+        check_mpc(self.mpc)
+        whole_number(f"{name}: lanes", self.lanes, 1)
+        whole_number(f"{name}: seed", self.seed, 0, 2 ** 64 - 1, "in [0, 2^64)")
+
+
+class ExpertLanes(_Lanes):
     """Expert lanes of a vector loop (include/ttenv.h: tt_env_mpc_act_ring): lanes [0, lanes) of the loop's env
     are driven by the MPC expert in every vector step -- one decision per lane between the policy launch and the env step, inside
     the captured step -- and their transitions land in the ring like any other lane's.  lanes: a whole number >= 1 (at most the
     env's lanes: the loop checks); mpc: an MPCConfig; seed: a whole number in [0, 2^64), the key of the planner's noise."""
-
-    def __init__(self, lanes, mpc=None, seed=0):
-        self.lanes, self.mpc, self.seed = lanes, MPCConfig() if mpc is None else mpc, seed
-        check_expert_lanes(self)
-        self.lanes, self.seed = int(lanes), int(seed)
-
-    def __repr__(self):
-        return f"ExpertLanes(lanes={self.lanes}, mpc={self.mpc!r}, seed={self.seed})"
-
-    def __eq__(self, other):
-        return isinstance(other, ExpertLanes) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def as_tuple(self):
-        return (self.lanes, self.mpc.as_tuple(), self.seed)
-
-    @classmethod
-    def from_tuple(cls, t):
-        return cls(int(t[0]), MPCConfig.from_tuple(tuple(t[1])), int(t[2]))
+    NAME = "expert"
 
 
 def expert_mask(index, lanes):
@@ -164,57 +133,19 @@ def check_expert_lanes(expert, n_envs=None, ring_mode=None, population=False, da
     """What is refused with expert lanes, each a ValueError that names expert: a malformed ExpertLanes; with n_envs, more lanes than
     the env has; a stepper that is not in ring mode (a CPU device or a torch actor: the launch addresses the ring through its device
     cursor); a population; data-parallel ranks, the p2p exchange or the TT_FORCE_DP launch structure (not testable on one GPU)."""
-    if not isinstance(expert, ExpertLanes):
-        raise ValueError(f"expert = {expert!r} is not an ExpertLanes")
-    if not isinstance(expert.mpc, MPCConfig):
-        raise ValueError(f"expert: mpc = {expert.mpc!r} is not an MPCConfig")
-    check_mpc(expert.mpc)
-    if not (_whole(expert.lanes) and expert.lanes >= 1):
-        raise ValueError(f"expert: lanes = {expert.lanes!r} is not a whole number >= 1")
-    if not (_whole(expert.seed) and 0 <= expert.seed < 2 ** 64):
-        raise ValueError(f"expert: seed = {expert.seed!r} is not a whole number in [0, 2^64)")
-    if n_envs is not None and expert.lanes > int(n_envs):
-        raise ValueError(f"expert: lanes = {expert.lanes} is outside [1, {int(n_envs)}], the env's lanes")
-    if ring_mode is not None and not ring_mode:
-        raise ValueError("expert lanes need a stepper in ring mode (the reference-shaped actor on a GPU): the expert's launch finds "
-                         "the step's ring row through the device cursor")
-    if population:
-        raise ValueError("expert lanes in a population are not supported (PopulationRollout / PopulationLearner)")
-    if data_parallel:
-        raise ValueError("expert lanes with data-parallel ranks (or the p2p exchange) are not supported")
-    if force_dp:
-        raise ValueError("expert lanes with the data-parallel launch structure (TT_FORCE_DP) are not supported")
-    return expert
+    ExpertLanes.expect("expert", expert)._well_formed("expert")
+    return refuse("expert", expert, n_envs=n_envs, ring_mode=ring_mode, population=population, data_parallel=data_parallel,
+                  force_dp=force_dp)
 
 
-class ExpertLabels:
+class ExpertLabels(_Lanes):
     """Expert labels of a vector loop (include/ttenv.h: tt_env_mpc_label_ring): the `lanes` lanes behind the
     loop's expert lanes, [M, M + lanes) with M = 0 without ExpertLanes, are driven by the POLICY as every lane is, and in every vector
     step the MPC expert makes one decision on each of them that goes to the ring's label array -- the learner's demonstration term
     clones the label on their ring rows (DAgger: the expert labels the states the policy reaches).  lanes: a whole number >= 1
     (M + lanes at most the env's lanes: the loop checks); mpc: an MPCConfig; seed: a whole number in [0, 2^64), the key of the
     planner's noise.  With ExpertLanes in the same loop mpc and seed must be the expert's: one launch plans for both."""
-
-    def __init__(self, lanes, mpc=None, seed=0):
-        self.lanes, self.mpc, self.seed = lanes, MPCConfig() if mpc is None else mpc, seed
-        check_expert_labels(self)
-        self.lanes, self.seed = int(lanes), int(seed)
-
-    def __repr__(self):
-        return f"ExpertLabels(lanes={self.lanes}, mpc={self.mpc!r}, seed={self.seed})"
-
-    def __eq__(self, other):
-        return isinstance(other, ExpertLabels) and self.as_tuple() == other.as_tuple()
-
-    def __hash__(self):
-        return hash(self.as_tuple())
-
-    def as_tuple(self):
-        return (self.lanes, self.mpc.as_tuple(), self.seed)
-
-    @classmethod
-    def from_tuple(cls, t):
-        return cls(int(t[0]), MPCConfig.from_tuple(tuple(t[1])), int(t[2]))
+    NAME = "labels"
 
 
 def label_mask(index, first, count):
@@ -236,24 +167,13 @@ def gather_labels(label, index, first, count):
     return mask, out
 
 
-_UNSET = object()
-
-
 def check_expert_labels(labels, expert=None, n_envs=None, ring_mode=None, population=False, data_parallel=False, force_dp=False,
-                        demo_loss=_UNSET):
+                        demo_loss=UNSET):
     """What is refused with expert labels, each a ValueError that names labels: a malformed ExpertLabels; with n_envs, more expert
     and labelled lanes together than the env has; with expert (the loop's ExpertLanes), another mpc or seed than the expert's; a
     stepper that is not in ring mode; a population; data-parallel ranks, the p2p exchange or the TT_FORCE_DP launch structure; with
     demo_loss passed, None (labels without a learner that reads them do nothing)."""
-    if not isinstance(labels, ExpertLabels):
-        raise ValueError(f"labels = {labels!r} is not an ExpertLabels")
-    if not isinstance(labels.mpc, MPCConfig):
-        raise ValueError(f"labels: mpc = {labels.mpc!r} is not an MPCConfig")
-    check_mpc(labels.mpc)
-    if not (_whole(labels.lanes) and labels.lanes >= 1):
-        raise ValueError(f"labels: lanes = {labels.lanes!r} is not a whole number >= 1")
-    if not (_whole(labels.seed) and 0 <= labels.seed < 2 ** 64):
-        raise ValueError(f"labels: seed = {labels.seed!r} is not a whole number in [0, 2^64)")
+    ExpertLabels.expect("labels", labels)._well_formed("labels")
     m = 0
     if expert is not None:
         check_expert_lanes(expert)
@@ -262,20 +182,8 @@ def check_expert_labels(labels, expert=None, n_envs=None, ring_mode=None, popula
             raise ValueError(f"labels: mpc = {labels.mpc!r} is not the expert lanes' {expert.mpc!r} (one launch plans for both)")
         if labels.seed != expert.seed:
             raise ValueError(f"labels: seed = {labels.seed} is not the expert lanes' {expert.seed} (one launch plans for both)")
-    if n_envs is not None and m + labels.lanes > int(n_envs):
-        raise ValueError(f"labels: {m} expert lanes + {labels.lanes} labelled lanes are more than the env's {int(n_envs)} lanes")
-    if ring_mode is not None and not ring_mode:
-        raise ValueError("expert labels need a stepper in ring mode (the reference-shaped actor on a GPU): the planner's launch finds "
-                         "the step's label row through the device cursor")
-    if population:
-        raise ValueError("expert labels in a population are not supported (PopulationRollout / PopulationLearner)")
-    if data_parallel:
-        raise ValueError("expert labels with data-parallel ranks (or the p2p exchange) are not supported")
-    if force_dp:
-        raise ValueError("expert labels with the data-parallel launch structure (TT_FORCE_DP) are not supported")
-    if demo_loss is None:
-        raise ValueError("expert labels without demo_loss: no learner would read the labels (DDPGRollout(demo_loss=DemoLoss(...)))")
-    return labels
+    return refuse("labels", labels, first=m, n_envs=n_envs, ring_mode=ring_mode, population=population, data_parallel=data_parallel,
+                  force_dp=force_dp, demo_loss=demo_loss)
 
 
 def exp_gen_poses(lanes, seed=0):

@@ -32,33 +32,24 @@ import ctypes as C
 import torch
 
 from ddpg_trucktrailer_amd import _lib as L
+from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner, LearnLog, check_learn_log, nstep_discount
+from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
+from ddpg_trucktrailer_amd.mpc import check_expert_lanes
+from ddpg_trucktrailer_amd.options import write_options
 from ddpg_trucktrailer_amd.replay_buffer import check_n_step, learn_start, slots_needed
 from ddpg_trucktrailer_amd.rollout import _CAPTURE_MODE, _SEED_STRIDE, _gc_off
 from ddpg_trucktrailer_amd.stepper import VectorStepper
 
 
-def _refuse_loss_shape(loss_shape, agents=()):
-    """A population has no loss shape (loss_shape.check_loss_shape): neither as an option nor on an agent it is given."""
-    from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
-    for shape in [loss_shape] + [getattr(ag, "loss_shape", None) for ag in agents]:
-        if shape is not None:
-            check_loss_shape(shape, population=True)
-
-
-def _refuse_demo_loss(demo_loss, agents=()):
-    """A population has no demonstration loss (demo_loss.check_demo_loss): neither as an option nor on an agent it is given."""
-    from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
-    for demo in [demo_loss] + [getattr(ag, "demo_loss", None) for ag in agents]:
-        if demo is not None:
-            check_demo_loss(demo, population=True)
-
-
-def _refuse_expert(expert):
-    """A population has no expert lanes (mpc.check_expert_lanes)."""
-    if expert is not None:
-        from ddpg_trucktrailer_amd.mpc import check_expert_lanes
-        check_expert_lanes(expert, population=True)
+def _refuse_lone_options(loss_shape, demo_loss, expert, agents=()):
+    """A population has no loss shape, demonstration loss or expert lanes (the options' own checks, with population=True): neither
+    as an option nor, of the first two, on an agent it is given."""
+    for name, check, value in (("loss_shape", check_loss_shape, loss_shape), ("demo_loss", check_demo_loss, demo_loss),
+                               ("expert", check_expert_lanes, expert)):
+        for v in [value] + [getattr(ag, name, None) for ag in agents if name != "expert"]:
+            if v is not None:
+                check(v, population=True)
 
 
 class _PopulationLearnerBase:
@@ -219,9 +210,7 @@ class PopulationLearner(_PopulationLearnerBase):
 
     def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1,
                  loss_shape=None, demo_loss=None, expert=None):
-        _refuse_loss_shape(loss_shape, agents)
-        _refuse_demo_loss(demo_loss, agents)
-        _refuse_expert(expert)
+        _refuse_lone_options(loss_shape, demo_loss, expert, agents)
         super().__init__(agents, batch_size, rings, seeds)
         if any(r._side_struct() is not None for r in rings):
             raise ValueError("expert side buffers are not supported in a population")
@@ -399,9 +388,7 @@ class PopulationRollout:
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
                  learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
-        _refuse_loss_shape(loss_shape)
-        _refuse_demo_loss(demo_loss)
-        _refuse_expert(expert)
+        _refuse_lone_options(loss_shape, demo_loss, expert)
         if td3 is not None:            # (before anything else: each refusal names its option)
             from ddpg_trucktrailer_amd.td3 import check_population_td3
             td3 = check_population_td3(td3, len(seeds), updates_per_step, _listed(n_step), 1 if n_step_max is None else n_step_max,
@@ -593,7 +580,7 @@ class PopulationRollout:
             st = {"format": 2, "handover_gave_up": [], "batch_size": self.batch_size, "updates_per_step": self.updates_per_step,
                   "n_step": int(self.n_steps[a]), **lp.acting_state(), "fused_adam": lr.state_dict(a), "hyper": lr._hyper_of(a)}
             if self.td3 is not None:
-                st["td3"] = list(lp.agent.td3.as_tuple())
+                write_options(st, td3=lp.agent.td3)
                 st["fused_adam"]["updates"] = int(lr.updates)
             agents.append(st)
         return {"format": POPULATION_FORMAT, "K": self.K, "n": self.n, "batch_size": self.batch_size,

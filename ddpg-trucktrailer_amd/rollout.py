@@ -38,6 +38,10 @@ import os
 import torch
 
 from ddpg_trucktrailer_amd import fused
+from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
+from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
+from ddpg_trucktrailer_amd.mpc import check_expert_labels, check_expert_lanes
+from ddpg_trucktrailer_amd.options import compare_options, write_options
 from ddpg_trucktrailer_amd.replay_buffer import check_n_step, learn_start, slots_needed
 from ddpg_trucktrailer_amd.stepper import VectorStepper
 
@@ -65,6 +69,23 @@ def _gc_off():
     finally:
         if was_on:
             gc.enable()
+
+
+_AGENT_OPTIONS = ("demo_loss", "loss_shape", "td3")        # what an agent passed in was itself built with: Agent(demo_loss=, ...)
+
+
+def _same_as_agent(name, agent, value):
+    """ValueError when the agent passed in (None: the loop makes its own) was built with another `name` than the loop's value.  Of
+    td3 only the presence counts: the agent's second critic."""
+    theirs = getattr(agent, name, None)
+    if agent is None or (theirs is None and value is None):
+        return
+    if value is None:
+        raise ValueError(f"{name}: the agent passed in was built with {'td3' if name == 'td3' else 'a ' + name}, the loop without")
+    if name == "td3" and theirs is None:
+        raise ValueError("td3: the agent passed in was built without td3 (Agent(td3=...))")
+    if name != "td3" and theirs != value:
+        raise ValueError(f"{name}: the agent passed in was built with {name} = {theirs!r}, the loop with {value!r}")
 
 
 class DDPGRollout(VectorStepper):
@@ -118,49 +139,26 @@ class DDPGRollout(VectorStepper):
         driven by the policy as every lane is -- their trajectories do not change by a bit -- and the expert's decision on each
         of their states goes to the ring's label array, in the expert lanes' launch.  The demonstration term clones the label on
         the ring rows of those lanes (code 3 in demo_stats: "labelled"), unfiltered.  mpc.check_expert_labels names what is refused."""
-        if labels is not None:
-            from ddpg_trucktrailer_amd.mpc import check_expert_labels
-            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
-            check_expert_labels(labels, expert=expert, n_envs=env.n_envs, data_parallel=ranks or dp_exchange == "p2p",
-                                force_dp=os.environ.get("TT_FORCE_DP") == "1", demo_loss=demo_loss)
-        if expert is not None:
-            from ddpg_trucktrailer_amd.mpc import check_expert_lanes
-            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
-            check_expert_lanes(expert, n_envs=env.n_envs, data_parallel=ranks or dp_exchange == "p2p",
-                               force_dp=os.environ.get("TT_FORCE_DP") == "1")
-        self.n_step = check_n_step(n_step)
-        self.demo_loss = None
-        if demo_loss is not None:
-            from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
-            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
-            self.demo_loss = check_demo_loss(demo_loss, td3=td3, data_parallel=ranks or dp_exchange == "p2p",
-                                             force_dp=os.environ.get("TT_FORCE_DP") == "1", n_step=self.n_step)
-            if agent is not None and getattr(agent, "demo_loss", None) != self.demo_loss:
-                raise ValueError(f"demo_loss: the agent passed in was built with demo_loss = {getattr(agent, 'demo_loss', None)!r}, "
-                                 f"the loop with {self.demo_loss!r}")
-        elif agent is not None and getattr(agent, "demo_loss", None) is not None:
-            raise ValueError("demo_loss: the agent passed in was built with a demo_loss, the loop without")
-        self.loss_shape = None
-        if loss_shape is not None:
-            from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
-            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
-            self.loss_shape = check_loss_shape(loss_shape, td3=td3, data_parallel=ranks or dp_exchange == "p2p",
-                                               force_dp=os.environ.get("TT_FORCE_DP") == "1")
-            if agent is not None and getattr(agent, "loss_shape", None) != self.loss_shape:
-                raise ValueError(f"loss_shape: the agent passed in was built with loss_shape = {getattr(agent, 'loss_shape', None)!r}, "
-                                 f"the loop with {self.loss_shape!r}")
-        elif agent is not None and getattr(agent, "loss_shape", None) is not None:
-            raise ValueError("loss_shape: the agent passed in was built with a loss_shape, the loop without")
-        self.td3 = None
-        if td3 is not None:
-            from ddpg_trucktrailer_amd.td3 import check_td3
-            ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
-            self.td3 = check_td3(td3, updates_per_step, self.n_step, ranks or dp_exchange == "p2p", pipeline, learn_log)
+        from ddpg_trucktrailer_amd.td3 import check_td3          # (here: td3.py imports this module)
+        ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
+        force_dp = os.environ.get("TT_FORCE_DP") == "1"
+        c = dict(labels=labels, expert=expert, n_step=n_step, demo_loss=demo_loss, loss_shape=loss_shape, td3=td3, n_envs=env.n_envs,
+                 data_parallel=ranks or dp_exchange == "p2p", force_dp=force_dp, updates_per_step=updates_per_step, pipeline=pipeline,
+                 learn_log=learn_log)
+        # the options in the order their refusals fire: (name, its check, the resolved values the check takes); the first bad one raises
+        for name, check, takes in (("labels", check_expert_labels, ("expert", "n_envs", "data_parallel", "force_dp", "demo_loss")),
+                                   ("expert", check_expert_lanes, ("n_envs", "data_parallel", "force_dp")),
+                                   ("n_step", check_n_step, ()),
+                                   ("demo_loss", check_demo_loss, ("td3", "data_parallel", "force_dp", "n_step")),
+                                   ("loss_shape", check_loss_shape, ("td3", "data_parallel", "force_dp")),
+                                   ("td3", check_td3, ("updates_per_step", "n_step", "data_parallel", "pipeline", "learn_log"))):
+            if c[name] is not None or name == "n_step":       # (n_step is no optional value)
+                c[name] = check(c[name], **{k: c[k] for k in takes})
+            if name in _AGENT_OPTIONS:
+                _same_as_agent(name, agent, c[name])
+        self.n_step, self.demo_loss, self.loss_shape, self.td3 = c["n_step"], c["demo_loss"], c["loss_shape"], c["td3"]
+        if self.td3 is not None:
             pipeline = False
-            if agent is not None and getattr(agent, "td3", None) is None:
-                raise ValueError("td3: the agent passed in was built without td3 (Agent(td3=...))")
-        elif agent is not None and getattr(agent, "td3", None) is not None:
-            raise ValueError("td3: the agent passed in was built with td3, the loop without")
         if learn_log is not None:
             from ddpg_trucktrailer_amd.fused_learn import check_learn_log
             learn_log, learn_log_every = check_learn_log(learn_log, learn_log_every)
@@ -169,7 +167,7 @@ class DDPGRollout(VectorStepper):
                              f"with their n steps intact needs at least {slots_needed(self.n_step)} slots")
         self.updates_per_step = int(updates_per_step)
         assert self.updates_per_step >= 1
-        self.dp = (world_size > 1) if data_parallel is None else bool(data_parallel)
+        self.dp = ranks
         if self.n_step > 1 and self.dp:
             raise ValueError("n_step > 1 with data-parallel ranks is not supported (the ranks' segments draw through the one-step sampler)")
         super().__init__(env, batch_size=batch_size, replay_slots=replay_slots, seed=seed, alpha=alpha, beta=beta, tau=tau, gamma=gamma,
@@ -222,12 +220,12 @@ class DDPGRollout(VectorStepper):
             if self.learner is None or self.device.type != "cuda":
                 raise ValueError("learn_log needs the fused learner (reference-shaped networks on a GPU): the torch path keeps "
                                  "Agent.last_critic_loss / last_actor_loss instead")
-            if self.dp or os.environ.get("TT_FORCE_DP") == "1":
+            if self.dp or force_dp:
                 raise ValueError("learn_log with data-parallel ranks is not supported: a rank's own gradient buffer is not what its "
                                  "optimizer applies")
             self.learner.enable_learn_log(learn_log, learn_log_every)
         self.use_graph = use_graph and self.device.type == "cuda"
-        if os.environ.get("TT_FORCE_DP") == "1" and self.learner is not None and not self.dp and self.td3 is None:
+        if force_dp and self.learner is not None and not self.dp and self.td3 is None:
             # measurement aid: the data-parallel launch structure (three graph segments, separate Adam launches) on ONE
             # rank with no-op collectives -- what a rank's step costs before any time on the wire
             self.dp = True
@@ -242,7 +240,7 @@ class DDPGRollout(VectorStepper):
         need = slots_needed(self.n_step, _PIPE_RESERVE if self.pipeline else 0)
         if self.n_step > 1 and replay_slots < need:
             raise ValueError(f"n_step = {self.n_step} with replay_slots = {replay_slots} is not supported: this order needs {need} slots")
-        if self.n_step > 1 and os.environ.get("TT_FORCE_DP") == "1":
+        if self.n_step > 1 and force_dp:
             raise ValueError("n_step > 1 with the data-parallel launch structure (TT_FORCE_DP) is not supported")
         self._learn_from, self._warm_steps = learn_start(self.n_step)
         self.two_images = self.pipeline         # (stepper.py: the policy reads the image its step's opening launch packed)
@@ -290,7 +288,7 @@ class DDPGRollout(VectorStepper):
             return {}
         from ddpg_trucktrailer_amd.mpc import expert_mask, gather_labels
         rows = dict(demo_rows=expert_mask(index, self.expert.lanes if self.expert is not None else 0))
-        if getattr(self, "labels", None) is not None:           # the label of a labelled row, from the ring's array at the row's (slot, lane)
+        if self.labels is not None:           # the label of a labelled row, from the ring's array at the row's (slot, lane)
             lab, values = gather_labels(self.ring.label, index, self.label_first, self.labels.lanes)      # (labelled rows only)
             rows.update(label_rows=lab, labels=values)
         return rows
@@ -716,13 +714,7 @@ class DDPGRollout(VectorStepper):
                 sd["optim"]["critic_2"] = ag.critic_2.optimizer.state_dict()
                 sd["td3_updates"] = int(ag.td3_updates)
                 sd["td3_noise"] = ag.td3_noise_state()               # (the torch path's generator; the fused path's noise is counter-based)
-        if self.td3 is not None:
-            sd["td3"] = list(self.td3.as_tuple())
-        if self.loss_shape is not None:
-            sd["loss_shape"] = list(self.loss_shape.as_tuple())
-        if self.demo_loss is not None:
-            sd["demo_loss"] = list(self.demo_loss.as_tuple())
-        return sd
+        return write_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss)      # (expert, labels: the stepper's)
 
     def demo_stats(self):
         """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}; with expert lanes the ring rows of those
@@ -743,18 +735,8 @@ class DDPGRollout(VectorStepper):
         assert int(sd["batch_size"]) == int(self.batch_size), "batch size differs"
         if int(sd.get("n_step", 1)) != self.n_step:
             raise ValueError(f"the checkpoint was written with n_step = {int(sd.get('n_step', 1))}, this loop has n_step = {self.n_step}")
-        if ("td3" in sd) != (self.td3 is not None):
-            raise ValueError("the checkpoint was written with td3, this loop has none" if "td3" in sd else
-                             "the checkpoint was written without td3, this loop has td3 (no second critic in it)")
-        have = tuple(sd["loss_shape"]) if sd.get("loss_shape") is not None else None
-        mine = self.loss_shape.as_tuple() if self.loss_shape is not None else None
-        if have != mine:
-            raise ValueError(f"the checkpoint was written with loss_shape = {have}, this loop has loss_shape = {mine}")
-        have = tuple(sd["demo_loss"]) if sd.get("demo_loss") is not None else None
-        mine = self.demo_loss.as_tuple() if self.demo_loss is not None else None
-        if have != mine:
-            raise ValueError(f"the checkpoint was written with demo_loss = {have}, this loop has demo_loss = {mine}")
-        self.check_expert_state(sd)                                   # (before anything is written)
+        compare_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, expert=self.expert,
+                        labels=self.labels)                           # (before anything is written)
         self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])

@@ -10,10 +10,13 @@ import torch
 from ddpg_trucktrailer_amd import fused
 from ddpg_trucktrailer_amd.agent import Agent
 from ddpg_trucktrailer_amd.noise import VecOUNoise
+from ddpg_trucktrailer_amd.options import compare_options, write_options
 from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 
 
 class VectorStepper:
+    expert = labels = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
+
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
                  episode_log_detail=False, td3=None, expert=None, labels=None):
@@ -163,9 +166,8 @@ class VectorStepper:
         vector_steps, nets (four networks, six with TD3), ring, ou and env (with the episode log's state when it is on).  The
         caller has synchronised."""
         ag = self.agent
-        ex = {} if self.expert is None else {"expert": list(self.expert.as_tuple()), "expert_plan": self.expert_plan.detach().cpu().clone()}
-        if self.labels is not None:           # (expert_plan is then the launch's whole plan [M + L, H])
-            ex["labels"] = list(self.labels.as_tuple())
+        ex = write_options({}, expert=self.expert, labels=self.labels)
+        if ex:                                # (with labels expert_plan is the launch's whole plan [M + L, H])
             ex["expert_plan"] = self.expert_plan.detach().cpu().clone()
         return {**ex, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
                 "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()} for n in self.net_names()},
@@ -180,17 +182,8 @@ class VectorStepper:
                     v.copy_(net_sd[k].to(v.device))
 
     def check_expert_state(self, sd):
-        """ValueError when acting_state() `sd` was written with other expert lanes than this stepper's (or with none)."""
-        have = sd.get("expert")
-        have = (int(have[0]), tuple(have[1]), int(have[2])) if have is not None else None
-        mine = self.expert.as_tuple() if self.expert is not None else None
-        if have != mine:
-            raise ValueError(f"the checkpoint was written with expert = {have}, this loop has expert = {mine}")
-        have = sd.get("labels")
-        have = (int(have[0]), tuple(have[1]), int(have[2])) if have is not None else None
-        mine = self.labels.as_tuple() if self.labels is not None else None
-        if have != mine:
-            raise ValueError(f"the checkpoint was written with labels = {have}, this loop has labels = {mine}")
+        """ValueError when acting_state() `sd` was written with other expert lanes or labels than this stepper's (or with none)."""
+        compare_options(sd, expert=self.expert, labels=self.labels)
 
     def load_acting_state(self, sd):
         """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are

@@ -9,54 +9,35 @@
 
 The torch form of the same update is Agent(td3=cfg).learn_batch (agent.py): the CPU path, and the twin the kernels are tested against."""
 import ctypes as C
-import math
 
 import torch
 
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner, _NetState
+from ddpg_trucktrailer_amd.options import Option, finite_number, refuse
 from ddpg_trucktrailer_amd.population import _PopulationLearnerBase
 
 
-class TD3Config:
+class TD3Config(Option):
     """policy_delay d >= 1: every d-th update is a full one (actor step, soft update of all three targets), the others train the two
-    critics only.  target_noise sigma >= 0 and noise_clip c >= 0: a' = clip(mu'(s') + clip(sigma N(0, 1), -c, c), -1, 1)."""
+    critics only.  target_noise sigma >= 0 and noise_clip c >= 0: a' = clip(mu'(s') + clip(sigma N(0, 1), -c, c), -1, 1).
+    Kept as they were: policy_delay may be an integer-valued float, and True / False count as numbers for the two noise values."""
+    FIELDS = ("policy_delay", "target_noise", "noise_clip")
 
     def __init__(self, policy_delay=2, target_noise=0.2, noise_clip=0.5):
         if isinstance(policy_delay, bool) or int(policy_delay) != policy_delay or int(policy_delay) < 1:
             raise ValueError(f"policy_delay = {policy_delay!r} is not an integer >= 1")
-        for name, x in (("target_noise", target_noise), ("noise_clip", noise_clip)):
-            if not (isinstance(x, (int, float)) and math.isfinite(x) and x >= 0):
-                raise ValueError(f"{name} = {x!r} is not a finite number >= 0")
+        finite_number("target_noise", target_noise, ">= 0", or_bool=True)
+        finite_number("noise_clip", noise_clip, ">= 0", or_bool=True)
         self.policy_delay, self.target_noise, self.noise_clip = int(policy_delay), float(target_noise), float(noise_clip)
-
-    def __repr__(self):
-        return f"TD3Config(policy_delay={self.policy_delay}, target_noise={self.target_noise}, noise_clip={self.noise_clip})"
-
-    def __eq__(self, other):
-        return isinstance(other, TD3Config) and self.as_tuple() == other.as_tuple()
-
-    def as_tuple(self):
-        return (self.policy_delay, self.target_noise, self.noise_clip)
 
 
 def check_td3(cfg, updates_per_step=1, n_step=1, data_parallel=False, pipeline=None, learn_log=None):
     """What a loop with TD3 refuses, each a ValueError that names the option.  The delay is counted inside a vector step, so that one
     captured step serves every step: updates_per_step must be a multiple of policy_delay."""
-    if not isinstance(cfg, TD3Config):
-        raise ValueError(f"td3 = {cfg!r} is not a TD3Config")
-    if int(updates_per_step) % cfg.policy_delay != 0:
-        raise ValueError(f"td3: updates_per_step = {updates_per_step} is not a multiple of policy_delay = {cfg.policy_delay} (the delay "
-                         "is counted inside a vector step)")
-    if int(n_step) > 1:
-        raise ValueError(f"td3: n_step = {n_step} > 1 is not supported")
-    if data_parallel:
-        raise ValueError("td3: data_parallel ranks (and the p2p exchange) are not supported")
-    if pipeline:
-        raise ValueError("td3: pipeline=True is not supported (TD3 runs in the serial order)")
-    if learn_log is not None:
-        raise ValueError("td3: learn_log is not supported")
-    return cfg
+    TD3Config.expect("td3", cfg)
+    return refuse("td3", cfg, updates_per_step=updates_per_step, delay=cfg.policy_delay, n_step=n_step, data_parallel=data_parallel,
+                  pipeline=pipeline, learn_log=learn_log)
 
 
 class TD3Learner(FusedLearner):
@@ -337,18 +318,6 @@ def check_population_td3(td3, K, updates_per_step=1, n_steps=(1,), n_step_max=1,
     else:
         cfgs = [td3] * K
     for c in cfgs:
-        if not isinstance(c, TD3Config):
-            raise ValueError(f"td3 = {c!r} is not a TD3Config")
-    delay = same_policy_delay(cfgs)
-    if int(updates_per_step) % delay != 0:
-        raise ValueError(f"td3: updates_per_step = {updates_per_step} is not a multiple of policy_delay = {delay} (the delay is "
-                         "counted inside a vector step)")
-    if any(int(n) > 1 for n in n_steps):
-        raise ValueError(f"td3: n_step = {list(n_steps)} > 1 is not supported")
-    if int(n_step_max) > 1:
-        raise ValueError(f"td3: n_step_max = {n_step_max} > 1 is not supported")
-    if learn_log is not None:
-        raise ValueError("td3: learn_log is not supported")
-    if torch.device(device).type != "cuda":
-        raise ValueError(f"td3: device = {device!r} is not supported: a population's TD3 update exists only as HIP kernels")
-    return cfgs
+        TD3Config.expect("td3", c)
+    return refuse("population_td3", cfgs, updates_per_step=updates_per_step, delay=same_policy_delay(cfgs), n_steps=n_steps,
+                  n_step_max=n_step_max, learn_log=learn_log, device=device)

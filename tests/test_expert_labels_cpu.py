@@ -21,6 +21,7 @@ import demo_ref as D
 import fake_args as F
 import label_ref as LR
 import learn_ref as R
+from cpu_env import CpuEnv as _CpuEnv
 
 _CASE = D.F64_CASES[1]          # B = 33, fresh state
 
@@ -99,15 +100,6 @@ def test_check_expert_labels_allows_what_fits_and_refuses_what_is_not_an_expert_
 
 
 # ------------------------------------------------------------------------------------------------- the loop, the stepper, the learner
-class _CpuEnv:
-    """What a VectorStepper asks of an env before its first step, on the CPU (no launch is ever made)."""
-    observation_dim, n_envs, device, max_steer = 23, 4, torch.device("cpu"), float(np.float32(np.pi / 4))
-
-    def observe(self, out=None):
-        out.zero_()
-        return out
-
-
 def test_the_loop_and_the_stepper_refuse_expert_labels(monkeypatch):
     from ddpg_trucktrailer_amd.demo_loss import DemoLoss
     from ddpg_trucktrailer_amd.mpc import ExpertLabels

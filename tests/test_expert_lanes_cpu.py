@@ -15,6 +15,7 @@ import pytest
 import torch
 
 import fake_args as F
+from cpu_env import CpuEnv as _CpuEnv
 
 
 @pytest.fixture(scope="module")
@@ -72,15 +73,6 @@ def test_check_expert_lanes_refuses_what_is_not_an_expert_lanes():
 
 
 # ------------------------------------------------------------------------------------------------- the loops
-class _CpuEnv:
-    """What a VectorStepper asks of an env before its first step, on the CPU (no launch is ever made)."""
-    observation_dim, n_envs, device, max_steer = 23, 4, torch.device("cpu"), float(np.float32(np.pi / 4))
-
-    def observe(self, out=None):
-        out.zero_()
-        return out
-
-
 def test_steppers_and_populations_refuse_expert_lanes(monkeypatch):
     from ddpg_trucktrailer_amd.mpc import ExpertLanes
     from ddpg_trucktrailer_amd.population import PopulationLearner, PopulationRollout
