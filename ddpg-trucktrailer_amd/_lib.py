@@ -245,6 +245,7 @@ _SIGNATURES = {
     "tt_p2p_attach": (C.c_int, [_P, _I, _P]),
     "tt_p2p_grad": (_P, [_P, _I]),
     "tt_p2p_reset": (C.c_int, [_P, _P]),
+    "tt_p2p_reset_at": (C.c_int, [_P, C.c_int64, _P]),
     "tt_p2p_set_timeout": (C.c_int, [_P, C.c_double]),
     "tt_p2p_gave_up": (C.c_int, [_P]),
     "tt_p2p_last_error": (C.c_char_p, [_P]),

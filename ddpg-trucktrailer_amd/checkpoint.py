@@ -39,6 +39,10 @@ def save_training_checkpoint(path, agent, env=None, ring=None, noise=None, train
           "hyper": dict(alpha=agent.alpha, beta=agent.beta, tau=agent.tau, gamma=agent.gamma, batch_size=agent.batch_size),
           "training_state": training_state or {},
           "rng": _rng_state()}
+    if getattr(agent, "fused_learner", None) is not None:
+        # the optimizers' `step` is an f32 tensor (torch.optim.Adam's own format): exact to 2^24 only.  The fused learner's 64-bit
+        # step counts -- TD3's noise key, the tail epoch and the learn log's labels hang on them -- go beside it as plain integers
+        ck["learn_steps"] = agent.fused_learner.step_counts()
     if getattr(agent, "td3", None) is not None:          # TD3: the second critic, its target and its optimizer state
         for n in ("critic_2", "target_critic_2"):
             ck["nets"][n] = getattr(agent, n).state_dict()
@@ -71,6 +75,8 @@ def load_training_checkpoint(path, agent, env=None, ring=None, noise=None):
         agent.critic_2.optimizer.load_state_dict(ck["optim"]["critic_2"])
     if getattr(agent, "fused_learner", None) is not None:
         agent.fused_learner.import_from_optimizers()
+        if "learn_steps" in ck:                # (a file written before the counts were kept has the f32 step alone)
+            agent.fused_learner.set_step_counts(ck["learn_steps"])
     if env is not None and "env" in ck:
         env.load_state_dict(ck["env"])
     if noise is not None and "ou" in ck:

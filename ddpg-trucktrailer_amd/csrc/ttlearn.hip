@@ -225,7 +225,7 @@ __global__ __launch_bounds__(256) void k_adam_soft_p2p(const AdamTable T, const 
         const unsigned long long t0 = wall_clock64();
         bool gave_up = false;
         for (int r = 0; r < X.world && !gave_up; ++r) {
-            while (__hip_atomic_load(mine + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) - epoch < 0) {
+            while (!ttnet::epoch_reached(__hip_atomic_load(mine + r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM), epoch)) {
                 __builtin_amdgcn_s_sleep(8);
                 if (wall_clock64() - t0 > X.wait_ticks) {      // never hang: mark (host-visible) and go on; the caller treats the ranks as diverged
                     __hip_atomic_store(X.gave_up_host, epoch, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);

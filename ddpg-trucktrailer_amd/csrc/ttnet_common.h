@@ -291,6 +291,15 @@ __device__ __forceinline__ void publish_image(const RingCursor &c, const int wor
         }
     }
 }
+// Epochs, progress and arrival words hold the LOW 32 BITS of 64-bit step numbers ((int)(k + 1), (int)*k_dev, (int)step), so "word
+// >= want" is asked of the wrapped difference: have has reached want when (have - want) mod 2^32, read as a signed number, is not
+// negative -- right whenever the two are less than 2^31 steps apart, wherever the counter stands (2^31 - 1 -> 2^31 and
+// 2^32 - 1 -> 2^32 included).  The difference is formed in UNSIGNED arithmetic: the signed `have - want >= 0` overflows at the
+// wrap, which is undefined, and a compiler may fold it to `have >= want`.  (Same instructions as the signed form gave: a 32-bit
+// subtraction and a signed compare.)  DESIGN.md, "Counter widths".
+__device__ __forceinline__ bool epoch_reached(const int have, const int want) {
+    return (int)((unsigned)have - (unsigned)want) >= 0;
+}
 // early: both epoch words as thread 0 found them BEFORE it knew the step number (await_image_early: loads that do not depend on
 // the step counter, so that they share its round trip instead of following it); {0, 0} from the other threads / without a cursor
 struct EpochPair { int e[2]; };
@@ -319,13 +328,13 @@ __device__ __forceinline__ void await_image(int *cursor, const long long *step_d
         // writer.  Checked by the 1500-step bitwise test and the soaks (tools/soak.py), not provable from here.
         // (`early`: the same word as read a round trip earlier, beside the step counter; epochs only grow, so an early value that
         // is large enough is as good as a fresh one)
-        if (early.e[k & 1] - want >= 0 || __hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want >= 0) TT_POLL(0);
+        if (epoch_reached(early.e[k & 1], want) || epoch_reached(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), want)) TT_POLL(0);
         else {
             TT_POLL(1);
             // (one poll per ~3 us and workgroup: 171 workgroups polling one word every 0.1 us slowed the very launches they
             // were waiting for -- seen under rocprofv3's kernel trace, where the learn chain falls behind: 224 us per policy launch)
             const unsigned long long t0 = wall_clock64();
-            while (__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want < 0) {
+            while (!epoch_reached(__hip_atomic_load(flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), want)) {
                 __builtin_amdgcn_s_sleep(127);
                 if (wall_clock64() - t0 > TT_IMAGE_WAIT_TICKS) {      // never hang: leave a mark the host checks, and go on
                     mark_gave_up(cursor, want);
@@ -349,11 +358,11 @@ __device__ __forceinline__ void await_progress(int *progress, const long long *k
     if (!progress) return;
     if (threadIdx.x == 0) {
         const int want = (int)*k_dev;
-        if (__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want >= 0) TT_POLL(2);
+        if (epoch_reached(__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), want)) TT_POLL(2);
         else {
             TT_POLL(3);
             const unsigned long long t0 = wall_clock64();
-            while (__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want < 0) {
+            while (!epoch_reached(__hip_atomic_load(progress, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), want)) {
                 __builtin_amdgcn_s_sleep(32);
                 if (wall_clock64() - t0 > TT_IMAGE_WAIT_TICKS) {
                     mark_gave_up(progress - CUR_PROGRESS, want + 1);

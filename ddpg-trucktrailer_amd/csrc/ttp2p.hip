@@ -130,14 +130,18 @@ float *tt_p2p_grad(const tt_p2p *x, int site) {
     return reinterpret_cast<float *>(x->block[x->rank] + x->offset[site]);
 }
 
-int tt_p2p_reset(tt_p2p *x, tt_stream_t stream) {
+int tt_p2p_reset_at(tt_p2p *x, int64_t step, tt_stream_t stream) {
     if (!x) return fail(nullptr, TT_EINVAL, "tt_p2p_reset: NULL handle");
     P2P_HIP(x, hipSetDevice(x->device));
-    P2P_HIP(x, hipMemsetAsync(x->flags[x->rank], 0, ttp2p::FLAG_BYTES, stream));
+    // every word of the flag block is an int: the arrival words are its first MAXS * MAXR
+    P2P_HIP(x, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(x->flags[x->rank]), (int)(uint32_t)(uint64_t)step,
+                                 ttp2p::FLAG_BYTES / sizeof(int), stream));
     P2P_HIP(x, hipStreamSynchronize(stream));
     *x->gave_up_host = 0;
     return TT_OK;
 }
+
+int tt_p2p_reset(tt_p2p *x, tt_stream_t stream) { return tt_p2p_reset_at(x, 0, stream); }
 
 int tt_p2p_set_timeout(tt_p2p *x, double seconds) {
     if (!x || !(seconds > 0.0) || seconds > 3600.0) return fail(x, TT_EINVAL, "tt_p2p_set_timeout: %g s", seconds);

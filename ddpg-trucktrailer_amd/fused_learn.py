@@ -13,7 +13,7 @@ import torch
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd import fused
 from ddpg_trucktrailer_amd.options import compare_options, refuse, write_options
-from ddpg_trucktrailer_amd.replay_buffer import check_n_step
+from ddpg_trucktrailer_amd.replay_buffer import check_n_step, wrap32
 
 _p = L.ptr        # (the name this module's callers import)
 
@@ -490,6 +490,7 @@ class FusedLearner:
         for site, st in enumerate((self.critic, self.actor)):
             st.bind_flat_grad(_device_view(self.lib.tt_p2p_grad(h, site), st.flat_grad.numel(), self.dev, owner=self))
         self.grad_sync_critic = self.grad_sync_actor = _no_sync       # (learn_batch's data-parallel order: separate Adam launches)
+        self.p2p_reset()                   # (the fresh block's zeros are behind the next epoch only below 2^31 - 1 learn steps)
 
     # ---- learn log -----------------------------------------------------------------------------------------------
     def _refuse_ranks_with_learn_log(self):
@@ -530,7 +531,9 @@ class FusedLearner:
         return int(self.lib.tt_p2p_gave_up(self.p2p)) if self.p2p is not None else 0
 
     def p2p_reset(self):
-        """After the learn-step counter was set back (a resume): arrival words of earlier runs must not satisfy new waits."""
+        """After the learn-step counter was set (a resume): arrival words of earlier runs must not satisfy new waits.  The words
+        become the low 32 bits of the step count as it stands, which is behind the next update's epoch in the kernel's wrapped
+        comparison wherever the count is (tt_p2p_reset_at); zeros are behind it only while the count is below 2^31 - 1."""
         if self.p2p is None:
             return
         import torch.distributed as dist
@@ -538,7 +541,7 @@ class FusedLearner:
         torch.cuda.synchronize(self.dev)
         if multi:
             dist.barrier(self._p2p_group)
-        L.check_p2p(self.lib.tt_p2p_reset(self.p2p, self._stream()), self.p2p)
+        L.check_p2p(self.lib.tt_p2p_reset_at(self.p2p, int(self.step_dev.item()), self._stream()), self.p2p)
         if multi:
             dist.barrier(self._p2p_group)
 
@@ -730,12 +733,34 @@ class FusedLearner:
             st = getattr(self, name)
             st.m.copy_(sd[name]["m"]); st.v.copy_(sd[name]["v"])
         self.step_dev.fill_(int(sd["step"]))
-        self.tail_words.fill_(-1)          # (tt_mlp_actor_tail: words of an earlier run must not match a step number set back)
+        self.reset_tail_words(int(sd["step"]))
         self.p2p_reset()
         if self.learn_log is not None:     # (a step counter set back must not meet records from its future)
             self.learn_log.clear()
 
+    def reset_tail_words(self, step):
+        """After the count the actor tail keys its words by was set to `step` (FusedLearner: the learn step; TD3Learner: the actor
+        step): no word of an earlier run may match the epoch of the next tail launch.  tail_row and tail_wait_hints
+        (csrc/ttlearn_bodies.h) compare a word's upper half with (int)(step + 1) for EQUALITY, so a stale word is harmless exactly
+        when it differs from wrap32(step + 1).  The fill is -1, a fresh learner's, which differs from every epoch but that of
+        step = 2^32 - 2 mod 2^32; there it is -2.  Every later launch finds the words of the launch before it, one step behind
+        its own epoch."""
+        self.tail_words.fill_(-1 if wrap32(step + 1) != -1 else -2)
+
+    def step_counts(self):
+        """The learner's step counts as exact integers (a checkpoint keeps them beside the torch optimizers' f32 `step` tensors,
+        which hold integers exactly only up to 2^24).  Synchronises."""
+        return {"step": int(self.step_dev.item())}
+
+    def set_step_counts(self, counts):
+        """step_counts() back, after import_from_optimizers (whose f32 step may be rounded)."""
+        self.step_dev.fill_(int(counts["step"]))
+        self.reset_tail_words(int(counts["step"]))
+        self.p2p_reset()
+
     # ---- checkpoint interoperability with the torch optimizers ------------------------------------------
+    # (the optimizers' own `step` stays an f32 tensor, as torch.optim.Adam makes it -- its fused form reads it as such --, so past
+    # 2^24 it is the learn step ROUNDED: checkpoint.py carries step_counts() beside the optimizer state)
     def export_to_optimizers(self):
         step = self.step_dev.to(torch.float32).clone()
         for st, opt in ((self.actor, self.agent.actor.optimizer), (self.critic, self.agent.critic.optimizer)):

@@ -19,6 +19,12 @@ def check_n_step(n):
     return n
 
 
+def wrap32(x):
+    """The low 32 bits of the integer x as a signed 32-bit number: what a device word holds of a 64-bit counter ((int)k in the
+    kernels), and what an int32 tensor takes without an overflow error."""
+    return ((int(x) + 2 ** 31) & 0xFFFFFFFF) - 2 ** 31
+
+
 def slots_needed(n_step, reserve=0):
     """Ring slots an n-step draw needs, as the kernels ask: a base step with all its n steps inside the window, which leaves out
     the slot being written and the `reserve` newest ones (a pipelined draw's)."""
@@ -218,16 +224,23 @@ class TrajectoryRing:
             self.side_epoch += 1
         self.k = int(sd["k"])               # the counters come back whether or not the contents did
         self.k_dev.fill_(self.k)
-        self.cursor_dev.zero_()             # image epochs are step numbers: a counter set back must not find newer ones
-        self.cursor_dev[16] = self.k        # ... and the step chain is where the counters say (TT_CURSOR_PROGRESS)
+        # The hand-over words hold the low 32 bits of 64-bit step numbers and are compared in wrapped arithmetic (ttnet_common.h:
+        # epoch_reached), so they are written RELATIVE to k ("Counter widths"): both image epochs become wrap32(k), which
+        # is behind k + 1 and k + 2, what the policy launches of the next two steps wait for -- a zero is "already published" for
+        # every k in [2^31 - 1, 2^32 - 2] -- and the step chain is where the counters say (TT_CURSOR_PROGRESS).  k = 0 keeps zeros.
+        self.cursor_dev.zero_()
+        self.cursor_dev[12:14] = wrap32(self.k)
+        self.cursor_dev[16] = wrap32(self.k)
         self._write_mirror_address()
         if self.gave_up_host is not None:
             self._gave_up_np[0] = 0
 
     def policy_gave_up(self):
-        """Step number + 1 at which a launch stopped waiting for the other chain -- a policy launch for its image, or learn()'s first
-        launch for the step chain's progress (include/ttenv.h: TT_CURSOR_GAVE_UP, TT_CURSOR_PROGRESS) --, 0 = never.
-        Synchronises."""
+        """The mark of a launch that stopped waiting for the other chain -- a policy launch for its image, or learn()'s first launch
+        for the step chain's progress (include/ttenv.h: TT_CURSOR_GAVE_UP, TT_CURSOR_PROGRESS) --, 0 = never.  The mark is the low
+        32 bits of (vector step number + 1) as a signed int32: the step number + 1 itself below 2^31, negative from there to
+        2^32, and 0 -- indistinguishable from "never" -- for the one step in every 2^32 with step + 1 = 0 mod 2^32 (DESIGN.md,
+        "Counter widths").  Synchronises."""
         return int(self.cursor_dev[15].item()) or self.gave_up_seen()
 
     def gave_up_seen(self):
@@ -238,10 +251,10 @@ class TrajectoryRing:
 
     def mark_gave_up_for_test(self, step):
         """What a launch of vector step `step` that gives up leaves behind (device word and host mirror): tests of the fallback."""
-        self.cursor_dev[15] = int(step) + 1
+        self.cursor_dev[15] = wrap32(int(step) + 1)
         torch.cuda.current_stream(self.device).synchronize()
         if self.gave_up_host is not None:
-            self._gave_up_np[0] = int(step) + 1
+            self._gave_up_np[0] = wrap32(int(step) + 1)
 
     def clear_gave_up(self):
         self.cursor_dev[15] = 0

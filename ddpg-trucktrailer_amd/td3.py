@@ -206,7 +206,16 @@ class TD3Learner(FusedLearner):
         super().load_state_dict(sd)
         self.critic_2.m.copy_(sd["critic_2"]["m"]); self.critic_2.v.copy_(sd["critic_2"]["v"])
         self.actor_step_dev.fill_(int(sd["actor_step"]))
+        self.reset_tail_words(int(sd["actor_step"]))      # (the TD3 tail's epoch is the ACTOR step: FusedLearner.reset_tail_words)
         self.updates = int(sd.get("updates", 0))
+
+    def step_counts(self):
+        return {"step": int(self.step_dev.item()), "actor_step": int(self.actor_step_dev.item())}
+
+    def set_step_counts(self, counts):
+        super().set_step_counts(counts)
+        self.actor_step_dev.fill_(int(counts["actor_step"]))
+        self.reset_tail_words(int(counts["actor_step"]))
 
     def export_to_optimizers(self):
         ag = self.agent
@@ -225,7 +234,7 @@ class TD3Learner(FusedLearner):
                 if s:
                     m.copy_(s["exp_avg"].reshape(-1)); v.copy_(s["exp_avg_sq"].reshape(-1))
                     step_dev.fill_(int(float(s["step"])))
-        self.tail_words.fill_(-1)
+        self.reset_tail_words(int(self.actor_step_dev.item()))
 
 
 HYPERS6 = ("alpha", "beta", "tau", "gamma", "target_noise", "noise_clip")

@@ -187,7 +187,9 @@ typedef struct tt_ring_cursor {
     int32_t slots, reserved_;
     int32_t *cursor;        /* [TT_CURSOR_INTS] device (tt_ring_view): the launch writes the four numbers of step *k_dev at [4 + 4 (k & 1)] */
 } tt_ring_cursor;
-/* Image hand-over (cursor[12..15], zero-initialised by the caller, re-zeroed when *k_dev is set back): a pack launch given a
+/* Image hand-over (cursor[12..15], zero-initialised by the caller; when *k_dev is set to k -- a resume -- the caller sets both
+ * epoch words to the low 32 bits of k, behind the epochs k + 1 and k + 2 that the next two steps wait for, and zeroes [14..15]):
+ * the words hold the low 32 bits of step numbers and are compared in wrapped 32-bit arithmetic.  A pack launch given a
  * cursor ends by publishing "cursor and image of step k = *k_dev are complete" as cursor[12 + (k & 1)] = k + 1 (release,
  * device scope), and tt_actor_act_ring begins by waiting for cursor[12 + (k & 1)] >= k + 1 with k = its *step_dev (bounded:
  * after 0.25 s it sets cursor[15] = k + 1 and goes on -- TT_CURSOR_GAVE_UP; a caller that lets the two launches run
@@ -203,7 +205,7 @@ typedef struct tt_ring_cursor {
  * only when everything in front of it on its stream is complete and written back, so cursor[16] >= k + 1 says: the env step of
  * step k - 1 -- and every launch before it -- is over and visible.  tt_mlp_forward_multi_sampled can wait for that word instead of
  * for a stream / graph dependency on the env step (tt_sample_args.step_progress), so that a loop's learn chain needs no edge
- * from its step chain either.  The caller sets the word to *k_dev whenever it sets *k_dev (resume). */
+ * from its step chain either.  The caller sets the word to the low 32 bits of *k_dev whenever it sets *k_dev (resume). */
 #define TT_CURSOR_PROGRESS 16
 /* tt_env_step with obs -> ring slot t+1, reward and done -> slot t (env.step of the vector loop, trainv2.py:520-525). */
 int tt_env_step_ring(tt_env *env, const float *action, const tt_ring_view *ring, int auto_reset, tt_stream_t stream);
@@ -846,8 +848,11 @@ int tt_p2p_destroy(tt_p2p *x);                               /* closes the peers
 int tt_p2p_export(const tt_p2p *x, void *handle_out /*[TT_P2P_HANDLE_BYTES]*/);
 int tt_p2p_attach(tt_p2p *x, int peer, const void *handle /*[TT_P2P_HANDLE_BYTES] of rank `peer`*/);
 float *tt_p2p_grad(const tt_p2p *x, int site);                /* this rank's gradient buffer of `site` (device memory), or NULL */
-int tt_p2p_reset(tt_p2p *x, tt_stream_t stream);              /* own arrival words back to 0 (a step counter set back: resume);
-                                                                 the caller keeps every rank out of the exchange meanwhile */
+int tt_p2p_reset(tt_p2p *x, tt_stream_t stream);              /* tt_p2p_reset_at(x, 0, stream) */
+/* Own arrival words to the low 32 bits of `step`, the value *step_dev was set to (resume): the words are compared with the
+ * 32-bit epoch (int)(step + 1) of the next update in wrapped arithmetic, so they must lie BEHIND it -- a zero counts as arrived
+ * for every step in [2^31 - 1, 2^32 - 2] mod 2^32.  The caller keeps every rank out of the exchange meanwhile. */
+int tt_p2p_reset_at(tt_p2p *x, int64_t step, tt_stream_t stream);
 int tt_p2p_set_timeout(tt_p2p *x, double seconds);
 int tt_p2p_gave_up(const tt_p2p *x);                          /* 0, or the step whose wait was abandoned; reads host memory only */
 const char *tt_p2p_last_error(const tt_p2p *x);

@@ -27,6 +27,7 @@ def learner(dev, state, hyper, batch, step, images=True, shape=None, tail=False,
     agent = R.load_agent(state, hyper, dev, torch.float32)
     fl = FusedLearner(agent, batch[0].shape[0], fc2_images=images, loss_shape=shape, demo_loss=demo)
     fl.import_from_optimizers()
+    fl.step_dev.fill_(int(step))          # (the optimizers' f32 step holds it exactly only below 2^24)
     fl.refresh_images()
     fl.fuse_tail = tail
     assert fl.use_images == images and int(fl.step_dev.item()) == step
@@ -91,7 +92,7 @@ def flat(loop):
     return torch.cat([p.detach().reshape(-1) for net in loop.agent._nets() for p in net.parameters()])
 
 
-def against_f64(dev, state, hyper, batch, ref, *, delta=None, c=0.0, demo=None, images, tag, frozen=()):
+def against_f64(dev, state, hyper, batch, ref, *, delta=None, c=0.0, demo=None, images, tag, frozen=(), tail=False, prepare=None):
     """One learn_batch of a FusedLearner that holds `state` -- with LossShape(delta, c) unless both are off, with the DemoLoss `demo`
     and demo_ref.demo_index's rows when one is given -- every result against f64: `ref` is learn_ref.ref_step's result on the same
     state, batch and options.
@@ -110,13 +111,16 @@ def against_f64(dev, state, hyper, batch, ref, *, delta=None, c=0.0, demo=None, 
 
     Prints the worst error / bound per check (RATIOS) and, as figures, not checks: kappa, p's error over the bound with 2^-19 alone
     (no kappa), and the rows whose dQ/da was taken from the other side of a ReLU boundary than f64's.
+    tail: the actor tail in one launch (fuse_tail); prepare: called with the learner before its update (e.g. to turn its learn log on).
     Returns (worst ratios, the learner, the f64 actor half at dq64, dq64)."""
     import torch
     B, step0 = batch[0].shape[0], state["step"]
     shape = loss_shape(delta, c) if (delta is not None or c) else None
     lam = demo.bc_weight if demo is not None else 0.0
     h32 = R.f32_hyper(hyper)
-    agent, fl, (s, a, r, s2, d8) = learner(dev, state, hyper, batch, step0, images, shape, demo=demo)
+    agent, fl, (s, a, r, s2, d8) = learner(dev, state, hyper, batch, step0, images, shape, tail=tail, demo=demo)
+    if prepare is not None:
+        prepare(fl)
     twin = R.load_agent(state, hyper, dev, torch.float32)
     twin.loss_shape = shape
     before = {st: dict(p=[x.detach().clone() for x in st.params], t=[x.detach().clone() for x in st.targets],

@@ -69,8 +69,13 @@ def net_hyper(hyper, name):
 
 def load_agent(state, hyper, device, dtype):
     """An Agent (replay=False) of `dtype` on `device` that holds `state`: four nets, both optimizers' hyperparameters, Adam
-    moments and step count."""
+    moments and step count.  The optimizers' step is torch.optim.Adam's own f32 tensor while that holds it exactly (below 2^24:
+    every case that existed before steps beyond it were tested keeps its bits); from 2^24 on it is an f64 tensor on the CPU, where
+    Adam reads the step as a Python float either way, and stays f32 -- rounded -- on a GPU, whose fused Adam reads f32 steps: the
+    f32 twin there only lends its gradients, and a learner takes its exact count from learn_checks.learner."""
     from ddpg_trucktrailer_amd.agent import Agent
+    step = int(state["step"])
+    step_dtype = torch.float64 if step >= 2 ** 24 and torch.device(device).type == "cpu" else torch.float32
     agent = Agent(alpha=hyper["actor"]["lr"], beta=hyper["critic"]["lr"], input_dims=(23,), tau=hyper["tau"], n_actions=1,
                   gamma=hyper["gamma"], batch_size=1, device=device, replay=False)
     for name in NETS:
@@ -82,7 +87,7 @@ def load_agent(state, hyper, device, dtype):
         h = hyper[name]
         group["lr"], group["betas"], group["eps"], group["weight_decay"] = h["lr"], tuple(h["betas"]), h["eps"], h["weight_decay"]
         for k, p in net.named_parameters():
-            net.optimizer.state[p] = {"step": torch.tensor(float(state["step"]), dtype=torch.float32, device=p.device),
+            net.optimizer.state[p] = {"step": torch.tensor(float(step), dtype=step_dtype, device=p.device),
                                       "exp_avg": state["m"][name][k].to(device=device, dtype=dtype).clone(),
                                       "exp_avg_sq": state["v"][name][k].to(device=device, dtype=dtype).clone()}
     return agent

@@ -116,6 +116,29 @@ def draw_nstep(seed, k_counter, batch, n_envs, slots, n_step, reserve=0, lag=0):
     return np.stack([(k - 1 - back) % slots, env], axis=1)
 
 
+def draw_side(seed, k_counter, batch, n_envs, slots, side_count, reserve=0, lag=0):
+    """A one-step draw from a ring with side_count stand-alone tuples (TrajectoryRing.load_side): every one of the avail * n_envs
+    ring transitions and the side tuples is as likely.  Row b is side tuple j -- the pair (-1, j), j = (r0 * side_count) >> 32 --
+    when (u * (avail * n_envs + side_count)) >> 64 < side_count with u the 64-bit word r2 : r3, and draw()'s ring row otherwise."""
+    k, avail, r = _draw_words(seed, k_counter, batch, slots, reserve, lag)
+    idx = draw(seed, k_counter, batch, n_envs, slots, reserve, lag)
+    total = avail * n_envs + side_count
+    for b in range(batch):
+        u = (int(r[2][b]) << 32) | int(r[3][b])
+        if (u * total) >> 64 < side_count:
+            idx[b] = (-1, (int(r[0][b]) * side_count) >> 32)
+    return idx
+
+
+def gather_side(ring, side, idx):
+    """gather() where idx may hold side rows (-1, j): those come from side = dict of numpy obs, act, rew, obs2, done [M, ...]."""
+    is_side, j = idx[:, 0] < 0, idx[:, 1]
+    out = [x.copy() for x in gather(ring, np.where(is_side[:, None], 0, idx))]
+    for i, key in enumerate(("obs", "act", "rew", "obs2", "done")):
+        out[i][is_side] = side[key][j[is_side]].reshape(out[i][is_side].shape)
+    return out
+
+
 def window(k_counter, slots, reserve=0, lag=0, n_step=1):
     """The vector steps a draw may return as base steps, oldest to newest (a range, empty when there is none), when the counter holds
     k_counter: the newest complete step is the one `lag` steps before the counter's; the ring keeps slots - 1 complete steps (the
@@ -155,11 +178,15 @@ class LoopRef:
     counts after its env step, so learn() of step t runs when t + 1 >= 1 + n_step, and draws with the ring counter t + 1 and the
     whole window.  The pipelined order counts the steps opened before the running one, so learn() of step t runs when t >= 1 + n_step,
     and draws with the counter t, lag 1 and reserve 2: from the steps up to t - 2.  Each learning step makes updates_per_step
-    updates, update u with the seed seed + u * SEED_STRIDE."""
+    updates, update u with the seed seed + u * SEED_STRIDE.
 
-    def __init__(self, seed, env_seed, n_envs, slots, batch, pipelined, updates_per_step=1, n_step=1, oracle=None):
+    k0, u0: the loop starts (a loaded checkpoint) with k0 vector steps and u0 learn steps already made; every method takes the
+    ABSOLUTE vector step number t >= k0, and with k0 = u0 = 0 every answer is that of a loop started fresh."""
+
+    def __init__(self, seed, env_seed, n_envs, slots, batch, pipelined, updates_per_step=1, n_step=1, oracle=None, k0=0, u0=0):
         self.seed, self.env_seed, self.n, self.slots, self.batch = int(seed), int(env_seed), n_envs, slots, batch
         self.pipelined, self.updates_per_step, self.n_step = bool(pipelined), int(updates_per_step), int(n_step)
+        self.k0, self.u0 = int(k0), int(u0)
         self.episode = np.zeros(n_envs, np.int64)
         self.oracle = oracle
 
@@ -189,8 +216,10 @@ class LoopRef:
         return counted >= 1 + self.n_step
 
     def updates_after(self, t):
-        """learn() calls made once step t is over."""
-        return self.updates_per_step * sum(1 for s in range(t + 1) if self.learns(s))
+        """learn() calls made once step t is over: u0, and updates_per_step for each of the steps k0 .. t that learn -- those from
+        the first learning step on, 1 + n_step (pipelined) or n_step (serial)."""
+        first = max(self.k0, 1 + self.n_step if self.pipelined else self.n_step)
+        return self.u0 + self.updates_per_step * max(0, int(t) - first + 1)
 
     def draw_window(self, t):
         """(counter, reserve, lag) of the draws of step t."""

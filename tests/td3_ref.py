@@ -76,7 +76,8 @@ def load_td3_agent(state, hyper, cfg, device, dtype):
         group["lr"], group["betas"], group["eps"], group["weight_decay"] = h["lr"], tuple(h["betas"]), h["eps"], h["weight_decay"]
         step = state["actor_step"] if name == "actor" else state["step"]
         for k, p in net.named_parameters():
-            net.optimizer.state[p] = {"step": torch.tensor(float(step), dtype=torch.float32, device=p.device),
+            exact = torch.float64 if step >= 2 ** 24 and p.device.type == "cpu" else torch.float32      # (learn_ref.load_agent's rule)
+            net.optimizer.state[p] = {"step": torch.tensor(float(step), dtype=exact, device=p.device),
                                       "exp_avg": state["m"][name][k].to(device=device, dtype=dtype).clone(),
                                       "exp_avg_sq": state["v"][name][k].to(device=device, dtype=dtype).clone()}
     return agent

@@ -19,6 +19,9 @@ held to its statement by tests/test_loop_ref_cpu.py) -- not against another path
             n_step = 3 (learn()'s first launch draws); serial TD3 with two updates (the TD3 launches draw).  The pipelined ones end
             with the ring's counter set one step behind the window's by hand (what a captured graph's learn chain may meet): the
             draw must follow the window counter -- in eager steps the two are equal whenever a draw is made.
+  edges     the same checks, 10 steps, on loops started at large counters through an edited state_dict (tests/big_counters.py:
+            start_at): serial and pipelined-2-updates from vector step 2^31 - 5 and 2^32 - 5 with 2^31 - 7
+            learn steps made, serial TD3 from 2^24 - 5 with 2^24 - 6; every ring row but the reset observation a seeded pattern.
 
 Tolerances.  Poses: "2 ulp of f64" is taken at the scale of the box (2 * spacing(max(|lo|, |hi|))): lo + (hi - lo) u as one fma
 differs from the separately rounded form by half an ulp of the product plus half an ulp of the sum, and near x = 0 the product is
@@ -37,9 +40,11 @@ Measured on MI355X (each figure from one run; worst error / bound over the run):
     pipelined, 2 updates    0.0055       0.029       0.38      0.5     -
     pipelined, n_step 3     0.0023       0.029       0.39      0.5     0.11
     serial TD3, 2 updates   0.0038       0.029       0.34      0.5     -
+    the five edge runs      0.0076       0.040       0.38      0.5     -      (the worst of the five; 146 episodes at 8 steps each)
   (the noise figure repeats because the four loops share the seed; test_gpu_td3.py::test_noise measured 0.019 for the same formula.)
   In every configuration 200 episodes ended, at 11 different steps; idx, done, scaled, the untouched ring rows, the counters, the
-  gathered batches and the second loop's learner state were equal bit for bit at every step.  The seven tests take 5 s together."""
+  gathered batches and the second loop's learner state were equal bit for bit at every step.  The seven tests take 5 s together,
+  the five edge configurations 0.1 s each."""
 import math
 
 import numpy as np
@@ -127,6 +132,13 @@ def test_ring_draws_are_the_documented_rows(gpu_device, reserve, lag):
     """n_envs = 200, B = 513, every counter 0 .. 14 given through an explicit k_dev: tt_ring_sample (6 slots), the seed-stride form
     through pack_and_sample(draws=3) (6 slots) and tt_ring_sample_nstep with n = 3 (8 slots: six have no window for n = 3 under a
     reserve of 2): idx is draw(...) / draw_nstep(...) exactly, and the batch is the host's gather of those rows."""
+    worst = check_ring_draws(gpu_device, reserve, lag, range(15))
+    print(f"RATIOS loop draws reserve {reserve} lag {lag}: idx exact, worst |R - R64| / bound {worst:.3g}")
+
+
+def check_ring_draws(gpu_device, reserve, lag, counters):
+    """The body of test_ring_draws_are_the_documented_rows for the given counter values (tests/test_gpu_big_counters.py passes the
+    edges of the counters' narrowings).  Returns the worst |R - R64| / bound of the n-step draws."""
     import torch
     from ddpg_trucktrailer_amd import fused
     from ddpg_trucktrailer_amd.agent import Agent
@@ -136,9 +148,9 @@ def test_ring_draws_are_the_documented_rows(gpu_device, reserve, lag):
     actor = Agent(1e-4, 1e-3, (23,), 1e-3, 1, batch_size=rows, device=dev, replay=False).actor
     kd = torch.zeros((), dtype=torch.int64, device=dev)
     worst = 0.0
-    for k in range(15):
+    for k in counters:
         kd.fill_(k)
-        seed = 2 ** 40 + 7 * k
+        seed = 2 ** 40 + 7 * (k % 1000)
         out = ring.sample_fused(rows, seed=seed, return_index=True, done_as_bool=False, k_dev=kd, reserve=reserve, lag=lag)
         idx = M.draw(seed, k, rows, N, 6, reserve, lag)
         assert np.array_equal(out[5].cpu().numpy(), idx), k
@@ -161,7 +173,7 @@ def test_ring_draws_are_the_documented_rows(gpu_device, reserve, lag):
             err = np.abs(out[2].double().cpu().numpy() - want["R"])
             assert (err <= want["bound"]).all(), k
             worst = max(worst, float((err / np.maximum(want["bound"], 1e-300)).max()))
-    print(f"RATIOS loop draws reserve {reserve} lag {lag}: idx exact, worst |R - R64| / bound {worst:.3g}")
+    return worst
 
 
 # ---- the loop in lock-step --------------------------------------------------------------------------------------------
@@ -200,7 +212,30 @@ def _ring_np(ring):
 
 @pytest.mark.parametrize("order,kw,slots", _configs())
 def test_vector_loop_in_lock_step_with_the_host_model(gpu_device, order, kw, slots):
+    lock_step(gpu_device, order, kw, slots)
+
+
+def _edge_configs():
+    serial, piped, td3 = _configs()[0].values, _configs()[1].values, _configs()[3].values
+    return [pytest.param(*serial, 2 ** 31 - 5, 2 ** 31 - 7, id="serial-2^31"), pytest.param(*piped, 2 ** 31 - 5, 2 ** 31 - 7, id="pipelined-2-updates-2^31"),
+            pytest.param(*serial, 2 ** 32 - 5, 2 ** 31 - 7, id="serial-2^32"), pytest.param(*piped, 2 ** 32 - 5, 2 ** 31 - 7, id="pipelined-2-updates-2^32"),
+            pytest.param(*td3, 2 ** 24 - 5, 2 ** 24 - 6, id="serial-td3-2^24")]
+
+
+@pytest.mark.parametrize("order,kw,slots,k0,u0", _edge_configs())
+def test_vector_loop_in_lock_step_across_a_counter_edge(gpu_device, order, kw, slots, k0, u0):
+    """The lock-step checks a to h as they are, on a loop started (an edited state_dict, tests/big_counters.py: start_at) with k0
+    vector steps and u0 learn steps made, 10 steps: the ring counter crosses 2^31 or 2^32 in the fifth step while the learn step
+    crosses 2^31 (serial: in the seventh step; two updates per step: in the fourth), or, with TD3, the ring counter and the critic
+    step cross 2^24 and the actor step 2^23.  Every ring row but the reset observation is a seeded pattern, so the draws of the
+    first steps -- whose window lies before k0 -- are checked against rows that no step of this loop wrote."""
+    lock_step(gpu_device, order, kw, slots, k0, u0, count=10)
+
+
+def lock_step(gpu_device, order, kw, slots, k0=0, u0=0, count=STEPS):
+    """The body of the lock-step tests: `count` vector steps from vector step k0 with u0 learn steps made (0, 0: a fresh loop)."""
     import torch
+    from big_counters import start_at
     from ddpg_trucktrailer_amd.networks import ActorNetwork
     from ddpg_trucktrailer_amd.td3 import TD3Learner
     from oracle import c_oracle
@@ -214,19 +249,21 @@ def test_vector_loop_in_lock_step_with_the_host_model(gpu_device, order, kw, slo
     gamma = float(loop.agent.gamma)
 
     ora = c_oracle.COracle(N)
-    ref = M.LoopRef(SEED, ENV_SEED, N, slots, B, pipelined, updates, n_step, oracle=ora)
+    ref = M.LoopRef(SEED, ENV_SEED, N, slots, B, pipelined, updates, n_step, oracle=ora, k0=k0, u0=u0)
+    if k0 or u0:
+        loop.load_state_dict(start_at(loop.state_dict(), k0, u0, slots, fill_seed=slots))
     obs0 = ora.place(ref.start_poses())
     for i in LANES:
         ora.set_max_steps(int(i), 3 + int(i) % 11)
     worst = dict(a=0.0, b=0.0, d=0.0, pose=0.0, R=0.0)
     worst["pose"] = _check_poses(env, ref.start_poses(), "reset")
     start_dev = env.episode()["start"].cpu().numpy()
-    assert np.abs(ring.obs[0].cpu().numpy() - obs0).max() <= 1e-5
+    assert np.abs(ring.obs[k0 % slots].cpu().numpy() - obs0).max() <= 1e-5
     actor64 = ActorNetwork(1e-4, (23,), 400, 300, 1, name="actor", device=torch.device("cpu")).double()
     high = np.float32(math.pi / 4)
     episodes, ended_at, restarted_lanes, both_updates = 0, set(), 0, 0
 
-    for t in range(STEPS):
+    for t in range(k0, k0 + count):
         sd = loop.state_dict()                     # (synchronises) weights, moments, counts, ring, noise, env before the step
         before = {k: sd["ring"][k].numpy() for k in ("obs", "act", "rew", "done")}
         x_before = sd["ou"].numpy().astype(np.float64)
@@ -362,7 +399,7 @@ def test_vector_loop_in_lock_step_with_the_host_model(gpu_device, order, kw, slo
             assert any(not torch.equal(p, q) for p, q in zip(_learn_state(loop)[:4], state_before[:4])), (t, "learn() moved no weight")
 
     assert episodes >= 20 and len(ended_at) >= 5 and restarted_lanes >= 5, (episodes, ended_at, restarted_lanes)
-    assert ring.k >= 2 * slots
+    assert ring.k == k0 + count and (k0 > 0 or ring.k >= 2 * slots)
     if updates > 1:
         assert both_updates >= 10, both_updates
     assert fl.tail_gave_up() == 0 and not loop.handover_gave_up
@@ -370,7 +407,7 @@ def test_vector_loop_in_lock_step_with_the_host_model(gpu_device, order, kw, slo
         # The pipelined draw reads the window counter k_pipe_dev, not the ring's k_dev.  In eager steps both hold t when the draw is
         # made, so the steps above cannot tell them apart; in a captured graph learn()'s chain runs ahead and the ring's counter may
         # still lack the env step of t - 1.  That state, made by hand: the rows are still those of the counter t.
-        t = STEPS
+        t = k0 + count
         ring.k_dev.fill_(t - 1)
         if n_step == 1:
             loop._open_step(True)              # the opening launch makes the step's draws
