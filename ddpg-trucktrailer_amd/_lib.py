@@ -146,6 +146,11 @@ class TTDemoLabels(C.Structure):
     _fields_ = [("label", C.c_void_p), ("n_envs", C.c_int32), ("slots", C.c_int32), ("first", C.c_int32), ("count", C.c_int32)]
 
 
+class TTGradClip(C.Structure):
+    """tt_grad_clip (include/ttenv.h): max_norm, partials [GRAD_CLIP_PARTIALS] f64, out [2] f32, counts [2] int64 or NULL."""
+    _fields_ = [("max_norm", C.c_float), ("partials", C.c_void_p), ("out", C.c_void_p), ("counts", C.c_void_p)]
+
+
 class TTMpcArgs(C.Structure):
     """tt_mpc_args (include/ttenv.h: tt_env_mpc_plan)."""
     _fields_ = [("horizon", C.c_int32), ("samples", C.c_int32)] + \
@@ -167,6 +172,7 @@ NSTEP_MAX = 16          # TT_NSTEP_MAX
 TD3_NOISE_TAG = 0x7D3E  # the Philox domain of TD3's target-smoothing noise (csrc/tttd3.h)
 MPC_NOISE_TAG = 0x4D50  # the Philox domain of the MPC expert's exploration noise (csrc/ttenv.hip)
 MPC_MAX_HORIZON, MPC_MAX_SAMPLES = 64, 1024     # TT_MPC_MAX_HORIZON, TT_MPC_MAX_SAMPLES
+GRAD_CLIP_PARTIALS = 64     # TT_GRAD_CLIP_PARTIALS
 
 
 class TTError(RuntimeError):
@@ -310,6 +316,8 @@ _SIGNATURES = {
                                                 C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                                 C.POINTER(TTFc2Images), _P, _P, _P, C.POINTER(TTLossShape), C.POINTER(TTDemoLoss),
                                                 C.c_int32, C.POINTER(TTDemoLabels), _P]),
+    "tt_adam_soft_update_clipped": (C.c_int, [_I, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float,
+                                              C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, C.POINTER(TTGradClip), _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

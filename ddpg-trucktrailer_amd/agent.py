@@ -45,13 +45,19 @@ class Agent():
     def __init__(self, alpha, beta, input_dims, tau, n_actions, gamma=0.99,
                  max_size=1000000, fc1_dims=400, fc2_dims=300,
                  batch_size=64, device=None, chkpt_dir='tmp/ddpg', capturable=False, replay=True, td3=None, loss_shape=None,
-                 demo_loss=None):
+                 demo_loss=None, grad_clip=None):
         """td3: None = DDPG, line for line; a td3.TD3Config = TD3 (Fujimoto et al., 2018): a second critic `critic_2` with its target
         `target_critic_2`, target-policy smoothing, and the actor and all targets updated on every policy_delay-th update only.
         loss_shape: None = the MSE critic loss and the plain actor loss; a loss_shape.LossShape = the Huber critic loss and / or the
         actor's pre-activation penalty c mean(pre^2) in learn_batch.  Not with td3.
         demo_loss: None, or a demo_loss.DemoLoss = a behaviour-cloning term on the rows learn_batch is told are demonstrations
-        (demo_rows=), gated by a Q-filter.  Composes with loss_shape.  Not with td3."""
+        (demo_rows=), gated by a Q-filter.  Composes with loss_shape.  Not with td3.
+        grad_clip: None, or a grad_clip.GradClip = torch.nn.utils.clip_grad_norm_(net.parameters(), max_norm) between the gradient and
+        optimizer.step() at each site that has a value.  Not with td3."""
+        if grad_clip is not None:
+            from ddpg_trucktrailer_amd.grad_clip import check_grad_clip
+            check_grad_clip(grad_clip, td3=td3)
+        self.grad_clip = grad_clip
         if demo_loss is not None:
             from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
             check_demo_loss(demo_loss, td3=td3)
@@ -180,6 +186,9 @@ class Agent():
             p.grad = g                                       # zero_grad(set_to_none=True) + backward()
         if self.grad_sync_critic is not None:
             self.grad_sync_critic()
+        clip = self.grad_clip
+        if clip is not None and clip.critic is not None:
+            T.nn.utils.clip_grad_norm_(self._critic_params, clip.critic)
         self.critic.optimizer.step()
 
         # The actor step differentiates -Q(s, mu(s)) through the ALREADY UPDATED critic.  The reference lets
@@ -213,6 +222,8 @@ class Agent():
             p.grad = g
         if self.grad_sync_actor is not None:
             self.grad_sync_actor()
+        if clip is not None and clip.actor is not None:
+            T.nn.utils.clip_grad_norm_(self._actor_params, clip.actor)
         self.actor.optimizer.step()
 
         self.update_network_parameters()

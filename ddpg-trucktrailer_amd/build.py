@@ -6,7 +6,7 @@ import subprocess
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
-SRC = [os.path.join(HERE, "csrc", f) for f in ("ttenv.hip", "ttnet.hip", "ttnet_split.hip", "ttlearn.hip", "ttp2p.hip", "ttpop.hip", "ttnstep.hip", "ttpop_nstep.hip", "ttlearnlog.hip", "tttd3.hip", "ttpop_td3.hip", "ttshape.hip", "ttdemo.hip")]
+SRC = [os.path.join(HERE, "csrc", f) for f in ("ttenv.hip", "ttnet.hip", "ttnet_split.hip", "ttlearn.hip", "ttp2p.hip", "ttpop.hip", "ttnstep.hip", "ttpop_nstep.hip", "ttlearnlog.hip", "tttd3.hip", "ttpop_td3.hip", "ttshape.hip", "ttdemo.hip", "ttclip.hip")]
 HDR = [os.path.join(ROOT, "include", "ttenv.h"), os.path.join(HERE, "csrc", "ttnet_common.h"), os.path.join(HERE, "csrc", "ttnet_pack.h"), os.path.join(HERE, "csrc", "ttp2p.h"), os.path.join(HERE, "csrc", "ttstamps.h"), os.path.join(HERE, "csrc", "ttlearn_bodies.h"), os.path.join(HERE, "csrc", "ttlearn_sites.h"), os.path.join(HERE, "csrc", "ttlearn_host.h"), os.path.join(HERE, "csrc", "ttnstep.h"), os.path.join(HERE, "csrc", "ttpop.h"), os.path.join(HERE, "csrc", "ttpop_exploit.h"), os.path.join(HERE, "csrc", "tthost.h"), os.path.join(HERE, "csrc", "ttphilox.h"), os.path.join(HERE, "csrc", "tttd3.h")]
 LIB = os.path.join(HERE, "libttenv.so")
 

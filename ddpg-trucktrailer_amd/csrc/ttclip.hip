@@ -1,0 +1,156 @@
+// ttclip.hip -- gradient-norm clipping of the lone learn(): torch.nn.utils.clip_grad_norm_ in front of optimizer.step(), as the
+// optimizer launch of one network (MI355X, gfx950; include/ttenv.h: tt_grad_clip).
+//
+//   k_grad_sqnorm        the sum of squares of a network's gradient tensors, in f64 (the square of an f32 is exact there): the
+//                        concatenated index space in CLIP_WGS equal runs, one per workgroup; a thread adds its elements in a fixed
+//                        order, the workgroup its 256 threads by a fixed tree through LDS, and stores ONE partial, partials[w].
+//                        No atomics, no wait between workgroups: the same inputs give the same bits, eager or replayed.
+//   k_adam_soft_clip     k_adam_soft (csrc/ttlearn.hip): its grid, its table, its arithmetic -- on coef * grad.  Every workgroup adds
+//                        the partials in index order (the same bits in each), norm = sqrt(sum), coef = max_norm / (norm + 1e-6)
+//                        where that is below 1, else 1.  With coef = 1 the product is exact and the launch leaves k_adam_soft's bits.
+//
+// The gradient buffers are read only: they keep the unclipped gradient (the learn log's norms are theirs).  A non-finite norm gets
+// no special case (clip_grad_norm_'s error_if_nonfinite=False): coef is then 0 (norm = inf) or NaN, and so is what it multiplies.
+#include "ttlearn_host.h"
+
+namespace {
+
+constexpr int CLIP_WGS = TT_GRAD_CLIP_PARTIALS;
+
+// the elements [lo, hi) of one tensor, by the whole workgroup: scalar loads up to the first 16-byte boundary, 16 B per lane from
+// there, scalar loads for the rest -- nothing outside [lo, hi) is read.  Thread t's order: head element t, vectors t, t + 256, ..
+// (x, y, z, w each), tail element t.
+__device__ __forceinline__ double sq_run(const float *__restrict__ g, const int lo, const int hi, double acc) {
+    const int t = threadIdx.x;
+    const int to_boundary = (int)(((16u - (unsigned)(reinterpret_cast<uintptr_t>(g + lo) & 15u)) & 15u) >> 2);
+    const int head = min(to_boundary, hi - lo);
+    const int nvec = (hi - lo - head) >> 2;
+    const int tail0 = lo + head + 4 * nvec;
+    if (t < head) {
+        const double x = (double)g[lo + t];
+        acc += x * x;
+    }
+    const float4 *__restrict__ v = reinterpret_cast<const float4 *>(g + lo + head);
+    for (int j = t; j < nvec; j += 256) {
+        const float4 q = v[j];
+        const double x = (double)q.x, y = (double)q.y, z = (double)q.z, w = (double)q.w;
+        acc += x * x;
+        acc += y * y;
+        acc += z * z;
+        acc += w * w;
+    }
+    if (t < hi - tail0) {
+        const double x = (double)g[tail0 + t];
+        acc += x * x;
+    }
+    return acc;
+}
+
+// workgroup w: the elements [w * chunk, (w + 1) * chunk) of the tensors laid end to end (chunk: the host's ceil(total / CLIP_WGS))
+__global__ __launch_bounds__(256) void k_grad_sqnorm(const AdamTable T, const long long chunk, double *__restrict__ partials) {
+    __shared__ double red[256];
+    const long long begin = (long long)blockIdx.x * chunk, end = begin + chunk;
+    double acc = 0.0;
+    long long off = 0;
+    for (int ti = 0; ti < T.count; ++ti) {
+        const long long n = T.numel[ti];
+        const long long lo = max(begin - off, 0LL), hi = min(end - off, n);
+        if (lo < hi) acc = sq_run(T.g[ti], (int)lo, (int)hi, acc);
+        off += n;
+    }
+    red[threadIdx.x] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if ((int)threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
+}
+
+// k_adam_soft with the clip coefficient on the gradient (the arithmetic below `g` is k_adam_soft's, line for line)
+__global__ __launch_bounds__(256) void k_adam_soft_clip(const AdamTable T, const long long *__restrict__ step_dev, const float lr,
+                                                        const float beta1, const float beta2, const float eps,
+                                                        const float weight_decay, const float tau,
+                                                        const float *__restrict__ bias_corr, const float max_norm,
+                                                        const double *__restrict__ partials, float *__restrict__ out,
+                                                        long long *__restrict__ counts) {
+    double sum = 0.0;
+    for (int w = 0; w < CLIP_WGS; ++w) sum += partials[w];      // index order, in every workgroup: the same bits
+    const double norm = sqrt(sum);
+    float coef = (float)((double)max_norm / (norm + 1e-6));
+    coef = coef > 1.f ? 1.f : coef;                             // (not fminf: a NaN stays a NaN)
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        out[0] = (float)norm;
+        out[1] = coef;
+        if (counts) {
+            counts[0] += 1;
+            counts[1] += coef < 1.f ? 1 : 0;
+        }
+    }
+    int ti = 0;
+    while (ti + 1 < T.count && (int)blockIdx.x >= T.block_start[ti + 1]) ++ti;
+    const int i = ((int)blockIdx.x - T.block_start[ti]) * 256 + threadIdx.x;
+    if (i >= T.numel[ti]) return;
+    float bcc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
+    if (bias_corr) {
+#pragma unroll
+        for (int q = 0; q < 5; ++q) bcc[q] = bias_corr[q];
+    }
+    float bc1, bc2;
+    adam_bias_corrections(beta1, beta2, *step_dev, bias_corr != nullptr, bcc, bc1, bc2);
+    float p = T.p[ti][i];
+    const float g = fmaf(weight_decay, p, __fmul_rn(coef, T.g[ti][i]));      // the product rounded on its own
+    const float m = fmaf(beta1, T.m[ti][i], (1.f - beta1) * g);          // exp_avg.lerp_(grad, 1 - beta1)
+    const float v = fmaf(beta2, T.v[ti][i], (1.f - beta2) * g * g);
+    T.m[ti][i] = m;
+    T.v[ti][i] = v;
+    const float denom = sqrtf(v) / sqrtf(bc2) + eps;
+    p -= (lr / bc1) * (m / denom);
+    T.p[ti][i] = p;
+    float tg = 0.f;
+    if (T.tgt[ti]) {
+        tg = T.tgt[ti][i];
+        tg = fmaf(tau, p - tg, tg);
+        T.tgt[ti][i] = tg;
+    }
+    if (ti == 4 && (T.img_p || T.img_t)) {
+        const int nn = i / H1, k = i - nn * H1;
+        if (T.img_p) img_store(T.img_p, nn, k, p, true);
+        if (T.img_t && T.tgt[ti]) img_store(T.img_t, nn, k, tg, false);
+    }
+}
+
+}  // namespace
+
+extern "C" {
+
+int tt_adam_soft_update_clipped(int count, float *const *params, const float *const *grads, float *const *exp_avg,
+                                float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const int64_t *step_dev,
+                                float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                                const tt_fc2_images *images, const float *bias_corr, const tt_grad_clip *clip, tt_stream_t stream) {
+    const char *const who = "tt_adam_soft_update_clipped";
+    if (!clip) return fail(TT_EINVAL, "%s: clip is NULL", who);
+    if (!clip->partials || !clip->out) return fail(TT_EINVAL, "%s: clip->partials or clip->out is NULL", who);
+    if (!std::isfinite(clip->max_norm) || !(clip->max_norm > 0.f))
+        return fail(TT_EINVAL, "%s: clip->max_norm = %g is not a finite number > 0", who, (double)clip->max_norm);
+    if (count < 1 || count > MAXT) return fail(TT_EINVAL, "%s: count = %d tensors, not in [1, %d]", who, count, MAXT);
+    if (!params || !grads || !exp_avg || !exp_avg_sq || !numel || !step_dev)
+        return fail(TT_EINVAL, "%s: params, grads, exp_avg, exp_avg_sq, numel or step_dev is NULL", who);
+    long long total = 0;
+    for (int i = 0; i < count; ++i) {
+        if (numel[i] < 0) return fail(TT_EINVAL, "%s: numel[%d] = %d is negative", who, i, (int)numel[i]);
+        total += numel[i];
+    }
+    AdamTable T{};
+    const int blocks = fill_adam_table(T, 256, count, params, grads, exp_avg, exp_avg_sq, targets, numel, images);
+    if (blocks <= 0)
+        return fail(TT_EINVAL, "%s: a tensor is missing or empty, or the fc2 images do not go with the tensor list", who);
+    const long long chunk = (total + CLIP_WGS - 1) / CLIP_WGS;
+    hipLaunchKernelGGL(k_grad_sqnorm, dim3(CLIP_WGS), dim3(256), 0, stream, T, chunk, clip->partials);
+    hipLaunchKernelGGL(k_adam_soft_clip, dim3(blocks), dim3(256), 0, stream, T, reinterpret_cast<const long long *>(step_dev), lr, beta1,
+                       beta2, eps, weight_decay, tau, bias_corr, clip->max_norm, static_cast<const double *>(clip->partials), clip->out,
+                       reinterpret_cast<long long *>(clip->counts));
+    return launched(who);
+}
+
+}  // extern "C"

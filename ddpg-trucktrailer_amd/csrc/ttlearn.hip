@@ -388,31 +388,6 @@ int tt_mlp_actor_tail(int n, const float *obs, const float *mu, const tt_mlp_wei
     return launched(who);
 }
 
-// The table of both optimizer launches: the tensors, the fc2 images and each tensor's first workgroup at `per_block` elements per
-// workgroup.  grads NULL: the peer-to-peer step, whose gradients come from the exchange.  Returns the launch's workgroups, or -1
-// for a missing tensor or images that do not go with the list.
-static int fill_adam_table(AdamTable &T, int per_block, int count, float *const *params, const float *const *grads,
-                           float *const *exp_avg, float *const *exp_avg_sq, float *const *targets, const int32_t *numel,
-                           const tt_fc2_images *images) {
-    if (images && (images->net || images->target)) {       // tensors must then be in tt_mlp_weights order: w2 is number 4
-        if (count < 5 || numel[4] != H2 * H1) return -1;
-        T.img_p = reinterpret_cast<_Float16 *>(images->net);
-        T.img_t = reinterpret_cast<_Float16 *>(images->target);
-    }
-    T.count = count;
-    int blocks = 0;
-    for (int i = 0; i < count; ++i) {
-        if (!params[i] || (grads && !grads[i]) || !exp_avg[i] || !exp_avg_sq[i] || numel[i] <= 0) return -1;
-        T.p[i] = params[i]; T.g[i] = grads ? grads[i] : nullptr; T.m[i] = exp_avg[i]; T.v[i] = exp_avg_sq[i];
-        T.tgt[i] = targets ? targets[i] : nullptr;
-        T.numel[i] = numel[i];
-        T.block_start[i] = blocks;
-        blocks += (numel[i] + per_block - 1) / per_block;
-    }
-    T.block_start[count] = blocks;
-    return blocks;
-}
-
 int tt_adam_soft_update(int count, float *const *params, const float *const *grads, float *const *exp_avg,
                         float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const int64_t *step_dev,
                         float lr, float beta1, float beta2, float eps, float weight_decay, float tau,

@@ -1,5 +1,6 @@
 // ttlearn_host.h -- the host side that the lone learn()'s launches share across their options (csrc/ttlearn.hip the plain ones,
-// csrc/ttshape.hip with a tt_loss_shape, csrc/ttdemo.hip with a tt_demo_loss): one checked conversion per launch, from the C arguments
+// csrc/ttshape.hip with a tt_loss_shape, csrc/ttdemo.hip with a tt_demo_loss, csrc/ttclip.hip the optimizer step with a tt_grad_clip): one
+// checked conversion per launch (and the table of the optimizer launches of their own, fill_adam_table), from the C arguments
 // (include/ttenv.h) to the structs the kernels take.  Each returns TT_OK, or TT_EINVAL with the message "<who>: <reason>", `who` the
 // entry point called; that is then its option's own refusals, the conversion, its own launch.  Host only.
 #pragma once
@@ -120,6 +121,30 @@ int to_actor_tail(const char *who, int n, const float *obs, const float *mu, con
     T.ts = TailSync{tail_words, reinterpret_cast<unsigned long long *>(tail_words + 64), nb, gave_up_host};
     T.grid = dim3(nb + WG_ACTOR_WEIGHTS);
     return TT_OK;
+}
+
+// The table of the optimizer launches of their own (k_adam_soft, k_adam_soft_p2p, k_adam_soft_clip): the tensors, the fc2 images and
+// each tensor's first workgroup at `per_block` elements per workgroup.  grads NULL: the peer-to-peer step, whose gradients come from
+// the exchange.  Returns the launch's workgroups, or -1 for a missing or empty tensor or images that do not go with the list.
+int fill_adam_table(AdamTable &T, int per_block, int count, float *const *params, const float *const *grads, float *const *exp_avg,
+                    float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const tt_fc2_images *images) {
+    if (images && (images->net || images->target)) {       // tensors must then be in tt_mlp_weights order: w2 is number 4
+        if (count < 5 || numel[4] != H2 * H1) return -1;
+        T.img_p = reinterpret_cast<_Float16 *>(images->net);
+        T.img_t = reinterpret_cast<_Float16 *>(images->target);
+    }
+    T.count = count;
+    int blocks = 0;
+    for (int i = 0; i < count; ++i) {
+        if (!params[i] || (grads && !grads[i]) || !exp_avg[i] || !exp_avg_sq[i] || numel[i] <= 0) return -1;
+        T.p[i] = params[i]; T.g[i] = grads ? grads[i] : nullptr; T.m[i] = exp_avg[i]; T.v[i] = exp_avg_sq[i];
+        T.tgt[i] = targets ? targets[i] : nullptr;
+        T.numel[i] = numel[i];
+        T.block_start[i] = blocks;
+        blocks += (numel[i] + per_block - 1) / per_block;
+    }
+    T.block_start[count] = blocks;
+    return blocks;
 }
 
 }  // namespace

@@ -186,7 +186,10 @@ class LearnLog:
 
 
 class FusedLearner:
-    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None, expert_lanes=None, labels=None):
+    grad_clip, _clip = None, {}        # (without a clip: set_grad_clip gives an instance its own)
+
+    def __init__(self, agent, batch_size, fc2_images=None, loss_shape=None, demo_loss=None, expert_lanes=None, labels=None,
+                 grad_clip=None):
         """fc2_images (None = on unless TT_LEARN_F32=1): the 400 x 300 products of learn() on the f16 MFMA from pre-split
         images of the four networks' fc2 (include/ttenv.h: tt_mlp_weights.fc2_img) that the optimizer launches keep current;
         off = every product on the exact-f32 MFMA straight from the weights.
@@ -202,7 +205,11 @@ class FusedLearner:
         labels (with demo_loss; None = the entry points above): (first, count) -- the ring rows of lanes [first, first + count) are
         LABELLED rows (the loop's mpc.ExpertLabels): their cloning target is the ring's label array, handed
         over as a third entry or with set_label_array() before the first update, the filter does not apply to them and the actor's step goes through
-        the _labels entry points.  first >= expert_lanes (None counts as 0)."""
+        the _labels entry points.  first >= expert_lanes (None counts as 0).
+        grad_clip (None = every launch the one it was): a grad_clip.GradClip -- learn_batch then runs the separate-optimizer order
+        inside itself (weight gradients with no optimizer step, then the optimizer launch, at both sites; fuse_tail does not apply), and
+        a network with a max_norm takes its step through tt_adam_soft_update_clipped (include/ttenv.h: tt_grad_clip; DESIGN.md section
+        34).  Not with data-parallel ranks, demo_loss, expert_lanes or labels."""
         import os
         if expert_lanes is not None and not (isinstance(expert_lanes, int) and not isinstance(expert_lanes, bool) and expert_lanes >= 0):
             raise ValueError(f"expert_lanes = {expert_lanes!r} is not None or a whole number >= 0")
@@ -268,6 +275,8 @@ class FusedLearner:
             self.set_label_array(label_array)
         if demo_loss is not None:
             self.set_demo_loss(demo_loss)
+        if grad_clip is not None:
+            self.set_grad_clip(grad_clip)
 
     def set_loss_shape(self, loss_shape):
         """Turn a LossShape on (before anything is captured: the constants travel by value in the launches' arguments).  The learner
@@ -281,7 +290,7 @@ class FusedLearner:
                                     pre=self.pre.data_ptr())
 
     def _refuse_ranks_with_loss_shape(self):
-        for name in ("loss_shape", "demo_loss"):
+        for name in ("loss_shape", "demo_loss", "grad_clip"):
             if getattr(self, name) is not None:
                 refuse(name, data_parallel=True)
 
@@ -295,6 +304,38 @@ class FusedLearner:
         self.demo_loss = demo_loss
         self.dq_eff = torch.zeros(self.B, dtype=torch.float32, device=self.dev)
         self.code = torch.zeros(self.B, dtype=torch.int32, device=self.dev)
+
+    def set_grad_clip(self, grad_clip):
+        """Turn a GradClip on (before anything is captured: max_norm travels by value, the buffers by address).  Per clipped network
+        the learner owns the norm's partial sums (f64), out = (norm, coef) of the last update and counts = (updates, clipped updates)."""
+        from ddpg_trucktrailer_amd.grad_clip import check_grad_clip
+        check_grad_clip(grad_clip, td3=getattr(self.agent, "td3", None),
+                        data_parallel=self.grad_sync_critic is not None or self.p2p is not None, demo_loss=self.demo_loss,
+                        expert=self.expert_lanes, labels=self.labels)
+        self.grad_clip, self._clip = grad_clip, {}
+        for name in ("critic", "actor"):
+            max_norm = getattr(grad_clip, name)
+            if max_norm is None:
+                continue
+            partials = torch.zeros(L.GRAD_CLIP_PARTIALS, dtype=torch.float64, device=self.dev)
+            out = torch.zeros(2, dtype=torch.float32, device=self.dev)
+            counts = torch.zeros(2, dtype=torch.int64, device=self.dev)
+            struct = L.TTGradClip(max_norm=max_norm, partials=partials.data_ptr(), out=out.data_ptr(), counts=counts.data_ptr())
+            self._clip[name] = dict(partials=partials, out=out, counts=counts, struct=struct)
+
+    def clip_stats(self):
+        """Per clipped network {"norm", "coef"} of its last update -- the norm of the unclipped gradient and the coefficient applied to
+        it -- and {"updates", "clipped"}, its updates so far and those with coef < 1 (counted from this learner's creation: a checkpoint
+        does not carry them).  Synchronises."""
+        if self.grad_clip is None:
+            raise ValueError("grad_clip is off (FusedLearner(grad_clip=...))")
+        if self.dev.type == "cuda":
+            torch.cuda.synchronize(self.dev)
+        stats = {}
+        for name, c in self._clip.items():
+            (norm, coef), (updates, clipped) = c["out"].tolist(), c["counts"].tolist()
+            stats[name] = {"norm": norm, "coef": coef, "updates": updates, "clipped": clipped}
+        return stats
 
     def _demo_struct(self, actions, demo_index):
         """tt_demo_loss of one update: the batch's stored actions, the draw's index buffer, q of the first launch."""
@@ -433,8 +474,13 @@ class FusedLearner:
                                                          L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau, st.images_ref(),
                                                          L.ptr(self.bias_corr), self._stream()), self.p2p)
             return
-        L.check(self.lib.tt_adam_soft_update(st.count, st.a_p, st.a_g, st.a_m, st.a_v, st.a_t, st.a_n, L.ptr(self.step_dev),
-                                             lr, b1, b2, eps, wd, tau, st.images_ref(), L.ptr(self.bias_corr), self._stream()))
+        args = (st.count, st.a_p, st.a_g, st.a_m, st.a_v, st.a_t, st.a_n, L.ptr(self.step_dev), lr, b1, b2, eps, wd, tau, st.images_ref(),
+                L.ptr(self.bias_corr))
+        clip = self._clip.get("critic" if st.critic else "actor")
+        if clip is not None:           # the norm's launch, then the optimizer step on coef * grad (csrc/ttclip.hip)
+            L.check(self.lib.tt_adam_soft_update_clipped(*args, C.byref(clip["struct"]), self._stream()))
+        else:
+            L.check(self.lib.tt_adam_soft_update(*args, self._stream()))
 
     def enable_data_parallel(self, group=None):
         """Mean of the flat gradient buffers over the ranks at the reference's two optimizer sites (RCCL: one AVG
@@ -706,29 +752,32 @@ class FusedLearner:
         if dp:
             self._refuse_ranks_with_learn_log()
             self._refuse_ranks_with_loss_shape()
+        separate = dp or self.grad_clip is not None      # a clip needs the whole gradient before the optimizer: the ranks' order, no collective
         assert image is None or sample is not None
-        self.phase_a(states, actions, rewards, states_, done_u8, fuse_adam=not dp, window_dev=window_dev, sample=sample, image=image, n_step=n_step)
+        self.phase_a(states, actions, rewards, states_, done_u8, fuse_adam=not separate, window_dev=window_dev, sample=sample, image=image,
+                     n_step=n_step)
         if dp:
             self.grad_sync_critic()
-        self.phase_b(states, separate_adam=dp, demo=demo)
+        self.phase_b(states, separate_adam=separate, demo=demo)
         if dp:
             self.grad_sync_actor()
+        if separate:
             self.phase_c()
         if self.learn_log is not None:
             self.learn_log.append()
 
     # ---- checkpoint ---------------------------------------------------------------------------------------------
     def state_dict(self):
-        """Adam moments of both networks (flat, tt_mlp_weights order), the learn-step count and the loss shape when one is set.
-        and the demonstration loss likewise.  (The learn log is not in it.)"""
+        """Adam moments of both networks (flat, tt_mlp_weights order), the learn-step count and the loss shape when one is set,
+        the demonstration loss and the gradient clip likewise.  (The learn log is not in it.)"""
         sd = {"step": int(self.step_dev.item()),
               "actor": {"m": self.actor.m.cpu(), "v": self.actor.v.cpu()},
               "critic": {"m": self.critic.m.cpu(), "v": self.critic.v.cpu()}}
-        write_options(sd, loss_shape=self.loss_shape, demo_loss=self.demo_loss)
+        write_options(sd, loss_shape=self.loss_shape, demo_loss=self.demo_loss, grad_clip=self.grad_clip)
         return sd
 
     def load_state_dict(self, sd):
-        compare_options(sd, "learner", loss_shape=self.loss_shape, demo_loss=self.demo_loss)
+        compare_options(sd, "learner", loss_shape=self.loss_shape, demo_loss=self.demo_loss, grad_clip=self.grad_clip)
         for name in ("actor", "critic"):
             st = getattr(self, name)
             st.m.copy_(sd[name]["m"]); st.v.copy_(sd[name]["v"])

@@ -1,5 +1,5 @@
 """What the loops' options share: the base of the option values (td3.TD3Config, loss_shape.LossShape,
-demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels) with the validators their constructors use, the one table of
+demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip) with the validators their constructors use, the one table of
 "not supported with" refusals behind the check_* functions, and the options' entries of a checkpoint.
 
     Option                        a value named by its FIELDS: repr, ==, hash, as_tuple(), from_tuple(); a nested Option nests
@@ -67,7 +67,7 @@ def whole_number(what, x, lo, hi=None, bound=None):
 # ---- the refusal table.  A row: (the context field it reads, when it refuses, the message); the context is a dict of DEFAULTS,
 # what the caller knows, and "value", the option itself.  A message is a template over the option's words, or a function of the context.
 # Beyond DEFAULTS an option's own rows read what its check_* passes: labels "first" (the expert lanes before the labelled ones);
-# td3 "updates_per_step" and "delay"; population_td3 those two and "n_steps", "n_step_max", "device".
+# grad_clip "demo_loss", "expert" and "labels" (each None or the loop's option); td3 "updates_per_step" and "delay"; population_td3 those two and "n_steps", "n_step_max", "device".
 UNSET = object()
 DEFAULTS = dict(td3=None, population=False, data_parallel=False, force_dp=False, n_step=1, ring_mode=None, n_envs=None, pipeline=None,
                 learn_log=None, demo_loss=UNSET)
@@ -109,6 +109,14 @@ TABLE = {
                          "ring_mode", "population", "data_parallel", "force_dp",
                          ("demo_loss", lambda c: c["demo_loss"] is None, "expert labels without demo_loss: no learner would read the "
                                                                          "labels (DDPGRollout(demo_loss=DemoLoss(...)))"))),
+    "grad_clip": dict(what="grad_clip", be="is", form="clipped", population="the population's launches have no clipped optimizer step",
+                      rows=("td3", "population", "data_parallel", "force_dp",
+                            ("demo_loss", lambda c: c["demo_loss"] is not None,
+                             "grad_clip with demo_loss is not supported (the demonstration entry points have no clipped optimizer step)"),
+                            ("expert", lambda c: c["expert"] is not None,
+                             "grad_clip with expert lanes is not supported (they train through the demonstration entry points)"),
+                            ("labels", lambda c: c["labels"] is not None,
+                             "grad_clip with expert labels is not supported (they train through the demonstration entry points)"))),
     "td3": dict(rows=(_TD3_MULTIPLE, ("n_step", lambda c: int(c["n_step"]) > 1, lambda c: f"td3: n_step = {c['n_step']} > 1 is not supported"),
                       ("data_parallel", lambda c: c["data_parallel"], "td3: data_parallel ranks (and the p2p exchange) are not supported"),
                       ("pipeline", lambda c: c["pipeline"], "td3: pipeline=True is not supported (TD3 runs in the serial order)"),
@@ -135,7 +143,7 @@ def refuse(option, value=None, **context):
 
 
 # ---- the options' entries of a checkpoint: each present option's as_tuple() as a list, under its key
-CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels")
+CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip")
 
 
 def write_options(sd, **options):

@@ -34,6 +34,7 @@ import torch
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner, LearnLog, check_learn_log, nstep_discount
+from ddpg_trucktrailer_amd.grad_clip import check_grad_clip
 from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
 from ddpg_trucktrailer_amd.mpc import check_expert_lanes
 from ddpg_trucktrailer_amd.options import write_options
@@ -44,9 +45,9 @@ from ddpg_trucktrailer_amd.stepper import VectorStepper
 
 def _refuse_lone_options(loss_shape, demo_loss, expert, agents=()):
     """A population has no loss shape, demonstration loss or expert lanes (the options' own checks, with population=True): neither
-    as an option nor, of the first two, on an agent it is given."""
+    as an option nor, of the first two, on an agent it is given; nor an agent that carries a gradient clip (Agent(grad_clip=))."""
     for name, check, value in (("loss_shape", check_loss_shape, loss_shape), ("demo_loss", check_demo_loss, demo_loss),
-                               ("expert", check_expert_lanes, expert)):
+                               ("expert", check_expert_lanes, expert), ("grad_clip", check_grad_clip, None)):
         for v in [value] + [getattr(ag, name, None) for ag in agents if name != "expert"]:
             if v is not None:
                 check(v, population=True)

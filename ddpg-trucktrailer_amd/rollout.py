@@ -39,6 +39,7 @@ import torch
 
 from ddpg_trucktrailer_amd import fused
 from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
+from ddpg_trucktrailer_amd.grad_clip import check_grad_clip
 from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
 from ddpg_trucktrailer_amd.mpc import check_expert_labels, check_expert_lanes
 from ddpg_trucktrailer_amd.options import compare_options, write_options
@@ -71,7 +72,7 @@ def _gc_off():
             gc.enable()
 
 
-_AGENT_OPTIONS = ("demo_loss", "loss_shape", "td3")        # what an agent passed in was itself built with: Agent(demo_loss=, ...)
+_AGENT_OPTIONS = ("demo_loss", "loss_shape", "grad_clip", "td3")        # what an agent passed in was itself built with: Agent(demo_loss=, ...)
 
 
 def _same_as_agent(name, agent, value):
@@ -93,7 +94,7 @@ class DDPGRollout(VectorStepper):
                  fc1_dims=400, fc2_dims=300, world_size=1, use_graph=True, agent=None, fused_learn=True, graph_steps=4,
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, labels=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, labels=None, grad_clip=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -138,25 +139,32 @@ class DDPGRollout(VectorStepper):
         labels: None, or an mpc.ExpertLabels (needs demo_loss): the lanes behind the expert's, [M, M + L), are
         driven by the policy as every lane is -- their trajectories do not change by a bit -- and the expert's decision on each
         of their states goes to the ring's label array, in the expert lanes' launch.  The demonstration term clones the label on
-        the ring rows of those lanes (code 3 in demo_stats: "labelled"), unfiltered.  mpc.check_expert_labels names what is refused."""
+        the ring rows of those lanes (code 3 in demo_stats: "labelled"), unfiltered.  mpc.check_expert_labels names what is refused.
+        grad_clip: None, or a grad_clip.GradClip: clip_grad_norm_ in front of the critic's and / or the actor's
+        optimizer step.  The fused learner then runs the separate-optimizer order inside learn() (nine launches per update against
+        four or five) -- in the serial and the pipelined order, eager and in graphs, with n_step, loss_shape and the learn log.
+        grad_clip.check_grad_clip names what is refused (td3, data-parallel ranks, the p2p exchange, TT_FORCE_DP, demo_loss, expert
+        lanes, expert labels)."""
         from ddpg_trucktrailer_amd.td3 import check_td3          # (here: td3.py imports this module)
         ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
         force_dp = os.environ.get("TT_FORCE_DP") == "1"
         c = dict(labels=labels, expert=expert, n_step=n_step, demo_loss=demo_loss, loss_shape=loss_shape, td3=td3, n_envs=env.n_envs,
                  data_parallel=ranks or dp_exchange == "p2p", force_dp=force_dp, updates_per_step=updates_per_step, pipeline=pipeline,
-                 learn_log=learn_log)
+                 learn_log=learn_log, grad_clip=grad_clip)
         # the options in the order their refusals fire: (name, its check, the resolved values the check takes); the first bad one raises
         for name, check, takes in (("labels", check_expert_labels, ("expert", "n_envs", "data_parallel", "force_dp", "demo_loss")),
                                    ("expert", check_expert_lanes, ("n_envs", "data_parallel", "force_dp")),
                                    ("n_step", check_n_step, ()),
                                    ("demo_loss", check_demo_loss, ("td3", "data_parallel", "force_dp", "n_step")),
                                    ("loss_shape", check_loss_shape, ("td3", "data_parallel", "force_dp")),
+                                   ("grad_clip", check_grad_clip, ("td3", "data_parallel", "force_dp", "demo_loss", "expert", "labels")),
                                    ("td3", check_td3, ("updates_per_step", "n_step", "data_parallel", "pipeline", "learn_log"))):
             if c[name] is not None or name == "n_step":       # (n_step is no optional value)
                 c[name] = check(c[name], **{k: c[k] for k in takes})
             if name in _AGENT_OPTIONS:
                 _same_as_agent(name, agent, c[name])
         self.n_step, self.demo_loss, self.loss_shape, self.td3 = c["n_step"], c["demo_loss"], c["loss_shape"], c["td3"]
+        self.grad_clip = c["grad_clip"]
         if self.td3 is not None:
             pipeline = False
         if learn_log is not None:
@@ -177,6 +185,7 @@ class DDPGRollout(VectorStepper):
         self.batch_size = batch_size
         self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
         self.agent.demo_loss = self.demo_loss
+        self.agent.grad_clip = self.grad_clip
         self.ring.n_step = self.n_step                     # (load_side refuses tuples an n-step draw cannot use)
         self.dp_exchange = dp_exchange or os.environ.get("TT_DP_EXCHANGE", "collective")
         assert self.dp_exchange in ("collective", "p2p"), self.dp_exchange
@@ -198,7 +207,7 @@ class DDPGRollout(VectorStepper):
                 from ddpg_trucktrailer_amd.td3 import TD3Learner
                 self.learner = TD3Learner(self.agent, batch_size, self.ring, self.seed)
             elif self.td3 is None:
-                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape, demo_loss=self.demo_loss,
+                self.learner = FusedLearner(self.agent, batch_size, loss_shape=self.loss_shape, demo_loss=self.demo_loss, grad_clip=self.grad_clip,
                                             expert_lanes=self.expert.lanes if self.expert is not None and self.demo_loss is not None else None,
                                             labels=(self.label_first, self.labels.lanes, self.ring.label) if self.labels is not None else None)
             self.agent.fused_learner = self.learner
@@ -714,7 +723,7 @@ class DDPGRollout(VectorStepper):
                 sd["optim"]["critic_2"] = ag.critic_2.optimizer.state_dict()
                 sd["td3_updates"] = int(ag.td3_updates)
                 sd["td3_noise"] = ag.td3_noise_state()               # (the torch path's generator; the fused path's noise is counter-based)
-        return write_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss)      # (expert, labels: the stepper's)
+        return write_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, grad_clip=self.grad_clip)      # (expert, labels: the stepper's)
 
     def demo_stats(self):
         """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}; with expert lanes the ring rows of those
@@ -736,7 +745,7 @@ class DDPGRollout(VectorStepper):
         if int(sd.get("n_step", 1)) != self.n_step:
             raise ValueError(f"the checkpoint was written with n_step = {int(sd.get('n_step', 1))}, this loop has n_step = {self.n_step}")
         compare_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, expert=self.expert,
-                        labels=self.labels)                           # (before anything is written)
+                        labels=self.labels, grad_clip=self.grad_clip)                           # (before anything is written)
         self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])

@@ -1082,6 +1082,38 @@ int tt_mlp_actor_tail_demo_labels(int n, const float *obs, const float *mu, cons
                                   const tt_demo_loss *demo, int32_t expert_lanes, const tt_demo_labels *labels /* may be NULL */,
                                   tt_stream_t stream);
 
+/* ------------------------------------------------------------------------------------------------------
+ * Gradient-norm clipping of the lone learn() (csrc/ttclip.hip): torch.nn.utils.clip_grad_norm_(parameters,
+ * max_norm) in front of optimizer.step(), as the optimizer launch of one network.  Clipping by the GLOBAL norm depends on every
+ * element of the network's gradient, so it cannot ride in the weight-gradient launch (tt_mlp_backward_weights with count = 0 leaves
+ * the gradients in memory); tt_adam_soft_update_clipped is tt_adam_soft_update with two launches on `stream`:
+ *   1. the sum of squares of the `count` gradient tensors in f64 (the square of an f32 is exact there), over a fixed partition of
+ *      the tensors laid end to end into TT_GRAD_CLIP_PARTIALS workgroups, each in a fixed order, each storing one partial into
+ *      clip->partials[w] -- no atomics, no wait between workgroups: the same inputs give the same bits, eager or replayed.  Ragged
+ *      numel are served by 16-byte loads between scalar heads and tails; nothing outside the tensors is read.
+ *   2. tt_adam_soft_update's launch, in which every workgroup adds the partials in index order in f64 (the same bits in each) and
+ *          norm = sqrt(sum)        coef = (float)(max_norm / (norm + 1e-6)), 1 where that is greater than 1
+ *      (clip_grad_norm_'s formula), and the gradient that enters Adam is g = fmaf(weight_decay, p, coef * grad) with the product
+ *      rounded on its own; moments, bias corrections, parameter, soft target update and fc2 images as tt_adam_soft_update.  With
+ *      coef == 1 the product is exact and the launch leaves tt_adam_soft_update's bits.
+ * out[0] = (float)norm, out[1] = coef.  counts (may be NULL): counts[0] += 1, counts[1] += (coef < 1), by plain loads and stores of
+ * one thread -- one launch at a time may touch them.  The gradient buffers are NOT rewritten: they keep the unclipped gradient (so
+ * the learn log's norms, tt_learn_log_*, stay those of the unclipped gradient).  A non-finite norm gets no special case (torch's
+ * error_if_nonfinite=False): norm = inf gives coef = 0, a NaN stays a NaN in coef and in everything it multiplies.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL clip, partials or out; max_norm not finite or
+ * not > 0; count outside 1..12; a NULL array or tensor; a negative (or, as tt_adam_soft_update, zero) numel. */
+#define TT_GRAD_CLIP_PARTIALS 64
+typedef struct tt_grad_clip {
+    float max_norm;      /* finite, > 0 */
+    double *partials;    /* [TT_GRAD_CLIP_PARTIALS] workspace the caller owns, one per clipped network */
+    float *out;          /* [2]: the norm, the coefficient */
+    int64_t *counts;     /* [2] or NULL: updates, updates with coef < 1 */
+} tt_grad_clip;
+int tt_adam_soft_update_clipped(int count, float *const *params, const float *const *grads, float *const *exp_avg,
+                                float *const *exp_avg_sq, float *const *targets, const int32_t *numel, const int64_t *step_dev,
+                                float lr, float beta1, float beta2, float eps, float weight_decay, float tau,
+                                const tt_fc2_images *images, const float *bias_corr, const tt_grad_clip *clip, tt_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -28,12 +28,15 @@ expert's are driven by the POLICY, and the expert's decision on each of their st
 follows the label on their ring rows, unfiltered.  Takes the expert's --expert-horizon, --expert-samples and --expert-seed (with
 --expert-lanes both use the same: one launch plans for both).  Each line then shows demonstration / labelled / applied rows of the block's
 last update, and the successes split into the policy's lanes and the others.
+--grad-clip C[,A]: gradient-norm clipping (DDPGRollout(grad_clip=GradClip(C, A))): clip_grad_norm_ with max_norm C
+in front of the critic's optimizer step and, when given, A in front of the actor's ("-" for C: the actor alone).  Each line adds
+"clipped x of y critic / actor updates", the block's share from FusedLearner.clip_stats().  Not with --td3, --bc-weight or the expert options.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
 Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
        [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M] [--label-lanes L] [--expert-horizon H] [--expert-samples S]
-       [--expert-seed K]
+       [--expert-seed K] [--grad-clip C[,A]]
        [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -109,6 +112,12 @@ if "--eval-lanes" in sys.argv[1:]:
     at = sys.argv.index("--eval-lanes")
     eval_lanes = int(sys.argv[at + 1])
     del sys.argv[at:at + 2]
+grad_clip = None
+if "--grad-clip" in sys.argv[1:]:
+    from ddpg_trucktrailer_amd.grad_clip import GradClip
+    at = sys.argv.index("--grad-clip")
+    grad_clip = GradClip(*[None if x in ("", "-") else float(x) for x in sys.argv[at + 1].split(",")])
+    del sys.argv[at:at + 2]
 loss_shape = None
 if huber is not None or pre_penalty:
     from ddpg_trucktrailer_amd.loss_shape import LossShape
@@ -143,14 +152,15 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    episode_log=min(n * every, 1 << 24), episode_log_detail=detail, n_step=n_step,
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
-                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert, labels=labels)
+                   learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert, labels=labels,
+                   grad_clip=grad_clip)
 if demos is not None:
     from ddpg_trucktrailer_amd.expert import load_transitions_npz
     d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
     loop.ring.load_side(d_obs, d_act[:, 0], d_rew, d_obs2, d_done)
 print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn() per vector step = {n / upd:.1f} env-steps per update, "
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else "") +
-      (f", {loss_shape}" if loss_shape is not None else "") +
+      (f", {loss_shape}" if loss_shape is not None else "") + (f", {grad_clip}" if grad_clip is not None else "") +
       (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else "") +
       (f", {expert}" if expert is not None else "") + (f", {labels}" if labels is not None else ""), flush=True)
 
@@ -163,6 +173,19 @@ def learn_line(rec):
     return (f"  update {int(rec['step'][-1])}: critic loss {rec['critic_loss'][-1]:.4g}  actor loss {rec['actor_loss'][-1]:.4g}  "
             f"Q mean {rec['q_mean'][-1]:.4g}  |TD| mean {rec['td_abs_mean'][-1]:.4g}  |grad| critic {rec['grad_norm_critic'][-1]:.4g} "
             f"actor {rec['grad_norm_actor'][-1]:.4g}  non-finite {bad}" + (f"  ({rec['dropped']} records overwritten)" if rec["dropped"] else ""))
+
+
+clip_seen = {}
+
+
+def clip_line(stats):
+    """The block's clipped share per clipped network, from the learner's running counts."""
+    parts = []
+    for key, st in stats.items():
+        updates0, clipped0 = clip_seen.get(key, (0, 0))
+        parts.append(f"{st['clipped'] - clipped0} of {st['updates'] - updates0} {key}")
+        clip_seen[key] = (st["updates"], st["clipped"])
+    return "  clipped " + " / ".join(parts) + " updates"
 
 
 def demo_line(st):
@@ -213,6 +236,7 @@ while s < total:
           f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
           f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}"
           f"{demo_line(loop.demo_stats()) if demo_loss is not None else ''}"
+          f"{clip_line(loop.learner.clip_stats()) if grad_clip is not None else ''}"
           f"{lanes_line(r, expert.lanes if expert is not None else 0, labels.lanes if labels is not None else 0) if expert is not None or labels is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
