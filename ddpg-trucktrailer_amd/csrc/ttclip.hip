@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void k_grad_sqnorm(const AdamTable T, const lo
     if (threadIdx.x == 0) partials[blockIdx.x] = red[0];
 }
 
-// k_adam_soft with the clip coefficient on the gradient (the arithmetic below `g` is k_adam_soft's, line for line)
+// k_adam_soft with the clip coefficient on the gradient (the element update is k_adam_soft's text: TT_ADAM_SOFT_ELEMENT)
 __global__ __launch_bounds__(256) void k_adam_soft_clip(const AdamTable T, const long long *__restrict__ step_dev, const float lr,
                                                         const float beta1, const float beta2, const float eps,
                                                         const float weight_decay, const float tau,
@@ -87,37 +87,7 @@ __global__ __launch_bounds__(256) void k_adam_soft_clip(const AdamTable T, const
             counts[1] += coef < 1.f ? 1 : 0;
         }
     }
-    int ti = 0;
-    while (ti + 1 < T.count && (int)blockIdx.x >= T.block_start[ti + 1]) ++ti;
-    const int i = ((int)blockIdx.x - T.block_start[ti]) * 256 + threadIdx.x;
-    if (i >= T.numel[ti]) return;
-    float bcc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};
-    if (bias_corr) {
-#pragma unroll
-        for (int q = 0; q < 5; ++q) bcc[q] = bias_corr[q];
-    }
-    float bc1, bc2;
-    adam_bias_corrections(beta1, beta2, *step_dev, bias_corr != nullptr, bcc, bc1, bc2);
-    float p = T.p[ti][i];
-    const float g = fmaf(weight_decay, p, __fmul_rn(coef, T.g[ti][i]));      // the product rounded on its own
-    const float m = fmaf(beta1, T.m[ti][i], (1.f - beta1) * g);          // exp_avg.lerp_(grad, 1 - beta1)
-    const float v = fmaf(beta2, T.v[ti][i], (1.f - beta2) * g * g);
-    T.m[ti][i] = m;
-    T.v[ti][i] = v;
-    const float denom = sqrtf(v) / sqrtf(bc2) + eps;
-    p -= (lr / bc1) * (m / denom);
-    T.p[ti][i] = p;
-    float tg = 0.f;
-    if (T.tgt[ti]) {
-        tg = T.tgt[ti][i];
-        tg = fmaf(tau, p - tg, tg);
-        T.tgt[ti][i] = tg;
-    }
-    if (ti == 4 && (T.img_p || T.img_t)) {
-        const int nn = i / H1, k = i - nn * H1;
-        if (T.img_p) img_store(T.img_p, nn, k, p, true);
-        if (T.img_t && T.tgt[ti]) img_store(T.img_t, nn, k, tg, false);
-    }
+    TT_ADAM_SOFT_ELEMENT(__fmul_rn(coef, T.g[ti][i]))      // the product rounded on its own
 }
 
 }  // namespace

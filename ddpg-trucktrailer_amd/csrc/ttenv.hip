@@ -700,7 +700,7 @@ __device__ __forceinline__ unsigned long long atomic_add_agent(unsigned long lon
 // outcome that has a finisher in the wave.  Called by every active lane of the wave (the ballots need them all) when the wave
 // has finishers (fin = __ballot(done) != 0); returns the wave's base slot.
 // The record's end_step is the launch number, read in log_write and at the workgroup's exit: both before the workgroup's exit
-// ticket (below, k_step_log), so before the last workgroup of the launch advances it.
+// ticket (below, TT_STEP_LAUNCH_COUNT), so before the last workgroup of the launch advances it.
 __device__ __forceinline__ unsigned long long log_reserve(const EpLog &lg, unsigned long long fin, bool done, uint32_t flags,
                                                           bool succ) {
     const bool lead = __lane_id() == 0;
@@ -747,6 +747,85 @@ __device__ __forceinline__ void log_append(const EpLog &lg, int i, bool done, ui
     }
 }
 
+// ---- the text that k_step, k_step_log and k_step_tally hold word for word, written ONCE ----
+// Function-like MACROS, not functions, for the reason csrc/ttlearn_sites.h gives: with k_step's body in a common inlined function
+// the register allocation of 8 of its 16 variants changed; as pasted text every variant of the three kernels keeps its .text byte
+// for byte (python -m ddpg_trucktrailer_amd.kernel_resources --text before.so after.so: the gate of every change here that is not
+// meant to change a kernel).  The pieces use the kernels' argument names (P, n, b, action, action_out, obs, reward, done, info,
+// seed, policy_seed, cursor, lg) and the template arguments as they stand; what a piece declares it declares in the scope it is
+// pasted into, and the ORDER of the declarations is each kernel's own.  What differs stays written out at the sites: the LDS tile's
+// declaration, k_step's TT_STAMPS and TT_DBG_STEP_MEM_ONLY blocks (no #ifdef inside a macro), the load of the running return in
+// front of the sched_barrier, step_env, k_step_tally's read of the start pose, and log_append / tally_append.
+//
+// Head: ring addressing, the lane's index, the count of vector steps.  Declares block_first, i, valid, nv, of.
+#define TT_STEP_HEAD()                                                                                                                  \
+    if (cursor) { /* tt_env_step_ring: obs / reward / done are the ring's bases, the slots come from the cursor */                      \
+        obs += (size_t)cursor[1] * n * OBS;                                                                                             \
+        reward += (size_t)cursor[0] * n;                                                                                                \
+        done += (size_t)cursor[0] * n;                                                                                                  \
+    }                                                                                                                                   \
+    const int block_first = blockIdx.x * BLOCK;                                                                                         \
+    const int i = block_first + threadIdx.x;                                                                                            \
+    const bool valid = i < n;                                                                                                           \
+    const int nv = min(BLOCK, n - block_first);                                                                                         \
+    float of[OBS];                                                                                                                      \
+                                                                                                                                        \
+    if (b.counter && i == 0) *b.counter += 1 /* one more vector step stored (read by later launches only) */
+// Loads, in front of the site's __builtin_amdgcn_sched_barrier(0).  A lone wave per SIMD hides no latency: every load of the step is
+// requested THERE, in one burst (one trip to L2 / the Infinity Cache instead of the four or five the scheduler otherwise spreads
+// through the arithmetic by sinking each load next to its first use).  Declares e and a.
+#define TT_STEP_LOADS()                                                                                                                 \
+    Env e;                                                                                                                              \
+    load_env<PER_ENV>(P, b, i, e);                                                                                                      \
+    float a = 0.f;                                                                                                                      \
+    if (!RANDOM_POLICY) a = action[i]
+// Act, behind the sched_barrier: the in-kernel random action
+#define TT_STEP_ACT()                                                                                                                   \
+    if (RANDOM_POLICY) {                                                                                                                \
+        a = random_action(policy_seed, (uint32_t)i, pk_steps(e.pk), b.episodes[i]);                                                     \
+        if (action_out) action_out[i] = a;                                                                                              \
+    }
+// Out: reward, done and the info rows of StepOut o
+#define TT_STEP_OUT()                                                                                                                   \
+    if (P.nt) {                                                                                                                         \
+        __builtin_nontemporal_store((float)o.total, reward + i);                                                                        \
+        __builtin_nontemporal_store((uint8_t)(o.done ? 1 : 0), done + i);                                                               \
+    } else {                                                                                                                            \
+        reward[i] = (float)o.total;                                                                                                     \
+        done[i] = o.done ? 1 : 0;                                                                                                       \
+    }                                                                                                                                   \
+    if (INFO) write_info(info, (size_t)n, i, e, o)
+// Reset: a finished lane's next episode, and the env's rows
+#define TT_STEP_RESET()                                                                                                                 \
+    if (AUTO_RESET && o.done) {                                                                                                         \
+        const uint32_t ep = b.episodes[i] + 1u;                                                                                         \
+        b.episodes[i] = ep;                                                                                                             \
+        double sx, sy, syaw;                                                                                                            \
+        random_pose(P, seed, (uint32_t)i, ep, sx, sy, syaw);                                                                            \
+        const Goal g0{P.gx, P.gy, P.sg, P.cg};                                                                                          \
+        place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);                                                                      \
+    }                                                                                                                                   \
+    store_env(b, i, e)
+// Return (the two log kernels): the lane's running return `ret`, summed in step order.  Declares len (the record is written after
+// the reset: fewer registers live across it).
+#define TT_STEP_RETURN()                                                                                                                \
+    ret += o.total;                                                                                                                     \
+    lg.acc[i] = o.done ? 0.0 : ret; /* a finished lane's next episode (auto-reset or not) starts from 0 */                              \
+    const uint32_t len = pk_steps(e.pk)
+// Launch count (the two log kernels), after store_obs_tile: behind its barrier every wave of this workgroup has read the count (its
+// records hold it), so the workgroup's exit ticket follows its reads, and the workgroup that draws the last ticket follows every
+// workgroup's.  Nothing waits and nothing is published to other workgroups of this launch, so the atomics are relaxed (an acq_rel
+// ticket wrote back and invalidated the L2 in every workgroup: 10 -> 78 us per launch at N = 65536).
+#define TT_STEP_LAUNCH_COUNT()                                                                                                          \
+    if (threadIdx.x == 0) {                                                                                                             \
+        const unsigned long long launch = __hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);          \
+        const unsigned long long t = atomic_add_agent(lg.hdr + LG_TICKET, 1ull);                                                        \
+        if (t == gridDim.x - 1u) { /* the last workgroup of the launch; the next launch reads the count */                              \
+            __hip_atomic_store(lg.hdr + LG_TICKET, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                                   \
+            __hip_atomic_store(lg.hdr + LG_LAUNCHES, launch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                        \
+        }                                                                                                                               \
+    }
+
 template <bool PER_ENV, bool INFO, bool AUTO_RESET, bool RANDOM_POLICY>
 __global__ __launch_bounds__(BLOCK) void k_step(const KParams P, const int n, const Bufs b,
                                                 const float *__restrict__ action, float *__restrict__ action_out,
@@ -757,31 +836,11 @@ __global__ __launch_bounds__(BLOCK) void k_step(const KParams P, const int n, co
 #ifdef TT_STAMPS      // diagnostic build: wall clock (100 MHz) at the begin and end of every workgroup (tools/step_timeline.py)
     if (threadIdx.x == 0 && blockIdx.x < 1024) g_stepblk[blockIdx.x][0] = wall_clock64();
 #endif
-    if (cursor) {       // ring addressing (tt_env_step_ring): obs / reward / done are the ring's bases, the slots come from the cursor
-        obs += (size_t)cursor[1] * n * OBS;
-        reward += (size_t)cursor[0] * n;
-        done += (size_t)cursor[0] * n;
-    }
-    const int block_first = blockIdx.x * BLOCK;
-    const int i = block_first + threadIdx.x;
-    const bool valid = i < n;
-    const int nv = min(BLOCK, n - block_first);
-    float of[OBS];
-
-    if (b.counter && i == 0) *b.counter += 1;      // one more vector step stored (read by later launches only)
+    TT_STEP_HEAD();
     if (valid) {
-        Env e;
-        load_env<PER_ENV>(P, b, i, e);
-        float a = 0.f;
-        if (!RANDOM_POLICY) a = action[i];
-        // A lone wave per SIMD hides no latency: every load of the step is requested HERE, in one burst (one trip to
-        // L2 / the Infinity Cache instead of the four or five the scheduler otherwise spreads through the arithmetic by
-        // sinking each load next to its first use)
+        TT_STEP_LOADS();
         __builtin_amdgcn_sched_barrier(0);
-        if (RANDOM_POLICY) {
-            a = random_action(policy_seed, (uint32_t)i, pk_steps(e.pk), b.episodes[i]);
-            if (action_out) action_out[i] = a;
-        }
+        TT_STEP_ACT();
         StepOut o;
 #ifdef TT_DBG_STEP_MEM_ONLY      // diagnostic build (wrong results): the step's memory traffic without its arithmetic
         o = StepOut{};
@@ -792,23 +851,8 @@ __global__ __launch_bounds__(BLOCK) void k_step(const KParams P, const int n, co
 #else
         step_env(P, e, a, of, o);
 #endif
-        if (P.nt) {
-            __builtin_nontemporal_store((float)o.total, reward + i);
-            __builtin_nontemporal_store((uint8_t)(o.done ? 1 : 0), done + i);
-        } else {
-            reward[i] = (float)o.total;
-            done[i] = o.done ? 1 : 0;
-        }
-        if (INFO) write_info(info, (size_t)n, i, e, o);
-        if (AUTO_RESET && o.done) {
-            const uint32_t ep = b.episodes[i] + 1u;
-            b.episodes[i] = ep;
-            double sx, sy, syaw;
-            random_pose(P, seed, (uint32_t)i, ep, sx, sy, syaw);
-            const Goal g0{P.gx, P.gy, P.sg, P.cg};
-            place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);
-        }
-        store_env(b, i, e);
+        TT_STEP_OUT();
+        TT_STEP_RESET();
     }
     store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
 #ifdef TT_STAMPS
@@ -821,12 +865,11 @@ __global__ __launch_bounds__(BLOCK) void k_step(const KParams P, const int n, co
 #endif
 }
 
-
-// k_step with the episode log on: the same step (the same inlined load_env / step_env / place_env / store_env /
-// store_obs_tile), plus the lane's running return -- loaded in the step's load burst, summed in step order --, the append of the
-// finishers' records and the launch count.  A kernel of its own, not a fifth template argument of k_step (that would rename
-// every k_step variant), and not a body shared with k_step either: moving k_step's body into a common inlined function
-// changed the register allocation of 8 of its 16 variants (DESIGN.md "Episode log").
+// k_step with the episode log on: the same step -- k_step's text, the TT_STEP_* pieces above --, plus the lane's running return
+// (loaded in the step's load burst, TT_STEP_RETURN), the append of the finishers' records and the launch count
+// (TT_STEP_LAUNCH_COUNT).  A kernel of its own, not a fifth template argument of k_step (that would rename every k_step variant);
+// and the shared text is pasted, not called: a common inlined body changed the register allocation of 8 of k_step's 16 variants
+// (DESIGN.md "Episode log", section 35).
 template <bool PER_ENV, bool INFO, bool AUTO_RESET, bool RANDOM_POLICY>
 __global__ __launch_bounds__(BLOCK) void k_step_log(const KParams P, const int n, const Bufs b,
                                                     const float *__restrict__ action, float *__restrict__ action_out,
@@ -835,66 +878,21 @@ __global__ __launch_bounds__(BLOCK) void k_step_log(const KParams P, const int n
                                                     const uint64_t policy_seed, const int *__restrict__ cursor,
                                                     const EpLog lg) {
     __shared__ __attribute__((aligned(16))) float tile[BLOCK * OBS];
-    if (cursor) {
-        obs += (size_t)cursor[1] * n * OBS;
-        reward += (size_t)cursor[0] * n;
-        done += (size_t)cursor[0] * n;
-    }
-    const int block_first = blockIdx.x * BLOCK;
-    const int i = block_first + threadIdx.x;
-    const bool valid = i < n;
-    const int nv = min(BLOCK, n - block_first);
-    float of[OBS];
-
-    if (b.counter && i == 0) *b.counter += 1;
+    TT_STEP_HEAD();
     if (valid) {
-        Env e;
-        load_env<PER_ENV>(P, b, i, e);
-        float a = 0.f;
-        if (!RANDOM_POLICY) a = action[i];
+        TT_STEP_LOADS();
         double ret = lg.acc[i];
-        __builtin_amdgcn_sched_barrier(0);     // every load of the step in one burst (k_step)
-        if (RANDOM_POLICY) {
-            a = random_action(policy_seed, (uint32_t)i, pk_steps(e.pk), b.episodes[i]);
-            if (action_out) action_out[i] = a;
-        }
+        __builtin_amdgcn_sched_barrier(0);
+        TT_STEP_ACT();
         StepOut o;
         step_env(P, e, a, of, o);
-        if (P.nt) {
-            __builtin_nontemporal_store((float)o.total, reward + i);
-            __builtin_nontemporal_store((uint8_t)(o.done ? 1 : 0), done + i);
-        } else {
-            reward[i] = (float)o.total;
-            done[i] = o.done ? 1 : 0;
-        }
-        if (INFO) write_info(info, (size_t)n, i, e, o);
-        ret += o.total;
-        lg.acc[i] = o.done ? 0.0 : ret;        // a finished lane's next episode (auto-reset or not) starts from 0
-        const uint32_t len = pk_steps(e.pk);   // (the record is written after the reset: fewer registers live across it)
-        if (AUTO_RESET && o.done) {
-            const uint32_t ep = b.episodes[i] + 1u;
-            b.episodes[i] = ep;
-            double sx, sy, syaw;
-            random_pose(P, seed, (uint32_t)i, ep, sx, sy, syaw);
-            const Goal g0{P.gx, P.gy, P.sg, P.cg};
-            place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);
-        }
-        store_env(b, i, e);
+        TT_STEP_OUT();
+        TT_STEP_RETURN();
+        TT_STEP_RESET();
         log_append(lg, i, o.done, o.flags, o.final_bonus > 0.0, len, ret);
     }
     store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
-    // Launch count: after store_obs_tile's barrier every wave of this workgroup has read the count (its records hold it), so
-    // the workgroup's exit ticket follows its reads, and the workgroup that draws the last ticket follows every workgroup's.
-    // Nothing waits and nothing is published to other workgroups of this launch, so the atomics are relaxed (an acq_rel
-    // ticket wrote back and invalidated the L2 in every workgroup: 10 -> 78 us per launch at N = 65536).
-    if (threadIdx.x == 0) {
-        const unsigned long long launch = __hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t = atomic_add_agent(lg.hdr + LG_TICKET, 1ull);
-        if (t == gridDim.x - 1u) {    // the last workgroup of the launch; the next launch reads the count
-            __hip_atomic_store(lg.hdr + LG_TICKET, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(lg.hdr + LG_LAUNCHES, launch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    TT_STEP_LAUNCH_COUNT();
 }
 
 // The detailed log's part of a step (k_step_tally), called by every active lane after the reset and store_env, as log_append is:
@@ -941,9 +939,9 @@ __device__ __forceinline__ void tally_append(const KParams &P, const EpLog &lg, 
     }
 }
 
-// k_step_log with the detailed log on: the same step and the same return, launch count and exit ticket, with tally_append in
-// place of log_append.  Its own kernel for the reason k_step_log is: k_step and k_step_log keep
-// their code and their register allocation (DESIGN.md "Episode log").
+// k_step_log with the detailed log on: the same TT_STEP_* pieces in the same order -- the step, the return, the launch count and
+// its exit ticket --, with the read of the start pose in front of the reset and tally_append in place of log_append.  Its own
+// kernel for the reason k_step_log is: k_step and k_step_log keep their names, their code and their register allocation.
 template <bool PER_ENV, bool INFO, bool AUTO_RESET, bool RANDOM_POLICY>
 __global__ __launch_bounds__(BLOCK) void k_step_tally(const KParams P, const int n, const Bufs b,
                                                       const float *__restrict__ action, float *__restrict__ action_out,
@@ -952,68 +950,27 @@ __global__ __launch_bounds__(BLOCK) void k_step_tally(const KParams P, const int
                                                       const uint64_t policy_seed, const int *__restrict__ cursor,
                                                       const EpLog lg) {
     __shared__ __attribute__((aligned(16))) float tile[BLOCK * OBS];
-    if (cursor) {
-        obs += (size_t)cursor[1] * n * OBS;
-        reward += (size_t)cursor[0] * n;
-        done += (size_t)cursor[0] * n;
-    }
-    const int block_first = blockIdx.x * BLOCK;
-    const int i = block_first + threadIdx.x;
-    const bool valid = i < n;
-    const int nv = min(BLOCK, n - block_first);
-    float of[OBS];
-
-    if (b.counter && i == 0) *b.counter += 1;
+    TT_STEP_HEAD();
     if (valid) {
-        Env e;
-        load_env<PER_ENV>(P, b, i, e);
-        float a = 0.f;
-        if (!RANDOM_POLICY) a = action[i];
+        TT_STEP_LOADS();
         double ret = lg.acc[i];
-        __builtin_amdgcn_sched_barrier(0);     // every load of the step in one burst (k_step)
-        if (RANDOM_POLICY) {
-            a = random_action(policy_seed, (uint32_t)i, pk_steps(e.pk), b.episodes[i]);
-            if (action_out) action_out[i] = a;
-        }
+        __builtin_amdgcn_sched_barrier(0);
+        TT_STEP_ACT();
         StepOut o;
         step_env(P, e, a, of, o);
-        if (P.nt) {
-            __builtin_nontemporal_store((float)o.total, reward + i);
-            __builtin_nontemporal_store((uint8_t)(o.done ? 1 : 0), done + i);
-        } else {
-            reward[i] = (float)o.total;
-            done[i] = o.done ? 1 : 0;
-        }
-        if (INFO) write_info(info, (size_t)n, i, e, o);
-        ret += o.total;
-        lg.acc[i] = o.done ? 0.0 : ret;
-        const uint32_t len = pk_steps(e.pk);
+        TT_STEP_OUT();
+        TT_STEP_RETURN();
         double s0 = 0.0, s1 = 0.0, s2 = 0.0;
         if (o.done) {           // the finished episode's start pose, before the reset places the next one (k_get_episode's rows)
             const double *cold = b.cold + i;
             const size_t S = (size_t)P.npad;
             s0 = cold[C_SX * S]; s1 = cold[C_SY * S]; s2 = cold[C_SYAW * S];
         }
-        if (AUTO_RESET && o.done) {
-            const uint32_t ep = b.episodes[i] + 1u;
-            b.episodes[i] = ep;
-            double sx, sy, syaw;
-            random_pose(P, seed, (uint32_t)i, ep, sx, sy, syaw);
-            const Goal g0{P.gx, P.gy, P.sg, P.cg};
-            place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);
-        }
-        store_env(b, i, e);
+        TT_STEP_RESET();
         tally_append(P, lg, i, o, len, ret, s0, s1, s2);
     }
     store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
-    if (threadIdx.x == 0) {     // the launch count (k_step_log)
-        const unsigned long long launch = __hip_atomic_load(lg.hdr + LG_LAUNCHES, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        const unsigned long long t = atomic_add_agent(lg.hdr + LG_TICKET, 1ull);
-        if (t == gridDim.x - 1u) {
-            __hip_atomic_store(lg.hdr + LG_TICKET, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(lg.hdr + LG_LAUNCHES, launch + 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
+    TT_STEP_LAUNCH_COUNT();
 }
 
 // K vector steps in ONE launch with the random policy: the env stays in registers, only the last

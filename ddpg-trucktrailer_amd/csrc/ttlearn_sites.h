@@ -1,6 +1,7 @@
 // ttlearn_sites.h -- device text that several of learn()'s kernels hold word for word, written ONCE: the sampled-row prologue of the
-// first launch (one-step and n-step), the two halves of the actor tail and the front of the rows-pair launch.  The kernels that use
-// it are in csrc/ttlearn.hip, ttpop.hip, ttnstep.hip, ttpop_nstep.hip, tttd3.hip, ttpop_td3.hip, ttshape.hip and ttdemo.hip.
+// first launch (one-step and n-step), the two halves of the actor tail, the front of the rows-pair launch and the element update of
+// the optimizer launches.  The kernels that use it are in csrc/ttlearn.hip, ttpop.hip, ttnstep.hip, ttpop_nstep.hip, tttd3.hip,
+// ttpop_td3.hip, ttshape.hip, ttdemo.hip and ttclip.hip.
 //
 // These are function-like MACROS, not functions, on purpose.  As __forceinline__ functions (the job indices by value or by
 // reference alike) the prologue and the tail changed the instructions of the kernels they served: csrc/ttpop.hip came out different
@@ -15,7 +16,8 @@
 //
 // Rules of the text: an argument is an expression of the SITE and is pasted as written (`blockIdx.x` stays unsigned, `J.R` stays a
 // kernel argument, `R` a local copy); outputs are variables the site has declared and names declared here live in the macro's own
-// block -- except in TT_SAMPLED_ROWS_NSTEP, which tells why.  What differs between sites stays at the site: finding the agent and the job, the seed of the launch's draw,
+// block -- except in TT_SAMPLED_ROWS_NSTEP, which tells why, and in TT_BWD_ROWS_PAIR_FRONT and TT_ADAM_SOFT_ELEMENT, which are the
+// opening text of their kernels.  What differs between sites stays at the site: finding the agent and the job, the seed of the launch's draw,
 // await_progress and the snapshots of the step numbers, KBEGIN / KEND, the load of the epoch.
 #pragma once
 
@@ -145,4 +147,41 @@
                                ((int)blockIdx.x - 2 * nb - 1) * (64 * NW) + (int)threadIdx.x);                                          \
         ttnet::publish_image((img).cur, IMAGE_WGS);                                                                                     \
         return;                                                                                                                         \
+    }
+
+// ---- one element of the optimizer launches of their own: k_adam_soft (csrc/ttlearn.hip) and k_adam_soft_clip (csrc/ttclip.hip) ----
+// torch.optim.Adam (amsgrad off, weight decay added to the gradient) on element i of the tensor the workgroup belongs to, the soft
+// target update and the fc2 image stores; the threads past the tensor's end RETURN from the kernel here.  GRAD: the element's
+// gradient, an expression in ti and i (declared here) -- what the two kernels differ in.  The rest are the kernels' argument names.
+#define TT_ADAM_SOFT_ELEMENT(GRAD)                                                                                                      \
+    int ti = 0;                                                                                                                         \
+    while (ti + 1 < T.count && (int)blockIdx.x >= T.block_start[ti + 1]) ++ti;                                                          \
+    const int i = ((int)blockIdx.x - T.block_start[ti]) * 256 + threadIdx.x;                                                            \
+    if (i >= T.numel[ti]) return;                                                                                                       \
+    float bcc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};                                                                                           \
+    if (bias_corr) {                                                                                                                    \
+        _Pragma("unroll")                                                                                                               \
+        for (int q = 0; q < 5; ++q) bcc[q] = bias_corr[q];                                                                              \
+    }                                                                                                                                   \
+    float bc1, bc2;                                                                                                                     \
+    adam_bias_corrections(beta1, beta2, *step_dev, bias_corr != nullptr, bcc, bc1, bc2);                                                \
+    float p = T.p[ti][i];                                                                                                               \
+    const float g = fmaf(weight_decay, p, GRAD);                                                                                        \
+    const float m = fmaf(beta1, T.m[ti][i], (1.f - beta1) * g); /* exp_avg.lerp_(grad, 1 - beta1) */                                    \
+    const float v = fmaf(beta2, T.v[ti][i], (1.f - beta2) * g * g);                                                                     \
+    T.m[ti][i] = m;                                                                                                                     \
+    T.v[ti][i] = v;                                                                                                                     \
+    const float denom = sqrtf(v) / sqrtf(bc2) + eps;                                                                                    \
+    p -= (lr / bc1) * (m / denom);                                                                                                      \
+    T.p[ti][i] = p;                                                                                                                     \
+    float tg = 0.f;                                                                                                                     \
+    if (T.tgt[ti]) {                                                                                                                    \
+        tg = T.tgt[ti][i];                                                                                                              \
+        tg = fmaf(tau, p - tg, tg);                                                                                                     \
+        T.tgt[ti][i] = tg;                                                                                                              \
+    }                                                                                                                                   \
+    if (ti == 4 && (T.img_p || T.img_t)) {                                                                                              \
+        const int nn = i / H1, k = i - nn * H1;                                                                                         \
+        if (T.img_p) img_store(T.img_p, nn, k, p, true);                                                                                \
+        if (T.img_t && T.tgt[ti]) img_store(T.img_t, nn, k, tg, false);                                                                 \
     }

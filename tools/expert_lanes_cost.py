@@ -14,103 +14,31 @@ leg.  The new launch's own average time comes from a kernel trace of one leg, in
 Usage: expert_lanes_cost.py [--legs 3] [--steps 400] [--warmup 60] [--lanes 64] [--horizon 64] [--samples 256] [--bc-weight 1.0]
                             [--parent-tree DIR] [--out FILE]
        expert_lanes_cost.py --leg off|expert|expert+bc [--tree DIR] ...   (one leg in this process; prints "LEG <ms per vector step>")"""
-import argparse
-import os
-import statistics
-import subprocess
-import sys
-import time
-
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N, UPD, B, SLOTS, GRAPH_STEPS = 4096, 64, 256, 64, 4
-
-
-def one_leg(a):
-    sys.path.insert(0, os.path.abspath(a.tree) if a.tree else HERE)
-    import torch
-    from ddpg_trucktrailer_amd.rollout import DDPGRollout
-    from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
-    kw = {}
-    if a.leg != "off":
-        from ddpg_trucktrailer_amd.mpc import ExpertLanes, MPCConfig
-        kw["expert"] = ExpertLanes(a.lanes, MPCConfig(horizon=a.horizon, samples=a.samples), seed=27)
-    if a.leg == "expert+bc":
-        from ddpg_trucktrailer_amd.demo_loss import DemoLoss
-        kw["demo_loss"] = DemoLoss(a.bc_weight)
-    env = TruckTrailerVecEnv(N)
-    env.reset(seed=27)
-    loop = DDPGRollout(env, batch_size=B, replay_slots=SLOTS, seed=27, updates_per_step=UPD, graph_steps=GRAPH_STEPS, **kw)
-    loop.run(a.warmup)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop.run(a.steps)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / a.steps
-    assert loop.graph_steps == GRAPH_STEPS and loop.handover_gave_up == [] and loop.learner.tail_gave_up() == 0
-    assert all(torch.isfinite(p).all() for p in loop.agent.actor.parameters())
-    print(f"pipeline={loop.pipeline} fuse_tail={loop.learner.fuse_tail} updates={int(loop.learner.step_dev.item())}" +
-          (f" demo_stats={loop.demo_stats()}" if a.leg == "expert+bc" else ""))
-    print(f"LEG {ms:.5f}")
-
-
-def run_leg(a, variant):
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "off" if variant == "parent" else variant, "--steps", str(a.steps),
-           "--warmup", str(a.warmup), "--lanes", str(a.lanes), "--horizon", str(a.horizon), "--samples", str(a.samples),
-           "--bc-weight", str(a.bc_weight)]
-    if variant == "parent":
-        cmd += ["--tree", a.parent_tree]
-    out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300).stdout
-    return float([ln for ln in out.splitlines() if ln.startswith("LEG ")][-1].split()[1])
+import option_cost
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--warmup", type=int, default=60)
-    ap.add_argument("--lanes", type=int, default=64)
-    ap.add_argument("--horizon", type=int, default=64)
-    ap.add_argument("--samples", type=int, default=256)
-    ap.add_argument("--bc-weight", type=float, default=1.0)
-    ap.add_argument("--parent-tree", default=None)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", choices=("off", "expert", "expert+bc"), default=None)
-    ap.add_argument("--tree", default=None)
-    a = ap.parse_args()
+    a = option_cost.parse([("--lanes", dict(type=int, default=64)), ("--horizon", dict(type=int, default=64)),
+                           ("--samples", dict(type=int, default=256)), ("--bc-weight", dict(type=float, default=1.0))],
+                          choices=("off", "expert", "expert+bc"))
+    bc = a.leg == "expert+bc"
+
+    def options():
+        kw = {}
+        if a.leg != "off":
+            from ddpg_trucktrailer_amd.mpc import ExpertLanes, MPCConfig
+            kw["expert"] = ExpertLanes(a.lanes, MPCConfig(horizon=a.horizon, samples=a.samples), seed=27)
+        if bc:
+            from ddpg_trucktrailer_amd.demo_loss import DemoLoss
+            kw["demo_loss"] = DemoLoss(a.bc_weight)
+        return kw
+
     if a.leg:
-        return one_leg(a)
-    variants = (["parent"] if a.parent_tree else []) + ["off", "expert", "expert+bc"]
-    res = {v: [] for v in variants}
-    for leg in range(a.legs):
-        for v in (variants if leg % 2 == 0 else variants[::-1]):
-            res[v].append(run_leg(a, v))
-            print(f"round {leg} {v:>9}: {res[v][-1]:.5f} ms per vector step", flush=True)
+        return option_cost.one_leg(a, options, stats=(lambda loop: f" demo_stats={loop.demo_stats()}") if bc else None)
     what = f"ExpertLanes({a.lanes}, H = {a.horizon}, S = {a.samples})"
-    names = {"off": "the loop without expert", "expert": what, "expert+bc": f"{what} + DemoLoss({a.bc_weight})",
-             "parent": "the parent commit's loop"}
-    lines = [f"# DDPGRollout, N = {N}, {UPD} updates per vector step, B = {B}, ring of {SLOTS} slots, whole-step graphs of {GRAPH_STEPS}; "
-             f"{a.steps} timed vector steps per leg after {a.warmup}, every leg a fresh process, {a.legs} legs, variants alternating"]
-    for v in variants:
-        x = res[v]
-        lines.append(f"{names[v]:>55}: " + "  ".join(f"leg {i} {t:8.5f}" for i, t in enumerate(x)) +
-                     f"  | median {statistics.median(x):8.5f} ms per vector step, max - min {max(x) - min(x):7.5f}")
-    off = statistics.median(res["off"])
-    spread = max(res["off"]) - min(res["off"])
-    for v in ("expert", "expert+bc"):
-        on = statistics.median(res[v])
-        lines.append(f"# {v} - off = {1e3 * (on - off):+.2f} us per vector step ({100 * (on - off) / off:+.2f} %); the off legs' own max - min is "
-                     f"{1e3 * spread:.2f} us per vector step (a record, not a gate)")
-    if a.parent_tree:
-        p = res["parent"]
-        limit = statistics.median(p) + (max(p) - min(p))
-        lines.append(f"# gate: off median {off:.5f} ms against the parent's median + its legs' max - min = {limit:.5f} ms: "
-                     + ("within" if off <= limit else "NOT within"))
-    else:
-        lines.append("# no --parent-tree: the gate against the parent commit was not evaluated")
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    option_cost.compare(a, __file__, ["off", "expert", "expert+bc"],
+                        ["--lanes", str(a.lanes), "--horizon", str(a.horizon), "--samples", str(a.samples), "--bc-weight", str(a.bc_weight)],
+                        {"off": "the loop without expert", "expert": what, "expert+bc": f"{what} + DemoLoss({a.bc_weight})"}, 55, records=True)
 
 
 if __name__ == "__main__":

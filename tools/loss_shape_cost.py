@@ -10,93 +10,24 @@ The gate is the rule of DESIGN.md section 13 on the leg without a shape: its med
 own max - min (it launches the parent's kernels: anything else is a host-side regression).  on - off is a record, not a gate.
 Usage: loss_shape_cost.py [--legs 3] [--steps 400] [--warmup 60] [--huber 1.0] [--pre-penalty 0.01] [--parent-tree DIR] [--out FILE]
        loss_shape_cost.py --leg off|on [--tree DIR] ...      (one leg in this process; prints "LEG <ms per vector step>")"""
-import argparse
-import os
-import statistics
-import subprocess
-import sys
-import time
-
-HERE = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-N, UPD, B, SLOTS, GRAPH_STEPS = 4096, 64, 256, 64, 4
-
-
-def one_leg(a):
-    sys.path.insert(0, os.path.abspath(a.tree) if a.tree else HERE)
-    import torch
-    from ddpg_trucktrailer_amd.rollout import DDPGRollout
-    from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
-    kw = {}
-    if a.leg == "on":
-        from ddpg_trucktrailer_amd.loss_shape import LossShape
-        kw["loss_shape"] = LossShape(a.huber if a.huber > 0 else None, a.pre_penalty)
-    env = TruckTrailerVecEnv(N)
-    env.reset(seed=27)
-    loop = DDPGRollout(env, batch_size=B, replay_slots=SLOTS, seed=27, updates_per_step=UPD, graph_steps=GRAPH_STEPS, **kw)
-    loop.run(a.warmup)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    loop.run(a.steps)
-    torch.cuda.synchronize()
-    ms = (time.perf_counter() - t0) * 1e3 / a.steps
-    assert loop.graph_steps == GRAPH_STEPS and loop.handover_gave_up == [] and loop.learner.tail_gave_up() == 0
-    assert all(torch.isfinite(p).all() for p in loop.agent.actor.parameters())
-    print(f"pipeline={loop.pipeline} fuse_tail={loop.learner.fuse_tail} updates={int(loop.learner.step_dev.item())}")
-    print(f"LEG {ms:.5f}")
-
-
-def run_leg(a, variant):
-    cmd = [sys.executable, os.path.abspath(__file__), "--leg", "off" if variant == "parent" else variant, "--steps", str(a.steps),
-           "--warmup", str(a.warmup), "--huber", str(a.huber), "--pre-penalty", str(a.pre_penalty)]
-    if variant == "parent":
-        cmd += ["--tree", a.parent_tree]
-    out = subprocess.run(cmd, check=True, capture_output=True, text=True, timeout=300).stdout
-    return float([ln for ln in out.splitlines() if ln.startswith("LEG ")][-1].split()[1])
+import option_cost
 
 
 def main():
-    ap = argparse.ArgumentParser()
-    ap.add_argument("--legs", type=int, default=3)
-    ap.add_argument("--steps", type=int, default=400)
-    ap.add_argument("--warmup", type=int, default=60)
-    ap.add_argument("--huber", type=float, default=1.0)
-    ap.add_argument("--pre-penalty", type=float, default=0.01)
-    ap.add_argument("--parent-tree", default=None)
-    ap.add_argument("--out", default=None)
-    ap.add_argument("--leg", choices=("off", "on"), default=None)
-    ap.add_argument("--tree", default=None)
-    a = ap.parse_args()
+    a = option_cost.parse([("--huber", dict(type=float, default=1.0)), ("--pre-penalty", dict(type=float, default=0.01))],
+                          choices=("off", "on"))
+    shape = (a.huber if a.huber > 0 else None, a.pre_penalty)
+
+    def options():
+        if a.leg == "off":
+            return {}
+        from ddpg_trucktrailer_amd.loss_shape import LossShape
+        return {"loss_shape": LossShape(*shape)}
+
     if a.leg:
-        return one_leg(a)
-    variants = ["off", "on"] + (["parent"] if a.parent_tree else [])
-    res = {v: [] for v in variants}
-    for leg in range(a.legs):
-        for v in (variants if leg % 2 == 0 else variants[::-1]):
-            res[v].append(run_leg(a, v))
-            print(f"round {leg} {v:>6}: {res[v][-1]:.5f} ms per vector step", flush=True)
-    names = dict(off="the loop without a shape", on=f"LossShape({a.huber if a.huber > 0 else None}, {a.pre_penalty})",
-                 parent="the parent commit's loop")
-    lines = [f"# DDPGRollout, N = {N}, {UPD} updates per vector step, B = {B}, ring of {SLOTS} slots, whole-step graphs of {GRAPH_STEPS}; "
-             f"{a.steps} timed vector steps per leg after {a.warmup}, every leg a fresh process, {a.legs} legs, variants alternating"]
-    for v in variants:
-        x = res[v]
-        lines.append(f"{names[v]:>28}: " + "  ".join(f"leg {i} {t:8.5f}" for i, t in enumerate(x)) +
-                     f"  | median {statistics.median(x):8.5f} ms per vector step, max - min {max(x) - min(x):7.5f}")
-    off, on = statistics.median(res["off"]), statistics.median(res["on"])
-    spread = max(res["off"]) - min(res["off"])
-    lines.append(f"# on - off = {1e3 * (on - off):+.2f} us per vector step = {1e3 * (on - off) / UPD:+.3f} us per update; the off legs' own max - min "
-                 f"is {1e3 * spread:.2f} us per vector step: " + ("within it" if on - off <= spread else "beyond it"))
-    if a.parent_tree:
-        p = res["parent"]
-        limit = statistics.median(p) + (max(p) - min(p))
-        lines.append(f"# gate: off median {off:.5f} ms against the parent's median + its legs' max - min = {limit:.5f} ms: "
-                     + ("within" if off <= limit else "NOT within"))
-    else:
-        lines.append("# no --parent-tree: the gate against the parent commit was not evaluated")
-    print("\n".join(lines))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+        return option_cost.one_leg(a, options)
+    option_cost.compare(a, __file__, ["off", "on"], ["--huber", str(a.huber), "--pre-penalty", str(a.pre_penalty)],
+                        dict(off="the loop without a shape", on=f"LossShape({shape[0]}, {shape[1]})"), 28)
 
 
 if __name__ == "__main__":
