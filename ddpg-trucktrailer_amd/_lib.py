@@ -116,6 +116,11 @@ class TTPopNstep(C.Structure):
     _fields_ = [("n_step", C.c_int32), ("gamma", C.c_float), ("discount", C.c_float)]
 
 
+class TTPopClip(C.Structure):
+    """struct tt_pop_clip (include/ttenv.h): max_norm of an agent's critic and actor, each a finite number > 0 or 0 = not clipped."""
+    _fields_ = [("max_norm_critic", C.c_float), ("max_norm_actor", C.c_float)]
+
+
 class TTTd3Agent(C.Structure):
     _fields_ = [("sample", C.POINTER(TTSampleArgs)), ("jobs", C.POINTER(TTFwdJob)), ("td", C.POINTER(TTTdInput)),
                 ("critic", TTPopNet), ("critic_2", TTPopNet), ("actor", TTPopNet), ("z_state_2", C.c_void_p),
@@ -318,6 +323,9 @@ _SIGNATURES = {
                                                 C.c_int32, C.POINTER(TTDemoLabels), _P]),
     "tt_adam_soft_update_clipped": (C.c_int, [_I, _P, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float,
                                               C.c_float, C.c_float, C.POINTER(TTFc2Images), _P, C.POINTER(TTGradClip), _P]),
+    "tt_pop_learn_set_clip": (C.c_int, [_P, C.POINTER(TTPopClip)]),
+    "tt_pop_clip_write": (C.c_int, [_P, _I, C.POINTER(C.c_int32), C.POINTER(TTPopClip), _P]),
+    "tt_pop_clip": (C.c_int, [_P, _I, C.POINTER(TTPopClip), C.POINTER(C.c_float * 4), C.POINTER(C.c_int64 * 4)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -117,7 +117,10 @@ def pbt_file_state(pbt):
     kind, keys, pos, has_gauss, gauss = sd["rng"]
     rng = {"kind": str(kind), "keys": torch.from_numpy(np.array(keys, dtype=np.uint32)), "pos": int(pos),
            "has_gauss": int(has_gauss), "gauss": float(gauss)}
-    return {"rng": rng, "windows": sd["windows"], "last_round": int(sd["last_round"]), "history": sd["history"]}
+    fs = {"rng": rng, "windows": sd["windows"], "last_round": int(sd["last_round"]), "history": sd["history"]}
+    if "clip_factors" in sd:           # (PBT(clip_factors=): only with the option)
+        fs["clip_factors"] = [float(f) for f in sd["clip_factors"]]
+    return fs
 
 
 def load_pbt_file_state(pbt, fs):
@@ -125,7 +128,7 @@ def load_pbt_file_state(pbt, fs):
     r = fs["rng"]
     pbt.load_state_dict({"rng": (r["kind"], r["keys"].numpy().astype(np.uint32), r["pos"], r["has_gauss"], r["gauss"]),
                          "windows": [[tuple(e) for e in w] for w in fs["windows"]], "last_round": fs["last_round"],
-                         "history": fs["history"]})
+                         "history": fs["history"], **({"clip_factors": fs["clip_factors"]} if "clip_factors" in fs else {})})
 
 
 def save_population_checkpoint(path, pop, pbt=None, training_state=None):

@@ -37,6 +37,12 @@ struct PopNstep {
     float gamma;
 };
 
+// agent a's entry of the clip table (tt_pop_learn_set_clip): max_norm of its critic [0] and its actor [1]; 0 = that network is not
+// clipped (its coefficient is 1 whatever the norm)
+struct PopClip {
+    float max_norm[2];
+};
+
 }  // namespace
 
 namespace ttpop {
@@ -52,5 +58,30 @@ struct NstepWrites {
 // csrc/ttpop_nstep.hip.  agents: PopAgent[K], table: PopNstep[K], both in device memory.
 void launch_fwd_multi_nstep(int K, int n, const void *agents, const void *table, int u, hipStream_t stream);
 void launch_set_nstep(const NstepWrites &w, void *table, hipStream_t stream);
+
+// one table write of tt_pop_clip_write (a launch argument)
+struct ClipWrites {
+    int n;
+    int agent[TT_POP_MAX_AGENTS];
+    float max_norm[TT_POP_MAX_AGENTS][2];
+};
+
+// what tt_pop_learn_set_clip makes, all in device memory: tables AdamTable[K][2] (agent a's tensors of network `net`, with its
+// gradients; block_start counts from a * blocks[net], the agent's first workgroup of the clipped optimizer launch), clip PopClip[K],
+// partials f64 [K][2][TT_GRAD_CLIP_PARTIALS], out f32 [K][2][2] = {norm, coef}, counts int64 [K][2][2] = {updates, clipped updates}
+struct ClipBufs {
+    void *tables, *clip, *partials, *out, *counts;
+    int blocks[2];              // fill_adam_table's count per network (the same for every agent)
+    long long chunk[2];         // ceil(a network's elements / TT_GRAD_CLIP_PARTIALS)
+};
+
+// csrc/ttclip.hip.  agents: PopAgent[K] in device memory; net: 0 the critic, 1 the actor.
+void launch_pop_grad_sqnorm(int K, int net, const ClipBufs &c, hipStream_t stream);
+void launch_pop_adam_soft_clip(int K, int net, const void *agents, const ClipBufs &c, hipStream_t stream);
+void launch_clip_write(const ClipWrites &w, void *clip, hipStream_t stream);
+// agent a's table of network `net` from its descriptor P (a host copy), its first workgroup at `first_block`; returns the network's
+// workgroups, or -1 as fill_adam_table does.  total: the network's elements.
+int fill_pop_clip_table(const void *P, int net, int first_block, void *table, long long *total);
+size_t clip_table_bytes();
 
 }  // namespace ttpop

@@ -13,6 +13,9 @@
 // and, off the learn() path, k_pop_exploit (tt_pop_exploit): population-based training's exploit/explore step between vector steps.
 // With per-agent n-step returns (tt_pop_learn_set_nstep) the first launch is k_pop_fwd_multi_nstep of csrc/ttpop_nstep.hip instead;
 // the other three are the same, an agent's td.gamma then holding its discount gamma ** n.
+// With per-agent gradient-norm clipping (tt_pop_learn_set_clip) the descriptors' optimizers are off: the critic's weight launch and
+// the actor tail leave gradients only, and each is followed by k_pop_grad_sqnorm and k_pop_adam_soft_clip of csrc/ttclip.hip --
+// eight launches.  No kernel of this file changes for it.
 //
 // So each agent's results are the bits of its lone learn() (tests/test_gpu_population.py).  Per-agent arguments live in device
 // memory (PopAgent), filled once at tt_pop_learn_create: a launch takes (K, B, descriptors, u) and is graph-capturable.
@@ -246,7 +249,25 @@ struct tt_population {
     PopAgent *dev = nullptr;
     PopNstep *table = nullptr;           // per-agent {n_step, gamma}: made by tt_pop_learn_set_nstep, then there for good
     std::vector<int> slots, reserve;     // each agent's ring, for the window check of a later n_step
+    bool clipped = false;                // tt_pop_learn_set_clip was called: learn() is eight launches for good
+    ttpop::ClipBufs clip{};              // the clip's tables and buffers (library-owned device memory)
 };
+
+// what tt_pop_learn_set_clip ("agent" a) and tt_pop_clip_write ("entry" i) refuse in one tt_pop_clip (host only: no HIP call)
+static int check_pop_clip(const char *who, const char *what, const int i, const struct tt_pop_clip &q) {
+    const float v[2] = {q.max_norm_critic, q.max_norm_actor};
+    for (int net = 0; net < 2; ++net)
+        if (!std::isfinite(v[net]) || v[net] < 0.f)
+            return fail(TT_EINVAL, "%s: %s %d: max_norm_%s = %g is neither a finite number > 0 nor 0 (this network is not clipped)", who,
+                        what, i, net ? "actor" : "critic", (double)v[net]);
+    return TT_OK;
+}
+
+static void free_clip(ttpop::ClipBufs &c) {
+    for (void *p : {c.tables, c.clip, c.partials, c.out, c.counts})
+        if (p) (void)hipFree(p);
+    c = ttpop::ClipBufs{};
+}
 
 // what tt_pop_exploit and tt_pop_exploit_nstep (`who`) refuse in a list of pairs, which goes into L (host only: no HIP call)
 static int check_pairs(const char *who, const tt_population *h, const int pairs, const tt_pop_exploit_pair *list, ExploitList &L) {
@@ -283,7 +304,15 @@ int tt_pop_learn(tt_population *h, int update, tt_stream_t stream) {
     else hipLaunchKernelGGL(k_pop_fwd_multi, dim3(K * 4 * nb), dim3(64 * NW), 0, stream, K, n, h->dev, update);
     hipLaunchKernelGGL(k_pop_bwd_rows_pair, dim3(K * (2 * nb + 1)), dim3(64 * NW), 0, stream, K, n, h->dev);
     hipLaunchKernelGGL(k_pop_bwd_weights<false>, dim3(K * WG_CRITIC_WEIGHTS), dim3(256), 0, stream, K, n, h->dev);
+    if (h->clipped) {           // (the descriptors' optimizers are off: the two launches above and below leave gradients only)
+        ttpop::launch_pop_grad_sqnorm(K, 0, h->clip, stream);
+        ttpop::launch_pop_adam_soft_clip(K, 0, h->dev, h->clip, stream);
+    }
     hipLaunchKernelGGL(k_pop_actor_tail, dim3(K * (nb + WG_ACTOR_WEIGHTS)), dim3(64 * NW), 0, stream, K, n, h->dev);
+    if (h->clipped) {
+        ttpop::launch_pop_grad_sqnorm(K, 1, h->clip, stream);
+        ttpop::launch_pop_adam_soft_clip(K, 1, h->dev, h->clip, stream);
+    }
     return hipGetLastError() == hipSuccess ? TT_OK : TT_EHIP;
 }
 
@@ -359,6 +388,96 @@ int tt_pop_nstep(tt_population *h, int agent, struct tt_pop_nstep *out) {
     return TT_OK;
 }
 
+int tt_pop_learn_set_clip(tt_population *h, const struct tt_pop_clip *per_agent) {
+    static const char who[] = "tt_pop_learn_set_clip";
+    if (!h) return fail(TT_EINVAL, "tt_pop_learn_set_clip: handle is NULL");
+    if (!per_agent) return fail(TT_EINVAL, "tt_pop_learn_set_clip: per_agent is NULL");
+    const int K = h->K;
+    std::vector<PopClip> values(K);
+    for (int a = 0; a < K; ++a) {
+        if (const int rc = check_pop_clip(who, "agent", a, per_agent[a])) return rc;
+        values[a] = PopClip{{per_agent[a].max_norm_critic, per_agent[a].max_norm_actor}};
+    }
+    if (hipDeviceSynchronize() != hipSuccess) return fail(TT_EHIP, "tt_pop_learn_set_clip: hipDeviceSynchronize");
+    if (h->clipped)             // (the tables stand: only the values are new)
+        return hipMemcpy(h->clip.clip, values.data(), sizeof(PopClip) * K, hipMemcpyHostToDevice) == hipSuccess
+                   ? TT_OK : fail(TT_EHIP, "tt_pop_learn_set_clip: hipMemcpy");
+    std::vector<PopAgent> host(K);
+    if (hipMemcpy(host.data(), h->dev, sizeof(PopAgent) * K, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TT_EHIP, "tt_pop_learn_set_clip: hipMemcpy");
+    // the tensor tables with the gradient pointers, filled once; every agent's grid of a network is the same
+    const size_t tb = ttpop::clip_table_bytes();
+    std::vector<char> tables(tb * K * 2);
+    ttpop::ClipBufs c{};
+    for (int a = 0; a < K; ++a)
+        for (int net = 0; net < 2; ++net) {
+            long long total = 0;
+            // (agent 0's call gives the network's workgroups, the same for every agent; agent a's first is a times that)
+            const int blocks = ttpop::fill_pop_clip_table(&host[a], net, a * c.blocks[net], tables.data() + tb * (a * 2 + net), &total);
+            if (blocks <= 0) return fail(TT_EINVAL, "tt_pop_learn_set_clip: agent %d: network %d lacks a tensor", a, net);
+            c.blocks[net] = blocks;
+            c.chunk[net] = (total + TT_GRAD_CLIP_PARTIALS - 1) / TT_GRAD_CLIP_PARTIALS;
+        }
+    const size_t np = sizeof(double) * K * 2 * TT_GRAD_CLIP_PARTIALS, no = sizeof(float) * K * 4, nc = sizeof(long long) * K * 4;
+    bool ok = hipMalloc(&c.tables, tables.size()) == hipSuccess && hipMalloc(&c.clip, sizeof(PopClip) * K) == hipSuccess &&
+              hipMalloc(&c.partials, np) == hipSuccess && hipMalloc(&c.out, no) == hipSuccess && hipMalloc(&c.counts, nc) == hipSuccess;
+    if (!ok) {
+        free_clip(c);
+        return fail(TT_ENOMEM, "tt_pop_learn_set_clip: hipMalloc");
+    }
+    for (PopAgent &P : host) P.Ac.on = P.Aa.on = 0;        // the weight-gradient launches leave the gradient and skip the optimizer
+    ok = hipMemcpy(c.tables, tables.data(), tables.size(), hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemcpy(c.clip, values.data(), sizeof(PopClip) * K, hipMemcpyHostToDevice) == hipSuccess &&
+         hipMemset(c.partials, 0, np) == hipSuccess && hipMemset(c.out, 0, no) == hipSuccess && hipMemset(c.counts, 0, nc) == hipSuccess &&
+         hipMemcpy(h->dev, host.data(), sizeof(PopAgent) * K, hipMemcpyHostToDevice) == hipSuccess &&
+         hipDeviceSynchronize() == hipSuccess;
+    if (!ok) {
+        free_clip(c);
+        return fail(TT_EHIP, "tt_pop_learn_set_clip: hipMemcpy");
+    }
+    h->clip = c;
+    h->clipped = true;
+    return TT_OK;
+}
+
+int tt_pop_clip_write(tt_population *h, int count, const int32_t *agents, const struct tt_pop_clip *values, tt_stream_t stream) {
+    static const char who[] = "tt_pop_clip_write";
+    if (!h) return fail(TT_EINVAL, "tt_pop_clip_write: handle is NULL");
+    if (!agents) return fail(TT_EINVAL, "tt_pop_clip_write: agents is NULL");
+    if (!values) return fail(TT_EINVAL, "tt_pop_clip_write: values is NULL");
+    if (!h->clipped) return fail(TT_EINVAL, "tt_pop_clip_write: this population has no clip table (tt_pop_learn_set_clip makes it)");
+    if (count < 1 || count > h->K) return fail(TT_EINVAL, "tt_pop_clip_write: count = %d, not in [1, K = %d]", count, h->K);
+    ttpop::ClipWrites W{};
+    W.n = count;
+    for (int i = 0; i < count; ++i) {
+        if (agents[i] < 0 || agents[i] >= h->K)
+            return fail(TT_EINVAL, "tt_pop_clip_write: entry %d: agent %d is not in [0, K = %d)", i, (int)agents[i], h->K);
+        for (int j = 0; j < i; ++j)
+            if (agents[j] == agents[i]) return fail(TT_EINVAL, "tt_pop_clip_write: entries %d and %d both name agent %d", j, i, (int)agents[i]);
+        if (const int rc = check_pop_clip(who, "entry", i, values[i])) return rc;
+        W.agent[i] = agents[i];
+        W.max_norm[i][0] = values[i].max_norm_critic;
+        W.max_norm[i][1] = values[i].max_norm_actor;
+    }
+    ttpop::launch_clip_write(W, h->clip.clip, stream);
+    return hipGetLastError() == hipSuccess ? TT_OK : fail(TT_EHIP, "tt_pop_clip_write: the launch failed");
+}
+
+int tt_pop_clip(tt_population *h, int agent, struct tt_pop_clip *value, float out[4], int64_t counts[4]) {
+    if (!h) return fail(TT_EINVAL, "tt_pop_clip: handle is NULL");
+    if (!value || !out || !counts) return fail(TT_EINVAL, "tt_pop_clip: value, out or counts is NULL");
+    if (agent < 0 || agent >= h->K) return fail(TT_EINVAL, "tt_pop_clip: agent %d is not in [0, K = %d)", agent, h->K);
+    if (!h->clipped) return fail(TT_EINVAL, "tt_pop_clip: this population has no clip table (tt_pop_learn_set_clip makes it)");
+    PopClip e;
+    if (hipMemcpy(&e, static_cast<const PopClip *>(h->clip.clip) + agent, sizeof e, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(out, static_cast<const float *>(h->clip.out) + 4 * agent, sizeof(float) * 4, hipMemcpyDeviceToHost) != hipSuccess ||
+        hipMemcpy(counts, static_cast<const long long *>(h->clip.counts) + 4 * agent, sizeof(int64_t) * 4, hipMemcpyDeviceToHost) != hipSuccess)
+        return fail(TT_EHIP, "tt_pop_clip: hipMemcpy");
+    value->max_norm_critic = e.max_norm[0];
+    value->max_norm_actor = e.max_norm[1];
+    return TT_OK;
+}
+
 int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
     if (!h) return fail(TT_EINVAL, "tt_pop_hyper: handle is NULL");
     if (!out) return fail(TT_EINVAL, "tt_pop_hyper: out is NULL");
@@ -382,6 +501,7 @@ int tt_pop_hyper(tt_population *h, int agent, float out[4]) {
 int tt_pop_learn_destroy(tt_population *h) {
     if (!h) return TT_OK;
     const hipError_t e = hipFree(h->dev), e2 = h->table ? hipFree(h->table) : hipSuccess;
+    free_clip(h->clip);
     delete h;
     return e == hipSuccess && e2 == hipSuccess ? TT_OK : TT_EHIP;
 }

@@ -67,7 +67,7 @@ def whole_number(what, x, lo, hi=None, bound=None):
 # ---- the refusal table.  A row: (the context field it reads, when it refuses, the message); the context is a dict of DEFAULTS,
 # what the caller knows, and "value", the option itself.  A message is a template over the option's words, or a function of the context.
 # Beyond DEFAULTS an option's own rows read what its check_* passes: labels "first" (the expert lanes before the labelled ones);
-# grad_clip "demo_loss", "expert" and "labels" (each None or the loop's option); td3 "updates_per_step" and "delay"; population_td3 those two and "n_steps", "n_step_max", "device".
+# grad_clip "demo_loss", "expert" and "labels" (each None or the loop's option); population_grad_clip "device" (None: not known yet); td3 "updates_per_step" and "delay"; population_td3 those two and "n_steps", "n_step_max", "device".
 UNSET = object()
 DEFAULTS = dict(td3=None, population=False, data_parallel=False, force_dp=False, n_step=1, ring_mode=None, n_envs=None, pipeline=None,
                 learn_log=None, demo_loss=UNSET)
@@ -117,6 +117,14 @@ TABLE = {
                              "grad_clip with expert lanes is not supported (they train through the demonstration entry points)"),
                             ("labels", lambda c: c["labels"] is not None,
                              "grad_clip with expert labels is not supported (they train through the demonstration entry points)"))),
+    # a population's OWN clip (PopulationLearner(grad_clips=) / PopulationRollout(grad_clip=)); "value": the list of per-agent entries
+    "population_grad_clip": dict(rows=(
+        ("td3", lambda c: c["td3"] is not None,
+         "grad_clip in a TD3 population (PopulationTD3Learner / PopulationRollout(td3=...)) is not supported: the shared TD3 launches "
+         "have no clipped optimizer step"),
+        ("data_parallel", lambda c: c["data_parallel"], "grad_clip in a data-parallel population is not supported (populations run on one GPU)"),
+        ("device", lambda c: c["device"] is not None and _device_type(c["device"]) != "cuda",
+         lambda c: f"grad_clip in a population on device = {c['device']!r} is not supported: the per-agent clip exists only as HIP kernels"))),
     "td3": dict(rows=(_TD3_MULTIPLE, ("n_step", lambda c: int(c["n_step"]) > 1, lambda c: f"td3: n_step = {c['n_step']} > 1 is not supported"),
                       ("data_parallel", lambda c: c["data_parallel"], "td3: data_parallel ranks (and the p2p exchange) are not supported"),
                       ("pipeline", lambda c: c["pipeline"], "td3: pipeline=True is not supported (TD3 runs in the serial order)"),

@@ -25,20 +25,26 @@ Rules:
   - n_step_choices (e.g. (1, 3, 5, 8); None: n is not PBT's business, and every decision and draw is as without the option): dst also
     inherits src's n-step horizon, and explore moves it to a neighbour in the sorted choices or keeps it -- one more draw of the
     same RNG (0, 1, 2: down, keep, up; clamped at the ends), taken after the pair's src and factor draws: the first pair of a
-    run takes the same src, alpha, beta, tau and gamma with the option as without, and every later draw comes one per pair later."""
+    run takes the same src, alpha, beta, tau and gamma with the option as without, and every later draw comes one per pair later;
+  - clip_factors (e.g. (0.8, 1.2); None: the gradient clip is not PBT's business, and every decision and draw is as without the
+    option): dst inherits src's two max_norm values ("clip_critic", "clip_actor": the clip travels with the weights it was tuned
+    on), and explore multiplies each by a factor drawn from clip_factors as alpha's is from `factors` -- two more draws of the same
+    RNG per pair, the critic's then the actor's, after the pair's other draws -- and clamps it to bounds["clip"].  A 0 (that
+    network is not clipped) stays 0, whatever its draw."""
 import collections
 import math
 
 import numpy as np
 
 HYPERS = ("alpha", "beta", "tau", "gamma")
-BOUNDS = {"alpha": (1e-6, 1e-2), "beta": (1e-6, 1e-1), "tau": (1e-5, 1e-1), "gamma": (0.9, 0.9999)}
+BOUNDS = {"alpha": (1e-6, 1e-2), "beta": (1e-6, 1e-1), "tau": (1e-5, 1e-1), "gamma": (0.9, 0.9999), "clip": (1e-3, 1e6)}
+CLIPS = ("clip_critic", "clip_actor")
 METRICS = ("return", "success")
 
 
 class PBT:
     def __init__(self, K, ready, seed=0, quantile=0.25, metric="return", window=100, min_episodes=None, explore=HYPERS,
-                 factors=(0.8, 1.2), bounds=None, n_step_choices=None):
+                 factors=(0.8, 1.2), bounds=None, n_step_choices=None, clip_factors=None):
         self.K, self.ready = int(K), int(ready)
         if self.K < 1 or self.ready < 1:
             raise ValueError(f"PBT: K = {K} and ready = {ready} must be >= 1")
@@ -62,6 +68,11 @@ class PBT:
             self.n_step_choices = tuple(sorted({int(n) for n in n_step_choices}))
             if not self.n_step_choices or self.n_step_choices[0] < 1:
                 raise ValueError(f"PBT: n_step_choices {n_step_choices} must be positive step counts")
+        self.clip_factors = None
+        if clip_factors is not None:
+            self.clip_factors = tuple(float(f) for f in clip_factors)
+            if not self.clip_factors or any(not (f > 0.0 and math.isfinite(f)) for f in self.clip_factors):
+                raise ValueError(f"PBT: clip_factors {clip_factors} must be positive")
         self.bounds = dict(BOUNDS)
         self.bounds.update(bounds or {})
         self.rng = np.random.RandomState(seed)
@@ -107,7 +118,8 @@ class PBT:
 
     # ------------------------------------------------------------------------------------------------- a round
     def decide(self, vector_step, hypers, evaluation=None):
-        """hypers: per agent {"alpha", "beta", "tau", "gamma"} (and "n_step" with n_step_choices) as they are now.  Returns the
+        """hypers: per agent {"alpha", "beta", "tau", "gamma"} (and "n_step" with n_step_choices, "clip_critic" and "clip_actor" with
+        clip_factors) as they are now.  Returns the
         round's decisions (possibly none): [{"step", "dst", "src", "dst_score", "src_score", "old", "new"}] -- "new" is what dst
         takes.  evaluation: the K record dicts of an evaluation -- the round then ranks on those records alone
         (evaluation_scores), everything after the ranking is the same."""
@@ -137,6 +149,13 @@ class PBT:
             if self.n_step_choices is not None:
                 old["n_step"] = int(hypers[dst]["n_step"])
                 new["n_step"] = self._explore_n(int(hypers[src]["n_step"]))
+            if self.clip_factors is not None:
+                lo, hi = self.bounds["clip"]
+                for k in CLIPS:
+                    f = self.clip_factors[self.rng.randint(len(self.clip_factors))]
+                    x = float(hypers[src][k])
+                    old[k] = float(hypers[dst][k])
+                    new[k] = min(max(x * f, lo), hi) if x > 0.0 else 0.0
             out.append({"step": int(vector_step), "dst": dst, "src": src, "dst_score": scores[dst], "src_score": scores[src],
                         "old": old, "new": new})
             self.windows[dst].clear()
@@ -162,6 +181,11 @@ class PBT:
         if self.n_step_choices is not None:
             for h, n in zip(hypers, pop.n_steps):
                 h["n_step"] = int(n)
+        if self.clip_factors is not None:
+            if not getattr(pop, "clip_table", False):
+                raise ValueError("PBT: clip_factors needs a population built with a gradient clip (PopulationRollout(grad_clip=...))")
+            for h, (c, a) in zip(hypers, pop.grad_clips):
+                h["clip_critic"], h["clip_actor"] = float(c), float(a)
         out = self.decide(pop.vector_steps, hypers, evaluation)
         if out:
             pop.exploit([(d["dst"], d["src"], d["new"]) for d in out])
@@ -169,12 +193,18 @@ class PBT:
 
     # ------------------------------------------------------------------------------------------------- checkpoint
     def state_dict(self):
-        return {"rng": self.rng.get_state(), "windows": [list(w) for w in self.windows], "last_round": self.last_round,
-                "history": [dict(d) for d in self.history]}
+        sd = {"rng": self.rng.get_state(), "windows": [list(w) for w in self.windows], "last_round": self.last_round,
+              "history": [dict(d) for d in self.history]}
+        if self.clip_factors is not None:          # (only with the option: a state written without it is what it was)
+            sd["clip_factors"] = list(self.clip_factors)
+        return sd
 
     def load_state_dict(self, sd):
         if len(sd["windows"]) != self.K:
             raise ValueError(f"PBT.load_state_dict: {len(sd['windows'])} windows for {self.K} agents")
+        have = None if sd.get("clip_factors") is None else tuple(float(f) for f in sd["clip_factors"])
+        if have != self.clip_factors:
+            raise ValueError(f"PBT.load_state_dict: the state was written with clip_factors = {have}, this controller has {self.clip_factors}")
         self.rng.set_state(sd["rng"])
         self.windows = [collections.deque(w, maxlen=self.window) for w in sd["windows"]]
         self.last_round = int(sd["last_round"])

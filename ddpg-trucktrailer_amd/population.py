@@ -15,6 +15,13 @@ discount gamma ** n travels by value (fused_learn.nstep_discount, the lone learn
 table its first launch is the n-step kernel for good -- also at n = 1, the one-step draw bit for bit -- so exploit() may change
 an agent's n under captured graphs.  A population built without n-step arguments launches the four one-step kernels.
 
+Gradient-norm clipping is per agent as well (grad_clips= / grad_clip=; include/ttenv.h: tt_pop_clip): one
+GradClip for all, or one GradClip or None per agent.  Any entry makes a table of the agents' max_norm values in device memory (0 =
+that network is not clipped), and a population update is then eight launches for good: the weight-gradient launches leave the
+gradients, and a norm launch and a clipped optimizer launch (csrc/ttclip.hip) follow each.  exploit() carries the clip with the
+weights, or sets a new one ("clip_critic" / "clip_actor"), under captured graphs.  An agent's bits are those of a lone
+FusedLearner(grad_clip=); an agent with no clip in such a population has the bits of the lone separate-optimizer chain.
+
 With td3= (one td3.TD3Config, or one per agent with equal policy_delay) every agent is a TD3 agent -- six networks, its own
 target_noise and noise_clip -- and a population update is the shared TD3 launches of csrc/ttpop_td3.hip (td3.PopulationTD3Learner,
 DESIGN.md section 17): update u of a vector step is a full one when (u + 1) % policy_delay == 0, as in a lone TD3 loop, whose bits
@@ -34,7 +41,7 @@ import torch
 from ddpg_trucktrailer_amd import _lib as L
 from ddpg_trucktrailer_amd.demo_loss import check_demo_loss
 from ddpg_trucktrailer_amd.fused_learn import FusedLearner, LearnLog, check_learn_log, nstep_discount
-from ddpg_trucktrailer_amd.grad_clip import check_grad_clip
+from ddpg_trucktrailer_amd.grad_clip import check_grad_clip, check_population_grad_clip, clip_values
 from ddpg_trucktrailer_amd.loss_shape import check_loss_shape
 from ddpg_trucktrailer_amd.mpc import check_expert_lanes
 from ddpg_trucktrailer_amd.options import write_options
@@ -142,9 +149,23 @@ class _PopulationLearnerBase:
             n = self._pair_n_step(i, dst, src, hyp)
             of_src = self._hyper_of(src)
             new.append((dst, src, {k: float(hyp.get(k, of_src[k])) for k in self.HYPERS}, n))
+        clips = self._pair_clips(pairs)
         self._launch_exploit(new)
+        self._launch_clip_write(clips)
         for dst, _, h, n in new:
             self._set_mirrors(dst, h, n)
+
+    def _pair_clips(self, pairs):
+        """What exploit()'s pairs say about the clip, checked before anything is launched: [(dst, max_norm critic, max_norm
+        actor)], or None for a population without a clip table, which refuses the keys."""
+        for i, (_, _, hyp) in enumerate(pairs):
+            if "clip_critic" in hyp or "clip_actor" in hyp:
+                raise ValueError(f"exploit: pair {i} sets clip_critic / clip_actor, but this population was built without a gradient clip "
+                                 "(PopulationLearner(grad_clips=...) / PopulationRollout(grad_clip=...))")
+        return None
+
+    def _launch_clip_write(self, clips):
+        pass
 
     def _set_mirrors(self, a, h, n):
         """Agent a's host mirrors of the hyperparameters h ({HYPERS}) and of its n: what exploit() and a checkpoint's load leave
@@ -207,12 +228,20 @@ class PopulationLearner(_PopulationLearnerBase):
     and drain_learn_log() collects them.  One K-agent handle, made with the descriptors.  Not part of any checkpoint.
     exploit() (include/ttenv.h: tt_pop_exploit): a pair's dict may also hold "n_step" (missing: src's): on an n-step population dst
     then draws with that n and the pair's gamma and discounts with gamma ** n (tt_pop_exploit_nstep); a population without the
-    table refuses an n other than 1."""
+    table refuses an n other than 1.
+    grad_clips: None = no clip, launch for launch; one grad_clip.GradClip or a list with one GradClip or None per agent = per-agent
+    gradient-norm clipping (include/ttenv.h: tt_pop_learn_set_clip).  Any entry makes the clip table, and learn() is then eight
+    launches for good.  Host mirrors: self.grad_clips[a] = [max_norm critic, max_norm actor], 0.0 = that network is not clipped.
+    exploit(): a pair's dict may hold "clip_critic" / "clip_actor" (missing: src's value -- the clip travels with the weights it was
+    tuned on; 0 = not clipped); tt_pop_clip_write follows the exploit launch on the same stream.  clip_stats(a), clip_of(a)."""
 
     def __init__(self, agents, batch_size, fc2_images=None, rings=None, seeds=None, n_steps=None, learn_log=None, learn_log_every=1,
-                 loss_shape=None, demo_loss=None, expert=None):
+                 loss_shape=None, demo_loss=None, expert=None, grad_clips=None):
         _refuse_lone_options(loss_shape, demo_loss, expert, agents)
         super().__init__(agents, batch_size, rings, seeds)
+        clips = check_population_grad_clip(grad_clips, self.K)
+        self.clip_table = clips is not None
+        self.grad_clips = [list(clip_values(c)) for c in (clips or [None] * self.K)]      # host mirrors: [max_norm critic, actor], 0 = off
         if any(r._side_struct() is not None for r in rings):
             raise ValueError("expert side buffers are not supported in a population")
         self.n_steps = [check_n_step(n) for n in _per_agent(1 if n_steps is None else n_steps, self.K, "n_steps")]
@@ -244,6 +273,8 @@ class PopulationLearner(_PopulationLearnerBase):
         if self.nstep_table:
             ns = (L.TTPopNstep * self.K)(*[self._nstep_struct(ag.gamma, n) for ag, n in zip(self.agents, self.n_steps)])
             L.check(self.lib.tt_pop_learn_set_nstep(h, ns))
+        if self.clip_table:
+            L.check(self.lib.tt_pop_learn_set_clip(h, (L.TTPopClip * self.K)(*[L.TTPopClip(c, a) for c, a in self.grad_clips])))
         if self._learn_log_args is not None:       # (rebuilt with the descriptors: a fresh, empty ring)
             self.learn_log = LearnLog(self.learners, *self._learn_log_args)
 
@@ -296,6 +327,53 @@ class PopulationLearner(_PopulationLearnerBase):
         L.check(self.lib.tt_pop_nstep(self._h, int(a), C.byref(out)))
         return int(out.n_step), float(out.gamma), float(out.discount)
 
+    # ---- the per-agent gradient clip
+    def _pair_clips(self, pairs):
+        if not self.clip_table:
+            return super()._pair_clips(pairs)
+        from ddpg_trucktrailer_amd.options import finite_number
+        out = []
+        for i, (dst, src, hyp) in enumerate(pairs):
+            values = []
+            for j, key in enumerate(("clip_critic", "clip_actor")):
+                x = hyp.get(key, self.grad_clips[int(src)][j])
+                finite_number(f"exploit: pair {i}: {key}", x, ">= 0")
+                values.append(float(x))
+            out.append((int(dst), *values))
+        return out
+
+    def _launch_clip_write(self, clips):
+        if clips is None:
+            return
+        agents = (C.c_int32 * len(clips))(*[d for d, _, _ in clips])
+        values = (L.TTPopClip * len(clips))(*[L.TTPopClip(c, a) for _, c, a in clips])
+        L.check(self.lib.tt_pop_clip_write(self._h, len(clips), agents, values, L.stream()))
+        for dst, c, a in clips:
+            self.grad_clips[dst] = [c, a]
+
+    def _read_clip(self, a, what):
+        if not self.clip_table:
+            raise ValueError("grad_clip is off (PopulationLearner(grad_clips=...))")
+        self._need_handle(what)
+        value, out, counts = L.TTPopClip(), (C.c_float * 4)(), (C.c_int64 * 4)()
+        torch.cuda.synchronize()
+        L.check(self.lib.tt_pop_clip(self._h, int(a), C.byref(value), C.byref(out), C.byref(counts)))
+        return value, out, counts
+
+    def clip_stats(self, a):
+        """Agent a's {"critic", "actor": {"norm", "coef", "updates", "clipped"}} of its last update, FusedLearner.clip_stats()'s
+        entries -- here for both networks, also one that is not clipped (coef 1.0, clipped 0).  Counted from the handle's creation.
+        Synchronises."""
+        _, out, counts = self._read_clip(a, "clip_stats")
+        return {name: {"norm": float(out[2 * j]), "coef": float(out[2 * j + 1]), "updates": int(counts[2 * j]),
+                       "clipped": int(counts[2 * j + 1])} for j, name in enumerate(("critic", "actor"))}
+
+    def clip_of(self, a):
+        """Agent a's (max_norm critic, max_norm actor) as the device holds them, 0.0 = not clipped (include/ttenv.h: tt_pop_clip;
+        synchronises)."""
+        value = self._read_clip(a, "clip_of")[0]
+        return float(value.max_norm_critic), float(value.max_norm_actor)
+
 
 def _no_records():
     import numpy as np
@@ -319,10 +397,10 @@ def _per_agent(x, K, name):
 POPULATION_FORMAT = 1          # PopulationRollout.state_dict()["format"]; its agents are DDPGRollout.state_dict()s of format 2
 
 
-def check_population_state(sd, K, lanes, slots, batch_size, policy_delay=None, n_step_max=1, n_step_table=False):
+def check_population_state(sd, K, lanes, slots, batch_size, policy_delay=None, n_step_max=1, n_step_table=False, grad_clip_table=False):
     """What PopulationRollout.load_state_dict refuses, each a ValueError that names what differs, before anything is written: sd is a
-    PopulationRollout.state_dict(), the other arguments describe the population that would load it (policy_delay: None = DDPG).
-    Returns the agents' n_steps.  A pure function: no GPU."""
+    PopulationRollout.state_dict(), the other arguments describe the population that would load it (policy_delay: None = DDPG;
+    grad_clip_table: it was built with a gradient clip).  Returns the agents' n_steps.  A pure function: no GPU."""
     if sd.get("format") != POPULATION_FORMAT:
         raise ValueError(f"format: the checkpoint has format {sd.get('format')!r}, this code reads format {POPULATION_FORMAT}")
     agents = sd["agents"]
@@ -338,6 +416,10 @@ def check_population_state(sd, K, lanes, slots, batch_size, policy_delay=None, n
                          "td3: the checkpoint was written without td3, this population has td3 (no second critics in it)")
     if have is not None and int(have) != int(policy_delay):
         raise ValueError(f"policy_delay: the checkpoint was written with {int(have)}, this population has {policy_delay}")
+    if bool(sd.get("grad_clip_table", False)) != bool(grad_clip_table):
+        raise ValueError("grad_clip: the checkpoint was written with a gradient clip, this population has none "
+                         "(PopulationRollout(grad_clip=...))" if sd.get("grad_clip_table") else
+                         "grad_clip: the checkpoint was written without a gradient clip, this population has one")
     ups = int(sd["updates_per_step"])
     if have is not None and ups % int(have) != 0:
         raise ValueError(f"updates_per_step: the checkpoint's {ups} is not a multiple of policy_delay = {int(have)} (the delay is "
@@ -363,6 +445,11 @@ def check_population_state(sd, K, lanes, slots, batch_size, policy_delay=None, n
         need = ("alpha", "beta", "tau", "gamma") + (("target_noise", "noise_clip") if have is not None else ())
         if any(k not in st.get("hyper", {}) for k in need):
             raise ValueError(f"hyper: agent {a}'s state lacks one of {need} (a lone loop's state is no population agent's)")
+        if grad_clip_table:
+            clip = st.get("clip")
+            if not (isinstance(clip, (list, tuple)) and len(clip) == 2 and all(isinstance(x, float) and x >= 0.0 and x != float("inf")
+                                                                                for x in clip)):
+                raise ValueError(f"grad_clip: agent {a}'s state holds clip = {clip!r}, not [max_norm critic, max_norm actor]")
         n = int(st.get("n_step", 1))
         if n > int(n_step_max):
             raise ValueError(f"n_step: agent {a} was saved with n_step = {n}, above this population's n_step_max = {n_step_max}")
@@ -382,14 +469,17 @@ class PopulationRollout:
     agent starts learning at vector step 1 + n_max -- an agent with a smaller n later than its lone loop would -- and graph
     replay starts after max(4, 1 + n_max) eager steps.  n_step_max: the largest n an exploit() may give an agent later (PBT over
     n); the ring check and the start use it.
-    learn_log / learn_log_every: the learn log's capacity per agent and its stride in updates (PopulationLearner); drain_learn_log()."""
+    learn_log / learn_log_every: the learn log's capacity per agent and its stride in updates (PopulationLearner); drain_learn_log().
+    grad_clip: None, one grad_clip.GradClip or a list with one GradClip or None per agent (PopulationLearner(grad_clips=)): per-agent
+    gradient-norm clipping; exploit() may then set "clip_critic" / "clip_actor"; clip_stats(a), clip_of(a), grad_clips.  Not with td3."""
 
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, grad_clip=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
         _refuse_lone_options(loss_shape, demo_loss, expert)
+        grad_clip = check_population_grad_clip(grad_clip, len(seeds), td3=td3, data_parallel=bool(data_parallel), device=device)
         if td3 is not None:            # (before anything else: each refusal names its option)
             from ddpg_trucktrailer_amd.td3 import check_population_td3
             td3 = check_population_td3(td3, len(seeds), updates_per_step, _listed(n_step), 1 if n_step_max is None else n_step_max,
@@ -441,7 +531,7 @@ class PopulationRollout:
         else:
             self.learner = PopulationLearner(self.agents, self.batch_size, fc2_images, rings=[lp.ring for lp in self.loops],
                                              seeds=self.seeds, n_steps=n_steps if nstep else None, learn_log=learn_log,
-                                             learn_log_every=learn_log_every)
+                                             learn_log_every=learn_log_every, grad_clips=grad_clip)
         self._learn_from, self._warm_steps = learn_start(self.n_step_max)      # (the largest n decides for every agent)
         self.graph_steps = int(graph_steps) if graph_steps else 0
         self.graph1 = self.graphG = self._graph_key = None
@@ -546,8 +636,8 @@ class PopulationRollout:
 
     def exploit(self, pairs):
         """PBT's exploit/explore step between vector steps, eagerly (PopulationLearner.exploit): pairs = [(dst, src, {"alpha",
-        "beta", "tau", "gamma"[, "n_step"]})].  The captured graphs stay as they are: the descriptors and the n-step table they
-        read change in place, no storage moves, and dst's fc2 images arrive with its weights.
+        "beta", "tau", "gamma"[, "n_step"][, "clip_critic", "clip_actor"]})].  The captured graphs stay as they are: the descriptors
+        and the n-step and clip tables they read change in place, no storage moves, and dst's fc2 images arrive with its weights.
         With td3 a pair's dict may hold six keys -- the four above, "target_noise" and "noise_clip" (a missing key: src's value) --
         and the copy is of six networks and three moment pairs (td3.PopulationTD3Learner.exploit); an "n_step" other than 1 is a
         ValueError there: n-step returns are not supported with td3, so n_step_max has nothing to check."""
@@ -567,6 +657,27 @@ class PopulationRollout:
     def n_step_of(self, a):
         return self.learner.n_step_of(a)
 
+    def clip_stats(self, a):
+        return self._clipped("clip_stats").clip_stats(a)
+
+    def clip_of(self, a):
+        return self._clipped("clip_of").clip_of(a)
+
+    def _clipped(self, what):
+        if not self.clip_table:
+            raise ValueError(f"{what}: grad_clip is off (PopulationRollout(grad_clip=...))")
+        return self.learner
+
+    @property
+    def clip_table(self):
+        return bool(getattr(self.learner, "clip_table", False))
+
+    @property
+    def grad_clips(self):
+        """Per agent [max_norm critic, max_norm actor] now, 0.0 = not clipped (the host mirror of the device table); None without
+        the option."""
+        return [list(c) for c in self.learner.grad_clips] if self.clip_table else None
+
     # -------------------------------------------------------------- checkpoint / resume of the whole population
     def state_dict(self):
         """Everything the next population step depends on (checkpoint.save_population_checkpoint writes
@@ -583,11 +694,16 @@ class PopulationRollout:
             if self.td3 is not None:
                 write_options(st, td3=lp.agent.td3)
                 st["fused_adam"]["updates"] = int(lr.updates)
+            if self.clip_table:            # (only with the option: a file written without it is what it was)
+                st["clip"] = [float(x) for x in lr.grad_clips[a]]
             agents.append(st)
-        return {"format": POPULATION_FORMAT, "K": self.K, "n": self.n, "batch_size": self.batch_size,
-                "updates_per_step": self.updates_per_step, "vector_steps": int(self.vector_steps), "seeds": list(self.seeds),
-                "n_step_table": bool(getattr(lr, "nstep_table", False)), "n_step_max": int(self.n_step_max),
-                "policy_delay": self.policy_delay if self.td3 is not None else None, "agents": agents}
+        sd = {"format": POPULATION_FORMAT, "K": self.K, "n": self.n, "batch_size": self.batch_size,
+              "updates_per_step": self.updates_per_step, "vector_steps": int(self.vector_steps), "seeds": list(self.seeds),
+              "n_step_table": bool(getattr(lr, "nstep_table", False)), "n_step_max": int(self.n_step_max),
+              "policy_delay": self.policy_delay if self.td3 is not None else None, "agents": agents}
+        if self.clip_table:
+            sd["grad_clip_table"] = True
+        return sd
 
     def load_state_dict(self, sd):
         """Restore a state_dict() in place, in a lone loop's order per agent -- networks, learner, ring, OU state, env, counters --
@@ -599,7 +715,7 @@ class PopulationRollout:
         that has never stepped and on one with captured graphs (they are dropped); run() goes on either way."""
         n_steps = check_population_state(sd, self.K, self.n, self.loops[0].ring.slots, self.batch_size,
                                          self.policy_delay if self.td3 is not None else None, self.n_step_max,
-                                         bool(getattr(self.learner, "nstep_table", False)))
+                                         bool(getattr(self.learner, "nstep_table", False)), self.clip_table)
         torch.cuda.synchronize(self.device)
         self.invalidate_graphs()           # (they hold the handle's address, and the policy launches their agent's seed)
         lr, agents = self.learner, sd["agents"]
@@ -612,6 +728,8 @@ class PopulationRollout:
         hypers = [dict(st["hyper"]) for st in agents]
         if self.td3 is not None:
             lr.updates = int(agents[0]["fused_adam"].get("updates", 0))
+        if self.clip_table:            # (restore() makes the handle, and with it the clip table, from the mirrors)
+            lr.grad_clips = [[float(x) for x in st["clip"]] for st in agents]
         lr.restore(self.seeds, hypers, n_steps)
         self.vector_steps = int(sd["vector_steps"])
         self.updates_per_step = int(sd["updates_per_step"])

@@ -253,8 +253,11 @@ class PopulationTD3Learner(_PopulationLearnerBase):
     HYPERS = HYPERS6
     _DESTROY, _HYPER = "tt_pop_td3_destroy", "tt_pop_td3_hyper"
 
-    def __init__(self, agents, batch_size, rings, seeds, noise_seeds=None, fc2_images=None):
+    def __init__(self, agents, batch_size, rings, seeds, noise_seeds=None, fc2_images=None, grad_clips=None):
         super().__init__(agents, batch_size, rings, seeds)
+        if grad_clips is not None:         # (refused by name: the per-agent clip is the DDPG population's)
+            from ddpg_trucktrailer_amd.grad_clip import check_population_grad_clip
+            check_population_grad_clip(grad_clips, self.K, td3=[getattr(ag, "td3", True) for ag in agents])
         if noise_seeds is not None and len(noise_seeds) != self.K:
             raise ValueError("one noise seed per agent")
         if any(getattr(ag, "td3", None) is None for ag in agents):

@@ -771,6 +771,37 @@ int tt_pop_exploit_nstep(tt_population *pop, int pairs, const tt_pop_exploit_pai
                          const struct tt_pop_nstep *ns /*[pairs], host*/, tt_stream_t stream);
 int tt_pop_nstep(tt_population *pop, int agent, struct tt_pop_nstep *out);
 
+/* Gradient-norm clipping in a population: each agent clips each of its two networks with ITS OWN max_norm (tt_grad_clip's formula:
+ * norm = sqrt(sum of squares over the network's gradient), coef = max_norm / (norm + 1e-6), 1 where that is greater; the optimizer
+ * sees coef * grad), in shared launches (csrc/ttclip.hip: k_pop_grad_sqnorm, K x TT_GRAD_CLIP_PARTIALS workgroups, and
+ * k_pop_adam_soft_clip, K x the workgroups of tt_adam_soft_update).  The library keeps a per-agent table {max_norm critic, max_norm
+ * actor} in device memory, with the norms' partial sums, out = {norm, coef} and counts = {updates, updates with coef < 1} per agent
+ * and network.
+ *   max_norm    a finite number > 0, or 0: this agent does not clip this network -- coef is 1 by definition, whatever the norm (a
+ *               NaN norm does not reach it); the norm is still reported
+ * tt_pop_learn_set_clip (synchronous: it waits for the device; call it before any capture) makes the table and the buffers on
+ * first use, writes every agent's entry and switches the optimizer step off inside the weight-gradient launches.  FROM THEN ON
+ * tt_pop_learn is eight launches, also when every value is 0: the draw and the forwards, the rows, the critic's weight gradients,
+ * the critic's norm, the critic's clipped step, the actor tail (gradients only), the actor's norm, the actor's clipped step.  A
+ * later change of a value changes no launch, so a captured graph stays valid.  A population on which it was never called launches
+ * exactly its four kernels.  It composes with tt_pop_learn_set_nstep in either order.
+ * Agent a's results, on the same draw: with a non-zero value, the bits of the lone separate-optimizer chain with
+ * tt_adam_soft_update_clipped at the clipped network(s); with {0, 0}, the bits of that chain with tt_adam_soft_update at both.
+ * The step sizes, tau, the step count and the fc2 images are read from the descriptors, so tt_pop_exploit's writes take effect.
+ * tt_pop_clip_write enqueues ONE small launch on `stream` that writes values[i] into agents[i]'s entry (capturable; after
+ * tt_pop_exploit on the same stream, the clip travels with the weights it was tuned on).  tt_pop_clip reads agent a's entry,
+ * out[4] = {norm, coef} of the critic then the actor and counts[4] = {updates, clipped} likewise back from the device (synchronous).
+ * TT_EINVAL with a message naming the entry point and the agent or entry, before any HIP call: a NULL handle or array; a negative,
+ * NaN or infinite value; count outside [1, K]; an agent out of range or listed twice; tt_pop_clip_write / tt_pop_clip without a
+ * table.  Not supported: TD3 populations (tt_pop_td3_*). */
+struct tt_pop_clip {         /* (a tag without a typedef: the read-back function below has the same name) */
+    float max_norm_critic, max_norm_actor;
+};
+int tt_pop_learn_set_clip(tt_population *pop, const struct tt_pop_clip *per_agent /*[K], host*/);
+int tt_pop_clip_write(tt_population *pop, int count, const int32_t *agents /*[count], host*/,
+                      const struct tt_pop_clip *values /*[count], host*/, tt_stream_t stream);
+int tt_pop_clip(tt_population *pop, int agent, struct tt_pop_clip *value, float out[4], int64_t counts[4]);
+
 /* ------------------------------------------------------------------------------------------------------
  * Learn log: one record per learn() update and agent -- the losses, the Q / TD-target / dQ/da / mu statistics and the two gradient
  * norms of that update -- reduced ON THE DEVICE by one launch (csrc/ttlearnlog.hip: k_learn_log) from the buffers learn() leaves

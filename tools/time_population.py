@@ -17,7 +17,13 @@ the no-table path is held to.
 and policy_delay DELAY (default 2: critic-only and full updates in alternation, the average update), beside the lone TD3Learner
 (tools/td3_cost.py's leg), all timed the same way in alternating legs; every leg is printed and, with --out, written to a file.
 Section 13's rule at K = 1: is the population's median within the lone median plus the lone legs' own max - min?
+--grad-clip C[,A]: instead of all that, what per-agent gradient-norm clipping costs: at K in {1, 4, 8}, us per
+population update and agent-updates/s of the population without a clip table (two populations, two series), with a table of
+zeros, and with max_norm C for every critic and A for every actor (0 or missing: not clipped), the variants interleaved within each
+leg; with --baseline-lib PATH that library's population without a table as well, twice.  With --loop-steps N > 0 and not --no-loop,
+then the K = 8 x 8192-env loop at 8 updates per step, without the option (this library and the baseline, alternating) and with it.
 Usage: time_population.py [--legs 5] [--updates 1000] [--no-loop] [--loop-steps 60] [--n-step N [--ks 1,4,8] [--baseline-lib PATH]]
+       time_population.py --grad-clip C[,A] [--ks 1,4,8] [--baseline-lib PATH] [--legs 3] [--no-loop] [--out FILE]
        time_population.py --td3 [DELAY] [--legs 3] [--updates 1000] [--per-graph 100] [--out profiles/population_td3_scaling.txt]"""
 import argparse
 import ctypes as C
@@ -127,6 +133,102 @@ def nstep_cost(a):
                 pop._h = None
 
 
+def _clip_pair(text):
+    from ddpg_trucktrailer_amd.grad_clip import clip_of_values
+    parts = [float(x) for x in text.split(",")]
+    if not 1 <= len(parts) <= 2:
+        raise argparse.ArgumentTypeError(f"--grad-clip {text!r}: C or C,A")
+    c, a = parts[0], parts[1] if len(parts) > 1 else 0.0
+    if clip_of_values(c, a) is None:
+        raise argparse.ArgumentTypeError(f"--grad-clip {text!r}: at least one value above 0")
+    return c, a
+
+
+def _other_library(path):
+    base = C.CDLL(path)
+    for name in ("tt_pop_learn_create", "tt_pop_learn", "tt_pop_learn_destroy", "tt_last_error"):
+        getattr(base, name).restype, getattr(base, name).argtypes = L._SIGNATURES[name]
+    return base
+
+
+def clip_cost(a):
+    """--grad-clip: the variants of one K are timed back to back within a leg, their order alternating from leg to leg."""
+    from ddpg_trucktrailer_amd.grad_clip import clip_of_values
+    Ks, clip = tuple(a.ks), clip_of_values(*a.grad_clip)
+    replays = max(1, -(-a.updates // a.per_graph))
+    base = _other_library(a.baseline_lib) if a.baseline_lib else None
+    label = f"clip {a.grad_clip[0]:g}, {a.grad_clip[1]:g}"
+    variants = [("no table", None, None), ("no table again", None, None), ("a table of zeros", "zeros", None), (label, clip, None)]
+    if base is not None:       # (made alternately with this library's populations: placement in memory is part of the spread)
+        variants = [("baseline library", None, base), variants[0], ("baseline library again", None, base)] + variants[1:]
+    lines, pops = [], {}
+    for K in Ks:
+        for name, what, lib in variants:
+            pop = PopulationLearner([agent(100 + i) for i in range(K)], B, rings=[ring(200 + i) for i in range(K)],
+                                    seeds=[300 + i for i in range(K)], grad_clips=None if what in (None, "zeros") else what)
+            if lib is not None:
+                pop.lib = lib              # (the descriptors are made at the first learn(): by this library)
+            if what == "zeros":            # (Python makes no table without a value: through the entry point)
+                pop._create()
+                pop._key = pop._storage_key()
+                L.check(pop.lib.tt_pop_learn_set_clip(pop._h, (L.TTPopClip * K)()))
+                pop.clip_table = True
+            pops[K, name] = (pop, captured(pop.learn, a.per_graph))
+    res = {key: [] for key in pops}
+    for leg in range(a.legs):
+        for K in (Ks if leg % 2 == 0 else Ks[::-1]):
+            for name, _, _ in (variants if leg % 2 == 0 else variants[::-1]):
+                res[K, name].append(timed(pops[K, name][1], replays) / (replays * a.per_graph))
+    lines.append(f"# learn() alone, B = {B}, {replays * a.per_graph} graph-replayed updates per leg, {a.legs} legs (variants interleaved, "
+                 f"order alternating), rings of 16 slots x 2048 envs, 5 % done flags")
+    lines.append(f"# device {torch.cuda.get_device_name(0)}")
+    lines.append(f"{'K':>3} {'variant':>24} {'us/pop update':>14} {'spread':>16} {'agent-updates/s':>16} {'vs no table':>12}  legs")
+    for K in Ks:
+        ref = statistics.median(res[K, "no table"])
+        for name, what, lib in variants:
+            pop, x = pops[K, name][0], res[K, name]
+            assert pop.tail_gave_up() == [0] * K
+            m = statistics.median(x)
+            lines.append(f"{K:3d} {name:>24} {m:14.2f} {min(x):7.2f}-{max(x):7.2f} {K * 1e6 / m:16.3e} {m - ref:+12.2f}  " +
+                         " ".join(f"{v:.2f}" for v in x))
+            if what not in (None, "zeros"):
+                st = pop.clip_stats(0)
+                lines.append(f"#   agent 0: {st}")
+            if lib is not None:            # its handle has that library's layout: it goes the way it came
+                torch.cuda.synchronize()
+                lib.tt_pop_learn_destroy(pop._h)
+                pop._h = None
+    if not a.no_loop and a.loop_steps > 0:
+        lines.append("")
+        lines.append(f"# the loop, K = 8 x n = 8192 envs, 8 updates per step, {a.loop_steps} graph-replayed vector steps after setup, per variant")
+        loops = [("no table", None, None), (label, clip, None)]
+        if base is not None:
+            loops = [("baseline library", None, base), loops[0], ("baseline library again", None, base), ("no table again", None, None), loops[1]]
+        for name, what, lib in loops:
+            lp = PopulationRollout(8192, [11 + i for i in range(8)], batch_size=B, replay_slots=64, updates_per_step=8, graph_steps=20,
+                                   grad_clip=what)
+            if lib is not None:
+                lp.learner.lib = lib
+            lp.run(24)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            lp.run(a.loop_steps)
+            torch.cuda.synchronize()
+            dt = (time.perf_counter() - t0) / a.loop_steps
+            lines.append(f"{name:>24} {dt * 1e3:8.3f} ms/step  {8 * 8192 / dt:10.3e} env-steps/s  {64 / dt:10.3e} agent-updates/s")
+            if what is not None:
+                lines.append(f"#   agent 0: {lp.clip_stats(0)}")
+            if lib is not None:
+                lp.invalidate_graphs()
+                lib.tt_pop_learn_destroy(lp.learner._h)
+                lp.learner._h = None
+            del lp
+    print("\n".join(lines))
+    if a.out:
+        with open(a.out, "a") as f:
+            f.write("\n".join(lines) + "\n\n")
+
+
 def td3_scaling(a):
     """--td3: us per population update and agent-updates/s of TD3 populations, and the lone TD3Learner beside them."""
     from ddpg_trucktrailer_amd.td3 import PopulationTD3Learner, TD3Config, TD3Learner
@@ -184,10 +286,13 @@ def main():
     ap.add_argument("--baseline-lib", default=None)
     ap.add_argument("--ks", type=lambda t: [int(x) for x in t.split(",")], default=[1, 4, 8], help="with --n-step: the K values")
     ap.add_argument("--td3", type=int, nargs="?", const=2, default=None, help="TD3 populations at this policy_delay (default 2)")
-    ap.add_argument("--out", default=None, help="with --td3: also write the table to this file")
+    ap.add_argument("--out", default=None, help="with --td3: also write the table to this file; with --grad-clip: append it")
+    ap.add_argument("--grad-clip", type=_clip_pair, default=None, help="C[,A]: what per-agent gradient clipping costs")
     a = ap.parse_args()
     if a.td3 is not None:
         return td3_scaling(a)
+    if a.grad_clip is not None:
+        return clip_cost(a)
     if a.n_step is not None:
         return nstep_cost(a)
     Ks = (1, 2, 4, 8, 16)

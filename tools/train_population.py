@@ -9,6 +9,10 @@ training (pbt.py) -- after each block, the records just drained go to the contro
 bottom agents copy a top agent's networks and optimizer state and perturb its hyperparameters; one line per decision
 (--pbt-quantile, default 0.25; --pbt-metric return | success, default return).  --n-step N[,N...]: n-step returns, one n for all
 agents or one per agent; with --pbt, --pbt-n-steps a,b,c lets the controller move an agent's n among those choices.
+--grad-clip C[,A][:C[,A]...]: per-agent gradient-norm clipping (PopulationRollout(grad_clip=)): max_norm C of
+the critic and A of the actor (0 or missing: that network is not clipped), one entry for all agents or K entries separated by
+colons; each agent's line then adds "clipped x of y" per network, the block's updates with a coefficient below 1.  With --pbt,
+--pbt-clip LO,HI lets the controller multiply a copied clip by one of the two factors (PBT(clip_factors=)).  Not with --td3.
 --learn-log EVERY: the learn log (PopulationRollout(learn_log=...)), one record per agent and EVERY updates; each agent's line adds
 the latest record's critic loss, actor loss, Q mean, |TD| mean and both gradient norms, and the block's non-finite total.
 --td3 [DELAY[,SIGMA[,CLIP]]]: a population of TD3 agents (PopulationRollout(td3=TD3Config(...)); defaults 2, 0.2, 0.5), with the
@@ -24,7 +28,7 @@ bit, to the vector_steps given: the other positional arguments and the options m
 shape is refused), --eval-every keeps its phase, and one line says from which vector step the run continues.  With --objectives
 the 100-episode objective averages start empty after a resume (RunningObjectives is not in the file).
 Usage: train_population.py [--objectives] [--n-step N[,N...]] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]]
-       [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c]] [--eval-every R --eval-lanes M [--pbt-on-eval]]
+       [--grad-clip C[,A][:C[,A]...]] [--pbt READY [--pbt-quantile Q] [--pbt-metric M] [--pbt-n-steps a,b,c] [--pbt-clip LO,HI]] [--eval-every R --eval-lanes M [--pbt-on-eval]]
        [--checkpoint PATH [--save-every BLOCKS]] [--resume PATH]
        K n_envs_per_agent ring_slots updates_per_step batch vector_steps report_every [first_seed [graph_steps]]"""
 import os
@@ -58,6 +62,21 @@ _ints = lambda text: [int(x) for x in text.split(",")]
 n_step = _option("--n-step", _ints, [1])
 pbt_n_steps = _option("--pbt-n-steps", _ints)
 learn_every = _option("--learn-log", int)
+
+
+def _clips(text):
+    from ddpg_trucktrailer_amd.grad_clip import clip_of_values
+    out = []
+    for entry in text.split(":"):
+        parts = [float(x) for x in entry.split(",")]
+        if not 1 <= len(parts) <= 2:
+            sys.exit(f"--grad-clip {text!r}: an entry is C or C,A")
+        out.append(clip_of_values(parts[0], parts[1] if len(parts) > 1 else 0.0))
+    return out
+
+
+grad_clip = _option("--grad-clip", _clips)
+pbt_clip = _option("--pbt-clip", lambda text: tuple(float(x) for x in text.split(",")))
 eval_every = _option("--eval-every", int)
 eval_lanes = _option("--eval-lanes", int, 256)
 checkpoint_path = _option("--checkpoint", str)
@@ -79,6 +98,8 @@ for at, arg in enumerate(sys.argv):
         break
 if pbt_n_steps is not None and pbt_ready is None:
     sys.exit("--pbt-n-steps needs --pbt")
+if pbt_clip is not None and (pbt_ready is None or grad_clip is None):
+    sys.exit("--pbt-clip needs --pbt and --grad-clip")
 if pbt_on_eval and (pbt_ready is None or eval_every is None):
     sys.exit("--pbt-on-eval needs --pbt and --eval-every")
 if save_every is not None and (checkpoint_path is None or save_every < 1):
@@ -92,13 +113,18 @@ if n_step != [1] or pbt_n_steps is not None:
     nstep_kw["n_step"] = n_step * K if len(n_step) == 1 else n_step      # (a list: the population keeps an n-step table)
     if pbt_n_steps is not None:
         nstep_kw["n_step_max"] = max(pbt_n_steps + n_step)
+if grad_clip is not None:
+    if len(grad_clip) not in (1, K):
+        sys.exit(f"--grad-clip: one entry for all agents or {K}, not {len(grad_clip)}")
+    nstep_kw["grad_clip"] = grad_clip * K if len(grad_clip) == 1 else grad_clip
 pop = PopulationRollout(n, seeds, batch_size=batch, replay_slots=slots, updates_per_step=upd, graph_steps=graph_steps,
                         episode_log=min(n * every, 1 << 24), episode_log_detail=detail,
                         # the log holds a report block's records: one per learn_every updates
                         learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
                         learn_log_every=learn_every or 1, td3=td3, **nstep_kw)
 print(f"K = {K} agents x N = {n} envs, ring {slots} steps, {upd} learn() per vector step = {n / upd:.1f} env-steps per update "
-      f"per agent, batch {batch}, seeds {seeds}, n_step {pop.n_steps}" + (f", {td3}" if td3 is not None else ""), flush=True)
+      f"per agent, batch {batch}, seeds {seeds}, n_step {pop.n_steps}" + (f", {td3}" if td3 is not None else "")
+      + (f", max_norm [critic, actor] {pop.grad_clips}" if pop.clip_table else ""), flush=True)
 for a, ag in enumerate(pop.agents):       # each agent saves its best networks into a directory of its own
     d = os.path.join("tmp", "ddpg", f"seed{seeds[a]}")
     os.makedirs(d, exist_ok=True)
@@ -116,16 +142,32 @@ def learn_line(rec):
             f"actor {rec['grad_norm_actor'][-1]:.4g}  non-finite {bad}" + (f"  ({rec['dropped']} records overwritten)" if rec["dropped"] else ""))
 
 
+clip_seen = [{"critic": (0, 0), "actor": (0, 0)} for _ in range(K)]
+
+
+def clip_line(a):
+    """Agent a's clipped updates of the block per network, from the device's counts (they start again with a resumed handle)."""
+    st, parts = pop.clip_stats(a), []
+    for key in ("critic", "actor"):
+        now = (st[key]["clipped"], st[key]["updates"])
+        was = clip_seen[a][key] if clip_seen[a][key][1] <= now[1] else (0, 0)
+        clip_seen[a][key] = now
+        parts.append(f"{key} clipped {now[0] - was[0]} of {now[1] - was[1]} (max_norm {pop.grad_clips[a][key == 'actor']:.4g}, "
+                     f"last |grad| {st[key]['norm']:.4g})")
+    return "  " + "  ".join(parts)
+
+
 trackers = [BestModelTracker() for _ in range(K)]
 pbt = None
 if pbt_ready is not None:
     from ddpg_trucktrailer_amd.pbt import PBT  # noqa: E402
     # (ranked on evaluations: all of an evaluation's M records count, whatever an agent's training window holds)
-    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric, n_step_choices=pbt_n_steps,
+    pbt = PBT(K, pbt_ready, seed=seed0, quantile=pbt_quantile, metric=pbt_metric, n_step_choices=pbt_n_steps, clip_factors=pbt_clip,
               **(dict(window=eval_lanes) if pbt_on_eval else {}))
     print(f"PBT: a round every {pbt_ready} vector steps, bottom/top quantile {pbt_quantile}, ranked by {pbt_metric} over the "
           f"last {pbt.window} episodes since an agent's last exploit"
-          + (f", n_step explored among {list(pbt.n_step_choices)}" if pbt_n_steps is not None else ""), flush=True)
+          + (f", n_step explored among {list(pbt.n_step_choices)}" if pbt_n_steps is not None else "")
+          + (f", a copied clip times one of {list(pbt.clip_factors)}" if pbt_clip is not None else ""), flush=True)
 running = [RunningObjectives() for _ in range(K)] if detail else None
 evaluator = None
 if eval_every is not None:
@@ -169,7 +211,8 @@ while s < total:
         print(f"agent {a} seed {seeds[a]}  vector steps {s:7d} ({s * n:.2e} env-steps): episodes {m:7d}  "
               f"mean return {r['ret'].sum().item() / e:9.1f}  successes {int(r['success'].sum().item()):6d}  "
               f"avg100 {avg if avg is not None else float('nan'):9.1f}  success100 {rate if rate is not None else float('nan'):5.2f}  "
-              f"{'BEST ' if best else ''}{objs}{lost}{learn_line(learned[a]) if learned is not None else ''}", flush=True)
+              f"{'BEST ' if best else ''}{objs}{lost}{learn_line(learned[a]) if learned is not None else ''}"
+              f"{clip_line(a) if pop.clip_table and pop.learner.has_handle else ''}", flush=True)
         if best:
             pop.agents[a].save_models()
     blocks += 1
