@@ -162,6 +162,23 @@ class TTMpcArgs(C.Structure):
                [(n, C.c_float) for n in ("sigma", "rho", "lambda_", "gamma", "k_lat", "k_yaw", "action_scale")] + [("seed", C.c_uint64)]
 
 
+class TTCurriculum(C.Structure):
+    """tt_curriculum (include/ttenv.h: tt_env_set_curriculum)."""
+    _fields_ = [("nx", C.c_int32), ("ny", C.c_int32), ("nyaw", C.c_int32), ("mode", C.c_int32), ("alpha", C.c_double),
+                ("uniform", C.c_double)]
+
+
+class TTCurriculumArrays(C.Structure):
+    """tt_curriculum_arrays (include/ttenv.h): p f64, seen u64, attempts / successes / q / cum u32, each [C]; cell u32 [npad]."""
+    _fields_ = [(n, C.c_void_p) for n in ("p", "seen", "attempts", "successes", "q", "cum", "cell")]
+
+
+CURRICULUM_MAX_CELLS = 4096             # TT_CURRICULUM_MAX_CELLS
+CURRICULUM_NO_CELL = 0xFFFFFFFF         # TT_CURRICULUM_NO_CELL
+CURRICULUM_MODES = ("frontier", "hard")  # TT_CURRICULUM_FRONTIER, TT_CURRICULUM_HARD
+CURRICULUM_ARRAYS = ("p", "seen", "attempts", "successes", "q", "cum", "cell")
+
+
 class TTLearnLogJob(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("y", "q", "q_pi", "dq_da", "mu", "grad_critic", "grad_actor")] + \
                [("numel_critic", C.c_int32), ("numel_actor", C.c_int32), ("step_dev", C.c_void_p)]
@@ -326,6 +343,10 @@ _SIGNATURES = {
     "tt_pop_learn_set_clip": (C.c_int, [_P, C.POINTER(TTPopClip)]),
     "tt_pop_clip_write": (C.c_int, [_P, _I, C.POINTER(C.c_int32), C.POINTER(TTPopClip), _P]),
     "tt_pop_clip": (C.c_int, [_P, _I, C.POINTER(TTPopClip), C.POINTER(C.c_float * 4), C.POINTER(C.c_int64 * 4)]),
+    "tt_env_set_curriculum": (C.c_int, [_P, C.POINTER(TTCurriculum), C.POINTER(TTCurriculumArrays), _P]),
+    "tt_env_curriculum_update": (C.c_int, [_P, _P]),
+    "tt_env_curriculum_read": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
+    "tt_env_curriculum_write": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

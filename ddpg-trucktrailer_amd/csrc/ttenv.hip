@@ -1566,6 +1566,225 @@ __global__ __launch_bounds__(BLOCK) void k_hold_read(const int n, const int npad
     if (end) { end[i] = h.end[i]; end[N + i] = h.end[S + i]; end[2 * N + i] = h.end[2 * S + i]; }
 }
 
+// ------------------------------------------------------------------------------------------
+// Start-pose curriculum (tt_env_set_curriculum): a grid of C = nx * ny * nyaw cells over the reset box, cell
+// c = (iyaw * ny + iy) * nx + ix, that counts the outcomes of the episodes started in each cell and draws the next start pose by
+// weights made from them.  The kernels get ONE pointer, to this descriptor in device memory (2 SGPRs; the step kernels have none to
+// spare): only a lane that finishes an episode reads it.  Everything that decides a draw is an integer (q, cum)
+// and everything that counts is an integer add, so a run does not depend on the order in which lanes arrive.
+struct CurDev {
+    uint32_t *cell;                 // [npad] the cell a lane's running episode was drawn from, TT_CURRICULUM_NO_CELL: none
+    uint32_t *cum;                  // [C] the inclusive prefix sum of q
+    uint32_t *attempts, *successes; // [C] counts since the last update
+    int C, nx, ny, nyaw;
+    uint32_t *q;                    // [C] draw weight in [1, 65536]
+    double *p;                      // [C] running success rate
+    unsigned long long *seen;       // [C] episodes ever counted
+    int mode, reserved_;
+    double alpha, uniform;
+    double lo[3], width[3];         // reset_lo and (reset_hi - reset_lo) / bins, formed on the host in f64
+    unsigned long long seed;        // the handle's reset seed (k_curriculum_seed): the step kernels read it here, in the path that
+                                    // needs it, not from their argument (two SGPRs less across step_env)
+};
+
+// The draw: random_pose's Philox words; r[3] picks the cell -- t = (r[3] * cum[C - 1]) >> 32, the smallest c with cum[c] > t --
+// and r[0..2] the pose inside it.  f64 with contraction off (as tally_append): a host model equals it bit for bit.  The search
+// stays inside [0, C) whatever cum holds.
+__device__ __forceinline__ void curriculum_pose(const CurDev *cur, uint64_t seed, uint32_t env, uint32_t episode, double &sx,
+                                                double &sy, double &syaw) {
+#pragma clang fp contract(off)
+    uint32_t r[4];
+    philox4x32(env, episode, 0u, 0x7452u, (uint32_t)seed, (uint32_t)(seed >> 32), r);
+    const uint32_t *cum = cur->cum;
+    const int C = cur->C;
+    const uint32_t t = (uint32_t)(((unsigned long long)r[3] * (unsigned long long)cum[C - 1]) >> 32);
+    // the number of cells with cum <= t, by halving steps without a branch (C <= 4096: twelve); t < cum[C - 1] keeps it below C
+    uint32_t lo = 0u;
+#pragma unroll
+    for (uint32_t s = TT_CURRICULUM_MAX_CELLS / 2; s > 0u; s >>= 1) {
+        const uint32_t j = lo + s;      // would cells [0, j) all have cum <= t?
+        const uint32_t v = cum[min(j, (uint32_t)C) - 1u];
+        lo = (j <= (uint32_t)C && v <= t) ? j : lo;
+    }
+    lo = min(lo, (uint32_t)C - 1u);     // (only a cum that is no prefix sum of positive weights gets here)
+    const uint32_t c = lo, nx = (uint32_t)cur->nx, ny = (uint32_t)cur->ny;
+    // c / nx and rest / ny as floor((a + 0.5) * rcp(b)) in f32: exact for a < 4096 (the nearest integer boundary is 0.5 / b away, a
+    // relative 1.2e-4 at the least, against the 2.4e-7 of the reciprocal and the product), and a tenth of an integer division's code
+    const uint32_t rest = (uint32_t)(((float)c + 0.5f) * __builtin_amdgcn_rcpf((float)nx)), ix = c - rest * nx;
+    const uint32_t iyaw = (uint32_t)(((float)rest + 0.5f) * __builtin_amdgcn_rcpf((float)ny)), iy = rest - iyaw * ny;
+    const double k = 1.0 / 4294967296.0;
+    const double u0 = ((double)r[0] + 0.5) * k, u1 = ((double)r[1] + 0.5) * k, u2 = ((double)r[2] + 0.5) * k;
+    sx = cur->lo[0] + ((double)ix + u0) * cur->width[0];
+    sy = cur->lo[1] + ((double)iy + u1) * cur->width[1];
+    syaw = cur->lo[2] + ((double)iyaw + u2) * cur->width[2];
+    cur->cell[env] = c;
+}
+
+// Head of the curriculum's step kernels, behind TT_STEP_HEAD: the descriptor's address and the address of the lane's episode number
+// into VECTOR registers, at the kernel's head (the empty asm pins them there: the compiler neither keeps the scalars nor forms the
+// addresses again later).  The step kernels' loop variants sit at their SGPR limit across step_env and have vector registers to
+// spare.  With the two held as scalars until the reset, the allocator split the tuple of kernel arguments that holds Bufs and left
+// a stack slot behind: 36 B of scratch that no instruction touches, but that every dispatch has to be given.  The descriptor's words
+// then arrive by vector loads, in the one path that reads them.  Declares cur and ep_ptr.
+#define TT_STEP_CUR()                                                                                                                   \
+    uint32_t cur_lo = (uint32_t)reinterpret_cast<uintptr_t>(cur_arg), cur_hi = (uint32_t)(reinterpret_cast<uintptr_t>(cur_arg) >> 32);  \
+    asm volatile("" : "+v"(cur_lo), "+v"(cur_hi));                                                                                      \
+    const CurDev *cur = reinterpret_cast<const CurDev *>(((uintptr_t)cur_hi << 32) | (uintptr_t)cur_lo);                               \
+    uint32_t *ep_ptr = b.episodes + i;                                                                                                  \
+    asm volatile("" : "+v"(ep_ptr))
+// Reset with the curriculum on (TT_STEP_RESET's place in k_step_cur / k_step_cur_log; auto-reset always): the finished episode is
+// counted in the cell it was drawn from -- one relaxed agent-scope u32 add to attempts[cell], one more to successes[cell] on success
+// (the episode log's test) -- BEFORE the draw overwrites the lane's cell; a lane whose episode no curriculum draw made (cell outside
+// [0, C)) counts nothing.
+#define TT_STEP_RESET_CURRICULUM()                                                                                                      \
+    /* (tests side by side, not nested: every level of divergent nesting holds an exec mask in two more SGPRs) */                       \
+    uint32_t cl = TT_CURRICULUM_NO_CELL, ncell = 0u;                                                                                    \
+    if (o.done) {                                                                                                                       \
+        cl = cur->cell[i];                                                                                                              \
+        ncell = (uint32_t)cur->C;                                                                                                       \
+    }                                                                                                                                   \
+    if (cl < ncell) __hip_atomic_fetch_add(cur->attempts + cl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                         \
+    if (cl < ncell && o.final_bonus > 0.0) __hip_atomic_fetch_add(cur->successes + cl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); \
+    if (o.done) {                                                                                                                       \
+        const uint32_t ep = *ep_ptr + 1u;                                                                                               \
+        *ep_ptr = ep;                                                                                                                   \
+        double sx, sy, syaw;                                                                                                            \
+        curriculum_pose(cur, cur->seed, (uint32_t)i, ep, sx, sy, syaw);                                                                 \
+        const Goal g0{P.gx, P.gy, P.sg, P.cg};                                                                                          \
+        place_env(P, b, i, e, sx, sy, syaw, g0, P.gyaw, e.L2, of);                                                                      \
+    }                                                                                                                                   \
+    store_env(b, i, e)
+
+// k_step with the curriculum on: k_step's text with the curriculum's reset piece.  A kernel of its own for k_step_log's reason (a
+// fifth template argument would rename every k_step variant); the curriculum's pointer travels in this kernel's last argument, and
+// KParams and Bufs keep their layout.
+template <bool PER_ENV, bool INFO, bool RANDOM_POLICY>
+__global__ __launch_bounds__(BLOCK) void k_step_cur(const KParams P, const int n, const Bufs b,
+                                                    const float *__restrict__ action, float *__restrict__ action_out,
+                                                    float *__restrict__ obs, float *__restrict__ reward,
+                                                    uint8_t *__restrict__ done, const Info info, const uint64_t seed,
+                                                    const uint64_t policy_seed, const int *__restrict__ cursor,
+                                                    const CurDev *cur_arg) {
+    __shared__ __attribute__((aligned(16))) float tile[BLOCK * OBS];
+    TT_STEP_HEAD();
+    TT_STEP_CUR();
+    if (valid) {
+        TT_STEP_LOADS();
+        __builtin_amdgcn_sched_barrier(0);
+        TT_STEP_ACT();
+        StepOut o;
+        step_env(P, e, a, of, o);
+        TT_STEP_OUT();
+        TT_STEP_RESET_CURRICULUM();
+    }
+    store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
+}
+
+// ... and k_step_log with the curriculum on: the same pieces in k_step_log's order
+template <bool PER_ENV, bool INFO, bool RANDOM_POLICY>
+__global__ __launch_bounds__(BLOCK) void k_step_cur_log(const KParams P, const int n, const Bufs b,
+                                                        const float *__restrict__ action, float *__restrict__ action_out,
+                                                        float *__restrict__ obs, float *__restrict__ reward,
+                                                        uint8_t *__restrict__ done, const Info info, const uint64_t seed,
+                                                        const uint64_t policy_seed, const int *__restrict__ cursor,
+                                                        const EpLog lg, const CurDev *cur_arg) {
+    __shared__ __attribute__((aligned(16))) float tile[BLOCK * OBS];
+    TT_STEP_HEAD();
+    TT_STEP_CUR();
+    if (valid) {
+        TT_STEP_LOADS();
+        double ret = lg.acc[i];
+        __builtin_amdgcn_sched_barrier(0);
+        TT_STEP_ACT();
+        StepOut o;
+        step_env(P, e, a, of, o);
+        TT_STEP_OUT();
+        TT_STEP_RETURN();
+        TT_STEP_RESET_CURRICULUM();
+        log_append(lg, i, o.done, o.flags, o.final_bonus > 0.0, len, ret);
+    }
+    store_obs_tile(tile, of, valid, obs, block_first, nv, P.nt != 0);
+    TT_STEP_LAUNCH_COUNT();
+}
+
+// k_reset with the curriculum on (k_reset keeps its text): the same reset, the pose from the curriculum's draw
+__global__ __launch_bounds__(BLOCK) void k_reset_curriculum(const KParams P, const int n, const Bufs b, const uint8_t *mask,
+                                                            float *obs, const uint64_t seed, const CurDev *cur) {
+    const int i = blockIdx.x * BLOCK + threadIdx.x;
+    if (i >= n || (mask && !mask[i])) return;
+    const uint32_t ep = mask ? b.episodes[i] + 1u : 0u;
+    b.episodes[i] = ep;
+    double sx, sy, syaw;
+    curriculum_pose(cur, seed, (uint32_t)i, ep, sx, sy, syaw);
+    float of[OBS];
+    const Goal g{P.gx, P.gy, P.sg, P.cg};
+    Env e;
+    place_env(P, b, i, e, sx, sy, syaw, g, P.gyaw, b.cold[C_L2 * (size_t)P.npad + i], obs ? of : nullptr);
+    store_env(b, i, e);
+    if (obs)
+        for (int j = 0; j < OBS; ++j) obs[(size_t)i * OBS + j] = of[j];
+}
+
+// the reset seed into the descriptor (tt_env_reset, tt_env_import; one thread)
+__global__ void k_curriculum_seed(CurDev *cur, const uint64_t seed) { cur->seed = seed; }
+
+// lanes placed from outside (tt_env_set_pose, tt_env_set_state): their episode is no curriculum draw's.  Entry j < k names lane
+// idx[j] (idx NULL: lane j), as k_log_zero's
+__global__ __launch_bounds__(BLOCK) void k_curriculum_unset(const int n, const int k, const int32_t *idx, uint32_t *cell) {
+    const int j = blockIdx.x * BLOCK + threadIdx.x;
+    if (j >= k) return;
+    const int i = idx ? idx[j] : j;
+    if (i < 0 || i >= n) return;
+    cell[i] = TT_CURRICULUM_NO_CELL;
+}
+
+// The update (tt_env_curriculum_update): ONE workgroup, thread t owns the cells [t * per, (t + 1) * per), per = ceil(C / BLOCK) <=
+// 16.  Per cell with n = attempts > 0: p <- (1 - alpha) p + alpha (s / n), seen += n, both counters 0.  Then for every cell
+// f = 4 p (1 - p) (frontier) or 1 - p (hard), w = u + (1 - u) f, q = min(65536, 1 + floor(65535 w)), and cum = the inclusive scan of
+// q: each thread's sum, a scan of the BLOCK sums through LDS, each thread's cells again.  f64 elementwise with contraction off, the
+// scan in integers (C * 65536 <= 2^28): a pure function of its inputs.
+__global__ __launch_bounds__(BLOCK) void k_curriculum_update(const CurDev *cur) {
+#pragma clang fp contract(off)
+    __shared__ uint32_t part[BLOCK];
+    const int C = cur->C, tid = threadIdx.x;
+    const int per = (C + BLOCK - 1) / BLOCK;
+    const int first = min(C, tid * per), last = min(C, first + per);
+    const double alpha = cur->alpha, u = cur->uniform;
+    const bool hard = cur->mode == TT_CURRICULUM_HARD;
+    uint32_t sum = 0u;
+    for (int c = first; c < last; ++c) {
+        double p = cur->p[c];
+        const uint32_t na = cur->attempts[c];
+        if (na > 0u) {
+            const uint32_t s = cur->successes[c];
+            p = (1.0 - alpha) * p + alpha * ((double)s / (double)na);
+            cur->p[c] = p;
+            cur->seen[c] += (unsigned long long)na;
+            cur->attempts[c] = 0u;
+            cur->successes[c] = 0u;
+        }
+        const double f = hard ? 1.0 - p : 4.0 * p * (1.0 - p);
+        const double w = u + (1.0 - u) * f;
+        const double x = floor(w * 65535.0);
+        const uint32_t q = x >= 65535.0 ? 65536u : (x >= 1.0 ? 1u + (uint32_t)x : 1u);       // (also for a p outside [0, 1] or NaN)
+        cur->q[c] = q;
+        sum += q;
+    }
+    part[tid] = sum;
+    __syncthreads();
+    for (int d = 1; d < BLOCK; d <<= 1) {
+        const uint32_t v = tid >= d ? part[tid - d] : 0u;
+        __syncthreads();
+        part[tid] += v;
+        __syncthreads();
+    }
+    uint32_t run = part[tid] - sum;
+    for (int c = first; c < last; ++c) {
+        run += cur->q[c];
+        cur->cum[c] = run;
+    }
+}
+
 char g_err[tthost::ERR_BYTES] = "";
 
 }  // namespace
@@ -1591,6 +1810,11 @@ struct tt_env {
     EpLog log{};
     uint32_t log_flags = 0;     // TT_LOG_DETAIL: the detailed log (k_step_tally)
     void *hold_block = nullptr; // evaluation block (tt_env_set_hold; hold_cols), nullptr <=> off
+    // start-pose curriculum (tt_env_set_curriculum): the descriptor in device memory (followed, in the same block, by the arrays
+    // the handle owns) and its host copy; cur_dev == nullptr <=> off
+    void *cur_block = nullptr;
+    CurDev *cur_dev = nullptr;
+    CurDev cur{};
     char err[tthost::ERR_BYTES] = "";
 };
 
@@ -1601,6 +1825,16 @@ __attribute__((format(printf, 3, 4))) int fail(tt_env *e, int code, const char *
     va_start(ap, fmt);
     tthost::vfail(e ? e->err : g_err, code, fmt, ap);
     va_end(ap);
+    return code;
+}
+
+// a refusal that reads the handle, left where both tt_last_error(env) and tt_last_error(NULL) find it (tthost::fail's message)
+__attribute__((format(printf, 3, 4))) int fail_both(tt_env *e, int code, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    tthost::vfail(g_err, code, fmt, ap);
+    va_end(ap);
+    if (e) std::memcpy(e->err, g_err, tthost::ERR_BYTES);
     return code;
 }
 
@@ -1687,7 +1921,11 @@ void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_
         hipExtLaunchKernelGGL(kernel, g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b, action, action_out, obs, reward, done, info, e->seed,
                               policy_seed, cursor, log...);
     };
-    if (e->log_flags & TT_LOG_DETAIL) {
+    if (e->cur_dev && auto_reset) {     // the curriculum counts and draws where the step resets (never with the detailed log)
+        const CurDev *cur = e->cur_dev;
+        if (e->log_bytes) launch(k_step_cur_log<PER_ENV, INFO, RANDOM_POLICY>, e->log, cur);
+        else launch(k_step_cur<PER_ENV, INFO, RANDOM_POLICY>, cur);
+    } else if (e->log_flags & TT_LOG_DETAIL) {
         if (auto_reset) launch(k_step_tally<PER_ENV, INFO, true, RANDOM_POLICY>, e->log);
         else launch(k_step_tally<PER_ENV, INFO, false, RANDOM_POLICY>, e->log);
     } else if (e->log_bytes) {
@@ -1758,6 +1996,9 @@ int check_counter_range(tt_env *env, const int32_t *values, int k, hipStream_t s
 int set_episode_log(tt_env *env, int64_t capacity, uint32_t flags, hipStream_t stream, const char *fn) {
     if (capacity < 0 || capacity > kLogMaxCapacity)
         return fail(env, TT_EINVAL, "%s: capacity %lld outside [0, %lld]", fn, (long long)capacity, kLogMaxCapacity);
+    if ((flags & TT_LOG_DETAIL) && capacity > 0 && env->cur_dev)
+        return fail_both(env, TT_EINVAL, "%s: the detailed episode log with a curriculum is not supported (the curriculum's step kernels "
+                                         "carry the plain log only); tt_env_set_curriculum(env, NULL, ...) first", fn);
     TT_HIP(env, hipSetDevice(env->device));
     if (env->log_block) {       // launches in flight may still write the old block
         TT_HIP(env, hipStreamSynchronize(stream));
@@ -1784,6 +2025,14 @@ int set_episode_log(tt_env *env, int64_t capacity, uint32_t flags, hipStream_t s
     env->log_flags = flags;
     TT_HIP(env, hipMemsetAsync(blk, 0, bytes, stream));
     if (flags) TT_HIP(env, hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(lg.hdr + LG_DETAIL), (int)flags, 1, stream));
+    return TT_OK;
+}
+
+// lanes placed from outside (entry j < k names lane idx[j], idx NULL: lane j): no curriculum draw made their episode
+int curriculum_unset(tt_env *env, int k, const int32_t *idx, hipStream_t stream) {
+    if (!env->cur_dev) return TT_OK;
+    hipLaunchKernelGGL(k_curriculum_unset, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, idx, env->cur.cell);
+    TT_HIP(env, hipGetLastError());
     return TT_OK;
 }
 
@@ -1916,6 +2165,7 @@ int tt_env_destroy(tt_env *env) {
     if (env->b.episodes) (void)hipFree(env->b.episodes);
     if (env->log_block) (void)hipFree(env->log_block);
     if (env->hold_block) (void)hipFree(env->hold_block);
+    if (env->cur_block) (void)hipFree(env->cur_block);
     for (hipEvent_t ev : env->ev_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : env->ev_stop) (void)hipEventDestroy(ev);
     delete env;
@@ -1927,8 +2177,13 @@ int tt_env_num_envs(const tt_env *env) { return env ? env->n : TT_EINVAL; }
 int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out, tt_stream_t stream) {
     TT_ENTER(env);
     env->seed = seed;
-    hipLaunchKernelGGL(k_reset, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
-                       env->seed);
+    if (env->cur_dev) {
+        hipLaunchKernelGGL(k_curriculum_seed, dim3(1), dim3(1), 0, stream, env->cur_dev, env->seed);
+        hipLaunchKernelGGL(k_reset_curriculum, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
+                           env->seed, (const CurDev *)env->cur_dev);
+    } else
+        hipLaunchKernelGGL(k_reset, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
+                           env->seed);
     TT_HIP(env, hipGetLastError());
     if (env->log_bytes) {       // the reset lanes' episodes start from a zero return (and zero term sums)
         if (mask)
@@ -1942,6 +2197,9 @@ int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out
 int tt_env_set_reset_pool(tt_env *env, const double *pool, int m) {
     TT_HANDLE(env);
     if (m < 0) return fail(env, TT_EINVAL, "tt_env_set_reset_pool: m=%d", m);
+    if (pool && m > 0 && env->cur_dev)
+        return fail_both(env, TT_EINVAL, "tt_env_set_reset_pool: a reset pool with a curriculum is not supported (the curriculum draws "
+                                         "from the reset box); tt_env_set_curriculum(env, NULL, ...) first");
     env->kp.pool_m = pool ? m : 0;
     env->kp.pool = env->kp.pool_m > 0 ? pool : nullptr;
     return TT_OK;
@@ -1958,6 +2216,7 @@ int tt_env_set_pose(tt_env *env, const int32_t *idx, int k, const double *start,
     hipLaunchKernelGGL(k_set_pose, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, idx, k, start, goal,
                        L2, obs_out);
     TT_HIP(env, hipGetLastError());
+    if (const int rc = curriculum_unset(env, k, idx, stream)) return rc;
     if (env->log_bytes) return log_restart(env, k, nullptr, idx, stream);
     return TT_OK;
 }
@@ -1983,7 +2242,7 @@ int tt_env_set_state(tt_env *env, const int32_t *idx, int k, const double *state
     TT_HIP(env, hipSetDevice(env->device));
     hipLaunchKernelGGL(k_set_state, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, env->b, idx, k, state);
     TT_HIP(env, hipGetLastError());
-    return TT_OK;
+    return curriculum_unset(env, k, idx, stream);
 }
 
 int tt_env_get_state(tt_env *env, double *state_out, tt_stream_t stream) {
@@ -2102,6 +2361,10 @@ int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stre
     TT_HIP(env, hipMemcpyAsync(env->b.episodes, src + hb + cb, sizeof(uint32_t) * npad, hipMemcpyDeviceToDevice, stream));
     env->per_env = meta[0] != 0;
     env->seed = meta[1];
+    if (env->cur_dev) {
+        hipLaunchKernelGGL(k_curriculum_seed, dim3(1), dim3(1), 0, stream, env->cur_dev, env->seed);
+        TT_HIP(env, hipGetLastError());
+    }
     return TT_OK;
 }
 
@@ -2226,6 +2489,7 @@ int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float 
     TT_HANDLE(env);
     if (k_steps < 0) return fail(env, TT_EINVAL, "tt_env_rollout_random: k_steps=%d", k_steps);
     if (env->log_bytes) return fail(env, TT_EINVAL, "tt_env_rollout_random: the episode log does not follow k_rollout; disable it first");
+    if (env->cur_dev) return fail(env, TT_EINVAL, "tt_env_rollout_random: the curriculum does not follow k_rollout; turn it off first");
     if (k_steps == 0) return TT_OK;
     TT_HIP(env, hipSetDevice(env->device));
     by_per_env(env, [&](auto per_env) {
@@ -2337,6 +2601,137 @@ int tt_env_mpc_label_ring(tt_env *env, const tt_mpc_args *args, float *plan, int
     });
     TT_HIP(env, hipGetLastError());
     return TT_OK;
+}
+
+// ---- start-pose curriculum (include/ttenv.h: tt_env_set_curriculum)
+static size_t cur_align(size_t x) { return (x + 255) & ~(size_t)255; }
+
+int tt_env_set_curriculum(tt_env *env, const tt_curriculum *cfg, const tt_curriculum_arrays *place, tt_stream_t stream) {
+    const char *const who = "tt_env_set_curriculum";
+    TT_HANDLE(env);
+    long long C = 0;
+    if (cfg) {      // (before the handle is read: these hold for any handle)
+        if (cfg->nx < 1 || cfg->ny < 1 || cfg->nyaw < 1)
+            return tthost::fail(TT_EINVAL, "%s: bins (%d, %d, %d): a bin count below 1", who, cfg->nx, cfg->ny, cfg->nyaw);
+        C = (long long)cfg->nx * cfg->ny * cfg->nyaw;
+        if (C > TT_CURRICULUM_MAX_CELLS)
+            return tthost::fail(TT_EINVAL, "%s: bins (%d, %d, %d) make %lld cells, outside [1, %d]", who, cfg->nx, cfg->ny, cfg->nyaw, C,
+                                TT_CURRICULUM_MAX_CELLS);
+        if (cfg->mode != TT_CURRICULUM_FRONTIER && cfg->mode != TT_CURRICULUM_HARD)
+            return tthost::fail(TT_EINVAL, "%s: unknown mode %d", who, cfg->mode);
+        if (!(cfg->alpha > 0.0 && cfg->alpha <= 1.0)) return tthost::fail(TT_EINVAL, "%s: alpha is outside (0, 1]", who);
+        if (!std::isfinite(cfg->uniform) || !(cfg->uniform >= 0.0 && cfg->uniform <= 1.0))
+            return tthost::fail(TT_EINVAL, "%s: uniform is outside [0, 1] or not finite", who);
+        if (place && (!place->p || !place->seen || !place->attempts || !place->successes || !place->q || !place->cum || !place->cell))
+            return tthost::fail(TT_EINVAL, "%s: place names every array or is NULL", who);
+        if (env->kp.pool_m > 0)
+            return fail_both(env, TT_EINVAL, "%s: a curriculum with a reset pool is not supported (the curriculum draws from the reset "
+                                             "box); tt_env_set_reset_pool(env, NULL, 0) first", who);
+        if (env->log_flags & TT_LOG_DETAIL)
+            return fail_both(env, TT_EINVAL, "%s: a curriculum with the detailed episode log is not supported (the curriculum's step "
+                                             "kernels carry the plain log only)", who);
+        for (int d = 0; d < 3; ++d)
+            if (!(env->params.reset_hi[d] >= env->params.reset_lo[d]))
+                return fail_both(env, TT_EINVAL, "%s: the reset box has reset_hi[%d] < reset_lo[%d]", who, d, d);
+    }
+    TT_HIP(env, hipSetDevice(env->device));
+    if (env->cur_block) {       // launches in flight may still read and write the old block
+        TT_HIP(env, hipStreamSynchronize(stream));
+        TT_HIP(env, hipDeviceSynchronize());
+        TT_HIP(env, hipFree(env->cur_block));
+        env->cur_block = nullptr;
+        env->cur_dev = nullptr;
+        env->cur = CurDev{};
+    }
+    if (!cfg) return TT_OK;
+    const size_t c = (size_t)C, npad = (size_t)env->npad;
+    // the block: the descriptor, then (without `place`) p | seen | attempts | successes | q | cum | cell, each 256-byte aligned
+    const size_t sizes[7] = {sizeof(double) * c, sizeof(unsigned long long) * c, sizeof(uint32_t) * c, sizeof(uint32_t) * c,
+                             sizeof(uint32_t) * c, sizeof(uint32_t) * c, sizeof(uint32_t) * npad};
+    size_t bytes = cur_align(sizeof(CurDev));
+    size_t off[7];
+    for (int a = 0; a < 7; ++a) {
+        off[a] = bytes;
+        if (!place) bytes += cur_align(sizes[a]);
+    }
+    void *blk = nullptr;
+    hipError_t err = hipMalloc(&blk, bytes);
+    if (err != hipSuccess) return fail(env, err == hipErrorOutOfMemory ? TT_ENOMEM : TT_EHIP, "%s: %s", who, hipGetErrorString(err));
+    char *base = static_cast<char *>(blk);
+    CurDev d{};
+    if (place) {
+        d.p = place->p; d.seen = reinterpret_cast<unsigned long long *>(place->seen);
+        d.attempts = place->attempts; d.successes = place->successes; d.q = place->q; d.cum = place->cum; d.cell = place->cell;
+    } else {
+        d.p = reinterpret_cast<double *>(base + off[0]);
+        d.seen = reinterpret_cast<unsigned long long *>(base + off[1]);
+        d.attempts = reinterpret_cast<uint32_t *>(base + off[2]);
+        d.successes = reinterpret_cast<uint32_t *>(base + off[3]);
+        d.q = reinterpret_cast<uint32_t *>(base + off[4]);
+        d.cum = reinterpret_cast<uint32_t *>(base + off[5]);
+        d.cell = reinterpret_cast<uint32_t *>(base + off[6]);
+    }
+    d.nx = cfg->nx; d.ny = cfg->ny; d.nyaw = cfg->nyaw; d.C = (int)C;
+    d.mode = cfg->mode;
+    d.alpha = cfg->alpha; d.uniform = cfg->uniform;
+    d.seed = env->seed;
+    const int bins[3] = {cfg->nx, cfg->ny, cfg->nyaw};
+    for (int k = 0; k < 3; ++k) {
+        d.lo[k] = env->params.reset_lo[k];
+        d.width[k] = (env->params.reset_hi[k] - env->params.reset_lo[k]) / (double)bins[k];
+    }
+    env->cur_block = blk;
+    env->cur = d;
+    // a fresh curriculum: p = 0.5 everywhere, nothing seen or counted, no lane's episode drawn by it; q and cum by the update
+    // itself (no counts: it forms the weights only)
+    const std::vector<double> half(c, 0.5);
+    TT_HIP(env, hipMemcpyAsync(blk, &d, sizeof(d), hipMemcpyHostToDevice, stream));
+    TT_HIP(env, hipMemcpyAsync(d.p, half.data(), sizes[0], hipMemcpyHostToDevice, stream));
+    TT_HIP(env, hipMemsetAsync(d.seen, 0, sizes[1], stream));
+    TT_HIP(env, hipMemsetAsync(d.attempts, 0, sizes[2], stream));
+    TT_HIP(env, hipMemsetAsync(d.successes, 0, sizes[3], stream));
+    TT_HIP(env, hipMemsetAsync(d.cell, 0xFF, sizes[6], stream));
+    hipLaunchKernelGGL(k_curriculum_update, dim3(1), dim3(BLOCK), 0, stream, (const CurDev *)blk);
+    TT_HIP(env, hipGetLastError());
+    TT_HIP(env, hipStreamSynchronize(stream));      // `d` and `half` are temporaries
+    env->cur_dev = static_cast<CurDev *>(blk);
+    return TT_OK;
+}
+
+int tt_env_curriculum_update(tt_env *env, tt_stream_t stream) {
+    TT_HANDLE(env);
+    if (!env->cur_dev) return fail_both(env, TT_EINVAL, "tt_env_curriculum_update: the curriculum is off (tt_env_set_curriculum)");
+    TT_HIP(env, hipSetDevice(env->device));
+    hipLaunchKernelGGL(k_curriculum_update, dim3(1), dim3(BLOCK), 0, stream, (const CurDev *)env->cur_dev);
+    TT_HIP(env, hipGetLastError());
+    return TT_OK;
+}
+
+// tt_env_curriculum_read (to_caller) and tt_env_curriculum_write: device-to-device copies of the arrays the caller names
+static int curriculum_copy(tt_env *env, const tt_curriculum_arrays *a, bool to_caller, hipStream_t stream, const char *who) {
+    if (!env) return tthost::fail(TT_EINVAL, "%s: NULL handle", who);
+    if (!a) return tthost::fail(TT_EINVAL, "%s: NULL argument", who);
+    if (!env->cur_dev) return fail_both(env, TT_EINVAL, "%s: the curriculum is off (tt_env_set_curriculum)", who);
+    TT_HIP(env, hipSetDevice(env->device));
+    const CurDev &d = env->cur;
+    const size_t c = (size_t)d.C;
+    void *mine[7] = {d.p, d.seen, d.attempts, d.successes, d.q, d.cum, d.cell};
+    void *theirs[7] = {a->p, a->seen, a->attempts, a->successes, a->q, a->cum, a->cell};
+    const size_t sizes[7] = {sizeof(double) * c, sizeof(uint64_t) * c, sizeof(uint32_t) * c, sizeof(uint32_t) * c, sizeof(uint32_t) * c,
+                             sizeof(uint32_t) * c, sizeof(uint32_t) * (size_t)env->n};
+    for (int k = 0; k < 7; ++k)
+        if (theirs[k])
+            TT_HIP(env, hipMemcpyAsync(to_caller ? theirs[k] : mine[k], to_caller ? mine[k] : theirs[k], sizes[k], hipMemcpyDeviceToDevice,
+                                       stream));
+    return TT_OK;
+}
+
+int tt_env_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt_stream_t stream) {
+    return curriculum_copy(env, out, true, stream, "tt_env_curriculum_read");
+}
+
+int tt_env_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream) {
+    return curriculum_copy(env, in, false, stream, "tt_env_curriculum_write");
 }
 
 int tt_env_profile(tt_env *env, int max_launches) {

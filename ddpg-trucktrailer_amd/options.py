@@ -1,6 +1,6 @@
 """What the loops' options share: the base of the option values (td3.TD3Config, loss_shape.LossShape,
-demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip) with the validators their constructors use, the one table of
-"not supported with" refusals behind the check_* functions, and the options' entries of a checkpoint.
+demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip, curriculum.Curriculum) with the validators
+their constructors use, the one table of "not supported with" refusals behind the check_* functions, and the options' entries of a checkpoint.
 
     Option                        a value named by its FIELDS: repr, ==, hash, as_tuple(), from_tuple(); a nested Option nests
     finite_number, whole_number   the constructors' tests, with their wording; refuse_value for any other bound
@@ -136,6 +136,20 @@ TABLE = {
         _TD3_LEARN_LOG,
         ("device", lambda c: _device_type(c["device"]) != "cuda", lambda c: f"td3: device = {c['device']!r} is not supported: a population's "
                                                                              "TD3 update exists only as HIP kernels"))),
+    # the env's start-pose curriculum (curriculum.check_curriculum passes expert, labels, device -- None: not known yet -- and
+    # episode_log_detail)
+    "curriculum": dict(what="a curriculum", be="is", population="a population's agents step envs of their own, and a curriculum per agent "
+                                                                "is not built",
+                       rows=("population", "data_parallel", "force_dp",
+                             ("expert", lambda c: c["expert"] is not None,
+                              "a curriculum with expert lanes is not supported (the expert's launch steps and resets its lanes itself)"),
+                             ("labels", lambda c: c["labels"] is not None,
+                              "a curriculum with expert labels is not supported (the planner's launch steps and resets its lanes itself)"),
+                             ("device", lambda c: c["device"] is not None and _device_type(c["device"]) != "cuda",
+                              lambda c: f"a curriculum on device = {c['device']!r} is not supported: it exists only inside the HIP env step"),
+                             ("episode_log_detail", lambda c: c["episode_log_detail"],
+                              "a curriculum with episode_log_detail is not supported (the curriculum's step kernels carry the plain "
+                              "episode log only)"))),
 }
 
 
@@ -151,7 +165,7 @@ def refuse(option, value=None, **context):
 
 
 # ---- the options' entries of a checkpoint: each present option's as_tuple() as a list, under its key
-CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip")
+CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum")
 
 
 def write_options(sd, **options):

@@ -15,11 +15,11 @@ from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 
 
 class VectorStepper:
-    expert = labels = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
+    expert = labels = curriculum = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
 
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
-                 episode_log_detail=False, td3=None, expert=None, labels=None):
+                 episode_log_detail=False, td3=None, expert=None, labels=None, curriculum=None):
         """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold);
         td3: its TD3Config (Agent(td3=)), whose torch path draws its smoothing noise from a generator seeded with `seed`.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
@@ -30,10 +30,19 @@ class VectorStepper:
         their plan [lanes, H].
         labels: None, or an mpc.ExpertLabels: the lanes behind the expert's, [M, M + labels.lanes), act on the
         policy's values as every lane does, and the expert's decision on each of them goes to the ring's label array (enabled
-        here) -- ONE launch, in the expert lanes' place, plans for both kinds of lane, and the stepper owns the plan [M + L, H]."""
+        here) -- ONE launch, in the expert lanes' place, plans for both kinds of lane, and the stepper owns the plan [M + L, H].
+        curriculum: None, or a curriculum.Curriculum, turned on in the env here, before any step or capture: the
+        env step counts every finished episode in the cell it started in and draws the next start pose by the cells' weights; the
+        owner of the stepper calls curriculum_tick() after every vector step it has advanced."""
         self.env, self.n, self.device, self.seed = env, env.n_envs, env.device, seed
         if episode_log:
             env.enable_episode_log(int(episode_log), detail=episode_log_detail)
+        self.curriculum = None
+        if curriculum is not None:
+            from ddpg_trucktrailer_amd.curriculum import check_curriculum
+            self.curriculum = check_curriculum(curriculum, expert=expert, labels=labels, device=env.device,
+                                               episode_log_detail=bool(episode_log) and episode_log_detail)
+            env.enable_curriculum(self.curriculum)
         # the order that decides the bits: the seed, the networks, the ring, the noise, the first observation
         torch.manual_seed(seed)
         self.agent = agent if agent is not None else Agent(
@@ -143,6 +152,18 @@ class VectorStepper:
         self.ring.advance(steps)
         self.vector_steps += steps
 
+    def curriculum_room(self, k):
+        """How many of k further vector steps may run before the curriculum's next update is due (k without a curriculum): graph
+        replays are cut there, so that the update sits between replays."""
+        if self.curriculum is None:
+            return k
+        return min(k, self.curriculum.every - self.vector_steps % self.curriculum.every)
+
+    def curriculum_tick(self):
+        """After advance(): the curriculum's update, on the env's stream, when the vector steps have reached a multiple of `every`."""
+        if self.curriculum is not None and self.vector_steps % self.curriculum.every == 0:
+            self.env.curriculum_update()
+
     def graph_key(self):
         """What captured launches of this stepper bake in: env.graph_epoch (reset seed, per-env-goal mode, pose pool), the ring's
         side-buffer count, the actor's parameter storages (the policy's packed-image struct is keyed on them, fused.py) and the
@@ -166,8 +187,8 @@ class VectorStepper:
         vector_steps, nets (four networks, six with TD3), ring, ou and env (with the episode log's state when it is on).  The
         caller has synchronised."""
         ag = self.agent
-        ex = write_options({}, expert=self.expert, labels=self.labels)
-        if ex:                                # (with labels expert_plan is the launch's whole plan [M + L, H])
+        ex = write_options({}, expert=self.expert, labels=self.labels, curriculum=self.curriculum)
+        if self.expert is not None or self.labels is not None:      # (with labels expert_plan is the launch's whole plan [M + L, H])
             ex["expert_plan"] = self.expert_plan.detach().cpu().clone()
         return {**ex, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
                 "nets": {n: {k: v.detach().cpu().clone() for k, v in getattr(ag, n).state_dict().items()} for n in self.net_names()},
@@ -183,7 +204,7 @@ class VectorStepper:
 
     def check_expert_state(self, sd):
         """ValueError when acting_state() `sd` was written with other expert lanes or labels than this stepper's (or with none)."""
-        compare_options(sd, expert=self.expert, labels=self.labels)
+        compare_options(sd, expert=self.expert, labels=self.labels, curriculum=self.curriculum)
 
     def load_acting_state(self, sd):
         """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are

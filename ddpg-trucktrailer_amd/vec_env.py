@@ -423,9 +423,91 @@ class TruckTrailerVecEnv:
         self._check(self.lib.tt_env_import_episode_log(self._h, L.ptr(blob), C.byref(meta), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()      # blob is a temporary
 
+    # ------------------------------------------------------------------ start-pose curriculum
+    @property
+    def curriculum(self):
+        """The curriculum.Curriculum that is on, or None."""
+        return getattr(self, "_curriculum", None)
+
+    def _curriculum_arrays(self, cells):
+        with torch.cuda.device(self.device):
+            z = lambda n, dt: torch.zeros(n, dtype=dt, device=self.device)
+            # (torch has no unsigned 32 / 64-bit arithmetic: the same bits in int32 / int64 tensors)
+            return dict(p=z(cells, torch.float64), seen=z(cells, torch.int64), attempts=z(cells, torch.int32),
+                        successes=z(cells, torch.int32), q=z(cells, torch.int32), cum=z(cells, torch.int32),
+                        cell=z(self.n_envs, torch.int32))
+
+    def enable_curriculum(self, cur, place=None):
+        """Turn on the start-pose curriculum (include/ttenv.h: tt_env_set_curriculum; curriculum.Curriculum): from the next reset
+        on, reset() and the step's auto-reset draw start poses by the cells' weights, and every finished episode is counted in the
+        cell it started in; curriculum_update() turns the counts into weights.  A fresh curriculum each call.  place: None, or a
+        dict of the seven device arrays (L.CURRICULUM_ARRAYS; cell of npad entries) the library is to use instead of its own.
+        Outside a graph capture; captured step graphs are re-captured (graph_epoch)."""
+        from ddpg_trucktrailer_amd.curriculum import Curriculum
+        Curriculum.expect("curriculum", cur)
+        if self.episode_log_detail:
+            raise ValueError("a curriculum with episode_log_detail is not supported (the curriculum's step kernels carry the plain "
+                             "episode log only)")
+        cfg = cur.c_struct()
+        arrays = None
+        if place is not None:
+            arrays = L.TTCurriculumArrays(*[place[k].data_ptr() for k in L.CURRICULUM_ARRAYS])
+        self._check(self.lib.tt_env_set_curriculum(self._h, C.byref(cfg), C.byref(arrays) if arrays is not None else None,
+                                                   self._stream()))
+        self._curriculum, self._cur_place = cur, place          # (place is kept alive here: the library only borrows it)
+        self._cur_out = self._curriculum_arrays(cur.cells)
+        self.graph_epoch += 1
+
+    def disable_curriculum(self):
+        """Turn the curriculum off: resets draw from the uniform box again, launch for launch (graphs are re-captured)."""
+        if self.curriculum is not None:
+            self._check(self.lib.tt_env_set_curriculum(self._h, None, None, self._stream()))
+        self._curriculum = self._cur_place = self._cur_out = None
+        self.graph_epoch += 1
+
+    def _need_curriculum(self):
+        if self.curriculum is None:
+            raise RuntimeError("the curriculum is off (enable_curriculum)")
+
+    def curriculum_update(self):
+        """The counts since the last update into the cells' success rates and draw weights: one small launch on this stream.
+        Capturable."""
+        self._need_curriculum()
+        self._check(self.lib.tt_env_curriculum_update(self._h, self._stream()))
+
+    def curriculum_state(self):
+        """The curriculum's arrays as device tensors (fresh copies): p f64, seen i64, attempts, successes, q and cum (i32 tensors
+        holding the u32 bits), each shaped [nyaw, ny, nx], and "cell" [N] i32, the cell every lane's running episode was drawn from
+        (-1, the bits of L.CURRICULUM_NO_CELL: none)."""
+        self._need_curriculum()
+        o = self._cur_out
+        arrays = L.TTCurriculumArrays(*[o[k].data_ptr() for k in L.CURRICULUM_ARRAYS])
+        self._check(self.lib.tt_env_curriculum_read(self._h, C.byref(arrays), self._stream()))
+        nx, ny, nyaw = self.curriculum.bins
+        return {k: (v.clone() if k == "cell" else v.clone().view(nyaw, ny, nx)) for k, v in o.items()}
+
+    def load_curriculum_state(self, state):
+        """Write the arrays of `state` that are present (curriculum_state()'s names and dtypes; any shape of the right size) into the
+        curriculum: a checkpoint's, or counters and weights a test plants.  A writer of q keeps cum its inclusive prefix sum."""
+        self._need_curriculum()
+        sizes = dict.fromkeys(L.CURRICULUM_ARRAYS, self.curriculum.cells)
+        sizes["cell"] = self.n_envs
+        held = {}
+        for k in L.CURRICULUM_ARRAYS:
+            if state.get(k) is None:
+                continue
+            t = torch.as_tensor(state[k]).to(device=self.device, dtype=self._cur_out[k].dtype).contiguous().reshape(-1)
+            if t.numel() != sizes[k]:
+                raise ValueError(f"curriculum: {k} has {t.numel()} elements, expected {sizes[k]}")
+            held[k] = t
+        arrays = L.TTCurriculumArrays(*[held[k].data_ptr() if k in held else None for k in L.CURRICULUM_ARRAYS])
+        self._check(self.lib.tt_env_curriculum_write(self._h, C.byref(arrays), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()      # `held` are temporaries
+
     def state_dict(self):
         """Everything needed to resume this env batch (device blob copied to the host + host-side mode); with the episode
-        log on, its state as well (running returns, counters, launch count, records not drained yet)."""
+        log on, its state as well (running returns, counters, launch count, records not drained yet); with a curriculum on, its
+        option and arrays under "curriculum"."""
         nbytes = int(self.lib.tt_env_state_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 4)()
@@ -434,6 +516,9 @@ class TruckTrailerVecEnv:
               "pool": None if getattr(self, "_pool", None) is None else self._pool.cpu()}
         if self.episode_log_capacity:
             sd["episode_log"] = self._episode_log_state()
+        if self.curriculum is not None:
+            sd["curriculum"] = {"option": list(self.curriculum.as_tuple()),
+                                **{k: v.cpu() for k, v in self.curriculum_state().items()}}
         return sd
 
     def load_state_dict(self, sd):
@@ -446,6 +531,13 @@ class TruckTrailerVecEnv:
             self.set_reset_pool(sd["pool"])
         if sd.get("episode_log") is not None:
             self._load_episode_log_state(sd["episode_log"])
+        if sd.get("curriculum") is not None:          # (an env without one turns it on as the file has it)
+            from ddpg_trucktrailer_amd.curriculum import Curriculum
+            from ddpg_trucktrailer_amd.options import _tupled
+            cur = Curriculum.from_tuple(_tupled(sd["curriculum"]["option"]))
+            if self.curriculum != cur:
+                self.enable_curriculum(cur)
+            self.load_curriculum_state(sd["curriculum"])
 
     def profile(self, max_launches):
         """Time the next `max_launches` step-kernel dispatches with per-dispatch HIP events (0 = off)."""

@@ -301,6 +301,57 @@ int tt_env_step_hold(tt_env *env, const float *mu, float action_scale, float *ob
 int tt_env_hold_read(tt_env *env, double *ret, int32_t *len, uint8_t *flags, uint8_t *success, double *end, int64_t *live_out,
                      tt_stream_t stream);
 
+/* Start-pose curriculum: resets drawn by the success rate of the cell they start in.  A curriculum is a
+ * grid of nx x ny x nyaw cells over the reset box reset_lo .. reset_hi, C = nx * ny * nyaw in [1, TT_CURRICULUM_MAX_CELLS], cell
+ * c = (iyaw * ny + iy) * nx + ix.  Per cell, in device memory:
+ *     p f64 [C]            a running success rate, 0.5 at first          seen u64 [C]      the episodes ever counted
+ *     attempts u32 [C]     episodes finished since the last update       successes u32 [C] those of them that succeeded
+ *     q u32 [C]            the draw weight, in [1, 65536]                cum u32 [C]       the inclusive prefix sum of q
+ * and per lane cell u32 [npad] (npad: N rounded up to a multiple of 64; read and write copy the first N): the cell the lane's
+ * running episode was drawn from, TT_CURRICULUM_NO_CELL when no curriculum draw made it.
+ * While a curriculum is on, tt_env_reset (masked or not) and the auto-reset of tt_env_step / _step_ring / _step_random draw
+ *     r = the reset's Philox words of (seed, env, episode);  t = (r[3] * cum[C - 1]) >> 32;  c = the smallest cell with cum[c] > t
+ *     x = lo_x + (ix + (r[0] + 0.5) / 2^32) * ((hi_x - lo_x) / nx),   y and yaw likewise with r[1] and r[2]
+ * in f64, every operation rounded on its own, and write the lane's cell.  A lane that finishes an episode in an auto-resetting
+ * step adds 1 to attempts[cell] and, with final_success_bonus > 0 (the episode log's success), to successes[cell] -- integer adds:
+ * the counts do not depend on the order of arrival -- before its next draw; a lane with no cell counts nothing.  tt_env_set_pose
+ * and tt_env_set_state set the lanes they touch to TT_CURRICULUM_NO_CELL.  Steps with auto_reset = 0 neither count nor draw.
+ * tt_env_curriculum_update (one small launch, capturable): per cell with n = attempts > 0: p <- (1 - alpha) p + alpha (successes / n),
+ * seen += n, both counters 0; then for every cell f = 4 p (1 - p) (TT_CURRICULUM_FRONTIER) or 1 - p (TT_CURRICULUM_HARD),
+ * w = uniform + (1 - uniform) f, q = min(65536, 1 + floor(65535 w)), cum = the inclusive scan of q.  f64 with every operation
+ * rounded on its own and an integer scan: p, q and cum are a pure function of the arrays before.  With p = 0.5 everywhere every
+ * cell has the same weight in both modes: a fresh curriculum draws cells uniformly.
+ * tt_env_set_curriculum(env, cfg, place, stream): cfg NULL turns the curriculum off (the step and the reset are then exactly the
+ * ones without it).  place NULL: the handle allocates and owns the arrays; otherwise the caller's device arrays of the extents
+ * above, all seven, which must outlive their use.  An allocation and a wait for `stream`: outside a graph capture.  Starts fresh
+ * (p = 0.5, nothing counted, every lane without a cell).  TT_EINVAL with a message: a bin count < 1 or C outside
+ * [1, TT_CURRICULUM_MAX_CELLS]; an unknown mode; alpha outside (0, 1]; uniform outside [0, 1] or not finite; a reset pool set
+ * (tt_env_set_reset_pool with m > 0 refuses likewise while a curriculum is on); the detailed episode log on
+ * (tt_env_set_episode_log2 with TT_LOG_DETAIL refuses likewise); a reset box with reset_hi < reset_lo.  tt_env_rollout_random
+ * refuses to run while a curriculum is on.
+ * tt_env_curriculum_read / _write: stream-ordered device-to-device copies between the curriculum's arrays and the caller's
+ * (members that are NULL are skipped) -- the curriculum's own export and import, beside tt_env_export, which stays as it is; also
+ * how a test plants counters or weights.  A writer of q keeps cum its prefix sum; cells outside [0, C) count as no cell. */
+#define TT_CURRICULUM_MAX_CELLS 4096
+#define TT_CURRICULUM_NO_CELL 0xFFFFFFFFu
+#define TT_CURRICULUM_FRONTIER 0
+#define TT_CURRICULUM_HARD 1
+typedef struct tt_curriculum {
+    int32_t nx, ny, nyaw;
+    int32_t mode;
+    double alpha, uniform;
+} tt_curriculum;
+typedef struct tt_curriculum_arrays {
+    double *p;
+    uint64_t *seen;
+    uint32_t *attempts, *successes, *q, *cum;
+    uint32_t *cell;
+} tt_curriculum_arrays;
+int tt_env_set_curriculum(tt_env *env, const tt_curriculum *cfg, const tt_curriculum_arrays *place, tt_stream_t stream);
+int tt_env_curriculum_update(tt_env *env, tt_stream_t stream);
+int tt_env_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt_stream_t stream);
+int tt_env_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */

@@ -31,12 +31,16 @@ last update, and the successes split into the policy's lanes and the others.
 --grad-clip C[,A]: gradient-norm clipping (DDPGRollout(grad_clip=GradClip(C, A))): clip_grad_norm_ with max_norm C
 in front of the critic's optimizer step and, when given, A in front of the actor's ("-" for C: the actor alone).  Each line adds
 "clipped x of y critic / actor updates", the block's share from FusedLearner.clip_stats().  Not with --td3, --bc-weight or the expert options.
+--curriculum NX,NY,NYAW[,EVERY[,MODE]]: the start-pose curriculum (DDPGRollout(curriculum=Curriculum((NX, NY, NYAW), every=EVERY,
+mode=MODE)); defaults EVERY = 64, MODE = frontier): resets drawn by the success rate of the cell they start in,
+counted and drawn inside the env step.  Each line adds the share of cells seen, the mean p and the weight share of the top decile of
+cells.  Composes with every learner option; not with the expert options or --objectives.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
 Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
        [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M] [--label-lanes L] [--expert-horizon H] [--expert-samples S]
-       [--expert-seed K] [--grad-clip C[,A]]
+       [--expert-seed K] [--grad-clip C[,A]] [--curriculum NX,NY,NYAW[,EVERY[,MODE]]]
        [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -118,6 +122,14 @@ if "--grad-clip" in sys.argv[1:]:
     at = sys.argv.index("--grad-clip")
     grad_clip = GradClip(*[None if x in ("", "-") else float(x) for x in sys.argv[at + 1].split(",")])
     del sys.argv[at:at + 2]
+curriculum = None
+if "--curriculum" in sys.argv[1:]:
+    from ddpg_trucktrailer_amd.curriculum import Curriculum, summary as curriculum_summary
+    at = sys.argv.index("--curriculum")
+    parts = sys.argv[at + 1].split(",")
+    curriculum = Curriculum(tuple(int(x) for x in parts[:3]), **({"every": int(parts[3])} if len(parts) > 3 else {}),
+                            **({"mode": parts[4]} if len(parts) > 4 else {}))
+    del sys.argv[at:at + 2]
 loss_shape = None
 if huber is not None or pre_penalty:
     from ddpg_trucktrailer_amd.loss_shape import LossShape
@@ -153,7 +165,7 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
                    learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert, labels=labels,
-                   grad_clip=grad_clip)
+                   grad_clip=grad_clip, curriculum=curriculum)
 if demos is not None:
     from ddpg_trucktrailer_amd.expert import load_transitions_npz
     d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
@@ -162,7 +174,8 @@ print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn()
       f"batch {batch}, pipeline={loop.pipeline}, graph_steps={loop.graph_steps}, n_step={loop.n_step}" + (f", {td3}" if td3 is not None else "") +
       (f", {loss_shape}" if loss_shape is not None else "") + (f", {grad_clip}" if grad_clip is not None else "") +
       (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else "") +
-      (f", {expert}" if expert is not None else "") + (f", {labels}" if labels is not None else ""), flush=True)
+      (f", {expert}" if expert is not None else "") + (f", {labels}" if labels is not None else "") +
+      (f", {curriculum}" if curriculum is not None else ""), flush=True)
 
 
 def learn_line(rec):
@@ -186,6 +199,10 @@ def clip_line(stats):
         parts.append(f"{st['clipped'] - clipped0} of {st['updates'] - updates0} {key}")
         clip_seen[key] = (st["updates"], st["clipped"])
     return "  clipped " + " / ".join(parts) + " updates"
+
+
+def curriculum_line(st):
+    return f"  curriculum: cells seen {100 * st['cells_seen']:5.1f} %, mean p {st['mean_p']:.3f}, top-decile weight {100 * st['top_decile_weight']:4.1f} %"
 
 
 def demo_line(st):
@@ -237,6 +254,7 @@ while s < total:
           f"best x{len(best)}{objs}{lost}{learn_line(loop.drain_learn_log()) if learn_every is not None else ''}"
           f"{demo_line(loop.demo_stats()) if demo_loss is not None else ''}"
           f"{clip_line(loop.learner.clip_stats()) if grad_clip is not None else ''}"
+          f"{curriculum_line(curriculum_summary(env.curriculum_state())) if curriculum is not None else ''}"
           f"{lanes_line(r, expert.lanes if expert is not None else 0, labels.lanes if labels is not None else 0) if expert is not None or labels is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
