@@ -192,7 +192,7 @@ LEARN_LOG_MAX_CAPACITY = 1 << 22        # TT_LEARN_LOG_MAX_CAPACITY
 POP_MAX_AGENTS = 16     # TT_POP_MAX_AGENTS
 NSTEP_MAX = 16          # TT_NSTEP_MAX
 TD3_NOISE_TAG = 0x7D3E  # the Philox domain of TD3's target-smoothing noise (csrc/tttd3.h)
-MPC_NOISE_TAG = 0x4D50  # the Philox domain of the MPC expert's exploration noise (csrc/ttenv.hip)
+MPC_NOISE_TAG = 0x4D50  # the Philox domain of the MPC expert's exploration noise (csrc/ttenv_mpc.h)
 MPC_MAX_HORIZON, MPC_MAX_SAMPLES = 64, 1024     # TT_MPC_MAX_HORIZON, TT_MPC_MAX_SAMPLES
 GRAD_CLIP_PARTIALS = 64     # TT_GRAD_CLIP_PARTIALS
 

@@ -1,5 +1,6 @@
 """Build libttenv.so (HIP, gfx950) in-tree with hipcc.  No JIT cache: the .so sits next to this
 file so that it travels to the GPU box with the repo snapshot."""
+import glob
 import os
 import shutil
 import subprocess
@@ -7,7 +8,9 @@ import subprocess
 HERE = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(HERE)
 SRC = [os.path.join(HERE, "csrc", f) for f in ("ttenv.hip", "ttnet.hip", "ttnet_split.hip", "ttlearn.hip", "ttp2p.hip", "ttpop.hip", "ttnstep.hip", "ttpop_nstep.hip", "ttlearnlog.hip", "tttd3.hip", "ttpop_td3.hip", "ttshape.hip", "ttdemo.hip", "ttclip.hip")]
-HDR = [os.path.join(ROOT, "include", "ttenv.h"), os.path.join(HERE, "csrc", "ttnet_common.h"), os.path.join(HERE, "csrc", "ttnet_pack.h"), os.path.join(HERE, "csrc", "ttp2p.h"), os.path.join(HERE, "csrc", "ttstamps.h"), os.path.join(HERE, "csrc", "ttlearn_bodies.h"), os.path.join(HERE, "csrc", "ttlearn_sites.h"), os.path.join(HERE, "csrc", "ttlearn_host.h"), os.path.join(HERE, "csrc", "ttnstep.h"), os.path.join(HERE, "csrc", "ttpop.h"), os.path.join(HERE, "csrc", "ttpop_exploit.h"), os.path.join(HERE, "csrc", "tthost.h"), os.path.join(HERE, "csrc", "ttphilox.h"), os.path.join(HERE, "csrc", "tttd3.h")]
+# every header a source may include: the public one and whatever csrc/ holds (derived, so that a new header cannot be left out and
+# stale() cannot call the library fresh after an edit; tests/test_kernel_resources.py follows the #include lines against it)
+HDR = [os.path.join(ROOT, "include", "ttenv.h")] + sorted(glob.glob(os.path.join(HERE, "csrc", "*.h")))
 LIB = os.path.join(HERE, "libttenv.so")
 
 

@@ -1,5 +1,5 @@
 // ttphilox.h -- the counter-based generator (Philox4x32-10, Salmon et al. 2011) under every random number of the library: the env's
-// reset poses and random actions (csrc/ttenv.hip), the OU noise and the replay draws (csrc/ttnet_common.h).
+// reset poses and random actions (csrc/ttenv_state.h), the OU noise and the replay draws (csrc/ttnet_common.h).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1,4 +1,4 @@
-"""Start-pose curriculum of the vector loop (include/ttenv.h: tt_env_set_curriculum; csrc/ttenv.hip: k_step_cur, k_curriculum_update;
+"""Start-pose curriculum of the vector loop (include/ttenv.h: tt_env_set_curriculum; csrc/ttenv_curriculum.h: k_step_cur, k_curriculum_update;
 DESIGN.md section 37): the env counts, per cell of a grid over its reset box, how the episodes started there end, and draws the next
 start pose by weights made from those counts -- all of it on the device, inside the env step and one small launch every `every`
 vector steps.

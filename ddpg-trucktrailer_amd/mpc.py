@@ -1,5 +1,5 @@
 """The sampling MPC expert (MPPI, Williams et al. 2017): demonstrations without a solver (include/ttenv.h: tt_env_mpc_plan;
-csrc/ttenv.hip: k_mpc_plan).  The reference makes its demonstrations with a CasADi / IPOPT NMPC
+csrc/ttenv_mpc.h: k_mpc_plan).  The reference makes its demonstrations with a CasADi / IPOPT NMPC
 (DDPG/exp_gen.py, npc_solver.py); here every lane rolls S perturbed steering sequences H steps forward through the env's own step,
 weights them by their return and executes the first action of the weighted mean.
 

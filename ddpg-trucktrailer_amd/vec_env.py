@@ -3,7 +3,8 @@
 The vector form of the reference's `Truck_trailer_Env_2` (truck_trailer_sim/simv2.py:20-545):
 same reset / step / observe / pose-override surface, but every array is a torch tensor resident
 on the GPU and one call advances all N envs.  torch is used for device memory and streams only;
-all arithmetic happens in ddpg-trucktrailer_amd/csrc/ttenv.hip behind the C ABI of include/ttenv.h.
+all arithmetic happens in ddpg-trucktrailer_amd/csrc/ttenv.hip and the csrc/ttenv_*.h topic headers
+it includes (step_env: csrc/ttenv_step.h), behind the C ABI of include/ttenv.h.
 """
 import ctypes as C
 

@@ -11,7 +11,7 @@ import numpy as np
 
 from td3_ref import philox4x32
 
-RESET_TAG = 0x7452          # csrc/ttenv.hip: the Philox domain of the reset's draw
+RESET_TAG = 0x7452          # csrc/ttenv_state.h: the Philox domain of the reset's draw
 NO_CELL = 0xFFFFFFFF
 MODES = ("frontier", "hard")
 

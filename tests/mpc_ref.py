@@ -11,7 +11,7 @@ import numpy as np
 from oracle import c_oracle
 from td3_ref import philox4x32
 
-NOISE_TAG = 0x4D50                      # csrc/ttenv.hip: MPC_NOISE_TAG
+NOISE_TAG = 0x4D50                      # csrc/ttenv_mpc.h: MPC_NOISE_TAG
 HIGH = np.float32(np.pi / 4)            # action_scale: the env's max_steer as the C struct holds it
 F32 = np.float32
 

@@ -1,5 +1,5 @@
 """CPU: the start-pose curriculum without a GPU (ddpg_trucktrailer_amd/curriculum.py; include/ttenv.h: tt_env_set_curriculum;
-csrc/ttenv.hip: k_step_cur, k_step_cur_log, k_curriculum_update).
+csrc/ttenv_curriculum.h: k_step_cur, k_step_cur_log, k_curriculum_update).
 
 * Curriculum's validation, its tuple round trip, and every row of its part of the refusal table, word for word;
 * the host model (tests/curriculum_ref.py) against its own statement: draw shares to the integer, cum[-1] == sum(q), equal weights at

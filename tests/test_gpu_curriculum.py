@@ -1,4 +1,4 @@
-"""GPU (-m gpu): the start-pose curriculum on the device (include/ttenv.h: tt_env_set_curriculum; csrc/ttenv.hip: k_step_cur,
+"""GPU (-m gpu): the start-pose curriculum on the device (include/ttenv.h: tt_env_set_curriculum; csrc/ttenv_curriculum.h: k_step_cur,
 k_step_cur_log, k_reset_curriculum, k_curriculum_update) against the host model tests/curriculum_ref.py.
 
 Sizes: N = 130 (two tiles and a ragged tail) and N = 1; bins (3, 2, 2) and (16, 16, 16).  Everything is compared bit for bit: cells and

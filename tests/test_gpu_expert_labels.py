@@ -1,5 +1,5 @@
 """GPU (-m gpu): expert labels of the vector loop (include/ttenv.h: tt_env_mpc_label_ring, tt_demo_labels, tt_mlp_*_demo_labels;
-csrc/ttenv.hip: k_mpc_label_ring; ddpg_trucktrailer_amd/mpc.py: ExpertLabels).
+csrc/ttenv_mpc.h: k_mpc_label_ring; ddpg_trucktrailer_amd/mpc.py: ExpertLabels).
 
     launch    tt_env_mpc_label_ring after tt_actor_act_ring on fenced buffers against tt_env_mpc_plan on an identical env: the labels
               of lanes [M, M + L) and the plan bit for bit; lanes < M as tt_env_mpc_act_ring leaves them on a third identical setup;

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): expert lanes of the vector loop (include/ttenv.h: tt_env_mpc_act_ring, tt_mlp_*_demo_lanes; csrc/ttenv.hip:
+"""GPU (-m gpu): expert lanes of the vector loop (include/ttenv.h: tt_env_mpc_act_ring, tt_mlp_*_demo_lanes; csrc/ttenv_mpc.h:
 k_mpc_act_ring; ddpg_trucktrailer_amd/mpc.py: ExpertLanes).
 
     entry     tt_env_mpc_act_ring after tt_actor_act_ring against tt_env_mpc_plan on an identical env: ring.act[t][:M], act_scaled[:M]

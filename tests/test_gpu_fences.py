@@ -18,7 +18,7 @@ import pytest
 
 pytestmark = pytest.mark.gpu
 
-ENV_NS = (1, 63, 65, 257, 1000)         # 257: one more than the step kernel's workgroup (TT_BLOCK = 256 in csrc/ttenv.hip)
+ENV_NS = (1, 63, 65, 257, 1000)         # 257: one more than the step kernel's workgroup (TT_BLOCK = 256 in csrc/ttenv_state.h)
 _FIELDS = ("w1", "b1", "g1", "be1", "w2", "b2", "g2", "be2", "w3", "b3", "wa", "ba")
 
 

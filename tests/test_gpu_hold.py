@@ -1,4 +1,4 @@
-"""GPU (-m gpu): greedy evaluation with held lanes (csrc/ttenv.hip: k_step_hold; evaluation.py).
+"""GPU (-m gpu): greedy evaluation with held lanes (csrc/ttenv_hold.h: k_step_hold; evaluation.py).
 
     masked     step_hold against the host-masked loop of grid_eval on a twin env: returns, records and final states bit for bit
     held       lanes that finished do not move under 20 more launches; the episode log and the step counter are not touched

@@ -1,4 +1,4 @@
-"""GPU (-m gpu): one decision of the sampling MPC (csrc/ttenv.hip: k_mpc_plan; include/ttenv.h: tt_env_mpc_plan)
+"""GPU (-m gpu): one decision of the sampling MPC (csrc/ttenv_mpc.h: k_mpc_plan; include/ttenv.h: tt_env_mpc_plan)
 against the env's own step, the C oracle and the host statement of tests/mpc_ref.py.
 
     prediction   S = 1, sigma = 0, no terminal term: the return is the f64 sum of TT_I_TOTAL over H env.step calls, bit for bit

@@ -65,3 +65,34 @@ def test_text_sections_lists_every_code_object_once_and_is_stable():
     for size, digest in ts:
         assert size > 0 and len(digest) == 64 and int(digest, 16) >= 0
     assert kr.text_sections() == ts
+
+
+def test_build_hdr_holds_every_header_the_sources_include():
+    """build.stale() and build_variant() compare the library's time with build.SRC + build.HDR: a header missing from HDR lets an
+    edit of it pass for a fresh library.  Followed from every source through the quoted #include lines (the angle-bracket ones are
+    the toolchain's), each must resolve -- next to the including file or under include/, as the compiler looks -- to a file of
+    HDR; and HDR holds every csrc/*.h, included yet or not."""
+    import glob
+    import os
+    import re
+
+    from ddpg_trucktrailer_amd import build
+
+    hdr = {os.path.realpath(p) for p in build.HDR}
+    assert len(hdr) == len(build.HDR) and all(os.path.isfile(p) for p in hdr)
+    quoted = re.compile(r'^[ \t]*#[ \t]*include[ \t]*"([^"]+)"', re.M)
+    todo, seen = [os.path.realpath(p) for p in build.SRC], set()
+    while todo:
+        path = todo.pop()
+        if path in seen:
+            continue
+        seen.add(path)
+        for name in quoted.findall(open(path).read()):
+            places = [os.path.join(os.path.dirname(path), name), os.path.join(build.ROOT, "include", name)]
+            found = [os.path.realpath(p) for p in places if os.path.isfile(p)]
+            assert found, f"{path} includes \"{name}\", which is neither next to it nor under include/"
+            assert found[0] in hdr, f"{path} includes {found[0]}, which build.HDR does not list"
+            todo.append(found[0])
+    assert len(seen) > len(build.SRC), "no #include line was followed: look at this test's pattern"
+    csrc = glob.glob(os.path.join(build.HERE, "csrc", "*.h"))
+    assert csrc and {os.path.realpath(p) for p in csrc} <= hdr

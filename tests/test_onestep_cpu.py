@@ -162,7 +162,7 @@ def test_reward_mirror_agrees_with_the_twin():
     assert worst.max() <= 5e-6
 
 
-# ---- negative controls: a local copy of the kernel's reduction-plus-Taylor scheme (csrc/ttenv.hip tt_sincos) in numpy f64
+# ---- negative controls: a local copy of the kernel's reduction-plus-Taylor scheme (csrc/ttenv_math.h tt_sincos) in numpy f64
 P1, P2, P3, P3T = (float.fromhex(h) for h in ("0x1.921fb54400000p+0", "0x1.0b4611a600000p-34", "0x1.3198a2e000000p-69",
                                                 "0x1.b839a252049c1p-104"))
 
