@@ -173,6 +173,11 @@ class TTCurriculumArrays(C.Structure):
     _fields_ = [(n, C.c_void_p) for n in ("p", "seen", "attempts", "successes", "q", "cum", "cell")]
 
 
+class TTRandomization(C.Structure):
+    """tt_randomization (include/ttenv.h: tt_env_set_randomization): goal_lo, goal_hi (x, y, yaw), L2_lo, L2_hi."""
+    _fields_ = [("goal_lo", C.c_double * 3), ("goal_hi", C.c_double * 3), ("L2_lo", C.c_double), ("L2_hi", C.c_double)]
+
+
 CURRICULUM_MAX_CELLS = 4096             # TT_CURRICULUM_MAX_CELLS
 CURRICULUM_NO_CELL = 0xFFFFFFFF         # TT_CURRICULUM_NO_CELL
 CURRICULUM_MODES = ("frontier", "hard")  # TT_CURRICULUM_FRONTIER, TT_CURRICULUM_HARD
@@ -347,6 +352,8 @@ _SIGNATURES = {
     "tt_env_curriculum_update": (C.c_int, [_P, _P]),
     "tt_env_curriculum_read": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
     "tt_env_curriculum_write": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
+    "tt_env_set_randomization": (C.c_int, [_P, C.POINTER(TTRandomization), _P]),
+    "tt_env_randomization": (C.c_int, [_P, C.POINTER(TTRandomization)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

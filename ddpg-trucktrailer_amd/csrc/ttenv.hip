@@ -48,8 +48,8 @@ namespace {
 
 // The device side by concern.  ONE translation unit: the order of these includes, and of the two further
 // down, is the order that keeps every kernel's code -- the non-template kernels stay in the order k_reset .. k_random_actions
-// (pose), k_log_zero .. k_log_drain (log), k_hold_* (hold), k_reset_curriculum .. k_curriculum_update (curriculum), and the
-// template kernels are instantiated in the order the host side below first names them.
+// (pose), k_log_zero .. k_log_drain (log), k_hold_* (hold), k_reset_curriculum .. k_curriculum_update (curriculum), k_reset_rnd,
+// k_rnd_seed (randomize), and the template kernels are instantiated in the order the host side below first names them.
 #include "ttenv_math.h"        // KTable, tt_sincos*, tt_exp_neg, tt_atan2_readback, tt_wrap_pi, u01
 #include "ttenv_state.h"       // rows, pk_*, KParams, Bufs, Goal, Env, observe, store_obs_tile, load / store / place_env, draws
 #include "ttenv_step.h"        // StepOut, Info, step_env, write_info
@@ -287,9 +287,10 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(const KParams P, const int n,
     if (obs) store_obs_tile(tile, of, valid, obs, block_first, min(BLOCK, n - block_first));
 }
 
-// behind the TT_STEP_* pieces, which the curriculum's step kernels paste
+// behind the TT_STEP_* pieces, which the curriculum's and the randomised step kernels paste
 #include "ttenv_mpc.h"         // MpcK, mpc_plan_body, k_mpc_plan / act_ring / label_ring
 #include "ttenv_curriculum.h"  // CurDev, k_step_cur, k_step_cur_log, k_reset_curriculum .. k_curriculum_update
+#include "ttenv_randomize.h"   // RndDev, randomized_task, k_step_rnd, k_step_rnd_log, k_reset_rnd, k_rnd_seed
 
 char g_err[tthost::ERR_BYTES] = "";
 
@@ -321,6 +322,10 @@ struct tt_env {
     void *cur_block = nullptr;
     CurDev *cur_dev = nullptr;
     CurDev cur{};
+    // episode randomisation (tt_env_set_randomization): the descriptor in device memory and the ranges as given; rnd_dev == nullptr
+    // <=> off
+    RndDev *rnd_dev = nullptr;
+    tt_randomization rnd{};
     char err[tthost::ERR_BYTES] = "";
 };
 
@@ -442,7 +447,11 @@ void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_
         hipExtLaunchKernelGGL(kernel, g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b, action, action_out, obs, reward, done, info, e->seed,
                               policy_seed, cursor, log...);
     };
-    if (e->cur_dev && auto_reset) {     // the curriculum counts and draws where the step resets (never with the detailed log)
+    if (e->rnd_dev && auto_reset) {     // the task is drawn where the step resets (a per-env handle; never with the detailed log)
+        const RndDev *rnd = e->rnd_dev;
+        if (e->log_bytes) launch(k_step_rnd_log<INFO, RANDOM_POLICY>, e->log, rnd);
+        else launch(k_step_rnd<INFO, RANDOM_POLICY>, rnd);
+    } else if (e->cur_dev && auto_reset) {     // the curriculum counts and draws where the step resets (never with the detailed log)
         const CurDev *cur = e->cur_dev;
         if (e->log_bytes) launch(k_step_cur_log<PER_ENV, INFO, RANDOM_POLICY>, e->log, cur);
         else launch(k_step_cur<PER_ENV, INFO, RANDOM_POLICY>, cur);
@@ -520,6 +529,9 @@ int set_episode_log(tt_env *env, int64_t capacity, uint32_t flags, hipStream_t s
     if ((flags & TT_LOG_DETAIL) && capacity > 0 && env->cur_dev)
         return fail_both(env, TT_EINVAL, "%s: the detailed episode log with a curriculum is not supported (the curriculum's step kernels "
                                          "carry the plain log only); tt_env_set_curriculum(env, NULL, ...) first", fn);
+    if ((flags & TT_LOG_DETAIL) && capacity > 0 && env->rnd_dev)
+        return fail_both(env, TT_EINVAL, "%s: the detailed episode log with episode randomisation is not supported (the randomised step "
+                                         "kernels carry the plain log only); tt_env_set_randomization(env, NULL, ...) first", fn);
     TT_HIP(env, hipSetDevice(env->device));
     if (env->log_block) {       // launches in flight may still write the old block
         TT_HIP(env, hipStreamSynchronize(stream));
@@ -682,6 +694,7 @@ int tt_env_destroy(tt_env *env) {
     if (env->log_block) (void)hipFree(env->log_block);
     if (env->hold_block) (void)hipFree(env->hold_block);
     if (env->cur_block) (void)hipFree(env->cur_block);
+    if (env->rnd_dev) (void)hipFree(env->rnd_dev);
     for (hipEvent_t ev : env->ev_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : env->ev_stop) (void)hipEventDestroy(ev);
     delete env;
@@ -693,7 +706,11 @@ int tt_env_num_envs(const tt_env *env) { return env ? env->n : TT_EINVAL; }
 int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out, tt_stream_t stream) {
     TT_ENTER(env);
     env->seed = seed;
-    if (env->cur_dev) {
+    if (env->rnd_dev) {
+        hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, env->rnd_dev, env->seed);
+        hipLaunchKernelGGL(k_reset_rnd, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
+                           env->seed, (const RndDev *)env->rnd_dev);
+    } else if (env->cur_dev) {
         hipLaunchKernelGGL(k_curriculum_seed, dim3(1), dim3(1), 0, stream, env->cur_dev, env->seed);
         hipLaunchKernelGGL(k_reset_curriculum, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
                            env->seed, (const CurDev *)env->cur_dev);
@@ -718,6 +735,12 @@ int tt_env_set_reset_pool(tt_env *env, const double *pool, int m) {
                                          "from the reset box); tt_env_set_curriculum(env, NULL, ...) first");
     env->kp.pool_m = pool ? m : 0;
     env->kp.pool = env->kp.pool_m > 0 ? pool : nullptr;
+    if (env->rnd_dev) {         // the randomised step kernels read the pool from the descriptor (RndDev); a setter, not a hot call
+        TT_HIP(env, hipSetDevice(env->device));
+        TT_HIP(env, hipDeviceSynchronize());
+        TT_HIP(env, hipMemcpy(&env->rnd_dev->pool, &env->kp.pool, sizeof(env->kp.pool), hipMemcpyHostToDevice));
+        TT_HIP(env, hipMemcpy(&env->rnd_dev->pool_m, &env->kp.pool_m, sizeof(env->kp.pool_m), hipMemcpyHostToDevice));
+    }
     return TT_OK;
 }
 
@@ -861,8 +884,9 @@ int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stre
     TT_HIP(env, hipMemcpyAsync(env->b.hot, src, hb, hipMemcpyDeviceToDevice, stream));
     TT_HIP(env, hipMemcpyAsync(env->b.cold, src + hb, cb, hipMemcpyDeviceToDevice, stream));
     TT_HIP(env, hipMemcpyAsync(env->b.episodes, src + hb + cb, sizeof(uint32_t) * npad, hipMemcpyDeviceToDevice, stream));
-    env->per_env = meta[0] != 0;
+    env->per_env = meta[0] != 0 || env->rnd_dev;      // (a randomised handle stays a per-env handle: every blob has the rows)
     env->seed = meta[1];
+    if (env->rnd_dev) TT_LAUNCH(env, hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, env->rnd_dev, env->seed));
     if (env->cur_dev) TT_LAUNCH(env, hipLaunchKernelGGL(k_curriculum_seed, dim3(1), dim3(1), 0, stream, env->cur_dev, env->seed));
     return TT_OK;
 }
@@ -979,6 +1003,8 @@ int tt_env_rollout_random(tt_env *env, int k_steps, uint64_t policy_seed, float 
     if (k_steps < 0) return fail(env, TT_EINVAL, "tt_env_rollout_random: k_steps=%d", k_steps);
     if (env->log_bytes) return fail(env, TT_EINVAL, "tt_env_rollout_random: the episode log does not follow k_rollout; disable it first");
     if (env->cur_dev) return fail(env, TT_EINVAL, "tt_env_rollout_random: the curriculum does not follow k_rollout; turn it off first");
+    if (env->rnd_dev)
+        return fail_both(env, TT_EINVAL, "tt_env_rollout_random: episode randomisation does not follow k_rollout; turn it off first");
     if (k_steps == 0) return TT_OK;
     TT_RUN(env, by_per_env(env, [&](auto per_env) {
         hipLaunchKernelGGL(k_rollout<decltype(per_env)::value>, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b,
@@ -1104,6 +1130,10 @@ int tt_env_set_curriculum(tt_env *env, const tt_curriculum *cfg, const tt_curric
         if (env->kp.pool_m > 0)
             return fail_both(env, TT_EINVAL, "%s: a curriculum with a reset pool is not supported (the curriculum draws from the reset "
                                              "box); tt_env_set_reset_pool(env, NULL, 0) first", who);
+        if (env->rnd_dev)
+            return fail_both(env, TT_EINVAL, "%s: a curriculum with episode randomisation is not supported (the two have step kernels "
+                                             "of their own, and the cells would be counted under a moving goal); "
+                                             "tt_env_set_randomization(env, NULL, ...) first", who);
         if (env->log_flags & TT_LOG_DETAIL)
             return fail_both(env, TT_EINVAL, "%s: a curriculum with the detailed episode log is not supported (the curriculum's step "
                                              "kernels carry the plain log only)", who);
@@ -1205,6 +1235,81 @@ int tt_env_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt_stre
 
 int tt_env_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream) {
     return curriculum_copy(env, in, false, stream, "tt_env_curriculum_write");
+}
+
+// ---- episode randomisation (include/ttenv.h: tt_env_set_randomization)
+int tt_env_set_randomization(tt_env *env, const tt_randomization *cfg, tt_stream_t stream) {
+    const char *const who = "tt_env_set_randomization";
+    TT_HANDLE(env);
+    if (cfg) {      // (before the handle is read: these hold for any handle)
+        static const char *const axis[3] = {"x", "y", "yaw"};
+        for (int d = 0; d < 3; ++d) {
+            if (!std::isfinite(cfg->goal_lo[d]) || !std::isfinite(cfg->goal_hi[d]))
+                return tthost::fail(TT_EINVAL, "%s: the goal %s range has a bound that is not finite", who, axis[d]);
+            if (cfg->goal_lo[d] > cfg->goal_hi[d])
+                return tthost::fail(TT_EINVAL, "%s: the goal %s range has lo = %g > hi = %g", who, axis[d], cfg->goal_lo[d], cfg->goal_hi[d]);
+        }
+        if (!std::isfinite(cfg->L2_lo) || !std::isfinite(cfg->L2_hi))
+            return tthost::fail(TT_EINVAL, "%s: the L2 range has a bound that is not finite", who);
+        if (cfg->L2_lo > cfg->L2_hi) return tthost::fail(TT_EINVAL, "%s: the L2 range has lo = %g > hi = %g", who, cfg->L2_lo, cfg->L2_hi);
+        if (!(cfg->L2_lo > 0.0)) return tthost::fail(TT_EINVAL, "%s: L2_lo = %g is not > 0", who, cfg->L2_lo);
+        const tt_params &p = env->params;
+        if (cfg->goal_lo[0] < p.map_min_x || cfg->goal_hi[0] > p.map_max_x || cfg->goal_lo[1] < p.map_min_y || cfg->goal_hi[1] > p.map_max_y)
+            return fail_both(env, TT_EINVAL, "%s: the goal range x [%g, %g], y [%g, %g] leaves the map x [%g, %g], y [%g, %g]", who,
+                             cfg->goal_lo[0], cfg->goal_hi[0], cfg->goal_lo[1], cfg->goal_hi[1], p.map_min_x, p.map_max_x, p.map_min_y,
+                             p.map_max_y);
+        const double turn = std::fabs(p.dt * p.v1x) / cfg->L2_lo;      // (tt_env_create's test, for the shortest trailer)
+        if (!(turn <= 0.25))
+            return fail_both(env, TT_EINVAL, "%s: with L2_lo = %g, dt*|v|/L2 = %.3f rad per step exceeds the 0.25 rad the integrator's "
+                                             "small-angle stage rotations are sized for", who, cfg->L2_lo, turn);
+        if (env->cur_dev)
+            return fail_both(env, TT_EINVAL, "%s: episode randomisation with a curriculum is not supported (the two have step kernels "
+                                             "of their own, and the cells would be counted under a moving goal); "
+                                             "tt_env_set_curriculum(env, NULL, ...) first", who);
+        if (env->log_flags & TT_LOG_DETAIL)
+            return fail_both(env, TT_EINVAL, "%s: episode randomisation with the detailed episode log is not supported (the randomised "
+                                             "step kernels carry the plain log only)", who);
+    }
+    TT_HIP(env, hipSetDevice(env->device));
+    if (env->rnd_dev) {         // launches in flight may still read the old descriptor
+        TT_HIP(env, hipStreamSynchronize(stream));
+        TT_HIP(env, hipDeviceSynchronize());
+        TT_HIP(env, hipFree(env->rnd_dev));
+        env->rnd_dev = nullptr;
+        env->rnd = tt_randomization{};
+    }
+    if (!cfg) return TT_OK;
+    void *blk = nullptr;
+    hipError_t err = hipMalloc(&blk, sizeof(RndDev));
+    if (err != hipSuccess) return fail(env, err == hipErrorOutOfMemory ? TT_ENOMEM : TT_EHIP, "%s: %s", who, hipGetErrorString(err));
+    RndDev d{};
+    for (int k = 0; k < 3; ++k) {
+        d.glo[k] = cfg->goal_lo[k];
+        d.gw[k] = cfg->goal_hi[k] - cfg->goal_lo[k];
+    }
+    d.l2lo = cfg->L2_lo;
+    d.l2w = cfg->L2_hi - cfg->L2_lo;
+    d.seed = env->seed;
+    for (int k = 0; k < 3; ++k) { d.rlo[k] = env->kp.rlo[k]; d.rhi[k] = env->kp.rhi[k]; }
+    d.pool = env->kp.pool;
+    d.pool_m = env->kp.pool_m;
+    err = hipMemcpyAsync(blk, &d, sizeof(d), hipMemcpyHostToDevice, stream);
+    if (err == hipSuccess) err = hipStreamSynchronize(stream);      // `d` is a temporary
+    if (err != hipSuccess) {
+        (void)hipFree(blk);
+        return fail(env, TT_EHIP, "%s: %s", who, hipGetErrorString(err));
+    }
+    env->rnd_dev = static_cast<RndDev *>(blk);
+    env->rnd = *cfg;
+    env->per_env = true;
+    return TT_OK;
+}
+
+int tt_env_randomization(const tt_env *env, tt_randomization *out) {
+    TT_HANDLE(env);
+    if (!env->rnd_dev) return 0;
+    if (out) *out = env->rnd;
+    return 1;
 }
 
 int tt_env_profile(tt_env *env, int max_launches) {

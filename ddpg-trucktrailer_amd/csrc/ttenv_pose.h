@@ -7,10 +7,13 @@
 // ------------------------------------------------------------------------------------------
 // reset / pose / state kernels (not hot)
 // The reset of the thread's lane, written once for k_reset and k_reset_curriculum (ttenv_curriculum.h), which differ in the draw
-// alone: pose(env, episode, sx, sy, syaw) gives the start pose of the lane's next episode.
-template <class POSE>
+// alone: pose(env, episode, sx, sy, syaw) gives the start pose of the lane's next episode.  k_reset_rnd (ttenv_randomize.h) also
+// draws the episode's task: task(env, episode, g, gyaw, L2) gives its goal and trailer length; without one they are the
+// parameters' goal and the lane's stored length.
+struct ResetTaskStored {};
+template <class POSE, class TASK = ResetTaskStored>
 __device__ __forceinline__ void reset_lane(const KParams &P, const int n, const Bufs &b, const uint8_t *mask, float *obs,
-                                           const POSE pose) {
+                                           const POSE pose, const TASK task = TASK{}) {
     const int i = blockIdx.x * BLOCK + threadIdx.x;
     if (i >= n || (mask && !mask[i])) return;
     // a full reset restarts every env's episode count, so reset(seed) is a pure function of the seed
@@ -20,12 +23,24 @@ __device__ __forceinline__ void reset_lane(const KParams &P, const int n, const 
     double sx, sy, syaw;
     pose((uint32_t)i, ep, sx, sy, syaw);
     float of[OBS];
-    const Goal g{P.gx, P.gy, P.sg, P.cg};
     Env e;
-    place_env(P, b, i, e, sx, sy, syaw, g, P.gyaw, b.cold[C_L2 * (size_t)P.npad + i], obs ? of : nullptr);
+    if constexpr (std::is_same<TASK, ResetTaskStored>::value) {
+        const Goal g{P.gx, P.gy, P.sg, P.cg};
+        place_env(P, b, i, e, sx, sy, syaw, g, P.gyaw, b.cold[C_L2 * (size_t)P.npad + i], obs ? of : nullptr);
+    } else {
+        Goal g;
+        double gyaw, L2;
+        task((uint32_t)i, ep, g, gyaw, L2);
+        place_env(P, b, i, e, sx, sy, syaw, g, gyaw, L2, of);      // (always observed: `of` then stays in registers, no stack)
+    }
     store_env(b, i, e);
-    if (obs)
+    if constexpr (std::is_same<TASK, ResetTaskStored>::value) {
+        if (obs)
+            for (int j = 0; j < OBS; ++j) obs[(size_t)i * OBS + j] = of[j];
+    } else if (obs) {       // (unrolled: the observation stays in registers)
+#pragma unroll
         for (int j = 0; j < OBS; ++j) obs[(size_t)i * OBS + j] = of[j];
+    }
 }
 
 __global__ __launch_bounds__(BLOCK) void k_reset(const KParams P, const int n, const Bufs b, const uint8_t *mask,

@@ -1,5 +1,6 @@
 """What the loops' options share: the base of the option values (td3.TD3Config, loss_shape.LossShape,
-demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip, curriculum.Curriculum) with the validators
+demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip, curriculum.Curriculum,
+randomize.EpisodeRandomization) with the validators
 their constructors use, the one table of "not supported with" refusals behind the check_* functions, and the options' entries of a checkpoint.
 
     Option                        a value named by its FIELDS: repr, ==, hash, as_tuple(), from_tuple(); a nested Option nests
@@ -150,6 +151,24 @@ TABLE = {
                              ("episode_log_detail", lambda c: c["episode_log_detail"],
                               "a curriculum with episode_log_detail is not supported (the curriculum's step kernels carry the plain "
                               "episode log only)"))),
+    # the env's episode randomisation (randomize.check_randomization passes curriculum, expert, labels, device -- None: not known
+    # yet -- and episode_log_detail)
+    "randomize": dict(what="episode randomisation", be="is", population="a population's agents step envs of their own, and a "
+                                                                          "randomisation per agent is not built",
+                      rows=("population", "data_parallel", "force_dp",
+                            ("curriculum", lambda c: c["curriculum"] is not None,
+                             "episode randomisation with a curriculum is not supported (the two have step kernels of their own, and the "
+                             "curriculum's cells would be counted under a moving goal)"),
+                            ("expert", lambda c: c["expert"] is not None,
+                             "episode randomisation with expert lanes is not supported (the expert on randomised lanes is not checked here)"),
+                            ("labels", lambda c: c["labels"] is not None,
+                             "episode randomisation with expert labels is not supported (the planner on randomised lanes is not checked here)"),
+                            ("device", lambda c: c["device"] is not None and _device_type(c["device"]) != "cuda",
+                             lambda c: f"episode randomisation on device = {c['device']!r} is not supported: it exists only inside the HIP "
+                                       "env step"),
+                            ("episode_log_detail", lambda c: c["episode_log_detail"],
+                             "episode randomisation with episode_log_detail is not supported (the randomised step kernels carry the plain "
+                             "episode log only)"))),
 }
 
 
@@ -165,7 +184,7 @@ def refuse(option, value=None, **context):
 
 
 # ---- the options' entries of a checkpoint: each present option's as_tuple() as a list, under its key
-CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum")
+CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum", "randomize")
 
 
 def write_options(sd, **options):

@@ -50,6 +50,7 @@ class TruckTrailerVecEnv:
         # bumped whenever something a captured step launch bakes in BY VALUE changes (reset seed, per-env-goal mode, pose
         # pool, step counter): holders of hipGraphs of step launches (DDPGRollout) re-capture when it moves
         self.graph_epoch = 0
+        self._randomization = None      # the EpisodeRandomization that is on (enable_randomization)
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -505,10 +506,52 @@ class TruckTrailerVecEnv:
         self._check(self.lib.tt_env_curriculum_write(self._h, C.byref(arrays), self._stream()))
         torch.cuda.current_stream(self.device).synchronize()      # `held` are temporaries
 
+    # ------------------------------------------------------------------ episode randomisation
+    @property
+    def randomization(self):
+        """The randomize.EpisodeRandomization that is on (as given to enable_randomization), or None."""
+        return self._randomization
+
+    def enable_randomization(self, rand):
+        """Turn on episode randomisation (include/ttenv.h: tt_env_set_randomization; randomize.EpisodeRandomization): from the next
+        reset on, reset(), the masked reset and the step's auto-reset draw every new episode's goal and trailer length from the
+        option's ranges (a None of the option: this env's parameters' value); the start pose is drawn as without it.  The lanes
+        keep what they have until their next reset: reset(seed) after enabling gives a randomised episode 0.  The env becomes a
+        per-env env, as set_pose(goal=) makes it.  Outside a graph capture; captured step graphs are re-captured (graph_epoch)."""
+        from ddpg_trucktrailer_amd.randomize import EpisodeRandomization
+        EpisodeRandomization.expect("randomize", rand)
+        if self.curriculum is not None:
+            raise ValueError("episode randomisation with a curriculum is not supported (the two have step kernels of their own, and the "
+                             "curriculum's cells would be counted under a moving goal)")
+        if self.episode_log_detail:
+            raise ValueError("episode randomisation with episode_log_detail is not supported (the randomised step kernels carry the "
+                             "plain episode log only)")
+        cfg = rand.c_struct(self.params)
+        self._check(self.lib.tt_env_set_randomization(self._h, C.byref(cfg), self._stream()))
+        self._randomization = rand
+        self.graph_epoch += 1
+
+    def disable_randomization(self):
+        """Turn episode randomisation off: the lanes keep their goals and lengths, and resets are the ones without the option from
+        then on -- the parameters' goal, the lane's length (graphs are re-captured)."""
+        if self.randomization is not None:
+            self._check(self.lib.tt_env_set_randomization(self._h, None, self._stream()))
+        self._randomization = None
+        self.graph_epoch += 1
+
+    def randomization_ranges(self):
+        """The ranges the library draws from, as a resolved EpisodeRandomization (tt_env_randomization), or None when it is off."""
+        from ddpg_trucktrailer_amd.randomize import EpisodeRandomization
+        out = L.TTRandomization()
+        if not self.lib.tt_env_randomization(self._h, C.byref(out)):
+            return None
+        return EpisodeRandomization(goal=(tuple(out.goal_lo), tuple(out.goal_hi)), L2=(out.L2_lo, out.L2_hi))
+
     def state_dict(self):
         """Everything needed to resume this env batch (device blob copied to the host + host-side mode); with the episode
         log on, its state as well (running returns, counters, launch count, records not drained yet); with a curriculum on, its
-        option and arrays under "curriculum"."""
+        option and arrays under "curriculum"; with episode randomisation on, its option under "randomize" (the lanes' goals and
+        lengths are in the blob)."""
         nbytes = int(self.lib.tt_env_state_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 4)()
@@ -520,9 +563,17 @@ class TruckTrailerVecEnv:
         if self.curriculum is not None:
             sd["curriculum"] = {"option": list(self.curriculum.as_tuple()),
                                 **{k: v.cpu() for k, v in self.curriculum_state().items()}}
+        if self.randomization is not None:
+            sd["randomize"] = list(self.randomization.as_tuple())
         return sd
 
     def load_state_dict(self, sd):
+        if sd.get("randomize") is not None:           # (before the blob: the import hands the blob's seed to the descriptor)
+            from ddpg_trucktrailer_amd.options import _tupled
+            from ddpg_trucktrailer_amd.randomize import EpisodeRandomization
+            rand = EpisodeRandomization.from_tuple(_tupled(sd["randomize"]))
+            if self.randomization != rand:
+                self.enable_randomization(rand)
         blob = sd["blob"].to(self.device)
         meta = (C.c_uint64 * 4)(*sd["meta"])
         self.graph_epoch += 1              # reset seed and per-env-goal mode come back with the blob

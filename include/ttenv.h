@@ -352,6 +352,35 @@ int tt_env_curriculum_update(tt_env *env, tt_stream_t stream);
 int tt_env_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt_stream_t stream);
 int tt_env_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream);
 
+/* Episode randomisation: the TASK is drawn per episode.  While it is on, every reset of a lane -- tt_env_reset
+ * (masked or not) and the auto-reset of tt_env_step / _step_ring / _step_random -- draws the new episode's goal and trailer length
+ *     r = philox4x32(env, episode, 1, 0x7452, seed_lo, seed_hi)     the reset's Philox domain with third counter word 1
+ *     u_k = (r[k] + 0.5) / 2^32
+ *     goal x = goal_lo[0] + (goal_hi[0] - goal_lo[0]) * u_0,  goal y and goal yaw likewise with u_1 and u_2
+ *     L2 = L2_lo + (L2_hi - L2_lo) * u_3
+ * in f64, every operation rounded on its own (the widths hi - lo are formed once, on the host): a pure function of (reset seed,
+ * lane, episode number), and a range of width 0 gives its bound exactly.  The start pose is drawn as without the option (third
+ * counter word 0; the box or the reset pool): a randomised env starts where a plain env with the same seed starts, bit for bit.
+ * The lane is then placed as tt_env_set_pose(start, goal, L2) places it: the start distance and max_episode_steps come from the drawn
+ * goal, the per-env rows hold goal and length (tt_env_get_episode reads them), and observation columns 12-15 carry the goal.
+ * Steps with auto_reset = 0 draw nothing.  tt_env_set_pose / _set_attrs still write a lane; its next reset draws again.
+ * tt_env_set_randomization(env, cfg, stream): cfg NULL turns it off -- the lanes' attributes stay as they are and the resets are the
+ * ones without the option from then on (goal back to the parameters', the lane's L2 kept).  Turning it on makes the handle a per-env
+ * handle (as tt_env_set_pose with a goal does); lanes change at their next reset.  An allocation and a wait for `stream`: outside a
+ * graph capture.  The state blob (tt_env_export) is unchanged: goal and length are in it already.
+ * TT_EINVAL with a message, before the handle is read: a bound that is not finite; lo > hi; L2_lo <= 0.  Reading the handle: a goal
+ * x / y range outside the map; an L2_lo for which dt * |v| / L2 exceeds the integrator's 0.25 rad per step (tt_env_create's test);
+ * a curriculum on (tt_env_set_curriculum refuses likewise while randomisation is on); the detailed episode log on
+ * (tt_env_set_episode_log2 with TT_LOG_DETAIL refuses likewise).  tt_env_rollout_random refuses to run while it is on.  The MPC
+ * launches only read the lanes' attributes and run as before.
+ * tt_env_randomization(env, out): 1 if on (and *out, when not NULL, receives the ranges), 0 if off, TT_EINVAL for a NULL handle. */
+typedef struct tt_randomization {
+    double goal_lo[3], goal_hi[3];      /* x, y, yaw */
+    double L2_lo, L2_hi;
+} tt_randomization;
+int tt_env_set_randomization(tt_env *env, const tt_randomization *cfg /* NULL: off */, tt_stream_t stream);
+int tt_env_randomization(const tt_env *env, tt_randomization *out);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */

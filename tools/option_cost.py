@@ -1,5 +1,5 @@
 """What the option-cost tools share (grad_clip_cost.py, loss_shape_cost.py, demo_cost.py, expert_lanes_cost.py, expert_labels_cost.py,
-curriculum_cost.py, which sets N and UPD from its own arguments): the configuration, a leg, the fresh child process per leg, the alternation of the variants and the report with
+curriculum_cost.py and randomize_cost.py, which set N and UPD from their own arguments): the configuration, a leg, the fresh child process per leg, the alternation of the variants and the report with
 the gate of DESIGN.md section 13 -- the loop without the option costs at most the parent's median plus the parent legs' own
 max - min.  A tool keeps its arguments and how it forwards them to a leg, the keyword arguments of its loops and its variants' names."""
 import argparse
@@ -55,9 +55,9 @@ def one_leg(a, options, prepare=None, stats=None):
     print(f"LEG {ms:.5f}")
 
 
-def run_leg(a, script, variant, forward, echo=None):
+def run_leg(a, script, variant, forward, echo=None, said=None):
     """One leg of `variant` in a fresh process ("parent": the off leg of --parent-tree); a failed or hung leg ends the tool.  The
-    leg's lines that start with `echo` are printed."""
+    leg's lines that start with `echo` are printed (and the last of them kept in said[variant], where `said` is given)."""
     cmd = [sys.executable, os.path.abspath(script), "--leg", "off" if variant == "parent" else variant, "--steps", str(a.steps),
            "--warmup", str(a.warmup)] + forward
     if variant == "parent":
@@ -66,13 +66,15 @@ def run_leg(a, script, variant, forward, echo=None):
     for ln in out.splitlines():
         if echo and ln.startswith(echo):
             print("      " + ln, flush=True)
+            if said is not None:
+                said[variant] = ln
     return float([ln for ln in out.splitlines() if ln.startswith("LEG ")][-1].split()[1])
 
 
-def report(res, names, width, steps, warmup, legs, records=False):
+def report(res, names, width, steps, warmup, legs, records=False, between=()):
     """The report's lines from res = {variant: [ms per vector step of each leg]} (its order is the report's): the header, a line per
     variant, `on - off` (records: a line per variant with the option, in per cent of off) and the gate, evaluated where res has
-    "parent"."""
+    "parent".  between: pairs (a, b) of variants whose medians' difference a - b is a record line of its own, behind `on - off`."""
     names = {"parent": PARENT, **names}
     lines = [f"# DDPGRollout, N = {N}, {UPD} updates per vector step, B = {B}, ring of {SLOTS} slots, whole-step graphs of {GRAPH_STEPS}; "
              f"{steps} timed vector steps per leg after {warmup}, every leg a fresh process, {legs} legs, variants alternating"]
@@ -89,6 +91,8 @@ def report(res, names, width, steps, warmup, legs, records=False):
         else:
             lines.append(f"# {v} - off = {1e3 * (on - off):+.2f} us per vector step = {1e3 * (on - off) / UPD:+.3f} us per update; the off legs' own max - min "
                          f"is {1e3 * spread:.2f} us per vector step: " + ("within it" if on - off <= spread else "beyond it"))
+    for a, b in between:
+        lines.append(f"# {a} - {b} = {1e3 * (statistics.median(res[a]) - statistics.median(res[b])):+.2f} us per vector step (a record, not a gate)")
     if "parent" in res:
         p = res["parent"]
         limit = statistics.median(p) + (max(p) - min(p))
@@ -99,17 +103,20 @@ def report(res, names, width, steps, warmup, legs, records=False):
     return lines
 
 
-def compare(a, script, variants, forward, names, width, records=False, echo=None):
+def compare(a, script, variants, forward, names, width, records=False, echo=None, between=()):
     """The tool without --leg: `a.legs` rounds of every variant (with --parent-tree "parent" too: last, or first for a tool whose
-    report is `records`), alternating within a round and in their order from round to round; the report is printed and written to --out."""
+    report is `records`), alternating within a round and in their order from round to round; the report (`between`: report()'s) is
+    printed and written to --out, and so is the last of each variant's echoed lines."""
     if a.parent_tree:
         variants = ["parent"] + variants if records else variants + ["parent"]
     res = {v: [] for v in variants}
+    said = {}
     for leg in range(a.legs):
         for v in (variants if leg % 2 == 0 else variants[::-1]):
-            res[v].append(run_leg(a, script, v, forward, echo))
+            res[v].append(run_leg(a, script, v, forward, echo, said))
             print(f"round {leg} {v:>{9 if records else 6}}: {res[v][-1]:.5f} ms per vector step", flush=True)
-    lines = report(res, names, width, a.steps, a.warmup, a.legs, records)
+    lines = report(res, names, width, a.steps, a.warmup, a.legs, records, between)
+    lines += [f"# the last {v} leg: {ln}" for v, ln in said.items()]
     print("\n".join(lines))
     if a.out:
         with open(a.out, "w") as f:
