@@ -178,6 +178,11 @@ class TTRandomization(C.Structure):
     _fields_ = [("goal_lo", C.c_double * 3), ("goal_hi", C.c_double * 3), ("L2_lo", C.c_double), ("L2_hi", C.c_double)]
 
 
+class TTTaskCurriculum(C.Structure):
+    """tt_task_curriculum (include/ttenv.h: tt_env_set_task_curriculum): bins (ngx, ngy, ngyaw, nl2), mode, alpha, uniform."""
+    _fields_ = [("bins", C.c_int32 * 4), ("mode", C.c_int32), ("alpha", C.c_double), ("uniform", C.c_double)]
+
+
 CURRICULUM_MAX_CELLS = 4096             # TT_CURRICULUM_MAX_CELLS
 CURRICULUM_NO_CELL = 0xFFFFFFFF         # TT_CURRICULUM_NO_CELL
 CURRICULUM_MODES = ("frontier", "hard")  # TT_CURRICULUM_FRONTIER, TT_CURRICULUM_HARD
@@ -354,6 +359,11 @@ _SIGNATURES = {
     "tt_env_curriculum_write": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
     "tt_env_set_randomization": (C.c_int, [_P, C.POINTER(TTRandomization), _P]),
     "tt_env_randomization": (C.c_int, [_P, C.POINTER(TTRandomization)]),
+    "tt_env_set_task_curriculum": (C.c_int, [_P, C.POINTER(TTTaskCurriculum), C.POINTER(TTCurriculumArrays), _P]),
+    "tt_env_task_curriculum_update": (C.c_int, [_P, _P]),
+    "tt_env_task_curriculum_read": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
+    "tt_env_task_curriculum_write": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
+    "tt_env_task_curriculum": (C.c_int, [_P, C.POINTER(TTTaskCurriculum)]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -49,7 +49,7 @@ namespace {
 // The device side by concern.  ONE translation unit: the order of these includes, and of the two further
 // down, is the order that keeps every kernel's code -- the non-template kernels stay in the order k_reset .. k_random_actions
 // (pose), k_log_zero .. k_log_drain (log), k_hold_* (hold), k_reset_curriculum .. k_curriculum_update (curriculum), k_reset_rnd,
-// k_rnd_seed (randomize), and the template kernels are instantiated in the order the host side below first names them.
+// k_rnd_seed (randomize), k_reset_task (task), and the template kernels are instantiated in the order the host side below first names them.
 #include "ttenv_math.h"        // KTable, tt_sincos*, tt_exp_neg, tt_atan2_readback, tt_wrap_pi, u01
 #include "ttenv_state.h"       // rows, pk_*, KParams, Bufs, Goal, Env, observe, store_obs_tile, load / store / place_env, draws
 #include "ttenv_step.h"        // StepOut, Info, step_env, write_info
@@ -291,6 +291,7 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(const KParams P, const int n,
 #include "ttenv_mpc.h"         // MpcK, mpc_plan_body, k_mpc_plan / act_ring / label_ring
 #include "ttenv_curriculum.h"  // CurDev, k_step_cur, k_step_cur_log, k_reset_curriculum .. k_curriculum_update
 #include "ttenv_randomize.h"   // RndDev, randomized_task, k_step_rnd, k_step_rnd_log, k_reset_rnd, k_rnd_seed
+#include "ttenv_task.h"        // TaskDev, task_draw, k_step_task, k_step_task_log, k_reset_task
 
 char g_err[tthost::ERR_BYTES] = "";
 
@@ -326,6 +327,12 @@ struct tt_env {
     // <=> off
     RndDev *rnd_dev = nullptr;
     tt_randomization rnd{};
+    // task curriculum (tt_env_set_task_curriculum): the descriptor in device memory (followed, in the same block, by the arrays the
+    // handle owns), its host copy and the option as given; task_dev == nullptr <=> off.  On only while rnd_dev is.
+    void *task_block = nullptr;
+    TaskDev *task_dev = nullptr;
+    TaskDev task{};
+    tt_task_curriculum task_cfg{};
     char err[tthost::ERR_BYTES] = "";
 };
 
@@ -447,7 +454,11 @@ void launch_step(tt_env *e, bool auto_reset, const float *action, float *action_
         hipExtLaunchKernelGGL(kernel, g, b, 0, s, t0, t1, 0, e->kp, e->n, e->b, action, action_out, obs, reward, done, info, e->seed,
                               policy_seed, cursor, log...);
     };
-    if (e->rnd_dev && auto_reset) {     // the task is drawn where the step resets (a per-env handle; never with the detailed log)
+    if (e->task_dev && auto_reset) {    // the task curriculum counts and draws where the step resets (randomisation is on with it)
+        const TaskDev *tk = e->task_dev;
+        if (e->log_bytes) launch(k_step_task_log<INFO, RANDOM_POLICY>, e->log, tk);
+        else launch(k_step_task<INFO, RANDOM_POLICY>, tk);
+    } else if (e->rnd_dev && auto_reset) {     // the task is drawn where the step resets (a per-env handle; never with the detailed log)
         const RndDev *rnd = e->rnd_dev;
         if (e->log_bytes) launch(k_step_rnd_log<INFO, RANDOM_POLICY>, e->log, rnd);
         else launch(k_step_rnd<INFO, RANDOM_POLICY>, rnd);
@@ -561,10 +572,11 @@ int set_episode_log(tt_env *env, int64_t capacity, uint32_t flags, hipStream_t s
     return TT_OK;
 }
 
-// lanes placed from outside (entry j < k names lane idx[j], idx NULL: lane j): no curriculum draw made their episode
+// lanes placed from outside (entry j < k names lane idx[j], idx NULL: lane j): no curriculum draw made their episode, neither the
+// start-pose curriculum's nor the task curriculum's
 int curriculum_unset(tt_env *env, int k, const int32_t *idx, hipStream_t stream) {
-    if (!env->cur_dev) return TT_OK;
-    TT_LAUNCH(env, hipLaunchKernelGGL(k_curriculum_unset, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, idx, env->cur.cell));
+    for (uint32_t *cell : {env->cur_dev ? env->cur.cell : nullptr, env->task_dev ? env->task.cur.cell : nullptr})
+        if (cell) TT_LAUNCH(env, hipLaunchKernelGGL(k_curriculum_unset, dim3(grid_for(k)), dim3(BLOCK), 0, stream, env->n, k, idx, cell));
     return TT_OK;
 }
 
@@ -695,6 +707,7 @@ int tt_env_destroy(tt_env *env) {
     if (env->hold_block) (void)hipFree(env->hold_block);
     if (env->cur_block) (void)hipFree(env->cur_block);
     if (env->rnd_dev) (void)hipFree(env->rnd_dev);
+    if (env->task_block) (void)hipFree(env->task_block);
     for (hipEvent_t ev : env->ev_start) (void)hipEventDestroy(ev);
     for (hipEvent_t ev : env->ev_stop) (void)hipEventDestroy(ev);
     delete env;
@@ -706,7 +719,12 @@ int tt_env_num_envs(const tt_env *env) { return env ? env->n : TT_EINVAL; }
 int tt_env_reset(tt_env *env, const uint8_t *mask, uint64_t seed, float *obs_out, tt_stream_t stream) {
     TT_ENTER(env);
     env->seed = seed;
-    if (env->rnd_dev) {
+    if (env->task_dev) {        // (randomisation is on with it: both descriptors get the seed)
+        hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, env->rnd_dev, env->seed);
+        hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, &env->task_dev->rnd, env->seed);
+        hipLaunchKernelGGL(k_reset_task, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
+                           env->seed, (const TaskDev *)env->task_dev);
+    } else if (env->rnd_dev) {
         hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, env->rnd_dev, env->seed);
         hipLaunchKernelGGL(k_reset_rnd, dim3(grid_for(env->n)), dim3(BLOCK), 0, stream, env->kp, env->n, env->b, mask, obs_out,
                            env->seed, (const RndDev *)env->rnd_dev);
@@ -740,6 +758,10 @@ int tt_env_set_reset_pool(tt_env *env, const double *pool, int m) {
         TT_HIP(env, hipDeviceSynchronize());
         TT_HIP(env, hipMemcpy(&env->rnd_dev->pool, &env->kp.pool, sizeof(env->kp.pool), hipMemcpyHostToDevice));
         TT_HIP(env, hipMemcpy(&env->rnd_dev->pool_m, &env->kp.pool_m, sizeof(env->kp.pool_m), hipMemcpyHostToDevice));
+        if (env->task_dev) {    // ... and so do the task curriculum's, from theirs
+            TT_HIP(env, hipMemcpy(&env->task_dev->rnd.pool, &env->kp.pool, sizeof(env->kp.pool), hipMemcpyHostToDevice));
+            TT_HIP(env, hipMemcpy(&env->task_dev->rnd.pool_m, &env->kp.pool_m, sizeof(env->kp.pool_m), hipMemcpyHostToDevice));
+        }
     }
     return TT_OK;
 }
@@ -887,6 +909,7 @@ int tt_env_import(tt_env *env, const void *blob, const uint64_t meta[4], tt_stre
     env->per_env = meta[0] != 0 || env->rnd_dev;      // (a randomised handle stays a per-env handle: every blob has the rows)
     env->seed = meta[1];
     if (env->rnd_dev) TT_LAUNCH(env, hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, env->rnd_dev, env->seed));
+    if (env->task_dev) TT_LAUNCH(env, hipLaunchKernelGGL(k_rnd_seed, dim3(1), dim3(1), 0, stream, &env->task_dev->rnd, env->seed));
     if (env->cur_dev) TT_LAUNCH(env, hipLaunchKernelGGL(k_curriculum_seed, dim3(1), dim3(1), 0, stream, env->cur_dev, env->seed));
     return TT_OK;
 }
@@ -1211,12 +1234,15 @@ int tt_env_curriculum_update(tt_env *env, tt_stream_t stream) {
 }
 
 // tt_env_curriculum_read (to_caller) and tt_env_curriculum_write: device-to-device copies of the arrays the caller names
-static int curriculum_copy(tt_env *env, const tt_curriculum_arrays *a, bool to_caller, hipStream_t stream, const char *who) {
+// (task: the task curriculum's arrays, tt_env_task_curriculum_read / _write)
+static int curriculum_copy(tt_env *env, const tt_curriculum_arrays *a, bool to_caller, hipStream_t stream, const char *who,
+                           bool task = false) {
     if (!env) return tthost::fail(TT_EINVAL, "%s: NULL handle", who);
     if (!a) return tthost::fail(TT_EINVAL, "%s: NULL argument", who);
-    if (!env->cur_dev) return fail_both(env, TT_EINVAL, "%s: the curriculum is off (tt_env_set_curriculum)", who);
+    if (task && !env->task_dev) return fail_both(env, TT_EINVAL, "%s: the task curriculum is off (tt_env_set_task_curriculum)", who);
+    if (!task && !env->cur_dev) return fail_both(env, TT_EINVAL, "%s: the curriculum is off (tt_env_set_curriculum)", who);
     TT_HIP(env, hipSetDevice(env->device));
-    const CurDev &d = env->cur;
+    const CurDev &d = task ? env->task.cur : env->cur;
     const size_t c = (size_t)d.C;
     void *mine[7] = {d.p, d.seen, d.attempts, d.successes, d.q, d.cum, d.cell};
     void *theirs[7] = {a->p, a->seen, a->attempts, a->successes, a->q, a->cum, a->cell};
@@ -1270,6 +1296,8 @@ int tt_env_set_randomization(tt_env *env, const tt_randomization *cfg, tt_stream
             return fail_both(env, TT_EINVAL, "%s: episode randomisation with the detailed episode log is not supported (the randomised "
                                              "step kernels carry the plain log only)", who);
     }
+    if (env->task_dev)          // (its cells lie on these ranges)
+        return fail_both(env, TT_EINVAL, "%s: turn the task curriculum off first (tt_env_set_task_curriculum(env, NULL, ...))", who);
     TT_HIP(env, hipSetDevice(env->device));
     if (env->rnd_dev) {         // launches in flight may still read the old descriptor
         TT_HIP(env, hipStreamSynchronize(stream));
@@ -1309,6 +1337,137 @@ int tt_env_randomization(const tt_env *env, tt_randomization *out) {
     TT_HANDLE(env);
     if (!env->rnd_dev) return 0;
     if (out) *out = env->rnd;
+    return 1;
+}
+
+// ---- task curriculum (include/ttenv.h: tt_env_set_task_curriculum)
+int tt_env_set_task_curriculum(tt_env *env, const tt_task_curriculum *cfg, const tt_curriculum_arrays *place, tt_stream_t stream) {
+    const char *const who = "tt_env_set_task_curriculum";
+    TT_HANDLE(env);
+    long long C = 1;
+    if (cfg) {      // (before the handle is read: these hold for any handle)
+        const int *const n = cfg->bins;
+        for (int k = 0; k < 4; ++k) {
+            if (n[k] < 1) return tthost::fail(TT_EINVAL, "%s: bins (%d, %d, %d, %d): a bin count below 1", who, n[0], n[1], n[2], n[3]);
+            C = std::min<long long>(C * n[k], (long long)TT_CURRICULUM_MAX_CELLS + 1);      // (no overflow)
+        }
+        if (C > TT_CURRICULUM_MAX_CELLS)
+            return tthost::fail(TT_EINVAL, "%s: bins (%d, %d, %d, %d) make more than %d cells", who, n[0], n[1], n[2], n[3],
+                                TT_CURRICULUM_MAX_CELLS);
+        if (cfg->mode != TT_CURRICULUM_FRONTIER && cfg->mode != TT_CURRICULUM_HARD)
+            return tthost::fail(TT_EINVAL, "%s: unknown mode %d", who, cfg->mode);
+        if (!(cfg->alpha > 0.0 && cfg->alpha <= 1.0)) return tthost::fail(TT_EINVAL, "%s: alpha is outside (0, 1]", who);
+        if (!std::isfinite(cfg->uniform) || !(cfg->uniform >= 0.0 && cfg->uniform <= 1.0))
+            return tthost::fail(TT_EINVAL, "%s: uniform is outside [0, 1] or not finite", who);
+        if (place && (!place->p || !place->seen || !place->attempts || !place->successes || !place->q || !place->cum || !place->cell))
+            return tthost::fail(TT_EINVAL, "%s: place names every array or is NULL", who);
+        if (!env->rnd_dev)
+            return fail_both(env, TT_EINVAL, "%s: episode randomisation is not on: there is no range to put cells on "
+                                             "(tt_env_set_randomization first)", who);
+        static const char *const axis[4] = {"goal x", "goal y", "goal yaw", "L2"};
+        const double lo[4] = {env->rnd.goal_lo[0], env->rnd.goal_lo[1], env->rnd.goal_lo[2], env->rnd.L2_lo};
+        const double hi[4] = {env->rnd.goal_hi[0], env->rnd.goal_hi[1], env->rnd.goal_hi[2], env->rnd.L2_hi};
+        for (int k = 0; k < 4; ++k)
+            if (n[k] > 1 && !(hi[k] - lo[k] > 0.0))
+                return fail_both(env, TT_EINVAL, "%s: %d bins on the %s range, which has width 0 (its cells could not be told apart)", who,
+                                 n[k], axis[k]);
+    }
+    TT_HIP(env, hipSetDevice(env->device));
+    if (env->task_block) {      // launches in flight may still read and write the old block
+        TT_HIP(env, hipStreamSynchronize(stream));
+        TT_HIP(env, hipDeviceSynchronize());
+        TT_HIP(env, hipFree(env->task_block));
+        env->task_block = nullptr;
+        env->task_dev = nullptr;
+        env->task = TaskDev{};
+        env->task_cfg = tt_task_curriculum{};
+    }
+    if (!cfg) return TT_OK;
+    const size_t c = (size_t)C, npad = (size_t)env->npad;
+    // the block: the descriptor, then (without `place`) p | seen | attempts | successes | q | cum | cell, each 256-byte aligned
+    const size_t sizes[7] = {sizeof(double) * c, sizeof(unsigned long long) * c, sizeof(uint32_t) * c, sizeof(uint32_t) * c,
+                             sizeof(uint32_t) * c, sizeof(uint32_t) * c, sizeof(uint32_t) * npad};
+    size_t bytes = cur_align(sizeof(TaskDev));
+    size_t off[7];
+    for (int a = 0; a < 7; ++a) {
+        off[a] = bytes;
+        if (!place) bytes += cur_align(sizes[a]);
+    }
+    void *blk = nullptr;
+    hipError_t err = hipMalloc(&blk, bytes);
+    if (err != hipSuccess) return fail(env, err == hipErrorOutOfMemory ? TT_ENOMEM : TT_EHIP, "%s: %s", who, hipGetErrorString(err));
+    char *base = static_cast<char *>(blk);
+    TaskDev d{};
+    if (place) {
+        d.cur.p = place->p; d.cur.seen = reinterpret_cast<unsigned long long *>(place->seen);
+        d.cur.attempts = place->attempts; d.cur.successes = place->successes; d.cur.q = place->q; d.cur.cum = place->cum;
+        d.cur.cell = place->cell;
+    } else {
+        d.cur.p = reinterpret_cast<double *>(base + off[0]);
+        d.cur.seen = reinterpret_cast<unsigned long long *>(base + off[1]);
+        d.cur.attempts = reinterpret_cast<uint32_t *>(base + off[2]);
+        d.cur.successes = reinterpret_cast<uint32_t *>(base + off[3]);
+        d.cur.q = reinterpret_cast<uint32_t *>(base + off[4]);
+        d.cur.cum = reinterpret_cast<uint32_t *>(base + off[5]);
+        d.cur.cell = reinterpret_cast<uint32_t *>(base + off[6]);
+    }
+    d.cur.C = (int)C;
+    d.cur.mode = cfg->mode;
+    d.cur.alpha = cfg->alpha; d.cur.uniform = cfg->uniform;
+    d.cur.seed = env->seed;
+    // the RndDev as tt_env_set_randomization forms it, and the cell widths
+    const tt_randomization &r = env->rnd;
+    for (int k = 0; k < 3; ++k) {
+        d.rnd.glo[k] = r.goal_lo[k];
+        d.rnd.gw[k] = r.goal_hi[k] - r.goal_lo[k];
+        d.cw[k] = (r.goal_hi[k] - r.goal_lo[k]) / (double)cfg->bins[k];
+        d.rnd.rlo[k] = env->kp.rlo[k]; d.rnd.rhi[k] = env->kp.rhi[k];
+    }
+    d.rnd.l2lo = r.L2_lo;
+    d.rnd.l2w = r.L2_hi - r.L2_lo;
+    d.cw[3] = (r.L2_hi - r.L2_lo) / (double)cfg->bins[3];
+    d.rnd.seed = env->seed;
+    d.rnd.pool = env->kp.pool;
+    d.rnd.pool_m = env->kp.pool_m;
+    for (int k = 0; k < 4; ++k) d.bins[k] = cfg->bins[k];
+    env->task_block = blk;
+    env->task = d;
+    // fresh, as tt_env_set_curriculum starts: p = 0.5 everywhere, nothing seen or counted, no lane's episode drawn by it; q and cum
+    // by the update itself
+    const std::vector<double> half(c, 0.5);
+    TT_HIP(env, hipMemcpyAsync(blk, &d, sizeof(d), hipMemcpyHostToDevice, stream));
+    TT_HIP(env, hipMemcpyAsync(d.cur.p, half.data(), sizes[0], hipMemcpyHostToDevice, stream));
+    TT_HIP(env, hipMemsetAsync(d.cur.seen, 0, sizes[1], stream));
+    TT_HIP(env, hipMemsetAsync(d.cur.attempts, 0, sizes[2], stream));
+    TT_HIP(env, hipMemsetAsync(d.cur.successes, 0, sizes[3], stream));
+    TT_HIP(env, hipMemsetAsync(d.cur.cell, 0xFF, sizes[6], stream));
+    TT_LAUNCH(env, hipLaunchKernelGGL(k_curriculum_update, dim3(1), dim3(BLOCK), 0, stream, (const CurDev *)blk));
+    TT_HIP(env, hipStreamSynchronize(stream));      // `d` and `half` are temporaries
+    env->task_dev = static_cast<TaskDev *>(blk);
+    env->task_cfg = *cfg;
+    return TT_OK;
+}
+
+int tt_env_task_curriculum_update(tt_env *env, tt_stream_t stream) {
+    TT_HANDLE(env);
+    if (!env->task_dev)
+        return fail_both(env, TT_EINVAL, "tt_env_task_curriculum_update: the task curriculum is off (tt_env_set_task_curriculum)");
+    // the curriculum's update on the descriptor's leading CurDev: it reads C, the arrays, mode, alpha and uniform only
+    TT_RUN(env, hipLaunchKernelGGL(k_curriculum_update, dim3(1), dim3(BLOCK), 0, stream, (const CurDev *)&env->task_dev->cur));
+}
+
+int tt_env_task_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt_stream_t stream) {
+    return curriculum_copy(env, out, true, stream, "tt_env_task_curriculum_read", true);
+}
+
+int tt_env_task_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream) {
+    return curriculum_copy(env, in, false, stream, "tt_env_task_curriculum_write", true);
+}
+
+int tt_env_task_curriculum(const tt_env *env, tt_task_curriculum *out) {
+    TT_HANDLE(env);
+    if (!env->task_dev) return 0;
+    if (out) *out = env->task_cfg;
     return 1;
 }
 

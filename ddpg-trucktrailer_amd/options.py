@@ -1,6 +1,6 @@
 """What the loops' options share: the base of the option values (td3.TD3Config, loss_shape.LossShape,
 demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip, curriculum.Curriculum,
-randomize.EpisodeRandomization) with the validators
+randomize.EpisodeRandomization, task_curriculum.TaskCurriculum) with the validators
 their constructors use, the one table of "not supported with" refusals behind the check_* functions, and the options' entries of a checkpoint.
 
     Option                        a value named by its FIELDS: repr, ==, hash, as_tuple(), from_tuple(); a nested Option nests
@@ -169,6 +169,16 @@ TABLE = {
                             ("episode_log_detail", lambda c: c["episode_log_detail"],
                              "episode randomisation with episode_log_detail is not supported (the randomised step kernels carry the plain "
                              "episode log only)"))),
+    # the env's task curriculum (task_curriculum.check_task_curriculum passes randomize and device -- None: not known yet; what
+    # randomisation refuses is refused by its own rows first: the option is on only with it)
+    "task_curriculum": dict(what="a task curriculum", be="is", population="a population's agents step envs of their own, and a task "
+                                                                          "curriculum per agent is not built",
+                            rows=(("randomize", lambda c: c["randomize"] is None,
+                                   "a task curriculum without randomize is not supported: there is no range to put cells on"),
+                                  "population", "data_parallel", "force_dp",
+                                  ("device", lambda c: c["device"] is not None and _device_type(c["device"]) != "cuda",
+                                   lambda c: f"a task curriculum on device = {c['device']!r} is not supported: it exists only inside the HIP "
+                                             "env step"))),
 }
 
 
@@ -184,7 +194,7 @@ def refuse(option, value=None, **context):
 
 
 # ---- the options' entries of a checkpoint: each present option's as_tuple() as a list, under its key
-CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum", "randomize")
+CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum", "task_curriculum", "randomize")
 
 
 def write_options(sd, **options):

@@ -476,7 +476,8 @@ class PopulationRollout:
     def __init__(self, n_envs_per_agent, seeds, alphas=1e-4, betas=1e-3, taus=1e-3, gammas=0.99, batch_size=256, replay_slots=64,
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
-                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, grad_clip=None, curriculum=None, randomize=None):
+                 learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, grad_clip=None, curriculum=None, randomize=None,
+                 task_curriculum=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
         _refuse_lone_options(loss_shape, demo_loss, expert)
         if curriculum is not None:     # (a lone loop's option: curriculum.check_curriculum refuses a population)
@@ -485,6 +486,9 @@ class PopulationRollout:
         if randomize is not None:      # (likewise: randomize.check_randomization refuses a population)
             from ddpg_trucktrailer_amd.randomize import check_randomization
             check_randomization(randomize, population=True)
+        if task_curriculum is not None:    # (likewise: task_curriculum.check_task_curriculum; without `randomize` that row comes first)
+            from ddpg_trucktrailer_amd.task_curriculum import check_task_curriculum
+            check_task_curriculum(task_curriculum, randomize=randomize, population=True)
         grad_clip = check_population_grad_clip(grad_clip, len(seeds), td3=td3, data_parallel=bool(data_parallel), device=device)
         if td3 is not None:            # (before anything else: each refusal names its option)
             from ddpg_trucktrailer_amd.td3 import check_population_td3

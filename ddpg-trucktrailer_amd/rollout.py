@@ -95,7 +95,7 @@ class DDPGRollout(VectorStepper):
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
                  learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, labels=None, grad_clip=None,
-                 curriculum=None, randomize=None):
+                 curriculum=None, randomize=None, task_curriculum=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -157,15 +157,22 @@ class DDPGRollout(VectorStepper):
         observation is taken.  It is the env's: TD3, n_step, loss_shape, grad_clip, demo_loss from a file, the learn log and the plain
         episode log compose with it unchanged, in graphs and eager steps.  randomize.check_randomization names what is refused
         (data-parallel ranks, the p2p exchange, TT_FORCE_DP, a curriculum, expert lanes, expert labels, an env that is not on a GPU,
-        episode_log_detail)."""
+        episode_log_detail).
+        task_curriculum: None, or a task_curriculum.TaskCurriculum, with `randomize`: the env draws every
+        episode's task by the success counted per cell of a grid over randomisation's ranges, inside the env step; its update is
+        launched behind every `every`-th vector step, between graph replays, as the curriculum's.  It is the env's: what composes with
+        `randomize` composes with it.  task_curriculum.check_task_curriculum names what is refused (no `randomize`, data-parallel
+        ranks, the p2p exchange, TT_FORCE_DP, an env that is not on a GPU)."""
         from ddpg_trucktrailer_amd.curriculum import check_curriculum
+        from ddpg_trucktrailer_amd.task_curriculum import check_task_curriculum
         from ddpg_trucktrailer_amd.randomize import check_randomization
         from ddpg_trucktrailer_amd.td3 import check_td3          # (here: td3.py imports this module)
         ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
         force_dp = os.environ.get("TT_FORCE_DP") == "1"
         c = dict(labels=labels, expert=expert, n_step=n_step, demo_loss=demo_loss, loss_shape=loss_shape, td3=td3, n_envs=env.n_envs,
                  data_parallel=ranks or dp_exchange == "p2p", force_dp=force_dp, updates_per_step=updates_per_step, pipeline=pipeline,
-                 learn_log=learn_log, grad_clip=grad_clip, curriculum=curriculum, randomize=randomize, device=env.device,
+                 learn_log=learn_log, grad_clip=grad_clip, curriculum=curriculum, randomize=randomize, task_curriculum=task_curriculum,
+                 device=env.device,
                  episode_log_detail=bool(episode_log) and episode_log_detail)
         # the options in the order their refusals fire: (name, its check, the resolved values the check takes); the first bad one raises
         for name, check, takes in (("labels", check_expert_labels, ("expert", "n_envs", "data_parallel", "force_dp", "demo_loss")),
@@ -178,7 +185,8 @@ class DDPGRollout(VectorStepper):
                                    ("curriculum", check_curriculum, ("data_parallel", "force_dp", "expert", "labels", "device",
                                                                      "episode_log_detail")),
                                    ("randomize", check_randomization, ("data_parallel", "force_dp", "curriculum", "expert", "labels",
-                                                                       "device", "episode_log_detail"))):
+                                                                       "device", "episode_log_detail")),
+                                   ("task_curriculum", check_task_curriculum, ("randomize", "data_parallel", "force_dp", "device"))):
             if c[name] is not None or name == "n_step":       # (n_step is no optional value)
                 c[name] = check(c[name], **{k: c[k] for k in takes})
             if name in _AGENT_OPTIONS:
@@ -201,7 +209,8 @@ class DDPGRollout(VectorStepper):
         super().__init__(env, batch_size=batch_size, replay_slots=replay_slots, seed=seed, alpha=alpha, beta=beta, tau=tau, gamma=gamma,
                          fc1_dims=fc1_dims, fc2_dims=fc2_dims, agent=agent, capturable=use_graph, policy_workgroups=policy_workgroups,
                          policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail,
-                         td3=self.td3, expert=expert, labels=labels, curriculum=c["curriculum"], randomize=c["randomize"])
+                         td3=self.td3, expert=expert, labels=labels, curriculum=c["curriculum"], randomize=c["randomize"],
+                         task_curriculum=c["task_curriculum"])
         self.batch_size = batch_size
         self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
         self.agent.demo_loss = self.demo_loss
@@ -524,6 +533,7 @@ class DDPGRollout(VectorStepper):
             self.advance()
             self.learn()
         self.curriculum_tick()
+        self.task_curriculum_tick()
 
     # -------------------------------------------------------------- many vector steps
     def invalidate_graphs(self):
@@ -699,7 +709,7 @@ class DDPGRollout(VectorStepper):
             self._check_handover()             # (a host-memory read; a give-up drops the graphs: captured again just below)
             G = self.graph_steps
             if G and self.ring.k >= self._warm_steps and (self._graphs_current() or self._try_capture()):
-                room = self.curriculum_room(k)        # (k without a curriculum; with one: up to its next update, which sits between replays)
+                room = self.curriculum_room(k)        # (k without a curriculum; with one, or a task curriculum: up to its next update, which sits between replays)
                 if self.dp and not self.dp_single_graph:
                     self._dp_step()
                     done = 1
@@ -715,6 +725,7 @@ class DDPGRollout(VectorStepper):
                 self.advance(done)
                 k -= done
                 self.curriculum_tick()
+                self.task_curriculum_tick()
             else:
                 self.step()
                 k -= 1
@@ -746,7 +757,7 @@ class DDPGRollout(VectorStepper):
                 sd["optim"]["critic_2"] = ag.critic_2.optimizer.state_dict()
                 sd["td3_updates"] = int(ag.td3_updates)
                 sd["td3_noise"] = ag.td3_noise_state()               # (the torch path's generator; the fused path's noise is counter-based)
-        return write_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, grad_clip=self.grad_clip)      # (expert, labels, curriculum, randomize: the stepper's)
+        return write_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, grad_clip=self.grad_clip)      # (expert, labels, curriculum, randomize, task_curriculum: the stepper's)
 
     def demo_stats(self):
         """FusedLearner.demo_stats of the last update: {"demo_rows", "applied", "bc_loss"}; with expert lanes the ring rows of those
@@ -768,7 +779,8 @@ class DDPGRollout(VectorStepper):
         if int(sd.get("n_step", 1)) != self.n_step:
             raise ValueError(f"the checkpoint was written with n_step = {int(sd.get('n_step', 1))}, this loop has n_step = {self.n_step}")
         compare_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, expert=self.expert,
-                        labels=self.labels, grad_clip=self.grad_clip, curriculum=self.curriculum, randomize=self.randomize)   # (before anything is written)
+                        labels=self.labels, grad_clip=self.grad_clip, curriculum=self.curriculum, randomize=self.randomize,
+                        task_curriculum=self.task_curriculum)   # (before anything is written)
         self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])

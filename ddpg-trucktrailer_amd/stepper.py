@@ -15,11 +15,12 @@ from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 
 
 class VectorStepper:
-    expert = labels = curriculum = randomize = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
+    expert = labels = curriculum = randomize = task_curriculum = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
 
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
-                 episode_log_detail=False, td3=None, expert=None, labels=None, curriculum=None, randomize=None):
+                 episode_log_detail=False, td3=None, expert=None, labels=None, curriculum=None, randomize=None,
+                 task_curriculum=None):
         """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold);
         td3: its TD3Config (Agent(td3=)), whose torch path draws its smoothing noise from a generator seeded with `seed`.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
@@ -36,7 +37,10 @@ class VectorStepper:
         owner of the stepper calls curriculum_tick() after every vector step it has advanced.
         randomize: None, or a randomize.EpisodeRandomization, turned on in the env here, before the first
         observation is taken, and followed by env.reset(seed) with this stepper's seed: every lane then runs a randomised episode 0,
-        and slot 0 of the ring holds its observation (columns 12-15: the drawn goal).  A reset the caller made before is replaced."""
+        and slot 0 of the ring holds its observation (columns 12-15: the drawn goal).  A reset the caller made before is replaced.
+        task_curriculum: None, or a task_curriculum.TaskCurriculum, which needs `randomize`: turned on in the
+        env after randomisation and before that reset, so episode 0's tasks are its draws (uniform over the cells: nothing is counted
+        yet); the owner of the stepper calls task_curriculum_tick() after every vector step it has advanced."""
         self.env, self.n, self.device, self.seed = env, env.n_envs, env.device, seed
         if episode_log:
             env.enable_episode_log(int(episode_log), detail=episode_log_detail)
@@ -52,6 +56,12 @@ class VectorStepper:
             self.randomize = check_randomization(randomize, curriculum=self.curriculum, expert=expert, labels=labels, device=env.device,
                                                  episode_log_detail=bool(episode_log) and episode_log_detail)
             env.enable_randomization(self.randomize)
+        self.task_curriculum = None
+        if task_curriculum is not None:
+            from ddpg_trucktrailer_amd.task_curriculum import check_task_curriculum
+            self.task_curriculum = check_task_curriculum(task_curriculum, randomize=self.randomize, device=env.device)
+            env.enable_task_curriculum(self.task_curriculum)
+        if self.randomize is not None:
             env.reset(seed=seed)
         # the order that decides the bits: the seed, the networks, the ring, the noise, the first observation (with randomize: of the
         # reset above -- enable, then reset(seed), then everything else, so that the ring starts on a randomised episode 0)
@@ -166,25 +176,32 @@ class VectorStepper:
     def curriculum_room(self, k):
         """How many of k further vector steps may run before the curriculum's next update is due (k without a curriculum): graph
         replays are cut there, so that the update sits between replays."""
-        if self.curriculum is None:
-            return k
-        return min(k, self.curriculum.every - self.vector_steps % self.curriculum.every)
+        for cur in (self.curriculum, self.task_curriculum):       # (the task curriculum's update likewise; the two are never on together)
+            if cur is not None:
+                k = min(k, cur.every - self.vector_steps % cur.every)
+        return k
 
     def curriculum_tick(self):
         """After advance(): the curriculum's update, on the env's stream, when the vector steps have reached a multiple of `every`."""
         if self.curriculum is not None and self.vector_steps % self.curriculum.every == 0:
             self.env.curriculum_update()
 
+    def task_curriculum_tick(self):
+        """After advance(): the task curriculum's update, likewise."""
+        if self.task_curriculum is not None and self.vector_steps % self.task_curriculum.every == 0:
+            self.env.task_curriculum_update()
+
     def graph_key(self):
         """What captured launches of this stepper bake in: env.graph_epoch (reset seed, per-env-goal mode, pose pool), the ring's
         side-buffer count, the actor's parameter storages (the policy's packed-image struct is keyed on them, fused.py), the
-        expert lanes' and the expert labels' configurations (their numbers are kernel arguments) and the episode randomisation
-        (its step kernels are others)."""
+        expert lanes' and the expert labels' configurations (their numbers are kernel arguments), the episode randomisation
+        and the task curriculum (their step kernels are others)."""
         return (getattr(self.env, "graph_epoch", 0), self.ring.side_epoch,
                 fused.packed_key_of(self.agent.actor) if self.fused_act else None,
                 self.expert.as_tuple() if self.expert is not None else None) + \
                ((self.labels.as_tuple(),) if self.labels is not None else ()) + \
-               ((self.randomize.as_tuple(),) if self.randomize is not None else ())
+               ((self.randomize.as_tuple(),) if self.randomize is not None else ()) + \
+               ((self.task_curriculum.as_tuple(),) if self.task_curriculum is not None else ())
 
     def drain_episodes(self):
         """The env's episode log since the last drain: records sorted by (end_step, lane), end_step = the vector step it ended in."""
@@ -200,7 +217,8 @@ class VectorStepper:
         vector_steps, nets (four networks, six with TD3), ring, ou and env (with the episode log's state when it is on).  The
         caller has synchronised."""
         ag = self.agent
-        ex = write_options({}, expert=self.expert, labels=self.labels, curriculum=self.curriculum, randomize=self.randomize)
+        ex = write_options({}, expert=self.expert, labels=self.labels, curriculum=self.curriculum, randomize=self.randomize,
+                           task_curriculum=self.task_curriculum)
         if self.expert is not None or self.labels is not None:      # (with labels expert_plan is the launch's whole plan [M + L, H])
             ex["expert_plan"] = self.expert_plan.detach().cpu().clone()
         return {**ex, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
@@ -217,7 +235,8 @@ class VectorStepper:
 
     def check_expert_state(self, sd):
         """ValueError when acting_state() `sd` was written with other expert lanes or labels than this stepper's (or with none)."""
-        compare_options(sd, expert=self.expert, labels=self.labels, curriculum=self.curriculum, randomize=self.randomize)
+        compare_options(sd, expert=self.expert, labels=self.labels, curriculum=self.curriculum, randomize=self.randomize,
+                        task_curriculum=self.task_curriculum)
 
     def load_acting_state(self, sd):
         """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are

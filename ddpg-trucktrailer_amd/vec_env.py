@@ -547,11 +547,83 @@ class TruckTrailerVecEnv:
             return None
         return EpisodeRandomization(goal=(tuple(out.goal_lo), tuple(out.goal_hi)), L2=(out.L2_lo, out.L2_hi))
 
+    # ------------------------------------------------------------------ task curriculum
+    @property
+    def task_curriculum(self):
+        """The task_curriculum.TaskCurriculum that is on, or None."""
+        return getattr(self, "_task_curriculum", None)
+
+    def enable_task_curriculum(self, cur, place=None):
+        """Turn on the task curriculum (include/ttenv.h: tt_env_set_task_curriculum; task_curriculum.TaskCurriculum), with episode
+        randomisation on: from the next reset on, every reset of a lane draws the episode's goal and trailer length by the weights
+        of the cells over randomisation's ranges, and every finished episode is counted in the cell its task was drawn in;
+        task_curriculum_update() turns the counts into weights.  A fresh one each call.  place: as enable_curriculum's.  Outside a
+        graph capture; captured step graphs are re-captured (graph_epoch)."""
+        from ddpg_trucktrailer_amd.task_curriculum import TaskCurriculum, check_task_curriculum
+        TaskCurriculum.expect("task_curriculum", cur)
+        check_task_curriculum(cur, randomize=self.randomization)
+        cur.check_ranges(self.randomization.resolved(self.params))
+        cfg = cur.c_struct()
+        arrays = None
+        if place is not None:
+            arrays = L.TTCurriculumArrays(*[place[k].data_ptr() for k in L.CURRICULUM_ARRAYS])
+        self._check(self.lib.tt_env_set_task_curriculum(self._h, C.byref(cfg), C.byref(arrays) if arrays is not None else None,
+                                                        self._stream()))
+        self._task_curriculum, self._task_place = cur, place        # (place is kept alive here: the library only borrows it)
+        self._task_out = self._curriculum_arrays(cur.cells)
+        self.graph_epoch += 1
+
+    def disable_task_curriculum(self):
+        """Turn the task curriculum off: resets draw the task uniformly again, with randomisation's own kernels (graphs are
+        re-captured)."""
+        if self.task_curriculum is not None:
+            self._check(self.lib.tt_env_set_task_curriculum(self._h, None, None, self._stream()))
+        self._task_curriculum = self._task_place = self._task_out = None
+        self.graph_epoch += 1
+
+    def _need_task_curriculum(self):
+        if self.task_curriculum is None:
+            raise RuntimeError("the task curriculum is off (enable_task_curriculum)")
+
+    def task_curriculum_update(self):
+        """The counts since the last update into the cells' success rates and draw weights: one small launch on this stream.
+        Capturable."""
+        self._need_task_curriculum()
+        self._check(self.lib.tt_env_task_curriculum_update(self._h, self._stream()))
+
+    def task_curriculum_state(self):
+        """The task curriculum's arrays as device tensors (fresh copies), as curriculum_state()'s, each shaped
+        [nl2, ngyaw, ngy, ngx], and "cell" [N] i32, the cell every lane's running episode's task was drawn in (-1: none)."""
+        self._need_task_curriculum()
+        o = self._task_out
+        arrays = L.TTCurriculumArrays(*[o[k].data_ptr() for k in L.CURRICULUM_ARRAYS])
+        self._check(self.lib.tt_env_task_curriculum_read(self._h, C.byref(arrays), self._stream()))
+        ngx, ngy, ngyaw, nl2 = self.task_curriculum.bins
+        return {k: (v.clone() if k == "cell" else v.clone().view(nl2, ngyaw, ngy, ngx)) for k, v in o.items()}
+
+    def load_task_curriculum_state(self, state):
+        """Write the arrays of `state` that are present (task_curriculum_state()'s names and dtypes; any shape of the right size):
+        a checkpoint's, or counters and weights a test plants.  A writer of q keeps cum its inclusive prefix sum."""
+        self._need_task_curriculum()
+        sizes = dict.fromkeys(L.CURRICULUM_ARRAYS, self.task_curriculum.cells)
+        sizes["cell"] = self.n_envs
+        held = {}
+        for k in L.CURRICULUM_ARRAYS:
+            if state.get(k) is None:
+                continue
+            t = torch.as_tensor(state[k]).to(device=self.device, dtype=self._task_out[k].dtype).contiguous().reshape(-1)
+            if t.numel() != sizes[k]:
+                raise ValueError(f"task_curriculum: {k} has {t.numel()} elements, expected {sizes[k]}")
+            held[k] = t
+        arrays = L.TTCurriculumArrays(*[held[k].data_ptr() if k in held else None for k in L.CURRICULUM_ARRAYS])
+        self._check(self.lib.tt_env_task_curriculum_write(self._h, C.byref(arrays), self._stream()))
+        torch.cuda.current_stream(self.device).synchronize()      # `held` are temporaries
+
     def state_dict(self):
         """Everything needed to resume this env batch (device blob copied to the host + host-side mode); with the episode
         log on, its state as well (running returns, counters, launch count, records not drained yet); with a curriculum on, its
         option and arrays under "curriculum"; with episode randomisation on, its option under "randomize" (the lanes' goals and
-        lengths are in the blob)."""
+        lengths are in the blob); with the task curriculum on, its option and arrays under "task_curriculum"."""
         nbytes = int(self.lib.tt_env_state_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         meta = (C.c_uint64 * 4)()
@@ -565,6 +637,9 @@ class TruckTrailerVecEnv:
                                 **{k: v.cpu() for k, v in self.curriculum_state().items()}}
         if self.randomization is not None:
             sd["randomize"] = list(self.randomization.as_tuple())
+        if self.task_curriculum is not None:
+            sd["task_curriculum"] = {"option": list(self.task_curriculum.as_tuple()),
+                                     **{k: v.cpu() for k, v in self.task_curriculum_state().items()}}
         return sd
 
     def load_state_dict(self, sd):
@@ -573,7 +648,16 @@ class TruckTrailerVecEnv:
             from ddpg_trucktrailer_amd.randomize import EpisodeRandomization
             rand = EpisodeRandomization.from_tuple(_tupled(sd["randomize"]))
             if self.randomization != rand:
+                if self.task_curriculum is not None:  # (its cells lie on the old ranges; the file's comes back below)
+                    self.disable_task_curriculum()
                 self.enable_randomization(rand)
+        if sd.get("task_curriculum") is not None:     # (after randomisation, before the blob, for the same reason)
+            from ddpg_trucktrailer_amd.options import _tupled
+            from ddpg_trucktrailer_amd.task_curriculum import TaskCurriculum
+            task = TaskCurriculum.from_tuple(_tupled(sd["task_curriculum"]["option"]))
+            if self.task_curriculum != task:
+                self.enable_task_curriculum(task)
+            self.load_task_curriculum_state(sd["task_curriculum"])
         blob = sd["blob"].to(self.device)
         meta = (C.c_uint64 * 4)(*sd["meta"])
         self.graph_epoch += 1              # reset seed and per-env-goal mode come back with the blob

@@ -381,6 +381,42 @@ typedef struct tt_randomization {
 int tt_env_set_randomization(tt_env *env, const tt_randomization *cfg /* NULL: off */, tt_stream_t stream);
 int tt_env_randomization(const tt_env *env, tt_randomization *out);
 
+/* Task curriculum: the task drawn by success.  On only while episode randomisation is on: a grid of
+ * bins = (ngx, ngy, ngyaw, nl2) cells over its ranges of goal x, goal y, goal yaw and L2, C = ngx * ngy * ngyaw * nl2 in
+ * [1, TT_CURRICULUM_MAX_CELLS], cell c = ((il2 * ngyaw + igyaw) * ngy + igy) * ngx + igx, with the start-pose curriculum's state per
+ * cell (p, seen, attempts, successes, q, cum: tt_curriculum_arrays) and per lane cell u32 [npad], the cell the lane's running episode
+ * was drawn in, TT_CURRICULUM_NO_CELL when no task-curriculum draw made it.  While it is on, every reset of a lane draws
+ *     r = philox4x32(env, episode, 1, 0x7452, seed_lo, seed_hi)     the task's words, as plain randomisation's
+ *     s = philox4x32(env, episode, 2, 0x7452, seed_lo, seed_hi)     the cell pick
+ *     t = (s[0] * cum[C - 1]) >> 32;  c = the smallest cell with cum[c] > t
+ *     goal x = goal_lo[0] + (igx + u_0) * ((goal_hi[0] - goal_lo[0]) / ngx),  goal y and goal yaw likewise;  L2 from il2, u_3, nl2
+ * with u_k = (r[k] + 0.5) / 2^32, in f64, every operation rounded on its own (the cell widths are formed once, on the host), and
+ * writes the lane's cell.  The start pose keeps its words (third counter word 0; the box or the reset pool).  With bins (1, 1, 1, 1)
+ * the draw is plain randomisation's, bit for bit.  The lane is then placed as plain randomisation places it.  A lane that finishes an
+ * episode in an auto-resetting step adds 1 to attempts[cell] and, with final_success_bonus > 0, to successes[cell] before its next
+ * draw, as the start-pose curriculum counts; a lane with no cell counts nothing; tt_env_set_pose and tt_env_set_state set the lanes
+ * they touch to TT_CURRICULUM_NO_CELL.  Steps with auto_reset = 0 neither count nor draw.
+ * tt_env_task_curriculum_update (one small launch, capturable): tt_env_curriculum_update's rule on these arrays.
+ * tt_env_set_task_curriculum(env, cfg, place, stream): cfg NULL turns it off (step and reset are then plain randomisation's).  place
+ * as tt_env_set_curriculum's.  An allocation and a wait for `stream`: outside a graph capture.  Starts fresh.  TT_EINVAL with a
+ * message, before the handle is read: a bin count < 1 or C outside [1, TT_CURRICULUM_MAX_CELLS]; an unknown mode; alpha outside
+ * (0, 1]; uniform outside [0, 1] or not finite.  Reading the handle: episode randomisation not on; more than one bin on a range of
+ * width 0.  While it is on tt_env_set_randomization refuses (new ranges or NULL): "turn the task curriculum off first".  A reset
+ * pool may be set or cleared while it is on.  TT_VERSION and the state blob do not change: the arrays travel by
+ * tt_env_task_curriculum_read / _write, which are tt_env_curriculum_read / _write on these arrays.
+ * tt_env_task_curriculum(env, out): 1 if on (and *out, when not NULL, receives the option), 0 if off, TT_EINVAL for a NULL handle. */
+typedef struct tt_task_curriculum {
+    int32_t bins[4];    /* ngx, ngy, ngyaw, nl2 */
+    int32_t mode;
+    double alpha, uniform;
+} tt_task_curriculum;
+int tt_env_set_task_curriculum(tt_env *env, const tt_task_curriculum *cfg /* NULL: off */, const tt_curriculum_arrays *place,
+                               tt_stream_t stream);
+int tt_env_task_curriculum_update(tt_env *env, tt_stream_t stream);
+int tt_env_task_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt_stream_t stream);
+int tt_env_task_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream);
+int tt_env_task_curriculum(const tt_env *env, tt_task_curriculum *out);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */

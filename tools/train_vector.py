@@ -39,13 +39,18 @@ cells.  Composes with every learner option; not with the expert options or --obj
 EpisodeRandomization(goal=((X0, Y0, YAW0), (X1, Y1, YAW1)), L2=(LO, HI)))): every episode's trailer length and / or
 goal is drawn from the range at the lane's reset, inside the env step.  Each line adds the min / mean / max of the lanes' current L2 and
 goal.  Composes with every learner option; not with --curriculum, the expert options or --objectives.
+--task-curriculum NGX,NGY,NGYAW,NL2[,EVERY[,MODE]]: the task curriculum (DDPGRollout(task_curriculum=TaskCurriculum((NGX, NGY, NGYAW, NL2),
+every=EVERY, mode=MODE)); needs a --randomize-*; defaults EVERY = 64, MODE = frontier): the episode's goal and
+trailer length drawn by the success rate of the cell of the randomised ranges they lie in, counted and drawn inside the env step.  Each
+line adds the share of cells seen, the mean p, the weight share of the top decile of cells and the success rate per L2 bin; the other
+dimensions' tables follow on lines of their own.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
 Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [DELAY[,SIGMA[,CLIP]]]] [--huber D] [--pre-penalty C]
        [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M] [--label-lanes L] [--expert-horizon H] [--expert-samples S]
        [--expert-seed K] [--grad-clip C[,A]] [--curriculum NX,NY,NYAW[,EVERY[,MODE]]]
-       [--randomize-L2 LO,HI] [--randomize-goal X0,X1,Y0,Y1,YAW0,YAW1]
+       [--randomize-L2 LO,HI] [--randomize-goal X0,X1,Y0,Y1,YAW0,YAW1] [--task-curriculum NGX,NGY,NGYAW,NL2[,EVERY[,MODE]]]
        [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -148,6 +153,16 @@ if "--randomize-goal" in sys.argv[1:]:
 if rnd_goal is not None or rnd_L2 is not None:
     from ddpg_trucktrailer_amd.randomize import EpisodeRandomization, summary as randomize_summary
     randomize = EpisodeRandomization(goal=rnd_goal, L2=rnd_L2)
+task_curriculum = None
+if "--task-curriculum" in sys.argv[1:]:
+    from ddpg_trucktrailer_amd.task_curriculum import TaskCurriculum, task_summary
+    at = sys.argv.index("--task-curriculum")
+    parts = sys.argv[at + 1].split(",")
+    if randomize is None:
+        sys.exit("--task-curriculum needs --randomize-L2 LO,HI and / or --randomize-goal ...: there is no range to put cells on")
+    task_curriculum = TaskCurriculum(tuple(int(x) for x in parts[:4]), **({"every": int(parts[4])} if len(parts) > 4 else {}),
+                                     **({"mode": parts[5]} if len(parts) > 5 else {}))
+    del sys.argv[at:at + 2]
 loss_shape = None
 if huber is not None or pre_penalty:
     from ddpg_trucktrailer_amd.loss_shape import LossShape
@@ -183,7 +198,7 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
                    learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert, labels=labels,
-                   grad_clip=grad_clip, curriculum=curriculum, randomize=randomize)
+                   grad_clip=grad_clip, curriculum=curriculum, randomize=randomize, task_curriculum=task_curriculum)
 if demos is not None:
     from ddpg_trucktrailer_amd.expert import load_transitions_npz
     d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
@@ -193,7 +208,8 @@ print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn()
       (f", {loss_shape}" if loss_shape is not None else "") + (f", {grad_clip}" if grad_clip is not None else "") +
       (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else "") +
       (f", {expert}" if expert is not None else "") + (f", {labels}" if labels is not None else "") +
-      (f", {curriculum}" if curriculum is not None else "") + (f", {randomize}" if randomize is not None else ""), flush=True)
+      (f", {curriculum}" if curriculum is not None else "") + (f", {randomize}" if randomize is not None else "") +
+      (f", {task_curriculum}" if task_curriculum is not None else ""), flush=True)
 
 
 def learn_line(rec):
@@ -227,6 +243,17 @@ def randomize_line(st):
     spans = "  ".join(f"{k} {st[k][0]:.3f} / {st[k][1]:.3f} / {st[k][2]:.3f}" for k in ("L2", "goal_x", "goal_y", "goal_yaw"))
     return (f"  randomize: goal {st['goal_lo']} .. {st['goal_hi']}, L2 {st['L2_lo']} .. {st['L2_hi']}; lanes now (min / mean / max) "
             + spans)
+
+
+def _bins(table):
+    return " ".join(f"[{lo:.3g}, {hi:.3g}) {'-' if rate is None else f'{rate:.2f}'} ({seen})" for lo, hi, seen, rate in table)
+
+
+def task_line(st):
+    """The task curriculum's summary; the success rate per bin (episodes seen) of L2 on the line, of the goal's dimensions behind it."""
+    head = (f"  task curriculum: cells seen {100 * st['cells_seen']:5.1f} %, mean p {st['mean_p']:.3f}, top-decile weight "
+            f"{100 * st['top_decile_weight']:4.1f} %, success by L2: {_bins(st['by_L2'])}")
+    return head + "".join(f"\n    success by {k}: {_bins(st['by_' + k])}" for k in ("goal_x", "goal_y", "goal_yaw") if len(st["by_" + k]) > 1)
 
 
 def demo_line(st):
@@ -280,6 +307,7 @@ while s < total:
           f"{clip_line(loop.learner.clip_stats()) if grad_clip is not None else ''}"
           f"{curriculum_line(curriculum_summary(env.curriculum_state())) if curriculum is not None else ''}"
           f"{randomize_line(randomize_summary(env.randomization_ranges(), env.episode())) if randomize is not None else ''}"
+          f"{task_line(task_summary(env.task_curriculum_state(), env.randomization_ranges())) if task_curriculum is not None else ''}"
           f"{lanes_line(r, expert.lanes if expert is not None else 0, labels.lanes if labels is not None else 0) if expert is not None or labels is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
