@@ -183,6 +183,14 @@ class TTTaskCurriculum(C.Structure):
     _fields_ = [("bins", C.c_int32 * 4), ("mode", C.c_int32), ("alpha", C.c_double), ("uniform", C.c_double)]
 
 
+class TTHarvest(C.Structure):
+    """tt_harvest (include/ttenv.h: tt_ring_harvest): state int64 [8]; the region's obs, act, rew, obs2, done; capacity, tail;
+    step_base; work int32 [record_capacity]."""
+    _fields_ = [(n, C.c_void_p) for n in ("state", "obs", "act", "rew", "obs2", "done")] + \
+               [("capacity", C.c_int32), ("tail", C.c_int32), ("step_base", C.c_int64), ("work", C.c_void_p)]
+
+
+HARVEST_STATE = ("mark", "written_rows", "episodes", "rows_cut", "expired")     # words 0..4 of tt_harvest.state; 5..7 are zero
 CURRICULUM_MAX_CELLS = 4096             # TT_CURRICULUM_MAX_CELLS
 CURRICULUM_NO_CELL = 0xFFFFFFFF         # TT_CURRICULUM_NO_CELL
 CURRICULUM_MODES = ("frontier", "hard")  # TT_CURRICULUM_FRONTIER, TT_CURRICULUM_HARD
@@ -364,6 +372,8 @@ _SIGNATURES = {
     "tt_env_task_curriculum_read": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
     "tt_env_task_curriculum_write": (C.c_int, [_P, C.POINTER(TTCurriculumArrays), _P]),
     "tt_env_task_curriculum": (C.c_int, [_P, C.POINTER(TTTaskCurriculum)]),
+    "tt_ring_harvest": (C.c_int, [C.POINTER(TTHarvest), C.POINTER(TTRingView), _P, _P, _P, _P, _P, _P, C.c_int64, _P]),
+    "tt_env_harvest": (C.c_int, [_P, C.POINTER(TTHarvest), C.POINTER(TTRingView), _P, _P]),
 }
 EXPORTS = tuple(_SIGNATURES)
 

@@ -49,7 +49,7 @@ namespace {
 // The device side by concern.  ONE translation unit: the order of these includes, and of the two further
 // down, is the order that keeps every kernel's code -- the non-template kernels stay in the order k_reset .. k_random_actions
 // (pose), k_log_zero .. k_log_drain (log), k_hold_* (hold), k_reset_curriculum .. k_curriculum_update (curriculum), k_reset_rnd,
-// k_rnd_seed (randomize), k_reset_task (task), and the template kernels are instantiated in the order the host side below first names them.
+// k_rnd_seed (randomize), k_reset_task (task), k_harvest_plan, k_harvest_copy (harvest), and the template kernels are instantiated in the order the host side below first names them.
 #include "ttenv_math.h"        // KTable, tt_sincos*, tt_exp_neg, tt_atan2_readback, tt_wrap_pi, u01
 #include "ttenv_state.h"       // rows, pk_*, KParams, Bufs, Goal, Env, observe, store_obs_tile, load / store / place_env, draws
 #include "ttenv_step.h"        // StepOut, Info, step_env, write_info
@@ -292,6 +292,7 @@ __global__ __launch_bounds__(BLOCK) void k_rollout(const KParams P, const int n,
 #include "ttenv_curriculum.h"  // CurDev, k_step_cur, k_step_cur_log, k_reset_curriculum .. k_curriculum_update
 #include "ttenv_randomize.h"   // RndDev, randomized_task, k_step_rnd, k_step_rnd_log, k_reset_rnd, k_rnd_seed
 #include "ttenv_task.h"        // TaskDev, task_draw, k_step_task, k_step_task_log, k_reset_task
+#include "ttenv_harvest.h"     // HarvestK, HarvestRecs, k_harvest_plan, k_harvest_copy
 
 char g_err[tthost::ERR_BYTES] = "";
 
@@ -1469,6 +1470,62 @@ int tt_env_task_curriculum(const tt_env *env, tt_task_curriculum *out) {
     if (!env->task_dev) return 0;
     if (out) *out = env->task_cfg;
     return 1;
+}
+
+}  // extern "C"
+
+namespace {
+
+// the refusals and the two launches of a harvest (include/ttenv.h: tt_ring_harvest); `env` (may be NULL: the current device) takes
+// the message, and its device is made current behind the refusals
+int ring_harvest(tt_env *env, const char *who, const tt_harvest *h, const tt_ring_view *ring, const int64_t *k_dev,
+                 const HarvestRecs &rc, hipStream_t stream) {
+    if (!h || !ring || !k_dev) return fail_both(env, TT_EINVAL, "%s: h, ring and k_dev are required", who);
+    if (!h->state || !h->obs || !h->act || !h->rew || !h->obs2 || !h->done || !h->work)
+        return fail_both(env, TT_EINVAL, "%s: a NULL pointer in tt_harvest (state, obs, act, rew, obs2, done and work are required)", who);
+    if (!ring->obs || !ring->act || !ring->rew || !ring->done)
+        return fail_both(env, TT_EINVAL, "%s: a NULL pointer in the ring view (obs, act, rew and done are required)", who);
+    if (!rc.lane || !rc.end_step || !rc.len || !rc.success || !rc.written)
+        return fail_both(env, TT_EINVAL, "%s: a NULL record column (lane, end_step, len, success and written_dev are required)", who);
+    if (h->capacity < 1 || h->tail < 0)
+        return fail_both(env, TT_EINVAL, "%s: capacity = %d is below 1 or tail = %d is negative", who, h->capacity, h->tail);
+    if (rc.capacity < 1) return fail_both(env, TT_EINVAL, "%s: record_capacity = %lld is below 1", who, rc.capacity);
+    if (ring->slots < 3 || ring->n_envs < 1)
+        return fail_both(env, TT_EINVAL, "%s: a ring of %d slots and %d envs (slots >= 3 and n_envs >= 1 are required)", who, ring->slots,
+                         ring->n_envs);
+    if (rc.capacity * (long long)(ring->slots - 1) > 2147483647ll)
+        return fail_both(env, TT_EINVAL, "%s: record_capacity = %lld with %d slots: work[] holds 32-bit row counts", who, rc.capacity,
+                         ring->slots);
+    const HarvestK k{reinterpret_cast<long long *>(h->state), h->obs, h->act, h->rew, h->obs2, h->done, h->capacity, h->tail,
+                     (long long)h->step_base, h->work, ring->obs, ring->act, ring->rew, ring->done, ring->n_envs, ring->slots,
+                     reinterpret_cast<const long long *>(k_dev)};
+    const long long groups = (rc.capacity + BLOCK - 1) / BLOCK;
+    if (env) TT_HIP(env, hipSetDevice(env->device));
+    TT_LAUNCH(env, hipLaunchKernelGGL(k_harvest_plan, dim3((unsigned)groups), dim3(BLOCK), 0, stream, k, rc));
+    TT_LAUNCH(env, hipLaunchKernelGGL(k_harvest_copy, dim3((unsigned)(groups < 4096 ? groups : 4096)), dim3(BLOCK), 0, stream, k, rc));
+    return TT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int tt_ring_harvest(const tt_harvest *h, const tt_ring_view *ring, const int64_t *k_dev, const int32_t *lane, const int64_t *end_step,
+                    const int32_t *len, const uint8_t *success, const uint64_t *written_dev, int64_t record_capacity,
+                    tt_stream_t stream) {
+    const HarvestRecs rc{lane, reinterpret_cast<const long long *>(end_step), len, success,
+                         reinterpret_cast<const unsigned long long *>(written_dev), (long long)record_capacity};
+    return ring_harvest(nullptr, "tt_ring_harvest", h, ring, k_dev, rc, stream);
+}
+
+int tt_env_harvest(tt_env *env, const tt_harvest *h, const tt_ring_view *ring, const int64_t *k_dev, tt_stream_t stream) {
+    TT_HANDLE(env);
+    if (!env->log_bytes) return fail_both(env, TT_EINVAL, "tt_env_harvest: the episode log is off (tt_env_set_episode_log)");
+    if (ring && ring->n_envs != env->n)
+        return fail_both(env, TT_EINVAL, "tt_env_harvest: the ring view has %d envs, this handle %d", ring->n_envs, env->n);
+    const LogCols c = log_cols(env->log);
+    const HarvestRecs rc{c.lane, c.end_step, c.len, c.success, env->log.hdr + LG_WRITTEN, (long long)env->log.capacity};
+    return ring_harvest(env, "tt_env_harvest", h, ring, k_dev, rc, stream);
 }
 
 int tt_env_profile(tt_env *env, int max_launches) {

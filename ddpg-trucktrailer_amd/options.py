@@ -1,6 +1,6 @@
 """What the loops' options share: the base of the option values (td3.TD3Config, loss_shape.LossShape,
 demo_loss.DemoLoss, mpc.MPCConfig, mpc.ExpertLanes, mpc.ExpertLabels, grad_clip.GradClip, curriculum.Curriculum,
-randomize.EpisodeRandomization, task_curriculum.TaskCurriculum) with the validators
+randomize.EpisodeRandomization, task_curriculum.TaskCurriculum, success_replay.SuccessReplay) with the validators
 their constructors use, the one table of "not supported with" refusals behind the check_* functions, and the options' entries of a checkpoint.
 
     Option                        a value named by its FIELDS: repr, ==, hash, as_tuple(), from_tuple(); a nested Option nests
@@ -179,6 +179,27 @@ TABLE = {
                                   ("device", lambda c: c["device"] is not None and _device_type(c["device"]) != "cuda",
                                    lambda c: f"a task curriculum on device = {c['device']!r} is not supported: it exists only inside the HIP "
                                              "env step"))),
+    # success replay (success_replay.check_success_replay passes episode_log -- None or the log's capacity --, td3, n_step, expert,
+    # labels and device -- None: not known yet)
+    "success_replay": dict(what="success replay", be="is", population="a population's agents have rings of their own, and a harvest "
+                                                                     "per agent is not built",
+                           rows=(("episode_log", lambda c: not c["episode_log"],
+                                  "success replay without episode_log is not supported: the harvest reads the episode log's records "
+                                  "(DDPGRollout(episode_log=...))"),
+                                 ("td3", lambda c: c["td3"] is not None,
+                                  "success replay with td3 is not supported (the TD3 draw refuses side buffers)"),
+                                 ("n_step", lambda c: int(c["n_step"]) > 1,
+                                  lambda c: f"success replay with n_step = {int(c['n_step'])} is not supported: side tuples are single "
+                                            "steps, and the ring refuses them in an n-step draw"),
+                                 "population", "data_parallel", "force_dp",
+                                 ("expert", lambda c: c["expert"] is not None,
+                                  "success replay with expert lanes is not supported (the expert's lanes are demonstrations already, and "
+                                  "their successes would be harvested as the agent's)"),
+                                 ("labels", lambda c: c["labels"] is not None,
+                                  "success replay with expert labels is not supported (the side region's rows carry no label)"),
+                                 ("device", lambda c: c["device"] is not None and _device_type(c["device"]) != "cuda",
+                                  lambda c: f"success replay on device = {c['device']!r} is not supported: the harvest exists only as HIP "
+                                            "kernels"))),
 }
 
 
@@ -194,7 +215,7 @@ def refuse(option, value=None, **context):
 
 
 # ---- the options' entries of a checkpoint: each present option's as_tuple() as a list, under its key
-CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum", "task_curriculum", "randomize")
+CHECKPOINT_KEYS = ("td3", "loss_shape", "demo_loss", "expert", "labels", "grad_clip", "curriculum", "success_replay", "task_curriculum", "randomize")
 
 
 def write_options(sd, **options):

@@ -477,7 +477,7 @@ class PopulationRollout:
                  updates_per_step=1, graph_steps=4, episode_log=None, fc2_images=None, device="cuda:0", data_parallel=None,
                  pipeline=None, side_buffer=None, episode_log_detail=False, n_step=1, n_step_max=None, learn_log=None,
                  learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, grad_clip=None, curriculum=None, randomize=None,
-                 task_curriculum=None):
+                 task_curriculum=None, success_replay=None):
         from ddpg_trucktrailer_amd.vec_env import TruckTrailerVecEnv
         _refuse_lone_options(loss_shape, demo_loss, expert)
         if curriculum is not None:     # (a lone loop's option: curriculum.check_curriculum refuses a population)
@@ -489,6 +489,9 @@ class PopulationRollout:
         if task_curriculum is not None:    # (likewise: task_curriculum.check_task_curriculum; without `randomize` that row comes first)
             from ddpg_trucktrailer_amd.task_curriculum import check_task_curriculum
             check_task_curriculum(task_curriculum, randomize=randomize, population=True)
+        if success_replay is not None:     # (likewise: success_replay.check_success_replay)
+            from ddpg_trucktrailer_amd.success_replay import check_success_replay
+            check_success_replay(success_replay, episode_log=episode_log, population=True)
         grad_clip = check_population_grad_clip(grad_clip, len(seeds), td3=td3, data_parallel=bool(data_parallel), device=device)
         if td3 is not None:            # (before anything else: each refusal names its option)
             from ddpg_trucktrailer_amd.td3 import check_population_td3

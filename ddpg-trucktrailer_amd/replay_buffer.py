@@ -102,6 +102,9 @@ class TrajectoryRing:
         self.side = None
         self.side_count = 0
         self.side_epoch = 0
+        # success replay (enable_success_replay): the side rows [base, base + capacity) are the harvest's region,
+        # `state` its device words (L.HARVEST_STATE), `work` the plan launch's scratch; None: off
+        self.harvest = None
         self.n_step = 1              # > 1: the loop that owns the ring draws n-step tuples (DDPGRollout(n_step=...)): no side tuples
         # {t, t+1, t-1, t > 0}: ring slots of the running vector step, written on the device by the step's opening launch
         # (include/ttenv.h: tt_ring_view / tt_ring_cursor) so that captured launches need no per-position pointers
@@ -160,6 +163,9 @@ class TrajectoryRing:
         if self.n_step > 1:
             raise ValueError(f"side tuples in a ring that is drawn with n_step = {self.n_step} are not supported: they are single "
                              "steps, and their rows would need a discount of their own in the TD launch")
+        if self.harvest is not None:
+            raise ValueError("load_side after enable_success_replay is not supported: the harvest's region lies behind the rows "
+                             "loaded before it (load the demonstrations first)")
         f = dict(dtype=torch.float32, device=self.device)
         obs = torch.as_tensor(obs, **f).reshape(-1, self.obs.shape[2])
         k = obs.shape[0]
@@ -182,6 +188,63 @@ class TrajectoryRing:
         self.side_epoch += 1
         return k
 
+    # ---- success replay: the agent's own successful episodes, harvested into a region of the side buffer -------------------
+    def enable_success_replay(self, capacity):
+        """Give the side buffer a region of `capacity` rows for harvested transitions, behind the rows loaded
+        so far: the side arrays are allocated, or extended by `capacity` rows (new addresses: before anything is captured).  The
+        region starts empty; harvest() fills it on the device, first in first out, and expose_successes() moves side_count --
+        which the samplers take by value -- up to the rows it holds.  load_side is refused from here on."""
+        if self.harvest is not None:
+            raise ValueError("success replay is already enabled on this ring")
+        if self.n_step > 1:
+            raise ValueError(f"success replay in a ring that is drawn with n_step = {self.n_step} is not supported: side tuples are single steps")
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError(f"capacity = {capacity} is not a whole number >= 1")
+        f = dict(dtype=torch.float32, device=self.device)
+        d, base = self.obs.shape[2], int(self.side_count)
+        new = dict(obs=torch.zeros((base + capacity, d), **f), act=torch.zeros(base + capacity, **f), rew=torch.zeros(base + capacity, **f),
+                   obs2=torch.zeros((base + capacity, d), **f), done=torch.zeros(base + capacity, dtype=torch.uint8, device=self.device))
+        if self.side is not None:
+            for k, v in new.items():
+                v[:base] = self.side[k][:base]
+        self.side = new
+        self.side_epoch += 1
+        self.harvest = dict(base=base, capacity=capacity, state=torch.zeros(8, dtype=torch.int64, device=self.device), work=None)
+        self._harvest_host = torch.zeros(8, dtype=torch.int64)
+        if torch.device(self.device).type == "cuda":
+            self._harvest_host = self._harvest_host.pin_memory()
+        return self.harvest
+
+    def harvest_struct(self, record_capacity, tail=0, step_base=0):
+        """tt_harvest over the region (include/ttenv.h), with a work array for a log of `record_capacity` records; keeps what it
+        points at alive."""
+        hv, sd = self.harvest, self.side
+        if hv["work"] is None or hv["work"].numel() < int(record_capacity):
+            hv["work"] = torch.zeros(int(record_capacity), dtype=torch.int32, device=self.device)
+        a, d = hv["base"], self.obs.shape[2]
+        at = lambda t, width: t.data_ptr() + a * width * t.element_size()
+        return L.TTHarvest(hv["state"].data_ptr(), at(sd["obs"], d), at(sd["act"], 1), at(sd["rew"], 1), at(sd["obs2"], d),
+                           at(sd["done"], 1), hv["capacity"], int(tail), int(step_base), hv["work"].data_ptr())
+
+    def harvest_state_async(self):
+        """Queue a copy of the harvest's device words to pinned host memory on the current stream; read_harvest_state() after the
+        stream's next synchronize."""
+        self._harvest_host.copy_(self.harvest["state"], non_blocking=True)
+
+    def read_harvest_state(self):
+        return dict(zip(L.HARVEST_STATE, (int(x) for x in self._harvest_host[:len(L.HARVEST_STATE)].tolist())))
+
+    def expose_successes(self, written_rows):
+        """side_count = base + min(written_rows, capacity): the samplers draw the region's filled rows from the next launch on.  The
+        count moves only while the region fills, so holders of captured graphs (side_epoch) re-capture until then and never after."""
+        hv = self.harvest
+        count = hv["base"] + min(int(written_rows), hv["capacity"])
+        if count != self.side_count:
+            self.side_count = count
+            self.side_epoch += 1
+        return count - hv["base"]
+
     def _side_struct(self):
         if self.side is None or self.side_count == 0:
             return None
@@ -198,10 +261,19 @@ class TrajectoryRing:
                 sd["label"] = self.label.cpu()
             if self.side is not None:
                 sd["side"] = {k: v.cpu() for k, v in self.side.items()}
+        if self.harvest is not None:      # the region's base and size, the device words, and (side_count above) the exposed count
+            sd["harvest"] = {"base": int(self.harvest["base"]), "capacity": int(self.harvest["capacity"]),
+                             "state": self.harvest["state"].cpu(), "exposed": int(self.side_count) - int(self.harvest["base"])}
         return sd
 
     def load_state_dict(self, sd):
         assert (int(sd["slots"]), int(sd["n"])) == (self.slots, self.n), "replay ring geometry differs"
+        mine = (self.harvest["base"], self.harvest["capacity"]) if self.harvest is not None else None
+        theirs = (int(sd["harvest"]["base"]), int(sd["harvest"]["capacity"])) if "harvest" in sd else None
+        if mine != theirs:
+            raise ValueError(f"the ring's success-replay region (base, capacity) is {mine} and the checkpoint's ring has {theirs}")
+        if self.harvest is not None:
+            self.harvest["state"].copy_(sd["harvest"]["state"])
         if "obs" in sd:
             if (self.label is not None) != ("label" in sd):
                 raise ValueError("the ring's label array is " + ("enabled" if self.label is not None else "off") +

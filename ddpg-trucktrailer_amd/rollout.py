@@ -95,7 +95,7 @@ class DDPGRollout(VectorStepper):
                  updates_per_step=1, data_parallel=None, pipeline=None, policy_workgroups=192, graph_collectives=None,
                  policy_capped_grids=4, dp_exchange=None, episode_log=None, episode_log_detail=False, n_step=1, learn_log=None,
                  learn_log_every=1, td3=None, loss_shape=None, demo_loss=None, expert=None, labels=None, grad_clip=None,
-                 curriculum=None, randomize=None, task_curriculum=None):
+                 curriculum=None, randomize=None, task_curriculum=None, success_replay=None):
         """updates_per_step: learn() calls per vector step (the reference does one per ENV step, trainv2.py:520-528; one
         per vector step is 1/N of that -- the knob moves the data/update ratio back towards the reference's).
         data_parallel: None = (world_size > 1); True forces the data-parallel launch structure with the process group's
@@ -162,17 +162,25 @@ class DDPGRollout(VectorStepper):
         episode's task by the success counted per cell of a grid over randomisation's ranges, inside the env step; its update is
         launched behind every `every`-th vector step, between graph replays, as the curriculum's.  It is the env's: what composes with
         `randomize` composes with it.  task_curriculum.check_task_curriculum names what is refused (no `randomize`, data-parallel
-        ranks, the p2p exchange, TT_FORCE_DP, an env that is not on a GPU)."""
+        ranks, the p2p exchange, TT_FORCE_DP, an env that is not on a GPU).
+        success_replay: None, or a success_replay.SuccessReplay, with `episode_log`: after every `every`-th vector
+        step, between graph replays, the transitions of the episodes that ended in success are copied from the ring into a region of
+        its side buffer, first in first out; they are drawn with the ring's transitions, and with demo_loss they are demonstration
+        rows behind the Q-filter.  The region's rows enter the draw when drain_episodes() or success_replay_stats() exposes them.
+        Nothing is added to a captured step, and graphs, eager steps and a resumed run agree bit for bit.
+        success_replay.check_success_replay names what is refused (no episode_log, td3, n_step > 1, data-parallel ranks, the p2p
+        exchange, TT_FORCE_DP, expert lanes, expert labels, an env that is not on a GPU)."""
         from ddpg_trucktrailer_amd.curriculum import check_curriculum
         from ddpg_trucktrailer_amd.task_curriculum import check_task_curriculum
         from ddpg_trucktrailer_amd.randomize import check_randomization
+        from ddpg_trucktrailer_amd.success_replay import check_success_replay
         from ddpg_trucktrailer_amd.td3 import check_td3          # (here: td3.py imports this module)
         ranks = (world_size > 1) if data_parallel is None else bool(data_parallel)
         force_dp = os.environ.get("TT_FORCE_DP") == "1"
         c = dict(labels=labels, expert=expert, n_step=n_step, demo_loss=demo_loss, loss_shape=loss_shape, td3=td3, n_envs=env.n_envs,
                  data_parallel=ranks or dp_exchange == "p2p", force_dp=force_dp, updates_per_step=updates_per_step, pipeline=pipeline,
                  learn_log=learn_log, grad_clip=grad_clip, curriculum=curriculum, randomize=randomize, task_curriculum=task_curriculum,
-                 device=env.device,
+                 success_replay=success_replay, episode_log=episode_log, device=env.device,
                  episode_log_detail=bool(episode_log) and episode_log_detail)
         # the options in the order their refusals fire: (name, its check, the resolved values the check takes); the first bad one raises
         for name, check, takes in (("labels", check_expert_labels, ("expert", "n_envs", "data_parallel", "force_dp", "demo_loss")),
@@ -186,7 +194,9 @@ class DDPGRollout(VectorStepper):
                                                                      "episode_log_detail")),
                                    ("randomize", check_randomization, ("data_parallel", "force_dp", "curriculum", "expert", "labels",
                                                                        "device", "episode_log_detail")),
-                                   ("task_curriculum", check_task_curriculum, ("randomize", "data_parallel", "force_dp", "device"))):
+                                   ("task_curriculum", check_task_curriculum, ("randomize", "data_parallel", "force_dp", "device")),
+                                   ("success_replay", check_success_replay, ("episode_log", "td3", "n_step", "data_parallel", "force_dp",
+                                                                             "expert", "labels", "device"))):
             if c[name] is not None or name == "n_step":       # (n_step is no optional value)
                 c[name] = check(c[name], **{k: c[k] for k in takes})
             if name in _AGENT_OPTIONS:
@@ -210,7 +220,7 @@ class DDPGRollout(VectorStepper):
                          fc1_dims=fc1_dims, fc2_dims=fc2_dims, agent=agent, capturable=use_graph, policy_workgroups=policy_workgroups,
                          policy_capped_grids=policy_capped_grids, episode_log=episode_log, episode_log_detail=episode_log_detail,
                          td3=self.td3, expert=expert, labels=labels, curriculum=c["curriculum"], randomize=c["randomize"],
-                         task_curriculum=c["task_curriculum"])
+                         task_curriculum=c["task_curriculum"], success_replay=c["success_replay"])
         self.batch_size = batch_size
         self.agent.loss_shape = self.loss_shape            # (the torch path of learn(): Agent.learn_batch)
         self.agent.demo_loss = self.demo_loss
@@ -534,6 +544,7 @@ class DDPGRollout(VectorStepper):
             self.learn()
         self.curriculum_tick()
         self.task_curriculum_tick()
+        self.success_replay_tick()
 
     # -------------------------------------------------------------- many vector steps
     def invalidate_graphs(self):
@@ -726,6 +737,8 @@ class DDPGRollout(VectorStepper):
                 k -= done
                 self.curriculum_tick()
                 self.task_curriculum_tick()
+                # (the replay's two chains joined at its end, on this stream: the harvest follows every launch of both)
+                self.success_replay_tick()
             else:
                 self.step()
                 k -= 1
@@ -780,7 +793,7 @@ class DDPGRollout(VectorStepper):
             raise ValueError(f"the checkpoint was written with n_step = {int(sd.get('n_step', 1))}, this loop has n_step = {self.n_step}")
         compare_options(sd, td3=self.td3, loss_shape=self.loss_shape, demo_loss=self.demo_loss, expert=self.expert,
                         labels=self.labels, grad_clip=self.grad_clip, curriculum=self.curriculum, randomize=self.randomize,
-                        task_curriculum=self.task_curriculum)   # (before anything is written)
+                        task_curriculum=self.task_curriculum, success_replay=self.success_replay)   # (before anything is written)
         self.load_nets(sd["nets"])                                    # in place: captured graphs keep the addresses
         if self.learner is not None and "fused_adam" in sd:
             self.learner.load_state_dict(sd["fused_adam"])

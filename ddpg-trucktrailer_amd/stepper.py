@@ -15,12 +15,12 @@ from ddpg_trucktrailer_amd.replay_buffer import TrajectoryRing
 
 
 class VectorStepper:
-    expert = labels = curriculum = randomize = task_curriculum = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
+    expert = labels = curriculum = randomize = task_curriculum = success_replay = None         # (what __init__ sets; on the class so that a stepper made without it, as tests make them, has both)
 
     def __init__(self, env, batch_size=256, replay_slots=64, seed=27, alpha=1e-4, beta=1e-3, tau=1e-3, gamma=0.99, fc1_dims=400,
                  fc2_dims=300, agent=None, capturable=True, policy_workgroups=192, policy_capped_grids=4, episode_log=None,
                  episode_log_detail=False, td3=None, expert=None, labels=None, curriculum=None, randomize=None,
-                 task_curriculum=None):
+                 task_curriculum=None, success_replay=None):
         """agent: made here from alpha .. batch_size when none is passed (capturable: torch optimizers that a graph may hold);
         td3: its TD3Config (Agent(td3=)), whose torch path draws its smoothing noise from a generator seeded with `seed`.
         episode_log: None, or the capacity of the env's episode log (TruckTrailerVecEnv.enable_episode_log), turned on here,
@@ -40,7 +40,10 @@ class VectorStepper:
         and slot 0 of the ring holds its observation (columns 12-15: the drawn goal).  A reset the caller made before is replaced.
         task_curriculum: None, or a task_curriculum.TaskCurriculum, which needs `randomize`: turned on in the
         env after randomisation and before that reset, so episode 0's tasks are its draws (uniform over the cells: nothing is counted
-        yet); the owner of the stepper calls task_curriculum_tick() after every vector step it has advanced."""
+        yet); the owner of the stepper calls task_curriculum_tick() after every vector step it has advanced.
+        success_replay: None, or a success_replay.SuccessReplay, which needs `episode_log`: the ring's side buffer
+        gets a region of its own (TrajectoryRing.enable_success_replay, before anything is captured), and the owner of the stepper
+        calls success_replay_tick() after every vector step it has advanced -- the harvest of the successful episodes the log names."""
         self.env, self.n, self.device, self.seed = env, env.n_envs, env.device, seed
         if episode_log:
             env.enable_episode_log(int(episode_log), detail=episode_log_detail)
@@ -75,6 +78,12 @@ class VectorStepper:
         self.ring = TrajectoryRing(self.n, replay_slots, env.observation_dim, self.device)
         if self.device.type == "cuda":
             self.ring.attach(env)                          # the step kernel advances the ring's device counter
+        self.success_replay = None
+        if success_replay is not None:
+            from ddpg_trucktrailer_amd.success_replay import check_success_replay
+            self.success_replay = check_success_replay(success_replay, episode_log=episode_log, td3=td3, expert=expert, labels=labels,
+                                                       device=env.device)
+            self.ring.enable_success_replay(self.success_replay.capacity)
         self.noise = VecOUNoise(self.n, self.device)
         self.high = float(np.float32(math.pi / 4))       # env.action_space.high (f32 pi/4, simv2.py:86-91)
         self.scaled = torch.zeros(self.n, dtype=torch.float32, device=self.device)
@@ -176,7 +185,7 @@ class VectorStepper:
     def curriculum_room(self, k):
         """How many of k further vector steps may run before the curriculum's next update is due (k without a curriculum): graph
         replays are cut there, so that the update sits between replays."""
-        for cur in (self.curriculum, self.task_curriculum):       # (the task curriculum's update likewise; the two are never on together)
+        for cur in (self.curriculum, self.task_curriculum, self.success_replay):       # (the task curriculum's update likewise, and success replay's harvest)
             if cur is not None:
                 k = min(k, cur.every - self.vector_steps % cur.every)
         return k
@@ -190,6 +199,39 @@ class VectorStepper:
         """After advance(): the task curriculum's update, likewise."""
         if self.task_curriculum is not None and self.vector_steps % self.task_curriculum.every == 0:
             self.env.task_curriculum_update()
+
+    def harvest(self):
+        """One harvest (success_replay), on the current stream: the log's records since the harvest's mark, the ring as it stands.
+        The log's launch 0 is ring step 0: the stepper enables the log before its first step, and a checkpoint carries both counts."""
+        sr = self.success_replay
+        self.env.harvest(self.ring.harvest_struct(self.env.episode_log_capacity, tail=sr.tail), self.ring.view(), self.ring.k_dev)
+
+    def success_replay_tick(self):
+        """After advance(), between graph replays: the harvest, when the vector steps have reached a multiple of `every`.  No launch
+        of the step or the learn chain is in flight there (rollout.py: run)."""
+        if self.success_replay is not None and self.vector_steps % self.success_replay.every == 0:
+            self.harvest()
+
+    def success_replay_stats(self):
+        """{"episodes", "rows", "rows_cut", "expired", "exposed"} of the harvests so far; also moves the side buffer's count up to the
+        region's filled rows ("exposed"; captured graphs are captured again while it moves).  Synchronises."""
+        if self.success_replay is None:
+            raise ValueError("success replay is off (DDPGRollout(success_replay=...))")
+        self.ring.harvest_state_async()
+        torch.cuda.current_stream(self.device).synchronize()
+        return self._exposed()
+
+    def _exposed(self):
+        st = self.ring.read_harvest_state()
+        return {"episodes": st["episodes"], "rows": st["written_rows"], "rows_cut": st["rows_cut"], "expired": st["expired"],
+                "exposed": self.ring.expose_successes(st["written_rows"])}
+
+    def export_successes(self, path):
+        """The region's exposed rows as a demonstration file for another run (expert.save_transitions_npz).  Synchronises."""
+        from ddpg_trucktrailer_amd.expert import save_transitions_npz
+        n, a = self.success_replay_stats()["exposed"], self.ring.harvest["base"]
+        sd = self.ring.side
+        return save_transitions_npz(path, *(sd[k][a:a + n].cpu().numpy() for k in ("obs", "act", "rew", "obs2", "done")))
 
     def graph_key(self):
         """What captured launches of this stepper bake in: env.graph_epoch (reset seed, per-env-goal mode, pose pool), the ring's
@@ -205,7 +247,16 @@ class VectorStepper:
 
     def drain_episodes(self):
         """The env's episode log since the last drain: records sorted by (end_step, lane), end_step = the vector step it ended in."""
-        return self.env.drain_episodes()
+        if self.success_replay is None:
+            return self.env.drain_episodes()
+        # harvest what the log still holds, drain (which empties the log: the mark goes back to 0), and expose the region's rows --
+        # the harvest's words travel to the host behind the harvest and are read after the drain's own synchronize
+        self.harvest()
+        self.ring.harvest_state_async()
+        out = self.env.drain_episodes()
+        self.ring.harvest["state"][0] = 0
+        self._exposed()
+        return out
 
     # -------------------------------------------------------------- the stepper's part of a checkpoint
     def net_names(self):
@@ -218,7 +269,7 @@ class VectorStepper:
         caller has synchronised."""
         ag = self.agent
         ex = write_options({}, expert=self.expert, labels=self.labels, curriculum=self.curriculum, randomize=self.randomize,
-                           task_curriculum=self.task_curriculum)
+                           task_curriculum=self.task_curriculum, success_replay=self.success_replay)
         if self.expert is not None or self.labels is not None:      # (with labels expert_plan is the launch's whole plan [M + L, H])
             ex["expert_plan"] = self.expert_plan.detach().cpu().clone()
         return {**ex, "seed": int(self.seed), "vector_steps": int(self.vector_steps),
@@ -236,7 +287,7 @@ class VectorStepper:
     def check_expert_state(self, sd):
         """ValueError when acting_state() `sd` was written with other expert lanes or labels than this stepper's (or with none)."""
         compare_options(sd, expert=self.expert, labels=self.labels, curriculum=self.curriculum, randomize=self.randomize,
-                        task_curriculum=self.task_curriculum)
+                        task_curriculum=self.task_curriculum, success_replay=self.success_replay)
 
     def load_acting_state(self, sd):
         """Ring, OU state and env of acting_state(), in the lone loop's order (the env's load bumps env.graph_epoch: graphs are

@@ -410,6 +410,12 @@ class TruckTrailerVecEnv:
         out["written"], out["dropped"] = written, written - m
         return out
 
+    def harvest(self, h, ring_view, k_dev):
+        """The successful episodes the log names since the harvest's mark, copied from the ring into the side buffer's region
+        (include/ttenv.h: tt_env_harvest): h a tt_harvest (TrajectoryRing.harvest_struct), k_dev the ring's
+        device step count.  Two launches on the current stream, while no step launch is in flight; the log is left untouched."""
+        self._check(self.lib.tt_env_harvest(self._h, C.byref(h), C.byref(ring_view), L.ptr(k_dev), self._stream()))
+
     def _episode_log_state(self):
         nbytes = int(self.lib.tt_env_episode_log_bytes(self._h))
         blob = torch.empty(nbytes, dtype=torch.uint8, device=self.device)

@@ -417,6 +417,42 @@ int tt_env_task_curriculum_read(tt_env *env, const tt_curriculum_arrays *out, tt
 int tt_env_task_curriculum_write(tt_env *env, const tt_curriculum_arrays *in, tt_stream_t stream);
 int tt_env_task_curriculum(const tt_env *env, tt_task_curriculum *out);
 
+/* Success replay (csrc/ttenv_harvest.h): the transitions of the successful episodes the episode log names
+ * are copied from the trajectory ring into a region of the ring's side buffer (tt_side_buffer) before the ring overwrites them.
+ * A harvest runs while no step and no learn() launch is in flight.  With k = *k_dev (vector steps completed) and
+ * W = min(k, slots - 1) (intact transitions per lane), it looks at the records [mark, m), m = min(*written_dev, record_capacity);
+ * s = end_step + step_base is the absolute ring step of a record's done transition:
+ *   - a record with success != 0 and s >= k - W is eligible; one with success != 0 and s < k - W is expired (counted).  A record
+ *     that cannot be one of this ring's (lane outside [0, n_envs), len < 1, s >= k) is neither;
+ *   - want = len (tail == 0) or min(len, tail); first = max(s - want + 1, k - W); rows = s - first + 1; want - rows joins rows_cut;
+ *   - eligible records are taken in ascending (s, lane) order (pairs are unique in a log), each episode's rows oldest first; R is
+ *     the sum of rows.  Row r of the harvest has the global number g = written_rows + r, is stored iff r >= R - capacity, and goes
+ *     to row g % capacity of the region: a bit copy of the ring's transition (t = j % slots, lane) of absolute step j -- obs, act,
+ *     rew, done of slot t and obs2 = obs of slot (j + 1) % slots;
+ *   - then written_rows += R, episodes += the eligible records, mark = m.
+ * state is int64 [8] in device memory: {mark, written_rows, episodes, rows_cut, expired, 0, 0, 0}; word 7 counts the plan
+ * launch's workgroups while it runs and is 0 again when it ends.  Two launches on `stream`, no allocation, wait or host read, all
+ * counts read on the device, integer arithmetic only: a plan launch (each record's rows from its first one to the harvest's end
+ * into work[], by counting against every other record of the window through LDS tiles -- (m - mark)^2 / 256 tile passes of 256
+ * compares; its last workgroup moves the state on) and a copy launch (one wave per eligible record at a time; lanes 0..22 move
+ * obs, 32..54 obs2, 63 the scalars).  tt_ring_harvest takes the record columns from anywhere; tt_env_harvest reads the env's own
+ * episode log in place and leaves it untouched (tt_env_drain_episode_log is unaffected).  ring->cursor is not read.
+ * TT_EINVAL with a message that names the entry point, before any HIP call: a NULL pointer; capacity < 1 or tail < 0;
+ * record_capacity < 1 or record_capacity * (slots - 1) past 2^31 - 1 (work[] holds 32-bit row counts); slots < 3 or n_envs < 1; for
+ * tt_env_harvest a ring view of another number of envs, or an episode log that is off. */
+typedef struct tt_harvest {
+    int64_t *state;                 /* [8] device */
+    float *obs, *act, *rew, *obs2;  /* the region's rows [0, capacity): obs / obs2 [capacity, 23], act / rew [capacity] */
+    uint8_t *done;                  /* [capacity] */
+    int32_t capacity, tail;
+    int64_t step_base;              /* ring step of the log's launch 0 */
+    int32_t *work;                  /* [record_capacity] scratch */
+} tt_harvest;
+int tt_ring_harvest(const tt_harvest *h, const tt_ring_view *ring, const int64_t *k_dev, const int32_t *lane, const int64_t *end_step,
+                    const int32_t *len, const uint8_t *success, const uint64_t *written_dev, int64_t record_capacity,
+                    tt_stream_t stream);
+int tt_env_harvest(tt_env *env, const tt_harvest *h, const tt_ring_view *ring, const int64_t *k_dev, tt_stream_t stream);
+
 /* K vector steps of the random policy in ONE launch (SURVEY.md §8d iii): each env stays in registers for
  * k_steps steps with in-kernel auto-reset; only the last observation is stored.  obs_out [N,23], reward_sum [N]
  * f32 (sum of the k_steps rewards) and episodes_done [N] i32 may each be NULL. */

@@ -1,5 +1,5 @@
 """What the option-cost tools share (grad_clip_cost.py, loss_shape_cost.py, demo_cost.py, expert_lanes_cost.py, expert_labels_cost.py,
-curriculum_cost.py, randomize_cost.py and task_curriculum_cost.py, which set N and UPD from their own arguments): the configuration, a leg, the fresh child process per leg, the alternation of the variants and the report with
+curriculum_cost.py, randomize_cost.py, task_curriculum_cost.py and success_replay_cost.py, which set N and UPD from their own arguments): the configuration, a leg, the fresh child process per leg, the alternation of the variants and the report with
 the gate of DESIGN.md section 13 -- the loop without the option costs at most the parent's median plus the parent legs' own
 max - min.  A tool keeps its arguments and how it forwards them to a leg, the keyword arguments of its loops and its variants' names."""
 import argparse

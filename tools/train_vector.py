@@ -44,6 +44,13 @@ every=EVERY, mode=MODE)); needs a --randomize-*; defaults 
 trailer length drawn by the success rate of the cell of the randomised ranges they lie in, counted and drawn inside the env step.  Each
 line adds the share of cells seen, the mean p, the weight share of the top decile of cells and the success rate per L2 bin; the other
 dimensions' tables follow on lines of their own.
+--success-replay CAP[,EVERY[,TAIL]]: success replay (DDPGRollout(success_replay=SuccessReplay(CAP, every=EVERY, tail=TAIL)); DESIGN.md
+section 41; defaults EVERY = 32, TAIL = 0 = whole episodes): every EVERY vector steps the transitions of the episodes that ended in
+success are copied from the ring into a region of CAP rows of its side buffer; they are drawn with the ring's transitions and, with
+--bc-weight L (no --demos needed), cloned behind the Q-filter.  Each line adds the episodes and rows harvested,
+the rows in the draw, the rows cut off episodes longer than the ring's window and the episodes that expired before a harvest.  Not with
+--td3, --n-step > 1, the expert options or --demos (the loop makes the region when it makes the ring, and a file's rows go in front).
+--bc-weight L --no-demos runs the demonstration launches on an empty side buffer: the other run of a pair.
 --eval-every R --eval-lanes M: after every R-th report block a greedy evaluation of the actor (evaluation.Evaluator: no noise, M start
 poses drawn once from the seed), one summary line; the networks are saved (Agent.save_models) whenever an evaluation is the best so
 far by (success rate, mean return).
@@ -51,7 +58,7 @@ Usage: train_vector.py [--objectives] [--n-step N] [--learn-log EVERY] [--td3 [D
        [--demos FILE.npz --bc-weight L [--no-q-filter]] [--expert-lanes M] [--label-lanes L] [--expert-horizon H] [--expert-samples S]
        [--expert-seed K] [--grad-clip C[,A]] [--curriculum NX,NY,NYAW[,EVERY[,MODE]]]
        [--randomize-L2 LO,HI] [--randomize-goal X0,X1,Y0,Y1,YAW0,YAW1] [--task-curriculum NGX,NGY,NGYAW,NL2[,EVERY[,MODE]]]
-       [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
+       [--success-replay CAP[,EVERY[,TAIL]]] [--no-demos] [--eval-every R --eval-lanes M] n_envs ring_slots updates_per_step batch vector_steps report_every [seed [graph_steps]]"""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from ddpg_trucktrailer_amd.checkpoint import BestModelTracker
@@ -94,6 +101,14 @@ if "--bc-weight" in sys.argv[1:]:
 if "--no-q-filter" in sys.argv[1:]:
     sys.argv.remove("--no-q-filter")
     q_filter = False
+success_replay = None
+if "--success-replay" in sys.argv[1:]:
+    from ddpg_trucktrailer_amd.success_replay import SuccessReplay, summary as success_replay_summary
+    at = sys.argv.index("--success-replay")
+    success_replay = SuccessReplay(*(int(x) for x in sys.argv[at + 1].split(",")))
+    del sys.argv[at:at + 2]
+    if demos is not None:
+        sys.exit("--success-replay with --demos is not supported by this tool: the loop makes the region with its ring")
 expert_opt = {}
 label_lanes = None
 if "--label-lanes" in sys.argv[1:]:
@@ -111,8 +126,12 @@ if label_lanes is not None and bc_weight is None:
     sys.exit("--label-lanes L needs --bc-weight L: labels without a learner that reads them do nothing")
 if demos is not None and bc_weight is None:
     sys.exit("--demos FILE.npz needs --bc-weight L")
-if bc_weight is not None and demos is None and not expert_opt and label_lanes is None:
-    sys.exit("--bc-weight L needs demonstrations: --demos FILE.npz, --expert-lanes M or --label-lanes L")
+no_demos = "--no-demos" in sys.argv[1:]      # the demonstration launches on an empty side buffer: the baseline of a --success-replay pair
+if no_demos:
+    sys.argv.remove("--no-demos")
+if bc_weight is not None and demos is None and not expert_opt and label_lanes is None and success_replay is None and not no_demos:
+    sys.exit("--bc-weight L needs demonstrations: --demos FILE.npz, --expert-lanes M, --label-lanes L or --success-replay CAP "
+             "(--no-demos: run its launches without any)")
 demo_loss = None
 if bc_weight is not None:
     from ddpg_trucktrailer_amd.demo_loss import DemoLoss
@@ -198,7 +217,8 @@ loop = DDPGRollout(env, batch_size=batch, replay_slots=slots, seed=seed, updates
                    # the log holds a report block's records: one per learn_every updates
                    learn_log=None if learn_every is None else min(max(1, upd * every // learn_every + 1), 1 << 22),
                    learn_log_every=learn_every or 1, td3=td3, loss_shape=loss_shape, demo_loss=demo_loss, expert=expert, labels=labels,
-                   grad_clip=grad_clip, curriculum=curriculum, randomize=randomize, task_curriculum=task_curriculum)
+                   grad_clip=grad_clip, curriculum=curriculum, randomize=randomize, task_curriculum=task_curriculum,
+                   success_replay=success_replay)
 if demos is not None:
     from ddpg_trucktrailer_amd.expert import load_transitions_npz
     d_obs, d_act, d_rew, d_obs2, d_done = load_transitions_npz(demos)
@@ -209,7 +229,8 @@ print(f"N = {n}, ring {slots} steps ({slots * n:.2e} transitions), {upd} learn()
       (f", {demo_loss} on {loop.ring.side_count} demonstrations" if demo_loss is not None else "") +
       (f", {expert}" if expert is not None else "") + (f", {labels}" if labels is not None else "") +
       (f", {curriculum}" if curriculum is not None else "") + (f", {randomize}" if randomize is not None else "") +
-      (f", {task_curriculum}" if task_curriculum is not None else ""), flush=True)
+      (f", {task_curriculum}" if task_curriculum is not None else "") +
+      (f", {success_replay}" if success_replay is not None else ""), flush=True)
 
 
 def learn_line(rec):
@@ -308,6 +329,7 @@ while s < total:
           f"{curriculum_line(curriculum_summary(env.curriculum_state())) if curriculum is not None else ''}"
           f"{randomize_line(randomize_summary(env.randomization_ranges(), env.episode())) if randomize is not None else ''}"
           f"{task_line(task_summary(env.task_curriculum_state(), env.randomization_ranges())) if task_curriculum is not None else ''}"
+          f"{'  ' + success_replay_summary(loop.success_replay_stats()) if success_replay is not None else ''}"
           f"{lanes_line(r, expert.lanes if expert is not None else 0, labels.lanes if labels is not None else 0) if expert is not None or labels is not None else ''}  "
           f"{time.time() - t0:.0f}s", flush=True)
     blocks += 1
